@@ -8,7 +8,18 @@ one batch of B=512 synthetic series per GPU, enqueued through libffd's
 metric is  value = N_gpus * B / (1000 * seconds_per_step)  -- the rate at which
 complete 1000-step samples leave the node (the prior draw and the final idft are two
 more launches per 1000 steps, < 0.01 % of the time).  With K = 1000 the
-timed region *is* one complete sampling of the batch.
+timed region *is* one complete sampling of the batch; K > 1000 goes on with further
+samplings of the same buffer from step 0.
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full
+adds every side measurement (per-kernel rooflines, CPU baselines, cache ratio, the
+split-FFN line, the reference harness regime, the other workloads, the API timing);
+--no-extras / --no-cpu-baseline / --no-other-workloads / --ablation refine it.
+
+--dump-outputs DIR writes what the timed steps computed (the samples x after step K,
+float32, as the caller of ffd_sample_batch receives them) to DIR/samples.npy
+(samples_rank<r>.npy per rank when N > 1); past 60 MiB a fixed seeded subset of the
+batch rows is kept.  Inputs are seeded, so equal arguments give equal inputs.
 
 Sampling is embarrassingly parallel over the batch: ranks are independent shards
 (weights replicated, Philox noise keyed by global sample index), no data-path
@@ -77,12 +88,18 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=512, help="samples per GPU")
     ap.add_argument("--workload", default="ecg", choices=sorted(WORKLOADS))
     ap.add_argument("--cache", action="store_true", help="time the E2-CRF cached path (BASELINE configs[2])")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (rooflines, CPU baselines, cache ratio, split-FFN line, harness "
+                         "regime, other workloads, API timing); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the samples the timed steps computed to DIR/samples.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip roofline / cache-ratio / harness side measurements")
     ap.add_argument("--no-other-workloads", action="store_true",
                     help="skip the compact lines for the other BASELINE configs and the API-level end-to-end timing")
     ap.add_argument("--ablation", action="store_true",
-                    help="also run the reference harness's ablation grid (cmd/benchmark_cache.py:274-422) at B=1")
+                    help="with --full: also run the reference harness's ablation grid (cmd/benchmark_cache.py:274-422) "
+                         "at B=1")
     ap.add_argument("--tune", action="append", default=[], help="key=value for ffd_tune (experiments)")
     ap.add_argument("--ffn-split", action="store_true",
                     help="run with the opt-in bf16x3-split FFN (fp32-equivalent, NOT the reference's fp32 arithmetic): "
@@ -92,7 +109,10 @@ def parse_args(argv=None):
                          "run over gloo (RCCL refuses two ranks on one device); the reported number is meaningless")
     ap.add_argument("--launch-plan", action="store_true",
                     help="print the rank plan the self-launcher would start (JSON) and exit; touches no GPU")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.ablation and not args.full:
+        ap.error("--ablation is one of the --full measurements: add --full")
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -206,6 +226,33 @@ def run_steps(model, X, ts_c, n_total, step_size, first, n_run, use_cache, strea
     rc = ctx.lib.ffd_sample_batch(ctx.handle, X.data_ptr(), X.shape[0], ts_c, n_total, step_size, first, n_run, 42,
                                   offset, None, int(use_cache), first if use_cache else 0, stream)
     N.check(rc, ctx.handle, "ffd_sample_batch")
+
+
+def run_samplings(model, X, ts_c, n_total, step_size, n, use_cache, stream, offset):
+    """n steps from step 0: one sampling of the batch for n <= n_total, further samplings of the same buffer after it
+    (a fresh cache for each, as in a new sampling)."""
+    done = 0
+    while done < n:
+        if done and use_cache:
+            model.cache.reset()
+        k = min(n - done, n_total)
+        run_steps(model, X, ts_c, n_total, step_size, 0, k, use_cache, stream, offset)
+        done += k
+
+
+DUMP_BYTES = 60 << 20  # --dump-outputs budget over all ranks
+
+
+def dump_outputs(out_dir, X, rank, world):
+    """The samples after the last timed step, float32; past the budget a fixed seeded subset of the batch rows."""
+    import numpy as np
+
+    x = X.detach().float().cpu().numpy()
+    rows = max(1, (DUMP_BYTES // world) // max(1, x[0].nbytes))
+    if rows < x.shape[0]:
+        x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], rows, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "samples.npy" if world == 1 else f"samples_rank{rank}.npy"), np.ascontiguousarray(x))
 
 
 def host_cores() -> int:
@@ -437,14 +484,14 @@ def main() -> None:
         torch.cuda.synchronize(device)
 
     K, W = args.steps, args.warmup
-    if K > n_total or K < 1:
-        raise SystemExit("--steps must be in [1, 1000] (1000 = one complete sampling)")
+    if K < 1:
+        raise SystemExit("--steps must be >= 1 (1000 = one complete sampling)")
     if use_cache:
         model.cache.reset()
     # warm-up: W untimed steps on a throw-away prior draw
     if W > 0:
         Xw = sampler.sample_prior(B, _sample_offset=offset)
-        run_steps(model, Xw, ts_c, n_total, step_size, 0, min(W, n_total), use_cache, stream, offset)
+        run_samplings(model, Xw, ts_c, n_total, step_size, W, use_cache, stream, offset)
     # timed region: the first K steps of a real sampling of a fresh batch (for the cached
     # path this includes the table-filling step 0, as in the reference's benchmark)
     if use_cache:
@@ -452,12 +499,14 @@ def main() -> None:
     X = sampler.sample_prior(B, _sample_offset=offset)
     barrier()
     t0 = time.perf_counter()
-    run_steps(model, X, ts_c, n_total, step_size, 0, K, use_cache, stream, offset)
+    run_samplings(model, X, ts_c, n_total, step_size, K, use_cache, stream, offset)
     barrier()
     own = time.perf_counter() - t0
     elapsed = reduce_max_seconds(own, comm_dev)
     per_rank = gather_seconds(own, comm_dev)
     assert torch.isfinite(X).all(), "non-finite samples"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, X, rank, world)
     ms_per_step = elapsed / K * 1e3
     value = world * B / (1000.0 * (elapsed / K))
 
@@ -473,7 +522,7 @@ def main() -> None:
         "ms_per_step_per_rank": [t / K * 1e3 for t in per_rank],
     }
 
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         ctx = model._ctx()
         lib = ctx.lib
         flops_step = lib.ffd_flops_per_sample_step(ctx.handle, 0) * B

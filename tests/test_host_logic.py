@@ -321,6 +321,27 @@ def test_bench_self_launcher_relays_rank0_and_fails_on_child_failure(tmp_path, m
         assert bench.self_launch(args, ["--gpus", "3"]) != 0
 
 
+def test_bench_full_option_and_dump_outputs(tmp_path):
+    """A plain bench run times the steps only (--full adds the side measurements, --ablation needs it); --dump-outputs
+    writes the samples as float32, a fixed seeded subset of batch rows past the size budget, one file per rank."""
+    import importlib
+
+    bench = importlib.import_module("bench")
+    assert not bench.parse_args([]).full and bench.parse_args(["--full", "--ablation"]).ablation
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--ablation"])
+    x = torch.arange(512 * 187, dtype=torch.float32).reshape(512, 187, 1)
+    bench.dump_outputs(str(tmp_path / "a"), x, 0, 1)
+    assert np.array_equal(np.load(tmp_path / "a" / "samples.npy"), x.numpy())
+    big = torch.randn(8192, 512, 8)
+    for r in range(2):
+        bench.dump_outputs(str(tmp_path / "b"), big, r, 2)
+    parts = [np.load(tmp_path / "b" / f"samples_rank{r}.npy") for r in range(2)]
+    assert sum(p.nbytes for p in parts) <= bench.DUMP_BYTES and parts[0].dtype == np.float32
+    assert np.array_equal(parts[0], parts[1]) and parts[0].shape[1:] == (512, 8)
+    assert any(np.array_equal(parts[0][0], big[i].numpy()) for i in range(big.shape[0]))
+
+
 def test_hydra_surface_targets_resolve_and_instantiate():
     """The north_star's "Hydra-config API surface": the reference pins it by composing and instantiating every
     cmd/conf/*.yaml (tests/test_hydra_configs.py:21-51).  hydra / omegaconf are not installed here, so the same

@@ -10,16 +10,16 @@ prof() {  # prof <name> <bench args...>: rocprofv3 --kernel-trace --stats of one
   cp $O/prof_$name/*/*kernel_stats.csv $O/${name}_kernel_stats.csv && rm -rf $O/prof_$name
 }
 rm -f $R/gpurun_out/traffic/r04_traffic.json
-python3 $R/bench.py --ablation > $O/bench_ecg_B512.json 2> $O/bench_ecg_B512.err
+python3 $R/bench.py --full --ablation > $O/bench_ecg_B512.json 2> $O/bench_ecg_B512.err
 echo "ecg done: $(python3 -c "import json; d=json.loads(open('$O/bench_ecg_B512.json').read().strip().splitlines()[-1]); print(d['value'], d['roofline']['frac'])")"
 prof ecg_B512
-python3 $R/bench.py --cache --no-cpu-baseline > $O/bench_ecg_B512_cache.json 2>/dev/null
-python3 $R/bench.py --workload syn512 --batch 8192 --cache --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_syn512_B8192_cache.json 2>/dev/null
-python3 $R/bench.py --workload syn512 --batch 2048 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_syn512_B2048.json 2>/dev/null
+python3 $R/bench.py --full --cache --no-cpu-baseline > $O/bench_ecg_B512_cache.json 2>/dev/null
+python3 $R/bench.py --full --workload syn512 --batch 8192 --cache --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_syn512_B8192_cache.json 2>/dev/null
+python3 $R/bench.py --full --workload syn512 --batch 2048 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_syn512_B2048.json 2>/dev/null
 prof syn512_B2048 --workload syn512 --batch 2048 --steps 3 --warmup 1
 echo "syn512 done"
-python3 $R/bench.py --workload nasa_lstm --batch 512 --steps 200 --warmup 10 > $O/bench_nasa_lstm_B512.json 2>/dev/null
-python3 $R/bench.py --workload nasa_lstm --batch 8192 --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_nasa_lstm_B8192.json 2>/dev/null
+python3 $R/bench.py --full --workload nasa_lstm --batch 512 --steps 200 --warmup 10 > $O/bench_nasa_lstm_B512.json 2>/dev/null
+python3 $R/bench.py --full --workload nasa_lstm --batch 8192 --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_nasa_lstm_B8192.json 2>/dev/null
 prof nasa_lstm_B512 --workload nasa_lstm --batch 512 --steps 20 --warmup 2
 prof nasa_lstm_B8192 --workload nasa_lstm --batch 8192 --steps 5 --warmup 1
 echo "lstm done"

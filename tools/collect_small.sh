@@ -12,5 +12,5 @@ bash tools/prof_small.sh r2_small/prof_b1_cache 1 300 cache > $O/b1_cache_kernel
 bash tools/prof_small.sh r2_small/prof_b8 8 300 > $O/b8_kernels.txt
 cp $O/prof_b1/*/*kernel_stats.csv $O/b1_kernel_stats.csv
 cp $O/prof_b1_cache/*/*kernel_stats.csv $O/b1_cache_kernel_stats.csv
-cd $R && python3 bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+cd $R && python3 bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
 tail -c 1500 $O/bench_default.json
