@@ -126,7 +126,11 @@ struct ffd_ctx {
       return ctx->fail(FFD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
   } while (0)
 
-static thread_local int g_fail_alloc_after = 0;  // tests: the n-th device allocation from now fails (ffd_tune "fail_alloc_after")
+namespace ffd {
+#define FFD_KNOB_DEF(key, var, def, ...) thread_local int var = def;
+FFD_KNOBS(FFD_KNOB_DEF, FFD_KNOB_DEF)
+#undef FFD_KNOB_DEF
+}  // namespace ffd
 
 static int dev_alloc(ffd_ctx* ctx, float** p, size_t nfloats) {
   *p = nullptr;
@@ -160,9 +164,6 @@ static int dev_regrow(ffd_ctx* ctx, float** p, size_t nfloats, CapT* cap, CapT c
   return rc;
 }
 static int dev_regrow(ffd_ctx* ctx, float** p, size_t nfloats) { return dev_regrow<int>(ctx, p, nfloats, nullptr, 0); }
-
-static thread_local int g_fuse_tail = 1;
-static thread_local int g_attn_kvq = 1;  // small-batch split attention on the kv | q pack (ffd_tune "attn_kvq")
 
 // HIP event pair around a launch of kernel class `cls` while ffd_kernel_timing_begin has its bit set
 struct Timed {
@@ -202,177 +203,110 @@ static bool hd_supported(int hd) {
   return false;
 }
 
+// ---------------------------------------------------------------------------
+// kernel plan: which forms run a layer at this batch (declared in ffd_internal.h)
+// ---------------------------------------------------------------------------
+namespace ffd {
+
+CacheMode cache_mode(int n_rec, int L) {
+  if (n_rec < 0) return CACHE_STD;
+  if (n_rec == L) return CACHE_FULL;
+  if ((double)n_rec > 0.8 * (double)L) return CACHE_STD;
+  return n_rec == 0 ? CACHE_PURE : CACHE_MIXED;
+}
+
+LayerPlan plan_layer(const ffd_model_desc& m, int B, CacheMode mode, const PackSet& pk) {
+  const int L = m.max_len, d = m.d_model, H = m.n_head, hd = d / H, F = m.dim_feedforward, M = B * L;
+  LayerPlan p{};
+  // attention: the fused in-projection + attention kernel where one exists; at small batches its split form (the kv | q
+  // pack where there is one and the step is not a pure cache hit), else one workgroup per head or head pair
+  p.attn = g_attn_fused && pk.aw_full ? ATTN_FUSED : ATTN_TWO_KERNEL;
+  p.hpw = 1;
+  p.q_only = mode == CACHE_PURE;
+  if (p.attn == ATTN_FUSED) {
+    p.kspl = qkv_attention_small_split(B, H, L);
+    if (pk.aw_full2 && !p.kspl) p.hpw = qkv_attention_hpw(d, hd, L);
+    if (g_attn_kvq && pk.aw_kvq && mode != CACHE_PURE && p.kspl) p.q_only = 2;
+  }
+  // FFN, in order of precedence: the opt-in bf16 split at every size; one 32- / 48-row k_ffn_ln tile per CU where the
+  // 16-row tiles are 1.4 - 3 per CU (ahead of the small-M pair unless small_wgs is set, of the sliced k_ffn_rows unless
+  // rows_slices is, and of the 64-row F slices unless mid_path forces them); the small-M F-split pair; the sliced
+  // k_ffn_rows; the 64-row F slices; k_ffn_rows (out-projection inside where fused); k_ffn_ln
+  const int hp = g_ffn_height && !g_ffn_split && !g_ffn_mb_override ? ffn_height_plan(M, d, F) : 0;
+  int unf = 0;
+  if (g_ffn_split) {
+    p.ffn = FFN_SPLIT;
+  } else if (hp && g_ffn_height == 1) {
+    p.ffn = FFN_LN_OPROJ, p.mb = hp;
+  } else if (!(hp && g_small_wgs == 0) && (p.ns = small_path_splits(M, d, F))) {
+    p.ffn = FFN_SMALL, p.part_floats = small_path_partial_floats(M, d, p.ns);
+  } else if (pk.ring && !(hp && g_rows_slices == 0) && rows_slice_plan(M, d, F, &p.nw, &p.nslice, &unf)) {
+    p.ffn = unf ? FFN_ROWS_SLICED : FFN_ROWS_SLICED_OPROJ, p.part_floats = rows_slice_floats(M, d, p.nslice);
+  } else if ((p.nm = hp && g_mid_path == 1 ? 0 : mid_path_splits(M, d, F))) {
+    p.ffn = FFN_MID, p.part_floats = small_path_partial_floats(cdiv(M, 64) * 64, d, p.nm);
+  } else if (pk.ring && ffn_rows_fused_selected(M, d, F)) {
+    p.ffn = FFN_ROWS_OPROJ;
+  } else if (pk.ring && ffn_rows_selected(M, d, F)) {
+    p.ffn = FFN_ROWS;
+  } else {
+    // k_ffn_ln tiles of 16 MB rows: MB = 4 (two workgroups resident per CU) once the grid fills the chip, smaller tiles
+    // for smaller M; ffn_height = 2 puts the 32- / 48-row tiles behind k_linear_res_ln
+    p.ffn = FFN_LN;
+    p.mb = g_ffn_mb_override >= 1 ? g_ffn_mb_override : cdiv(M, 64) >= 512 ? 4 : cdiv(M, 32) >= 512 ? 2 : 1;
+    if (hp) p.mb = hp;
+  }
+  p.oproj_separate = p.ffn >= FFN_ROWS_SLICED;
+  p.swap = p.ffn == FFN_ROWS_SLICED_OPROJ || p.ffn == FFN_ROWS_OPROJ;
+  return p;
+}
+
+LstmPlan plan_lstm(const ffd_model_desc& m, int B) {
+  // the layers as a wavefront (ffd_lstm.hip) in sub-batches of a 16-sample tile per CU; else the per-layer kernels
+  const int maxb = lstm_wave_max_batch(m.max_len, m.d_model);
+  if (g_lstm_wave && m.d_model % 4 == 0 && m.d_model >= 16 && m.num_layers <= 64 && maxb >= 16)
+    return {true, B < maxb ? B : maxb};
+  return {false, B};
+}
+
+}  // namespace ffd
+
 extern "C" {
 
 int ffd_tune(const char* key, int value) {
   if (!key) return FFD_ERR_INVALID;
   if (!strcmp(key, "reset")) {  // every knob back to its default (the test suite calls this after each test)
-    g_ffn_mb_override = 0, g_ffn_height = 1, g_ffn_persist = 1, g_ffn_rem = 1, g_ffn_split = 0, g_ffn_rows = 1, g_ffn_rows_nw = 0,
-    g_ffn_rows_cps = 0, g_ffn_rows_fuse = 1, g_rows_slices = 0, g_rows_slices_fuse = 0, g_mid_path = 1, g_small_path = 1, g_small_wgs = 0, g_attn_small = 1, g_attn_fused = 1,
-    g_attn_hpw = 0, g_attn_qg = 0, g_embed_ldsx = 1, g_embed_threads = 262144,
-    g_lstm_wave = 1, g_lstm_wave_persist = 1, g_lstm_wave_per = 0, g_lstm_wave_chunk = 0, g_fuse_tail = 1, g_attn_kvq = 1, g_fail_alloc_after = 0, g_lstm_wave_fault = 0, g_lstm_wave_spin_ms = 2000;
+#define FFD_KNOB_RESET(k, var, def, ...) var = def;
+    FFD_KNOBS(FFD_KNOB_RESET, FFD_KNOB_RESET)
+#undef FFD_KNOB_RESET
     return FFD_OK;
   }
-  if (!strcmp(key, "ffn_mb")) {
-    if (value < 0 || value > 4) return FFD_ERR_INVALID;
-    g_ffn_mb_override = value;
-    return FFD_OK;
+  const int v = value;
+#define FFD_KNOB_SET(k, var, def, ok) \
+  if (!strcmp(key, k)) {              \
+    if (!(ok)) return FFD_ERR_INVALID; \
+    var = v;                          \
+    return FFD_OK;                    \
   }
-  if (!strcmp(key, "ffn_height")) {  // 32- / 48-row k_ffn_ln tiles where the 16-row tiles are 1.4 - 3 per CU: 0 off | 1 one launch | 2 behind k_linear_res_ln
-    if (value < 0 || value > 2) return FFD_ERR_INVALID;
-    g_ffn_height = value;
-    return FFD_OK;
+#define FFD_KNOB_SET_BOOL(k, var, def) \
+  if (!strcmp(key, k)) {               \
+    var = v ? 1 : 0;                   \
+    return FFD_OK;                     \
   }
-  if (!strcmp(key, "ffn_persist")) {  // 0: one workgroup per tile; n >= 1: persistent grid of n x the resident workgroups
-    if (value < 0 || value > 8) return FFD_ERR_INVALID;
-    g_ffn_persist = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "attn_small")) {  // small-batch attention: 0 never, 1 by batch size, 2 / 4 force the key pieces
-    if (value != 0 && value != 1 && value != 2 && value != 4) return FFD_ERR_INVALID;
-    g_attn_small = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "embed_ldsx")) {  // embedding kernel: the wave's x rows through LDS (1) or per-lane loads (0)
-    g_embed_ldsx = value ? 1 : 0;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "embed_threads")) {
-    if (value < 256) return FFD_ERR_INVALID;
-    g_embed_threads = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "ffn_split")) {  // opt-in bf16x3-split FFN (not the reference's fp32 arithmetic; ffd_ffn_split.hip)
-    g_ffn_split = value ? 1 : 0;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "mid_path")) {  // 64-row FFN over F slices for mid-size M: 0 off, 1 heuristic, 2 / 4 / 8 forced
-    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return FFD_ERR_INVALID;
-    g_mid_path = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "small_wgs")) {  // most workgroups (row tiles x F splits) the small-M pair is used for
-    if (value < 0) return FFD_ERR_INVALID;
-    g_small_wgs = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "small_path")) {  // split out-proj + FFN pair for small M (0 = always the large-M kernels)
-    g_small_path = value ? 1 : 0;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "ffn_rows")) {  // large-M FFN: row-owning waves + CU-shared weight ring (1, default) or k_ffn_ln (0)
-    if (value < 0 || value > 2) return FFD_ERR_INVALID;
-    g_ffn_rows = value;  // 2: at every M (the test suite runs the goldens through it)
-    return FFD_OK;
-  }
-  if (!strcmp(key, "ffn_rows_cps")) {
-    if (value < 0 || value > 2) return FFD_ERR_INVALID;
-    g_ffn_rows_cps = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "ffn_rows_fuse")) {  // out-projection + LN1 inside k_ffn_rows (1, default) or k_linear_res_ln before it (0)
-    g_ffn_rows_fuse = value ? 1 : 0;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "rows_slices")) {  // sliced form of the fused kernel at mid-size M: 0 heuristic, -1 off, 2..32 slices forced
-    if (value < -1 || value == 1 || value > 32) return FFD_ERR_INVALID;
-    g_rows_slices = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "rows_slices_fuse")) {  // sliced form: 0 by estimate | 1 out-projection inside every unit | 2 k_linear_res_ln once in front
-    if (value < 0 || value > 2) return FFD_ERR_INVALID;
-    g_rows_slices_fuse = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "ffn_rows_nw")) {
-    if (value != 0 && value != 4 && value != 8 && value != 12) return FFD_ERR_INVALID;
-    g_ffn_rows_nw = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "ffn_rem")) {
-    g_ffn_rem = value ? 1 : 0;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "lstm_wave")) {  // LSTM layers as a wavefront (1, default; 2 = the same) | 0: the per-layer kernels
-    if (value < 0 || value > 2) return FFD_ERR_INVALID;
-    g_lstm_wave = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "lstm_wave_persist")) {  // k_lstm_wave workgroups walk their tile's layers (1) | one launch per layer group (0)
-    g_lstm_wave_persist = value ? 1 : 0;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "lstm_wave_chunk")) {  // cell steps per unit of the time-shared wavefront: 0 = by the pass count, 1 = never, even n = forced
-    if (value < 0 || (value > 1 && (value & 1)) || value > 1024) return FFD_ERR_INVALID;
-    g_lstm_wave_chunk = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "lstm_wave_per")) {  // at most this many layers in flight (0 = as many as the CUs hold)
-    if (value < 0 || value > 16) return FFD_ERR_INVALID;
-    g_lstm_wave_per = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "lstm_wave_fault")) {  // tests: unit (value - 1) of k_lstm_wave never publishes its progress
-    if (value < 0) return FFD_ERR_INVALID;
-    g_lstm_wave_fault = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "lstm_wave_spin_ms")) {  // time limit of one wait on a progress word
-    if (value < 1 || value > 20000) return FFD_ERR_INVALID;
-    g_lstm_wave_spin_ms = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "fuse_tail")) {  // unembed inside the SDE-step kernel of ffd_sample_batch
-    g_fuse_tail = value ? 1 : 0;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "attn_qg")) {
-    if (value < 0 || value > 3) return FFD_ERR_INVALID;
-    g_attn_qg = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "attn_hpw")) {
-    if (value < 0 || value > 2) return FFD_ERR_INVALID;
-    g_attn_hpw = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "fail_alloc_after")) {  // tests: the n-th device allocation from now fails with FFD_ERR_NOMEM (0 = off)
-    if (value < 0) return FFD_ERR_INVALID;
-    g_fail_alloc_after = value;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "attn_kvq")) {  // small-batch split attention: q projected for own q-tiles only (kv | q pack) | 0: whole head
-    g_attn_kvq = value ? 1 : 0;
-    return FFD_OK;
-  }
-  if (!strcmp(key, "attn_fused")) {
-    if (value < 0 || value > 1) return FFD_ERR_INVALID;
-    g_attn_fused = value;
-    return FFD_OK;
-  }
+  FFD_KNOBS(FFD_KNOB_SET, FFD_KNOB_SET_BOOL)
+#undef FFD_KNOB_SET
+#undef FFD_KNOB_SET_BOOL
   return FFD_ERR_INVALID;
 }
 
 int ffd_tune_get(const char* key, int* value) {
   if (!key || !value) return FFD_ERR_INVALID;
-  static const struct { const char* name; int* (*ptr)(); } tab[] = {
-#define K(name, var) {name, []() -> int* { return &var; }}
-      K("ffn_mb", g_ffn_mb_override), K("ffn_height", g_ffn_height), K("ffn_persist", g_ffn_persist), K("attn_small", g_attn_small),
-      K("embed_ldsx", g_embed_ldsx), K("embed_threads", g_embed_threads), K("ffn_split", g_ffn_split),
-      K("mid_path", g_mid_path), K("small_wgs", g_small_wgs), K("small_path", g_small_path), K("ffn_rows", g_ffn_rows),
-      K("ffn_rows_cps", g_ffn_rows_cps), K("ffn_rows_fuse", g_ffn_rows_fuse), K("rows_slices", g_rows_slices), K("rows_slices_fuse", g_rows_slices_fuse),
-      K("ffn_rows_nw", g_ffn_rows_nw), K("ffn_rem", g_ffn_rem), K("lstm_wave", g_lstm_wave),
-      K("lstm_wave_persist", g_lstm_wave_persist), K("lstm_wave_chunk", g_lstm_wave_chunk),
-      K("lstm_wave_per", g_lstm_wave_per), K("lstm_wave_fault", g_lstm_wave_fault),
-      K("lstm_wave_spin_ms", g_lstm_wave_spin_ms), K("fuse_tail", g_fuse_tail), K("attn_qg", g_attn_qg),
-      K("attn_hpw", g_attn_hpw), K("attn_kvq", g_attn_kvq), K("fail_alloc_after", g_fail_alloc_after), K("attn_fused", g_attn_fused),
-#undef K
-  };
-  for (const auto& e : tab)
-    if (!strcmp(key, e.name)) {
-      *value = *e.ptr();  // (the calling thread's copy: the knobs are thread_local)
-      return FFD_OK;
-    }
+#define FFD_KNOB_GET(k, var, ...) \
+  if (!strcmp(key, k)) {          \
+    *value = var;                 \
+    return FFD_OK;                \
+  }
+  FFD_KNOBS(FFD_KNOB_GET, FFD_KNOB_GET)  // (the calling thread's copy: the knobs are thread_local)
+#undef FFD_KNOB_GET
   return FFD_ERR_INVALID;
 }
 
@@ -713,6 +647,89 @@ static int ensure_qkv(ffd_ctx* ctx, size_t floats) {
   return dev_regrow(ctx, &ctx->qkv, floats, &ctx->qkv_floats, floats);
 }
 
+static LayerPlan plan_of(const ffd_ctx* ctx, int B, CacheMode mode) {
+  const LayerPacked& pk = ctx->packed[0];
+  return plan_layer(ctx->desc, B, mode, PackSet{pk.aw_full != nullptr, pk.aw_full2 != nullptr, pk.aw_kvq != nullptr,
+                                                pk.ring_op != nullptr});
+}
+
+static int ensure_ffn_part(ffd_ctx* ctx, const LayerPlan& p) {
+  if (p.part_floats <= ctx->ffn_part_floats) return FFD_OK;
+  return dev_regrow(ctx, &ctx->ffn_part, p.part_floats, &ctx->ffn_part_floats, p.part_floats);
+}
+
+// The FFD_K_ATTN launch(es) of layer i as planned, x -> ctx->attn.  kt / vt: the layer's K/V tables to read (cached
+// modes); kt_out / vt_out: where batch element 0's recomputed rows go (MIXED).  The two-kernel form needs ensure_qkv.
+static hipError_t run_attention(const ffd_ctx* ctx, const LayerPlan& p, int i, const float* x, const float* kt,
+                                const float* vt, float* kt_out, float* vt_out, int B, int n_own, hipStream_t s,
+                                unsigned long long* stamp = nullptr) {
+  const ffd_model_desc& m = ctx->desc;
+  const int L = m.max_len, d = m.d_model, H = m.n_head, hd = d / H;
+  const LayerPacked& pk = ctx->packed[i];
+  if (p.attn == ATTN_FUSED) {
+    // in-projection + attention in one launch: q/k/v never leave the CU (ffd_qkvattn.hip); in MIXED batch element 0's
+    // workgroups also publish their recomputed K/V rows (caching.py:326-328)
+    const float* pack = p.q_only == 2 ? pk.aw_kvq
+                        : p.hpw == 2  ? (p.q_only ? pk.aw_q2 : pk.aw_full2)
+                                      : (p.q_only ? pk.aw_q : pk.aw_full);
+    return launch_qkv_attention(x, pack, p.hpw, p.q_only, kt, vt, kt_out, vt_out, ctx->attn, B, L, d, hd, n_own, p.kspl,
+                                s, stamp);
+  }
+  if (stamp != nullptr) return hipErrorInvalidValue;
+  // q / k / v regions, head-major (B,H,L,hd)
+  const size_t M = (size_t)B * L;
+  float *q = ctx->qkv, *k = ctx->qkv + M * d, *v = ctx->qkv + 2 * M * d;
+  hipError_t e = launch_linear_hm(x, p.q_only ? pk.q_wp : pk.in_wp, ctx->layers[i].in_b, q, k, v, (int)M,
+                                  p.q_only ? 1 : 3, d, L, H, hd, s);
+  if (e == hipSuccess) e = launch_attention(q, k, v, kt, vt, ctx->attn, B, L, H, hd, n_own, s);
+  if (e == hipSuccess && kt_out)  // (caching.py:326-328, cached_transformer.py:301-305)
+    e = launch_kv_store(k, v, kt_out, vt_out, L, H, hd, n_own, s);
+  return e;
+}
+
+// The FFD_K_FFN launch(es) of layer weights w as planned: from attn + the residual rows cur, or (p.oproj_separate) from
+// the k_linear_res_ln output in alt; the output goes to cur, or to alt where p.swap.  Partial tiles: ensure_ffn_part.
+static hipError_t run_ffn(const ffd_ctx* ctx, const LayerPlan& p, const LayerWeights& w, const float* attn, float* cur,
+                          float* alt, int M, hipStream_t s, unsigned long long* stamp = nullptr) {
+  const int d = ctx->desc.d_model, F = ctx->desc.dim_feedforward;
+  float* P = ctx->ffn_part;
+  switch (p.ffn) {
+    case FFN_LN_OPROJ:  // one 32- / 48-row tile per CU, out-proj + LN1 + FFN + LN2 in one launch, in place
+      return stamp ? hipErrorInvalidValue : launch_oproj_ffn_ln(attn, cur, w, cur, M, d, F, p.mb, s);
+    case FFN_SMALL:  // out-proj + LN1 recomputed per F split, FFN partials + a deterministic reduce / LN2 launch
+      return stamp ? hipErrorInvalidValue : launch_oproj_ffn_small(attn, cur, w, alt, P, cur, M, d, F, p.ns, s);
+    case FFN_ROWS_SLICED_OPROJ:  // tiles x slices of the hidden dimension + the reduce / LN2 launch (slices added in order)
+      return stamp ? hipErrorInvalidValue
+                   : launch_oproj_ffn_rows_sliced(attn, cur, w, P, alt, M, d, F, p.nw, p.nslice, s);
+    case FFN_ROWS_OPROJ:  // x1 never leaves the CU; rows are read and written by different waves: no in-place form
+      return launch_oproj_ffn_rows(attn, cur, w, alt, M, d, F, s, stamp);
+    case FFN_ROWS_SLICED:
+      return stamp ? hipErrorInvalidValue : launch_ffn_rows_sliced(alt, w, P, cur, M, d, F, p.nw, p.nslice, s);
+    case FFN_MID:  // 64-row tiles x F slices, partial tiles + the reduce / LN2 launch
+      return stamp ? hipErrorInvalidValue : launch_ffn_mid(alt, w, P, cur, M, d, F, p.nm, s);
+    case FFN_SPLIT: return launch_ffn_ln_split(alt, w, cur, M, d, F, s, stamp);
+    case FFN_ROWS: return launch_ffn_rows(alt, w, cur, M, d, F, s, stamp);
+    case FFN_LN: return launch_ffn_ln(alt, w, cur, M, d, F, p.mb, s, stamp);
+  }
+  return hipErrorInvalidValue;
+}
+
+// ffd_kernel_work's row per FFN form: name; the out-projection inside it (work of one, per slice where sliced)
+static const struct {
+  const char* name;
+  bool oproj;
+} kFfnForms[] = {
+    {"k_ffn_ln<oproj>", true},                                  // FFN_LN_OPROJ
+    {"k_oproj_ffn_split + k_ffn_reduce_ln", true},              // FFN_SMALL
+    {"k_ffn_rows<oproj, sliced> + k_rows_reduce_ln", true},     // FFN_ROWS_SLICED_OPROJ
+    {"k_ffn_rows<oproj>", true},                                // FFN_ROWS_OPROJ
+    {"k_ffn_rows<sliced> + k_rows_reduce_ln", false},           // FFN_ROWS_SLICED
+    {"k_ffn_part", false},                                      // FFN_MID
+    {"k_ffn_ln_split", false},                                  // FFN_SPLIT
+    {"k_ffn_rows", false},                                      // FFN_ROWS
+    {"k_ffn_ln", false},                                        // FFN_LN
+};
+
 // one score evaluation; temb points at d floats on the device (temb_stride = 0: shared by the batch) or at a
 // (B, d) table (temb_stride = d: per-sample diffusion times).
 // n_rec < 0: no cache.  Otherwise the E2-CRF mode for |recompute_tokens| = n_rec.
@@ -747,8 +764,8 @@ static int forward_impl(ffd_ctx* ctx, const float* x, const float* temb, int tem
   if (m.kind == FFD_MODEL_LSTM) {
     TIMED(FFD_K_EMBED, launch_embed(x, ctx->raw["embedder.weight"].p, ctx->raw["embedder.bias"].p, nullptr, temb,
                                     temb_stride, ctx->h0, B, L, C, d, s));
-    if (lstm_wave_selected(B, d) && m.num_layers <= 64 && lstm_wave_max_batch(L, d) >= 16) {  // mid-size batches: the layers as a wavefront (ffd_lstm.hip)
-      const int Bw = B < lstm_wave_max_batch(L, d) ? B : lstm_wave_max_batch(L, d);  // samples per launch
+    if (const LstmPlan lp = plan_lstm(m, B); lp.wave) {
+      const int Bw = lp.Bw;  // samples per launch
       const size_t need = (size_t)16 + 16 * cdiv(Bw, 16);
       if (need > ctx->lstm_prog_ints) {
         float* pbuf = reinterpret_cast<float*>(ctx->lstm_prog);
@@ -785,57 +802,28 @@ static int forward_impl(ffd_ctx* ctx, const float* x, const float* temb, int tem
   const int H = m.n_head, hd = d / H, F = m.dim_feedforward;
   TIMED(FFD_K_EMBED, launch_embed(x, ctx->raw["embedder.weight"].p, ctx->raw["embedder.bias"].p,
                                   ctx->raw["pos_encoder.embedding.weight"].p, temb, temb_stride, ctx->h0, B, L, C, d, s));
-  // mode selection, cached_transformer.py:139-220
-  enum { STD, FULL, PURE, MIXED } mode = STD;
-  if (n_rec >= 0) {
-    if (n_rec == L) mode = FULL;
-    else if ((double)n_rec > 0.8 * (double)L) mode = STD;
-    else if (n_rec == 0) mode = PURE;
-    else mode = MIXED;
-  }
+  const CacheMode mode = cache_mode(n_rec, L);  // cached_transformer.py:139-220
   const size_t lt = (size_t)H * L * hd;  // table floats per layer
-  const int nreg = (mode == PURE) ? 1 : 3;
-  const int n_own = (mode == PURE) ? 0 : (mode == MIXED) ? n_rec : L;
-  const bool qkv_attn = g_attn_fused && ctx->packed[0].aw_full != nullptr;
-  // q / k / v regions, head-major (B,H,L,hd): only the two-kernel fallback uses them
-  if (!qkv_attn)
-    if (int rc = ensure_qkv(ctx, (size_t)M * 3 * d)) return rc;
-  float* qreg = ctx->qkv;
-  float* kreg = ctx->qkv + (size_t)M * d;
-  float* vreg = ctx->qkv + 2 * (size_t)M * d;
-  float* cur = ctx->h0;  // layer input / residual
-  float* alt = ctx->h1;
-  auto proj_w = [&](int i) { return mode == PURE ? ctx->packed[i].q_wp : ctx->packed[i].in_wp; };
+  const int n_own = (mode == CACHE_PURE) ? 0 : (mode == CACHE_MIXED) ? n_rec : L;
+  const bool tables = (mode == CACHE_PURE || mode == CACHE_MIXED);
   // opt-in: the FFN on the bf16 matrix cores as a three-part split (ffd_ffn_split.hip); takes every batch size, so
   // that all parity cases exercise it when it is on
   if (g_ffn_split && !ffn_split_supported(d, F))
     return ctx->fail(FFD_ERR_UNSUPPORTED, "ffn_split needs d_model %% 4 == 0, d_model <= 96, dim_feedforward %% 128 == 0");
-  const bool split_ffn = g_ffn_split != 0;
+  const LayerPlan plan = plan_of(ctx, B, mode);  // (every layer has the same shape and packs)
+  if (plan.attn == ATTN_TWO_KERNEL)
+    if (int rc = ensure_qkv(ctx, (size_t)M * 3 * d)) return rc;
+  if (int rc = ensure_ffn_part(ctx, plan)) return rc;
+  float* cur = ctx->h0;  // layer input / residual
+  float* alt = ctx->h1;
   for (int i = 0; i < m.num_layers; ++i) {
     const LayerWeights& w = ctx->layers[i];
     const LayerPacked& pk = ctx->packed[i];
     float* kt = ctx->kt ? ctx->kt + i * lt : nullptr;
     float* vt = ctx->vt ? ctx->vt + i * lt : nullptr;
-    const bool tables = (mode == PURE || mode == MIXED);
-    if (qkv_attn) {
-      // in-projection + attention in one launch: q/k/v never leave the CU (ffd_qkvattn.hip); in MIXED batch
-      // element 0's workgroups also publish their recomputed K/V rows (caching.py:326-328)
-      const int hpw = pk.aw_full2 ? qkv_attention_hpw(d, hd, L, B) : 1;
-      // (small batches, not a pure cache hit: the split form on the kv | q pack -- q projected for own q-tiles only)
-      const bool kvq = g_attn_kvq && pk.aw_kvq != nullptr && mode != PURE && qkv_attention_small_split(B, H, L) != 0;
-      const float* pack = kvq ? pk.aw_kvq
-                              : hpw == 2 ? (mode == PURE ? pk.aw_q2 : pk.aw_full2) : (mode == PURE ? pk.aw_q : pk.aw_full);
-      TIMED(FFD_K_ATTN, launch_qkv_attention(cur, pack, hpw, kvq ? 2 : mode == PURE, tables ? kt : nullptr,
-                                             tables ? vt : nullptr, mode == MIXED ? kt : nullptr,
-                                             mode == MIXED ? vt : nullptr, ctx->attn, B, L, d, hd, n_own, s));
-    } else {
-      HIPCHECK(launch_linear_hm(cur, proj_w(i), w.in_b, qreg, kreg, vreg, M, nreg, d, L, H, hd, s));
-      HIPCHECK(launch_attention(qreg, kreg, vreg, tables ? kt : nullptr, tables ? vt : nullptr, ctx->attn, B, L, H, hd,
-                                n_own, s));
-      if (mode == MIXED)  // store batch element 0's recomputed rows (caching.py:326-328, cached_transformer.py:301-305)
-        HIPCHECK(launch_kv_store(kreg, vreg, kt, vt, L, H, hd, n_rec, s));
-    }
-    if (split_ffn && pk.w1s == nullptr) {  // first use: make the packs
+    TIMED(FFD_K_ATTN, run_attention(ctx, plan, i, cur, tables ? kt : nullptr, tables ? vt : nullptr,
+                                    mode == CACHE_MIXED ? kt : nullptr, mode == CACHE_MIXED ? vt : nullptr, B, n_own, s));
+    if (plan.ffn == FFN_SPLIT && pk.w1s == nullptr) {  // first use: make the packs
       LayerPacked& pkm = ctx->packed[i];
       if (int rc = dev_alloc(ctx, &pkm.w1s, w1split_bytes(d, F) / sizeof(float))) return rc;
       if (int rc = dev_alloc(ctx, &pkm.w2s, w2split_bytes(d, F) / sizeof(float))) return rc;
@@ -843,51 +831,11 @@ static int forward_impl(ffd_ctx* ctx, const float* x, const float* temb, int tem
       ctx->layers[i].w1s = pkm.w1s;
       ctx->layers[i].w2s = pkm.w2s;
     }
-    if (!split_ffn && g_ffn_height == 1 && ffn_height_plan(M, d, F)) {
-      // 1.4 - 3 16-row tiles per CU: one 32- / 48-row tile per CU, out-proj + LN1 + FFN + LN2 in one launch, in place
-      TIMED(FFD_K_FFN, launch_oproj_ffn_ln(ctx->attn, cur, w, cur, M, d, F, s));
-    } else if (const int ns = split_ffn ? 0 : small_path_splits(M, d, F)) {
-      // small M: out-proj + LN1 recomputed per F split, FFN partials + a deterministic reduce / LN2 launch
-      const size_t need = small_path_partial_floats(M, d, ns);
-      if (need > ctx->ffn_part_floats) {
-        if (int rc = dev_regrow(ctx, &ctx->ffn_part, need, &ctx->ffn_part_floats, need)) return rc;
-      }
-      TIMED(FFD_K_FFN, launch_oproj_ffn_small(ctx->attn, cur, w, alt, ctx->ffn_part, cur, M, d, F, ns, s));
-    } else if (int snw = 0, sns = 0, sunf = 0; !split_ffn && w.ring_op != nullptr && rows_slice_plan(M, d, F, &snw, &sns, &sunf)) {
-      // mid-size M: the row-owning kernel over tiles x slices of the hidden dimension and the reduce / LN2 launch
-      // (deterministic: the slices are added in order) -- with the out-projection + LN1 inside every unit, or (where
-      // the units are short) as one k_linear_res_ln launch in front
-      const size_t need = rows_slice_floats(M, d, sns);
-      if (need > ctx->ffn_part_floats) {
-        if (int rc = dev_regrow(ctx, &ctx->ffn_part, need, &ctx->ffn_part_floats, need)) return rc;
-      }
-      if (sunf) {
-        TIMED(FFD_K_OUTPROJ, launch_linear_res_ln(ctx->attn, pk.out_wp, w.out_b, cur, w.n1w, w.n1b, alt, M, d, s));
-        TIMED(FFD_K_FFN, launch_ffn_rows_sliced(alt, w, ctx->ffn_part, cur, M, d, F, snw, sns, s));
-      } else {
-        TIMED(FFD_K_FFN, launch_oproj_ffn_rows_sliced(ctx->attn, cur, w, ctx->ffn_part, alt, M, d, F, snw, sns, s));
-        float* t = cur;
-        cur = alt, alt = t;
-      }
-    } else if (!split_ffn && !mid_path_splits(M, d, F) && w.ring_op != nullptr && ffn_rows_fused_selected(M, d, F)) {
-      // large M, d_model 72: out-proj + LN1 + FFN + LN2 in one launch (x1 never leaves the CU); the output goes to the
-      // other hidden buffer (rows are read and written by different waves of different tiles: no in-place form)
-      TIMED(FFD_K_FFN, launch_oproj_ffn_rows(ctx->attn, cur, w, alt, M, d, F, s));
-      float* t = cur;
-      cur = alt, alt = t;
-    } else {
+    if (plan.oproj_separate)
       TIMED(FFD_K_OUTPROJ, launch_linear_res_ln(ctx->attn, pk.out_wp, w.out_b, cur, w.n1w, w.n1b, alt, M, d, s));
-      const int nm = split_ffn ? 0 : mid_path_splits(M, d, F);
-      if (nm) {  // mid-size M: 64-row tiles x F slices, partial tiles + the reduce / LN2 launch
-        const size_t need = small_path_partial_floats(cdiv(M, 64) * 64, d, nm);
-        if (need > ctx->ffn_part_floats) {
-          if (int rc = dev_regrow(ctx, &ctx->ffn_part, need, &ctx->ffn_part_floats, need)) return rc;
-        }
-        TIMED(FFD_K_FFN, launch_ffn_mid(alt, w, ctx->ffn_part, cur, M, d, F, nm, s));
-      } else if (split_ffn) TIMED(FFD_K_FFN, launch_ffn_ln_split(alt, w, cur, M, d, F, s));
-      else TIMED(FFD_K_FFN, launch_ffn_ln(alt, w, cur, M, d, F, s));
-    }
-    if (mode == FULL) {
+    TIMED(FFD_K_FFN, run_ffn(ctx, plan, w, ctx->attn, cur, alt, M, s));
+    if (plan.swap) std::swap(cur, alt);
+    if (mode == CACHE_FULL) {
       // K,V of the layer OUTPUT for batch element 0 (cached_transformer.py:144-158), written
       // straight into this layer's tables: head-major (1,H,L,hd) == table layout
       HIPCHECK(launch_linear_hm(cur, pk.kv_wp, w.in_b + d, kt, vt, nullptr, L, 2, d, L, H, hd, s));
@@ -896,9 +844,9 @@ static int forward_impl(ffd_ctx* ctx, const float* x, const float* temb, int tem
       HIPCHECK(hipMemcpyAsync(crf_out + (size_t)i * L * d, cur, sizeof(float) * L * d, hipMemcpyDeviceToDevice, s));
   }
   if (n_rec >= 0) {  // counters, caching.py:283,299,396
-    if (mode == FULL) ctx->stats.recompute_count += (int64_t)L * m.num_layers, ctx->table_allocated = true;
-    else if (mode == PURE) ctx->stats.cache_hit_count += (int64_t)L * m.num_layers;
-    else if (mode == MIXED) {
+    if (mode == CACHE_FULL) ctx->stats.recompute_count += (int64_t)L * m.num_layers, ctx->table_allocated = true;
+    else if (mode == CACHE_PURE) ctx->stats.cache_hit_count += (int64_t)L * m.num_layers;
+    else if (mode == CACHE_MIXED) {
       ctx->stats.cache_hit_count += (int64_t)(L - n_rec) * m.num_layers;
       ctx->stats.recompute_count += (int64_t)n_rec * m.num_layers;
       ctx->table_allocated = true;
@@ -1461,60 +1409,44 @@ const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cac
   if (!ctx || B < 1) return nullptr;
   const ffd_model_desc& m = ctx->desc;
   const double L = m.max_len, d = m.d_model, C = m.n_channels, F = m.dim_feedforward, M = (double)B * L;
-  const bool tr = m.kind == FFD_MODEL_TRANSFORMER, ls = m.kind == FFD_MODEL_LSTM;
+  // (the transformer's forms need the packs ffd_finalize_weights made)
+  const bool tr = m.kind == FFD_MODEL_TRANSFORMER && !ctx->packed.empty(), ls = m.kind == FFD_MODEL_LSTM;
+  const LayerPlan p = tr ? plan_of(ctx, B, cache_hit ? CACHE_PURE : CACHE_STD) : LayerPlan{};
+  const LstmPlan lp = ls ? plan_lstm(m, B) : LstmPlan{};
   double fl = 0.0, by = 0.0;
   const char* name = nullptr;
   switch (kernel_class) {
-    case FFD_K_FFN:  // 4 d F FLOP per row; x in, y out, both weight matrices once
-      if (tr && g_ffn_split) name = "k_ffn_ln_split", fl = 4.0 * M * d * F, by = 4.0 * (2.0 * M * d) + 6.0 * (2.0 * d * F);
-      else if (tr && g_ffn_height == 1 && ffn_height_plan((int)M, m.d_model, m.dim_feedforward))  // + the out-projection it absorbs
-        name = "k_ffn_ln<oproj>", fl = 4.0 * M * d * F + 2.0 * M * d * d, by = 4.0 * (3.0 * M * d + 2.0 * d * F + d * d);
-      else if (tr && small_path_splits((int)M, m.d_model, m.dim_feedforward))  // + the out-projection it absorbs
-        name = "k_oproj_ffn_split + k_ffn_reduce_ln", fl = 4.0 * M * d * F + 2.0 * M * d * d,
-        by = 4.0 * (3.0 * M * d + 2.0 * d * F + d * d);
-      else if (int a_ = 0, b_ = 0, u_ = 0; tr && rows_slice_plan((int)M, m.d_model, m.dim_feedforward, &a_, &b_, &u_)) {
-        if (u_) name = "k_ffn_rows<sliced> + k_rows_reduce_ln", fl = 4.0 * M * d * F, by = 4.0 * (2.0 * M * d + 2.0 * d * F);
-        else name = "k_ffn_rows<oproj, sliced> + k_rows_reduce_ln", fl = 4.0 * M * d * F + b_ * 2.0 * M * d * d,
-             by = 4.0 * (3.0 * M * d + 2.0 * d * F + d * d);
+    case FFD_K_FFN:  // 4 d F FLOP per row; x in, y out, both weight matrices once (+ the out-projection it absorbs)
+      if (tr) {
+        const bool op = kFfnForms[p.ffn].oproj;
+        name = kFfnForms[p.ffn].name;
+        fl = 4.0 * M * d * F + (op ? (p.ffn == FFN_ROWS_SLICED_OPROJ ? p.nslice : 1) * 2.0 * M * d * d : 0.0);
+        by = p.ffn == FFN_SPLIT ? 4.0 * (2.0 * M * d) + 6.0 * (2.0 * d * F)
+             : op               ? 4.0 * (3.0 * M * d + 2.0 * d * F + d * d)
+                                : 4.0 * (2.0 * M * d + 2.0 * d * F);
       }
-      else if (tr && mid_path_splits((int)M, m.d_model, m.dim_feedforward))
-        name = "k_ffn_part", fl = 4.0 * M * d * F, by = 4.0 * (2.0 * M * d + 2.0 * d * F);
-      else if (tr && ffn_rows_fused_selected((int)M, m.d_model, m.dim_feedforward))  // + the out-projection it absorbs
-        name = "k_ffn_rows<oproj>", fl = 4.0 * M * d * F + 2.0 * M * d * d, by = 4.0 * (3.0 * M * d + 2.0 * d * F + d * d);
-      else if (tr && ffn_rows_selected((int)M, m.d_model, m.dim_feedforward))
-        name = "k_ffn_rows", fl = 4.0 * M * d * F, by = 4.0 * (2.0 * M * d + 2.0 * d * F);
-      else if (tr) name = "k_ffn_ln", fl = 4.0 * M * d * F, by = 4.0 * (2.0 * M * d + 2.0 * d * F);
       break;
     case FFD_K_ATTN:  // in-projection (Q only on a pure-cache step) + QK^T + PV; x in, attention output out
       if (tr) {
-        name = "k_qkv_attention";
+        name = p.attn == ATTN_FUSED ? "k_qkv_attention" : "k_linear_hm + k_attention_mfma";
         fl = M * (2.0 * d * (cache_hit ? d : 3.0 * d) + 4.0 * L * d);
         by = 4.0 * (2.0 * M * d + 3.0 * d * d + (cache_hit ? 2.0 * L * d : 0.0));
+        if (p.attn == ATTN_TWO_KERNEL) by += 4.0 * 2.0 * M * (cache_hit ? d : 3.0 * d);  // q / k / v through HBM
       }
       break;
     case FFD_K_OUTPROJ:  // attention output + residual in, LN1 output out
-      if (tr && !g_ffn_split && g_ffn_height == 1 && ffn_height_plan((int)M, m.d_model, m.dim_feedforward)) break;  // inside k_ffn_ln<oproj>
-      if (int a_ = 0, b_ = 0, u_ = 0; !g_ffn_split && tr && !small_path_splits((int)M, m.d_model, m.dim_feedforward) &&
-                                       rows_slice_plan((int)M, m.d_model, m.dim_feedforward, &a_, &b_, &u_)) {
-        if (u_) name = "k_linear_res_ln", fl = 2.0 * M * d * d, by = 4.0 * (3.0 * M * d + d * d);
-        break;
-      }
-      if (tr && (g_ffn_split || (!small_path_splits((int)M, m.d_model, m.dim_feedforward) &&
-                                 !(!mid_path_splits((int)M, m.d_model, m.dim_feedforward) &&
-                                   ffn_rows_fused_selected((int)M, m.d_model, m.dim_feedforward)))))
-        name = "k_linear_res_ln", fl = 2.0 * M * d * d, by = 4.0 * (3.0 * M * d + d * d);
+      if (tr && p.oproj_separate) name = "k_linear_res_ln", fl = 2.0 * M * d * d, by = 4.0 * (3.0 * M * d + d * d);
       break;
     case FFD_K_LSTM_REC:
-      if (ls && lstm_wave_selected(B, m.d_model)) {  // every layer in one launch: x W_ih^T + h W_hh^T
-        // per launch: batches past a 16-sample tile per CU go in sub-batches (exact where B is a multiple of that)
-        const double Ml = (double)(B < lstm_wave_max_batch(L, m.d_model) ? B : lstm_wave_max_batch(L, m.d_model)) * L;
+      if (ls && lp.wave) {  // every layer in one launch: x W_ih^T + h W_hh^T; per launch: a sub-batch of Bw samples
+        const double Ml = (double)lp.Bw * L;
         name = "k_lstm_wave", fl = m.num_layers * 2.0 * Ml * 8.0 * d * d, by = m.num_layers * 4.0 * (2.0 * Ml * d + 8.0 * d * d);
       }
       else if (ls)  // h W_hh^T for L cell steps; gate pre-activations + residual rows in, rows out
         name = "k_lstm_layer", fl = 2.0 * M * 4.0 * d * d, by = 4.0 * (M * 4.0 * d + 2.0 * M * d + 4.0 * d * d);
       break;
     case FFD_K_LSTM_GATES:
-      if (ls && !lstm_wave_selected(B, m.d_model))
+      if (ls && !lp.wave)
         name = "k_linear_rm", fl = 2.0 * M * 4.0 * d * d, by = 4.0 * (M * d + M * 4.0 * d + 4.0 * d * d);
       break;
     case FFD_K_SDE:
@@ -1538,99 +1470,98 @@ const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cac
   return name;
 }
 
-int ffd_bench_ffn(ffd_ctx* ctx, int B, int iters, float* ms_out, void* stream) {
-  if (!ctx) return FFD_ERR_INVALID;
-  int rc = check_ready(ctx, B);
-  if (rc) return rc;
-  if (ctx->desc.kind != FFD_MODEL_TRANSFORMER) return ctx->fail(FFD_ERR_UNSUPPORTED, "no FFN in the LSTM backbone");
-  if (iters < 1 || !ms_out) return ctx->fail(FFD_ERR_INVALID, "bad argument to ffd_bench_ffn");
-  HIPCHECK(hipSetDevice(ctx->device));
-  if ((rc = ensure_workspace(ctx, B))) return rc;
-  const ffd_model_desc& m = ctx->desc;
-  const int M = B * m.max_len, d = m.d_model;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h1, (size_t)M * d, 0x9E3779B9u);
-  HIPCHECK(hipGetLastError());
-  // (the form the forward pass takes at this size: with the out-projection + LN1 inside it where that is selected)
-  const bool fused = !g_ffn_split && ctx->layers[0].ring_op && !mid_path_splits(M, d, m.dim_feedforward) &&
-                     ffn_rows_fused_selected(M, d, m.dim_feedforward);
-  if (fused) {
-    hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->attn, (size_t)M * d, 0x85EBCA6Bu);
-    HIPCHECK(hipGetLastError());
-  }
-  auto run = [&]() -> hipError_t {
-    return fused ? launch_oproj_ffn_rows(ctx->attn, ctx->h1, ctx->layers[0], ctx->h0, M, d, m.dim_feedforward, s)
-                 : launch_ffn_ln(ctx->h1, ctx->layers[0], ctx->h0, M, d, m.dim_feedforward, s);
-  };
-  for (int i = 0; i < 3; ++i) HIPCHECK(run());
-  hipEvent_t e0, e1;
-  HIPCHECK(hipEventCreate(&e0));
-  HIPCHECK(hipEventCreate(&e1));
-  HIPCHECK(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) HIPCHECK(run());
-  HIPCHECK(hipEventRecord(e1, s));
-  HIPCHECK(hipEventSynchronize(e1));
+
+}  // extern "C"
+
+// Launches run() back to back: batches of `batch` until warm_seconds have passed (at least one batch), then -- iters
+// > 0 -- `iters` launches between a fresh event pair, *ms_out = milliseconds per launch.  The events go on every path.
+template <typename Run>
+static int time_launches(ffd_ctx* ctx, hipStream_t s, Run run, int batch, double warm_seconds, int iters, float* ms_out) {
+  struct Events {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Events() {
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+    }
+  } ev;
+  HIPCHECK(hipEventCreate(&ev.e0));
+  HIPCHECK(hipEventCreate(&ev.e1));
+  HIPCHECK(hipEventRecord(ev.e0, s));
   float ms = 0.f;
-  HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  do {
+    for (int i = 0; i < batch; ++i) HIPCHECK(run());
+    HIPCHECK(hipEventRecord(ev.e1, s));
+    HIPCHECK(hipEventSynchronize(ev.e1));
+    HIPCHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  } while (ms * 1e-3 < warm_seconds);
+  if (iters < 1) return FFD_OK;
+  HIPCHECK(hipEventRecord(ev.e0, s));
+  for (int i = 0; i < iters; ++i) HIPCHECK(run());
+  HIPCHECK(hipEventRecord(ev.e1, s));
+  HIPCHECK(hipEventSynchronize(ev.e1));
+  HIPCHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
   *ms_out = ms / iters;
   return FFD_OK;
+}
+
+extern "C" {
+
+struct StampBuf {  // a probe's stamp records on the device, freed on every path
+  unsigned long long* p = nullptr;
+  ~StampBuf() { (void)hipFree(p); }
+};
+
+// Common set-up of the FFN probes: layer 0's planned FFD_K_FFN launch(es) at batch B on random rows (attention output
+// in ctx->attn, residual rows in h1, x1 in h0 for the forms behind k_linear_res_ln)
+static int ffn_probe_setup(ffd_ctx* ctx, int B, hipStream_t s, LayerPlan* plan) {
+  if (int rc = check_ready(ctx, B)) return rc;
+  if (ctx->desc.kind != FFD_MODEL_TRANSFORMER) return ctx->fail(FFD_ERR_UNSUPPORTED, "no FFN in this backbone");
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (int rc = ensure_workspace(ctx, B)) return rc;
+  *plan = plan_of(ctx, B, CACHE_STD);
+  if (plan->ffn == FFN_SPLIT && ctx->layers[0].w1s == nullptr)
+    return ctx->fail(FFD_ERR_STATE, "ffn_split: run one forward first (the packs are made on first use)");
+  if (int rc = ensure_ffn_part(ctx, *plan)) return rc;
+  const size_t n = (size_t)B * ctx->desc.max_len * ctx->desc.d_model;
+  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h1, n, 0x9E3779B9u);
+  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->attn, n, 0x85EBCA6Bu);
+  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h0, n, 0xC2B2AE35u);
+  HIPCHECK(hipGetLastError());
+  return FFD_OK;
+}
+
+int ffd_bench_ffn(ffd_ctx* ctx, int B, int iters, float* ms_out, void* stream) {
+  if (!ctx) return FFD_ERR_INVALID;
+  if (iters < 1 || !ms_out) return ctx->fail(FFD_ERR_INVALID, "bad argument to ffd_bench_ffn");
+  hipStream_t s = (hipStream_t)stream;
+  LayerPlan p;
+  if (int rc = ffn_probe_setup(ctx, B, s, &p)) return rc;
+  const int M = B * ctx->desc.max_len;
+  auto run = [&]() { return run_ffn(ctx, p, ctx->layers[0], ctx->attn, ctx->h1, ctx->h0, M, s); };
+  return time_launches(ctx, s, run, 3, 0.0, iters, ms_out);
 }
 
 int ffd_probe_ffn_clock(ffd_ctx* ctx, int B, double warm_seconds, double* ghz_out, double* loop_us_out,
                         unsigned long long* raw_out, int raw_capacity, int* nwg_out, void* stream) {
   if (!ctx) return FFD_ERR_INVALID;
-  int rc = check_ready(ctx, B);
-  if (rc) return rc;
-  if (ctx->desc.kind != FFD_MODEL_TRANSFORMER) return ctx->fail(FFD_ERR_UNSUPPORTED, "no FFN in this backbone");
   if (!ghz_out || !(warm_seconds >= 0.0) || warm_seconds > 30.0) return ctx->fail(FFD_ERR_INVALID, "bad argument");
-  HIPCHECK(hipSetDevice(ctx->device));
-  if ((rc = ensure_workspace(ctx, B))) return rc;
-  const ffd_model_desc& m = ctx->desc;
-  const int M = B * m.max_len, d = m.d_model;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h1, (size_t)M * d, 0x9E3779B9u);  // random data
-  HIPCHECK(hipGetLastError());
-  const bool split = g_ffn_split && ctx->layers[0].w1s != nullptr;  // (packed by the first forward with ffn_split on)
-  if (g_ffn_split && !split) return ctx->fail(FFD_ERR_STATE, "ffn_split: run one forward first (the packs are made on first use)");
-  const int nwg = split ? (cdiv(M, 64) < num_cus() ? cdiv(M, 64) : num_cus()) : cdiv(M, ffn_tile_rows(M));  // upper bound of the grid (the persistent form launches fewer)
-  const bool fused = !split && ctx->layers[0].ring_op && !mid_path_splits(M, d, m.dim_feedforward) &&
-                     ffn_rows_fused_selected(M, d, m.dim_feedforward);
-  if (fused) {
-    hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->attn, (size_t)M * d, 0x85EBCA6Bu);
-    HIPCHECK(hipGetLastError());
-  }
-  auto launch = [&](unsigned long long* st) {
-    return split ? launch_ffn_ln_split(ctx->h1, ctx->layers[0], ctx->h0, M, d, m.dim_feedforward, s, st)
-           : fused ? launch_oproj_ffn_rows(ctx->attn, ctx->h1, ctx->layers[0], ctx->h0, M, d, m.dim_feedforward, s, st)
-                   : launch_ffn_ln(ctx->h1, ctx->layers[0], ctx->h0, M, d, m.dim_feedforward, s, st);
-  };
-  unsigned long long* stamps = nullptr;
-  HIPCHECK(hipMalloc((void**)&stamps, sizeof(unsigned long long) * 8 * nwg));
-  HIPCHECK(hipMemsetAsync(stamps, 0, sizeof(unsigned long long) * 8 * nwg, s));
+  LayerPlan p;
+  if (int rc = ffn_probe_setup(ctx, B, s, &p)) return rc;
+  const int M = B * ctx->desc.max_len;
+  const int nwg = cdiv(M, 16);  // upper bound of every form's grid (16-row tiles at the smallest)
+  StampBuf stamps;
+  HIPCHECK(hipMalloc((void**)&stamps.p, sizeof(unsigned long long) * 8 * nwg));
+  HIPCHECK(hipMemsetAsync(stamps.p, 0, sizeof(unsigned long long) * 8 * nwg, s));
+  auto launch = [&](unsigned long long* st) { return run_ffn(ctx, p, ctx->layers[0], ctx->attn, ctx->h1, ctx->h0, M, s, st); };
   // back-to-back launches for warm_seconds (the clock the chip settles at under this load), then the stamped one
-  hipEvent_t e0, e1;
-  HIPCHECK(hipEventCreate(&e0));
-  HIPCHECK(hipEventCreate(&e1));
-  HIPCHECK(hipEventRecord(e0, s));
-  double elapsed = 0.0;
-  while (elapsed < warm_seconds) {
-    for (int i = 0; i < 50; ++i)
-      HIPCHECK(launch(nullptr));
-    HIPCHECK(hipEventRecord(e1, s));
-    HIPCHECK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
-    elapsed = ms * 1e-3;
-  }
-  HIPCHECK(launch(stamps));
+  float unused;
+  if (int rc = time_launches(ctx, s, [&]() { return launch(nullptr); }, 50, warm_seconds, 0, &unused)) return rc;
+  if (launch(stamps.p) != hipSuccess)
+    return ctx->fail(FFD_ERR_UNSUPPORTED, "no stamped twin of the planned FFN form (%s)", kFfnForms[p.ffn].name);
   std::vector<unsigned long long> h(8 * (size_t)nwg);
-  HIPCHECK(hipMemcpyAsync(h.data(), stamps, sizeof(unsigned long long) * 8 * nwg, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(h.data(), stamps.p, sizeof(unsigned long long) * 8 * nwg, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
-  (void)hipFree(stamps);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   std::vector<double> ghz, us;
   int used = 0;
   for (int i = 0; i < nwg; ++i)
@@ -1662,65 +1593,40 @@ int ffd_probe_attn(ffd_ctx* ctx, int B, int n_recompute, double warm_seconds, in
   const ffd_model_desc& m = ctx->desc;
   if (m.kind != FFD_MODEL_TRANSFORMER) return ctx->fail(FFD_ERR_UNSUPPORTED, "no attention in this backbone");
   if (!ms_out || iters < 1 || !(warm_seconds >= 0.0) || warm_seconds > 30.0) return ctx->fail(FFD_ERR_INVALID, "bad argument");
-  if (!ctx->packed[0].aw_full) return ctx->fail(FFD_ERR_UNSUPPORTED, "no fused attention kernel for this shape");
-  const int L = m.max_len, d = m.d_model, H = m.n_head, hd = d / H;
+  const int L = m.max_len, d = m.d_model, H = m.n_head;
   if (n_recompute > L) return ctx->fail(FFD_ERR_INVALID, "n_recompute=%d outside [-1,%d]", n_recompute, L);
-  enum { STD, PURE, MIXED } mode = STD;
-  if (n_recompute >= 0 && (double)n_recompute <= 0.8 * (double)L) mode = n_recompute == 0 ? PURE : MIXED;
-  if (mode != STD && !(ctx->cache_enabled && ctx->table_allocated))
+  const CacheMode mode = cache_mode(n_recompute, L);  // (FULL reads no tables: the plain layer's launch)
+  const bool tables = mode == CACHE_PURE || mode == CACHE_MIXED;
+  if (tables && !(ctx->cache_enabled && ctx->table_allocated))
     return ctx->fail(FFD_ERR_STATE, "cached modes need ffd_cache_enable and one full step (the tables)");
   HIPCHECK(hipSetDevice(ctx->device));
   if ((rc = ensure_workspace(ctx, B))) return rc;
+  const LayerPlan p = plan_of(ctx, B, mode);
+  if (p.attn == ATTN_TWO_KERNEL)
+    if ((rc = ensure_qkv(ctx, (size_t)B * L * 3 * d))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const size_t M = (size_t)B * L;
-  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h1, M * d, 0x9E3779B9u);  // random rows
+  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h1, (size_t)B * L * d, 0x9E3779B9u);  // random rows
   HIPCHECK(hipGetLastError());
-  const LayerPacked& pk = ctx->packed[0];
-  const int hpw = pk.aw_full2 ? qkv_attention_hpw(d, hd, L, B) : 1;
-  const float* pack = hpw == 2 ? (mode == PURE ? pk.aw_q2 : pk.aw_full2) : (mode == PURE ? pk.aw_q : pk.aw_full);
-  const int n_own = mode == PURE ? 0 : mode == MIXED ? n_recompute : L;
+  const int n_own = mode == CACHE_PURE ? 0 : mode == CACHE_MIXED ? n_recompute : L;
   // (MIXED: the recomputed rows of batch element 0 are NOT written back -- the probe leaves the tables as they are)
   auto launch = [&](unsigned long long* st) {
-    return launch_qkv_attention(ctx->h1, pack, hpw, mode == PURE, mode != STD ? ctx->kt : nullptr,
-                                mode != STD ? ctx->vt : nullptr, nullptr, nullptr, ctx->attn, B, L, d, hd, n_own, s, st);
+    return run_attention(ctx, p, 0, ctx->h1, tables ? ctx->kt : nullptr, tables ? ctx->vt : nullptr, nullptr, nullptr,
+                         B, n_own, s, st);
   };
-  hipEvent_t e0, e1;
-  HIPCHECK(hipEventCreate(&e0));
-  HIPCHECK(hipEventCreate(&e1));
-  HIPCHECK(hipEventRecord(e0, s));
-  double elapsed = 0.0;
-  do {
-    for (int i = 0; i < 20; ++i) HIPCHECK(launch(nullptr));
-    HIPCHECK(hipEventRecord(e1, s));
-    HIPCHECK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
-    elapsed = ms * 1e-3;
-  } while (elapsed < warm_seconds);
-  HIPCHECK(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) HIPCHECK(launch(nullptr));
-  HIPCHECK(hipEventRecord(e1, s));
-  HIPCHECK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  *ms_out = ms / iters;
+  if ((rc = time_launches(ctx, s, [&]() { return launch(nullptr); }, 20, warm_seconds, iters, ms_out))) return rc;
   if (nrec_out) *nrec_out = 0;
   if (raw_out && raw_capacity > 0) {
     const size_t nwave = (size_t)B * H * 4;  // upper bound: at most 4 waves per (sample, head) workgroup / head pair
-    unsigned long long* stamps = nullptr;
-    HIPCHECK(hipMalloc((void**)&stamps, sizeof(unsigned long long) * 16 * nwave));
-    HIPCHECK(hipMemsetAsync(stamps, 0, sizeof(unsigned long long) * 16 * nwave, s));
-    hipError_t e = launch(stamps);
-    if (e != hipSuccess) {
-      (void)hipFree(stamps);
-      return ctx->fail(FFD_ERR_UNSUPPORTED, "no stamped twin of the attention kernel for this shape / mode");
-    }
+    StampBuf stamps;
+    HIPCHECK(hipMalloc((void**)&stamps.p, sizeof(unsigned long long) * 16 * nwave));
+    HIPCHECK(hipMemsetAsync(stamps.p, 0, sizeof(unsigned long long) * 16 * nwave, s));
+    if (launch(stamps.p) != hipSuccess)
+      return ctx->fail(FFD_ERR_UNSUPPORTED, "no stamped twin of the planned attention form (%s, %d head(s) per workgroup, "
+                       "pack mode %d, %d key pieces) for this shape", p.attn == ATTN_FUSED ? "k_qkv_attention" : "two-kernel",
+                       p.hpw, p.q_only, p.kspl);
     std::vector<unsigned long long> h(16 * nwave);
-    HIPCHECK(hipMemcpyAsync(h.data(), stamps, sizeof(unsigned long long) * 16 * nwave, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(h.data(), stamps.p, sizeof(unsigned long long) * 16 * nwave, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
-    (void)hipFree(stamps);
     int used = 0;
     for (size_t i = 0; i < nwave && used < raw_capacity; ++i)
       if (h[16 * i + 1] != 0) memcpy(raw_out + 16 * (size_t)used++, &h[16 * i], sizeof(unsigned long long) * 16);

@@ -519,7 +519,6 @@ __global__ __launch_bounds__(256, (MB <= 4 ? 2 : 1)) void k_ffn_ln(const float* 
   }
 }
 
-thread_local int g_ffn_persist = 1;      // 1: persistent grid for MB >= 4 (n > 1: n x the resident workgroups); 0: one workgroup per tile
 int num_cus() {
   static int n = 0;
   if (n == 0) {
@@ -530,7 +529,6 @@ int num_cus() {
   }
   return n;
 }
-thread_local int g_ffn_height = 1;  // ffd_tune "ffn_height": tile heights of 32 / 48 rows where the 16-row tiles are 1.4 - 3 per CU: 1 with the out-projection + LN1 inside, 2 behind a k_linear_res_ln launch; 0 off
 // Between the small-batch pair and the sliced row-owning kernel (ECG: B = 12 ... 21 and 28 ... 65, the reference's default
 // sample_batch_size of 50 among them): 16 MB rows per workgroup with MB = the 16-row tiles per CU, so that every CU takes
 // one tile and its four waves split F -- 141 ... 256 16-row tiles: one each (B = 16: 0.479 -> 0.430 ms per step, B = 20:
@@ -540,28 +538,17 @@ thread_local int g_ffn_height = 1;  // ffd_tune "ffn_height": tile heights of 32
 // 0.958 -> 0.903 -> 0.874, B = 64 1.086 -> 0.920 -> 0.885; from 769 tiles on the 64-row forms were as fast already: a tile
 // costs ~ 13 us + 16.2 us per 16 rows, 15.6 of them matrix time).  0 = another form.
 int ffn_height_plan(int M, int D, int F) {
-  if (!g_ffn_height || g_ffn_mb_override != 0 || g_ffn_split || D % 4 != 0 || D > 72 || F % 64 != 0) return 0;
+  if (D % 4 != 0 || D > 72 || F % 64 != 0) return 0;
   const int t16 = cdiv(M, 16), cus = num_cus();
   if (20 * t16 >= 11 * cus && t16 <= cus) return 1;
   if (4 * t16 >= 5 * cus && t16 <= 2 * cus) return 2;
   if (t16 > 2 * cus && t16 <= 3 * cus) return 3;
   return 0;
 }
-thread_local int g_ffn_rem = 1;          // 1: remainder rows of GEMM2 on the 4x4x1 MFMA (ffd_tune "ffn_rem")
-thread_local int g_ffn_mb_override = 0;  // 0 = heuristic; 1 / 2 / 4 forces the tile height (ffd_tune "ffn_mb"; the 128-row MB = 8 instances -- never
-                            // selected, 400-656 B of scratch at d_model >= 48 -- were retired in round 4)
 
 template <int D>
-static hipError_t launch_ffn_d(const float* X, const LayerWeights& w, float* Y, int M, int F, hipStream_t s,
+static hipError_t launch_ffn_d(const float* X, const LayerWeights& w, float* Y, int M, int F, int mb, hipStream_t s,
                                unsigned long long* stamp) {
-  // Tile height 16*MB rows.  MB = 4 keeps two workgroups (two waves per SIMD) resident per CU
-  // and is the default once the grid fills the chip; smaller tiles for small batches.
-  int mb = g_ffn_mb_override;
-  if (mb < 1 || mb > 4) {
-    const int target = 2 * 256;
-    mb = cdiv(M, 64) >= target ? 4 : cdiv(M, 32) >= target ? 2 : 1;
-    if (const int hp = ffn_height_plan(M, D, F)) mb = hp;
-  }
   dim3 block(256);
   // MB >= 4 is persistent: as many workgroups as the chip holds (two per CU at MB = 4, one at MB = 8)
   const int resident = num_cus() * (mb == 4 ? 2 : 1) * (g_ffn_persist > 0 ? g_ffn_persist : 1);
@@ -615,10 +602,9 @@ static hipError_t launch_oproj_ffn_d(const float* attn, const float* Rres, const
 }
 
 hipError_t launch_oproj_ffn_ln(const float* attn, const float* Rres, const LayerWeights& w, float* Y, int M, int D, int F,
-                               hipStream_t s) {
-  const int mb = ffn_height_plan(M, D, F);
+                               int mb, hipStream_t s) {
   if (M <= 0) return hipSuccess;
-  if (!mb || w.out_wp == nullptr) return hipErrorInvalidValue;
+  if (w.out_wp == nullptr) return hipErrorInvalidValue;
   switch (D) {
 #define X(d) \
     case d: return launch_oproj_ffn_d<d>(attn, Rres, w, Y, M, F, mb, s);
@@ -628,20 +614,13 @@ hipError_t launch_oproj_ffn_ln(const float* attn, const float* Rres, const Layer
   }
 }
 
-int ffn_tile_rows(int M) {  // rows per workgroup launch_ffn_ln picks (one stamp pair per workgroup)
-  int mb = g_ffn_mb_override;
-  if (mb < 1 || mb > 4) mb = cdiv(M, 64) >= 512 ? 4 : cdiv(M, 32) >= 512 ? 2 : 1;  // (+ ffn_height_plan: the callers that stamp pass large M)
-  return 16 * mb;
-}
-
-hipError_t launch_ffn_ln(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, hipStream_t s,
+hipError_t launch_ffn_ln(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, int mb, hipStream_t s,
                          unsigned long long* stamp) {
   if (M <= 0) return hipSuccess;
   if (F % 64 != 0) return hipErrorInvalidValue;
-  if (w.ring != nullptr && ffn_rows_selected(M, D, F)) return launch_ffn_rows(X, w, Y, M, D, F, s, stamp);
   switch (D) {
 #define X(d) \
-    case d: return launch_ffn_d<d>(X, w, Y, M, F, s, stamp);
+    case d: return launch_ffn_d<d>(X, w, Y, M, F, mb, s, stamp);
     FFD_D_LIST(X)
 #undef X
     default: return hipErrorInvalidValue;

@@ -703,11 +703,6 @@ __global__ __launch_bounds__(64 * NW, 3) void k_ffn_rows(const float* __restrict
 }
 
 #ifndef FFD_ROWS_EXTRA_D
-thread_local int g_ffn_rows = 1;     // 1: row-owning kernel for large M (ffd_tune "ffn_rows"); 0: k_ffn_ln; 2: at every M (tests)
-thread_local int g_ffn_rows_nw = 0;  // 0 = heuristic; 4 / 8 / 12 waves per workgroup
-thread_local int g_ffn_rows_cps = 0;  // 0 / 2: two chunks per ring slot; 1: one
-thread_local int g_ffn_rows_fuse = 1;  // out-projection + LN1 inside the kernel (ffd_tune "ffn_rows_fuse"; two-chunk slots only)
-
 // d_model values with an instance (round 4: 48, 60 -- the reference's class default, score_models.py:31 -- and 64 beside
 // 72; the compacted remainder groups are what fits d_model 60's seven of them into the ring)
 bool ffn_rows_supported(int D, int F) { return (D == 72 || D == 64 || D == 60 || D == 48) && F % 64 == 0 && F >= 64; }
@@ -758,23 +753,19 @@ __global__ __launch_bounds__(256) void k_rows_reduce_ln(const float* __restrict_
 }
 
 #ifndef FFD_ROWS_EXTRA_D
-thread_local int g_rows_slices = 0;  // sliced form of the fused kernel: 0 heuristic, -1 off, 2 / 4 / 8 / 16 forced (ffd_tune "rows_slices")
-
 // Mid-size M: (waves per workgroup, slices) of the sliced form, or false where another form is expected to be faster.
 // Estimate per launch (us, tools/ffn_rows_sweep.py at d_model 72, F 2048): out-projection slot + chunk slots at the
 // pace of NW / 4 waves per SIMD + launch / prologue / tile end, + the reduce launch; a unit per CU at most.
 // *unfused_out (round 4): 1 where the slices should NOT recompute the out-projection (k_linear_res_ln once in front, no
 // out-projection slot per unit: the better deal where the units are short, i.e. small M and many slices).
-thread_local int g_rows_slices_fuse = 0;  // 0 heuristic, 1 fused only, 2 unfused only (ffd_tune "rows_slices_fuse")
 bool rows_slice_plan(int M, int D, int F, int* nw_out, int* nslice_out, int* unfused_out) {
   if (g_rows_slices < 0 || !g_ffn_rows || !g_ffn_rows_fuse || g_ffn_rows_cps == 1 || !ffn_rows_supported(D, F)) return false;
-  if (g_rows_slices == 0 && ffn_height_plan(M, D, F)) return false;  // (one 32- / 48-row k_ffn_ln tile per CU there)
   const int nslots = F / 64;
   double best = 1e30;
   int bnw = 0, bs = 0, bunf = 0;
   for (int unf = 0; unf <= 1; ++unf)
   for (int nw = 8; nw <= 12; nw += 4) {
-    if ((unf == 1 && (g_rows_slices_fuse == 1 || unfused_out == nullptr)) || (unf == 0 && g_rows_slices_fuse == 2 && unfused_out)) continue;
+    if ((unf == 1 && g_rows_slices_fuse == 1) || (unf == 0 && g_rows_slices_fuse == 2)) continue;
     if (g_ffn_rows_nw && g_ffn_rows_nw != nw) continue;
     const int tiles = cdiv(M, 32 * nw);
     // (measured at d_model 72; the matrix cycles of a slot go with d_model)
@@ -809,8 +800,7 @@ bool rows_slice_plan(int M, int D, int F, int* nw_out, int* nslice_out, int* unf
     }
     if (best > 0.97 * alt) return false;
   }
-  *nw_out = bnw, *nslice_out = bs;
-  if (unfused_out) *unfused_out = bunf;
+  *nw_out = bnw, *nslice_out = bs, *unfused_out = bunf;
   return true;
 }
 size_t rows_slice_floats(int M, int D, int nslice) { return (size_t)nslice * M * D; }

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/ffd.h"
+
 namespace ffd {
 
 constexpr int WAVE = 64;
@@ -22,6 +24,44 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 }
 
 constexpr __host__ __device__ int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// ---- ffd_tune knobs: each a thread_local int (a thread's knobs select the kernels of the launches it makes; a new
+// thread starts from the defaults).  I(key, variable, default, accepted values of v); B(key, variable, default): any
+// value, stored as 0 / 1.  ffd_tune, ffd_tune_get, "reset" and the definitions are generated from this table.
+#define FFD_KNOBS(I, B)                                                                                                 \
+  I("ffn_mb", g_ffn_mb_override, 0, v >= 0 && v <= 4)     /* k_ffn_ln tile height 16 x 1 / 2 / 3 / 4 rows forced; 0 heuristic */ \
+  I("ffn_height", g_ffn_height, 1, v >= 0 && v <= 2)      /* 32- / 48-row k_ffn_ln tiles (ffn_height_plan): 0 off | 1 one launch | 2 behind k_linear_res_ln */ \
+  I("ffn_persist", g_ffn_persist, 1, v >= 0 && v <= 8)    /* k_ffn_ln MB >= 4: 0 a workgroup per tile; n: persistent grid of n x the resident workgroups */ \
+  B("ffn_rem", g_ffn_rem, 1)                              /* remainder rows of GEMM2 on the 4x4x1 MFMA */ \
+  B("ffn_split", g_ffn_split, 0)                          /* opt-in bf16x3-split FFN (not the reference's fp32 arithmetic; ffd_ffn_split.hip) */ \
+  I("ffn_rows", g_ffn_rows, 1, v >= 0 && v <= 2)          /* large-M FFN: 1 row-owning waves + CU-shared weight ring | 0 k_ffn_ln | 2 at every M (tests) */ \
+  I("ffn_rows_nw", g_ffn_rows_nw, 0, v == 0 || v == 4 || v == 8 || v == 12)  /* k_ffn_rows waves per workgroup; 0 heuristic */ \
+  I("ffn_rows_cps", g_ffn_rows_cps, 0, v >= 0 && v <= 2)  /* k_ffn_rows 32-unit chunks per ring slot: 0 / 2 two | 1 one */ \
+  B("ffn_rows_fuse", g_ffn_rows_fuse, 1)                  /* out-projection + LN1 inside k_ffn_rows (1) | k_linear_res_ln before it (0) */ \
+  I("rows_slices", g_rows_slices, 0, v >= -1 && v != 1 && v <= 32)  /* sliced k_ffn_rows at mid-size M: 0 heuristic | -1 off | 2 ... 32 slices forced */ \
+  I("rows_slices_fuse", g_rows_slices_fuse, 0, v >= 0 && v <= 2)  /* sliced form: 0 by estimate | 1 out-projection in every unit | 2 k_linear_res_ln once in front */ \
+  I("mid_path", g_mid_path, 1, v == 0 || v == 1 || v == 2 || v == 4 || v == 8)  /* 64-row FFN over F slices for mid-size M: 0 off | 1 heuristic | 2 / 4 / 8 forced */ \
+  B("small_path", g_small_path, 1)                        /* split out-proj + FFN pair for small M (0: always the larger forms) */ \
+  I("small_wgs", g_small_wgs, 0, v >= 0)                  /* most workgroups (row tiles x F splits) of the small-M pair; 0 heuristic */ \
+  I("attn_small", g_attn_small, 1, v == 0 || v == 1 || v == 2 || v == 4)  /* small-batch split attention: 0 never | 1 by batch size | 2 / 4 key pieces forced */ \
+  I("attn_fused", g_attn_fused, 1, v >= 0 && v <= 1)      /* fused in-projection + attention where a kernel exists | 0 the two-kernel path */ \
+  I("attn_hpw", g_attn_hpw, 0, v >= 0 && v <= 2)          /* heads per attention workgroup: 0 heuristic | 1 / 2 */ \
+  I("attn_qg", g_attn_qg, 0, v >= 0 && v <= 3)            /* q-tile group size of the attention kernels: 0 heuristic | 1 / 2 / 3 */ \
+  B("attn_kvq", g_attn_kvq, 1)                            /* small-batch split attention on the kv | q pack (q projected for own q-tiles only) */ \
+  B("embed_ldsx", g_embed_ldsx, 1)                        /* embedding: the wave's x rows through LDS (1) | per-lane loads (0) */ \
+  I("embed_threads", g_embed_threads, 262144, v >= 256)   /* threads the embed grid aims at (tools/probes/embed_sweep.py: 114 us at 256 k, 118 at 512 k, 137 at 128 k on the config-5 shape) */ \
+  I("lstm_wave", g_lstm_wave, 1, v >= 0 && v <= 2)        /* LSTM layers as a wavefront (1, 2 the same) | 0 the per-layer kernels k_linear_rm + k_lstm_layer */ \
+  B("lstm_wave_persist", g_lstm_wave_persist, 1)          /* k_lstm_wave workgroups walk their tile's layers (1) | a launch per layer group (0) */ \
+  I("lstm_wave_per", g_lstm_wave_per, 0, v >= 0 && v <= 16)  /* at most this many layers in flight (0: as many as the CUs hold) */ \
+  I("lstm_wave_chunk", g_lstm_wave_chunk, 0, v >= 0 && !(v > 1 && (v & 1)) && v <= 1024)  /* cell steps per unit of the time-shared wavefront: 0 by the pass count | 1 never | even n forced */ \
+  I("lstm_wave_fault", g_lstm_wave_fault, 0, v >= 0)      /* tests: unit (v - 1) of k_lstm_wave never publishes its progress */ \
+  I("lstm_wave_spin_ms", g_lstm_wave_spin_ms, 2000, v >= 1 && v <= 20000)  /* time limit of one wait on a progress word */ \
+  B("fuse_tail", g_fuse_tail, 1)                          /* unembed inside the SDE-step kernel of ffd_sample_batch */ \
+  I("fail_alloc_after", g_fail_alloc_after, 0, v >= 0)    /* tests: the n-th device allocation from now fails with FFD_ERR_NOMEM (0 off) */
+
+#define FFD_KNOB_DECL(key, var, ...) extern thread_local int var;
+FFD_KNOBS(FFD_KNOB_DECL, FFD_KNOB_DECL)
+#undef FFD_KNOB_DECL
 
 // ---- LDS-DMA issued by hand + counted waits (k_ffn_rows, k_linear_res_ln) ----
 template <int N>
@@ -124,17 +164,15 @@ hipError_t launch_linear(const float* X, const float* Wp, const float* bias, flo
 // Y[M x D] = LayerNorm(R + X Wp^T + b) * g + beta    (out-proj + residual + LN1)
 hipError_t launch_linear_res_ln(const float* X, const float* Wp, const float* bias, const float* R, const float* g,
                                 const float* beta, float* Y, int M, int D, hipStream_t s);
-// Fused FFN: Y = LN2(X + W2 relu(W1 X + b1) + b2)
+// Fused FFN: Y = LN2(X + W2 relu(W1 X + b1) + b2) in 16 mb-row tiles (k_ffn_ln)
 // stamp != nullptr (diagnostics): per-workgroup (shader-clock, 100 MHz real-time) deltas around the main loop
-hipError_t launch_ffn_ln(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, hipStream_t s,
+hipError_t launch_ffn_ln(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, int mb, hipStream_t s,
                          unsigned long long* stamp = nullptr);
-int ffn_tile_rows(int M);
-// 16-row tiles per CU between 1.4 and 3: k_ffn_ln at 32 / 48 rows per workgroup (one tile per CU); 0 = another form
+// 16-row tiles per CU between 1.4 and 3: k_ffn_ln at 32 / 48 rows per workgroup (one tile per CU); 0 = not this form
 int ffn_height_plan(int M, int D, int F);
-// ... as ONE launch, out-projection + LN1 inside (g_ffn_height == 1); Y may be Rres
+// ... as ONE launch (mb = 1 / 2 / 3), out-projection + LN1 inside; Y may be Rres
 hipError_t launch_oproj_ffn_ln(const float* attn, const float* Rres, const LayerWeights& w, float* Y, int M, int D, int F,
-                               hipStream_t s);
-extern thread_local int g_ffn_height;
+                               int mb, hipStream_t s);
 // Row-owning FFN with a CU-shared LDS weight ring (ffd_ffn_rows.hip): the large-M form
 bool ffn_rows_supported(int D, int F);
 bool ffn_rows_selected(int M, int D, int F);
@@ -142,7 +180,6 @@ size_t ffn_ring_floats(int D, int F);
 hipError_t launch_pack_ffn_ring(const float* W1, const float* b1, const float* W2, float* out, int D, int F, hipStream_t s);
 hipError_t launch_ffn_rows(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, hipStream_t s,
                            unsigned long long* stamp = nullptr);
-extern thread_local int g_ffn_rows, g_ffn_rows_nw, g_ffn_rows_cps, g_ffn_rows_fuse;
 // out-proj + LN1 + FFN + LN2 in one launch (the fused form of k_ffn_rows); Y must not alias attn / Rin
 bool ffn_rows_fused_selected(int M, int D, int F);
 size_t ffn_ring_oproj_floats(int D);
@@ -150,16 +187,14 @@ hipError_t launch_pack_oproj_ring(const float* Wo, float* out, int D, hipStream_
 hipError_t launch_oproj_ffn_rows(const float* attn, const float* Rin, const LayerWeights& w, float* Y, int M, int D,
                                  int F, hipStream_t s, unsigned long long* stamp = nullptr);
 // mid-size M: the fused kernel over tiles x slices of the hidden dimension + a reduce / LN2 launch
-extern thread_local int g_rows_slices;
-bool rows_slice_plan(int M, int D, int F, int* nw_out, int* nslice_out, int* unfused_out = nullptr);
-extern thread_local int g_rows_slices_fuse;
+bool rows_slice_plan(int M, int D, int F, int* nw_out, int* nslice_out, int* unfused_out);
 hipError_t launch_ffn_rows_sliced(const float* X1, const LayerWeights& w, float* P, float* Y, int M, int D, int F, int nw,
                                   int nslice, hipStream_t s);
 size_t rows_slice_floats(int M, int D, int nslice);
 hipError_t launch_oproj_ffn_rows_sliced(const float* attn, const float* Rin, const LayerWeights& w, float* P, float* Y,
                                         int M, int D, int F, int nw, int nslice, hipStream_t s);
 // Small M (the reference harness's batch 1): out-proj + LN1 + FFN + LN2 as two launches with F split over NS
-// workgroups per 16-row tile (ffd_small.hip).  small_path_splits returns 0 when the large-M kernels should run.
+// workgroups per 16-row tile (ffd_small.hip).  small_path_splits returns 0 where this form does not apply.
 int small_path_splits(int M, int D, int F);
 size_t small_path_partial_floats(int M, int D, int NS);
 hipError_t launch_oproj_ffn_small(const float* attn, const float* xres, const LayerWeights& w, float* x1, float* P,
@@ -167,38 +202,25 @@ hipError_t launch_oproj_ffn_small(const float* attn, const float* xres, const La
 // Mid-size M: the 64-row FFN main loop over F slices + the same reduce (ffd_small.hip); 0 = not this form
 int mid_path_splits(int M, int D, int F);
 hipError_t launch_ffn_mid(const float* x1, const LayerWeights& w, float* P, float* Y, int M, int D, int F, int NS, hipStream_t s);
-extern thread_local int g_mid_path;
-extern thread_local int g_small_path;
-extern thread_local int g_small_wgs;
-// Opt-in bf16x3-split FFN (ffd_tune "ffn_split"; ffd_ffn_split.hip)
-extern thread_local int g_ffn_split;
-extern thread_local int g_embed_threads;
-extern thread_local int g_embed_ldsx;
 bool ffn_split_supported(int D, int F);
 size_t w1split_bytes(int D, int F);
 size_t w2split_bytes(int D, int F);
 hipError_t launch_pack_ffn_split(const float* W1, const float* W2, void* w1s, void* w2s, int D, int F, hipStream_t s);
 hipError_t launch_ffn_ln_split(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, hipStream_t s,
                                unsigned long long* stamp = nullptr);
-extern thread_local int g_ffn_mb_override;
-extern thread_local int g_ffn_rem;
-extern thread_local int g_ffn_persist;
-extern thread_local int g_attn_fused;
 // fused in-projection + attention (ffd_qkvattn.hip)
 size_t attn_pack_floats(int D, int H, int hpw, int q_only);  // q_only = pack mode: 0 q | k | v, 1 q only, 2 tile 0 = k | v, tile 1 = q
 bool attn_kvq_supported(int hd);                              // head dims with a mode-2 pack (the split small-batch form's)
 hipError_t launch_pack_attn(const float* in_w, const float* in_b, float* pack, int D, int H, int hpw, int q_only,
                             hipStream_t s);
 bool qkv_attention_supported(int D, int hd);
-int qkv_attention_hpw(int D, int hd, int L, int B);
+int qkv_attention_hpw(int D, int hd, int L);
 int qkv_attention_small_split(int B, int H, int L);
-extern thread_local int g_attn_small;
 int num_cus();  // compute units of the current device (256 on MI355X); ffd_ffn.hip
-extern thread_local int g_attn_hpw;
+// kspl > 0: the small-batch split form with that many key pieces per q-tile (hpw 1; no stamped twin)
 hipError_t launch_qkv_attention(const float* x, const float* awp, int hpw, int q_only, const float* kt,
                                 const float* vt, float* kt_out, float* vt_out, float* out, int B, int L, int D, int hd,
-                                int n_own, hipStream_t s, unsigned long long* stamp = nullptr);
-extern thread_local int g_attn_qg;
+                                int n_own, int kspl, hipStream_t s, unsigned long long* stamp = nullptr);
 
 // Head-major projection: columns [r*d, (r+1)*d) of Y = X Wp^T + b go to region out[r]
 // laid out (B, H, L, hd) -- each (sample, head) slice contiguous, the layout of the K/V tables.
@@ -217,9 +239,7 @@ hipError_t launch_lstm_layer(float* x, const float* gx, const float* whh, int B,
 // batches below that kernel's crossover: all layers as a wavefront of (16-sample tile, layer) workgroups, in place on x;
 // prog: >= 16 + 16 * ceil(B / 16) ints of device scratch (abort word + progress words, cleared by the launcher);
 // err: host-visible word that receives 1 + (unit index) when a wait on a progress word runs out of time
-bool lstm_wave_selected(int B, int D);
 int lstm_wave_max_batch(int L, int D);  // samples one k_lstm_wave launch takes (a 16-sample tile per CU, rows < 2^31 bytes); larger batches go in sub-batches
-extern thread_local int g_lstm_wave, g_lstm_wave_persist, g_lstm_wave_per, g_lstm_wave_chunk, g_lstm_wave_fault, g_lstm_wave_spin_ms;
 hipError_t launch_lstm_wave(float* x, const float* const* wih_pk, const float* const* whh_pk, const float* const* bias_pk, int NL,
                             int B, int L, int D, int* prog, float* state, int* err, hipStream_t s,
                             unsigned long long* trace = nullptr);  // trace: 4 u64 per unit (ffd_lstm_trace), diagnostics
@@ -247,5 +267,38 @@ bool fresca2d_supported(int H, int W);
 size_t fresca2d_work_floats(int B, int H, int W, int C);
 hipError_t launch_fresca2d(const float* in, float* out, float* work, int B, int H, int W, int C, float low, float high,
                            double cutoff_ratio, int strategy, hipStream_t s);
+
+// ---- the kernels of one transformer layer / of the LSTM stack at a batch (ffd_api.hip) --------------------------
+// plan_layer is the one place that orders the forms; each heuristic above answers for its own form only.
+enum CacheMode { CACHE_STD, CACHE_FULL, CACHE_PURE, CACHE_MIXED };  // cached_transformer.py:139-220
+CacheMode cache_mode(int n_rec, int L);  // n_rec < 0: no cache
+enum AttnForm { ATTN_FUSED, ATTN_TWO_KERNEL };  // k_qkv_attention | k_linear_hm + k_attention_mfma (+ k_kv_store)
+// FFD_K_FFN forms: the first four take the out-projection + LN1 in, the other five run behind k_linear_res_ln
+enum FfnForm { FFN_LN_OPROJ, FFN_SMALL, FFN_ROWS_SLICED_OPROJ, FFN_ROWS_OPROJ, FFN_ROWS_SLICED, FFN_MID, FFN_SPLIT, FFN_ROWS,
+               FFN_LN };
+struct PackSet {  // the per-layer packs ffd_finalize_weights made for this shape
+  bool aw_full, aw_full2, aw_kvq;  // fused attention: per head, per head pair, kv | q
+  bool ring;                       // k_ffn_rows weight ring + its out-projection slot
+};
+struct LayerPlan {
+  AttnForm attn;
+  int hpw;     // heads per workgroup
+  int q_only;  // 0 q | k | v pack, 1 q only (pure cache hit), 2 kv | q pack
+  int kspl;    // key pieces of the small-batch split form, 0 = one workgroup per head (pair)
+  FfnForm ffn;
+  int mb;              // FFN_LN_OPROJ / FFN_LN: 16-row tiles per workgroup
+  int ns;              // FFN_SMALL: F splits
+  int nw, nslice;      // FFN_ROWS_SLICED*: waves per workgroup, slices
+  int nm;              // FFN_MID: F slices
+  bool oproj_separate;  // k_linear_res_ln (attn, residual -> x1 in the other hidden buffer) runs in front
+  bool swap;            // the output lands in the other hidden buffer
+  size_t part_floats;   // partial-buffer floats the form needs
+};
+LayerPlan plan_layer(const ffd_model_desc& m, int B, CacheMode mode, const PackSet& packs);
+struct LstmPlan {
+  bool wave;  // k_lstm_wave (all layers) in sub-batches of Bw samples | k_linear_rm + k_lstm_layer per layer
+  int Bw;
+};
+LstmPlan plan_lstm(const ffd_model_desc& m, int B);
 
 }  // namespace ffd

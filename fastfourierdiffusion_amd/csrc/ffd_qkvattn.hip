@@ -1194,8 +1194,6 @@ static hipError_t launch_split_t(const float* x, const float* awp, const float* 
   return hipGetLastError();
 }
 
-thread_local int g_attn_small = 1;  // 0 never, 1 by batch size, 2 / 4 force that many key pieces (ffd_tune "attn_small")
-
 // Key pieces per q-tile of the small-batch split form, 0 when the one-workgroup-per-head(-pair) kernels run: the
 // split form projects a head once per q-split, which only pays while the chip is not full.
 int qkv_attention_small_split(int B, int H, int L) {
@@ -1211,11 +1209,12 @@ int qkv_attention_small_split(int B, int H, int L) {
 
 template <int D, int HD>
 static hipError_t launch_dh(const float* x, const float* awp, int q_only, const float* kt, const float* vt,
-                            float* kt_out, float* vt_out, float* out, int B, int L, int n_own, hipStream_t s,
+                            float* kt_out, float* vt_out, float* out, int B, int L, int n_own, int kspl, hipStream_t s,
                             unsigned long long* stamp) {
   constexpr int NCTF = (3 * HD + 15) / 16;
   const int QT = (L + 31) / 32;
-  if (const int kspl = stamp ? 0 : qkv_attention_small_split(B, D / HD, L)) {
+  if (kspl) {
+    if (stamp != nullptr) return hipErrorInvalidValue;  // (no stamped twin of the split form)
     if constexpr (2 * HD <= 16 && 3 * HD > 16) {  // (q_only == 2: the caller handed over the kv | q pack)
       if (q_only == 2) return launch_split_t<D, HD, 2, true>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 0, kspl, s);
     }
@@ -1244,8 +1243,6 @@ static hipError_t launch_dh(const float* x, const float* awp, int q_only, const 
   return launch_t<D, HD, 2, NCTF>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 0, s, stamp);
 }
 
-thread_local int g_attn_fused = 1;  // 1: fused in-projection + attention where a kernel exists (ffd_tune "attn_fused")
-
 // (d_model, head_dim) pairs with a fused kernel; anything else keeps the two-kernel path.
 bool qkv_attention_supported(int D, int hd) {
   return (D == 72 && hd == 6) || (D == 60 && hd == 5) || (D == 24 && hd == 6) || (D == 8 && hd == 2) ||
@@ -1253,18 +1250,15 @@ bool qkv_attention_supported(int D, int hd) {
          (D == 24 && hd == 3);
 }
 
-thread_local int g_attn_hpw = 0;  // 0 heuristic, 1 / 2 force heads per workgroup (ffd_tune "attn_hpw")
-
-// heads per workgroup the fused kernel uses for this shape (the caller passes the matching weight pack)
-int qkv_attention_hpw(int D, int hd, int L, int B) {
-  if (qkv_attention_small_split(B, D / hd, L)) return 1;
+// heads per workgroup of the one-workgroup-per-head(-pair) kernels for this shape (the caller passes the matching pack)
+int qkv_attention_hpw(int D, int hd, int L) {
   const bool mh2 = ((D == 72 && hd == 6) || (D == 60 && hd == 5) || (D == 48 && hd == 4)) && L <= 192;
   return (g_attn_hpw == 1 || !mh2) ? 1 : 2;
 }
 
 hipError_t launch_qkv_attention(const float* x, const float* awp, int hpw, int q_only, const float* kt,
                                 const float* vt, float* kt_out, float* vt_out, float* out, int B, int L, int D, int hd,
-                                int n_own, hipStream_t s, unsigned long long* stamp) {
+                                int n_own, int kspl, hipStream_t s, unsigned long long* stamp) {
   if (B <= 0) return hipSuccess;
   if (hpw == 2) {
     if (D == 72 && hd == 6) return launch_mh2<72, 6>(x, awp, q_only, kt, vt, kt_out, vt_out, out, B, L, n_own, s, stamp);
@@ -1273,7 +1267,7 @@ hipError_t launch_qkv_attention(const float* x, const float* awp, int hpw, int q
     return hipErrorInvalidValue;
   }
 #define FFD_QA(dd, hh) \
-  if (D == dd && hd == hh) return launch_dh<dd, hh>(x, awp, q_only, kt, vt, kt_out, vt_out, out, B, L, n_own, s, stamp);
+  if (D == dd && hd == hh) return launch_dh<dd, hh>(x, awp, q_only, kt, vt, kt_out, vt_out, out, B, L, n_own, kspl, s, stamp);
   FFD_QA(72, 6)
   FFD_QA(60, 5)
   FFD_QA(24, 6)

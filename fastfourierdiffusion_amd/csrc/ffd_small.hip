@@ -423,16 +423,12 @@ __global__ __launch_bounds__(256) void k_ffn_reduce_ln(const float* __restrict__
   }
 }
 
-thread_local int g_small_wgs = 0;   // ffd_tune "small_wgs": most workgroups (row tiles x F splits) of the split pair; 0 = heuristic
-thread_local int g_small_path = 1;  // ffd_tune "small_path": 0 disables the split out-proj + FFN pair
-
-// F splits for M rows (0: use the large-M kernels).  The most splits (<= 16, F / (64 NS) chunks per wave in
+// F splits for M rows (0: not this form).  The most splits (<= 16, F / (64 NS) chunks per wave in
 // {2, 4, 8, 16}: the kernel's instances) that keep the grid within 2.5 workgroups per CU; failing that, within 6
 // (tools/sweep_mid.py on the ECG shape: the pair beats every tile height of k_ffn_ln up to M ~ 12 000 rows, where
 // 16-row tiles no longer fit the chip in one round and 64-row tiles leave half of it idle).
 int small_path_splits(int M, int D, int F) {
   if (!g_small_path || D % 4 != 0 || D > 128 || F % 64 != 0) return 0;
-  if (g_small_wgs == 0 && ffn_height_plan(M, D, F)) return 0;  // (one 32- / 48-row tile per CU is the faster form there)
   const int tiles = cdiv(M, 16);
   const int caps[2] = {g_small_wgs > 0 ? g_small_wgs : 5 * num_cus() / 2, g_small_wgs > 0 ? g_small_wgs : 6 * num_cus()};
   for (int cap : caps)
@@ -444,9 +440,7 @@ int small_path_splits(int M, int D, int F) {
   return 0;
 }
 
-thread_local int g_mid_path = 1;  // ffd_tune "mid_path": 0 off, 1 heuristic, 2 / 4 / 8 force that many F slices where the form applies
-
-// F slices of the 64-row form for M rows, 0 = not this form (checked after small_path_splits).  Model fitted to
+// F slices of the 64-row form for M rows, 0 = not this form.  Model fitted to
 // tools/sweep_mid.py: a CU retires a 64-row tile of k_ffn_ln every ~73 us whether it hosts one workgroup or two, so
 // the persistent kernel costs ceil(tiles / CUs) tile times; four F slices cost ceil(4 tiles / CUs) / 4 of them, times
 // 1.15 for what a slice pays per unit (X staging, first weight fetch, partial tile, no 4x4x1 remainder path, the
@@ -454,7 +448,6 @@ thread_local int g_mid_path = 1;  // ffd_tune "mid_path": 0 off, 1 heuristic, 2 
 // two slices were never better than four, eight only equal.
 int mid_path_splits(int M, int D, int F) {
   if (!g_mid_path || D % 4 != 0 || D > 128) return 0;
-  if (g_mid_path == 1 && ffn_height_plan(M, D, F)) return 0;
   if (g_mid_path > 1) return (F / 64) % g_mid_path == 0 ? g_mid_path : 0;
   if ((F / 64) % 4 != 0) return 0;
   const int tiles = cdiv(M, 64), cus = num_cus();

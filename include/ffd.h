@@ -387,22 +387,27 @@ int ffd_kernel_timing_begin(ffd_ctx* ctx, uint32_t class_mask, int max_launches)
 int ffd_kernel_timing_end(ffd_ctx* ctx);
 int ffd_kernel_timing_get(const ffd_ctx* ctx, int kernel_class, float* avg_ms_out, int* launches_out);
 /* Algorithmic work of ONE launch of a kernel class at batch B (SURVEY 8(d) figures: FLOPs for the
- * MFMA-bound classes, HBM bytes for all); cache_hit = 1 for a pure-cache step.  Returns the kernel's
- * name (static string) or NULL for a class this model does not launch. */
+ * MFMA-bound classes, HBM bytes for all); cache_hit = 1 for a pure-cache step.  Returns the name of the
+ * kernel(s) the forward pass plans for that class under the calling thread's ffd_tune knobs (static
+ * string), or NULL for a class the forward does not launch at this batch. */
 const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cache_hit, double* flops_out,
                             double* bytes_out);
-/* Time `iters` launches of the dominant kernel (fused FFN+LN2 of layer 0) at batch B
- * on `stream` with HIP events; returns average milliseconds per launch in *ms_out.
- * Synchronous (benchmark helper only). */
+/* Time `iters` runs of layer 0's FFN at batch B as the forward pass plans it (the launches
+ * ffd_kernel_timing counts as FFD_K_FFN, named by ffd_kernel_work) on random rows, on `stream`
+ * with HIP events; returns average milliseconds per run in *ms_out.  Synchronous (benchmark
+ * helper only). */
 int ffd_bench_ffn(ffd_ctx* ctx, int B, int iters, float* ms_out, void* stream);
 
-/* Diagnostic: the shader clock the chip holds under the dominant kernel, and a timeline of one launch.  Launches the
- * fused FFN back to back for `warm_seconds` on random data, then once more with in-kernel stamps (s_memtime /
+/* Diagnostic: the shader clock the chip holds under the dominant kernel, and a timeline of one launch.  Launches layer
+ * 0's FFN as the forward pass plans it at batch B back to back for `warm_seconds` on random data, then once more with
+ * in-kernel stamps (s_memtime /
  * s_memrealtime, written to a scratch buffer nothing else reads); *ghz_out = median over workgroups of shader cycles
  * per 10 ns tick x 0.1 inside the main loop, *loop_us_out (may be NULL) = median time a workgroup spent in its main
  * loops.  raw_out (may be NULL): up to raw_capacity records of 8 x u64 per workgroup -- [0] main-loop shader cycles,
  * [1] main-loop 10 ns ticks, then chip-wide 100 MHz timestamps [2] entry, [3] / [4] first main loop begin / end,
- * [5] first epilogue end, [6] exit, and [7] tiles processed; *nwg_out = workgroups that ran.  Synchronous. */
+ * [5] first epilogue end, [6] exit, and [7] tiles processed; *nwg_out = workgroups that ran.  FFD_ERR_UNSUPPORTED
+ * (naming the form) where the planned form has no stamped twin (k_ffn_ln, k_ffn_rows and the split FFN have one).
+ * Synchronous. */
 int ffd_probe_ffn_clock(ffd_ctx* ctx, int B, double warm_seconds, double* ghz_out, double* loop_us_out,
                         unsigned long long* raw_out, int raw_capacity, int* nwg_out, void* stream);
 
@@ -417,12 +422,12 @@ int ffd_probe_ffn_clock(ffd_ctx* ctx, int B, double warm_seconds, double* ghz_ou
  * the next call.  (The reference has no counterpart: its nn.LSTM layers are separate stream-ordered kernels.) */
 int ffd_async_status(ffd_ctx* ctx);
 
-/* Diagnostic + benchmark helper for the fused in-projection + attention launch of layer 0 (ffd_qkvattn.hip) at batch B
- * on random rows (replaces nothing in the reference: measurement scaffolding for cached_transformer.py:228-311's
+/* Diagnostic + benchmark helper for layer 0's attention launch as the forward pass plans it at batch B (the fused
+ * in-projection + attention of ffd_qkvattn.hip where it exists, else the two-kernel form) on random rows (replaces nothing in the reference: measurement scaffolding for cached_transformer.py:228-311's
  * kernel).  n_recompute < 0: plain layer; otherwise the E2-CRF mode of that recompute-set size (needs ffd_cache_enable
  * and one FULL step for the tables).  Launches it back to back for `warm_seconds`, times `iters` launches with HIP
  * events (*ms_out = milliseconds per launch), then -- when raw_out != NULL -- once more as its stamped twin (d_model 72,
- * head_dim 6 only): up to raw_capacity records of 16 x u64 per WAVE: [0] 100 MHz real time at entry, shader-clock
+ * head_dim 6, one workgroup per head or head pair, q | k | v pack; FFD_ERR_UNSUPPORTED naming the form otherwise): up to raw_capacity records of 16 x u64 per WAVE: [0] 100 MHz real time at entry, shader-clock
  * (s_memtime) stamps [1] entry, [2] projection begin, [3] projection end, [4] attention begin, [5] attention end,
  * [6] exit, shader cycles summed over the wave's key tiles [7] K fragments + QK^T, [8] mask + softmax, [9] P.V,
  * [10] key tiles walked, [11] HW_ID, [12] 100 MHz real time at exit; *nrec_out = records written.  Synchronous. */

@@ -1133,6 +1133,53 @@ def test_kernel_timing_and_work_accounting(ffd):
     assert ctx.lib.ffd_kernel_work(ctx.handle, N.K_FFN, 1, 0, C.byref(fl), C.byref(by)).startswith(b"k_oproj_ffn_split")
     assert fl.value == 4.0 * L * d * F + 2.0 * L * d * d
 
+    # a batch sweep of timed forwards: ffd_kernel_work names a class exactly when the forward launched it, and the
+    # launch counts are the plan's (one attention / FFN launch per layer; k_linear_res_ln only where named)
+    def forward_counts(model, c_, B):
+        ctx_ = model._ctx()
+        xb = torch.randn(B, c_["L"], c_["C"], device="cuda")
+        N.check(ctx_.lib.ffd_kernel_timing_begin(ctx_.handle, 0xFF, 4 * c_["NL"] + 8), ctx_.handle, "begin")
+        model(batch_of(xb, 0.5))
+        torch.cuda.synchronize()
+        N.check(ctx_.lib.ffd_kernel_timing_end(ctx_.handle), ctx_.handle, "end")
+        out = {}
+        for cls in range(8):
+            ms, n = C.c_float(), C.c_int()
+            N.check(ctx_.lib.ffd_kernel_timing_get(ctx_.handle, cls, C.byref(ms), C.byref(n)), ctx_.handle, "get")
+            name = ctx_.lib.ffd_kernel_work(ctx_.handle, cls, B, 0, C.byref(fl), C.byref(by))
+            out[cls] = (name, n.value)
+        return out
+
+    for knob in (None, (b"ffn_rows_fuse", 0), (b"ffn_height", 2), (b"ffn_split", 1)):
+        if knob:
+            assert ctx.lib.ffd_tune(*knob) == 0
+        for B in (1, 8, 16, 32, 50, 96, 200, 384, 512):
+            got = forward_counts(m, c, B)
+            for cls in (N.K_FFN, N.K_ATTN, N.K_OUTPROJ, N.K_LSTM_REC, N.K_LSTM_GATES, N.K_EMBED, N.K_UNEMBED):
+                assert (got[cls][0] is not None) == (got[cls][1] > 0), (knob, B, cls, got[cls])
+            assert got[N.K_FFN][1] == got[N.K_ATTN][1] == NL, (knob, B, got)
+            assert got[N.K_OUTPROJ][1] in (0, NL), (knob, B, got)
+        assert ctx.lib.ffd_tune(b"reset", 0) == 0
+    # the FFN / attention probes run the planned form at a small and a mid batch
+    for B in (8, 96):
+        ms = C.c_float()
+        N.check(ctx.lib.ffd_bench_ffn(ctx.handle, B, 5, C.byref(ms), None), ctx.handle, "bench_ffn")
+        assert ms.value > 0
+        ms = C.c_float()
+        N.check(ctx.lib.ffd_probe_attn(ctx.handle, B, -1, 0.0, 5, C.byref(ms), None, 0, None, None), ctx.handle, "probe_attn")
+        assert ms.value > 0
+    cl = next(c for c in cases.MODEL_CASES if c["name"] == "nasa_lstm")
+    ml, _ = make_model(ffd, cl)
+    for wave in (1, 0):
+        assert ml._ctx().lib.ffd_tune(b"lstm_wave", wave) == 0
+        for B in (1, 64, 512):
+            got = forward_counts(ml, cl, B)
+            for cls in (N.K_FFN, N.K_ATTN, N.K_OUTPROJ, N.K_LSTM_REC, N.K_LSTM_GATES):
+                assert (got[cls][0] is not None) == (got[cls][1] > 0), (wave, B, cls, got[cls])
+            assert got[N.K_LSTM_REC] == ((b"k_lstm_wave", 1) if wave else (b"k_lstm_layer", cl["NL"])), (B, got)
+            assert got[N.K_LSTM_GATES][1] == (0 if wave else cl["NL"]), (B, got)
+    assert ml._ctx().lib.ffd_tune(b"reset", 0) == 0
+
 
 @pytest.mark.parametrize("case", cases.AFFINE_FFT_CASES, ids=lambda c: f"L{c[0]}C{c[1]}")
 def test_affine_fft_golden(ffd, golden, case):
