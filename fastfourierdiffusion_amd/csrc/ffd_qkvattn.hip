@@ -11,7 +11,7 @@
 // two 16-feature tiles.  x rows go from global memory directly into the A operand -- each lane holds 4
 // consecutive k of its token per 16-wide chunk (float4), the weight pack uses the same k permutation --
 // and the softmax scale log2(e)/sqrt(hd) is folded into the q rows of the pack.
-// Phase 2 (attention): identical to k_attention_pk (ffd_attn.hip): S^T tiles on v_mfma_f32_32x32x2_f32 with the
+// Phase 2 (attention, attend_qtiles: one routine for both kernels): S^T tiles on v_mfma_f32_32x32x2_f32 with the
 // stale-max reference riding on contraction dim hd (skipped while it is zero), packed-fp32 softmax / P.V, V rows
 // pipelined from LDS.
 //
@@ -46,6 +46,21 @@ __device__ __forceinline__ f32x2 pk_fma_hi(f32x2 p, f32x2 v, f32x2 acc) {
 // over the wave's key tiles: [7] K fragments + QK^T until the scores are readable, [8] mask + softmax, [9] P.V;
 // [10] key tiles walked, [11] hardware id (HW_ID), [12] 100 MHz real time at exit.
 #define FFD_STAMP_T() ((unsigned long long)__builtin_amdgcn_s_memtime())
+struct WaveStamps {
+  unsigned long long t[7] = {0, 0, 0, 0, 0, 0, 0}, qk = 0, sm = 0, pv = 0, n = 0;  // [0 .. 6], [7], [8], [9], [10]
+  __device__ __forceinline__ void begin() { t[0] = __builtin_amdgcn_s_memrealtime(), t[1] = FFD_STAMP_T(); }
+  // lane 0 of each wave writes record (workgroup, wave) at kernel exit
+  __device__ __forceinline__ void write(unsigned long long* stamp, int nwaves) {
+    if ((threadIdx.x & 63) == 0 && stamp != nullptr) {
+      unsigned long long* r = stamp + ((size_t)blockIdx.x * nwaves + (threadIdx.x >> 6)) * 16;
+      t[6] = FFD_STAMP_T();
+#pragma unroll
+      for (int i = 0; i < 7; ++i) r[i] = t[i];
+      r[7] = qk, r[8] = sm, r[9] = pv, r[10] = n, r[11] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));
+      r[12] = __builtin_amdgcn_s_memrealtime();
+    }
+  }
+};
 
 // ---- weight pack ---------------------------------------------------------------------------------
 // awp[h][ct][step4][lane][4]: the B operand of k-step (4*step4 + i) for lane (n = lane & 15, q = lane >> 4):
@@ -165,6 +180,308 @@ __device__ __forceinline__ void head_norms(const float* kts, const float* qts, u
   }
 }
 
+// One head's LDS images at row stride LS: V [Lp][8] | K^T [2 KST][LS] | Q^T [2 KST][LS] (Q^T already scaled by
+// log2(e)/sqrt(hd)).  Dims e of the 32x32x2 QK^T sit in k-pair step e / 2, half e % 2; one more step carries -m_ref.
+template <int HD>
+struct HeadDims {
+  static constexpr int KST = (HD + 1) / 2;  // k-steps of the head dims
+  static constexpr int KSX = (HD + 2) / 2;  // ... with the -m_ref step
+  static constexpr int SX = HD / 2;         // the -m_ref step's index
+  static constexpr int HX = HD & 1;         // ... and the half that carries it
+  static constexpr int HP = (HD + 1) / 2;   // output feature pairs per row
+  static constexpr float T = 64.0f;  // scores (log2 domain) may sit this far from the reference before it is refreshed
+  static constexpr size_t floats(int LS) { return (size_t)LS * (8 + 4 * KST); }  // V | K^T | Q^T
+};
+
+// every score of the head is within +- sqrt(max |q|^2 max |k|^2) (wave-uniform; after the barrier behind head_norms)
+template <int HD>
+__device__ __forceinline__ bool head_bounded(const unsigned* nrm) {
+  constexpr float T = HeadDims<HD>::T;
+  return __builtin_amdgcn_ballot_w64(__uint_as_float(nrm[1]) * __uint_as_float(nrm[0]) <= T * T) != 0;
+}
+
+// XCD-aware mapping of workgroup `pair` to (sample b, head or head group g of NG): workgroups are dealt round-robin to the
+// 8 XCDs (blockIdx % 8), each with its own L2.  All groups of a sample read the same x rows, so they are placed on one
+// XCD: x is fetched into one L2 once instead of into (up to) eight.
+__device__ __forceinline__ void xcd_sample_group(int pair, int B, int NG, int& b, int& g) {
+  const int nmain = (B >> 3) * 8 * NG;
+  if (pair < nmain) {
+    const int xcd = pair & 7, slot = pair >> 3;
+    const int sb = slot / NG;
+    b = sb * 8 + xcd, g = slot - sb * NG;
+  } else {
+    b = pair / NG, g = pair - b * NG;
+  }
+}
+
+// Rows served by the shared tables (PURE: all of them; MIXED: tokens >= n_own) overwrite / fill head h's K^T and V,
+// by threads tid of nthreads.  (I is the caller's index type: the compiler unrolls a loop over unsigned threadIdx /
+// blockDim strides differently from one over int strides, so each kernel keeps the loops it had.)
+template <int HD, typename I>
+__device__ __forceinline__ void fill_from_tables(float* vs, float* kts, int LS, const float* kt, const float* vt, int h,
+                                                 int L, int Lp, int n_own, int q_only, I tid, I nthreads) {
+  if (!q_only && n_own > 0) __syncthreads();  // MIXED: the projection wrote these rows first
+  const float* ktab = kt + (size_t)h * L * HD;
+  const float* vtab = vt + (size_t)h * L * HD;
+  for (int j = n_own + tid; j < L; j += nthreads) {
+    float kx[HD], vx[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) vx[e] = 0.f;
+    const float* kp = ktab + (size_t)j * HD;
+    const float* vp = vtab + (size_t)j * HD;
+    if constexpr (HD % 2 == 0) {
+#pragma unroll
+      for (int e = 0; e < HD; e += 2) {
+        const float2 a = *reinterpret_cast<const float2*>(kp + e);
+        const float2 c2 = *reinterpret_cast<const float2*>(vp + e);
+        kx[e] = a.x, kx[e + 1] = a.y, vx[e] = c2.x, vx[e + 1] = c2.y;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < HD; ++e) kx[e] = kp[e], vx[e] = vp[e];
+    }
+#pragma unroll
+    for (int e = 0; e < HD; ++e) kts[e * LS + j] = kx[e];
+    *reinterpret_cast<float4*>(vs + (size_t)j * 8) = float4{vx[0], vx[1], vx[2], vx[3]};
+    *reinterpret_cast<float4*>(vs + (size_t)j * 8 + 4) = float4{vx[4], vx[5], vx[6], vx[7]};
+  }
+  if (q_only) {  // PURE: key rows in [L, Lp) were never written; they are masked but must be finite
+    for (int j = L + tid; j < Lp; j += nthreads) {
+#pragma unroll
+      for (int e = 0; e < HD; ++e) kts[e * LS + j] = 0.f;
+      *reinterpret_cast<float4*>(vs + (size_t)j * 8) = float4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<float4*>(vs + (size_t)j * 8 + 4) = float4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+}
+
+// MIXED: batch element 0 publishes head h's recomputed rows (tokens < n_own; caching.py:326-328,
+// cached_transformer.py:301-305), by threads tid of nthreads (I: see fill_from_tables)
+template <int HD, typename I>
+__device__ __forceinline__ void publish_kv(const float* vs, const float* kts, int LS, float* kt_out, float* vt_out, int h,
+                                           int L, int n_own, I tid, I nthreads) {
+  for (int idx = tid; idx < n_own * HD; idx += nthreads) {
+    const int j = idx / HD, e = idx - j * HD;
+    kt_out[(size_t)h * L * HD + idx] = kts[e * LS + j];
+    vt_out[(size_t)h * L * HD + idx] = vs[(size_t)j * 8 + e];
+  }
+}
+
+// per query row of a wave's QG q-tiles: reference exponent, row sum and unnormalised output (pairs of the two halves)
+template <int HD, int QG>
+struct QRows {
+  float mref[QG];
+  f32x2 lsum[QG], acc[QG][HeadDims<HD>::HP];
+};
+
+// The images as LDS pointers: the compiler optimises the routine before inlining it, and with generic pointers it
+// plans the LDS addressing as if they could point anywhere (more registers in most instances).
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef __attribute__((address_space(3))) const float lds_f32;
+typedef __attribute__((address_space(3))) const float4 lds_f32x4;
+#else  // (the host pass parses the routine too)
+typedef const float lds_f32;
+typedef const float4 lds_f32x4;
+#endif
+
+// ---- phase 2: attention ------------------------------------------------------------------------------
+// One wave attends q-tiles qt0 = q_first, q_first + q_step, ... < q_end, QG at a time, over key tiles [t_lo, t_hi) of
+// the head's LDS images.  Their row stride is LSC where the kernel has a compile-time one (0: the run-time LSR), so
+// that the LDS addresses are per-lane bases + immediate offsets.  STORE: normalise and write query row q to
+// orow0 + q * ostride; otherwise (the split form's key pieces) the last q-group's rows are returned unnormalised for
+// the caller to merge.
+template <int HD, int QG, bool STAMP, bool STORE, int LSC>
+__device__ __forceinline__ QRows<HD, QG> attend_qtiles(lds_f32* vs, lds_f32* kts, lds_f32* qts, int LSR,
+                                                       int q_first, int q_step, int q_end, int t_lo, int t_hi,
+                                                       bool head_bounded, int L, float* orow0, int ostride,
+                                                       WaveStamps& st) {
+  constexpr int KST = HeadDims<HD>::KST, KSX = HeadDims<HD>::KSX, SX = HeadDims<HD>::SX, HX = HeadDims<HD>::HX;
+  constexpr int HP = HeadDims<HD>::HP;
+  constexpr float T = HeadDims<HD>::T;
+  const int lane = threadIdx.x & 63;
+  const int half = lane >> 5, l31 = lane & 31;
+  const int QT = (L + 31) >> 5;
+  const int LS = LSC ? LSC : LSR;
+  const bool xlane = half == HX;
+  constexpr int PF = 4;
+  auto load_v = [&](int r, int kbase, f32x2(&dst)[4]) {
+    lds_f32* vr = vs + (size_t)(kbase + (r & 3) + 8 * (r >> 2)) * 8;
+    const float4 v0 = *reinterpret_cast<lds_f32x4*>(vr);
+    dst[0] = f32x2{v0.x, v0.y}, dst[1] = f32x2{v0.z, v0.w};
+    if (HD > 4) {
+      const float4 v1 = *reinterpret_cast<lds_f32x4*>(vr + 4);
+      dst[2] = f32x2{v1.x, v1.y}, dst[3] = f32x2{v1.z, v1.w};
+    } else {
+      dst[2] = f32x2{0.f, 0.f}, dst[3] = f32x2{0.f, 0.f};
+    }
+  };
+  QRows<HD, QG> rows;
+  for (int qt0 = q_first; qt0 < q_end; qt0 += q_step) {
+    float qf[QG][KSX], mref[QG];
+    f32x2 lsum[QG], acc[QG][HP];
+    bool ref_on = false;  // wave-uniform: some lane of this wave carries a non-zero reference
+    bool acc_empty[QG];
+#pragma unroll
+    for (int g = 0; g < QG; ++g) acc_empty[g] = true;
+#pragma unroll
+    for (int g = 0; g < QG; ++g) {
+      const int qtile = (qt0 + g < QT) ? qt0 + g : QT - 1;
+#pragma unroll
+      for (int s = 0; s < KSX; ++s) {
+        const int e = 2 * s + half;
+        qf[g][s] = (e < HD) ? qts[e * LS + 32 * qtile + l31] : 0.f;  // dim HD starts at -m_ref = 0
+      }
+      mref[g] = 0.f;
+      lsum[g] = f32x2{0.f, 0.f};
+#pragma unroll
+      for (int e = 0; e < HP; ++e) acc[g][e] = f32x2{0.f, 0.f};
+    }
+#pragma unroll 1
+    for (int t = t_lo; t < t_hi; ++t) {
+      unsigned long long st_a = 0;
+      if constexpr (STAMP) st_a = FFD_STAMP_T();
+      float kf[KSX];
+#pragma unroll
+      for (int s = 0; s < KSX; ++s) {
+        const int e = 2 * s + half;
+        kf[s] = (s < KST && (2 * s + 1 < HD || half == 0)) ? kts[e * LS + 32 * t + l31] : 0.f;
+      }
+      if (xlane) kf[SX] = 1.0f;
+      f32x16 sc[QG];
+#pragma unroll
+      for (int g = 0; g < QG; ++g) {
+        f32x16 z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < KSX; ++s) {
+          if (HD % 2 == 0 && s == SX && !ref_on) continue;  // even hd: that step carries nothing but -m_ref = 0
+          z = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s], qf[g][s], z, 0, 0, 0);
+        }
+        sc[g] = z;
+      }
+      const int kbase = 32 * t + 4 * half;
+      f32x2 vb[PF][4];
+#pragma unroll
+      for (int r = 0; r < PF; ++r) load_v(r, kbase, vb[r]);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (STAMP) {  // the stamp follows an instruction that reads the last score tile: QK^T has retired
+        asm volatile("v_mov_b32 %0, %0" : "+v"(sc[QG - 1][15]));
+        const unsigned long long n = FFD_STAMP_T();
+        st.qk += n - st_a, st_a = n, ++st.n;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (32 * t + 32 > L) {
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          if (32 * t + 8 * r4 + 8 > L) {  // (uniform) registers 4 r4 .. 4 r4 + 3 hold key rows 8 r4 .. 8 r4 + 7 of the tile
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+              const bool dead = kbase + rr + 8 * r4 >= L;
+#pragma unroll
+              for (int g = 0; g < QG; ++g) sc[g][4 * r4 + rr] = dead ? -INFINITY : sc[g][4 * r4 + rr];
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < QG; ++g) {
+        // while the head's bound stays within T and no lane of the wave uses a reference, nothing below can trigger
+        if (ref_on || !head_bounded) {
+        float bm = __builtin_fmaxf(__builtin_fmaxf(sc[g][0], sc[g][1]), sc[g][2]);
+#pragma unroll
+        for (int r = 3; r < 15; r += 2) bm = __builtin_fmaxf(__builtin_fmaxf(bm, sc[g][r]), sc[g][r + 1]);
+        bm = __builtin_fmaxf(bm, sc[g][15]);
+        const float bmx = fmaxf(bm, __shfl_xor(bm, 32));
+        // m_ref starts at 0 and usually stays there: |scores| <= 64 (log2 domain) neither overflow nor lose the row
+        // to underflow, and the factor 2^-m_ref cancels in the normalisation whatever it is.
+        const bool first = acc_empty[g];  // nothing accumulated yet: this is the row's first key tile
+        const bool refresh = first ? (fabsf(bmx) > T) : (bmx > T);
+        if (__builtin_amdgcn_ballot_w64(refresh) != 0) ref_on = true;
+        if (refresh) {
+          const float delta = bmx;
+          mref[g] += delta;
+          if (!first) {
+            const float corr = __builtin_amdgcn_exp2f(-delta);
+            lsum[g] *= corr;
+#pragma unroll
+            for (int e = 0; e < HP; ++e) acc[g][e] *= corr;
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) sc[g][r] -= delta;
+          if (xlane) qf[g][SX] = -mref[g];
+        }
+        }
+        acc_empty[g] = false;
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          const float p0 = __builtin_amdgcn_exp2f(sc[g][r]);
+          const float p1 = __builtin_amdgcn_exp2f(sc[g][r + 1]);
+          sc[g][r] = p0;
+          sc[g][r + 1] = p1;
+          lsum[g] += f32x2{p0, p1};
+        }
+      }
+      if constexpr (STAMP) {
+        __builtin_amdgcn_sched_barrier(0);
+        const unsigned long long n = FFD_STAMP_T();
+        st.sm += n - st_a, st_a = n;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        f32x2 vv[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) vv[e] = vb[r % PF][e];
+#pragma unroll
+        for (int g = 0; g < QG; ++g) {
+          const f32x2 pp = f32x2{sc[g][r & ~1], sc[g][(r & ~1) + 1]};  // (adjacent registers of the accumulator)
+#pragma unroll
+          for (int e = 0; e < HP; ++e) acc[g][e] = (r & 1) ? pk_fma_hi(pp, vv[e], acc[g][e]) : pk_fma_lo(pp, vv[e], acc[g][e]);
+        }
+        if (r + PF < 16) {
+          load_v(r + PF, kbase, vb[r % PF]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if constexpr (STAMP) {
+        __builtin_amdgcn_sched_barrier(0);
+        st.pv += FFD_STAMP_T() - st_a;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if constexpr (STAMP) st.t[5] = FFD_STAMP_T();
+    if constexpr (STORE) {
+#pragma unroll
+      for (int g = 0; g < QG; ++g) {
+        float l = lsum[g].x + lsum[g].y;
+        l += __shfl_xor(l, 32);
+        const float inv = __builtin_amdgcn_rcpf(l);  // (1 ulp; the IEEE division sequence is ten vector instructions per q-tile)
+        const int q = 32 * (qt0 + g) + l31;
+        float o[2 * HP];
+#pragma unroll
+        for (int e = 0; e < HP; ++e) {
+          float a0 = acc[g][e].x, a1 = acc[g][e].y;
+          a0 += __shfl_xor(a0, 32);
+          a1 += __shfl_xor(a1, 32);
+          o[2 * e] = a0 * inv, o[2 * e + 1] = a1 * inv;
+        }
+        if (half == 0 && q < L && qt0 + g < QT) {
+          float* orow = orow0 + (size_t)q * ostride;
+#pragma unroll
+          for (int e = 0; e < HD; ++e) orow[e] = o[e];
+        }
+      }
+    } else {
+#pragma unroll
+      for (int g = 0; g < QG; ++g) {
+        rows.mref[g] = mref[g], rows.lsum[g] = lsum[g];
+#pragma unroll
+        for (int e = 0; e < HP; ++e) rows.acc[g][e] = acc[g][e];
+      }
+    }
+  }
+  return rows;
+}
+
 // ---- the kernel ----------------------------------------------------------------------------------
 //
 // SPLIT (small batches, e.g. the benchmark_cache.py harness at batch 1: B*H workgroups would leave most of the chip
@@ -179,48 +496,34 @@ __global__ __launch_bounds__(256, (SPLIT && NCT >= 2 ? 2 : QG <= 2 ? 4 : 3)) voi
     const float* __restrict__ x, const float* __restrict__ awp, const float* __restrict__ kt,
     const float* __restrict__ vt, float* __restrict__ kt_out, float* __restrict__ vt_out, float* __restrict__ out,
     int B, int L, int n_own, int q_only, int qsplit, int kspl, unsigned long long* __restrict__ stamp) {
-  unsigned long long st_t[7] = {0, 0, 0, 0, 0, 0, 0}, st_qk = 0, st_sm = 0, st_pv = 0, st_n = 0;
-  if constexpr (STAMP) st_t[0] = __builtin_amdgcn_s_memrealtime(), st_t[1] = FFD_STAMP_T();
+  WaveStamps st;
+  if constexpr (STAMP) st.begin();
   constexpr int H = D / HD;
-  constexpr int KST = (HD + 1) / 2;
-  constexpr int KSX = (HD + 2) / 2;
-  constexpr int SX = HD / 2;
-  constexpr int HX = HD & 1;
-  constexpr int HP = (HD + 1) / 2;
+  constexpr int KST = HeadDims<HD>::KST;
   constexpr int C16 = D / 16;           // full 16-wide k chunks
   constexpr int REM = (D % 16) / 4;     // remaining k-steps (k = 16*C16 + 4 i + q)
   constexpr int S4 = (D + 15) / 16;     // float4 groups of packed weight per (h, ct)
-  constexpr float T = 64.0f;  // scores (log2 domain) may sit this far from the reference before it is refreshed
   extern __shared__ __align__(16) float lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nwaves = blockDim.x >> 6;
-  // XCD-aware mapping: workgroups are dealt round-robin to the 8 XCDs (blockIdx % 8), each with its own L2.
-  // All H heads of a sample read the same x rows, so they are placed on one XCD: x is fetched into one L2
-  // once instead of into (up to) eight.
   int b, h, qs = 0;
   {
     int pair = blockIdx.x;
     if constexpr (SPLIT) qs = pair % qsplit, pair /= qsplit;
-    const int nmain = (B >> 3) * 8 * H;
-    if (pair < nmain) {
-      const int xcd = pair & 7, slot = pair >> 3;
-      const int sb = slot / H;
-      b = sb * 8 + xcd, h = slot - sb * H;
-    } else {
-      b = pair / H, h = pair - b * H;
-    }
+    xcd_sample_group(pair, B, H, b, h);
   }
   const int KT = (L + 31) >> 5;
   const int Lp = KT * 32;
   // row stride of the LDS images: a compile-time 516 in the four-q-tiles-per-wave instance (launched for KT = 16 only), so
   // that its LDS addresses are per-lane bases + immediate offsets; the run-time Lp elsewhere
   // (+ 4: a stride that is a multiple of 64 floats puts the 16 feature rows a projection tile stores into the same banks)
-  const int LS = (QG == 4 && !SPLIT) ? 516 : Lp + 4;
+  constexpr int LSC = (QG == 4 && !SPLIT) ? 516 : 0;
+  const int LS = LSC ? LSC : Lp + 4;
   float* vs = lds;                               // V   [Lp][8]
   float* kts = vs + (size_t)LS * 8;              // K^T [2*KST][LS]
   float* qts = kts + (size_t)2 * KST * LS;       // Q^T [2*KST][LS]   (already scaled by log2(e)/sqrt(hd))
-  const int half = lane >> 5, l31 = lane & 31;
-  unsigned* nrm = reinterpret_cast<unsigned*>(lds + (size_t)LS * (8 + 4 * KST) + (SPLIT ? 4 * 32 * (2 + 2 * HP) : 0));  // see head_norms
+  constexpr int PS = 2 + 2 * HeadDims<HD>::HP;  // SPLIT partials per query row: reference exponent, row sum, output
+  unsigned* nrm = reinterpret_cast<unsigned*>(lds + HeadDims<HD>::floats(LS) + (SPLIT ? 4 * 32 * PS : 0));  // see head_norms
   if (threadIdx.x < 2) nrm[threadIdx.x] = 0u;  // (ordered before head_norms by the barrier behind the projection)
 
   if constexpr (HD % 2 == 1) {  // odd head dims read one pad row / pad column: keep them zero
@@ -308,7 +611,7 @@ __global__ __launch_bounds__(256, (SPLIT && NCT >= 2 ? 2 : QG <= 2 ? 4 : 3)) voi
     for (int u = 0; u < PFX; ++u)  // unconditional (tile index clamped): conditional loads would force vmcnt(0) waits
       load_x(min(tt0 + wave + u * nwaves, TT - 1), xa[u], xr[u]);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (STAMP) st_t[2] = FFD_STAMP_T();
+    if constexpr (STAMP) st.t[2] = FFD_STAMP_T();
     // Straight-line code (full unroll, forward exits only): a loop back-edge would make the compiler wait for
     // *all* outstanding loads at every tile (vmcnt(0)), which defeats the ring.  MAXT tiles per wave cover
     // L <= 512 with 4 waves.
@@ -399,43 +702,8 @@ __global__ __launch_bounds__(256, (SPLIT && NCT >= 2 ? 2 : QG <= 2 ? 4 : 3)) voi
       }
     }
   }
-  if constexpr (STAMP) st_t[3] = FFD_STAMP_T();
-  // rows served by the shared tables (PURE: all of them; MIXED: tokens >= n_own) overwrite / fill K^T and V
-  if (kt != nullptr) {
-    if (!q_only && n_own > 0) __syncthreads();  // MIXED: the projection wrote these rows first
-    const float* ktab = kt + (size_t)h * L * HD;
-    const float* vtab = vt + (size_t)h * L * HD;
-    for (int j = n_own + threadIdx.x; j < L; j += blockDim.x) {
-      float kx[HD], vx[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) vx[e] = 0.f;
-      const float* kp = ktab + (size_t)j * HD;
-      const float* vp = vtab + (size_t)j * HD;
-      if constexpr (HD % 2 == 0) {
-#pragma unroll
-        for (int e = 0; e < HD; e += 2) {
-          const float2 a = *reinterpret_cast<const float2*>(kp + e);
-          const float2 c2 = *reinterpret_cast<const float2*>(vp + e);
-          kx[e] = a.x, kx[e + 1] = a.y, vx[e] = c2.x, vx[e + 1] = c2.y;
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < HD; ++e) kx[e] = kp[e], vx[e] = vp[e];
-      }
-#pragma unroll
-      for (int e = 0; e < HD; ++e) kts[e * LS + j] = kx[e];
-      *reinterpret_cast<float4*>(vs + (size_t)j * 8) = float4{vx[0], vx[1], vx[2], vx[3]};
-      *reinterpret_cast<float4*>(vs + (size_t)j * 8 + 4) = float4{vx[4], vx[5], vx[6], vx[7]};
-    }
-    if (q_only) {  // PURE: key rows in [L, Lp) were never written; they are masked but must be finite
-      for (int j = L + threadIdx.x; j < Lp; j += blockDim.x) {
-#pragma unroll
-        for (int e = 0; e < HD; ++e) kts[e * LS + j] = 0.f;
-        *reinterpret_cast<float4*>(vs + (size_t)j * 8) = float4{0.f, 0.f, 0.f, 0.f};
-        *reinterpret_cast<float4*>(vs + (size_t)j * 8 + 4) = float4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-  }
+  if constexpr (STAMP) st.t[3] = FFD_STAMP_T();
+  if (kt != nullptr) fill_from_tables<HD>(vs, kts, LS, kt, vt, h, L, Lp, n_own, q_only, threadIdx.x, blockDim.x);
   __syncthreads();
   {  // (q rows outside the projected token range were never written: they stay out of the bound)
     int jq0 = 0, jq1 = Lp;
@@ -447,245 +715,58 @@ __global__ __launch_bounds__(256, (SPLIT && NCT >= 2 ? 2 : QG <= 2 ? 4 : 3)) voi
     }
     head_norms<HD>(kts, qts, nrm, Lp, LS, threadIdx.x, blockDim.x, jq0, jq1);
   }
-  // MIXED: batch element 0 publishes its recomputed rows (caching.py:326-328, cached_transformer.py:301-305)
-  if (kt_out != nullptr && b == 0 && qs == 0) {
-    for (int idx = threadIdx.x; idx < n_own * HD; idx += blockDim.x) {
-      const int j = idx / HD, e = idx - j * HD;
-      kt_out[(size_t)h * L * HD + idx] = kts[e * LS + j];
-      vt_out[(size_t)h * L * HD + idx] = vs[(size_t)j * 8 + e];
-    }
-  }
+  if (kt_out != nullptr && b == 0 && qs == 0)
+    publish_kv<HD>(vs, kts, LS, kt_out, vt_out, h, L, n_own, threadIdx.x, blockDim.x);
 
   __syncthreads();  // the tile norms
-  if constexpr (STAMP) st_t[4] = FFD_STAMP_T();
-  // every score of this head is within +- sqrt(max |q|^2 max |k|^2) (wave-uniform)
-  const bool head_bounded =
-      __builtin_amdgcn_ballot_w64(__uint_as_float(nrm[1]) * __uint_as_float(nrm[0]) <= T * T) != 0;
-  // ------------------------------------------------------------------ phase 2: attention (see k_attention_pk)
-  const bool xlane = half == HX;
-  constexpr int PF = 4;
-  auto load_v = [&](int r, int kbase, f32x2(&dst)[4]) {
-    const float* vr = vs + (size_t)(kbase + (r & 3) + 8 * (r >> 2)) * 8;
-    const float4 v0 = *reinterpret_cast<const float4*>(vr);
-    dst[0] = f32x2{v0.x, v0.y}, dst[1] = f32x2{v0.z, v0.w};
-    if (HD > 4) {
-      const float4 v1 = *reinterpret_cast<const float4*>(vr + 4);
-      dst[2] = f32x2{v1.x, v1.y}, dst[3] = f32x2{v1.z, v1.w};
-    } else {
-      dst[2] = f32x2{0.f, 0.f}, dst[3] = f32x2{0.f, 0.f};
-    }
-  };
-  const int QT = KT;
-  const int d = D;
-  // q-tiles of this wave: qt0 = q_first, q_first + q_step, ... < q_end; key tiles [t_lo, t_hi)
-  int q_first = wave * QG, q_step = nwaves * QG, q_end = QT, t_lo = 0, t_hi = KT;
-  if constexpr (SPLIT) {  // one (q-tile, key piece) per wave; exactly one trip so that every wave reaches the merge
+  if constexpr (STAMP) st.t[4] = FFD_STAMP_T();
+  const bool bounded = head_bounded<HD>(nrm);
+  float* orow0 = out + (size_t)b * L * D + h * HD;  // the head's output row for query token q: orow0 + q * D
+  if constexpr (SPLIT) {  // one (q-tile, key piece) per wave
     const int qpw = nwaves / kspl, kps = (KT + kspl - 1) / kspl;
-    q_first = qs * qpw + wave / kspl, q_step = 1, q_end = q_first + 1;
-    t_lo = (wave % kspl) * kps, t_hi = min(KT, t_lo + kps);
-    if (q_first >= QT) t_hi = t_lo;  // ragged last workgroup: an empty piece
+    const int qt = qs * qpw + wave / kspl, t_lo = (wave % kspl) * kps;
+    int t_hi = min(KT, t_lo + kps);
+    if (qt >= KT) t_hi = t_lo;  // ragged last workgroup: an empty piece (every wave reaches the merge)
+    const QRows<HD, 1> r = attend_qtiles<HD, 1, STAMP, false, 0>((lds_f32*)vs, (lds_f32*)kts, (lds_f32*)qts, LS, qt, 1,
+                                                                 qt + 1, t_lo, t_hi, bounded, L, orow0, D, st);
+    const int half = lane >> 5, l31 = lane & 31;
+    float* part = lds + HeadDims<HD>::floats(LS);  // [wave][32][PS]
+    float l = r.lsum[0].x + r.lsum[0].y;
+    l += __shfl_xor(l, 32);
+    float o[PS - 2];
+#pragma unroll
+    for (int e = 0; e < HeadDims<HD>::HP; ++e) {
+      float a0 = r.acc[0][e].x, a1 = r.acc[0][e].y;
+      o[2 * e] = a0 + __shfl_xor(a0, 32), o[2 * e + 1] = a1 + __shfl_xor(a1, 32);
+    }
+    if (half == 0) {
+      float* pw = part + (size_t)(wave * 32 + l31) * PS;
+      pw[0] = (t_lo < t_hi) ? r.mref[0] : -INFINITY;  // an empty piece weighs 2^-inf = 0 in the merge
+      pw[1] = l;
+#pragma unroll
+      for (int e = 0; e < PS - 2; ++e) pw[2 + e] = o[e];
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < qpw * 32 * HD; idx += blockDim.x) {
+      const int e = idx % HD, ql = (idx / HD) & 31, qi = idx / (HD * 32);
+      const int qtile = qs * qpw + qi, q = 32 * qtile + ql;
+      if (qtile >= KT || q >= L) continue;
+      const float* p0 = part + (size_t)(qi * kspl * 32 + ql) * PS;
+      float mx = -INFINITY;
+      for (int sp = 0; sp < kspl; ++sp) mx = fmaxf(mx, p0[(size_t)sp * 32 * PS]);
+      float lt = 0.f, ot = 0.f;
+      for (int sp = 0; sp < kspl; ++sp) {
+        const float* pp = p0 + (size_t)sp * 32 * PS;
+        const float wgt = __builtin_amdgcn_exp2f(pp[0] - mx);
+        lt = fmaf(pp[1], wgt, lt), ot = fmaf(pp[2 + e], wgt, ot);
+      }
+      orow0[(size_t)q * D + e] = ot / lt;
+    }
+  } else {
+    attend_qtiles<HD, QG, STAMP, true, LSC>((lds_f32*)vs, (lds_f32*)kts, (lds_f32*)qts, LS, wave * QG, nwaves * QG, KT,
+                                            0, KT, bounded, L, orow0, D, st);
   }
-  for (int qt0 = q_first; qt0 < q_end; qt0 += q_step) {
-    float qf[QG][KSX], mref[QG];
-    bool ref_on = false;  // wave-uniform: some lane of this wave carries a non-zero reference
-    bool acc_empty[QG];
-#pragma unroll
-    for (int g = 0; g < QG; ++g) acc_empty[g] = true;
-    f32x2 lsum[QG], acc[QG][HP];
-#pragma unroll
-    for (int g = 0; g < QG; ++g) {
-      const int qtile = (qt0 + g < QT) ? qt0 + g : QT - 1;
-#pragma unroll
-      for (int s = 0; s < KSX; ++s) {
-        const int e = 2 * s + half;
-        qf[g][s] = (e < HD) ? qts[e * LS + 32 * qtile + l31] : 0.f;  // dim HD starts at -m_ref = 0
-      }
-      mref[g] = 0.f;
-      lsum[g] = f32x2{0.f, 0.f};
-#pragma unroll
-      for (int e = 0; e < HP; ++e) acc[g][e] = f32x2{0.f, 0.f};
-    }
-#pragma unroll 1
-    for (int t = t_lo; t < t_hi; ++t) {
-      unsigned long long st_a = 0;
-      if constexpr (STAMP) st_a = FFD_STAMP_T();
-      float kf[KSX];
-#pragma unroll
-      for (int s = 0; s < KSX; ++s) {
-        const int e = 2 * s + half;
-        kf[s] = (s < KST && (2 * s + 1 < HD || half == 0)) ? kts[e * LS + 32 * t + l31] : 0.f;
-      }
-      if (xlane) kf[SX] = 1.0f;
-      f32x16 sc[QG];
-#pragma unroll
-      for (int g = 0; g < QG; ++g) {
-        f32x16 z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < KSX; ++s) {
-          if (HD % 2 == 0 && s == SX && !ref_on) continue;  // even hd: that step carries nothing but -m_ref = 0
-          z = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s], qf[g][s], z, 0, 0, 0);
-        }
-        sc[g] = z;
-      }
-      const int kbase = 32 * t + 4 * half;
-      f32x2 vb[PF][4];
-#pragma unroll
-      for (int r = 0; r < PF; ++r) load_v(r, kbase, vb[r]);
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (STAMP) {  // the stamp follows an instruction that reads the last score tile: QK^T has retired
-        asm volatile("v_mov_b32 %0, %0" : "+v"(sc[QG - 1][15]));
-        const unsigned long long n = FFD_STAMP_T();
-        st_qk += n - st_a, st_a = n, ++st_n;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (32 * t + 32 > L) {
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-          if (32 * t + 8 * r4 + 8 > L) {  // (uniform) registers 4 r4 .. 4 r4 + 3 hold key rows 8 r4 .. 8 r4 + 7 of the tile
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-              const bool dead = kbase + rr + 8 * r4 >= L;
-#pragma unroll
-              for (int g = 0; g < QG; ++g) sc[g][4 * r4 + rr] = dead ? -INFINITY : sc[g][4 * r4 + rr];
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < QG; ++g) {
-        // while the head's bound stays within T and no lane of the wave uses a reference, nothing below can trigger
-        if (ref_on || !head_bounded) {
-        float bm = __builtin_fmaxf(__builtin_fmaxf(sc[g][0], sc[g][1]), sc[g][2]);
-#pragma unroll
-        for (int r = 3; r < 15; r += 2) bm = __builtin_fmaxf(__builtin_fmaxf(bm, sc[g][r]), sc[g][r + 1]);
-        bm = __builtin_fmaxf(bm, sc[g][15]);
-        const float bmx = fmaxf(bm, __shfl_xor(bm, 32));
-        // m_ref starts at 0 and usually stays there: |scores| <= 64 (log2 domain) neither overflow nor lose the row
-        // to underflow, and the factor 2^-m_ref cancels in the normalisation whatever it is.
-        const bool first = acc_empty[g];  // nothing accumulated yet: this is the row's first key tile
-        const bool refresh = first ? (fabsf(bmx) > T) : (bmx > T);
-        if (__builtin_amdgcn_ballot_w64(refresh) != 0) ref_on = true;
-        if (refresh) {
-          const float delta = bmx;
-          mref[g] += delta;
-          if (!first) {
-            const float corr = __builtin_amdgcn_exp2f(-delta);
-            lsum[g] *= corr;
-#pragma unroll
-            for (int e = 0; e < HP; ++e) acc[g][e] *= corr;
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sc[g][r] -= delta;
-          if (xlane) qf[g][SX] = -mref[g];
-        }
-        }
-        acc_empty[g] = false;
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const float p0 = __builtin_amdgcn_exp2f(sc[g][r]);
-          const float p1 = __builtin_amdgcn_exp2f(sc[g][r + 1]);
-          sc[g][r] = p0;
-          sc[g][r + 1] = p1;
-          lsum[g] += f32x2{p0, p1};
-        }
-      }
-      if constexpr (STAMP) {
-        __builtin_amdgcn_sched_barrier(0);
-        const unsigned long long n = FFD_STAMP_T();
-        st_sm += n - st_a, st_a = n;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        f32x2 vv[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) vv[e] = vb[r % PF][e];
-#pragma unroll
-        for (int g = 0; g < QG; ++g) {
-          const f32x2 pp = f32x2{sc[g][r & ~1], sc[g][(r & ~1) + 1]};  // (adjacent registers of the accumulator)
-#pragma unroll
-          for (int e = 0; e < HP; ++e) acc[g][e] = (r & 1) ? pk_fma_hi(pp, vv[e], acc[g][e]) : pk_fma_lo(pp, vv[e], acc[g][e]);
-        }
-        if (r + PF < 16) {
-          load_v(r + PF, kbase, vb[r % PF]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      if constexpr (STAMP) {
-        __builtin_amdgcn_sched_barrier(0);
-        st_pv += FFD_STAMP_T() - st_a;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if constexpr (STAMP) st_t[5] = FFD_STAMP_T();
-    if constexpr (SPLIT) {
-      constexpr int PS = 2 + 2 * HP;  // per query row: reference exponent, row sum, unnormalised output
-      float* part = lds + (size_t)LS * (8 + 4 * KST);  // [wave][32][PS]
-      float l = lsum[0].x + lsum[0].y;
-      l += __shfl_xor(l, 32);
-      float o[2 * HP];
-#pragma unroll
-      for (int e = 0; e < HP; ++e) {
-        float a0 = acc[0][e].x, a1 = acc[0][e].y;
-        o[2 * e] = a0 + __shfl_xor(a0, 32), o[2 * e + 1] = a1 + __shfl_xor(a1, 32);
-      }
-      if (half == 0) {
-        float* pw = part + (size_t)(wave * 32 + l31) * PS;
-        pw[0] = (t_lo < t_hi) ? mref[0] : -INFINITY;  // an empty piece weighs 2^-inf = 0 in the merge
-        pw[1] = l;
-#pragma unroll
-        for (int e = 0; e < 2 * HP; ++e) pw[2 + e] = o[e];
-      }
-      __syncthreads();
-      const int qpw = nwaves / kspl;
-      for (int idx = threadIdx.x; idx < qpw * 32 * HD; idx += blockDim.x) {
-        const int e = idx % HD, ql = (idx / HD) & 31, qi = idx / (HD * 32);
-        const int qtile = qs * qpw + qi, q = 32 * qtile + ql;
-        if (qtile >= QT || q >= L) continue;
-        const float* p0 = part + (size_t)(qi * kspl * 32 + ql) * PS;
-        float mx = -INFINITY;
-        for (int sp = 0; sp < kspl; ++sp) mx = fmaxf(mx, p0[(size_t)sp * 32 * PS]);
-        float lt = 0.f, ot = 0.f;
-        for (int sp = 0; sp < kspl; ++sp) {
-          const float* pp = p0 + (size_t)sp * 32 * PS;
-          const float wgt = __builtin_amdgcn_exp2f(pp[0] - mx);
-          lt = fmaf(pp[1], wgt, lt), ot = fmaf(pp[2 + e], wgt, ot);
-        }
-        out[((size_t)b * L + q) * d + h * HD + e] = ot / lt;
-      }
-    } else {
-#pragma unroll
-    for (int g = 0; g < QG; ++g) {
-      float l = lsum[g].x + lsum[g].y;
-      l += __shfl_xor(l, 32);
-      const float inv = __builtin_amdgcn_rcpf(l);  // (1 ulp; the IEEE division sequence is ten vector instructions per q-tile)
-      const int q = 32 * (qt0 + g) + l31;
-      float o[2 * HP];
-#pragma unroll
-      for (int e = 0; e < HP; ++e) {
-        float a0 = acc[g][e].x, a1 = acc[g][e].y;
-        a0 += __shfl_xor(a0, 32);
-        a1 += __shfl_xor(a1, 32);
-        o[2 * e] = a0 * inv, o[2 * e + 1] = a1 * inv;
-      }
-      if (half == 0 && q < L && qt0 + g < QT) {
-        float* orow = out + ((size_t)b * L + q) * d + h * HD;
-#pragma unroll
-        for (int e = 0; e < HD; ++e) orow[e] = o[e];
-      }
-    }
-    }
-  }
-  if constexpr (STAMP) {
-    if (lane == 0 && stamp != nullptr) {
-      unsigned long long* r = stamp + ((size_t)blockIdx.x * (blockDim.x >> 6) + wave) * 16;
-      st_t[6] = FFD_STAMP_T();
-#pragma unroll
-      for (int i = 0; i < 7; ++i) r[i] = st_t[i];
-      r[7] = st_qk, r[8] = st_sm, r[9] = st_pv, r[10] = st_n, r[11] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));
-      r[12] = __builtin_amdgcn_s_memrealtime();
-    }
-  }
+  if constexpr (STAMP) st.write(stamp, nwaves);
 }
 
 // ---- multi-head variant ------------------------------------------------------------------------------
@@ -702,15 +783,11 @@ __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
     const float* __restrict__ x, const float* __restrict__ awp, const float* __restrict__ kt,
     const float* __restrict__ vt, float* __restrict__ kt_out, float* __restrict__ vt_out, float* __restrict__ out,
     int B, int L, int n_own, int q_only, unsigned long long* __restrict__ stamp) {
-  unsigned long long st_t[7] = {0, 0, 0, 0, 0, 0, 0}, st_qk = 0, st_sm = 0, st_pv = 0, st_n = 0;
-  if constexpr (STAMP) st_t[0] = __builtin_amdgcn_s_memrealtime(), st_t[1] = FFD_STAMP_T();
+  WaveStamps st;
+  if constexpr (STAMP) st.begin();
   constexpr int H = D / HD;
   constexpr int NG = H / HPW;
-  constexpr int KST = (HD + 1) / 2;
-  constexpr int KSX = (HD + 2) / 2;
-  constexpr int SX = HD / 2;
-  constexpr int HX = HD & 1;
-  constexpr int HP = (HD + 1) / 2;
+  constexpr int KST = HeadDims<HD>::KST;
   constexpr int C16 = D / 16;
   constexpr int REM = (D % 16) / 4;
   constexpr int S4 = (D + 15) / 16;
@@ -723,29 +800,17 @@ __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
   // L2 reads per workgroup, 72 registers): 100.4 -> 99.8 us at ECG B = 512 without it.
   constexpr bool REMV = HD == 6 && HPW == 2 && NCT == 3;
   constexpr int NCTM = REMV ? 2 : NCT;  // 16-wide feature tiles on the 16x16x4 form
-  constexpr float T = 64.0f;  // scores (log2 domain) may sit this far from the reference before it is refreshed
   extern __shared__ __align__(16) float lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int b, hg;
-  {
-    const int pair = blockIdx.x;
-    const int nmain = (B >> 3) * 8 * NG;
-    if (pair < nmain) {  // all head groups of a sample on one XCD (see k_qkv_attention)
-      const int xcd = pair & 7, slot = pair >> 3;
-      const int sb = slot / NG;
-      b = sb * 8 + xcd, hg = slot - sb * NG;
-    } else {
-      b = pair / NG, hg = pair - b * NG;
-    }
-  }
+  xcd_sample_group(blockIdx.x, B, NG, b, hg);
   const int KT = (L + 31) >> 5;
   const int Lp = KT * 32;
   // the LDS images have a COMPILE-TIME row stride (a wave owns QG q-tiles, a head two waves: Lp <= LS): every LDS address
   // below is one per-lane base + immediate offsets instead of multiplications by a run-time Lp
   constexpr int LS = 64 * QG + 4;  // (+ 4: see k_qkv_attention)
-  constexpr int RS = LS * (8 + 4 * KST);                       // floats per head region: V | K^T | Q^T
+  constexpr int RS = HeadDims<HD>::floats(LS);                 // floats per head region: V | K^T | Q^T
   float4* wl = reinterpret_cast<float4*>(lds + (size_t)HPW * RS);  // weight pack [NCT][S4][64] float4
-  const int half = lane >> 5, l31 = lane & 31;
   constexpr int fph = QO ? HD : 3 * HD;                        // features per head in this pack (QO == q_only)
   if (threadIdx.x < 2 * HPW)  // the heads' norm words (ordered before head_norms by the barriers of the projection)
     reinterpret_cast<unsigned*>(lds + (size_t)HPW * RS + (size_t)NCT * S4 * 256)[threadIdx.x] = 0u;
@@ -793,7 +858,7 @@ __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
                   : hh * RS + (reg == 0 ? LS * 8 + 2 * KST * LS + e * LS : reg == 1 ? LS * 8 + e * LS : e);
     }
     __syncthreads();
-    if constexpr (STAMP) st_t[2] = FFD_STAMP_T();
+    if constexpr (STAMP) st.t[2] = FFD_STAMP_T();
     // columns n = 0 .. 3 of the pack's third tile for this lane's k subset (qq), from the staged pack
     float4 wv4[REMV ? 4 : 1][REMV ? C16 : 1];
     float2 wvr[REMV ? 4 : 1];
@@ -875,256 +940,33 @@ __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
       }
     }
   }
-  if constexpr (STAMP) st_t[3] = FFD_STAMP_T();
+  if constexpr (STAMP) st.t[3] = FFD_STAMP_T();
   // this wave's head for the rest of the kernel
   const int hh = wave >> 1, gw = wave & 1;
   const int h = hg * HPW + hh;
   float* vs = lds + (size_t)hh * RS;
   float* kts = vs + LS * 8;
   float* qts = kts + 2 * KST * LS;
-  // rows served by the shared tables (PURE: all of them; MIXED: tokens >= n_own): the head's two waves fill them
-  if (kt != nullptr) {
-    if (!q_only && n_own > 0) __syncthreads();  // MIXED: the projection wrote these rows first
-    const float* ktab = kt + (size_t)h * L * HD;
-    const float* vtab = vt + (size_t)h * L * HD;
-    const int tid2 = gw * 64 + lane;  // 0..127 inside the head's wave pair
-    for (int j = n_own + tid2; j < L; j += 128) {
-      float kx[HD], vx[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) vx[e] = 0.f;
-      const float* kp = ktab + (size_t)j * HD;
-      const float* vp = vtab + (size_t)j * HD;
-      if constexpr (HD % 2 == 0) {
-#pragma unroll
-        for (int e = 0; e < HD; e += 2) {
-          const float2 a = *reinterpret_cast<const float2*>(kp + e);
-          const float2 c2 = *reinterpret_cast<const float2*>(vp + e);
-          kx[e] = a.x, kx[e + 1] = a.y, vx[e] = c2.x, vx[e + 1] = c2.y;
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < HD; ++e) kx[e] = kp[e], vx[e] = vp[e];
-      }
-#pragma unroll
-      for (int e = 0; e < HD; ++e) kts[e * LS + j] = kx[e];
-      *reinterpret_cast<float4*>(vs + (size_t)j * 8) = float4{vx[0], vx[1], vx[2], vx[3]};
-      *reinterpret_cast<float4*>(vs + (size_t)j * 8 + 4) = float4{vx[4], vx[5], vx[6], vx[7]};
-    }
-    if (q_only) {  // PURE: key rows in [L, Lp) were never written; they are masked but must be finite
-      for (int j = L + tid2; j < Lp; j += 128) {
-#pragma unroll
-        for (int e = 0; e < HD; ++e) kts[e * LS + j] = 0.f;
-        *reinterpret_cast<float4*>(vs + (size_t)j * 8) = float4{0.f, 0.f, 0.f, 0.f};
-        *reinterpret_cast<float4*>(vs + (size_t)j * 8 + 4) = float4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-  }
+  if (kt != nullptr) fill_from_tables<HD>(vs, kts, LS, kt, vt, h, L, Lp, n_own, q_only, gw * 64 + lane, 128);
   __syncthreads();
   unsigned* nrm = reinterpret_cast<unsigned*>(lds + (size_t)HPW * RS + (size_t)NCT * S4 * 256) + 2 * hh;  // this head's pair, see head_norms
   head_norms<HD>(kts, qts, nrm, Lp, LS, gw * 64 + lane, 128);
-  if (kt_out != nullptr && b == 0) {  // MIXED: batch element 0 publishes its recomputed rows
-    const int tid2 = gw * 64 + lane;
-    for (int idx = tid2; idx < n_own * HD; idx += 128) {
-      const int j = idx / HD, e = idx - j * HD;
-      kt_out[(size_t)h * L * HD + idx] = kts[e * LS + j];
-      vt_out[(size_t)h * L * HD + idx] = vs[(size_t)j * 8 + e];
-    }
-  }
+  if (kt_out != nullptr && b == 0) publish_kv<HD>(vs, kts, LS, kt_out, vt_out, h, L, n_own, gw * 64 + lane, 128);
 
   __syncthreads();  // the tile norms
-  if constexpr (STAMP) st_t[4] = FFD_STAMP_T();
-  // every score of this head is within +- sqrt(max |q|^2 max |k|^2) (wave-uniform)
-  const bool head_bounded =
-      __builtin_amdgcn_ballot_w64(__uint_as_float(nrm[1]) * __uint_as_float(nrm[0]) <= T * T) != 0;
-  // ------------------------------------------------------------------ phase 2: attention (see k_attention_pk)
-  const bool xlane = half == HX;
-  constexpr int PF = 4;
-  auto load_v = [&](int r, int kbase, f32x2(&dst)[4]) {
-    const float* vr = vs + (size_t)(kbase + (r & 3) + 8 * (r >> 2)) * 8;
-    const float4 v0 = *reinterpret_cast<const float4*>(vr);
-    dst[0] = f32x2{v0.x, v0.y}, dst[1] = f32x2{v0.z, v0.w};
-    if (HD > 4) {
-      const float4 v1 = *reinterpret_cast<const float4*>(vr + 4);
-      dst[2] = f32x2{v1.x, v1.y}, dst[3] = f32x2{v1.z, v1.w};
-    } else {
-      dst[2] = f32x2{0.f, 0.f}, dst[3] = f32x2{0.f, 0.f};
-    }
-  };
-  const int QT = KT;
-  for (int qt0 = gw * QG; qt0 < QT; qt0 += 2 * QG) {
-    float qf[QG][KSX], mref[QG];
-    bool ref_on = false;  // wave-uniform: some lane of this wave carries a non-zero reference
-    bool acc_empty[QG];
-#pragma unroll
-    for (int g = 0; g < QG; ++g) acc_empty[g] = true;
-    f32x2 lsum[QG], acc[QG][HP];
-#pragma unroll
-    for (int g = 0; g < QG; ++g) {
-      const int qtile = (qt0 + g < QT) ? qt0 + g : QT - 1;
-#pragma unroll
-      for (int s = 0; s < KSX; ++s) {
-        const int e = 2 * s + half;
-        qf[g][s] = (e < HD) ? qts[e * LS + 32 * qtile + l31] : 0.f;
-      }
-      mref[g] = 0.f;
-      lsum[g] = f32x2{0.f, 0.f};
-#pragma unroll
-      for (int e = 0; e < HP; ++e) acc[g][e] = f32x2{0.f, 0.f};
-    }
-#pragma unroll 1
-    for (int t = 0; t < KT; ++t) {
-      unsigned long long st_a = 0;
-      if constexpr (STAMP) st_a = FFD_STAMP_T();
-      float kf[KSX];
-#pragma unroll
-      for (int s = 0; s < KSX; ++s) {
-        const int e = 2 * s + half;
-        kf[s] = (s < KST && (2 * s + 1 < HD || half == 0)) ? kts[e * LS + 32 * t + l31] : 0.f;
-      }
-      if (xlane) kf[SX] = 1.0f;
-      f32x16 sc[QG];
-#pragma unroll
-      for (int g = 0; g < QG; ++g) {
-        f32x16 z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < KSX; ++s) {
-          if (HD % 2 == 0 && s == SX && !ref_on) continue;  // even hd: that step carries nothing but -m_ref = 0
-          z = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s], qf[g][s], z, 0, 0, 0);
-        }
-        sc[g] = z;
-      }
-      const int kbase = 32 * t + 4 * half;
-      f32x2 vb[PF][4];
-#pragma unroll
-      for (int r = 0; r < PF; ++r) load_v(r, kbase, vb[r]);
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (STAMP) {  // the stamp follows an instruction that reads the last score tile: QK^T has retired
-        asm volatile("v_mov_b32 %0, %0" : "+v"(sc[QG - 1][15]));
-        const unsigned long long n = FFD_STAMP_T();
-        st_qk += n - st_a, st_a = n, ++st_n;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (32 * t + 32 > L) {
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-          if (32 * t + 8 * r4 + 8 > L) {  // (uniform) registers 4 r4 .. 4 r4 + 3 hold key rows 8 r4 .. 8 r4 + 7 of the tile
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-              const bool dead = kbase + rr + 8 * r4 >= L;
-#pragma unroll
-              for (int g = 0; g < QG; ++g) sc[g][4 * r4 + rr] = dead ? -INFINITY : sc[g][4 * r4 + rr];
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < QG; ++g) {
-        // while the head's bound stays within T and no lane of the wave uses a reference, nothing below can trigger
-        if (ref_on || !head_bounded) {
-        float bm = __builtin_fmaxf(__builtin_fmaxf(sc[g][0], sc[g][1]), sc[g][2]);
-#pragma unroll
-        for (int r = 3; r < 15; r += 2) bm = __builtin_fmaxf(__builtin_fmaxf(bm, sc[g][r]), sc[g][r + 1]);
-        bm = __builtin_fmaxf(bm, sc[g][15]);
-        const float bmx = fmaxf(bm, __shfl_xor(bm, 32));
-        // m_ref starts at 0 and usually stays there: |scores| <= 64 (log2 domain) neither overflow nor lose the row
-        // to underflow, and the factor 2^-m_ref cancels in the normalisation whatever it is.
-        const bool first = acc_empty[g];  // nothing accumulated yet: this is the row's first key tile
-        const bool refresh = first ? (fabsf(bmx) > T) : (bmx > T);
-        if (__builtin_amdgcn_ballot_w64(refresh) != 0) ref_on = true;
-        if (refresh) {
-          const float delta = bmx;
-          mref[g] += delta;
-          if (!first) {
-            const float corr = __builtin_amdgcn_exp2f(-delta);
-            lsum[g] *= corr;
-#pragma unroll
-            for (int e = 0; e < HP; ++e) acc[g][e] *= corr;
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sc[g][r] -= delta;
-          if (xlane) qf[g][SX] = -mref[g];
-        }
-        }
-        acc_empty[g] = false;
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const float p0 = __builtin_amdgcn_exp2f(sc[g][r]);
-          const float p1 = __builtin_amdgcn_exp2f(sc[g][r + 1]);
-          sc[g][r] = p0;
-          sc[g][r + 1] = p1;
-          lsum[g] += f32x2{p0, p1};
-        }
-      }
-      if constexpr (STAMP) {
-        __builtin_amdgcn_sched_barrier(0);
-        const unsigned long long n = FFD_STAMP_T();
-        st_sm += n - st_a, st_a = n;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        f32x2 vv[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) vv[e] = vb[r % PF][e];
-#pragma unroll
-        for (int g = 0; g < QG; ++g) {
-          const f32x2 pp = f32x2{sc[g][r & ~1], sc[g][(r & ~1) + 1]};  // (adjacent registers of the accumulator)
-#pragma unroll
-          for (int e = 0; e < HP; ++e) acc[g][e] = (r & 1) ? pk_fma_hi(pp, vv[e], acc[g][e]) : pk_fma_lo(pp, vv[e], acc[g][e]);
-        }
-        if (r + PF < 16) {
-          load_v(r + PF, kbase, vb[r % PF]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      if constexpr (STAMP) {
-        __builtin_amdgcn_sched_barrier(0);
-        st_pv += FFD_STAMP_T() - st_a;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if constexpr (STAMP) st_t[5] = FFD_STAMP_T();
-#pragma unroll
-    for (int g = 0; g < QG; ++g) {
-      float l = lsum[g].x + lsum[g].y;
-      l += __shfl_xor(l, 32);
-      const float inv = __builtin_amdgcn_rcpf(l);  // (1 ulp; the IEEE division sequence is ten vector instructions per q-tile)
-      const int q = 32 * (qt0 + g) + l31;
-      float o[2 * HP];
-#pragma unroll
-      for (int e = 0; e < HP; ++e) {
-        float a0 = acc[g][e].x, a1 = acc[g][e].y;
-        a0 += __shfl_xor(a0, 32);
-        a1 += __shfl_xor(a1, 32);
-        o[2 * e] = a0 * inv, o[2 * e + 1] = a1 * inv;
-      }
-      if (half == 0 && q < L && qt0 + g < QT) {
-        float* orow = out + ((size_t)b * L + q) * D + h * HD;
-#pragma unroll
-        for (int e = 0; e < HD; ++e) orow[e] = o[e];
-      }
-    }
-  }
-  if constexpr (STAMP) {
-    if (lane == 0 && stamp != nullptr) {
-      unsigned long long* r = stamp + ((size_t)blockIdx.x * NW + wave) * 16;
-      st_t[6] = FFD_STAMP_T();
-#pragma unroll
-      for (int i = 0; i < 7; ++i) r[i] = st_t[i];
-      r[7] = st_qk, r[8] = st_sm, r[9] = st_pv, r[10] = st_n, r[11] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));
-      r[12] = __builtin_amdgcn_s_memrealtime();
-    }
-  }
+  if constexpr (STAMP) st.t[4] = FFD_STAMP_T();
+  attend_qtiles<HD, QG, STAMP, true, LS>((lds_f32*)vs, (lds_f32*)kts, (lds_f32*)qts, LS, gw * QG, 2 * QG, KT, 0, KT,
+                                         head_bounded<HD>(nrm), L, out + (size_t)b * L * D + h * HD, D, st);
+  if constexpr (STAMP) st.write(stamp, NW);
 }
 
 template <int D, int HD, int HPW, int QG, int NCT, bool QO>
 static hipError_t launch_mh_t(const float* x, const float* awp, const float* kt, const float* vt, float* kt_out,
                               float* vt_out, float* out, int B, int L, int n_own, int q_only, hipStream_t s,
                               unsigned long long* stamp) {
-  constexpr int KST = (HD + 1) / 2;
   constexpr int S4 = (D + 15) / 16;
   const int KT = (L + 31) / 32;
-  const size_t lds = ((size_t)HPW * (64 * QG + 4) * (8 + 4 * KST) + (size_t)NCT * S4 * 256 + (size_t)HPW * 2) * sizeof(float);
+  const size_t lds = (HPW * HeadDims<HD>::floats(64 * QG + 4) + (size_t)NCT * S4 * 256 + (size_t)HPW * 2) * sizeof(float);
   if (cdiv(2 * KT, 2 * HPW) > 3 || cdiv(KT, 2) > QG) return hipErrorInvalidValue;  // <= 3 token tiles, one q-group per wave
   if constexpr (D == 72 && HD == 6) {  // (the stamped twin exists for the headline shape only)
     if (stamp != nullptr) {
@@ -1161,9 +1003,8 @@ template <int D, int HD, int QG, int NCT>
 static hipError_t launch_t(const float* x, const float* awp, const float* kt, const float* vt, float* kt_out,
                            float* vt_out, float* out, int B, int L, int n_own, int q_only, hipStream_t s,
                            unsigned long long* stamp = nullptr) {
-  constexpr int KST = (HD + 1) / 2;
   const int KT = (L + 31) / 32;
-  const size_t lds = ((size_t)(KT * 32 + 4) * (8 + 4 * KST) + (size_t)2 * KT) * sizeof(float);
+  const size_t lds = (HeadDims<HD>::floats(KT * 32 + 4) + (size_t)2 * KT) * sizeof(float);
   int nwaves = cdiv(KT, QG);
   if (nwaves > 4) nwaves = 4;
   if (cdiv(2 * KT, nwaves) > 8) return hipErrorInvalidValue;  // the projection loop is unrolled for <= 8 token tiles per wave
@@ -1184,11 +1025,11 @@ static hipError_t launch_t(const float* x, const float* awp, const float* kt, co
 template <int D, int HD, int NCT, bool KVQ = false>
 static hipError_t launch_split_t(const float* x, const float* awp, const float* kt, const float* vt, float* kt_out,
                                  float* vt_out, float* out, int B, int L, int n_own, int q_only, int kspl, hipStream_t s) {
-  constexpr int KST = (HD + 1) / 2, HP = (HD + 1) / 2;
   const int KT = (L + 31) / 32;
   if (cdiv(2 * KT, 4) > 8 || (kspl != 1 && kspl != 2 && kspl != 4)) return hipErrorInvalidValue;
   const int qsplit = cdiv(KT, 4 / kspl);
-  const size_t lds = ((size_t)(KT * 32 + 4) * (8 + 4 * KST) + (size_t)4 * 32 * (2 + 2 * HP) + (size_t)2 * KT) * sizeof(float);
+  const size_t lds =
+      (HeadDims<HD>::floats(KT * 32 + 4) + (size_t)4 * 32 * (2 + 2 * HeadDims<HD>::HP) + (size_t)2 * KT) * sizeof(float);
   hipLaunchKernelGGL((k_qkv_attention<D, HD, 1, NCT, true, false, KVQ>), dim3(B * (D / HD) * qsplit), dim3(256), lds, s, x, awp, kt,
                      vt, kt_out, vt_out, out, B, L, n_own, q_only, qsplit, kspl, (unsigned long long*)nullptr);
   return hipGetLastError();
