@@ -215,3 +215,51 @@ ROUND4_TRAJ_CASES = [
     dict(name="traj_ecg_b50_cache_12", **_ECG, sde="vp", sde_kwargs=VP, fourier=True, B=50, num_samples=50, N=12,
          use_cache=True, cache_kwargs={}, wseed=42, zseed=154),
 ]
+
+
+# ---- the reference's other datamodules (g15) -------------------------------------------------------------------------
+# Their (L, C) reach the channel-count branches no shape above does: C > 8 (generic embedding), 9 <= C <= 16 (the upper
+# lane quads of the MFMA unembedding), C > 16 (generic unembedding, unfused sampling tail), and non-power-of-two FFT
+# slabs too large for one workgroup's LDS (channel groups).
+_NASDAQ = dict(L=252, C=5)     # datamodules.py:406-410: (252, 6) tensors, the last feature (volume) dropped
+_MIMIC = dict(L=24, C=40)      # cmd/conf/datamodule/mimiciii.yaml: n_feats 40, 24 hourly steps
+# US-droughts (datamodules.py:530-538) keeps the features of the preprocessed tensor other than {4, 5, 6, 7, 9}.  That
+# tensor holds every column of the dataset's CSV that has no missing value in 2011 (preprocessing.py:353-395); the
+# reference itself does not fix how many there are.  The published CSV has 18 daily meteorological columns (the weekly
+# drought score is NaN on most days and is dropped); in pivot_table's sorted order {4, 5, 6, 7, 9} are T2MDEW, T2MWET,
+# T2M_MAX, T2M_MIN and TS, the "high correlation with T2M" of the comment there, hence C = 18 - 5 = 13.
+# L = 365: one year (end - start date).
+_DROUGHTS = dict(L=365, C=13)
+_TF72 = dict(kind="transformer", d=72, H=12, NL=10)    # cmd/conf/score_model/default.yaml
+_LSTM72 = dict(kind="lstm", d=72, H=1, NL=10)          # cmd/conf/score_model/lstm.yaml
+
+DATASET_MODEL_CASES = [
+    dict(name="nasdaq_tf", **_TF72, **_NASDAQ, sde="vp", sde_kwargs=VP, fourier=True, B=3, wseed=161, xseed=171,
+         t_values=[1.0, 0.35]),
+    dict(name="nasdaq_lstm", **_LSTM72, **_NASDAQ, sde="vp", sde_kwargs=VP, fourier=True, B=3, wseed=162, xseed=172,
+         t_values=[0.8, 0.1]),
+    dict(name="mimic_tf", **_TF72, **_MIMIC, sde="vp", sde_kwargs=VP, fourier=True, B=3, wseed=163, xseed=173,
+         t_values=[0.9, 0.2]),
+    dict(name="mimic_lstm", **_LSTM72, **_MIMIC, sde="vp", sde_kwargs=VP, fourier=True, B=3, wseed=164, xseed=174,
+         t_values=[1.0, 0.45]),
+    # (B = 2 at the largest shape keeps g15 small)
+    dict(name="droughts_tf", **_TF72, **_DROUGHTS, sde="vp", sde_kwargs=VP, fourier=True, B=2, wseed=165, xseed=175,
+         t_values=[0.7, 0.05]),
+    dict(name="droughts_lstm", **_LSTM72, **_DROUGHTS, sde="vp", sde_kwargs=VP, fourier=True, B=2, wseed=166, xseed=176,
+         t_values=[1.0, 0.6]),
+]
+DATASET_TRAJ_CASES = [
+    dict(name="traj_nasdaq_tf_vp", **_TF72, **_NASDAQ, sde="vp", sde_kwargs=VP, fourier=True, B=3, num_samples=3, N=40,
+         use_cache=False, wseed=161, zseed=181),
+    dict(name="traj_nasdaq_lstm_ve", **_LSTM72, **_NASDAQ, sde="ve", sde_kwargs=VE, fourier=True, B=3, num_samples=3,
+         N=30, use_cache=False, wseed=162, zseed=182),
+    # two batches: the second one runs on the first one's tables (Q3)
+    dict(name="traj_mimic_tf_ve_cache", **_TF72, **_MIMIC, sde="ve", sde_kwargs=VE, fourier=True, B=2, num_samples=4,
+         N=40, use_cache=True, cache_kwargs={}, wseed=163, zseed=183),
+    dict(name="traj_mimic_lstm_vp", **_LSTM72, **_MIMIC, sde="vp", sde_kwargs=VP, fourier=True, B=3, num_samples=3,
+         N=30, use_cache=False, wseed=164, zseed=184),
+    dict(name="traj_droughts_tf_vp_cache", **_TF72, **_DROUGHTS, sde="vp", sde_kwargs=VP, fourier=True, B=2,
+         num_samples=2, N=36, use_cache=True, cache_kwargs={}, wseed=165, zseed=185),
+    dict(name="traj_droughts_lstm_ve", **_LSTM72, **_DROUGHTS, sde="ve", sde_kwargs=VE, fourier=True, B=2,
+         num_samples=2, N=30, use_cache=False, wseed=166, zseed=186),
+]

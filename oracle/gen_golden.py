@@ -242,10 +242,41 @@ def gen_fresca2d(ns) -> None:
     np.savez_compressed(os.path.join(OUT, "g14_fresca2d.npz"), **g)
 
 
+def gen_datasets(ns) -> None:
+    """G15: the NASDAQ, MIMIC-III and US-droughts shapes with the default transformer and the LSTM backbone: score
+    evaluations at two t, and short trajectories with injected noise, each with the timestep grid used."""
+    g = {}
+    for c in cases.DATASET_MODEL_CASES:
+        m, sch = make_model(ns, c)
+        B, L, C = c["B"], c["L"], c["C"]
+        x = torch.from_numpy(next(synthetic.noise_stream((B, L, C), 1, c["xseed"])))
+        with torch.no_grad():
+            for tv in c["t_values"]:
+                t = torch.full((B,), tv, dtype=torch.float32)
+                g[f"{c['name']}_score_t{tv}"] = m(ns.DiffusableBatch(X=x, y=None, timesteps=t)).numpy()
+        print(c["name"], flush=True)
+    for c in cases.DATASET_TRAJ_CASES:
+        m, sch = make_model(ns, c)
+        B, L, C, N = c["B"], c["L"], c["C"], c["N"]
+        nb = max(1, c["num_samples"] // B)
+        stream = synthetic.noise_stream((B, L, C), nb * (N + 1), c["zseed"])
+        sampler = ns.DiffusionSampler(score_model=m, sample_batch_size=B, use_cache=c["use_cache"],
+                                      cache_kwargs=dict(c.get("cache_kwargs", {})))
+        with injected_noise(stream):
+            out = sampler.sample(num_samples=c["num_samples"], num_diffusion_steps=N)
+        g[c["name"]] = out.numpy()
+        g[c["name"] + "_ts"] = sch.timesteps.numpy().copy()
+        print(c["name"], out.shape, float(out.abs().max()), flush=True)
+    np.savez_compressed(os.path.join(OUT, "g15_datasets.npz"), **g)
+
+
 def main() -> None:
     os.makedirs(OUT, exist_ok=True)
     ns = import_reference()
     torch.set_num_threads(8)
+    if "--only-datasets" in sys.argv:  # just G15
+        gen_datasets(ns)
+        return
     if "--only-fresca2d" in sys.argv:  # just G14
         gen_fresca2d(ns)
         return
@@ -389,6 +420,7 @@ def main() -> None:
     gen_extra_traj(ns)
     gen_round2(ns)
     gen_round4(ns)
+    gen_datasets(ns)
 
     with open(os.path.join(OUT, "META.txt"), "w") as f:
         f.write("generated by oracle/gen_golden.py from the unmodified reference at /root/reference\n")

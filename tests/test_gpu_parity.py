@@ -1876,3 +1876,309 @@ def test_failed_workspace_growth_leaves_no_stale_capacity(ffd):
                 assert torch.equal(out, full)
             m, _ = make_model(ffd, c)  # a fresh context for the next injection point
             small = m(batch_of(x[:3], 0.5)).cpu()
+
+
+# ------------------------------------------------------- the channel axis (g15) ----
+# The kernels choose their code path by the channel count C (csrc/ffd_elem.hip, ffd_api.hip, ffd_fft.hip):
+#   embedding    C <= 8: k_embed_reg (float4 x rows only at C = 4 / 8 with 16-B aligned X) | C > 8: k_embed (the
+#                transposed weight staged in LDS)
+#   unembedding  C <= 16: k_unembed_mfma, lane quad q = 0 .. 3 carries channels 4q .. 4q + 3, float4 stores where
+#                C % 4 == 0, scalar ones otherwise | C > 16: k_unembed (16 lanes per row, weight in LDS)
+#   sampling     C <= 16: the unembedding fused into the step kernel, quad or scalar Philox draws | C > 16: k_sde_step_v4
+#                (C % 4 == 0) or k_sde_step behind the unembedding
+def _channel_branches(C):
+    embed = ("reg_xvec" if C in (4, 8) else "reg") if C <= 8 else "lds"
+    if C <= 16:
+        return f"C{C}-embed_{embed}-unembed_mfma_q{(C - 1) // 4}_{'quad' if C % 4 == 0 else 'scalar'}-fused_tail"
+    return f"C{C}-embed_{embed}-unembed_generic-{'sde_step_v4' if C % 4 == 0 else 'sde_step'}"
+
+
+def _fft_channel_group(L, C):
+    """Channels per workgroup of the non-power-of-two FFT kernels (launch_dft / slab_geom): halved until the twiddle
+    table and two complex (L x CG) slabs fit in 64 KiB of LDS."""
+    CG = C
+    while CG > 1 and (L + 2 * L * CG) * 8 > 64 * 1024:
+        CG = (CG + 1) // 2
+    return CG
+
+
+def _cached_seq_vs_oracle(m, sd, c, B, tv, seed):
+    """FULL -> PURE -> MIXED against the oracle's KV table."""
+    L, C = c["L"], c["C"]
+    m.enable_caching()
+    m.cache.reset()
+    table = O.KVTable(c["NL"], L)
+    t = torch.full((B,), tv, dtype=torch.float32)
+    for j, n in enumerate([L, 0, min(10, L - 1)]):
+        xj = torch.from_numpy(next(synthetic.noise_stream((B, L, C), 1, seed + j)))
+        ref = O.score_forward(xj, t, sd, c["NL"], c["H"], table, list(range(n)))
+        got = m(batch_of(xj.cuda(), tv), recompute_tokens=set(range(n)), step=j)
+        assert rel_err(got.cpu(), ref) < TOL_SCORE, (j, n)
+    m.disable_caching()
+
+
+@pytest.mark.parametrize("c", cases.DATASET_MODEL_CASES, ids=lambda c: f"{c['name']}-{_channel_branches(c['C'])}")
+def test_dataset_model_golden(ffd, golden, c, variant):
+    """G15: the NASDAQ (252 x 5), MIMIC-III (24 x 40) and US-droughts (365 x 13) shapes with the reference's default
+    transformer and its LSTM, against the unmodified reference's scores; the transformer's cached modes against the
+    oracle at the same shapes."""
+    g = golden["g15_datasets"]
+    m, _ = make_model(ffd, c)
+    B, L, C = c["B"], c["L"], c["C"]
+    x = torch.from_numpy(next(synthetic.noise_stream((B, L, C), 1, c["xseed"]))).cuda()
+    for tv in c["t_values"]:
+        assert rel_err(m(batch_of(x, tv)).cpu(), g[f"{c['name']}_score_t{tv}"]) < TOL_SCORE, tv
+    if c["kind"] == "lstm":
+        if variant == "auto":  # the per-layer LSTM kernels at L = 24 / 252 / 365 as well
+            from fastfourierdiffusion_amd import _native as N
+
+            assert N.lib().ffd_tune(b"lstm_wave", 0) == 0
+            for tv in c["t_values"]:
+                assert rel_err(m(batch_of(x, tv)).cpu(), g[f"{c['name']}_score_t{tv}"]) < TOL_SCORE, tv
+        return
+    _cached_seq_vs_oracle(m, make_sd(c), c, B, c["t_values"][0], c["xseed"] + 100)
+
+
+@pytest.mark.parametrize("c", cases.DATASET_TRAJ_CASES, ids=lambda c: f"{c['name']}-{_channel_branches(c['C'])}")
+def test_dataset_traj_golden(ffd, golden, c):
+    """G15 trajectories with injected noise: the sampling tail at C = 5 / 13 (unembedding fused into the step kernel,
+    scalar draws) and C = 40 (k_unembed + k_sde_step_v4), against the unmodified reference."""
+    from fastfourierdiffusion_amd.sampling.sampler import DiffusionSampler
+
+    g = golden["g15_datasets"]
+    m, sch = make_model(ffd, c)
+    B, L, C, N = c["B"], c["L"], c["C"], c["N"]
+    _pin_grid(sch, g[c["name"] + "_ts"], N)
+    sampler = DiffusionSampler(m, B, use_cache=c["use_cache"], cache_kwargs=dict(c.get("cache_kwargs", {})),
+                               z_chunk_steps=16)
+    sampler.inject_noise(synthetic.noise_stream((B, L, C), max(1, c["num_samples"] // B) * (N + 1), c["zseed"]))
+    out = sampler.sample(c["num_samples"], N)
+    assert tuple(out.shape) == g[c["name"]].shape
+    err = rel_err(out, g[c["name"]])
+    assert err < TOL_TRAJ, err
+    if c["use_cache"]:
+        m.disable_caching()
+
+
+@pytest.mark.parametrize("strategy", ["energy", "spatial"])
+def test_droughts_fresca_trajectory_vs_oracle(ffd, strategy):
+    """FreSca in every step at the droughts shape: the score goes through the generic FFT in two channel groups
+    (7 + 6 of 13) and the unfused k_sde_step (C % 4 != 0), against the oracle's sampler on the same draws."""
+    from fastfourierdiffusion_amd.sampling.sampler import DiffusionSampler
+
+    c = next(c for c in cases.DATASET_MODEL_CASES if c["name"] == "droughts_tf")
+    assert _fft_channel_group(c["L"], c["C"]) == 7
+    m, _ = make_model(ffd, c)
+    sd = make_sd(c)
+    B, L, C, N = 2, c["L"], c["C"], 12
+    fk = dict(low_scale=0.9, high_scale=1.4, cutoff_ratio=0.45, cutoff_strategy=strategy)
+    sampler = DiffusionSampler(m, B, use_fresca=True, fresca_low_scale=fk["low_scale"], fresca_high_scale=fk["high_scale"],
+                               fresca_cutoff_ratio=fk["cutoff_ratio"], fresca_cutoff_strategy=strategy)
+    sampler.inject_noise(synthetic.noise_stream((B, L, C), N + 1, 187))
+    out = sampler.sample(B, N)
+    noise = (torch.from_numpy(z) for z in synthetic.noise_stream((B, L, C), N + 1, 187))
+    ref = O.sample(sd, kind="transformer", n_channels=C, max_len=L, num_layers=c["NL"], n_head=c["H"], sde="vp",
+                   sde_kwargs=cases.VP, fourier_noise_scaling=True, num_samples=B, batch_size=B, num_steps=N, noise=noise,
+                   fresca_kwargs=fk)
+    assert rel_err(out, ref) < 2 * TOL_TRAJ, rel_err(out, ref)  # (the tolerance of the sampler option matrix)
+
+
+# C: the first value past each threshold (8 -> 9, 16 -> 17) and every C % 4 on both sides of 8 and of 16
+_SWEEP_C = [5, 6, 7, 9, 12, 13, 15, 16, 17, 24, 40]
+_SWEEP_MODELS = [dict(kind="transformer", d=24, H=4, NL=2, L=23), dict(kind="transformer", d=72, H=12, NL=2, L=37),
+                 dict(kind="lstm", d=24, H=1, NL=2, L=29)]
+
+
+@pytest.mark.parametrize("C", _SWEEP_C, ids=_channel_branches)
+@pytest.mark.parametrize("base", _SWEEP_MODELS, ids=lambda b: f"{b['kind']}_d{b['d']}L{b['L']}")
+def test_channel_sweep_vs_oracle(ffd, base, C, variant):
+    """Every channel-count branch of the embedding, the unembedding and the sampling tail (see _channel_branches)
+    against the oracle: the score forward, the cached FULL -> PURE -> MIXED sequence (transformers), and with the
+    default kernels a short injected-noise trajectory (prior + 4 steps, two batches) through the sampling tail."""
+    from fastfourierdiffusion_amd.sampling.sampler import DiffusionSampler
+
+    c = dict(base, C=C, sde="vp", sde_kwargs=cases.VP, fourier=True, wseed=700 + 3 * C + base["d"] + base["L"])
+    m, _ = make_model(ffd, c)
+    sd = make_sd(c)
+    B, L, NL = 3, c["L"], c["NL"]
+    x = torch.from_numpy(next(synthetic.noise_stream((B, L, C), 1, 7100 + C)))
+    t = torch.full((B,), 0.65, dtype=torch.float32)
+    ref = O.lstm_score_forward(x, t, sd, NL) if c["kind"] == "lstm" else O.score_forward(x, t, sd, NL, c["H"])
+    assert rel_err(m(batch_of(x.cuda(), 0.65)).cpu(), ref) < TOL_SCORE
+    if c["kind"] != "lstm":
+        _cached_seq_vs_oracle(m, sd, c, B, 0.65, 7200 + C)
+    if variant != "auto":
+        return
+    N, ns = 4, 2 * B
+    sampler = DiffusionSampler(m, B)
+    sampler.inject_noise(synthetic.noise_stream((B, L, C), 2 * (N + 1), 7300 + C))
+    out = sampler.sample(ns, N)
+    noise = (torch.from_numpy(z) for z in synthetic.noise_stream((B, L, C), 2 * (N + 1), 7300 + C))
+    ref = O.sample(sd, kind=c["kind"], n_channels=C, max_len=L, num_layers=NL, n_head=c["H"], sde="vp",
+                   sde_kwargs=cases.VP, fourier_noise_scaling=True, num_samples=ns, batch_size=B, num_steps=N, noise=noise)
+    assert rel_err(out, ref) < TOL_TRAJ, rel_err(out, ref)
+
+
+# (name, model, sample offset): C = 5 / 13 take the fused tail with scalar stores and draws at an element offset
+# elem_off = offset * L * C with elem_off % 4 != 0 (115 % 4 = 3; 4745 % 4 = 1); C = 16 takes it with float4 quads in all
+# four lane quads; C = 40 has no fused form (k_unembed + k_sde_step_v4)
+_TAIL_CASES = [
+    ("C5_L23_off1", dict(kind="transformer", d=24, H=4, NL=2, L=23, C=5), 1),
+    ("C13_L365_off1", dict(kind="transformer", d=72, H=12, NL=2, L=365, C=13), 1),
+    ("C16_L20_off3", dict(kind="lstm", d=24, H=1, NL=2, L=20, C=16), 3),
+    ("C40_L24_off1", dict(kind="transformer", d=72, H=12, NL=2, L=24, C=40), 1),
+]
+
+
+@pytest.mark.parametrize("name,base,off", _TAIL_CASES, ids=[t[0] for t in _TAIL_CASES])
+def test_fused_tail_at_dataset_channel_counts(ffd, name, base, off):
+    """The fused unembedding + SDE step equals the two-kernel tail bit for bit at C = 5 / 13 / 16, with on-device
+    Philox draws at an unaligned element offset and with injected draws; at C = 40 the fused form is not planned.
+    Every form agrees with the oracle's steps on the injected draws."""
+    import ctypes as Ct
+
+    from fastfourierdiffusion_amd import _native as N
+
+    c = dict(base, sde="vp", sde_kwargs=cases.VP, fourier=True, wseed=800 + base["C"])
+    m, sch = make_model(ffd, c)
+    sd = make_sd(c)
+    ctx = m._ctx()
+    B, L, Cn, n_steps, first, n_run = 3, c["L"], c["C"], 20, 2, 4
+    assert (Cn % 4 == 0) or (off * L * Cn) % 4 != 0
+    sch.set_timesteps(n_steps)
+    ts_c = (Ct.c_float * n_steps)(*sch.timesteps.tolist())
+    x0 = torch.from_numpy(next(synthetic.noise_stream((B, L, Cn), 1, 81)))
+    zs = torch.from_numpy(np.stack(list(synthetic.noise_stream((B, L, Cn), n_run, 82))))
+    s = N.current_stream_ptr(torch.device("cuda"))
+    fl, by = Ct.c_double(), Ct.c_double()
+    res = {}
+    try:
+        for fuse in (1, 0):
+            assert ctx.lib.ffd_tune(b"fuse_tail", fuse) == 0
+            kname = ctx.lib.ffd_kernel_work(ctx.handle, N.K_SDE, B, 0, Ct.byref(fl), Ct.byref(by))
+            assert kname.startswith(b"k_unembed_mfma") == bool(fuse and Cn <= 16), kname
+            for z in (None, zs.cuda()):
+                x = x0.cuda()
+                N.check(ctx.lib.ffd_sample_batch(ctx.handle, x.data_ptr(), B, ts_c, n_steps, float(sch.step_size), first,
+                                                 n_run, 9, off, z.data_ptr() if z is not None else None, 0, 0, s),
+                        ctx.handle, "sample")
+                res[(fuse, z is None)] = x.cpu()
+    finally:
+        ctx.lib.ffd_tune(b"fuse_tail", 1)
+    for philox in (True, False):
+        assert torch.isfinite(res[(1, philox)]).all()
+        assert torch.equal(res[(1, philox)], res[(0, philox)]), philox
+    assert not torch.equal(res[(1, True)], res[(1, False)])
+    G = O.noise_scaling(L, True)
+    ts = sch.timesteps.cpu()
+    x = x0.clone()
+    for j in range(n_run):
+        tv = ts[first + j].item()
+        t = torch.full((B,), tv, dtype=torch.float32)
+        score = O.lstm_score_forward(x, t, sd, c["NL"]) if c["kind"] == "lstm" else O.score_forward(x, t, sd, c["NL"], c["H"])
+        x = O.vp_step(x, score, zs[j], tv, G, ts[0] - ts[1], **cases.VP)
+    assert rel_err(res[(1, False)], x) < TOL_TRAJ, rel_err(res[(1, False)], x)
+
+
+@pytest.mark.parametrize("L,C", [(365, 13), (24, 40)], ids=["L365_C13_fused_scalar_draws", "L24_C40_sde_step_v4"])
+def test_philox_shards_at_dataset_channel_counts(ffd, L, C):
+    """Philox draws are keyed by the global element index: uneven shards at odd sample offsets (elem_off % 4 = 1 and 3
+    at C = 13) reproduce the whole batch bit for bit.  The LSTM backbone keeps every shard's forward arithmetic that of
+    the whole batch (one 16-sample tile, per-row kernels), so any difference is the noise indexing."""
+    import ctypes as Ct
+
+    from fastfourierdiffusion_amd import _native as N
+    from fastfourierdiffusion_amd.sampling.sampler import DiffusionSampler
+
+    c = dict(kind="lstm", d=24, H=1, NL=2, L=L, C=C, sde="vp", sde_kwargs=cases.VP, fourier=True, wseed=900 + C)
+    m, _ = make_model(ffd, c)
+    fl, by = Ct.c_double(), Ct.c_double()
+    ctx = m._ctx()
+    kname = ctx.lib.ffd_kernel_work(ctx.handle, N.K_SDE, 7, 0, Ct.byref(fl), Ct.byref(by))
+    assert kname.startswith(b"k_unembed_mfma") == (C <= 16), kname
+    B, Nst = 7, 10
+
+    def run(bs, off):
+        return DiffusionSampler(m, bs, rng="philox", seed=23, sample_offset=off).sample(bs, Nst)
+
+    full = run(B, 0)
+    assert torch.isfinite(full).all()
+    shards = torch.cat([run(1, 0), run(2, 1), run(4, 3)])
+    assert torch.equal(shards, full)
+    assert not torch.equal(run(4, 2), full[3:])  # a wrong offset draws other noise
+
+
+_GROUPED_FFT = [(2, 365, 13), (3, 252, 5), (2, 24, 40), (2, 509, 9), (1, 187, 41)]
+
+
+@pytest.mark.parametrize("shape", _GROUPED_FFT,
+                         ids=lambda s: f"B{s[0]}L{s[1]}C{s[2]}-cg{_fft_channel_group(s[1], s[2])}")
+def test_generic_fft_channel_groups_vs_oracle(ffd, shape):
+    """Non-power-of-two lengths at the dataset shapes.  365 x 13, 509 x 9 and 187 x 41 exceed one workgroup's 64 KiB
+    LDS slab and run in channel groups of 7 + 6, 5 + 4 and 21 + 20 (grid .y = 2): dft / idft, FreSca (both cutoffs),
+    the frequency decomposition and the standardising wrappers against the fp64 oracle."""
+    from fastfourierdiffusion_amd.utils.fourier import dft, dft_standardize, frequency_decompose_fft, idft, unstandardize_idft
+    from fastfourierdiffusion_amd.utils.fresca import apply_fresca_to_score
+
+    B, L, C = shape
+    CG = _fft_channel_group(L, C)
+    if (L, C) in ((365, 13), (509, 9), (187, 41)):
+        assert CG < C and C % CG != 0, CG  # grouped, with an uneven last group
+    else:
+        assert CG == C
+    x, mean, std = (torch.from_numpy(a) for a in synthetic.noise_stream((B, L, C), 3, 1300 + L + C))
+    mean, std = mean[0], std[0].abs() + 0.5
+    assert rel_err(dft(x.cuda()).cpu(), O.dft(x)) < TOL_OP
+    assert rel_err(idft(x.cuda()).cpu(), O.idft(x)) < TOL_OP
+    for strat in ("energy", "spatial"):
+        y = apply_fresca_to_score(x.cuda(), low_scale=0.9, high_scale=1.4, cutoff_ratio=0.45, cutoff_strategy=strat)
+        assert rel_err(y.cpu(), O.fresca(x, 0.9, 1.4, 0.45, strat, None, None)) < TOL_OP, strat
+    lo, hi = frequency_decompose_fft(x.cuda(), 0.3)
+    olo, ohi = O.frequency_decompose(x, 0.3)
+    assert rel_err(lo.cpu(), olo) < TOL_OP and rel_err(hi.cpu(), ohi) < TOL_OP
+    assert rel_err(unstandardize_idft(x.cuda(), mean, std).cpu(), O.unstandardize_idft(x, mean, std)) < TOL_OP
+    assert rel_err(dft_standardize(x.cuda(), mean, std).cpu(), O.dft_standardize(x, mean, std)) < TOL_OP
+
+
+def _misaligned(x, off):
+    """A contiguous device copy of x at storage offset `off` floats: data_ptr() % 16 == 4 * off."""
+    buf = torch.zeros(x.numel() + 4, device="cuda")
+    v = buf[off:off + x.numel()].view(x.shape)
+    v.copy_(x)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4 * off
+    return v
+
+
+@pytest.mark.parametrize("off", [1, 2, 3])
+def test_misaligned_inputs_equal_aligned(ffd, off):
+    """X not 16-B aligned turns off the float4 x loads of the embedding (C = 4 / 8) and the float4 slab I/O of the
+    power-of-two FFT / FreSca kernels.  Those paths read and write the same values in another width and do the same
+    arithmetic (the FFT's shape-specialised 512 x 8 instance runs the same passes with the shape as a constant), so
+    the results are bit-identical; L = 187 (no float4 path) is the control.  Each also agrees with the oracle."""
+    from fastfourierdiffusion_amd.utils.fourier import dft, idft
+    from fastfourierdiffusion_amd.utils.fresca import apply_fresca_to_score
+
+    for C, kind in ((4, "transformer"), (8, "transformer"), (8, "lstm")):
+        c = dict(kind=kind, d=72, H=12, NL=2, L=50, C=C, sde="vp", sde_kwargs=cases.VP, fourier=True, wseed=1400 + C)
+        m, _ = make_model(ffd, c)
+        sd = make_sd(c)
+        x = torch.from_numpy(next(synthetic.noise_stream((3, 50, C), 1, 1450 + C)))
+        a = m(batch_of(x.cuda(), 0.4))
+        b = m(batch_of(_misaligned(x.cuda(), off), 0.4))
+        assert torch.equal(a, b), (C, kind)
+        t = torch.full((3,), 0.4, dtype=torch.float32)
+        ref = O.lstm_score_forward(x, t, sd, 2) if kind == "lstm" else O.score_forward(x, t, sd, 2, 12)
+        assert rel_err(b.cpu(), ref) < TOL_SCORE, (C, kind)
+    for L, C in ((512, 4), (512, 8), (187, 4)):
+        x = torch.from_numpy(next(synthetic.noise_stream((2, L, C), 1, 1500 + L + C)))
+        xa = x.cuda()
+        xm = _misaligned(xa, off)
+        for fn, oracle in ((dft, O.dft), (idft, O.idft)):
+            ya, ym = fn(xa), fn(xm)
+            assert torch.equal(ya, ym), (L, C, fn.__name__)
+            assert rel_err(ym.cpu(), oracle(x)) < TOL_OP
+        for strat in ("energy", "spatial"):
+            ya = apply_fresca_to_score(xa, low_scale=0.9, high_scale=1.4, cutoff_ratio=0.45, cutoff_strategy=strat)
+            ym = apply_fresca_to_score(xm, low_scale=0.9, high_scale=1.4, cutoff_ratio=0.45, cutoff_strategy=strat)
+            assert torch.equal(ya, ym), (L, C, strat)
+            assert rel_err(ym.cpu(), O.fresca(x, 0.9, 1.4, 0.45, strat, None, None)) < TOL_OP, (L, C, strat)

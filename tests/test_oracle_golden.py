@@ -358,3 +358,36 @@ def test_stock_module_form_equals_the_explicit_restatement(golden):
             a = O.score_forward_stock(x, t, sd, c["NL"], c["H"])
             assert rel_err(a, O.score_forward(x, t, sd, c["NL"], c["H"])) < TOL_KERNEL
             assert rel_err(a, golden["g5_models"][f"{name}_score_t{tv}"]) < TOL_KERNEL * 5
+
+
+# ---- G15: the NASDAQ (252 x 5), MIMIC-III (24 x 40) and US-droughts (365 x 13) shapes, transformer and LSTM ----
+@pytest.mark.parametrize("c", cases.DATASET_MODEL_CASES, ids=lambda c: c["name"])
+def test_dataset_model_golden(golden, c):
+    sd = make_sd(c)
+    B, L, C = c["B"], c["L"], c["C"]
+    x = torch.from_numpy(next(synthetic.noise_stream((B, L, C), 1, c["xseed"])))
+    for tv in c["t_values"]:
+        t = torch.full((B,), tv, dtype=torch.float32)
+        if c["kind"] == "lstm":
+            sc = O.lstm_score_forward(x, t, sd, c["NL"])
+        else:
+            sc = O.score_forward(x, t, sd, c["NL"], c["H"])
+        assert rel_err(sc, golden["g15_datasets"][f"{c['name']}_score_t{tv}"]) < TOL_KERNEL * 5, tv
+
+
+@pytest.mark.parametrize("c", cases.DATASET_TRAJ_CASES, ids=lambda c: c["name"])
+def test_dataset_traj_golden(golden, c):
+    torch.set_num_threads(8)
+    sd = make_sd(c)
+    B, L, C, N = c["B"], c["L"], c["C"], c["N"]
+    g = golden["g15_datasets"]
+    nb = max(1, c["num_samples"] // B)
+    noise = (torch.from_numpy(z) for z in synthetic.noise_stream((B, L, C), nb * (N + 1), c["zseed"]))
+    ck = c.get("cache_kwargs", {})
+    out = O.sample(sd, kind=c["kind"], n_channels=C, max_len=L, num_layers=c["NL"], n_head=c["H"], sde=c["sde"],
+                   sde_kwargs=c["sde_kwargs"], fourier_noise_scaling=c["fourier"], num_samples=c["num_samples"],
+                   batch_size=B, num_steps=N, noise=noise, use_cache=c["use_cache"], K=ck.get("K", 5), R=ck.get("R", 10),
+                   stock_modules=c["kind"] == "lstm")
+    ref = g[c["name"]]
+    assert out.shape == ref.shape
+    assert rel_err(out, ref) < TOL_TRAJ, rel_err(out, ref)
