@@ -10,6 +10,8 @@ sub-modules mirror the reference's import paths
     fdiff.utils.fourier.{dft,idft,spectral_density,frequency_decompose_*,predict_hermite} -> .utils.fourier
     fdiff.utils.dataclasses.DiffusableBatch      -> .utils.dataclasses
     fdiff.utils.extraction.{get_best_checkpoint,get_model_type,flatten_config} -> .utils.extraction
+    fdiff.sampling.metrics.{MetricCollection,SlicedWasserstein,MarginalWasserstein} -> .sampling.metrics
+    fdiff.utils.wasserstein.WassersteinDistances, fdiff.utils.tensors.check_flat_array -> .utils.{wasserstein,tensors}
 
 and ``install_as_fdiff()`` registers them under the ``fdiff.*`` names so that existing
 scripts and Hydra ``_target_`` strings resolve unchanged.  All arithmetic runs in
@@ -35,6 +37,9 @@ _MIRROR = {
     "fdiff.utils.fresca": "fastfourierdiffusion_amd.utils.fresca",
     "fdiff.utils.dataclasses": "fastfourierdiffusion_amd.utils.dataclasses",
     "fdiff.utils.extraction": "fastfourierdiffusion_amd.utils.extraction",
+    "fdiff.utils.tensors": "fastfourierdiffusion_amd.utils.tensors",
+    "fdiff.utils.wasserstein": "fastfourierdiffusion_amd.utils.wasserstein",
+    "fdiff.sampling.metrics": "fastfourierdiffusion_amd.sampling.metrics",
 }
 
 

@@ -63,6 +63,16 @@ SIGNATURES = {
     "ffd_freq_decompose": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, _P]),
     "ffd_hermite_predict": (C.c_int, [_P, C.POINTER(C.c_double), C.c_double, C.c_int, _P, C.c_int, C.c_size_t, _P]),
     "ffd_spectral_density": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_w2_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]),
+    "ffd_w2_sliced": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_w2_marginal": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_w2_prepare": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_w2_against_prepared": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P,
+                                          C.c_size_t, _P]),
+    "ffd_w2_summary": (C.c_int, [_P, C.c_int, _P, _P]),
+    "ffd_col_mean_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ffd_col_mean": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_w2_bench_kernels": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _F, _P]),
     "ffd_cache_crf_capture": (C.c_int, [_P, C.POINTER(CrfCaptureCfg)]),
     "ffd_create": (C.c_int, [C.POINTER(_P), C.POINTER(ModelDesc), C.c_int]),
     "ffd_destroy": (None, [_P]),

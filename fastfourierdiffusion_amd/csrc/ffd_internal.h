@@ -268,6 +268,20 @@ size_t fresca2d_work_floats(int B, int H, int W, int C);
 hipError_t launch_fresca2d(const float* in, float* out, float* work, int B, int H, int W, int C, float low, float high,
                            double cutoff_ratio, int strategy, hipStream_t s);
 
+// ---- sample metrics (ffd_metrics.hip): sliced / marginal Wasserstein-2 distances ----
+// P (K, N) = U (K, D) . X (N, D)^T, direction-major
+hipError_t launch_w2_project(const float* X, const float* U, float* P, int N, int D, int K, hipStream_t s);
+// P (Kb, N) = columns [f0, f0 + Kb) of X (N, D)
+hipError_t launch_w2_columns(const float* X, float* P, int N, int D, int f0, int Kb, hipStream_t s);
+// every row of `rows` (Kb, N) sorted ascending in place; scratch: Kb * N floats
+hipError_t launch_w2_sort(float* rows, float* scratch, int N, int Kb, hipStream_t s);
+// dist[k] = W2(pa row k (n sorted keys), pb row k (m sorted keys)) (/ population std of pa's row)
+hipError_t launch_w2_integral(const float* pa, int n, const float* pb, int m, int standardise, double* dist, int Kb,
+                              hipStream_t s);
+hipError_t launch_w2_summary(const double* dist, int K, double* out, hipStream_t s);
+size_t col_mean_work_doubles(int N, int D);
+hipError_t launch_col_mean(const float* X, int N, int D, float* out, double* work, hipStream_t s);
+
 // ---- the kernels of one transformer layer / of the LSTM stack at a batch (ffd_api.hip) --------------------------
 // plan_layer is the one place that orders the forms; each heuristic above answers for its own form only.
 enum CacheMode { CACHE_STD, CACHE_FULL, CACHE_PURE, CACHE_MIXED };  // cached_transformer.py:139-220

@@ -1,0 +1,165 @@
+"""``fdiff.sampling.metrics`` mirror (reference src/fdiff/sampling/metrics.py:13-217): ``Metric``,
+``MetricCollection``, ``SlicedWasserstein``, ``MarginalWasserstein`` with the reference's constructor arguments,
+result keys and key order.  Every number comes from libffd (``utils.wasserstein``): distances, their mean / max, the
+mean sample of the "dummy" baseline, ``dft`` and ``spectral_density``.  A metric object uploads its original set once
+and keeps it projected and sorted between calls (the reference re-creates the same directions from its seed at every
+call, metrics.py:113-119).  Each metric object holds its own upload (n x D fp32) and its own prepared buffer
+(directions x n fp32, not bounded by the workspace budget): a ``MetricCollection`` built from the reference's config
+holds five of each (sliced and marginal in time and frequency, marginal on the spectral density)."""
+from __future__ import annotations
+
+from abc import ABC, abstractmethod
+from functools import partial
+
+from ..utils.fourier import dft, spectral_density
+from ..utils.tensors import check_flat_array
+from ..utils.wasserstein import WassersteinDistances, _column_mean, _summary, _to_device
+
+
+class Metric(ABC):
+    def __init__(self, original_samples) -> None:
+        self.original_samples = check_flat_array(original_samples)
+        self._device_set = None
+        self._prepared: dict = {}
+
+    @abstractmethod
+    def __call__(self, other_samples) -> dict: ...
+
+    @property
+    @abstractmethod
+    def name(self) -> str: ...
+
+    @property
+    def baseline_metrics(self) -> dict:
+        return {}
+
+    def _original(self):
+        if self._device_set is None:
+            self._device_set = _to_device(self.original_samples)
+        return self._device_set
+
+    def _wd(self, original, other, cached: bool) -> WassersteinDistances:
+        wd = WassersteinDistances(original_data=original, other_data=other, seed=self.random_seed)
+        if cached and self.random_seed is not None:
+            wd._prepared = self._prepared
+        return wd
+
+    def _baseline_sets(self):
+        x = self._original()
+        n = x.shape[0]
+        return x[: n // 2], x[n // 2:], _column_mean(x)  # metrics.py:131-140
+
+
+def _stats(wd: WassersteinDistances, distances, prefix: str, suffix: str = "", save_all: bool = False) -> dict:
+    mean, mx = _summary(wd.last_distances)
+    out = {f"{prefix}_mean{suffix}": float(mean), f"{prefix}_max{suffix}": float(mx)}
+    if save_all:
+        out[f"{prefix}_all"] = distances.tolist()
+    return out
+
+
+class MetricCollection:
+    """metrics.py:28-97: every metric once on the time series and once on their ``dft``, optionally the marginal
+    metric on the spectral densities; results under ``time_`` / ``freq_`` / ``spectral_`` prefixes, sorted by key."""
+
+    def __init__(self, metrics: list, original_samples=None, include_baselines: bool = True,
+                 include_spectral_density: bool = False) -> None:
+        # only partially applied metrics are built (metrics.py:43-50); anything else in the list is skipped
+        todo = [m for m in metrics if isinstance(m, partial)]
+        assert not todo or original_samples is not None, \
+            f"Original samples must be provided for metric {todo[0] if todo else None} to be instantiated."
+        in_freq = None if original_samples is None else dft(original_samples)
+        self.metrics_time = [build(original_samples=original_samples) for build in todo]
+        self.metrics_freq = [build(original_samples=in_freq) for build in todo]
+        self.include_baselines = include_baselines
+        self.metric_spectral = None
+        if include_spectral_density:
+            self.metric_spectral = MarginalWasserstein(original_samples=spectral_density(original_samples),
+                                                       random_seed=42, save_all_distances=True)
+
+    def _pairs(self):
+        """(prefix, metric) in the reference's update order: time then freq, metric by metric."""
+        for in_time, in_freq in zip(self.metrics_time, self.metrics_freq):
+            yield "time", in_time
+            yield "freq", in_freq
+
+    def __call__(self, other_samples) -> dict:
+        views = {"time": other_samples, "freq": dft(other_samples)}
+        found: dict = {}
+        for prefix, metric in self._pairs():
+            _merge(found, prefix, metric(views[prefix]))
+        if self.include_baselines:
+            found.update(self.baseline_metrics)
+        if self.metric_spectral is not None:
+            _merge(found, "spectral", self.metric_spectral(spectral_density(other_samples)))
+        return {key: found[key] for key in sorted(found)}
+
+    @property
+    def baseline_metrics(self) -> dict:
+        found: dict = {}
+        for prefix, metric in self._pairs():
+            _merge(found, prefix, metric.baseline_metrics)
+        return found
+
+
+def _merge(into: dict, prefix: str, values: dict) -> None:
+    for key, value in values.items():
+        into[f"{prefix}_{key}"] = value
+
+
+class SlicedWasserstein(Metric):
+    """metrics.py:100-158."""
+
+    def __init__(self, original_samples, random_seed: int, num_directions: int,
+                 save_all_distances: bool = False) -> None:
+        super().__init__(original_samples=original_samples)
+        self.random_seed = random_seed
+        self.num_directions = num_directions
+        self.save_all_distances = save_all_distances
+
+    def __call__(self, other_samples) -> dict:
+        wd = self._wd(self._original(), check_flat_array(other_samples), cached=True)
+        distances = wd.sliced_distances(self.num_directions)
+        return _stats(wd, distances, "sliced_wasserstein", save_all=self.save_all_distances)
+
+    @property
+    def baseline_metrics(self) -> dict:
+        fold_a, fold_b, avg_sample = self._baseline_sets()
+        wd_self = self._wd(fold_a, fold_b, cached=False)
+        d_self = wd_self.sliced_distances(self.num_directions)
+        wd_dummy = self._wd(self._original(), avg_sample, cached=True)
+        d_dummy = wd_dummy.sliced_distances(self.num_directions)
+        return {**_stats(wd_self, d_self, "sliced_wasserstein", "_self"),
+                **_stats(wd_dummy, d_dummy, "sliced_wasserstein", "_dummy")}
+
+    @property
+    def name(self) -> str:
+        return "sliced_wasserstein"
+
+
+class MarginalWasserstein(Metric):
+    """metrics.py:161-217."""
+
+    def __init__(self, original_samples, random_seed: int, save_all_distances: bool = False) -> None:
+        super().__init__(original_samples=original_samples)
+        self.random_seed = random_seed
+        self.save_all_distances = save_all_distances
+
+    def __call__(self, other_samples) -> dict:
+        wd = self._wd(self._original(), check_flat_array(other_samples), cached=True)
+        distances = wd.marginal_distances()
+        return _stats(wd, distances, "marginal_wasserstein", save_all=self.save_all_distances)
+
+    @property
+    def baseline_metrics(self) -> dict:
+        fold_a, fold_b, avg_sample = self._baseline_sets()
+        wd_self = self._wd(fold_a, fold_b, cached=False)
+        d_self = wd_self.marginal_distances()
+        wd_dummy = self._wd(self._original(), avg_sample, cached=True)
+        d_dummy = wd_dummy.marginal_distances()
+        return {**_stats(wd_self, d_self, "marginal_wasserstein", "_self"),
+                **_stats(wd_dummy, d_dummy, "marginal_wasserstein", "_dummy")}
+
+    @property
+    def name(self) -> str:
+        return "marginal_wasserstein"

@@ -114,12 +114,18 @@ def _locate(path: str) -> Callable:
 
 def instantiate(cfg: Any, **overrides: Any) -> Any:
     """``hydra.utils.instantiate`` for the shapes the sampling configs use: ``_target_`` = dotted path of a
-    callable, every other key a keyword argument (nested ``_target_`` dicts are instantiated first),
+    callable, every other key a keyword argument (nested ``_target_`` dicts are instantiated first, also inside lists,
+    as Hydra does: ``cmd/conf/metrics/default.yaml`` holds a list of partial metrics),
     ``_partial_: true`` returns ``functools.partial`` instead of calling."""
     cfg = dict(_as_dict(cfg))
     target = cfg.pop("_target_")
     partial = bool(cfg.pop("_partial_", False))
-    kwargs = {k: (instantiate(v) if isinstance(v, dict) and "_target_" in v else v) for k, v in cfg.items()}
+    def nested(v):  # sub-configs, also inside lists (cmd/conf/metrics/default.yaml: a list of partial metrics)
+        if isinstance(v, dict) and "_target_" in v:
+            return instantiate(v)
+        return [nested(i) for i in v] if isinstance(v, list) else v
+
+    kwargs = {k: nested(v) for k, v in cfg.items()}
     kwargs.update(overrides)
     fn = _locate(target)
     return functools.partial(fn, **kwargs) if partial else fn(**kwargs)

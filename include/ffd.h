@@ -246,6 +246,52 @@ int ffd_hermite_predict(const float* history, const double* timesteps, double ta
  * callers with time-domain input run ffd_dft first (apply_dft=True). */
 int ffd_spectral_density(const float* xf, float* out, int B, int L, int C, void* stream);
 
+/* ---- sample metrics: sliced / marginal Wasserstein-2 distances (src/fdiff/utils/wasserstein.py) ----
+ * For one direction u the two sets are projected (fp32, exact-fp32 MFMA), each projection is sorted, and
+ *   W2^2 = integral over t in [0,1] of (a[floor(t n)] - b[floor(t m)])^2
+ * is summed in fp64 over the intervals of the integer grid n*m: what ot.emd2_1d returns for uniform weights
+ * (wasserstein.py:116-117,142-143).  standardise != 0 divides by the population std of orig's projection
+ * (wasserstein.py:152-160).  orig (n, D), other (m, D), dirs (K, D): fp32 device, dense row-major (float64 data is
+ * rounded to fp32 by the caller); dist_out: K doubles on the device.  Reductions are fixed-order fp64 trees without
+ * atomics: results are bit-identical from run to run and do not depend on work_bytes.  NaN input: unspecified.
+ * Context-free, stream ordered, no host synchronisation.  `work`: device scratch of
+ * ffd_w2_work_bytes(n, m, D, K, budget) bytes = kb * 4 * (n + m + max(n, m)), kb = the directions handled at once
+ * (as many as `budget_bytes` allows, at least 1, at most K): a smaller buffer means more blocks, never other results.
+ * FFD_ERR_INVALID: n, m, D, K < 1, a null pointer, or work_bytes below one direction's need;
+ * FFD_ERR_UNSUPPORTED: n, m > 2^26 or D, K > 2^20. */
+size_t ffd_w2_work_bytes(int n, int m, int D, int K, size_t budget_bytes);
+/* WassersteinDistances.sliced_distances / directional_distance (wasserstein.py:120-144,162-181):
+ * dist_out[k] = W2(orig . dirs[k], other . dirs[k]). */
+int ffd_w2_sliced(const float* orig, int n, const float* other, int m, int D, const float* dirs, int K,
+                  int standardise, double* dist_out, void* work, size_t work_bytes, void* stream);
+/* WassersteinDistances.marginal_distances / feature_distance (wasserstein.py:95-118,183-199): K = D, direction k is
+ * the k-th basis vector, i.e. column k (a transpose instead of a product). */
+int ffd_w2_marginal(const float* orig, int n, const float* other, int m, int D, int standardise, double* dist_out,
+                    void* work, size_t work_bytes, void* stream);
+/* The same in two steps, so that a Metric object (metrics.py:100-217, which re-creates its directions from one seed at
+ * every call, metrics.py:113-119) projects and sorts its original set once: prepared_out (K, n) fp32 = row k holds
+ * the ascending projections of x (n, D) on dirs[k] (dirs == NULL: K == D, row k = sorted column k; -0.0 sorts before
+ * +0.0).  work: ffd_w2_work_bytes(n, 0, D, K, budget) = kb * 4 * n bytes. */
+int ffd_w2_prepare(const float* x, int n, int D, const float* dirs, int K, float* prepared_out, void* work,
+                   size_t work_bytes, void* stream);
+/* dist_out[k] = W2(prepared row k, other . dirs[k]) with the dirs ffd_w2_prepare was given.
+ * work: ffd_w2_work_bytes(0, m, D, K, budget) = kb * 8 * m bytes. */
+int ffd_w2_against_prepared(const float* prepared, int n, const float* other, int m, int D, const float* dirs, int K,
+                            int standardise, double* dist_out, void* work, size_t work_bytes, void* stream);
+/* np.mean / np.max of the distances (metrics.py:120-123,179-182): mean_max_out[0] = mean, [1] = max (device doubles). */
+int ffd_w2_summary(const double* dist, int K, double* mean_max_out, void* stream);
+/* np.mean(original_samples, axis=0) of the "dummy" baseline (metrics.py:140,199): mean_out (D) fp32, summed in fp64
+ * over fixed slabs of 1024 rows in a fixed order (n <= 2^25).  work: ffd_col_mean_work_bytes(n, D) bytes, 8-byte aligned. */
+size_t ffd_col_mean_work_bytes(int n, int D);
+int ffd_col_mean(const float* x, int n, int D, float* mean_out, void* work, size_t work_bytes, void* stream);
+
+/* Benchmark helper for the kernels above (replaces nothing in the reference; tools/metrics_bench.py): `iters` times,
+ * after one warm-up, project x (n, D) on dirs (K, D) into rows (K, n), sort them (scratch: K * n floats), integrate
+ * against other_rows (K, m, sorted) into dist (K), and transpose columns [0, min(K, D)) of x into scratch (K <= 32768).
+ * ms_out[0..3] = mean milliseconds of the projection, the sort, the integral, the column transpose.  Synchronous. */
+int ffd_w2_bench_kernels(const float* x, int n, int D, const float* dirs, int K, float* rows, float* scratch,
+                         const float* other_rows, int m, double* dist, int iters, float* ms_out, void* stream);
+
 /* CRF capture inside ffd_sample_batch (the reference's cache.update_crf call, sampler.py:70-73):
  * on cached steps whose global step g satisfies g % every == 0 the (NL, L, d) CRF (score_models.py:181-194)
  * is written to ring slot (g / every) % n_slots; `last` receives the CRF of the last step of each
