@@ -7,7 +7,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -18,25 +17,37 @@ using namespace ffd;
 
 namespace {
 
-struct DevBuf {
-  float* p = nullptr;
-  size_t n = 0;
+// A workspace buffer on the device that only grows (ensure); cap = the elements that p holds, 0 while there are none
+template <typename T>
+struct Grow {
+  T* p = nullptr;
+  size_t cap = 0;
+};
+
+// One parameter of the state dict: its key and size, the device copy ffd_load_weight made, and the field of
+// ModelWeights / LayerWeights / LstmLayer / MlpLayer the launch sites read it from
+struct WeightSlot {
+  std::string key;
+  size_t n;
+  const float** field;
+  float* dev = nullptr;
+};
+
+struct ModelWeights {
+  const float *embed_w, *embed_b, *unembed_w, *unembed_b;
+  const float* pos;  // transformer: positional table, renormalised in place by ffd_finalize_weights
+  const float *time_W, *time_dense_w, *time_dense_b;
+};
+
+// torchvision.ops.MLP(d, [d_mlp, d]) = Sequential(Linear, ReLU, Dropout, Linear, Dropout): indices 0 and 3
+struct MlpLayer {
+  const float *w0, *b0, *w3, *b3;
 };
 
 struct LstmLayer {
   const float *wih, *whh, *bih, *bhh;
-  float *wih_p, *bsum;
+  float *wih_p = nullptr, *bsum = nullptr;
   float *ih_wpk = nullptr, *hh_wpk = nullptr, *b_wpk = nullptr;  // k_lstm_wave's fragment-ordered packs (d_model % 4 == 0, >= 16)
-};
-
-struct LayerPacked {
-  float *in_wp, *q_wp, *kv_wp, *out_wp, *w1p, *w2p, *w2r;
-  float* ring = nullptr;  // weight ring pack of the row-owning FFN
-  float* ring_op = nullptr;  // + its out-projection slot (fused form)
-  float *w1s = nullptr, *w2s = nullptr;  // bf16x3 packs of the opt-in split FFN, made on first use
-  float *aw_full = nullptr, *aw_q = nullptr;    // per-head packs of the fused in-projection + attention kernel
-  float *aw_full2 = nullptr, *aw_q2 = nullptr;  // same, per pair of heads (two-head workgroups)
-  float* aw_kvq = nullptr;                      // per head, tile 0 = k | v, tile 1 = q (the split small-batch form)
 };
 
 __global__ void k_add_vec(const float* a, const float* b, float* o, int n) {
@@ -58,20 +69,24 @@ struct ffd_ctx {
   ffd_model_desc desc{};
   int device = 0;
   std::string err;
-  std::map<std::string, DevBuf> raw;
+  std::vector<WeightSlot> weights;  // every parameter the model takes, bound once by ffd_create (bind_weights)
   std::vector<void*> owned;  // packed / table / workspace allocations
   bool finalized = false;
-  std::vector<LayerWeights> layers;
-  std::vector<LayerPacked> packed;
+  ModelWeights model{};
+  std::vector<LayerWeights> layers;  // one of the three, by desc.kind (sized by ffd_create: `weights` points into them)
   std::vector<LstmLayer> lstm;
+  std::vector<MlpLayer> mlp;
   float* G_dev = nullptr;
   std::vector<float> G_host;
-  // workspace
-  int ws_B = 0;
-  float *h0 = nullptr, *h1 = nullptr, *qkv = nullptr, *attn = nullptr, *score = nullptr;
-  size_t qkv_floats = 0;
-  float *temb1 = nullptr, *temb_tab = nullptr, *ts_dev = nullptr;
-  int temb_cap = 0;
+  // workspace (ensure_workspace; qkv, ffn_part and the LSTM wavefront's on first use)
+  Grow<float> h0, h1, attn, score;
+  Grow<float> qkv;      // head-major q / k / v of the two-kernel attention | LSTM gate pre-activations | MLP hidden (B, d_mlp)
+  Grow<float> temb_b;   // (B, d) per-sample time embeddings (ffd_score_forward_ts)
+  Grow<float> temb_tab, ts_dev;  // the trajectory's time embeddings (n_steps, d) and its timesteps
+  float* temb1 = nullptr;        // (d,) time embedding of a scalar-t evaluation
+  Grow<float> ffn_part;    // partial Y tiles of the small-M split FFN
+  Grow<int> lstm_prog;     // progress words of the LSTM layer wavefront
+  Grow<float> lstm_state;  // (tile, layer) state blocks of the time-chunked wavefront
   std::vector<float> ts_host;
   long weight_epoch = 0, temb_epoch = -1;
   // in-situ kernel timing (ffd_kernel_timing_*)
@@ -81,23 +96,15 @@ struct ffd_ctx {
   size_t ev_used = 0;
   float tm_ms[FFD_K_COUNT] = {0};
   int tm_n[FFD_K_COUNT] = {0};
-  float* temb_b = nullptr;  // (B, d) per-sample time embeddings (ffd_score_forward_ts)
-  int* lstm_prog = nullptr;  // progress words of the LSTM layer wavefront
-  size_t lstm_prog_ints = 0;
   int* async_err = nullptr;  // host-mapped word a kernel's timed-out wait writes (k_lstm_wave); read by check_async
-  float* lstm_state = nullptr;  // (tile, layer) state blocks of the time-chunked wavefront
-  size_t lstm_state_floats = 0;
-  float* ffn_part = nullptr;  // partial Y tiles of the small-M split FFN
   unsigned long long* lstm_trace = nullptr;  // ffd_lstm_trace: per-unit records of the next k_lstm_wave launch
   int lstm_trace_units = 0;
-  size_t ffn_part_floats = 0;
   // FreSca (sampler-level)
   bool fresca_on = false;
   bool crf_cap_on = false;
   ffd_crf_capture_cfg crf_cap{};
   ffd_fresca_cfg fcfg{};
-  float *score2 = nullptr, *fwork = nullptr;
-  int fwork_B = 0;
+  Grow<float> score2, fwork;
   // cache
   bool cache_enabled = false;
   ffd_cache_cfg ccfg{5, 10};
@@ -116,6 +123,7 @@ struct ffd_ctx {
   }
   int d() const { return desc.d_model; }
   int hd() const { return desc.d_model / desc.n_head; }
+  bool packs_made() const { return !layers.empty() && layers[0].in_wp != nullptr; }  // (transformer) by ffd_finalize_weights
   size_t table_floats() const { return (size_t)desc.num_layers * desc.n_head * desc.max_len * hd(); }
 };
 
@@ -132,38 +140,40 @@ FFD_KNOBS(FFD_KNOB_DEF, FFD_KNOB_DEF)
 #undef FFD_KNOB_DEF
 }  // namespace ffd
 
-static int dev_alloc(ffd_ctx* ctx, float** p, size_t nfloats) {
+// n elements of 4 bytes (float; int for the LSTM progress words)
+template <typename T>
+static int dev_alloc(ffd_ctx* ctx, T** p, size_t n) {
+  static_assert(sizeof(T) == sizeof(float), "the sizes in the messages are in floats");
   *p = nullptr;
   if (g_fail_alloc_after > 0 && --g_fail_alloc_after == 0)
-    return ctx->fail(FFD_ERR_NOMEM, "hipMalloc(%zu floats) failed: injected by ffd_tune(\"fail_alloc_after\")", nfloats);
-  hipError_t e = hipMalloc((void**)p, nfloats * sizeof(float) + 256);
-  if (e != hipSuccess) return ctx->fail(FFD_ERR_NOMEM, "hipMalloc(%zu floats) failed: %s", nfloats, hipGetErrorString(e));
+    return ctx->fail(FFD_ERR_NOMEM, "hipMalloc(%zu floats) failed: injected by ffd_tune(\"fail_alloc_after\")", n);
+  hipError_t e = hipMalloc((void**)p, n * sizeof(T) + 256);
+  if (e != hipSuccess) return ctx->fail(FFD_ERR_NOMEM, "hipMalloc(%zu floats) failed: %s", n, hipGetErrorString(e));
   ctx->owned.push_back(*p);
   return FFD_OK;
 }
 
-// Replace a workspace buffer by a larger one: the old allocation is released after the stream has drained (workspaces
-// grow a handful of times; without this every growth kept the old buffer until ffd_destroy -- 3.6 GB for the q/k/v
-// regions at B = 8192, L = 512).  `cap` is the capacity that guards the buffer: it reads 0 from the moment the old
-// buffer is gone until the new one exists, so a failed growth (out of memory) leaves "nothing allocated", never a
-// capacity that vouches for a freed or null pointer.  Capacities shared by several buffers (ws_B, fwork_B, temb_cap)
-// are zeroed by the caller before the first regrow and set after the last.
-template <typename CapT>
-static int dev_regrow(ffd_ctx* ctx, float** p, size_t nfloats, CapT* cap, CapT cap_value) {
-  float* old = *p;
-  if (cap) *cap = 0;
-  *p = nullptr;
+// Make a workspace buffer hold at least n elements (contents are not kept).  The old allocation is released after the
+// stream has drained (workspaces grow a handful of times; without this every growth kept the old buffer until
+// ffd_destroy -- 3.6 GB for the q/k/v regions at B = 8192, L = 512).  The capacity reads 0 from the moment the old buffer
+// is gone until the new one exists, so a failed growth (out of memory) leaves "nothing allocated", never a capacity that
+// vouches for a freed or null pointer.
+template <typename T>
+static int ensure(ffd_ctx* ctx, Grow<T>& b, size_t n) {
+  if (n <= b.cap) return FFD_OK;
+  T* old = b.p;
+  b.cap = 0;
+  b.p = nullptr;
   if (old) {
     (void)hipDeviceSynchronize();
     auto it = std::find(ctx->owned.begin(), ctx->owned.end(), (void*)old);
     if (it != ctx->owned.end()) ctx->owned.erase(it);
     (void)hipFree(old);
   }
-  int rc = dev_alloc(ctx, p, nfloats);
-  if (rc == FFD_OK && cap) *cap = cap_value;
+  int rc = dev_alloc(ctx, &b.p, n);
+  if (rc == FFD_OK) b.cap = n;
   return rc;
 }
-static int dev_regrow(ffd_ctx* ctx, float** p, size_t nfloats) { return dev_regrow<int>(ctx, p, nfloats, nullptr, 0); }
 
 // HIP event pair around a launch of kernel class `cls` while ffd_kernel_timing_begin has its bit set
 struct Timed {
@@ -356,6 +366,61 @@ int ffd_host_gate(int step, int max_len, int K, int R) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// weights
+// ---------------------------------------------------------------------------
+// Every parameter of the state dict, in the order ffd_finalize_weights reports a missing one, bound to the field the
+// launch sites read.  The one place that spells the keys.  (Runs before ffd_create has checked the shape.)
+static void bind_weights(ffd_ctx* ctx) {
+  const ffd_model_desc& m = ctx->desc;
+  const int NL = std::max(m.num_layers, 0);
+  const size_t d = m.d_model, C = m.n_channels, L = m.max_len, F = m.dim_feedforward;
+  auto bind = [&](const std::string& key, size_t n, const float** field) { ctx->weights.push_back({key, n, field}); };
+  ModelWeights& w = ctx->model;
+  if (m.kind == FFD_MODEL_TRANSFORMER) bind("pos_encoder.embedding.weight", L * d, &w.pos);
+  bind("time_encoder.W", (d + 1) / 2, &w.time_W);
+  bind("time_encoder.dense.weight", d * d, &w.time_dense_w);
+  bind("time_encoder.dense.bias", d, &w.time_dense_b);
+  const size_t io = m.kind == FFD_MODEL_MLP ? L * C : C;  // the MLP embeds the flattened series (score_models.py:392-397)
+  bind("embedder.weight", d * io, &w.embed_w);
+  bind("embedder.bias", d, &w.embed_b);
+  bind("unembedder.weight", io * d, &w.unembed_w);
+  bind("unembedder.bias", io, &w.unembed_b);
+  if (m.kind == FFD_MODEL_TRANSFORMER) ctx->layers.resize(NL);
+  else if (m.kind == FFD_MODEL_MLP) ctx->mlp.resize(NL);
+  else ctx->lstm.resize(NL);
+  for (int i = 0; i < NL; ++i) {
+    const std::string s = (m.kind == FFD_MODEL_TRANSFORMER ? "backbone.layers." : "backbone.") + std::to_string(i) + ".";
+    if (m.kind == FFD_MODEL_TRANSFORMER) {
+      LayerWeights& l = ctx->layers[i];
+      bind(s + "self_attn.in_proj_weight", 3 * d * d, &l.in_w);
+      bind(s + "self_attn.in_proj_bias", 3 * d, &l.in_b);
+      bind(s + "self_attn.out_proj.weight", d * d, &l.out_w);
+      bind(s + "self_attn.out_proj.bias", d, &l.out_b);
+      bind(s + "linear1.weight", F * d, &l.w1);
+      bind(s + "linear1.bias", F, &l.b1);
+      bind(s + "linear2.weight", d * F, &l.w2);
+      bind(s + "linear2.bias", d, &l.b2);
+      bind(s + "norm1.weight", d, &l.n1w);
+      bind(s + "norm1.bias", d, &l.n1b);
+      bind(s + "norm2.weight", d, &l.n2w);
+      bind(s + "norm2.bias", d, &l.n2b);
+    } else if (m.kind == FFD_MODEL_MLP) {
+      MlpLayer& l = ctx->mlp[i];
+      bind(s + "0.weight", F * d, &l.w0);
+      bind(s + "0.bias", F, &l.b0);
+      bind(s + "3.weight", d * F, &l.w3);
+      bind(s + "3.bias", d, &l.b3);
+    } else {
+      LstmLayer& l = ctx->lstm[i];
+      bind(s + "weight_ih_l0", 4 * d * d, &l.wih);
+      bind(s + "weight_hh_l0", 4 * d * d, &l.whh);
+      bind(s + "bias_ih_l0", 4 * d, &l.bih);
+      bind(s + "bias_hh_l0", 4 * d, &l.bhh);
+    }
+  }
+}
+
 int ffd_create(ffd_ctx** out, const ffd_model_desc* desc, int device) {
   if (!out || !desc) return FFD_ERR_INVALID;
   *out = nullptr;
@@ -364,6 +429,7 @@ int ffd_create(ffd_ctx** out, const ffd_model_desc* desc, int device) {
   ctx->device = device;
   *out = ctx;  // returned even on failure so the caller can read the message
   const ffd_model_desc& m = ctx->desc;
+  bind_weights(ctx);
   if (m.n_channels < 1 || m.max_len < 1 || m.num_layers < 1)
     return ctx->fail(FFD_ERR_INVALID, "bad shape: C=%d L=%d NL=%d", m.n_channels, m.max_len, m.num_layers);
   if (m.kind == FFD_MODEL_MLP) {
@@ -411,81 +477,26 @@ int ffd_create(ffd_ctx** out, const ffd_model_desc* desc, int device) {
 void ffd_destroy(ffd_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
-  for (auto& kv : ctx->raw) (void)hipFree(kv.second.p);
+  for (WeightSlot& w : ctx->weights) (void)hipFree(w.dev);
   for (void* p : ctx->owned) (void)hipFree(p);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
   if (ctx->async_err) (void)hipHostFree(ctx->async_err);
   delete ctx;
 }
 
-// ---------------------------------------------------------------------------
-// weights
-// ---------------------------------------------------------------------------
-static void expected_weights(const ffd_model_desc& m, std::vector<std::pair<std::string, size_t>>& out) {
-  const size_t d = m.d_model, C = m.n_channels, L = m.max_len, F = m.dim_feedforward;
-  if (m.kind == FFD_MODEL_TRANSFORMER) out.push_back({"pos_encoder.embedding.weight", L * d});
-  out.push_back({"time_encoder.W", (d + 1) / 2});
-  out.push_back({"time_encoder.dense.weight", d * d});
-  out.push_back({"time_encoder.dense.bias", d});
-  const size_t io = m.kind == FFD_MODEL_MLP ? L * C : C;  // the MLP embeds the flattened series (score_models.py:392-397)
-  out.push_back({"embedder.weight", d * io});
-  out.push_back({"embedder.bias", d});
-  out.push_back({"unembedder.weight", io * d});
-  out.push_back({"unembedder.bias", io});
-  for (int i = 0; i < m.num_layers; ++i) {
-    char p[64];
-    if (m.kind == FFD_MODEL_TRANSFORMER) {
-      snprintf(p, sizeof p, "backbone.layers.%d.", i);
-      std::string s(p);
-      out.push_back({s + "self_attn.in_proj_weight", 3 * d * d});
-      out.push_back({s + "self_attn.in_proj_bias", 3 * d});
-      out.push_back({s + "self_attn.out_proj.weight", d * d});
-      out.push_back({s + "self_attn.out_proj.bias", d});
-      out.push_back({s + "linear1.weight", F * d});
-      out.push_back({s + "linear1.bias", F});
-      out.push_back({s + "linear2.weight", d * F});
-      out.push_back({s + "linear2.bias", d});
-      out.push_back({s + "norm1.weight", d});
-      out.push_back({s + "norm1.bias", d});
-      out.push_back({s + "norm2.weight", d});
-      out.push_back({s + "norm2.bias", d});
-    } else if (m.kind == FFD_MODEL_MLP) {
-      // torchvision.ops.MLP(d, [d_mlp, d]) = Sequential(Linear, ReLU, Dropout, Linear, Dropout): indices 0 and 3
-      snprintf(p, sizeof p, "backbone.%d.", i);
-      std::string s(p);
-      out.push_back({s + "0.weight", F * d});
-      out.push_back({s + "0.bias", F});
-      out.push_back({s + "3.weight", d * F});
-      out.push_back({s + "3.bias", d});
-    } else {
-      snprintf(p, sizeof p, "backbone.%d.", i);
-      std::string s(p);
-      out.push_back({s + "weight_ih_l0", 4 * d * d});
-      out.push_back({s + "weight_hh_l0", 4 * d * d});
-      out.push_back({s + "bias_ih_l0", 4 * d});
-      out.push_back({s + "bias_hh_l0", 4 * d});
-    }
-  }
-}
-
 int ffd_load_weight(ffd_ctx* ctx, const char* name, const float* data, size_t n) {
   if (!ctx) return FFD_ERR_INVALID;
   if (!name || !data) return ctx->fail(FFD_ERR_INVALID, "ffd_load_weight: null argument");
-  std::vector<std::pair<std::string, size_t>> exp;
-  expected_weights(ctx->desc, exp);
-  size_t want = 0;
-  for (auto& kv : exp)
-    if (kv.first == name) want = kv.second;
-  if (!want) return ctx->fail(FFD_ERR_INVALID, "unexpected parameter '%s' for this model", name);
-  if (want != n) return ctx->fail(FFD_ERR_INVALID, "parameter '%s': got %zu floats, expected %zu", name, n, want);
+  auto w = std::find_if(ctx->weights.begin(), ctx->weights.end(), [&](const WeightSlot& v) { return v.key == name; });
+  if (w == ctx->weights.end()) return ctx->fail(FFD_ERR_INVALID, "unexpected parameter '%s' for this model", name);
+  if (w->n != n) return ctx->fail(FFD_ERR_INVALID, "parameter '%s': got %zu floats, expected %zu", name, n, w->n);
   HIPCHECK(hipSetDevice(ctx->device));
-  DevBuf& b = ctx->raw[name];
-  if (!b.p) {
-    hipError_t e = hipMalloc((void**)&b.p, n * sizeof(float) + 256);
+  if (!w->dev) {
+    hipError_t e = hipMalloc((void**)&w->dev, n * sizeof(float) + 256);
     if (e != hipSuccess) return ctx->fail(FFD_ERR_NOMEM, "hipMalloc for '%s' failed: %s", name, hipGetErrorString(e));
-    b.n = n;
+    *w->field = w->dev;
   }
-  HIPCHECK(hipMemcpy(b.p, data, n * sizeof(float), hipMemcpyDefault));
+  HIPCHECK(hipMemcpy(w->dev, data, n * sizeof(float), hipMemcpyDefault));
   ctx->finalized = false;
   return FFD_OK;
 }
@@ -493,104 +504,64 @@ int ffd_load_weight(ffd_ctx* ctx, const char* name, const float* data, size_t n)
 int ffd_finalize_weights(ffd_ctx* ctx) {
   if (!ctx) return FFD_ERR_INVALID;
   const ffd_model_desc& m = ctx->desc;
-  std::vector<std::pair<std::string, size_t>> exp;
-  expected_weights(m, exp);
-  for (auto& kv : exp)
-    if (!ctx->raw.count(kv.first)) return ctx->fail(FFD_ERR_STATE, "missing parameter '%s'", kv.first.c_str());
+  for (const WeightSlot& w : ctx->weights)
+    if (!w.dev) return ctx->fail(FFD_ERR_STATE, "missing parameter '%s'", w.key.c_str());
   HIPCHECK(hipSetDevice(ctx->device));
   const int d = m.d_model, F = m.dim_feedforward;
-  auto W = [&](const std::string& k) { return ctx->raw[k].p; };
   hipStream_t s = nullptr;
   if (m.kind == FFD_MODEL_TRANSFORMER) {
-    HIPCHECK(launch_renorm_rows(W("pos_encoder.embedding.weight"), m.max_len, d, sqrtf((float)d), s));
-    const bool first = ctx->packed.empty();
-    if (first) ctx->packed.resize(m.num_layers);
-    ctx->layers.resize(m.num_layers);
-    for (int i = 0; i < m.num_layers; ++i) {
-      char p[64];
-      snprintf(p, sizeof p, "backbone.layers.%d.", i);
-      std::string pre(p);
-      LayerPacked& pk = ctx->packed[i];
-      if (first) {
+    // (the one parameter the library writes: nn.Embedding(max_norm) renormalises its rows, transformer.py:13-15)
+    HIPCHECK(launch_renorm_rows(const_cast<float*>(ctx->model.pos), m.max_len, d, sqrtf((float)d), s));
+    for (LayerWeights& l : ctx->layers) {
+      if (!l.in_wp) {  // first time: the packs
         int rc;
-        if ((rc = dev_alloc(ctx, &pk.in_wp, dpack_floats(3 * d, d)))) return rc;
-        if ((rc = dev_alloc(ctx, &pk.q_wp, dpack_floats(d, d)))) return rc;
-        if ((rc = dev_alloc(ctx, &pk.kv_wp, dpack_floats(2 * d, d)))) return rc;
+        if ((rc = dev_alloc(ctx, &l.in_wp, dpack_floats(3 * d, d)))) return rc;
+        if ((rc = dev_alloc(ctx, &l.q_wp, dpack_floats(d, d)))) return rc;
+        if ((rc = dev_alloc(ctx, &l.kv_wp, dpack_floats(2 * d, d)))) return rc;
         if (qkv_attention_supported(d, d / m.n_head)) {
-          if ((rc = dev_alloc(ctx, &pk.aw_full, attn_pack_floats(d, m.n_head, 1, 0)))) return rc;
-          if ((rc = dev_alloc(ctx, &pk.aw_q, attn_pack_floats(d, m.n_head, 1, 1)))) return rc;
+          if ((rc = dev_alloc(ctx, &l.aw_full, attn_pack_floats(d, m.n_head, 1, 0)))) return rc;
+          if ((rc = dev_alloc(ctx, &l.aw_q, attn_pack_floats(d, m.n_head, 1, 1)))) return rc;
           if (attn_kvq_supported(d / m.n_head))
-            if ((rc = dev_alloc(ctx, &pk.aw_kvq, attn_pack_floats(d, m.n_head, 1, 2)))) return rc;
+            if ((rc = dev_alloc(ctx, &l.aw_kvq, attn_pack_floats(d, m.n_head, 1, 2)))) return rc;
           if (m.n_head % 2 == 0) {
-            if ((rc = dev_alloc(ctx, &pk.aw_full2, attn_pack_floats(d, m.n_head, 2, 0)))) return rc;
-            if ((rc = dev_alloc(ctx, &pk.aw_q2, attn_pack_floats(d, m.n_head, 2, 1)))) return rc;
+            if ((rc = dev_alloc(ctx, &l.aw_full2, attn_pack_floats(d, m.n_head, 2, 0)))) return rc;
+            if ((rc = dev_alloc(ctx, &l.aw_q2, attn_pack_floats(d, m.n_head, 2, 1)))) return rc;
           }
         }
-        if ((rc = dev_alloc(ctx, &pk.out_wp, dpack_floats(d, d)))) return rc;
-        if ((rc = dev_alloc(ctx, &pk.w1p, dpack_floats(F, d)))) return rc;
-        if ((rc = dev_alloc(ctx, &pk.w2p, w2pack_floats(d, F)))) return rc;
-        if ((rc = dev_alloc(ctx, &pk.w2r, w2rem_floats(d, F)))) return rc;
-        if (ffn_rows_supported(d, F))
-        {
-          if ((rc = dev_alloc(ctx, &pk.ring, ffn_ring_floats(d, F)))) return rc;
-          if ((rc = dev_alloc(ctx, &pk.ring_op, ffn_ring_oproj_floats(d)))) return rc;
+        if ((rc = dev_alloc(ctx, &l.out_wp, dpack_floats(d, d)))) return rc;
+        if ((rc = dev_alloc(ctx, &l.w1p, dpack_floats(F, d)))) return rc;
+        if ((rc = dev_alloc(ctx, &l.w2p, w2pack_floats(d, F)))) return rc;
+        if ((rc = dev_alloc(ctx, &l.w2r, w2rem_floats(d, F)))) return rc;
+        if (ffn_rows_supported(d, F)) {
+          if ((rc = dev_alloc(ctx, &l.ring, ffn_ring_floats(d, F)))) return rc;
+          if ((rc = dev_alloc(ctx, &l.ring_op, ffn_ring_oproj_floats(d)))) return rc;
         }
       }
-      float* in_w = W(pre + "self_attn.in_proj_weight");
-      HIPCHECK(launch_pack_dweight(in_w, pk.in_wp, 3 * d, d, s));
-      HIPCHECK(launch_pack_dweight(in_w, pk.q_wp, d, d, s));
-      HIPCHECK(launch_pack_dweight(in_w + (size_t)d * d, pk.kv_wp, 2 * d, d, s));
-      if (pk.aw_full) {
-        const float* in_b = W(pre + "self_attn.in_proj_bias");
-        HIPCHECK(launch_pack_attn(in_w, in_b, pk.aw_full, d, m.n_head, 1, 0, s));
-        HIPCHECK(launch_pack_attn(in_w, in_b, pk.aw_q, d, m.n_head, 1, 1, s));
-        if (pk.aw_kvq) HIPCHECK(launch_pack_attn(in_w, in_b, pk.aw_kvq, d, m.n_head, 1, 2, s));
-        if (pk.aw_full2) {
-          HIPCHECK(launch_pack_attn(in_w, in_b, pk.aw_full2, d, m.n_head, 2, 0, s));
-          HIPCHECK(launch_pack_attn(in_w, in_b, pk.aw_q2, d, m.n_head, 2, 1, s));
+      HIPCHECK(launch_pack_dweight(l.in_w, l.in_wp, 3 * d, d, s));
+      HIPCHECK(launch_pack_dweight(l.in_w, l.q_wp, d, d, s));
+      HIPCHECK(launch_pack_dweight(l.in_w + (size_t)d * d, l.kv_wp, 2 * d, d, s));
+      if (l.aw_full) {
+        HIPCHECK(launch_pack_attn(l.in_w, l.in_b, l.aw_full, d, m.n_head, 1, 0, s));
+        HIPCHECK(launch_pack_attn(l.in_w, l.in_b, l.aw_q, d, m.n_head, 1, 1, s));
+        if (l.aw_kvq) HIPCHECK(launch_pack_attn(l.in_w, l.in_b, l.aw_kvq, d, m.n_head, 1, 2, s));
+        if (l.aw_full2) {
+          HIPCHECK(launch_pack_attn(l.in_w, l.in_b, l.aw_full2, d, m.n_head, 2, 0, s));
+          HIPCHECK(launch_pack_attn(l.in_w, l.in_b, l.aw_q2, d, m.n_head, 2, 1, s));
         }
       }
-      HIPCHECK(launch_pack_dweight(W(pre + "self_attn.out_proj.weight"), pk.out_wp, d, d, s));
-      HIPCHECK(launch_pack_dweight(W(pre + "linear1.weight"), pk.w1p, F, d, s));
-      HIPCHECK(launch_pack_w2(W(pre + "linear2.weight"), pk.w2p, d, F, s));
-      HIPCHECK(launch_pack_w2rem(W(pre + "linear2.weight"), pk.w2r, d, F, s));
-      if (pk.ring) {
-        HIPCHECK(launch_pack_ffn_ring(W(pre + "linear1.weight"), W(pre + "linear1.bias"), W(pre + "linear2.weight"), pk.ring, d, F, s));
-        HIPCHECK(launch_pack_oproj_ring(W(pre + "self_attn.out_proj.weight"), pk.ring_op, d, s));
+      HIPCHECK(launch_pack_dweight(l.out_w, l.out_wp, d, d, s));
+      HIPCHECK(launch_pack_dweight(l.w1, l.w1p, F, d, s));
+      HIPCHECK(launch_pack_w2(l.w2, l.w2p, d, F, s));
+      HIPCHECK(launch_pack_w2rem(l.w2, l.w2r, d, F, s));
+      if (l.ring) {
+        HIPCHECK(launch_pack_ffn_ring(l.w1, l.b1, l.w2, l.ring, d, F, s));
+        HIPCHECK(launch_pack_oproj_ring(l.out_w, l.ring_op, d, s));
       }
-      if (pk.w1s) HIPCHECK(launch_pack_ffn_split(W(pre + "linear1.weight"), W(pre + "linear2.weight"), pk.w1s, pk.w2s, d, F, s));
-      LayerWeights& lw = ctx->layers[i];
-      lw.in_w = in_w;
-      lw.in_b = W(pre + "self_attn.in_proj_bias");
-      lw.out_w = W(pre + "self_attn.out_proj.weight");
-      lw.out_b = W(pre + "self_attn.out_proj.bias");
-      lw.w1 = W(pre + "linear1.weight");
-      lw.b1 = W(pre + "linear1.bias");
-      lw.w2 = W(pre + "linear2.weight");
-      lw.b2 = W(pre + "linear2.bias");
-      lw.n1w = W(pre + "norm1.weight");
-      lw.n1b = W(pre + "norm1.bias");
-      lw.n2w = W(pre + "norm2.weight");
-      lw.n2b = W(pre + "norm2.bias");
-      lw.in_wp = pk.in_wp;
-      lw.out_wp = pk.out_wp;
-      lw.w1p = pk.w1p;
-      lw.w2p = pk.w2p;
-      lw.w2r = pk.w2r;
-      lw.ring = pk.ring;
-      lw.ring_op = pk.ring_op;
-      lw.w1s = pk.w1s;
-      lw.w2s = pk.w2s;
+      if (l.w1s) HIPCHECK(launch_pack_ffn_split(l.w1, l.w2, l.w1s, l.w2s, d, F, s));
     }
   } else if (m.kind == FFD_MODEL_LSTM) {
-    const bool first = ctx->lstm.empty();
-    if (first) ctx->lstm.resize(m.num_layers);
-    for (int i = 0; i < m.num_layers; ++i) {
-      char p[64];
-      snprintf(p, sizeof p, "backbone.%d.", i);
-      std::string pre(p);
-      LstmLayer& l = ctx->lstm[i];
-      if (first) {
+    for (LstmLayer& l : ctx->lstm) {
+      if (!l.wih_p) {  // first time: the packs
         int rc;
         if ((rc = dev_alloc(ctx, &l.wih_p, dpack_floats(4 * d, d)))) return rc;
         if ((rc = dev_alloc(ctx, &l.bsum, 4 * d))) return rc;
@@ -600,10 +571,6 @@ int ffd_finalize_weights(ffd_ctx* ctx) {
           if ((rc = dev_alloc(ctx, &l.b_wpk, lstm_wave_bpack_floats(d)))) return rc;
         }
       }
-      l.wih = W(pre + "weight_ih_l0");
-      l.whh = W(pre + "weight_hh_l0");
-      l.bih = W(pre + "bias_ih_l0");
-      l.bhh = W(pre + "bias_hh_l0");
       HIPCHECK(launch_pack_dweight(l.wih, l.wih_p, 4 * d, d, s));
       hipLaunchKernelGGL(k_add_vec, dim3(cdiv(4 * d, 256)), dim3(256), 0, s, l.bih, l.bhh, l.bsum, 4 * d);
       HIPCHECK(hipGetLastError());
@@ -620,79 +587,76 @@ int ffd_finalize_weights(ffd_ctx* ctx) {
 // workspace
 // ---------------------------------------------------------------------------
 static int ensure_workspace(ffd_ctx* ctx, int B) {
-  if (B <= ctx->ws_B) return FFD_OK;
   const ffd_model_desc& m = ctx->desc;
   const size_t M = (size_t)B * m.max_len, d = m.d_model;
-  HIPCHECK(hipSetDevice(ctx->device));
   int rc;
-  ctx->ws_B = 0;  // (nothing vouches for these buffers until all of them exist at the new size)
-  if ((rc = dev_regrow(ctx, &ctx->h0, M * d))) return rc;
-  if ((rc = dev_regrow(ctx, &ctx->score, M * m.n_channels))) return rc;
-  if ((rc = dev_regrow(ctx, &ctx->temb_b, (size_t)B * d))) return rc;
+  if ((rc = ensure(ctx, ctx->h0, M * d))) return rc;
+  if ((rc = ensure(ctx, ctx->score, M * m.n_channels))) return rc;
+  if ((rc = ensure(ctx, ctx->temb_b, (size_t)B * d))) return rc;
   if (m.kind == FFD_MODEL_MLP) {
-    if ((rc = dev_regrow(ctx, &ctx->h1, (size_t)B * d))) return rc;                  // ping-pong of the (B, d) state
-    if ((rc = dev_regrow(ctx, &ctx->qkv, (size_t)B * m.dim_feedforward, &ctx->qkv_floats, (size_t)B * m.dim_feedforward))) return rc;  // hidden (B, d_mlp)
+    if ((rc = ensure(ctx, ctx->h1, (size_t)B * d))) return rc;                   // ping-pong of the (B, d) state
+    if ((rc = ensure(ctx, ctx->qkv, (size_t)B * m.dim_feedforward))) return rc;  // hidden (B, d_mlp)
   } else if (m.kind == FFD_MODEL_TRANSFORMER) {
-    if ((rc = dev_regrow(ctx, &ctx->h1, M * d))) return rc;
-    if ((rc = dev_regrow(ctx, &ctx->attn, M * d))) return rc;
+    if ((rc = ensure(ctx, ctx->h1, M * d))) return rc;
+    if ((rc = ensure(ctx, ctx->attn, M * d))) return rc;
   }
   // (the head-major q/k/v regions of the two-kernel attention fallback and the LSTM gate pre-activations are
-  //  allocated on first use by ensure_qkv: the default paths never touch them -- 3.6 GB at B = 8192, L = 512)
-  ctx->ws_B = B;
+  //  allocated on first use: the default paths never touch them -- 3.6 GB at B = 8192, L = 512)
   return FFD_OK;
 }
 
-static int ensure_qkv(ffd_ctx* ctx, size_t floats) {
-  if (floats <= ctx->qkv_floats) return FFD_OK;
-  return dev_regrow(ctx, &ctx->qkv, floats, &ctx->qkv_floats, floats);
-}
-
 static LayerPlan plan_of(const ffd_ctx* ctx, int B, CacheMode mode) {
-  const LayerPacked& pk = ctx->packed[0];
-  return plan_layer(ctx->desc, B, mode, PackSet{pk.aw_full != nullptr, pk.aw_full2 != nullptr, pk.aw_kvq != nullptr,
-                                                pk.ring_op != nullptr});
+  const LayerWeights& w = ctx->layers[0];  // (every layer has the same shape and packs)
+  return plan_layer(ctx->desc, B, mode,
+                    PackSet{w.aw_full != nullptr, w.aw_full2 != nullptr, w.aw_kvq != nullptr, w.ring_op != nullptr});
 }
 
-static int ensure_ffn_part(ffd_ctx* ctx, const LayerPlan& p) {
-  if (p.part_floats <= ctx->ffn_part_floats) return FFD_OK;
-  return dev_regrow(ctx, &ctx->ffn_part, p.part_floats, &ctx->ffn_part_floats, p.part_floats);
+// What a cached mode means for a layer's attention: tokens below n_own use the sample's own K/V rows; `tables`: the others
+// read the layer's K/V tables; `store`: batch element 0's recomputed rows go back into them (caching.py:326-328)
+struct CacheUse {
+  int n_own;
+  bool tables, store;
+};
+static CacheUse cache_use(CacheMode mode, int n_rec, int L) {
+  return {mode == CACHE_PURE ? 0 : mode == CACHE_MIXED ? n_rec : L, mode == CACHE_PURE || mode == CACHE_MIXED,
+          mode == CACHE_MIXED};
 }
 
-// The FFD_K_ATTN launch(es) of layer i as planned, x -> ctx->attn.  kt / vt: the layer's K/V tables to read (cached
-// modes); kt_out / vt_out: where batch element 0's recomputed rows go (MIXED).  The two-kernel form needs ensure_qkv.
-static hipError_t run_attention(const ffd_ctx* ctx, const LayerPlan& p, int i, const float* x, const float* kt,
-                                const float* vt, float* kt_out, float* vt_out, int B, int n_own, hipStream_t s,
-                                unsigned long long* stamp = nullptr) {
+// The FFD_K_ATTN launch(es) of layer weights w as planned, x -> ctx->attn.  kt / vt: the layer's K/V tables to read
+// (cached modes); kt_out / vt_out: where batch element 0's recomputed rows go (MIXED).  The two-kernel form needs
+// ctx->qkv to hold 3 M d floats.
+static hipError_t run_attention(const ffd_ctx* ctx, const LayerPlan& p, const LayerWeights& w, const float* x,
+                                const float* kt, const float* vt, float* kt_out, float* vt_out, int B, int n_own,
+                                hipStream_t s, unsigned long long* stamp = nullptr) {
   const ffd_model_desc& m = ctx->desc;
   const int L = m.max_len, d = m.d_model, H = m.n_head, hd = d / H;
-  const LayerPacked& pk = ctx->packed[i];
+  float* out = ctx->attn.p;
   if (p.attn == ATTN_FUSED) {
     // in-projection + attention in one launch: q/k/v never leave the CU (ffd_qkvattn.hip); in MIXED batch element 0's
     // workgroups also publish their recomputed K/V rows (caching.py:326-328)
-    const float* pack = p.q_only == 2 ? pk.aw_kvq
-                        : p.hpw == 2  ? (p.q_only ? pk.aw_q2 : pk.aw_full2)
-                                      : (p.q_only ? pk.aw_q : pk.aw_full);
-    return launch_qkv_attention(x, pack, p.hpw, p.q_only, kt, vt, kt_out, vt_out, ctx->attn, B, L, d, hd, n_own, p.kspl,
-                                s, stamp);
+    const float* pack = p.q_only == 2 ? w.aw_kvq
+                        : p.hpw == 2  ? (p.q_only ? w.aw_q2 : w.aw_full2)
+                                      : (p.q_only ? w.aw_q : w.aw_full);
+    return launch_qkv_attention(x, pack, p.hpw, p.q_only, kt, vt, kt_out, vt_out, out, B, L, d, hd, n_own, p.kspl, s,
+                                stamp);
   }
   if (stamp != nullptr) return hipErrorInvalidValue;
   // q / k / v regions, head-major (B,H,L,hd)
   const size_t M = (size_t)B * L;
-  float *q = ctx->qkv, *k = ctx->qkv + M * d, *v = ctx->qkv + 2 * M * d;
-  hipError_t e = launch_linear_hm(x, p.q_only ? pk.q_wp : pk.in_wp, ctx->layers[i].in_b, q, k, v, (int)M,
-                                  p.q_only ? 1 : 3, d, L, H, hd, s);
-  if (e == hipSuccess) e = launch_attention(q, k, v, kt, vt, ctx->attn, B, L, H, hd, n_own, s);
+  float *q = ctx->qkv.p, *k = q + M * d, *v = q + 2 * M * d;
+  hipError_t e = launch_linear_hm(x, p.q_only ? w.q_wp : w.in_wp, w.in_b, q, k, v, (int)M, p.q_only ? 1 : 3, d, L, H, hd, s);
+  if (e == hipSuccess) e = launch_attention(q, k, v, kt, vt, out, B, L, H, hd, n_own, s);
   if (e == hipSuccess && kt_out)  // (caching.py:326-328, cached_transformer.py:301-305)
     e = launch_kv_store(k, v, kt_out, vt_out, L, H, hd, n_own, s);
   return e;
 }
 
 // The FFD_K_FFN launch(es) of layer weights w as planned: from attn + the residual rows cur, or (p.oproj_separate) from
-// the k_linear_res_ln output in alt; the output goes to cur, or to alt where p.swap.  Partial tiles: ensure_ffn_part.
+// the k_linear_res_ln output in alt; the output goes to cur, or to alt where p.swap.  ctx->ffn_part holds p.part_floats.
 static hipError_t run_ffn(const ffd_ctx* ctx, const LayerPlan& p, const LayerWeights& w, const float* attn, float* cur,
                           float* alt, int M, hipStream_t s, unsigned long long* stamp = nullptr) {
   const int d = ctx->desc.d_model, F = ctx->desc.dim_feedforward;
-  float* P = ctx->ffn_part;
+  float* P = ctx->ffn_part.p;
   switch (p.ffn) {
     case FFN_LN_OPROJ:  // one 32- / 48-row tile per CU, out-proj + LN1 + FFN + LN2 in one launch, in place
       return stamp ? hipErrorInvalidValue : launch_oproj_ffn_ln(attn, cur, w, cur, M, d, F, p.mb, s);
@@ -739,106 +703,86 @@ static int forward_impl(ffd_ctx* ctx, const float* x, const float* temb, int tem
                         float* crf_out, int B, int n_rec, hipStream_t s, const float** hidden_out = nullptr) {
   const ffd_model_desc& m = ctx->desc;
   const int L = m.max_len, C = m.n_channels, d = m.d_model, M = B * L;
+  const ModelWeights& mw = ctx->model;
   if (m.kind == FFD_MODEL_MLP) {  // MLPScoreModule.forward, score_models.py:406-440
     const int io = L * C, F = m.dim_feedforward;
     // flatten "b t c -> b (t c)" is the memory layout already; time encoding is one (d,) vector per step
     // embedder(X) + time encoding: one (d,) vector per step (second bias), or a (B, d) table (added like a residual)
-    HIPCHECK(launch_dense(x, ctx->raw["embedder.weight"].p, ctx->raw["embedder.bias"].p, temb_stride ? nullptr : temb,
-                          temb_stride ? temb : nullptr, ctx->h0, B, d, io, 0, s));
-    float* cur = ctx->h0;
-    float* alt = ctx->h1;
-    for (int i = 0; i < m.num_layers; ++i) {
-      char p[64];
-      snprintf(p, sizeof p, "backbone.%d.", i);
-      const std::string pre(p);
-      HIPCHECK(launch_dense(cur, ctx->raw[pre + "0.weight"].p, ctx->raw[pre + "0.bias"].p, nullptr, nullptr, ctx->qkv,
-                            B, F, d, 1, s));
-      HIPCHECK(launch_dense(ctx->qkv, ctx->raw[pre + "3.weight"].p, ctx->raw[pre + "3.bias"].p, nullptr, cur, alt, B,
-                            d, F, 0, s));  // X + layer(X)
+    HIPCHECK(launch_dense(x, mw.embed_w, mw.embed_b, temb_stride ? nullptr : temb, temb_stride ? temb : nullptr,
+                          ctx->h0.p, B, d, io, 0, s));
+    float* cur = ctx->h0.p;
+    float* alt = ctx->h1.p;
+    for (const MlpLayer& l : ctx->mlp) {
+      HIPCHECK(launch_dense(cur, l.w0, l.b0, nullptr, nullptr, ctx->qkv.p, B, F, d, 1, s));
+      HIPCHECK(launch_dense(ctx->qkv.p, l.w3, l.b3, nullptr, cur, alt, B, d, F, 0, s));  // X + layer(X)
       std::swap(cur, alt);
     }
-    HIPCHECK(launch_dense(cur, ctx->raw["unembedder.weight"].p, ctx->raw["unembedder.bias"].p, nullptr, nullptr,
-                          score_out, B, io, d, 0, s));
+    HIPCHECK(launch_dense(cur, mw.unembed_w, mw.unembed_b, nullptr, nullptr, score_out, B, io, d, 0, s));
     return FFD_OK;
   }
+  float* const h0 = ctx->h0.p;
   if (m.kind == FFD_MODEL_LSTM) {
-    TIMED(FFD_K_EMBED, launch_embed(x, ctx->raw["embedder.weight"].p, ctx->raw["embedder.bias"].p, nullptr, temb,
-                                    temb_stride, ctx->h0, B, L, C, d, s));
+    TIMED(FFD_K_EMBED, launch_embed(x, mw.embed_w, mw.embed_b, nullptr, temb, temb_stride, h0, B, L, C, d, s));
     if (const LstmPlan lp = plan_lstm(m, B); lp.wave) {
       const int Bw = lp.Bw;  // samples per launch
-      const size_t need = (size_t)16 + 16 * cdiv(Bw, 16);
-      if (need > ctx->lstm_prog_ints) {
-        float* pbuf = reinterpret_cast<float*>(ctx->lstm_prog);
-        ctx->lstm_prog = nullptr;
-        if (int rc = dev_regrow(ctx, &pbuf, need, &ctx->lstm_prog_ints, need)) return rc;
-        ctx->lstm_prog = reinterpret_cast<int*>(pbuf);
-      }
+      if (int rc = ensure(ctx, ctx->lstm_prog, (size_t)16 + 16 * cdiv(Bw, 16))) return rc;
       const float *wih[64], *whh[64], *bs[64];
       for (int i = 0; i < m.num_layers; ++i) wih[i] = ctx->lstm[i].ih_wpk, whh[i] = ctx->lstm[i].hh_wpk, bs[i] = ctx->lstm[i].b_wpk;
-      const size_t need_st = lstm_wave_state_floats(Bw, d, m.num_layers);
-      if (need_st > ctx->lstm_state_floats) {
-        if (int rc = dev_regrow(ctx, &ctx->lstm_state, need_st, &ctx->lstm_state_floats, need_st)) return rc;
-      }
+      if (int rc = ensure(ctx, ctx->lstm_state, lstm_wave_state_floats(Bw, d, m.num_layers))) return rc;
       for (int b0 = 0; b0 < B; b0 += Bw) {  // (samples are independent: sub-batches of a tile per CU, one after the other)
         const int nb = B - b0 < Bw ? B - b0 : Bw;
-        TIMED(FFD_K_LSTM_REC, launch_lstm_wave(ctx->h0 + (size_t)b0 * L * d, wih, whh, bs, m.num_layers, nb, L, d,
-                                               ctx->lstm_prog, ctx->lstm_state, ctx->async_err, s, b0 == 0 ? ctx->lstm_trace : nullptr));
+        TIMED(FFD_K_LSTM_REC, launch_lstm_wave(h0 + (size_t)b0 * L * d, wih, whh, bs, m.num_layers, nb, L, d,
+                                               ctx->lstm_prog.p, ctx->lstm_state.p, ctx->async_err, s,
+                                               b0 == 0 ? ctx->lstm_trace : nullptr));
       }
     } else
-    for (int i = 0; i < m.num_layers; ++i) {
-      const LstmLayer& l = ctx->lstm[i];
-      if (int rc = ensure_qkv(ctx, (size_t)M * 4 * d)) return rc;  // gate pre-activations gx
-      TIMED(FFD_K_LSTM_GATES, launch_linear(ctx->h0, l.wih_p, l.bsum, ctx->qkv, M, 4 * d, d, 4 * d, s));
-      TIMED(FFD_K_LSTM_REC, launch_lstm_layer(ctx->h0, ctx->qkv, l.whh, B, L, d, s));
+    for (const LstmLayer& l : ctx->lstm) {
+      if (int rc = ensure(ctx, ctx->qkv, (size_t)M * 4 * d)) return rc;  // gate pre-activations gx
+      TIMED(FFD_K_LSTM_GATES, launch_linear(h0, l.wih_p, l.bsum, ctx->qkv.p, M, 4 * d, d, 4 * d, s));
+      TIMED(FFD_K_LSTM_REC, launch_lstm_layer(h0, ctx->qkv.p, l.whh, B, L, d, s));
     }
     if (hidden_out) {
-      *hidden_out = ctx->h0;
+      *hidden_out = h0;
       return FFD_OK;
     }
-    TIMED(FFD_K_UNEMBED, launch_unembed(ctx->h0, ctx->raw["unembedder.weight"].p, ctx->raw["unembedder.bias"].p,
-                                        score_out, M, C, d, s));
+    TIMED(FFD_K_UNEMBED, launch_unembed(h0, mw.unembed_w, mw.unembed_b, score_out, M, C, d, s));
     return FFD_OK;
   }
   const int H = m.n_head, hd = d / H, F = m.dim_feedforward;
-  TIMED(FFD_K_EMBED, launch_embed(x, ctx->raw["embedder.weight"].p, ctx->raw["embedder.bias"].p,
-                                  ctx->raw["pos_encoder.embedding.weight"].p, temb, temb_stride, ctx->h0, B, L, C, d, s));
+  TIMED(FFD_K_EMBED, launch_embed(x, mw.embed_w, mw.embed_b, mw.pos, temb, temb_stride, h0, B, L, C, d, s));
   const CacheMode mode = cache_mode(n_rec, L);  // cached_transformer.py:139-220
+  const CacheUse cu = cache_use(mode, n_rec, L);
   const size_t lt = (size_t)H * L * hd;  // table floats per layer
-  const int n_own = (mode == CACHE_PURE) ? 0 : (mode == CACHE_MIXED) ? n_rec : L;
-  const bool tables = (mode == CACHE_PURE || mode == CACHE_MIXED);
   // opt-in: the FFN on the bf16 matrix cores as a three-part split (ffd_ffn_split.hip); takes every batch size, so
   // that all parity cases exercise it when it is on
   if (g_ffn_split && !ffn_split_supported(d, F))
     return ctx->fail(FFD_ERR_UNSUPPORTED, "ffn_split needs d_model %% 4 == 0, d_model <= 96, dim_feedforward %% 128 == 0");
-  const LayerPlan plan = plan_of(ctx, B, mode);  // (every layer has the same shape and packs)
+  const LayerPlan plan = plan_of(ctx, B, mode);
   if (plan.attn == ATTN_TWO_KERNEL)
-    if (int rc = ensure_qkv(ctx, (size_t)M * 3 * d)) return rc;
-  if (int rc = ensure_ffn_part(ctx, plan)) return rc;
-  float* cur = ctx->h0;  // layer input / residual
-  float* alt = ctx->h1;
+    if (int rc = ensure(ctx, ctx->qkv, (size_t)M * 3 * d)) return rc;
+  if (int rc = ensure(ctx, ctx->ffn_part, plan.part_floats)) return rc;
+  float* const attn = ctx->attn.p;
+  float* cur = h0;  // layer input / residual
+  float* alt = ctx->h1.p;
   for (int i = 0; i < m.num_layers; ++i) {
-    const LayerWeights& w = ctx->layers[i];
-    const LayerPacked& pk = ctx->packed[i];
+    LayerWeights& w = ctx->layers[i];
     float* kt = ctx->kt ? ctx->kt + i * lt : nullptr;
     float* vt = ctx->vt ? ctx->vt + i * lt : nullptr;
-    TIMED(FFD_K_ATTN, run_attention(ctx, plan, i, cur, tables ? kt : nullptr, tables ? vt : nullptr,
-                                    mode == CACHE_MIXED ? kt : nullptr, mode == CACHE_MIXED ? vt : nullptr, B, n_own, s));
-    if (plan.ffn == FFN_SPLIT && pk.w1s == nullptr) {  // first use: make the packs
-      LayerPacked& pkm = ctx->packed[i];
-      if (int rc = dev_alloc(ctx, &pkm.w1s, w1split_bytes(d, F) / sizeof(float))) return rc;
-      if (int rc = dev_alloc(ctx, &pkm.w2s, w2split_bytes(d, F) / sizeof(float))) return rc;
-      HIPCHECK(launch_pack_ffn_split(w.w1, w.w2, pkm.w1s, pkm.w2s, d, F, s));
-      ctx->layers[i].w1s = pkm.w1s;
-      ctx->layers[i].w2s = pkm.w2s;
+    TIMED(FFD_K_ATTN, run_attention(ctx, plan, w, cur, cu.tables ? kt : nullptr, cu.tables ? vt : nullptr,
+                                    cu.store ? kt : nullptr, cu.store ? vt : nullptr, B, cu.n_own, s));
+    if (plan.ffn == FFN_SPLIT && w.w1s == nullptr) {  // first use: make the packs
+      if (int rc = dev_alloc(ctx, &w.w1s, w1split_bytes(d, F) / sizeof(float))) return rc;
+      if (int rc = dev_alloc(ctx, &w.w2s, w2split_bytes(d, F) / sizeof(float))) return rc;
+      HIPCHECK(launch_pack_ffn_split(w.w1, w.w2, w.w1s, w.w2s, d, F, s));
     }
     if (plan.oproj_separate)
-      TIMED(FFD_K_OUTPROJ, launch_linear_res_ln(ctx->attn, pk.out_wp, w.out_b, cur, w.n1w, w.n1b, alt, M, d, s));
-    TIMED(FFD_K_FFN, run_ffn(ctx, plan, w, ctx->attn, cur, alt, M, s));
+      TIMED(FFD_K_OUTPROJ, launch_linear_res_ln(attn, w.out_wp, w.out_b, cur, w.n1w, w.n1b, alt, M, d, s));
+    TIMED(FFD_K_FFN, run_ffn(ctx, plan, w, attn, cur, alt, M, s));
     if (plan.swap) std::swap(cur, alt);
     if (mode == CACHE_FULL) {
       // K,V of the layer OUTPUT for batch element 0 (cached_transformer.py:144-158), written
       // straight into this layer's tables: head-major (1,H,L,hd) == table layout
-      HIPCHECK(launch_linear_hm(cur, pk.kv_wp, w.in_b + d, kt, vt, nullptr, L, 2, d, L, H, hd, s));
+      HIPCHECK(launch_linear_hm(cur, w.kv_wp, w.in_b + d, kt, vt, nullptr, L, 2, d, L, H, hd, s));
     }
     if (n_rec >= 0 && crf_out)  // crf[l] = h_l[0]  (score_models.py:181-194)
       HIPCHECK(hipMemcpyAsync(crf_out + (size_t)i * L * d, cur, sizeof(float) * L * d, hipMemcpyDeviceToDevice, s));
@@ -856,8 +800,7 @@ static int forward_impl(ffd_ctx* ctx, const float* x, const float* temb, int tem
     *hidden_out = cur;
     return FFD_OK;
   }
-  TIMED(FFD_K_UNEMBED, launch_unembed(cur, ctx->raw["unembedder.weight"].p, ctx->raw["unembedder.bias"].p, score_out,
-                                      M, C, d, s));
+  TIMED(FFD_K_UNEMBED, launch_unembed(cur, mw.unembed_w, mw.unembed_b, score_out, M, C, d, s));
   return FFD_OK;
 }
 
@@ -883,163 +826,63 @@ static int check_ready(ffd_ctx* ctx, int B) {
   return FFD_OK;
 }
 
-static int temb_single(ffd_ctx* ctx, float t, hipStream_t s) {
-  HIPCHECK(launch_time_embed(nullptr, t, 1, ctx->raw["time_encoder.W"].p, ctx->raw["time_encoder.dense.weight"].p,
-                             ctx->raw["time_encoder.dense.bias"].p, ctx->temb1, ctx->desc.d_model, s));
+// temb[n][d] for the n timesteps ts on the device, or (ts == nullptr, n = 1) for the scalar t
+static int time_embed(ffd_ctx* ctx, const float* ts, float t, int n, float* temb, hipStream_t s) {
+  const ModelWeights& w = ctx->model;
+  HIPCHECK(launch_time_embed(ts, t, n, w.time_W, w.time_dense_w, w.time_dense_b, temb, ctx->desc.d_model, s));
+  return FFD_OK;
+}
+
+// What the three ffd_score_forward* entry points do once their arguments have passed: one time embedding for the batch
+// (ts == nullptr: the scalar t) or one per sample: dense(gamma(t_b)) (transformer.py:77-91)
+static int score_forward(ffd_ctx* ctx, const float* x, const float* ts, float t, float* score_out, float* crf_out, int B,
+                         int n_rec, void* stream) {
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (int rc = ensure_workspace(ctx, B)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  float* temb = ts ? ctx->temb_b.p : ctx->temb1;
+  if (int rc = time_embed(ctx, ts, ts ? 0.f : t, ts ? B : 1, temb, s)) return rc;
+  return forward_impl(ctx, x, temb, ts ? ctx->desc.d_model : 0, score_out, crf_out, B, n_rec, s);
+}
+
+// (n_recompute's range is checked by the caller: the entry points differ in where it comes among their checks)
+static int check_cached(ffd_ctx* ctx) {
+  if (ctx->desc.kind != FFD_MODEL_TRANSFORMER)
+    return ctx->fail(FFD_ERR_UNSUPPORTED, "caching is only defined for the transformer backbone (SURVEY Q9)");
+  if (!ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "cache not enabled (call ffd_cache_enable)");
   return FFD_OK;
 }
 
 int ffd_score_forward(ffd_ctx* ctx, const float* x, float t, float* score_out, int B, void* stream) {
   if (!ctx) return FFD_ERR_INVALID;
-  int rc = check_ready(ctx, B);
-  if (rc) return rc;
+  if (int rc = check_ready(ctx, B)) return rc;
   if (!x || !score_out) return ctx->fail(FFD_ERR_INVALID, "null buffer");
-  HIPCHECK(hipSetDevice(ctx->device));
-  if ((rc = ensure_workspace(ctx, B))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = temb_single(ctx, t, s))) return rc;
-  return forward_impl(ctx, x, ctx->temb1, 0, score_out, nullptr, B, -1, s);
+  return score_forward(ctx, x, nullptr, t, score_out, nullptr, B, -1, stream);
 }
 
 int ffd_score_forward_cached(ffd_ctx* ctx, const float* x, float t, float* score_out, float* crf_out, int B,
                              int n_recompute, void* stream) {
   if (!ctx) return FFD_ERR_INVALID;
-  int rc = check_ready(ctx, B);
-  if (rc) return rc;
-  if (ctx->desc.kind != FFD_MODEL_TRANSFORMER)
-    return ctx->fail(FFD_ERR_UNSUPPORTED, "caching is only defined for the transformer backbone (SURVEY Q9)");
-  if (!ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "cache not enabled (call ffd_cache_enable)");
+  if (int rc = check_ready(ctx, B)) return rc;
+  if (int rc = check_cached(ctx)) return rc;
   if (!x || !score_out) return ctx->fail(FFD_ERR_INVALID, "null buffer");
   if (n_recompute < 0 || n_recompute > ctx->desc.max_len)
     return ctx->fail(FFD_ERR_INVALID, "n_recompute=%d outside [0,%d]", n_recompute, ctx->desc.max_len);
-  HIPCHECK(hipSetDevice(ctx->device));
-  if ((rc = ensure_workspace(ctx, B))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = temb_single(ctx, t, s))) return rc;
-  return forward_impl(ctx, x, ctx->temb1, 0, score_out, crf_out, B, n_recompute, s);
+  return score_forward(ctx, x, nullptr, t, score_out, crf_out, B, n_recompute, stream);
 }
 
 int ffd_score_forward_ts(ffd_ctx* ctx, const float* x, const float* timesteps, float* score_out, float* crf_out,
                          int B, int n_recompute, void* stream) {
   if (!ctx) return FFD_ERR_INVALID;
-  int rc = check_ready(ctx, B);
-  if (rc) return rc;
+  if (int rc = check_ready(ctx, B)) return rc;
   if (!x || !timesteps || !score_out) return ctx->fail(FFD_ERR_INVALID, "null buffer");
   if (n_recompute >= 0) {
-    if (ctx->desc.kind != FFD_MODEL_TRANSFORMER)
-      return ctx->fail(FFD_ERR_UNSUPPORTED, "caching is only defined for the transformer backbone (SURVEY Q9)");
-    if (!ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "cache not enabled (call ffd_cache_enable)");
+    if (int rc = check_cached(ctx)) return rc;
     if (n_recompute > ctx->desc.max_len)
       return ctx->fail(FFD_ERR_INVALID, "n_recompute=%d outside [0,%d]", n_recompute, ctx->desc.max_len);
   }
-  HIPCHECK(hipSetDevice(ctx->device));
-  if ((rc = ensure_workspace(ctx, B))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  // one time embedding per sample: dense(gamma(t_b)) (transformer.py:77-91)
-  HIPCHECK(launch_time_embed(timesteps, 0.f, B, ctx->raw["time_encoder.W"].p, ctx->raw["time_encoder.dense.weight"].p,
-                             ctx->raw["time_encoder.dense.bias"].p, ctx->temb_b, ctx->desc.d_model, s));
-  return forward_impl(ctx, x, ctx->temb_b, ctx->desc.d_model, score_out, n_recompute >= 0 ? crf_out : nullptr, B,
-                      n_recompute >= 0 ? n_recompute : -1, s);
-}
-
-// ---------------------------------------------------------------------------
-// SDE
-// ---------------------------------------------------------------------------
-static SdeParams sde_params(int sde, double a, double b, double t, float step_size) {
-  SdeParams p{};
-  p.sde = sde;
-  if (sde == FFD_SDE_VP) {
-    const double beta = a + t * (b - a);  // sde.py:212-213
-    p.a = (float)(-0.5 * beta);
-    p.cs = (float)sqrt(beta);
-  } else {
-    const double r = b / a;
-    p.cs = (float)(a * sqrt(2.0 * log(r)) * pow(r, t));  // sde.py:143-147
-    p.a = 0.f;
-  }
-  p.dt = step_size;
-  p.sqdt = sqrtf(step_size);
-  return p;
-}
-
-int ffd_sde_step(const ffd_sde_desc* sde, float* x, const float* score, const float* G, double t, float step_size,
-                 const float* z, uint64_t seed, uint64_t sample_offset, int step, int B, int L, int C, void* stream) {
-  if (!sde || !x || !score || !G || B < 1 || L < 1 || C < 1) return FFD_ERR_INVALID;
-  if (sde->sde != FFD_SDE_VP && sde->sde != FFD_SDE_VE) return FFD_ERR_UNSUPPORTED;
-  if (!(step_size > 0.f)) return FFD_ERR_INVALID;  // sde.py:157,238 assert
-  hipError_t e = launch_sde_step(x, score, z, G, sde_params(sde->sde, sde->a, sde->b, t, step_size), seed,
-                                 sample_offset * (uint64_t)L * C, (uint32_t)step, B, L, C, (hipStream_t)stream);
-  return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
-}
-
-int ffd_prior(const ffd_sde_desc* sde, float* x, const float* z, const float* G, uint64_t seed, uint64_t sample_offset,
-              int B, int L, int C, void* stream) {
-  if (!sde || !x || !G || B < 1 || L < 1 || C < 1) return FFD_ERR_INVALID;
-  const float scale = (sde->sde == FFD_SDE_VE) ? (float)sde->b : 1.0f;
-  hipError_t e = launch_prior(x, z, G, scale, seed, sample_offset * (uint64_t)L * C, B, L, C, (hipStream_t)stream);
-  return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
-}
-
-int ffd_dft(const float* in, float* out, int B, int L, int C, void* stream) {
-  if (!in || !out || in == out || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
-  hipError_t e = launch_dft(in, out, B, L, C, 0, nullptr, nullptr, (hipStream_t)stream);
-  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
-}
-
-int ffd_idft(const float* in, float* out, int B, int L, int C, void* stream) {
-  if (!in || !out || in == out || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
-  hipError_t e = launch_dft(in, out, B, L, C, 1, nullptr, nullptr, (hipStream_t)stream);
-  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
-}
-
-int ffd_dft_standardize(const float* in, float* out, const float* mean, const float* std, int B, int L, int C,
-                        void* stream) {
-  if (!in || !out || in == out || !mean || !std || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
-  hipError_t e = launch_dft(in, out, B, L, C, 0, mean, std, (hipStream_t)stream);
-  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
-}
-
-int ffd_unstandardize_idft(const float* in, float* out, const float* mean, const float* std, int B, int L, int C,
-                           void* stream) {
-  if (!in || !out || in == out || !mean || !std || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
-  hipError_t e = launch_dft(in, out, B, L, C, 1, std, mean, (hipStream_t)stream);
-  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
-}
-
-int ffd_positional_encoding(const float* x, float* weight, float* out, int B, int L, int D, float max_norm,
-                            void* stream) {
-  if (!x || !weight || !out || B < 1 || L < 1 || D < 1) return FFD_ERR_INVALID;
-  hipStream_t s = (hipStream_t)stream;
-  // nn.Embedding(max_norm) renormalises the looked-up rows in place at every forward (transformer.py:13-15,26)
-  if (max_norm > 0.f && launch_renorm_rows_once(weight, L, D, max_norm, s) != hipSuccess) return FFD_ERR_HIP;
-  return launch_add_table(x, weight, nullptr, out, B, L, D, s) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
-}
-
-int ffd_time_encoding(const float* x, const float* timesteps, const float* W, const float* dense_w,
-                      const float* dense_b, float* temb_work, float* out, int B, int L, int D, void* stream) {
-  if (!x || !timesteps || !W || !dense_w || !dense_b || !temb_work || !out || B < 1 || L < 1 || D < 1)
-    return FFD_ERR_INVALID;
-  hipStream_t s = (hipStream_t)stream;
-  if (launch_time_embed(timesteps, 0.f, B, W, dense_w, dense_b, temb_work, D, s) != hipSuccess) return FFD_ERR_HIP;
-  return launch_add_table(x, nullptr, temb_work, out, B, L, D, s) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
-}
-
-int ffd_fresca(const float* in, float* out, float* work, int B, int L, int C, float low_scale, float high_scale,
-               double cutoff_ratio, int strategy, void* stream) {
-  if (!in || !out || in == out || B < 1 || L < 2 || C < 1) return FFD_ERR_INVALID;
-  if (strategy != FFD_FRESCA_SPATIAL && strategy != FFD_FRESCA_ENERGY) return FFD_ERR_INVALID;  // fresca.py:60 ValueError
-  if (strategy == FFD_FRESCA_ENERGY && !work) return FFD_ERR_INVALID;
-  hipError_t e = launch_fresca(in, out, work, B, L, C, low_scale, high_scale, cutoff_ratio, strategy, (hipStream_t)stream);
-  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
-}
-
-int ffd_fresca2d(const float* in, float* out, float* work, int B, int H, int W, int C, float low_scale,
-                 float high_scale, double cutoff_ratio, int strategy, void* stream) {
-  if (!in || !out || !work || in == out || B < 1 || H < 1 || W < 1 || C < 1) return FFD_ERR_INVALID;
-  if (strategy != FFD_FRESCA_SPATIAL && strategy != FFD_FRESCA_ENERGY) return FFD_ERR_INVALID;  // fresca.py:103 ValueError
-  if (!fresca2d_supported(H, W)) return FFD_ERR_UNSUPPORTED;
-  hipError_t e = launch_fresca2d(in, out, work, B, H, W, C, low_scale, high_scale, cutoff_ratio, strategy, (hipStream_t)stream);
-  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
+  return score_forward(ctx, x, timesteps, 0.f, score_out, n_recompute >= 0 ? crf_out : nullptr, B,
+                       n_recompute >= 0 ? n_recompute : -1, stream);
 }
 
 int ffd_fresca_enable(ffd_ctx* ctx, const ffd_fresca_cfg* cfg) {
@@ -1056,234 +899,6 @@ int ffd_fresca_disable(ffd_ctx* ctx) {
   if (!ctx) return FFD_ERR_INVALID;
   ctx->fresca_on = false;
   return FFD_OK;
-}
-
-int ffd_freq_decompose(const float* x, float* low, float* high, int B, int L, int D, double low_freq_ratio,
-                       void* stream) {
-  if (!x || !low || !high || x == low || x == high || low == high || B < 1 || L < 2 || D < 1) return FFD_ERR_INVALID;
-  hipError_t e = launch_freq_decompose(x, low, high, B, L, D, low_freq_ratio, (hipStream_t)stream);
-  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
-}
-
-int ffd_spectral_density(const float* xf, float* out, int B, int L, int C, void* stream) {
-  if (!xf || !out || xf == out || B < 1 || L < 1 || C < 1) return FFD_ERR_INVALID;
-  return launch_spectral_density(xf, out, B, L, C, (hipStream_t)stream) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
-}
-
-// ---- sample metrics: sliced / marginal Wasserstein-2 (wasserstein.py:95-199) ----
-// Limits: n, m <= 2^26, D <= 2^20, K <= 2^20 (FFD_ERR_UNSUPPORTED past them); a block takes at most 32768 directions.
-static const int W2_MAX_N = 1 << 26, W2_MAX_D = 1 << 20, W2_MAX_K = 1 << 20, W2_MAX_BLOCK = 32768;
-
-static size_t w2_floats_per_dir(int n, int m) {
-  return m == 0 ? (size_t)n : (size_t)n + (size_t)m + (size_t)std::max(n, m);
-}
-
-static int w2_block(size_t per_dir_floats, int K, size_t work_bytes) {
-  const size_t kb = work_bytes / (per_dir_floats * sizeof(float));
-  return (int)std::min<size_t>(kb, (size_t)std::min(K, W2_MAX_BLOCK));
-}
-
-// rows [k0, k0 + kb) of the projected + sorted set: dirs == nullptr takes features k0 .. k0 + kb instead
-static hipError_t w2_rows(const float* x, int n, int D, const float* dirs, int k0, int kb, float* dst, float* scratch,
-                          hipStream_t s) {
-  hipError_t e = dirs ? launch_w2_project(x, dirs + (size_t)k0 * D, dst, n, D, kb, s)
-                      : launch_w2_columns(x, dst, n, D, k0, kb, s);
-  if (e != hipSuccess) return e;
-  return launch_w2_sort(dst, scratch, n, kb, s);
-}
-
-static int w2_check(int n, int m, int D, int K) {
-  if (n < 1 || m < 1 || D < 1 || K < 1) return FFD_ERR_INVALID;
-  if (n > W2_MAX_N || m > W2_MAX_N || D > W2_MAX_D || K > W2_MAX_K) return FFD_ERR_UNSUPPORTED;
-  return FFD_OK;
-}
-
-size_t ffd_w2_work_bytes(int n, int m, int D, int K, size_t budget_bytes) {
-  if (n < 0 || m < 0 || n + m < 1 || D < 1 || K < 1) return 0;
-  const size_t per = w2_floats_per_dir(n, m) * sizeof(float);
-  size_t kb = budget_bytes / per;
-  kb = std::max<size_t>(1, std::min<size_t>(kb, (size_t)std::min(K, W2_MAX_BLOCK)));
-  return kb * per;
-}
-
-static int w2_run(const float* orig, int n, const float* other, int m, int D, const float* dirs, int K, int standardise,
-                  double* dist_out, void* work, size_t work_bytes, void* stream) {
-  if (!orig || !other || !dist_out || !work) return FFD_ERR_INVALID;
-  if (int rc = w2_check(n, m, D, K)) return rc;
-  const int Kb = w2_block(w2_floats_per_dir(n, m), K, work_bytes);
-  if (Kb < 1) return FFD_ERR_INVALID;
-  hipStream_t s = (hipStream_t)stream;
-  float* pa = (float*)work;
-  float* pb = pa + (size_t)Kb * n;
-  float* scratch = pb + (size_t)Kb * m;
-  for (int k0 = 0; k0 < K; k0 += Kb) {
-    const int kb = std::min(Kb, K - k0);
-    if (w2_rows(orig, n, D, dirs, k0, kb, pa, scratch, s) != hipSuccess) return FFD_ERR_HIP;
-    if (w2_rows(other, m, D, dirs, k0, kb, pb, scratch, s) != hipSuccess) return FFD_ERR_HIP;
-    if (launch_w2_integral(pa, n, pb, m, standardise, dist_out + k0, kb, s) != hipSuccess) return FFD_ERR_HIP;
-  }
-  return FFD_OK;
-}
-
-int ffd_w2_sliced(const float* orig, int n, const float* other, int m, int D, const float* dirs, int K, int standardise,
-                  double* dist_out, void* work, size_t work_bytes, void* stream) {
-  if (!dirs) return FFD_ERR_INVALID;
-  return w2_run(orig, n, other, m, D, dirs, K, standardise, dist_out, work, work_bytes, stream);
-}
-
-int ffd_w2_marginal(const float* orig, int n, const float* other, int m, int D, int standardise, double* dist_out,
-                    void* work, size_t work_bytes, void* stream) {
-  return w2_run(orig, n, other, m, D, nullptr, D, standardise, dist_out, work, work_bytes, stream);
-}
-
-int ffd_w2_prepare(const float* x, int n, int D, const float* dirs, int K, float* prepared_out, void* work,
-                   size_t work_bytes, void* stream) {
-  if (!x || !prepared_out || !work) return FFD_ERR_INVALID;
-  if (int rc = w2_check(n, 1, D, K)) return rc;
-  if (!dirs && K != D) return FFD_ERR_INVALID;
-  const int Kb = w2_block(w2_floats_per_dir(n, 0), K, work_bytes);
-  if (Kb < 1) return FFD_ERR_INVALID;
-  for (int k0 = 0; k0 < K; k0 += Kb)
-    if (w2_rows(x, n, D, dirs, k0, std::min(Kb, K - k0), prepared_out + (size_t)k0 * n, (float*)work,
-                (hipStream_t)stream) != hipSuccess)
-      return FFD_ERR_HIP;
-  return FFD_OK;
-}
-
-int ffd_w2_against_prepared(const float* prepared, int n, const float* other, int m, int D, const float* dirs, int K,
-                            int standardise, double* dist_out, void* work, size_t work_bytes, void* stream) {
-  if (!prepared || !other || !dist_out || !work) return FFD_ERR_INVALID;
-  if (int rc = w2_check(n, m, D, K)) return rc;
-  if (!dirs && K != D) return FFD_ERR_INVALID;
-  const int Kb = w2_block(w2_floats_per_dir(0, m), K, work_bytes);
-  if (Kb < 1) return FFD_ERR_INVALID;
-  hipStream_t s = (hipStream_t)stream;
-  float* pb = (float*)work;
-  float* scratch = pb + (size_t)Kb * m;
-  for (int k0 = 0; k0 < K; k0 += Kb) {
-    const int kb = std::min(Kb, K - k0);
-    if (w2_rows(other, m, D, dirs, k0, kb, pb, scratch, s) != hipSuccess) return FFD_ERR_HIP;
-    if (launch_w2_integral(prepared + (size_t)k0 * n, n, pb, m, standardise, dist_out + k0, kb, s) != hipSuccess)
-      return FFD_ERR_HIP;
-  }
-  return FFD_OK;
-}
-
-int ffd_w2_summary(const double* dist, int K, double* mean_max_out, void* stream) {
-  if (!dist || !mean_max_out || K < 1) return FFD_ERR_INVALID;
-  return launch_w2_summary(dist, K, mean_max_out, (hipStream_t)stream) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
-}
-
-size_t ffd_col_mean_work_bytes(int n, int D) {
-  return n < 1 || D < 1 ? 0 : col_mean_work_doubles(n, D) * sizeof(double);
-}
-
-int ffd_col_mean(const float* x, int n, int D, float* mean_out, void* work, size_t work_bytes, void* stream) {
-  if (!x || !mean_out || !work || n < 1 || D < 1 || work_bytes < ffd_col_mean_work_bytes(n, D)) return FFD_ERR_INVALID;
-  if (n > W2_MAX_N / 2 || D > W2_MAX_D) return FFD_ERR_UNSUPPORTED;  // a 1024-row slab per grid row: 32768 of 65535
-  return launch_col_mean(x, n, D, mean_out, (double*)work, (hipStream_t)stream) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
-}
-
-// Benchmark helper (tools/metrics_bench.py): the kernel classes of the metric one by one, HIP events around each.
-int ffd_w2_bench_kernels(const float* x, int n, int D, const float* dirs, int K, float* rows, float* scratch,
-                         const float* other_rows, int m, double* dist, int iters, float* ms_out, void* stream) {
-  if (!x || !dirs || !rows || !scratch || !other_rows || !dist || !ms_out || iters < 1 || K > W2_MAX_BLOCK)
-    return FFD_ERR_INVALID;
-  if (int rc = w2_check(n, m, D, K)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  struct Events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~Events() {
-      for (hipEvent_t ev : e)
-        if (ev) (void)hipEventDestroy(ev);
-    }
-  } ev;
-  for (hipEvent_t& e : ev.e)
-    if (hipEventCreate(&e) != hipSuccess) return FFD_ERR_HIP;
-  double acc[4] = {0, 0, 0, 0};
-  float ms = 0.f;
-  auto lap = [&](int a, int b, double& into) {
-    if (hipEventElapsedTime(&ms, ev.e[a], ev.e[b]) != hipSuccess) return false;
-    into += ms;
-    return true;
-  };
-  for (int it = -1; it < iters; ++it) {  // iteration -1 warms up; the sort always meets freshly projected rows
-    bool ok = hipEventRecord(ev.e[0], s) == hipSuccess && launch_w2_project(x, dirs, rows, n, D, K, s) == hipSuccess &&
-              hipEventRecord(ev.e[1], s) == hipSuccess && launch_w2_sort(rows, scratch, n, K, s) == hipSuccess &&
-              hipEventRecord(ev.e[2], s) == hipSuccess && hipEventSynchronize(ev.e[2]) == hipSuccess;
-    double skip = 0;
-    ok = ok && lap(0, 1, it < 0 ? skip : acc[0]) && lap(1, 2, it < 0 ? skip : acc[1]);
-    ok = ok && hipEventRecord(ev.e[0], s) == hipSuccess &&
-         launch_w2_integral(rows, n, other_rows, m, 0, dist, K, s) == hipSuccess &&
-         hipEventRecord(ev.e[1], s) == hipSuccess && launch_w2_columns(x, scratch, n, D, 0, std::min(K, D), s) == hipSuccess &&
-         hipEventRecord(ev.e[2], s) == hipSuccess && hipEventSynchronize(ev.e[2]) == hipSuccess;
-    ok = ok && lap(0, 1, it < 0 ? skip : acc[2]) && lap(1, 2, it < 0 ? skip : acc[3]);
-    if (!ok) return FFD_ERR_HIP;
-  }
-  for (int i = 0; i < 4; ++i) ms_out[i] = (float)(acc[i] / iters);
-  return FFD_OK;
-}
-
-// Hermite polynomials H_0..H_order at s (fourier.py:341-394: physicists' recurrence)
-static void hermite_row(double s, int order, double* H) {
-  H[0] = 1.0;
-  if (order >= 1) H[1] = 2.0 * s;
-  for (int n = 1; n < order; ++n) H[n + 1] = 2.0 * s * H[n] - 2.0 * n * H[n - 1];
-}
-
-int ffd_hermite_predict(const float* history, const double* timesteps, double target, int order, float* out, int K,
-                        size_t n, void* stream) {
-  if (!history || !timesteps || !out || K < 1 || K > 32 || order < 0 || order > 8) return FFD_ERR_INVALID;
-  float w[32] = {0};
-  double tmin = timesteps[0], tmax = timesteps[0];
-  for (int k = 1; k < K; ++k) tmin = std::min(tmin, timesteps[k]), tmax = std::max(tmax, timesteps[k]);
-  if (K < 2 || tmax == tmin) {
-    w[K - 1] = 1.f;  // fourier.py:416-428: not enough history -> last value
-  } else {
-    const int P = order + 1;
-    auto norm = [&](double t) {  // fourier.py:431-441, values held in fp32 tensors and clamped to [-1,1]
-      double v = (double)(float)(2.0 * (t - tmin) / (tmax - tmin) - 1.0);
-      return std::min(1.0, std::max(-1.0, v));
-    };
-    double Hm[32][9], Ht[9], A[9][18];
-    for (int k = 0; k < K; ++k) hermite_row(norm(timesteps[k]), order, Hm[k]);
-    hermite_row(norm(target), order, Ht);
-    // normal equations with ridge 1e-6 (fourier.py:462-466), inverted by Gauss-Jordan with partial pivoting
-    for (int i = 0; i < P; ++i)
-      for (int j = 0; j < P; ++j) {
-        double acc = 0.0;
-        for (int k = 0; k < K; ++k) acc += Hm[k][i] * Hm[k][j];
-        A[i][j] = acc + (i == j ? 1e-6 : 0.0);
-        A[i][P + j] = i == j ? 1.0 : 0.0;
-      }
-    for (int c = 0; c < P; ++c) {
-      int piv = c;
-      for (int r = c + 1; r < P; ++r)
-        if (fabs(A[r][c]) > fabs(A[piv][c])) piv = r;
-      if (A[piv][c] == 0.0) return FFD_ERR_INVALID;
-      if (piv != c)
-        for (int j = 0; j < 2 * P; ++j) std::swap(A[c][j], A[piv][j]);
-      const double inv = 1.0 / A[c][c];
-      for (int j = 0; j < 2 * P; ++j) A[c][j] *= inv;
-      for (int r = 0; r < P; ++r)
-        if (r != c) {
-          const double f = A[r][c];
-          if (f != 0.0)
-            for (int j = 0; j < 2 * P; ++j) A[r][j] -= f * A[c][j];
-        }
-    }
-    // w_k = H_target . (HtH)^-1 . H_k   (prediction = sum_k w_k history_k, fourier.py:476-481)
-    for (int k = 0; k < K; ++k) {
-      double acc = 0.0;
-      for (int i = 0; i < P; ++i) {
-        double u = 0.0;
-        for (int j = 0; j < P; ++j) u += A[i][P + j] * Hm[k][j];
-        acc += Ht[i] * u;
-      }
-      w[k] = (float)acc;
-    }
-  }
-  return launch_weighted_sum(history, w, out, K, n, (hipStream_t)stream) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
 }
 
 int ffd_cache_crf_capture(ffd_ctx* ctx, const ffd_crf_capture_cfg* cfg) {
@@ -1366,6 +981,12 @@ int ffd_cache_tables_read(ffd_ctx* ctx, float* k_out, float* v_out, void* stream
 // ---------------------------------------------------------------------------
 // the sampling loop (sampler.py:156-210)
 // ---------------------------------------------------------------------------
+// Can this model's sampling step unembed inside the SDE-step kernel?  (ffd_sample_batch adds its arguments' alignment.)
+static bool tail_fusable(const ffd_ctx* ctx) {
+  const ffd_model_desc& m = ctx->desc;
+  return g_fuse_tail && !ctx->fresca_on && m.kind != FFD_MODEL_MLP && unembed_sde_supported(m.n_channels, m.d_model);
+}
+
 int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
                      int first_step, int n_run, uint64_t seed, uint64_t sample_offset, const float* z_inject,
                      int use_cache, int global_step0, void* stream) {
@@ -1384,11 +1005,9 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
   const ffd_model_desc& m = ctx->desc;
   const int d = m.d_model;
   hipStream_t s = (hipStream_t)stream;
-  if (ctx->fresca_on && B > ctx->fwork_B) {
-    ctx->fwork_B = 0;
-    if ((rc = dev_regrow(ctx, &ctx->score2, (size_t)B * m.max_len * m.n_channels))) return rc;
-    if ((rc = dev_regrow(ctx, &ctx->fwork, (size_t)B * m.n_channels * (m.max_len / 2 + 1) + 4))) return rc;
-    ctx->fwork_B = B;
+  if (ctx->fresca_on) {
+    if ((rc = ensure(ctx, ctx->score2, (size_t)B * m.max_len * m.n_channels))) return rc;
+    if ((rc = ensure(ctx, ctx->fwork, (size_t)B * m.n_channels * (m.max_len / 2 + 1) + 4))) return rc;
   }
   // All time embeddings of the trajectory in one launch: t is shared by the batch
   // (sampler.py:59-60).  The table is kept across batches and only rebuilt (with one
@@ -1396,25 +1015,18 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
   if ((int)ctx->ts_host.size() != n_steps || memcmp(ctx->ts_host.data(), timesteps, sizeof(float) * n_steps) != 0 ||
       ctx->temb_epoch != ctx->weight_epoch) {
     HIPCHECK(hipStreamSynchronize(s));
-    if (n_steps > ctx->temb_cap) {
-      ctx->temb_cap = 0;
-      if ((rc = dev_regrow(ctx, &ctx->temb_tab, (size_t)n_steps * d))) return rc;
-      if ((rc = dev_regrow(ctx, &ctx->ts_dev, (size_t)n_steps))) return rc;
-      ctx->temb_cap = n_steps;
-    }
+    if ((rc = ensure(ctx, ctx->temb_tab, (size_t)n_steps * d))) return rc;
+    if ((rc = ensure(ctx, ctx->ts_dev, (size_t)n_steps))) return rc;
     ctx->ts_host.assign(timesteps, timesteps + n_steps);
-    HIPCHECK(hipMemcpy(ctx->ts_dev, ctx->ts_host.data(), sizeof(float) * n_steps, hipMemcpyHostToDevice));
-    HIPCHECK(launch_time_embed(ctx->ts_dev, 0.f, n_steps, ctx->raw["time_encoder.W"].p,
-                               ctx->raw["time_encoder.dense.weight"].p, ctx->raw["time_encoder.dense.bias"].p,
-                               ctx->temb_tab, d, s));
+    HIPCHECK(hipMemcpy(ctx->ts_dev.p, ctx->ts_host.data(), sizeof(float) * n_steps, hipMemcpyHostToDevice));
+    if ((rc = time_embed(ctx, ctx->ts_dev.p, 0.f, n_steps, ctx->temb_tab.p, s))) return rc;
     ctx->temb_epoch = ctx->weight_epoch;
   }
   const size_t slab = (size_t)B * m.max_len * m.n_channels;
   const uint64_t elem_off = sample_offset * (uint64_t)m.max_len * m.n_channels;
   // Without FreSca the score is consumed only by the SDE step: unembed inside the step kernel (one launch and a
   // (B, L, C) round trip less per step).  FreSca needs the whole score (FFT along L).
-  const bool fuse_tail = g_fuse_tail && !ctx->fresca_on && m.kind != FFD_MODEL_MLP &&
-                         unembed_sde_supported(m.n_channels, d) && (m.n_channels % 4 != 0 || elem_off % 4 == 0) &&
+  const bool fuse_tail = tail_fusable(ctx) && (m.n_channels % 4 != 0 || elem_off % 4 == 0) &&
                          (m.n_channels % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 == 0) &&  // float4 x rows
                          (!z_inject || m.n_channels % 4 != 0 ||  // float4 reads of the injected noise only when C % 4 == 0
                           (reinterpret_cast<uintptr_t>(z_inject) % 16 == 0 && slab % 4 == 0));
@@ -1442,7 +1054,7 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
       }
     }
     const float* hidden = nullptr;
-    if ((rc = forward_impl(ctx, x, ctx->temb_tab + (size_t)i * d, 0, ctx->score, crf_dst, B, n_rec, s,
+    if ((rc = forward_impl(ctx, x, ctx->temb_tab.p + (size_t)i * d, 0, ctx->score.p, crf_dst, B, n_rec, s,
                            fuse_tail ? &hidden : nullptr)))
       return rc;
     if (crf_copy)
@@ -1450,19 +1062,19 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
                               hipMemcpyDeviceToDevice, s));
     if (use_cache) ctx->stats.current_step = i;  // sampler.py:73-74 (Q4)
     const double t = (double)timesteps[i];
-    const float* score = ctx->score;
+    const float* score = ctx->score.p;
     if (ctx->fresca_on) {  // sampler.py:79-93 -> fresca.py:220-268
       const ffd_fresca_cfg& f = ctx->fcfg;
       double h = (double)f.high_scale;
       if (f.num_steps > 0 && h > 1.0) h = (1.0 - t / (double)f.num_steps) * (h - 1.0) + 1.0;
       if (!((double)f.low_scale == 1.0 && h == 1.0)) {  // fresca.py:137-138 early exit
-        HIPCHECK(launch_fresca(ctx->score, ctx->score2, ctx->fwork, B, m.max_len, m.n_channels, f.low_scale, (float)h,
+        HIPCHECK(launch_fresca(ctx->score.p, ctx->score2.p, ctx->fwork.p, B, m.max_len, m.n_channels, f.low_scale, (float)h,
                                f.cutoff_ratio, f.strategy, s));
-        score = ctx->score2;
+        score = ctx->score2.p;
       }
     }
     if (hidden)
-      TIMED(FFD_K_SDE, launch_unembed_sde(hidden, ctx->raw["unembedder.weight"].p, ctx->raw["unembedder.bias"].p, x,
+      TIMED(FFD_K_SDE, launch_unembed_sde(hidden, ctx->model.unembed_w, ctx->model.unembed_b, x,
                                           z_inject ? z_inject + (size_t)j * slab : nullptr, ctx->G_dev,
                                           sde_params(m.sde, m.sde_a, m.sde_b, t, step_size), seed, elem_off, (uint32_t)i,
                                           B, m.max_len, m.n_channels, d, s));
@@ -1564,7 +1176,7 @@ const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cac
   const ffd_model_desc& m = ctx->desc;
   const double L = m.max_len, d = m.d_model, C = m.n_channels, F = m.dim_feedforward, M = (double)B * L;
   // (the transformer's forms need the packs ffd_finalize_weights made)
-  const bool tr = m.kind == FFD_MODEL_TRANSFORMER && !ctx->packed.empty(), ls = m.kind == FFD_MODEL_LSTM;
+  const bool tr = m.kind == FFD_MODEL_TRANSFORMER && ctx->packs_made(), ls = m.kind == FFD_MODEL_LSTM;
   const LayerPlan p = tr ? plan_of(ctx, B, cache_hit ? CACHE_PURE : CACHE_STD) : LayerPlan{};
   const LstmPlan lp = ls ? plan_lstm(m, B) : LstmPlan{};
   double fl = 0.0, by = 0.0;
@@ -1606,7 +1218,7 @@ const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cac
     case FFD_K_SDE:
       // x, score in; x out (noise generated on chip): 12 B per element; with the unembedding fused
       // into it the score term is replaced by the hidden row: 4 (d + 2 C) B per row
-      if (g_fuse_tail && !ctx->fresca_on && m.kind != FFD_MODEL_MLP && unembed_sde_supported(m.n_channels, m.d_model))
+      if (tail_fusable(ctx))
         name = "k_unembed_mfma<sde>", fl = 2.0 * M * C * d, by = 4.0 * M * (d + 2.0 * C);
       else
         name = "k_sde_step", by = 12.0 * M * C;
@@ -1675,11 +1287,11 @@ static int ffn_probe_setup(ffd_ctx* ctx, int B, hipStream_t s, LayerPlan* plan) 
   *plan = plan_of(ctx, B, CACHE_STD);
   if (plan->ffn == FFN_SPLIT && ctx->layers[0].w1s == nullptr)
     return ctx->fail(FFD_ERR_STATE, "ffn_split: run one forward first (the packs are made on first use)");
-  if (int rc = ensure_ffn_part(ctx, *plan)) return rc;
+  if (int rc = ensure(ctx, ctx->ffn_part, plan->part_floats)) return rc;
   const size_t n = (size_t)B * ctx->desc.max_len * ctx->desc.d_model;
-  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h1, n, 0x9E3779B9u);
-  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->attn, n, 0x85EBCA6Bu);
-  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h0, n, 0xC2B2AE35u);
+  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h1.p, n, 0x9E3779B9u);
+  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->attn.p, n, 0x85EBCA6Bu);
+  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h0.p, n, 0xC2B2AE35u);
   HIPCHECK(hipGetLastError());
   return FFD_OK;
 }
@@ -1691,7 +1303,7 @@ int ffd_bench_ffn(ffd_ctx* ctx, int B, int iters, float* ms_out, void* stream) {
   LayerPlan p;
   if (int rc = ffn_probe_setup(ctx, B, s, &p)) return rc;
   const int M = B * ctx->desc.max_len;
-  auto run = [&]() { return run_ffn(ctx, p, ctx->layers[0], ctx->attn, ctx->h1, ctx->h0, M, s); };
+  auto run = [&]() { return run_ffn(ctx, p, ctx->layers[0], ctx->attn.p, ctx->h1.p, ctx->h0.p, M, s); };
   return time_launches(ctx, s, run, 3, 0.0, iters, ms_out);
 }
 
@@ -1707,7 +1319,7 @@ int ffd_probe_ffn_clock(ffd_ctx* ctx, int B, double warm_seconds, double* ghz_ou
   StampBuf stamps;
   HIPCHECK(hipMalloc((void**)&stamps.p, sizeof(unsigned long long) * 8 * nwg));
   HIPCHECK(hipMemsetAsync(stamps.p, 0, sizeof(unsigned long long) * 8 * nwg, s));
-  auto launch = [&](unsigned long long* st) { return run_ffn(ctx, p, ctx->layers[0], ctx->attn, ctx->h1, ctx->h0, M, s, st); };
+  auto launch = [&](unsigned long long* st) { return run_ffn(ctx, p, ctx->layers[0], ctx->attn.p, ctx->h1.p, ctx->h0.p, M, s, st); };
   // back-to-back launches for warm_seconds (the clock the chip settles at under this load), then the stamped one
   float unused;
   if (int rc = time_launches(ctx, s, [&]() { return launch(nullptr); }, 50, warm_seconds, 0, &unused)) return rc;
@@ -1750,22 +1362,21 @@ int ffd_probe_attn(ffd_ctx* ctx, int B, int n_recompute, double warm_seconds, in
   const int L = m.max_len, d = m.d_model, H = m.n_head;
   if (n_recompute > L) return ctx->fail(FFD_ERR_INVALID, "n_recompute=%d outside [-1,%d]", n_recompute, L);
   const CacheMode mode = cache_mode(n_recompute, L);  // (FULL reads no tables: the plain layer's launch)
-  const bool tables = mode == CACHE_PURE || mode == CACHE_MIXED;
-  if (tables && !(ctx->cache_enabled && ctx->table_allocated))
+  const CacheUse cu = cache_use(mode, n_recompute, L);
+  if (cu.tables && !(ctx->cache_enabled && ctx->table_allocated))
     return ctx->fail(FFD_ERR_STATE, "cached modes need ffd_cache_enable and one full step (the tables)");
   HIPCHECK(hipSetDevice(ctx->device));
   if ((rc = ensure_workspace(ctx, B))) return rc;
   const LayerPlan p = plan_of(ctx, B, mode);
   if (p.attn == ATTN_TWO_KERNEL)
-    if ((rc = ensure_qkv(ctx, (size_t)B * L * 3 * d))) return rc;
+    if ((rc = ensure(ctx, ctx->qkv, (size_t)B * L * 3 * d))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h1, (size_t)B * L * d, 0x9E3779B9u);  // random rows
+  hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h1.p, (size_t)B * L * d, 0x9E3779B9u);  // random rows
   HIPCHECK(hipGetLastError());
-  const int n_own = mode == CACHE_PURE ? 0 : mode == CACHE_MIXED ? n_recompute : L;
   // (MIXED: the recomputed rows of batch element 0 are NOT written back -- the probe leaves the tables as they are)
   auto launch = [&](unsigned long long* st) {
-    return run_attention(ctx, p, 0, ctx->h1, tables ? ctx->kt : nullptr, tables ? ctx->vt : nullptr, nullptr, nullptr,
-                         B, n_own, s, st);
+    return run_attention(ctx, p, ctx->layers[0], ctx->h1.p, cu.tables ? ctx->kt : nullptr, cu.tables ? ctx->vt : nullptr,
+                         nullptr, nullptr, B, cu.n_own, s, st);
   };
   if ((rc = time_launches(ctx, s, [&]() { return launch(nullptr); }, 20, warm_seconds, iters, ms_out))) return rc;
   if (nrec_out) *nrec_out = 0;

@@ -4,6 +4,9 @@
 //   - VP / VE reverse Euler-Maruyama step with on-device Philox4x32-10 noise
 //   - KV-table store
 // All HBM-bound: one pass over the data, coalesced, no re-reads.
+// The entry points that need no context (SDE step, prior, the two encodings, Hermite prediction) follow the kernels.
+#include <math.h>
+
 #include <algorithm>
 
 #include "ffd_internal.h"
@@ -349,8 +352,8 @@ __global__ void k_add_table(const float* __restrict__ x, const float* __restrict
   }
 }
 
-hipError_t launch_add_table(const float* x, const float* rowtab, const float* battab, float* out, int B, int L, int D,
-                            hipStream_t s) {
+static hipError_t launch_add_table(const float* x, const float* rowtab, const float* battab, float* out, int B, int L, int D,
+                                   hipStream_t s) {
   const unsigned total = (unsigned)((size_t)B * L * D);
   unsigned blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
@@ -372,7 +375,7 @@ __global__ void k_renorm_rows_once(float* __restrict__ W, int D, float max_norm)
   }
 }
 
-hipError_t launch_renorm_rows_once(float* W, int rows, int D, float max_norm, hipStream_t s) {
+static hipError_t launch_renorm_rows_once(float* W, int rows, int D, float max_norm, hipStream_t s) {
   hipLaunchKernelGGL(k_renorm_rows_once, dim3(rows), dim3(WAVE), 0, s, W, D, max_norm);
   return hipGetLastError();
 }
@@ -548,8 +551,8 @@ __global__ void k_prior(float* __restrict__ x, const float* __restrict__ z, cons
   }
 }
 
-hipError_t launch_prior(float* x, const float* z, const float* G, float scale, uint64_t seed, uint64_t elem_offset,
-                        int B, int L, int C, hipStream_t s) {
+static hipError_t launch_prior(float* x, const float* z, const float* G, float scale, uint64_t seed, uint64_t elem_offset,
+                               int B, int L, int C, hipStream_t s) {
   size_t total = (size_t)B * L * C;
   size_t blocks = ((total + 3) / 4 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -769,7 +772,7 @@ __global__ void k_weighted_sum(const float* __restrict__ hist, WeightVec wv, flo
   }
 }
 
-hipError_t launch_weighted_sum(const float* hist, const float* w_host, float* out, int K, size_t n, hipStream_t s) {
+static hipError_t launch_weighted_sum(const float* hist, const float* w_host, float* out, int K, size_t n, hipStream_t s) {
   if (K < 1 || K > 32) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   WeightVec wv{};
@@ -779,4 +782,126 @@ hipError_t launch_weighted_sum(const float* hist, const float* w_host, float* ou
   return hipGetLastError();
 }
 
+SdeParams sde_params(int sde, double a, double b, double t, float step_size) {
+  SdeParams p{};
+  p.sde = sde;
+  if (sde == FFD_SDE_VP) {
+    const double beta = a + t * (b - a);  // sde.py:212-213
+    p.a = (float)(-0.5 * beta);
+    p.cs = (float)sqrt(beta);
+  } else {
+    const double r = b / a;
+    p.cs = (float)(a * sqrt(2.0 * log(r)) * pow(r, t));  // sde.py:143-147
+    p.a = 0.f;
+  }
+  p.dt = step_size;
+  p.sqdt = sqrtf(step_size);
+  return p;
+}
+
 }  // namespace ffd
+
+// ---- C ABI (include/ffd.h): the context-free entry points on these kernels ----
+using namespace ffd;
+
+extern "C" {
+
+int ffd_sde_step(const ffd_sde_desc* sde, float* x, const float* score, const float* G, double t, float step_size,
+                 const float* z, uint64_t seed, uint64_t sample_offset, int step, int B, int L, int C, void* stream) {
+  if (!sde || !x || !score || !G || B < 1 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  if (sde->sde != FFD_SDE_VP && sde->sde != FFD_SDE_VE) return FFD_ERR_UNSUPPORTED;
+  if (!(step_size > 0.f)) return FFD_ERR_INVALID;  // sde.py:157,238 assert
+  hipError_t e = launch_sde_step(x, score, z, G, sde_params(sde->sde, sde->a, sde->b, t, step_size), seed,
+                                 sample_offset * (uint64_t)L * C, (uint32_t)step, B, L, C, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+int ffd_prior(const ffd_sde_desc* sde, float* x, const float* z, const float* G, uint64_t seed, uint64_t sample_offset,
+              int B, int L, int C, void* stream) {
+  if (!sde || !x || !G || B < 1 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  const float scale = (sde->sde == FFD_SDE_VE) ? (float)sde->b : 1.0f;
+  hipError_t e = launch_prior(x, z, G, scale, seed, sample_offset * (uint64_t)L * C, B, L, C, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+int ffd_positional_encoding(const float* x, float* weight, float* out, int B, int L, int D, float max_norm,
+                            void* stream) {
+  if (!x || !weight || !out || B < 1 || L < 1 || D < 1) return FFD_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  // nn.Embedding(max_norm) renormalises the looked-up rows in place at every forward (transformer.py:13-15,26)
+  if (max_norm > 0.f && launch_renorm_rows_once(weight, L, D, max_norm, s) != hipSuccess) return FFD_ERR_HIP;
+  return launch_add_table(x, weight, nullptr, out, B, L, D, s) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+int ffd_time_encoding(const float* x, const float* timesteps, const float* W, const float* dense_w,
+                      const float* dense_b, float* temb_work, float* out, int B, int L, int D, void* stream) {
+  if (!x || !timesteps || !W || !dense_w || !dense_b || !temb_work || !out || B < 1 || L < 1 || D < 1)
+    return FFD_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  if (launch_time_embed(timesteps, 0.f, B, W, dense_w, dense_b, temb_work, D, s) != hipSuccess) return FFD_ERR_HIP;
+  return launch_add_table(x, nullptr, temb_work, out, B, L, D, s) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+// Hermite polynomials H_0..H_order at s (fourier.py:341-394: physicists' recurrence)
+static void hermite_row(double s, int order, double* H) {
+  H[0] = 1.0;
+  if (order >= 1) H[1] = 2.0 * s;
+  for (int n = 1; n < order; ++n) H[n + 1] = 2.0 * s * H[n] - 2.0 * n * H[n - 1];
+}
+
+int ffd_hermite_predict(const float* history, const double* timesteps, double target, int order, float* out, int K,
+                        size_t n, void* stream) {
+  if (!history || !timesteps || !out || K < 1 || K > 32 || order < 0 || order > 8) return FFD_ERR_INVALID;
+  float w[32] = {0};
+  double tmin = timesteps[0], tmax = timesteps[0];
+  for (int k = 1; k < K; ++k) tmin = std::min(tmin, timesteps[k]), tmax = std::max(tmax, timesteps[k]);
+  if (K < 2 || tmax == tmin) {
+    w[K - 1] = 1.f;  // fourier.py:416-428: not enough history -> last value
+  } else {
+    const int P = order + 1;
+    auto norm = [&](double t) {  // fourier.py:431-441, values held in fp32 tensors and clamped to [-1,1]
+      double v = (double)(float)(2.0 * (t - tmin) / (tmax - tmin) - 1.0);
+      return std::min(1.0, std::max(-1.0, v));
+    };
+    double Hm[32][9], Ht[9], A[9][18];
+    for (int k = 0; k < K; ++k) hermite_row(norm(timesteps[k]), order, Hm[k]);
+    hermite_row(norm(target), order, Ht);
+    // normal equations with ridge 1e-6 (fourier.py:462-466), inverted by Gauss-Jordan with partial pivoting
+    for (int i = 0; i < P; ++i)
+      for (int j = 0; j < P; ++j) {
+        double acc = 0.0;
+        for (int k = 0; k < K; ++k) acc += Hm[k][i] * Hm[k][j];
+        A[i][j] = acc + (i == j ? 1e-6 : 0.0);
+        A[i][P + j] = i == j ? 1.0 : 0.0;
+      }
+    for (int c = 0; c < P; ++c) {
+      int piv = c;
+      for (int r = c + 1; r < P; ++r)
+        if (fabs(A[r][c]) > fabs(A[piv][c])) piv = r;
+      if (A[piv][c] == 0.0) return FFD_ERR_INVALID;
+      if (piv != c)
+        for (int j = 0; j < 2 * P; ++j) std::swap(A[c][j], A[piv][j]);
+      const double inv = 1.0 / A[c][c];
+      for (int j = 0; j < 2 * P; ++j) A[c][j] *= inv;
+      for (int r = 0; r < P; ++r)
+        if (r != c) {
+          const double f = A[r][c];
+          if (f != 0.0)
+            for (int j = 0; j < 2 * P; ++j) A[r][j] -= f * A[c][j];
+        }
+    }
+    // w_k = H_target . (HtH)^-1 . H_k   (prediction = sum_k w_k history_k, fourier.py:476-481)
+    for (int k = 0; k < K; ++k) {
+      double acc = 0.0;
+      for (int i = 0; i < P; ++i) {
+        double u = 0.0;
+        for (int j = 0; j < P; ++j) u += A[i][P + j] * Hm[k][j];
+        acc += Ht[i] * u;
+      }
+      w[k] = (float)acc;
+    }
+  }
+  return launch_weighted_sum(history, w, out, K, n, (hipStream_t)stream) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+}  // extern "C"

@@ -806,8 +806,9 @@ static hipError_t get_twiddles(int L, const float2** out) {
   return hipSuccess;
 }
 
-hipError_t launch_dft(const float* in, float* out, int B, int L, int C, int inverse, const float* a0, const float* a1,
-                      hipStream_t s) {
+// a0 / a1 (both or neither; (L, C) on the device): forward out = (dft(in) - a0) / a1, inverse out = idft(in * a0 + a1)
+static hipError_t launch_dft(const float* in, float* out, int B, int L, int C, int inverse, const float* a0, const float* a1,
+                             hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (L < 1 || C < 1 || L > 8192) return hipErrorInvalidValue;
   if ((a0 == nullptr) != (a1 == nullptr)) return hipErrorInvalidValue;
@@ -960,8 +961,8 @@ hipError_t launch_fresca(const float* in, float* out, float* work, int B, int L,
 // frequency_decompose_fft (fourier.py:219-286): rfft along L, keep bins k < n_low for the low part and
 // k >= n_low for the high part, irfft each.  Same LDS-resident FFT -> mask -> inverse FFT kernel as FreSca
 // with factors (1,0) and (0,1); the tensor is (B, L, D) with D innermost, exactly the (B, L, C) layout.
-hipError_t launch_freq_decompose(const float* in, float* low, float* high, int B, int L, int D, double low_freq_ratio,
-                                 hipStream_t s) {
+static hipError_t launch_freq_decompose(const float* in, float* low, float* high, int B, int L, int D, double low_freq_ratio,
+                                        hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (L < 2 || D < 1 || L > 4096) return hipErrorInvalidValue;
   const float2* W = nullptr;
@@ -995,7 +996,7 @@ __global__ void k_spectral_density(const float* __restrict__ xf, float* __restri
   }
 }
 
-hipError_t launch_spectral_density(const float* xf, float* out, int B, int L, int C, hipStream_t s) {
+static hipError_t launch_spectral_density(const float* xf, float* out, int B, int L, int C, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   const size_t n = (size_t)B * (L / 2 + 1) * C;
   const int blocks = (int)std::min<size_t>((n + 255) / 256, 256 * 16);
@@ -1155,14 +1156,15 @@ __global__ __launch_bounds__(256) void k_fresca2d_inv(const float2* __restrict__
   }
 }
 
-bool fresca2d_supported(int H, int W) {
+// the 4-D (B, H, W, C) branch (rfft2 / irfft2 over H, W)
+static bool fresca2d_supported(int H, int W) {
   return H >= 1 && W >= 1 && H <= F2D_MAX_DIM && W <= F2D_MAX_DIM && H * W <= F2D_MAX_HW;
 }
-size_t fresca2d_work_floats(int B, int H, int W, int C) { return (size_t)3 * B * C * H * (W / 2 + 1) + 4; }
+static size_t fresca2d_work_floats(int B, int H, int W, int C) { return (size_t)3 * B * C * H * (W / 2 + 1) + 4; }
 
 // work: fresca2d_work_floats(B, H, W, C) floats, 8-byte aligned
-hipError_t launch_fresca2d(const float* in, float* out, float* work, int B, int H, int W, int C, float low, float high,
-                           double cutoff_ratio, int strategy, hipStream_t s) {
+static hipError_t launch_fresca2d(const float* in, float* out, float* work, int B, int H, int W, int C, float low, float high,
+                                  double cutoff_ratio, int strategy, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (C < 1 || !fresca2d_supported(H, W)) return hipErrorInvalidValue;
   const int nW = W / 2 + 1, nimg = B * C;
@@ -1182,5 +1184,67 @@ hipError_t launch_fresca2d(const float* in, float* out, float* work, int B, int 
   return hipGetLastError();
 }
 
-
 }  // namespace ffd
+
+// ---- C ABI (include/ffd.h): the context-free transforms ----
+using namespace ffd;
+
+extern "C" {
+
+int ffd_dft(const float* in, float* out, int B, int L, int C, void* stream) {
+  if (!in || !out || in == out || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  hipError_t e = launch_dft(in, out, B, L, C, 0, nullptr, nullptr, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
+}
+
+int ffd_idft(const float* in, float* out, int B, int L, int C, void* stream) {
+  if (!in || !out || in == out || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  hipError_t e = launch_dft(in, out, B, L, C, 1, nullptr, nullptr, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
+}
+
+int ffd_dft_standardize(const float* in, float* out, const float* mean, const float* std, int B, int L, int C,
+                        void* stream) {
+  if (!in || !out || in == out || !mean || !std || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  hipError_t e = launch_dft(in, out, B, L, C, 0, mean, std, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
+}
+
+int ffd_unstandardize_idft(const float* in, float* out, const float* mean, const float* std, int B, int L, int C,
+                           void* stream) {
+  if (!in || !out || in == out || !mean || !std || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  hipError_t e = launch_dft(in, out, B, L, C, 1, std, mean, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
+}
+
+int ffd_fresca(const float* in, float* out, float* work, int B, int L, int C, float low_scale, float high_scale,
+               double cutoff_ratio, int strategy, void* stream) {
+  if (!in || !out || in == out || B < 1 || L < 2 || C < 1) return FFD_ERR_INVALID;
+  if (strategy != FFD_FRESCA_SPATIAL && strategy != FFD_FRESCA_ENERGY) return FFD_ERR_INVALID;  // fresca.py:60 ValueError
+  if (strategy == FFD_FRESCA_ENERGY && !work) return FFD_ERR_INVALID;
+  hipError_t e = launch_fresca(in, out, work, B, L, C, low_scale, high_scale, cutoff_ratio, strategy, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
+}
+
+int ffd_fresca2d(const float* in, float* out, float* work, int B, int H, int W, int C, float low_scale,
+                 float high_scale, double cutoff_ratio, int strategy, void* stream) {
+  if (!in || !out || !work || in == out || B < 1 || H < 1 || W < 1 || C < 1) return FFD_ERR_INVALID;
+  if (strategy != FFD_FRESCA_SPATIAL && strategy != FFD_FRESCA_ENERGY) return FFD_ERR_INVALID;  // fresca.py:103 ValueError
+  if (!fresca2d_supported(H, W)) return FFD_ERR_UNSUPPORTED;
+  hipError_t e = launch_fresca2d(in, out, work, B, H, W, C, low_scale, high_scale, cutoff_ratio, strategy, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
+}
+
+int ffd_freq_decompose(const float* x, float* low, float* high, int B, int L, int D, double low_freq_ratio,
+                       void* stream) {
+  if (!x || !low || !high || x == low || x == high || low == high || B < 1 || L < 2 || D < 1) return FFD_ERR_INVALID;
+  hipError_t e = launch_freq_decompose(x, low, high, B, L, D, low_freq_ratio, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
+}
+
+int ffd_spectral_density(const float* xf, float* out, int B, int L, int C, void* stream) {
+  if (!xf || !out || xf == out || B < 1 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  return launch_spectral_density(xf, out, B, L, C, (hipStream_t)stream) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+}  // extern "C"

@@ -106,15 +106,18 @@ constexpr __host__ __device__ size_t w2pack_floats(int D, int F) { return (size_
 struct LayerWeights {
   // raw (device) parameters
   const float *in_w, *in_b, *out_w, *out_b, *w1, *b1, *w2, *b2, *n1w, *n1b, *n2w, *n2b;
-  // packed
-  const float *in_wp;   // dpack (3d x d)
-  const float *out_wp;  // dpack (d x d)
-  const float *w1p;     // dpack (F x d)
-  const float *w2p;     // w2pack
-  const float *w2r;     // w2rem (remainder rows d % 16 of linear2.weight, 4x4x1 MFMA A-operand order)
-  const float* ring = nullptr;  // CU-shared weight ring pack of the row-owning FFN (ffd_ffn_rows.hip)
-  const float* ring_op = nullptr;  // its out-projection slot (fused out-proj + LN1 form)
-  const void *w1s = nullptr, *w2s = nullptr;  // three-part bf16 packs of the opt-in split FFN (ffd_ffn_split.hip)
+  // packed by ffd_finalize_weights (the context owns them); nullptr: no kernel of that form for this shape
+  float *in_wp = nullptr, *q_wp = nullptr, *kv_wp = nullptr;  // dpack (3d x d), of its q rows (d x d), of its k | v rows (2d x d)
+  float* out_wp = nullptr;  // dpack (d x d)
+  float* w1p = nullptr;     // dpack (F x d)
+  float* w2p = nullptr;     // w2pack
+  float* w2r = nullptr;     // w2rem (remainder rows d % 16 of linear2.weight, 4x4x1 MFMA A-operand order)
+  float* ring = nullptr;     // CU-shared weight ring pack of the row-owning FFN (ffd_ffn_rows.hip)
+  float* ring_op = nullptr;  // its out-projection slot (fused out-proj + LN1 form)
+  float *w1s = nullptr, *w2s = nullptr;  // three-part bf16 packs of the opt-in split FFN (ffd_ffn_split.hip), made on first use
+  float *aw_full = nullptr, *aw_q = nullptr;    // per-head packs of the fused in-projection + attention kernel
+  float *aw_full2 = nullptr, *aw_q2 = nullptr;  // same, per pair of heads (two-head workgroups)
+  float* aw_kvq = nullptr;                      // per head, tile 0 = k | v, tile 1 = q (the split small-batch form)
 };
 
 hipError_t launch_pack_dweight(const float* W, float* Wp, int N, int D, hipStream_t s);
@@ -127,9 +130,6 @@ constexpr __host__ __device__ int w2rem_groups(int D) { return (D % 16) / 4; }
 constexpr __host__ __device__ size_t w2rem_floats(int D, int F) { return (size_t)(F / 16) * (w2rem_groups(D) ? w2rem_groups(D) : 1) * 64 * 4; }
 hipError_t launch_pack_w2rem(const float* W2, float* W2r, int D, int F, hipStream_t s);
 hipError_t launch_renorm_rows(float* W, int rows, int D, float max_norm, hipStream_t s);
-hipError_t launch_renorm_rows_once(float* W, int rows, int D, float max_norm, hipStream_t s);
-hipError_t launch_add_table(const float* x, const float* rowtab, const float* battab, float* out, int B, int L, int D,
-                            hipStream_t s);
 
 // temb[n][d] = dense(gamma(t_n)) for n timesteps (transformer.py:77-91)
 // (ts == nullptr: a single embedding of the immediate t_imm)
@@ -148,6 +148,7 @@ struct SdeParams {
   float cs;         // (float)sqrt(beta) | (float)sqrt_derivative
   float dt, sqdt;   // step_size, sqrtf(step_size)
 };
+SdeParams sde_params(int sde, double a, double b, double t, float step_size);  // the step at time t (sde.py:143-147, 212-213)
 hipError_t launch_sde_step(float* x, const float* score, const float* z, const float* G, SdeParams p, uint64_t seed,
                            uint64_t elem_offset, uint32_t step, int B, int L, int C, hipStream_t s);
 // the two fused: x <- step(x, unembed(h)); the score stays in registers.  Needs unembed_sde_supported(C, D).
@@ -155,8 +156,6 @@ bool unembed_sde_supported(int C, int D);
 hipError_t launch_unembed_sde(const float* h, const float* Wu, const float* bu, float* x, const float* z, const float* G,
                               SdeParams p, uint64_t seed, uint64_t elem_offset, uint32_t step, int B, int L, int C,
                               int D, hipStream_t s);
-hipError_t launch_prior(float* x, const float* z, const float* G, float scale, uint64_t seed, uint64_t elem_offset,
-                        int B, int L, int C, hipStream_t s);
 
 // Y[M x N] (row stride ldy) = X[M x D] Wp^T + b ; Wp is dpack of the N x D weight.
 hipError_t launch_linear(const float* X, const float* Wp, const float* bias, float* Y, int M, int N, int D, int ldy,
@@ -252,35 +251,9 @@ hipError_t launch_pack_lstm_wave(const float* wih, const float* whh, const float
 
 hipError_t launch_dense(const float* X, const float* W, const float* b, const float* b2, const float* R, float* Y,
                         int M, int N, int K, int relu, hipStream_t s);
-// a0 / a1 (both or neither; (L, C) on the device): forward out = (dft(in) - a0) / a1, inverse out = idft(in * a0 + a1)
-hipError_t launch_dft(const float* in, float* out, int B, int L, int C, int inverse, const float* a0, const float* a1,
-                      hipStream_t s);
-hipError_t launch_freq_decompose(const float* in, float* low, float* high, int B, int L, int D, double low_freq_ratio,
-                                 hipStream_t s);
-hipError_t launch_spectral_density(const float* xf, float* out, int B, int L, int C, hipStream_t s);
-hipError_t launch_weighted_sum(const float* hist, const float* w_host, float* out, int K, size_t n, hipStream_t s);
 // FreSca spectral scaling of a (B,L,C) score; work: B*(L/2+1) + 1 floats; strategy 0 spatial, 1 energy
 hipError_t launch_fresca(const float* in, float* out, float* work, int B, int L, int C, float low, float high,
                          double cutoff_ratio, int strategy, hipStream_t s);
-// the 4-D (B, H, W, C) branch (rfft2 / irfft2 over H, W); work: fresca2d_work_floats floats
-bool fresca2d_supported(int H, int W);
-size_t fresca2d_work_floats(int B, int H, int W, int C);
-hipError_t launch_fresca2d(const float* in, float* out, float* work, int B, int H, int W, int C, float low, float high,
-                           double cutoff_ratio, int strategy, hipStream_t s);
-
-// ---- sample metrics (ffd_metrics.hip): sliced / marginal Wasserstein-2 distances ----
-// P (K, N) = U (K, D) . X (N, D)^T, direction-major
-hipError_t launch_w2_project(const float* X, const float* U, float* P, int N, int D, int K, hipStream_t s);
-// P (Kb, N) = columns [f0, f0 + Kb) of X (N, D)
-hipError_t launch_w2_columns(const float* X, float* P, int N, int D, int f0, int Kb, hipStream_t s);
-// every row of `rows` (Kb, N) sorted ascending in place; scratch: Kb * N floats
-hipError_t launch_w2_sort(float* rows, float* scratch, int N, int Kb, hipStream_t s);
-// dist[k] = W2(pa row k (n sorted keys), pb row k (m sorted keys)) (/ population std of pa's row)
-hipError_t launch_w2_integral(const float* pa, int n, const float* pb, int m, int standardise, double* dist, int Kb,
-                              hipStream_t s);
-hipError_t launch_w2_summary(const double* dist, int K, double* out, hipStream_t s);
-size_t col_mean_work_doubles(int N, int D);
-hipError_t launch_col_mean(const float* X, int N, int D, float* out, double* work, hipStream_t s);
 
 // ---- the kernels of one transformer layer / of the LSTM stack at a batch (ffd_api.hip) --------------------------
 // plan_layer is the one place that orders the forms; each heuristic above answers for its own form only.

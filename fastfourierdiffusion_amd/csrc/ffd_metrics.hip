@@ -10,7 +10,10 @@
 //   k_w2_summary   mean and max of the K distances; k_col_partial + k_col_final: the column mean of a sample set
 //
 // Every reduction is a fixed-order tree in fp64 with no atomics: a direction's distance depends on its own row only,
-// never on the launch grid or on how the directions are cut into blocks.
+// never on the launch grid or on how the directions are cut into blocks.  The ffd_w2_* / ffd_col_mean* entry points
+// follow the kernels.
+#include <algorithm>
+
 #include "ffd_internal.h"
 
 namespace ffd {
@@ -90,7 +93,8 @@ __global__ __launch_bounds__(256) void k_w2_project(const float* __restrict__ X,
   }
 }
 
-hipError_t launch_w2_project(const float* X, const float* U, float* P, int N, int D, int K, hipStream_t s) {
+// P (K, N) = U (K, D) . X (N, D)^T, direction-major
+static hipError_t launch_w2_project(const float* X, const float* U, float* P, int N, int D, int K, hipStream_t s) {
   dim3 grid(cdiv(N, PJ_ROWS), cdiv(K, PJ_DIRS));
   hipLaunchKernelGGL(k_w2_project, grid, dim3(256), 0, s, X, U, P, N, D, K);
   return hipGetLastError();
@@ -109,7 +113,8 @@ __global__ __launch_bounds__(256) void k_w2_columns(const float* __restrict__ X,
     if (c0 + r < Kb && n0 + tx < N) P[(size_t)(c0 + r) * N + n0 + tx] = tile[tx][r];
 }
 
-hipError_t launch_w2_columns(const float* X, float* P, int N, int D, int f0, int Kb, hipStream_t s) {
+// P (Kb, N) = columns [f0, f0 + Kb) of X (N, D)
+static hipError_t launch_w2_columns(const float* X, float* P, int N, int D, int f0, int Kb, hipStream_t s) {
   dim3 grid(cdiv(N, 32), cdiv(Kb, 32));
   hipLaunchKernelGGL(k_w2_columns, grid, dim3(256), 0, s, X, P, N, D, f0, Kb);
   return hipGetLastError();
@@ -205,7 +210,7 @@ __global__ __launch_bounds__(256) void k_w2_merge(const uint32_t* __restrict__ i
 }
 
 // Sort the Kb rows of `rows` (Kb, N) ascending in place; `scratch` holds Kb * N more words.
-hipError_t launch_w2_sort(float* rows, float* scratch, int N, int Kb, hipStream_t s) {
+static hipError_t launch_w2_sort(float* rows, float* scratch, int N, int Kb, hipStream_t s) {
   int passes = 0;
   for (long long R = SORT_CHUNK; R < N; R <<= 1) ++passes;
   uint32_t* buf[2] = {(uint32_t*)rows, (uint32_t*)scratch};
@@ -274,8 +279,9 @@ __global__ __launch_bounds__(256) void k_w2_integral(const float* __restrict__ b
   if (threadIdx.x == 0) dist[blockIdx.x] = res;
 }
 
-hipError_t launch_w2_integral(const float* pa, int n, const float* pb, int m, int standardise, double* dist, int Kb,
-                              hipStream_t s) {
+// dist[k] = W2(pa row k (n sorted keys), pb row k (m sorted keys)) (/ population std of pa's row)
+static hipError_t launch_w2_integral(const float* pa, int n, const float* pb, int m, int standardise, double* dist, int Kb,
+                                     hipStream_t s) {
   const float* sd = standardise ? pa : nullptr;
   if (n >= m)
     hipLaunchKernelGGL(k_w2_integral, dim3(Kb), dim3(256), 0, s, pa, n, pb, m, sd, n, dist);
@@ -311,7 +317,7 @@ __global__ __launch_bounds__(256) void k_w2_summary(const double* __restrict__ d
   }
 }
 
-hipError_t launch_w2_summary(const double* dist, int K, double* out, hipStream_t s) {
+static hipError_t launch_w2_summary(const double* dist, int K, double* out, hipStream_t s) {
   hipLaunchKernelGGL(k_w2_summary, dim3(1), dim3(256), 0, s, dist, K, out);
   return hipGetLastError();
 }
@@ -340,8 +346,8 @@ __global__ __launch_bounds__(256) void k_col_final(const double* __restrict__ pa
   out[c] = (float)(s / (double)N);
 }
 
-size_t col_mean_work_doubles(int N, int D) { return (size_t)cdiv(N, COL_SLAB) * D; }
-hipError_t launch_col_mean(const float* X, int N, int D, float* out, double* work, hipStream_t s) {
+static size_t col_mean_work_doubles(int N, int D) { return (size_t)cdiv(N, COL_SLAB) * D; }
+static hipError_t launch_col_mean(const float* X, int N, int D, float* out, double* work, hipStream_t s) {
   const int nslab = cdiv(N, COL_SLAB);
   hipLaunchKernelGGL(k_col_partial, dim3(cdiv(D, 64), nslab), dim3(256), 0, s, X, N, D, work);
   hipLaunchKernelGGL(k_col_final, dim3(cdiv(D, 256)), dim3(256), 0, s, work, nslab, N, D, out);
@@ -349,3 +355,164 @@ hipError_t launch_col_mean(const float* X, int N, int D, float* out, double* wor
 }
 
 }  // namespace ffd
+
+// ---- C ABI (include/ffd.h): the sample metrics ----
+using namespace ffd;
+
+extern "C" {
+
+// ---- sample metrics: sliced / marginal Wasserstein-2 (wasserstein.py:95-199) ----
+// Limits: n, m <= 2^26, D <= 2^20, K <= 2^20 (FFD_ERR_UNSUPPORTED past them); a block takes at most 32768 directions.
+static const int W2_MAX_N = 1 << 26, W2_MAX_D = 1 << 20, W2_MAX_K = 1 << 20, W2_MAX_BLOCK = 32768;
+
+static size_t w2_floats_per_dir(int n, int m) {
+  return m == 0 ? (size_t)n : (size_t)n + (size_t)m + (size_t)std::max(n, m);
+}
+
+static int w2_block(size_t per_dir_floats, int K, size_t work_bytes) {
+  const size_t kb = work_bytes / (per_dir_floats * sizeof(float));
+  return (int)std::min<size_t>(kb, (size_t)std::min(K, W2_MAX_BLOCK));
+}
+
+// rows [k0, k0 + kb) of the projected + sorted set: dirs == nullptr takes features k0 .. k0 + kb instead
+static hipError_t w2_rows(const float* x, int n, int D, const float* dirs, int k0, int kb, float* dst, float* scratch,
+                          hipStream_t s) {
+  hipError_t e = dirs ? launch_w2_project(x, dirs + (size_t)k0 * D, dst, n, D, kb, s)
+                      : launch_w2_columns(x, dst, n, D, k0, kb, s);
+  if (e != hipSuccess) return e;
+  return launch_w2_sort(dst, scratch, n, kb, s);
+}
+
+static int w2_check(int n, int m, int D, int K) {
+  if (n < 1 || m < 1 || D < 1 || K < 1) return FFD_ERR_INVALID;
+  if (n > W2_MAX_N || m > W2_MAX_N || D > W2_MAX_D || K > W2_MAX_K) return FFD_ERR_UNSUPPORTED;
+  return FFD_OK;
+}
+
+size_t ffd_w2_work_bytes(int n, int m, int D, int K, size_t budget_bytes) {
+  if (n < 0 || m < 0 || n + m < 1 || D < 1 || K < 1) return 0;
+  const size_t per = w2_floats_per_dir(n, m) * sizeof(float);
+  size_t kb = budget_bytes / per;
+  kb = std::max<size_t>(1, std::min<size_t>(kb, (size_t)std::min(K, W2_MAX_BLOCK)));
+  return kb * per;
+}
+
+static int w2_run(const float* orig, int n, const float* other, int m, int D, const float* dirs, int K, int standardise,
+                  double* dist_out, void* work, size_t work_bytes, void* stream) {
+  if (!orig || !other || !dist_out || !work) return FFD_ERR_INVALID;
+  if (int rc = w2_check(n, m, D, K)) return rc;
+  const int Kb = w2_block(w2_floats_per_dir(n, m), K, work_bytes);
+  if (Kb < 1) return FFD_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  float* pa = (float*)work;
+  float* pb = pa + (size_t)Kb * n;
+  float* scratch = pb + (size_t)Kb * m;
+  for (int k0 = 0; k0 < K; k0 += Kb) {
+    const int kb = std::min(Kb, K - k0);
+    if (w2_rows(orig, n, D, dirs, k0, kb, pa, scratch, s) != hipSuccess) return FFD_ERR_HIP;
+    if (w2_rows(other, m, D, dirs, k0, kb, pb, scratch, s) != hipSuccess) return FFD_ERR_HIP;
+    if (launch_w2_integral(pa, n, pb, m, standardise, dist_out + k0, kb, s) != hipSuccess) return FFD_ERR_HIP;
+  }
+  return FFD_OK;
+}
+
+int ffd_w2_sliced(const float* orig, int n, const float* other, int m, int D, const float* dirs, int K, int standardise,
+                  double* dist_out, void* work, size_t work_bytes, void* stream) {
+  if (!dirs) return FFD_ERR_INVALID;
+  return w2_run(orig, n, other, m, D, dirs, K, standardise, dist_out, work, work_bytes, stream);
+}
+
+int ffd_w2_marginal(const float* orig, int n, const float* other, int m, int D, int standardise, double* dist_out,
+                    void* work, size_t work_bytes, void* stream) {
+  return w2_run(orig, n, other, m, D, nullptr, D, standardise, dist_out, work, work_bytes, stream);
+}
+
+int ffd_w2_prepare(const float* x, int n, int D, const float* dirs, int K, float* prepared_out, void* work,
+                   size_t work_bytes, void* stream) {
+  if (!x || !prepared_out || !work) return FFD_ERR_INVALID;
+  if (int rc = w2_check(n, 1, D, K)) return rc;
+  if (!dirs && K != D) return FFD_ERR_INVALID;
+  const int Kb = w2_block(w2_floats_per_dir(n, 0), K, work_bytes);
+  if (Kb < 1) return FFD_ERR_INVALID;
+  for (int k0 = 0; k0 < K; k0 += Kb)
+    if (w2_rows(x, n, D, dirs, k0, std::min(Kb, K - k0), prepared_out + (size_t)k0 * n, (float*)work,
+                (hipStream_t)stream) != hipSuccess)
+      return FFD_ERR_HIP;
+  return FFD_OK;
+}
+
+int ffd_w2_against_prepared(const float* prepared, int n, const float* other, int m, int D, const float* dirs, int K,
+                            int standardise, double* dist_out, void* work, size_t work_bytes, void* stream) {
+  if (!prepared || !other || !dist_out || !work) return FFD_ERR_INVALID;
+  if (int rc = w2_check(n, m, D, K)) return rc;
+  if (!dirs && K != D) return FFD_ERR_INVALID;
+  const int Kb = w2_block(w2_floats_per_dir(0, m), K, work_bytes);
+  if (Kb < 1) return FFD_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  float* pb = (float*)work;
+  float* scratch = pb + (size_t)Kb * m;
+  for (int k0 = 0; k0 < K; k0 += Kb) {
+    const int kb = std::min(Kb, K - k0);
+    if (w2_rows(other, m, D, dirs, k0, kb, pb, scratch, s) != hipSuccess) return FFD_ERR_HIP;
+    if (launch_w2_integral(prepared + (size_t)k0 * n, n, pb, m, standardise, dist_out + k0, kb, s) != hipSuccess)
+      return FFD_ERR_HIP;
+  }
+  return FFD_OK;
+}
+
+int ffd_w2_summary(const double* dist, int K, double* mean_max_out, void* stream) {
+  if (!dist || !mean_max_out || K < 1) return FFD_ERR_INVALID;
+  return launch_w2_summary(dist, K, mean_max_out, (hipStream_t)stream) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+size_t ffd_col_mean_work_bytes(int n, int D) {
+  return n < 1 || D < 1 ? 0 : col_mean_work_doubles(n, D) * sizeof(double);
+}
+
+int ffd_col_mean(const float* x, int n, int D, float* mean_out, void* work, size_t work_bytes, void* stream) {
+  if (!x || !mean_out || !work || n < 1 || D < 1 || work_bytes < ffd_col_mean_work_bytes(n, D)) return FFD_ERR_INVALID;
+  if (n > W2_MAX_N / 2 || D > W2_MAX_D) return FFD_ERR_UNSUPPORTED;  // a 1024-row slab per grid row: 32768 of 65535
+  return launch_col_mean(x, n, D, mean_out, (double*)work, (hipStream_t)stream) == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+// Benchmark helper (tools/metrics_bench.py): the kernel classes of the metric one by one, HIP events around each.
+int ffd_w2_bench_kernels(const float* x, int n, int D, const float* dirs, int K, float* rows, float* scratch,
+                         const float* other_rows, int m, double* dist, int iters, float* ms_out, void* stream) {
+  if (!x || !dirs || !rows || !scratch || !other_rows || !dist || !ms_out || iters < 1 || K > W2_MAX_BLOCK)
+    return FFD_ERR_INVALID;
+  if (int rc = w2_check(n, m, D, K)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  struct Events {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t ev : e)
+        if (ev) (void)hipEventDestroy(ev);
+    }
+  } ev;
+  for (hipEvent_t& e : ev.e)
+    if (hipEventCreate(&e) != hipSuccess) return FFD_ERR_HIP;
+  double acc[4] = {0, 0, 0, 0};
+  float ms = 0.f;
+  auto lap = [&](int a, int b, double& into) {
+    if (hipEventElapsedTime(&ms, ev.e[a], ev.e[b]) != hipSuccess) return false;
+    into += ms;
+    return true;
+  };
+  for (int it = -1; it < iters; ++it) {  // iteration -1 warms up; the sort always meets freshly projected rows
+    bool ok = hipEventRecord(ev.e[0], s) == hipSuccess && launch_w2_project(x, dirs, rows, n, D, K, s) == hipSuccess &&
+              hipEventRecord(ev.e[1], s) == hipSuccess && launch_w2_sort(rows, scratch, n, K, s) == hipSuccess &&
+              hipEventRecord(ev.e[2], s) == hipSuccess && hipEventSynchronize(ev.e[2]) == hipSuccess;
+    double skip = 0;
+    ok = ok && lap(0, 1, it < 0 ? skip : acc[0]) && lap(1, 2, it < 0 ? skip : acc[1]);
+    ok = ok && hipEventRecord(ev.e[0], s) == hipSuccess &&
+         launch_w2_integral(rows, n, other_rows, m, 0, dist, K, s) == hipSuccess &&
+         hipEventRecord(ev.e[1], s) == hipSuccess && launch_w2_columns(x, scratch, n, D, 0, std::min(K, D), s) == hipSuccess &&
+         hipEventRecord(ev.e[2], s) == hipSuccess && hipEventSynchronize(ev.e[2]) == hipSuccess;
+    ok = ok && lap(0, 1, it < 0 ? skip : acc[2]) && lap(1, 2, it < 0 ? skip : acc[3]);
+    if (!ok) return FFD_ERR_HIP;
+  }
+  for (int i = 0; i < 4; ++i) ms_out[i] = (float)(acc[i] / iters);
+  return FFD_OK;
+}
+
+}  // extern "C"
