@@ -283,11 +283,11 @@ __global__ __launch_bounds__(256, (MB <= 4 ? 2 : 1)) void k_ffn_ln(const float* 
       __builtin_amdgcn_sched_barrier(0);
       load_w1(nx);
       __builtin_amdgcn_sched_barrier(0);
-      // relu as one v_med3_f32 (x, 0, +inf) per element
+      // relu as one v_max_i32 per element (relu_bits; a float max of an MFMA result is two instructions)
 #pragma unroll
       for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) h[mb][r] = __builtin_amdgcn_fmed3f(h[mb][r], 0.f, __builtin_inff());
+        for (int r = 0; r < 4; ++r) h[mb][r] = relu_bits(h[mb][r]);
       // GEMM2: Y^T += W2[:, chunk] H^T chunk ; accumulator register r is the k-step
 #pragma unroll
       for (int r = 0; r < 4; ++r)

@@ -603,11 +603,11 @@ __global__ __launch_bounds__(64 * NW, 3) void k_ffn_rows(const float* __restrict
             // ---- GEMM2: Y^T += W2[:, chunk] relu(H^T chunk); accumulator register r is the k pair (f_r, f_r + 4) ----
             const int idx = 4 * (k - NQ1) + j, r = idx / CTA, ct = idx % CTA;
             yacc[ct] = mfma32(f4e(w, j), h[r], yacc[ct]);
-            if (j == 0) {  // relu (one v_med3_f32 (x, 0, +inf) per element)
+            if (j == 0) {  // relu (one v_max_i32 per element: relu_bits)
 #pragma unroll
               for (int rr = 0; rr < RPG; ++rr) {
                 const int rn = (k - NQ1 + 1) * RPG + rr;
-                if (rn < 16) h[rn] = __builtin_amdgcn_fmed3f(h[rn], 0.f, __builtin_inff());
+                if (rn < 16) h[rn] = relu_bits(h[rn]);
               }
             }
           } else {
@@ -638,7 +638,7 @@ __global__ __launch_bounds__(64 * NW, 3) void k_ffn_rows(const float* __restrict
         if (k == NQ1 - 1) {
           // relu of the accumulator registers the first GEMM2 group reads
 #pragma unroll
-          for (int r = 0; r < RPG; ++r) h[r] = __builtin_amdgcn_fmed3f(h[r], 0.f, __builtin_inff());
+          for (int r = 0; r < RPG; ++r) h[r] = relu_bits(h[r]);
           if (c == CPS - 1) {
             // ---- the slot's barrier: my pieces of slot it+1 have landed; afterwards slot it+1 is readable by
             //      everyone and nobody reads slot it-1 any more.  In flight and allowed to stay so: the slots after

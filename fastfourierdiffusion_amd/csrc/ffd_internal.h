@@ -25,6 +25,17 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 
 constexpr __host__ __device__ int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// relu as ONE vector instruction (v_max_i32): max of the bit pattern, as a signed integer, with 0.  Negative floats
+// and -0.0 are negative integers -> +0.0; +0.0, positive floats and +inf are themselves: for every non-NaN x the bits
+// of fmaxf(x, 0).  (A float max / med3 of an MFMA result costs two: hipcc cannot prove the accumulator canonical and
+// puts a quieting v_max_f32 x, x, x in front, and on this chip a vector instruction in a matrix-bound loop is matrix
+// time lost.  Plain C++ on purpose: behind an inline-asm v_max_f32 the compiler no longer inserts the MFMA-write ->
+// VALU-read wait states.)
+__device__ __forceinline__ float relu_bits(float x) {
+  const int i = __builtin_bit_cast(int, x);
+  return __builtin_bit_cast(float, i > 0 ? i : 0);
+}
+
 // ---- ffd_tune knobs: each a thread_local int (a thread's knobs select the kernels of the launches it makes; a new
 // thread starts from the defaults).  I(key, variable, default, accepted values of v); B(key, variable, default): any
 // value, stored as 0 / 1.  ffd_tune, ffd_tune_get, "reset" and the definitions are generated from this table.

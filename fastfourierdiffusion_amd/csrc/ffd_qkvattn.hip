@@ -794,10 +794,11 @@ __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
   constexpr int NW = 2 * HPW;           // waves per workgroup
   constexpr int MAXT = 3;               // token tiles per wave: Lp <= 192 -> 12 tiles over >= 4 waves
   // Two heads of head_dim 6 are 36 features: two 16-wide tiles + 4 (head 1's v[2..5]).  A third tile would be three
-  // quarters padding; the four features are vector-ALU dot products instead (each lane holds 18 of its token's 72 x
-  // values as A operand anyway: 4 x 18 FMAs + two xor-shuffles per 16 tokens, like k_qkv_attention's two).  Round 3 ran
-  // them on v_mfma_f32_4x4x1_16b_f32 (lane = token), which needed every x row a second time in that layout (55 KB more
-  // L2 reads per workgroup, 72 registers): 100.4 -> 99.8 us at ECG B = 512 without it.
+  // quarters padding; the four features are partial dot products over the 18 of its token's 72 x values each lane holds
+  // as A operand anyway, added up over the token's four lanes (two xor-shuffles).  They run on v_mfma_f32_4x4x1_16b_f32
+  // with those x registers as B operand as they are (18 steps = 144 matrix cycles per 16 tokens, 18 weight registers);
+  // as vector-ALU FMAs (round 4) they were 72 v_fmac = 288 cycles and 72 weight registers, and fp32 vector time adds to
+  // matrix time on a SIMD.  (Round 3's 4x4x1 form was lane = token and read every x row a second time: dropped.)
   constexpr bool REMV = HD == 6 && HPW == 2 && NCT == 3;
   constexpr int NCTM = REMV ? 2 : NCT;  // 16-wide feature tiles on the 16x16x4 form
   extern __shared__ __align__(16) float lds[];
@@ -859,36 +860,47 @@ __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
     }
     __syncthreads();
     if constexpr (STAMP) st.t[2] = FFD_STAMP_T();
-    // columns n = 0 .. 3 of the pack's third tile for this lane's k subset (qq), from the staged pack
-    float4 wv4[REMV ? 4 : 1][REMV ? C16 : 1];
-    float2 wvr[REMV ? 4 : 1];
+    // The third tile's columns 0 .. 3 as the A operand of the 4x4x1 form: block b = lane >> 2 pairs A[lane 4 b + i] with
+    // B[lane 4 b + j], and the four lanes of a block share qq (= b >> 2), so with A = column (lane & 3) over this lane's k
+    // subset and B = the x values the lane holds anyway, output register i of lane (qq, n) is the partial dot product
+    // of feature 32 + i and token n over qq's k values: one k per step, in the order of the former FMA chain.
+    float wrem[REMV ? 4 * C16 + REM : 1];
     float bvv[REMV ? 4 : 1];
     if constexpr (REMV) {
+      static_assert(!REMV || REM <= 4, "remainder k-steps come from one staged float4");
 #pragma unroll
-      for (int f = 0; f < 4; ++f) {
-#pragma unroll
-        for (int j = 0; j < C16; ++j) wv4[f][j] = wl[(2 * S4 + j) * 64 + 16 * qq + f];
-        const float4 r4 = wl[(2 * S4 + S4 - 1) * 64 + 16 * qq + f];
-        wvr[f] = float2{r4.x, r4.y};
-        bvv[f] = abp[2 * 16 + f];
+      for (int j = 0; j < C16; ++j) {
+        const float4 w4 = wl[(2 * S4 + j) * 64 + 16 * qq + (lane & 3)];
+        wrem[4 * j] = w4.x, wrem[4 * j + 1] = w4.y, wrem[4 * j + 2] = w4.z, wrem[4 * j + 3] = w4.w;
       }
+      if constexpr (REM > 0) {
+        const float4 r4 = wl[(2 * S4 + S4 - 1) * 64 + 16 * qq + (lane & 3)];
+#pragma unroll
+        for (int i = 0; i < REM; ++i) wrem[4 * C16 + i] = i == 0 ? r4.x : i == 1 ? r4.y : i == 2 ? r4.z : r4.w;
+      }
+#pragma unroll
+      for (int f = 0; f < 4; ++f) bvv[f] = abp[2 * 16 + f];
     }
 #pragma unroll
     for (int it = 0; it < MAXT; ++it) {
       const int tt = wave + it * NW;
       if (tt >= TT) break;
       if constexpr (REMV) {
+        // all of a tile's 4x4x1 steps together (switching MFMA forms step by step costs 47 cycles each: ffd_ffn_rows.hip)
+        f32x4 pr = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < C16; ++j) {
+          pr = __builtin_amdgcn_mfma_f32_4x4x1f32(wrem[4 * j], xa[it][j].x, pr, 0, 0, 0);
+          pr = __builtin_amdgcn_mfma_f32_4x4x1f32(wrem[4 * j + 1], xa[it][j].y, pr, 0, 0, 0);
+          pr = __builtin_amdgcn_mfma_f32_4x4x1f32(wrem[4 * j + 2], xa[it][j].z, pr, 0, 0, 0);
+          pr = __builtin_amdgcn_mfma_f32_4x4x1f32(wrem[4 * j + 3], xa[it][j].w, pr, 0, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < REM; ++i) pr = __builtin_amdgcn_mfma_f32_4x4x1f32(wrem[4 * C16 + i], xr[it][i], pr, 0, 0, 0);
         float pv[4];
 #pragma unroll
-        for (int f = 0; f < 4; ++f) {
-          float p = 0.f;
-#pragma unroll
-          for (int j = 0; j < C16; ++j) {
-            p = fmaf(xa[it][j].x, wv4[f][j].x, p), p = fmaf(xa[it][j].y, wv4[f][j].y, p);
-            p = fmaf(xa[it][j].z, wv4[f][j].z, p), p = fmaf(xa[it][j].w, wv4[f][j].w, p);
-          }
-#pragma unroll
-          for (int i = 0; i < REM; ++i) p = fmaf(xr[it][i], i == 0 ? wvr[f].x : wvr[f].y, p);
+        for (int f = 0; f < 4; ++f) {  // the token's four lanes (k subsets qq = 0 .. 3, 16 lanes apart) add up
+          float p = pr[f];
           p += __shfl_xor(p, 16);
           p += __shfl_xor(p, 32);
           pv[f] = p + bvv[f];
