@@ -233,10 +233,19 @@ LayerPlan plan_layer(const ffd_model_desc& m, int B, CacheMode mode, const PackS
   p.attn = g_attn_fused && pk.aw_full ? ATTN_FUSED : ATTN_TWO_KERNEL;
   p.hpw = 1;
   p.q_only = mode == CACHE_PURE;
+  const int QT = cdiv(L, 32);
   if (p.attn == ATTN_FUSED) {
     p.kspl = qkv_attention_small_split(B, H, L);
     if (pk.aw_full2 && !p.kspl) p.hpw = qkv_attention_hpw(d, hd, L);
     if (g_attn_kvq && pk.aw_kvq && mode != CACHE_PURE && p.kspl) p.q_only = 2;
+    // q-tiles per wave: the split form has one; a wave pair of the two-heads form takes half the q-tiles; attn_qg = 1 / 2
+    // forces the instances of the full pack only (the q-only ones ignore it, and 3 means the heuristic here)
+    p.qg = p.kspl                                               ? 1
+           : p.hpw == 2                                         ? cdiv(QT, 2)
+           : !p.q_only && (g_attn_qg == 1 || g_attn_qg == 2)    ? g_attn_qg
+                                                                : attn_qg(QT, hd, true);
+  } else {
+    p.qg = QT == 1 ? 1 : g_attn_qg ? g_attn_qg : attn_qg(QT, hd, false);
   }
   // FFN, in order of precedence: the opt-in bf16 split at every size; one 32- / 48-row k_ffn_ln tile per CU where the
   // 16-row tiles are 1.4 - 3 per CU (ahead of the small-M pair unless small_wgs is set, of the sliced k_ffn_rows unless
@@ -244,6 +253,7 @@ LayerPlan plan_layer(const ffd_model_desc& m, int B, CacheMode mode, const PackS
   // k_ffn_rows; the 64-row F slices; k_ffn_rows (out-projection inside where fused); k_ffn_ln
   const int hp = g_ffn_height && !g_ffn_split && !g_ffn_mb_override ? ffn_height_plan(M, d, F) : 0;
   int unf = 0;
+  auto rows_nw = [&] { return g_ffn_rows_nw ? g_ffn_rows_nw : rows_waves(M); };  // unsliced k_ffn_rows: waves per workgroup
   if (g_ffn_split) {
     p.ffn = FFN_SPLIT;
   } else if (hp && g_ffn_height == 1) {
@@ -251,20 +261,22 @@ LayerPlan plan_layer(const ffd_model_desc& m, int B, CacheMode mode, const PackS
   } else if (!(hp && g_small_wgs == 0) && (p.ns = small_path_splits(M, d, F))) {
     p.ffn = FFN_SMALL, p.part_floats = small_path_partial_floats(M, d, p.ns);
   } else if (pk.ring && !(hp && g_rows_slices == 0) && rows_slice_plan(M, d, F, &p.nw, &p.nslice, &unf)) {
-    p.ffn = unf ? FFN_ROWS_SLICED : FFN_ROWS_SLICED_OPROJ, p.part_floats = rows_slice_floats(M, d, p.nslice);
+    p.ffn = unf ? FFN_ROWS_SLICED : FFN_ROWS_SLICED_OPROJ, p.cps = 2, p.part_floats = rows_slice_floats(M, d, p.nslice);
   } else if ((p.nm = hp && g_mid_path == 1 ? 0 : mid_path_splits(M, d, F))) {
     p.ffn = FFN_MID, p.part_floats = small_path_partial_floats(cdiv(M, 64) * 64, d, p.nm);
   } else if (pk.ring && ffn_rows_fused_selected(M, d, F)) {
-    p.ffn = FFN_ROWS_OPROJ;
+    p.ffn = FFN_ROWS_OPROJ, p.nw = rows_nw(), p.cps = 2;
   } else if (pk.ring && ffn_rows_selected(M, d, F)) {
-    p.ffn = FFN_ROWS;
+    p.ffn = FFN_ROWS, p.nw = rows_nw(), p.cps = g_ffn_rows_cps == 1 && d == 72 ? 1 : 2;  // (one-chunk slots: d_model 72 only)
   } else {
     // k_ffn_ln tiles of 16 MB rows: MB = 4 (two workgroups resident per CU) once the grid fills the chip, smaller tiles
     // for smaller M; ffn_height = 2 puts the 32- / 48-row tiles behind k_linear_res_ln
     p.ffn = FFN_LN;
     p.mb = g_ffn_mb_override >= 1 ? g_ffn_mb_override : cdiv(M, 64) >= 512 ? 4 : cdiv(M, 32) >= 512 ? 2 : 1;
     if (hp) p.mb = hp;
+    p.persist = g_ffn_persist;
   }
+  if (p.ffn == FFN_LN || p.ffn == FFN_LN_OPROJ) p.rem = g_ffn_rem && ffn_rem_rows(d, p.mb);
   p.oproj_separate = p.ffn >= FFN_ROWS_SLICED;
   p.swap = p.ffn == FFN_ROWS_SLICED_OPROJ || p.ffn == FFN_ROWS_OPROJ;
   return p;
@@ -637,15 +649,15 @@ static hipError_t run_attention(const ffd_ctx* ctx, const LayerPlan& p, const La
     const float* pack = p.q_only == 2 ? w.aw_kvq
                         : p.hpw == 2  ? (p.q_only ? w.aw_q2 : w.aw_full2)
                                       : (p.q_only ? w.aw_q : w.aw_full);
-    return launch_qkv_attention(x, pack, p.hpw, p.q_only, kt, vt, kt_out, vt_out, out, B, L, d, hd, n_own, p.kspl, s,
-                                stamp);
+    return launch_qkv_attention(AttnArgs{x, pack, kt, vt, kt_out, vt_out, out, B, L, n_own, stamp}, d, hd, p.hpw, p.q_only,
+                                p.kspl, p.qg, s);
   }
   if (stamp != nullptr) return hipErrorInvalidValue;
   // q / k / v regions, head-major (B,H,L,hd)
   const size_t M = (size_t)B * L;
   float *q = ctx->qkv.p, *k = q + M * d, *v = q + 2 * M * d;
   hipError_t e = launch_linear_hm(x, p.q_only ? w.q_wp : w.in_wp, w.in_b, q, k, v, (int)M, p.q_only ? 1 : 3, d, L, H, hd, s);
-  if (e == hipSuccess) e = launch_attention(q, k, v, kt, vt, out, B, L, H, hd, n_own, s);
+  if (e == hipSuccess) e = launch_attention(q, k, v, kt, vt, out, B, L, H, hd, n_own, p.qg, s);
   if (e == hipSuccess && kt_out)  // (caching.py:326-328, cached_transformer.py:301-305)
     e = launch_kv_store(k, v, kt_out, vt_out, L, H, hd, n_own, s);
   return e;
@@ -657,23 +669,30 @@ static hipError_t run_ffn(const ffd_ctx* ctx, const LayerPlan& p, const LayerWei
                           float* alt, int M, hipStream_t s, unsigned long long* stamp = nullptr) {
   const int d = ctx->desc.d_model, F = ctx->desc.dim_feedforward;
   float* P = ctx->ffn_part.p;
+  // k_ffn_rows: whole rows (the fused form: x1 never leaves the CU; rows are read and written by different waves, so no
+  // in-place form), or tiles x slices of the hidden dimension into P + the reduce / LN2 launch (slices added in order)
+  const bool sliced = p.ffn == FFN_ROWS_SLICED_OPROJ || p.ffn == FFN_ROWS_SLICED;
+  const bool fused = p.ffn == FFN_ROWS_SLICED_OPROJ || p.ffn == FFN_ROWS_OPROJ;
+  float* const y = fused ? alt : cur;
+  const RowsArgs rows{fused ? attn : alt, fused ? cur : nullptr, &w, sliced ? P : y, M, d, F, p.nw, p.cps, fused,
+                      sliced ? p.nslice : 0, stamp};
   switch (p.ffn) {
     case FFN_LN_OPROJ:  // one 32- / 48-row tile per CU, out-proj + LN1 + FFN + LN2 in one launch, in place
-      return stamp ? hipErrorInvalidValue : launch_oproj_ffn_ln(attn, cur, w, cur, M, d, F, p.mb, s);
+      return stamp ? hipErrorInvalidValue : launch_oproj_ffn_ln(attn, cur, w, cur, M, d, F, p.mb, p.rem, s);
     case FFN_SMALL:  // out-proj + LN1 recomputed per F split, FFN partials + a deterministic reduce / LN2 launch
       return stamp ? hipErrorInvalidValue : launch_oproj_ffn_small(attn, cur, w, alt, P, cur, M, d, F, p.ns, s);
-    case FFN_ROWS_SLICED_OPROJ:  // tiles x slices of the hidden dimension + the reduce / LN2 launch (slices added in order)
-      return stamp ? hipErrorInvalidValue
-                   : launch_oproj_ffn_rows_sliced(attn, cur, w, P, alt, M, d, F, p.nw, p.nslice, s);
-    case FFN_ROWS_OPROJ:  // x1 never leaves the CU; rows are read and written by different waves: no in-place form
-      return launch_oproj_ffn_rows(attn, cur, w, alt, M, d, F, s, stamp);
-    case FFN_ROWS_SLICED:
-      return stamp ? hipErrorInvalidValue : launch_ffn_rows_sliced(alt, w, P, cur, M, d, F, p.nw, p.nslice, s);
+    case FFN_ROWS_SLICED_OPROJ:
+    case FFN_ROWS_SLICED: {
+      if (stamp || p.nslice < 2) return hipErrorInvalidValue;
+      const hipError_t e = launch_ffn_rows(rows, s);
+      return e != hipSuccess ? e : launch_rows_reduce_ln(P, w, y, M, d, p.nslice, s);
+    }
+    case FFN_ROWS_OPROJ:
+    case FFN_ROWS: return launch_ffn_rows(rows, s);
     case FFN_MID:  // 64-row tiles x F slices, partial tiles + the reduce / LN2 launch
       return stamp ? hipErrorInvalidValue : launch_ffn_mid(alt, w, P, cur, M, d, F, p.nm, s);
     case FFN_SPLIT: return launch_ffn_ln_split(alt, w, cur, M, d, F, s, stamp);
-    case FFN_ROWS: return launch_ffn_rows(alt, w, cur, M, d, F, s, stamp);
-    case FFN_LN: return launch_ffn_ln(alt, w, cur, M, d, F, p.mb, s, stamp);
+    case FFN_LN: return launch_ffn_ln(alt, w, cur, M, d, F, p.mb, p.rem, p.persist, s, stamp);
   }
   return hipErrorInvalidValue;
 }

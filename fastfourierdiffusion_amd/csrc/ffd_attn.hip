@@ -181,21 +181,19 @@ static hipError_t launch_attn_mfma_t(const float* q, const float* k, const float
 
 template <int HD>
 static hipError_t launch_attn_mfma_hd(const float* q, const float* k, const float* v, const float* kt,
-                                      const float* vt, float* out, int B, int L, int H, int n_own, hipStream_t s) {
-  const int QT = (L + 31) / 32;
-  if (g_attn_qg == 1 || QT == 1) return launch_attn_mfma_t<HD, 1>(q, k, v, kt, vt, out, B, L, H, n_own, s);
-  if (g_attn_qg == 2) return launch_attn_mfma_t<HD, 2>(q, k, v, kt, vt, out, B, L, H, n_own, s);
-  if (g_attn_qg == 3) return launch_attn_mfma_t<HD, 3>(q, k, v, kt, vt, out, B, L, H, n_own, s);
-  if (QT % 3 == 0) return launch_attn_mfma_t<HD, 3>(q, k, v, kt, vt, out, B, L, H, n_own, s);
-  return launch_attn_mfma_t<HD, 2>(q, k, v, kt, vt, out, B, L, H, n_own, s);
+                                      const float* vt, float* out, int B, int L, int H, int n_own, int qg, hipStream_t s) {
+  if (qg == 1) return launch_attn_mfma_t<HD, 1>(q, k, v, kt, vt, out, B, L, H, n_own, s);
+  if (qg == 2) return launch_attn_mfma_t<HD, 2>(q, k, v, kt, vt, out, B, L, H, n_own, s);
+  if (qg == 3) return launch_attn_mfma_t<HD, 3>(q, k, v, kt, vt, out, B, L, H, n_own, s);
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_attention(const float* qkv, const float* k, const float* v, const float* kt, const float* vt,
-                            float* out, int B, int L, int H, int hd, int n_own, hipStream_t s) {
+                            float* out, int B, int L, int H, int hd, int n_own, int qg, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   switch (hd) {
 #define X(h) \
-    case h: return launch_attn_mfma_hd<h>(qkv, k, v, kt, vt, out, B, L, H, n_own, s);
+    case h: return launch_attn_mfma_hd<h>(qkv, k, v, kt, vt, out, B, L, H, n_own, qg, s);
     FFD_HD_LIST(X)
 #undef X
     default: return hipErrorInvalidValue;

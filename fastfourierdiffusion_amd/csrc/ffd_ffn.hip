@@ -546,19 +546,23 @@ int ffn_height_plan(int M, int D, int F) {
   return 0;
 }
 
+// The remainder rows (d_model % 16) of GEMM2 go to the 4x4x1 MFMA in the 48- and 64-row tiles of the d_models that have
+// some (ffd_tune "ffn_rem" turns it off)
+bool ffn_rem_rows(int D, int mb) { return mb >= 3 && D >= 16 && w2rem_groups(D) > 0; }
+
 template <int D>
-static hipError_t launch_ffn_d(const float* X, const LayerWeights& w, float* Y, int M, int F, int mb, hipStream_t s,
-                               unsigned long long* stamp) {
+static hipError_t launch_ffn_d(const float* X, const LayerWeights& w, float* Y, int M, int F, int mb, bool rem, int persist,
+                               hipStream_t s, unsigned long long* stamp) {
   dim3 block(256);
   // MB >= 4 is persistent: as many workgroups as the chip holds (two per CU at MB = 4, one at MB = 8)
-  const int resident = num_cus() * (mb == 4 ? 2 : 1) * (g_ffn_persist > 0 ? g_ffn_persist : 1);
+  const int resident = num_cus() * (mb == 4 ? 2 : 1) * (persist > 0 ? persist : 1);
   auto grid_of = [&](int mbv) {
     const int ntiles = cdiv(M, 16 * mbv);
-    return dim3((mbv >= 4 && g_ffn_persist != 0 && ntiles > resident) ? resident : ntiles);
+    return dim3((mbv >= 4 && persist != 0 && ntiles > resident) ? resident : ntiles);
   };
 #define FFD_LAUNCH_FFN(MBV)                                                                                       \
   do {                                                                                                            \
-    if (g_ffn_rem && MBV >= 3 && D >= 16 && w2rem_groups(D) > 0)                                                                       \
+    if (rem)                                                                                                      \
       hipLaunchKernelGGL((k_ffn_ln<D, MBV, true>), grid_of(MBV), block, 0, s, X, w.w1p, w.b1, w.w2p,             \
                          w.w2r, w.b2, w.n2w, w.n2b, Y, M, F, stamp, FfnOprojArgs{});                      \
     else                                                                                                          \
@@ -579,11 +583,11 @@ static hipError_t launch_ffn_d(const float* X, const LayerWeights& w, float* Y, 
 // tile per CU; cached_transformer.py:316-327).  Y may be Rres.
 template <int D>
 static hipError_t launch_oproj_ffn_d(const float* attn, const float* Rres, const LayerWeights& w, float* Y, int M, int F,
-                                     int mb, hipStream_t s) {
+                                     int mb, bool rem, hipStream_t s) {
   const FfnOprojArgs op{Rres, w.out_wp, w.out_b, w.n1w, w.n1b};
   const dim3 block(256), grid(cdiv(M, 16 * mb));
   if (mb == 3) {
-    if (g_ffn_rem && D >= 16 && w2rem_groups(D) > 0)
+    if (rem)
       hipLaunchKernelGGL((k_ffn_ln<D, 3, true, true>), grid, block, 0, s, attn, w.w1p, w.b1, w.w2p, w.w2r, w.b2, w.n2w, w.n2b,
                          Y, M, F, nullptr, op);
     else
@@ -602,25 +606,25 @@ static hipError_t launch_oproj_ffn_d(const float* attn, const float* Rres, const
 }
 
 hipError_t launch_oproj_ffn_ln(const float* attn, const float* Rres, const LayerWeights& w, float* Y, int M, int D, int F,
-                               int mb, hipStream_t s) {
+                               int mb, bool rem, hipStream_t s) {
   if (M <= 0) return hipSuccess;
-  if (w.out_wp == nullptr) return hipErrorInvalidValue;
+  if (w.out_wp == nullptr || (rem && !ffn_rem_rows(D, mb))) return hipErrorInvalidValue;
   switch (D) {
 #define X(d) \
-    case d: return launch_oproj_ffn_d<d>(attn, Rres, w, Y, M, F, mb, s);
+    case d: return launch_oproj_ffn_d<d>(attn, Rres, w, Y, M, F, mb, rem, s);
     FFD_D_LIST(X)
 #undef X
     default: return hipErrorInvalidValue;
   }
 }
 
-hipError_t launch_ffn_ln(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, int mb, hipStream_t s,
-                         unsigned long long* stamp) {
+hipError_t launch_ffn_ln(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, int mb, bool rem, int persist,
+                         hipStream_t s, unsigned long long* stamp) {
   if (M <= 0) return hipSuccess;
-  if (F % 64 != 0) return hipErrorInvalidValue;
+  if (F % 64 != 0 || (rem && !ffn_rem_rows(D, mb))) return hipErrorInvalidValue;
   switch (D) {
 #define X(d) \
-    case d: return launch_ffn_d<d>(X, w, Y, M, F, mb, s, stamp);
+    case d: return launch_ffn_d<d>(X, w, Y, M, F, mb, rem, persist, s, stamp);
     FFD_D_LIST(X)
 #undef X
     default: return hipErrorInvalidValue;

@@ -702,10 +702,17 @@ __global__ __launch_bounds__(64 * NW, 3) void k_ffn_rows(const float* __restrict
   }
 }
 
-#ifndef FFD_ROWS_EXTRA_D
 // d_model values with an instance (round 4: 48, 60 -- the reference's class default, score_models.py:31 -- and 64 beside
 // 72; the compacted remainder groups are what fits d_model 60's seven of them into the ring)
-bool ffn_rows_supported(int D, int F) { return (D == 72 || D == 64 || D == 60 || D == 48) && F % 64 == 0 && F >= 64; }
+#define FFD_ROWS_D_LIST(X) X(72) X(64) X(60) X(48)
+
+#ifndef FFD_ROWS_EXTRA_D
+bool ffn_rows_supported(int D, int F) {
+#define X(d) if (D == d) return F % 64 == 0 && F >= 64;
+  FFD_ROWS_D_LIST(X)
+#undef X
+  return false;
+}
 // large M: where k_ffn_ln ran its 64-row persistent form
 bool ffn_rows_selected(int M, int D, int F) {
   return g_ffn_rows && ffn_rows_supported(D, F) && (g_ffn_rows == 2 || cdiv(M, 64) >= 512);
@@ -805,17 +812,23 @@ bool rows_slice_plan(int M, int D, int F, int* nw_out, int* nslice_out, int* unf
 }
 size_t rows_slice_floats(int M, int D, int nslice) { return (size_t)nslice * M * D; }
 
-#endif
+// Waves per workgroup: a tile is 32 NW rows and every CU walks ceil(tiles / CUs) of them at NW / 4 waves per SIMD.
+// Pick the NW with the least estimated time = passes x waves per SIMD / measured main-loop efficiency
+// (tools/ffn_rows_sweep.py at the ECG B = 512 shape: 0.85 / 0.915 / 0.938 of the matrix pipe at 1 / 2 / 3 waves per
+// SIMD); ties go to more waves (the weights are then streamed fewer times).  ffd_tune "ffn_rows_nw" forces it.
+int rows_waves(int M) {
+  const double eff[3] = {0.85, 0.915, 0.938};
+  double best = 0.0;
+  int nw = 0;
+  for (int i = 2; i >= 0; --i) {
+    const int cand = 4 * (i + 1);
+    const double t = (double)cdiv(cdiv(M, 32 * cand), num_cus()) * (i + 1) / eff[i];
+    if (best == 0.0 || t < best * 0.999) best = t, nw = cand;
+  }
+  return nw;
+}
 
-struct RowsArgs {
-  const float *X, *Rin;  // fused: attention output + layer input; else the FFN input (Rin unused)
-  const LayerWeights* w;
-  float* Y;
-  int M, F;
-  bool fused;
-  unsigned long long* stamp;
-  int nslice = 0;  // > 0: the sliced form (Y = the partial rows [nslice][M][D])
-};
+#endif
 
 template <int D, int NW, int CPS, int NSLOT>
 static hipError_t launch_rows_cfg(const RowsArgs& a, hipStream_t s) {
@@ -870,32 +883,17 @@ static hipError_t launch_rows_cfg(const RowsArgs& a, hipStream_t s) {
 }
 
 template <int D>
-hipError_t launch_rows_d(const RowsArgs& a, hipStream_t s, int nw_forced) {
-  // Waves per workgroup: a tile is 32 NW rows and every CU walks ceil(tiles / CUs) of them at NW / 4 waves per SIMD.
-  // Pick the NW with the least estimated time = passes x waves per SIMD / measured main-loop efficiency
-  // (tools/ffn_rows_sweep.py at the ECG B = 512 shape: 0.85 / 0.915 / 0.938 of the matrix pipe at 1 / 2 / 3 waves per
-  // SIMD); ties go to more waves (the weights are then streamed fewer times).  ffd_tune "ffn_rows_nw" forces it.
-  int nw = nw_forced ? nw_forced : g_ffn_rows_nw;
-  if (nw != 4 && nw != 8 && nw != 12) {
-    const double eff[3] = {0.85, 0.915, 0.938};
-    double best = 0.0;
-    for (int i = 2; i >= 0; --i) {
-      const int cand = 4 * (i + 1);
-      const double t = (double)cdiv(cdiv(a.M, 32 * cand), num_cus()) * (i + 1) / eff[i];
-      if (best == 0.0 || t < best * 0.999) best = t, nw = cand;
-    }
-  }
-  const int cps = g_ffn_rows_cps == 1 ? 1 : 2;  // 32-unit chunks per ring slot = per barrier (ffd_tune "ffn_rows_cps")
+hipError_t launch_rows_d(const RowsArgs& a, hipStream_t s) {
   if constexpr (D == 72) {  // (one-chunk slots: an experiment knob of the d_model 72 instances only)
-    if (cps == 1) {
-      switch (nw) {
+    if (a.cps == 1) {
+      switch (a.nw) {
         case 4: return launch_rows_cfg<72, 4, 1, 4>(a, s);
         case 8: return launch_rows_cfg<72, 8, 1, 4>(a, s);
         default: return launch_rows_cfg<72, 12, 1, 4>(a, s);
       }
     }
   }
-  switch (nw) {
+  switch (a.nw) {
     case 4: return launch_rows_cfg<D, 4, 2, 3>(a, s);
     case 8: return launch_rows_cfg<D, 8, 2, 3>(a, s);
     default: return launch_rows_cfg<D, 12, 2, 3>(a, s);
@@ -903,64 +901,30 @@ hipError_t launch_rows_d(const RowsArgs& a, hipStream_t s, int nw_forced) {
 }
 
 #ifdef FFD_ROWS_EXTRA_D
-template hipError_t launch_rows_d<FFD_ROWS_EXTRA_D>(const RowsArgs&, hipStream_t, int);
+template hipError_t launch_rows_d<FFD_ROWS_EXTRA_D>(const RowsArgs&, hipStream_t);
 #else
 // (d_model 64 / 60 / 48: instantiated in ffd_ffn_rows_d64.hip / _d60 / _d48, which compile this file with FFD_ROWS_EXTRA_D set -- in parallel)
-extern template hipError_t launch_rows_d<64>(const RowsArgs&, hipStream_t, int);
-extern template hipError_t launch_rows_d<60>(const RowsArgs&, hipStream_t, int);
-extern template hipError_t launch_rows_d<48>(const RowsArgs&, hipStream_t, int);
-static hipError_t launch_rows_any(const RowsArgs& a, int D, hipStream_t s, int nw_forced = 0) {
+extern template hipError_t launch_rows_d<64>(const RowsArgs&, hipStream_t);
+extern template hipError_t launch_rows_d<60>(const RowsArgs&, hipStream_t);
+extern template hipError_t launch_rows_d<48>(const RowsArgs&, hipStream_t);
+
+hipError_t launch_ffn_rows(const RowsArgs& a, hipStream_t s) {
   if (a.M <= 0) return hipSuccess;
-  if (!ffn_rows_supported(D, a.F) || a.w->ring == nullptr || (a.fused && a.w->ring_op == nullptr)) return hipErrorInvalidValue;
-  switch (D) {
-    case 72: return launch_rows_d<72>(a, s, nw_forced);
-    case 64: return launch_rows_d<64>(a, s, nw_forced);
-    case 60: return launch_rows_d<60>(a, s, nw_forced);
-    case 48: return launch_rows_d<48>(a, s, nw_forced);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-hipError_t launch_ffn_rows(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, hipStream_t s,
-                           unsigned long long* stamp) {
-  return launch_rows_any(RowsArgs{X, nullptr, &w, Y, M, F, false, stamp}, D, s);
-}
-
-// Y = LN2(x1 + FFN(x1)), x1 = LN1(Rin + Wo attn + bo): cached_transformer.py:316-327 in one launch.  Y must not alias
-// attn or Rin (a wave's stores and another wave's loads are not ordered).
-hipError_t launch_oproj_ffn_rows(const float* attn, const float* Rin, const LayerWeights& w, float* Y, int M, int D,
-                                 int F, hipStream_t s, unsigned long long* stamp) {
-  return launch_rows_any(RowsArgs{attn, Rin, &w, Y, M, F, true, stamp}, D, s);
-}
-
-// The same for mid-size M as tiles x nslice units + the reduce / LN2 launch; P holds nslice x M x D floats.
-hipError_t launch_oproj_ffn_rows_sliced(const float* attn, const float* Rin, const LayerWeights& w, float* P, float* Y,
-                                        int M, int D, int F, int nw, int nslice, hipStream_t s) {
-  if (!ffn_rows_supported(D, F) || nslice < 2) return hipErrorInvalidValue;
-  RowsArgs a{attn, Rin, &w, P, M, F, true, nullptr};
-  a.nslice = nslice;
-  const hipError_t e = launch_rows_any(a, D, s, nw);
-  if (e != hipSuccess) return e;
-  switch (D) {
-#define X(d) case d: hipLaunchKernelGGL(k_rows_reduce_ln<d>, dim3(cdiv(M, 8)), dim3(256), 0, s, P, nslice, M, w.n2w, w.n2b, Y); break;
-    X(72) X(64) X(60) X(48)
+  if (!ffn_rows_supported(a.D, a.F) || a.w->ring == nullptr || (a.fused && a.w->ring_op == nullptr) ||
+      (a.nw != 4 && a.nw != 8 && a.nw != 12) || (a.cps != 2 && !(a.cps == 1 && a.D == 72)))
+    return hipErrorInvalidValue;
+  switch (a.D) {
+#define X(d) case d: return launch_rows_d<d>(a, s);
+    FFD_ROWS_D_LIST(X)
 #undef X
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 
-// The same slicing on x1 rows (k_linear_res_ln has run): Y = LN2(x1 + FFN(x1)); P holds nslice x M x D floats.
-hipError_t launch_ffn_rows_sliced(const float* X1, const LayerWeights& w, float* P, float* Y, int M, int D, int F, int nw,
-                                  int nslice, hipStream_t s) {
-  if (!ffn_rows_supported(D, F) || nslice < 2) return hipErrorInvalidValue;
-  RowsArgs a{X1, nullptr, &w, P, M, F, false, nullptr};
-  a.nslice = nslice;
-  const hipError_t e = launch_rows_any(a, D, s, nw);
-  if (e != hipSuccess) return e;
+hipError_t launch_rows_reduce_ln(const float* P, const LayerWeights& w, float* Y, int M, int D, int nslice, hipStream_t s) {
   switch (D) {
 #define X(d) case d: hipLaunchKernelGGL(k_rows_reduce_ln<d>, dim3(cdiv(M, 8)), dim3(256), 0, s, P, nslice, M, w.n2w, w.n2b, Y); break;
-    X(72) X(64) X(60) X(48)
+    FFD_ROWS_D_LIST(X)
 #undef X
     default: return hipErrorInvalidValue;
   }

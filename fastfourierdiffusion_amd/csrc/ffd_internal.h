@@ -174,35 +174,42 @@ hipError_t launch_linear(const float* X, const float* Wp, const float* bias, flo
 // Y[M x D] = LayerNorm(R + X Wp^T + b) * g + beta    (out-proj + residual + LN1)
 hipError_t launch_linear_res_ln(const float* X, const float* Wp, const float* bias, const float* R, const float* g,
                                 const float* beta, float* Y, int M, int D, hipStream_t s);
-// Fused FFN: Y = LN2(X + W2 relu(W1 X + b1) + b2) in 16 mb-row tiles (k_ffn_ln)
+// Fused FFN: Y = LN2(X + W2 relu(W1 X + b1) + b2) in 16 mb-row tiles (k_ffn_ln); rem: the instance with GEMM2's remainder
+// rows on the 4x4x1 MFMA (only where ffn_rem_rows); persist (mb = 4): 0 a workgroup per tile, n: a grid of n x the resident ones
 // stamp != nullptr (diagnostics): per-workgroup (shader-clock, 100 MHz real-time) deltas around the main loop
-hipError_t launch_ffn_ln(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, int mb, hipStream_t s,
-                         unsigned long long* stamp = nullptr);
+bool ffn_rem_rows(int D, int mb);
+hipError_t launch_ffn_ln(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, int mb, bool rem, int persist,
+                         hipStream_t s, unsigned long long* stamp = nullptr);
 // 16-row tiles per CU between 1.4 and 3: k_ffn_ln at 32 / 48 rows per workgroup (one tile per CU); 0 = not this form
 int ffn_height_plan(int M, int D, int F);
 // ... as ONE launch (mb = 1 / 2 / 3), out-projection + LN1 inside; Y may be Rres
 hipError_t launch_oproj_ffn_ln(const float* attn, const float* Rres, const LayerWeights& w, float* Y, int M, int D, int F,
-                               int mb, hipStream_t s);
+                               int mb, bool rem, hipStream_t s);
 // Row-owning FFN with a CU-shared LDS weight ring (ffd_ffn_rows.hip): the large-M form
 bool ffn_rows_supported(int D, int F);
 bool ffn_rows_selected(int M, int D, int F);
 size_t ffn_ring_floats(int D, int F);
 hipError_t launch_pack_ffn_ring(const float* W1, const float* b1, const float* W2, float* out, int D, int F, hipStream_t s);
-hipError_t launch_ffn_rows(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, hipStream_t s,
-                           unsigned long long* stamp = nullptr);
-// out-proj + LN1 + FFN + LN2 in one launch (the fused form of k_ffn_rows); Y must not alias attn / Rin
+// One k_ffn_rows launch as the plan says: nw waves per workgroup, cps 32-unit chunks per ring slot
+struct RowsArgs {
+  const float *X, *Rin;  // fused: attention output + layer input; else the FFN input (Rin unused)
+  const LayerWeights* w;
+  float* Y;  // fused: must not alias X / Rin (rows are read and written by different waves); sliced: the partial rows
+  int M, D, F;
+  int nw, cps;
+  bool fused;  // out-proj + LN1 + FFN + LN2 in one launch: Y = LN2(x1 + FFN(x1)), x1 = LN1(Rin + Wo X + bo)
+  int nslice;  // >= 2: the sliced form of mid-size M, tiles x nslice units (Y = [nslice][M][D]); 0: whole rows
+  unsigned long long* stamp;
+};
+int rows_waves(int M);  // waves per workgroup of the unsliced forms
+hipError_t launch_ffn_rows(const RowsArgs& a, hipStream_t s);
 bool ffn_rows_fused_selected(int M, int D, int F);
 size_t ffn_ring_oproj_floats(int D);
 hipError_t launch_pack_oproj_ring(const float* Wo, float* out, int D, hipStream_t s);
-hipError_t launch_oproj_ffn_rows(const float* attn, const float* Rin, const LayerWeights& w, float* Y, int M, int D,
-                                 int F, hipStream_t s, unsigned long long* stamp = nullptr);
-// mid-size M: the fused kernel over tiles x slices of the hidden dimension + a reduce / LN2 launch
+// mid-size M: the kernel over tiles x slices of the hidden dimension, then Y = LN2(the partial rows P added in slice order)
 bool rows_slice_plan(int M, int D, int F, int* nw_out, int* nslice_out, int* unfused_out);
-hipError_t launch_ffn_rows_sliced(const float* X1, const LayerWeights& w, float* P, float* Y, int M, int D, int F, int nw,
-                                  int nslice, hipStream_t s);
 size_t rows_slice_floats(int M, int D, int nslice);
-hipError_t launch_oproj_ffn_rows_sliced(const float* attn, const float* Rin, const LayerWeights& w, float* P, float* Y,
-                                        int M, int D, int F, int nw, int nslice, hipStream_t s);
+hipError_t launch_rows_reduce_ln(const float* P, const LayerWeights& w, float* Y, int M, int D, int nslice, hipStream_t s);
 // Small M (the reference harness's batch 1): out-proj + LN1 + FFN + LN2 as two launches with F split over NS
 // workgroups per 16-row tile (ffd_small.hip).  small_path_splits returns 0 where this form does not apply.
 int small_path_splits(int M, int D, int F);
@@ -226,20 +233,28 @@ hipError_t launch_pack_attn(const float* in_w, const float* in_b, float* pack, i
 bool qkv_attention_supported(int D, int hd);
 int qkv_attention_hpw(int D, int hd, int L);
 int qkv_attention_small_split(int B, int H, int L);
+int attn_qg(int QT, int hd, bool fused);  // q-tiles per wave at QT q-tiles: of k_qkv_attention (fused), else of k_attention_mfma
 int num_cus();  // compute units of the current device (256 on MI355X); ffd_ffn.hip
-// kspl > 0: the small-batch split form with that many key pieces per q-tile (hpw 1; no stamped twin)
-hipError_t launch_qkv_attention(const float* x, const float* awp, int hpw, int q_only, const float* kt,
-                                const float* vt, float* kt_out, float* vt_out, float* out, int B, int L, int D, int hd,
-                                int n_own, int kspl, hipStream_t s, unsigned long long* stamp = nullptr);
+struct AttnArgs {
+  const float *x, *pack;    // the layer's input rows; the in-projection pack that (hpw, q_only) name
+  const float *kt, *vt;     // the layer's K/V tables to read (cached modes), else nullptr
+  float *kt_out, *vt_out;   // where batch element 0's recomputed rows go (MIXED), else nullptr
+  float* out;               // (M x d) row-major
+  int B, L, n_own;          // tokens >= n_own take K/V from the tables
+  unsigned long long* stamp;
+};
+// kspl > 0: the small-batch split form with that many key pieces per q-tile (hpw 1; no stamped twin); else qg q-tiles per
+// wave (hpw 2: per wave pair)
+hipError_t launch_qkv_attention(const AttnArgs& a, int D, int hd, int hpw, int q_only, int kspl, int qg, hipStream_t s);
 
 // Head-major projection: columns [r*d, (r+1)*d) of Y = X Wp^T + b go to region out[r]
 // laid out (B, H, L, hd) -- each (sample, head) slice contiguous, the layout of the K/V tables.
 hipError_t launch_linear_hm(const float* X, const float* Wp, const float* bias, float* out0, float* out1, float* out2,
                             int M, int nreg, int D, int L, int H, int hd, hipStream_t s);
 // attention over head-major q, k, v (B,H,L,hd); tokens >= n_own take K/V from the
-// (H,L,hd) tables kt/vt instead of the sample's own rows. out: (M x d) row-major.
+// (H,L,hd) tables kt/vt instead of the sample's own rows. out: (M x d) row-major.  qg: q-tiles per wave (1 / 2 / 3)
 hipError_t launch_attention(const float* q, const float* k, const float* v, const float* kt, const float* vt,
-                            float* out, int B, int L, int H, int hd, int n_own, hipStream_t s);
+                            float* out, int B, int L, int H, int hd, int n_own, int qg, hipStream_t s);
 // table[h][l][:] (l < n) <- sample 0's head-major K/V rows
 hipError_t launch_kv_store(const float* k, const float* v, float* kt, float* vt, int L, int H, int hd, int n,
                            hipStream_t s);
@@ -267,7 +282,8 @@ hipError_t launch_fresca(const float* in, float* out, float* work, int B, int L,
                          double cutoff_ratio, int strategy, hipStream_t s);
 
 // ---- the kernels of one transformer layer / of the LSTM stack at a batch (ffd_api.hip) --------------------------
-// plan_layer is the one place that orders the forms; each heuristic above answers for its own form only.
+// plan_layer is the one place that orders the forms and picks their instances; each heuristic above answers for its own
+// form only, and the launchers map the plan to a kernel without reading a knob.
 enum CacheMode { CACHE_STD, CACHE_FULL, CACHE_PURE, CACHE_MIXED };  // cached_transformer.py:139-220
 CacheMode cache_mode(int n_rec, int L);  // n_rec < 0: no cache
 enum AttnForm { ATTN_FUSED, ATTN_TWO_KERNEL };  // k_qkv_attention | k_linear_hm + k_attention_mfma (+ k_kv_store)
@@ -283,10 +299,14 @@ struct LayerPlan {
   int hpw;     // heads per workgroup
   int q_only;  // 0 q | k | v pack, 1 q only (pure cache hit), 2 kv | q pack
   int kspl;    // key pieces of the small-batch split form, 0 = one workgroup per head (pair)
+  int qg;      // q-tiles per wave (per wave pair at hpw 2; 1 in the split form)
   FfnForm ffn;
   int mb;              // FFN_LN_OPROJ / FFN_LN: 16-row tiles per workgroup
+  bool rem;            //   GEMM2's remainder rows on the 4x4x1 MFMA
+  int persist;         //   FFN_LN at mb 4: 0 a workgroup per tile, n a grid of n x the resident workgroups
   int ns;              // FFN_SMALL: F splits
-  int nw, nslice;      // FFN_ROWS_SLICED*: waves per workgroup, slices
+  int nw, cps;         // FFN_ROWS*: waves per workgroup, 32-unit chunks per ring slot
+  int nslice;          // FFN_ROWS_SLICED*: slices
   int nm;              // FFN_MID: F slices
   bool oproj_separate;  // k_linear_res_ln (attn, residual -> x1 in the other hidden buffer) runs in front
   bool swap;            // the output lands in the other hidden buffer

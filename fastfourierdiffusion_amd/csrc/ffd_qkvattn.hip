@@ -973,77 +973,68 @@ __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
 }
 
 template <int D, int HD, int HPW, int QG, int NCT, bool QO>
-static hipError_t launch_mh_t(const float* x, const float* awp, const float* kt, const float* vt, float* kt_out,
-                              float* vt_out, float* out, int B, int L, int n_own, int q_only, hipStream_t s,
-                              unsigned long long* stamp) {
+static hipError_t launch_mh_t(const AttnArgs& a, int q_only, hipStream_t s) {
   constexpr int S4 = (D + 15) / 16;
-  const int KT = (L + 31) / 32;
+  const int KT = (a.L + 31) / 32;
   const size_t lds = (HPW * HeadDims<HD>::floats(64 * QG + 4) + (size_t)NCT * S4 * 256 + (size_t)HPW * 2) * sizeof(float);
   if (cdiv(2 * KT, 2 * HPW) > 3 || cdiv(KT, 2) > QG) return hipErrorInvalidValue;  // <= 3 token tiles, one q-group per wave
   if constexpr (D == 72 && HD == 6) {  // (the stamped twin exists for the headline shape only)
-    if (stamp != nullptr) {
-      hipLaunchKernelGGL((k_qkv_attention_mh<D, HD, HPW, QG, NCT, QO, true>), dim3(B * (D / HD / HPW)), dim3(128 * HPW), lds,
-                         s, x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, q_only, stamp);
+    if (a.stamp != nullptr) {
+      hipLaunchKernelGGL((k_qkv_attention_mh<D, HD, HPW, QG, NCT, QO, true>), dim3(a.B * (D / HD / HPW)), dim3(128 * HPW), lds,
+                         s, a.x, a.pack, a.kt, a.vt, a.kt_out, a.vt_out, a.out, a.B, a.L, a.n_own, q_only, a.stamp);
       return hipGetLastError();
     }
   }
-  if (stamp != nullptr) return hipErrorInvalidValue;
+  if (a.stamp != nullptr) return hipErrorInvalidValue;
   if (q_only != (QO ? 1 : 0)) return hipErrorInvalidValue;
   auto kern = k_qkv_attention_mh<D, HD, HPW, QG, NCT, QO>;
-  hipLaunchKernelGGL(kern, dim3(B * (D / HD / HPW)), dim3(128 * HPW), lds, s, x, awp, kt, vt, kt_out, vt_out, out, B, L,
-                     n_own, q_only, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL(kern, dim3(a.B * (D / HD / HPW)), dim3(128 * HPW), lds, s, a.x, a.pack, a.kt, a.vt, a.kt_out, a.vt_out,
+                     a.out, a.B, a.L, a.n_own, q_only, (unsigned long long*)nullptr);
   return hipGetLastError();
 }
 
 // 2 heads per workgroup, 2 waves per head: L <= 192 (<= 3 q-tiles per wave, 12 token tiles over 4 waves)
 template <int D, int HD>
-static hipError_t launch_mh2(const float* x, const float* awp, int q_only, const float* kt, const float* vt,
-                             float* kt_out, float* vt_out, float* out, int B, int L, int n_own, hipStream_t s,
-                             unsigned long long* stamp) {
+static hipError_t launch_mh2(const AttnArgs& a, int q_only, int qg, hipStream_t s) {
   constexpr int NF = (2 * 3 * HD + 15) / 16, NQ = (2 * HD + 15) / 16;
-  const int QG = cdiv((L + 31) / 32, 2);
-#define FFD_MH(qg)                                                                                                   \
-  if (QG == qg)                                                                                                      \
-    return q_only ? launch_mh_t<D, HD, 2, qg, NQ, true>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 1, s, stamp)     \
-                  : launch_mh_t<D, HD, 2, qg, NF, false>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 0, s, stamp);
+#define FFD_MH(g) \
+  if (qg == g) return q_only ? launch_mh_t<D, HD, 2, g, NQ, true>(a, 1, s) : launch_mh_t<D, HD, 2, g, NF, false>(a, 0, s);
   FFD_MH(1) FFD_MH(2) FFD_MH(3)
 #undef FFD_MH
   return hipErrorInvalidValue;
 }
 
 template <int D, int HD, int QG, int NCT>
-static hipError_t launch_t(const float* x, const float* awp, const float* kt, const float* vt, float* kt_out,
-                           float* vt_out, float* out, int B, int L, int n_own, int q_only, hipStream_t s,
-                           unsigned long long* stamp = nullptr) {
-  const int KT = (L + 31) / 32;
+static hipError_t launch_t(const AttnArgs& a, int q_only, hipStream_t s) {
+  const int KT = (a.L + 31) / 32;
   const size_t lds = (HeadDims<HD>::floats(KT * 32 + 4) + (size_t)2 * KT) * sizeof(float);
   int nwaves = cdiv(KT, QG);
   if (nwaves > 4) nwaves = 4;
   if (cdiv(2 * KT, nwaves) > 8) return hipErrorInvalidValue;  // the projection loop is unrolled for <= 8 token tiles per wave
   if constexpr (D == 72 && HD == 6 && NCT == 2) {  // (the stamped twin exists for the headline model's full pack only)
-    if (stamp != nullptr) {
-      hipLaunchKernelGGL((k_qkv_attention<D, HD, QG, NCT, false, true>), dim3(B * (D / HD)), dim3(64 * nwaves), lds, s, x,
-                         awp, kt, vt, kt_out, vt_out, out, B, L, n_own, q_only, 1, 1, stamp);
+    if (a.stamp != nullptr) {
+      hipLaunchKernelGGL((k_qkv_attention<D, HD, QG, NCT, false, true>), dim3(a.B * (D / HD)), dim3(64 * nwaves), lds, s, a.x,
+                         a.pack, a.kt, a.vt, a.kt_out, a.vt_out, a.out, a.B, a.L, a.n_own, q_only, 1, 1, a.stamp);
       return hipGetLastError();
     }
   }
-  if (stamp != nullptr) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_qkv_attention<D, HD, QG, NCT>), dim3(B * (D / HD)), dim3(64 * nwaves), lds, s, x, awp, kt, vt,
-                     kt_out, vt_out, out, B, L, n_own, q_only, 1, 1, (unsigned long long*)nullptr);
+  if (a.stamp != nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_qkv_attention<D, HD, QG, NCT>), dim3(a.B * (D / HD)), dim3(64 * nwaves), lds, s, a.x, a.pack, a.kt,
+                     a.vt, a.kt_out, a.vt_out, a.out, a.B, a.L, a.n_own, q_only, 1, 1, (unsigned long long*)nullptr);
   return hipGetLastError();
 }
 
 // small batches: 4 waves per workgroup, 4 / kspl q-tiles per workgroup, the key range of each cut into kspl pieces
 template <int D, int HD, int NCT, bool KVQ = false>
-static hipError_t launch_split_t(const float* x, const float* awp, const float* kt, const float* vt, float* kt_out,
-                                 float* vt_out, float* out, int B, int L, int n_own, int q_only, int kspl, hipStream_t s) {
-  const int KT = (L + 31) / 32;
+static hipError_t launch_split_t(const AttnArgs& a, int q_only, int kspl, hipStream_t s) {
+  const int KT = (a.L + 31) / 32;
   if (cdiv(2 * KT, 4) > 8 || (kspl != 1 && kspl != 2 && kspl != 4)) return hipErrorInvalidValue;
   const int qsplit = cdiv(KT, 4 / kspl);
   const size_t lds =
       (HeadDims<HD>::floats(KT * 32 + 4) + (size_t)4 * 32 * (2 + 2 * HeadDims<HD>::HP) + (size_t)2 * KT) * sizeof(float);
-  hipLaunchKernelGGL((k_qkv_attention<D, HD, 1, NCT, true, false, KVQ>), dim3(B * (D / HD) * qsplit), dim3(256), lds, s, x, awp, kt,
-                     vt, kt_out, vt_out, out, B, L, n_own, q_only, qsplit, kspl, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL((k_qkv_attention<D, HD, 1, NCT, true, false, KVQ>), dim3(a.B * (D / HD) * qsplit), dim3(256), lds, s, a.x,
+                     a.pack, a.kt, a.vt, a.kt_out, a.vt_out, a.out, a.B, a.L, a.n_own, q_only, qsplit, kspl,
+                     (unsigned long long*)nullptr);
   return hipGetLastError();
 }
 
@@ -1060,76 +1051,77 @@ int qkv_attention_small_split(int B, int H, int L) {
   return 0;
 }
 
-template <int D, int HD>
-static hipError_t launch_dh(const float* x, const float* awp, int q_only, const float* kt, const float* vt,
-                            float* kt_out, float* vt_out, float* out, int B, int L, int n_own, int kspl, hipStream_t s,
-                            unsigned long long* stamp) {
-  constexpr int NCTF = (3 * HD + 15) / 16;
-  const int QT = (L + 31) / 32;
-  if (kspl) {
-    if (stamp != nullptr) return hipErrorInvalidValue;  // (no stamped twin of the split form)
-    if constexpr (2 * HD <= 16 && 3 * HD > 16) {  // (q_only == 2: the caller handed over the kv | q pack)
-      if (q_only == 2) return launch_split_t<D, HD, 2, true>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 0, kspl, s);
-    }
-    if (q_only == 2) return hipErrorInvalidValue;
-    return q_only ? launch_split_t<D, HD, 1>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 1, kspl, s)
-                  : launch_split_t<D, HD, NCTF>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 0, kspl, s);
-  }
-  if (q_only == 2) return hipErrorInvalidValue;  // the kv | q pack is the split form's only
-  if (q_only) {
-    if (stamp != nullptr) return hipErrorInvalidValue;
-    if (QT == 1) return launch_t<D, HD, 1, 1>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 1, s);
-    if (QT % 3 == 0) return launch_t<D, HD, 3, 1>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 1, s);
-    if constexpr (HD <= 6) {
-      if (QT % 4 == 0 && QT >= 16) return launch_t<D, HD, 4, 1>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 1, s);
-    }
-    return launch_t<D, HD, 2, 1>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 1, s);
-  }
-  if (g_attn_qg == 2) return launch_t<D, HD, 2, NCTF>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 0, s, stamp);
-  if (g_attn_qg == 1) return launch_t<D, HD, 1, NCTF>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 0, s, stamp);
-  if (QT == 1) return launch_t<D, HD, 1, NCTF>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 0, s, stamp);
-  if (QT % 3 == 0) return launch_t<D, HD, 3, NCTF>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 0, s, stamp);
-  // long sequences: four q-tiles per wave share every K^T / V read (L = 512: 2422 -> 2286 us against two per wave)
-  if constexpr (HD <= 6) {  // (hd = 8 would spill at four query groups)
-    if (QT % 4 == 0 && QT >= 16) return launch_t<D, HD, 4, NCTF>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 0, s, stamp);
-  }
-  return launch_t<D, HD, 2, NCTF>(x, awp, kt, vt, kt_out, vt_out, out, B, L, n_own, 0, s, stamp);
+// q-tiles per wave (the group shares every K^T / V read) of the one-workgroup-per-head kernels at QT q-tiles: of
+// k_qkv_attention (fused), else of k_attention_mfma, which has no instance of four
+int attn_qg(int QT, int hd, bool fused) {
+  if (QT == 1) return 1;
+  if (QT % 3 == 0) return 3;
+  // long sequences: four q-tiles per wave (L = 512: 2422 -> 2286 us against two per wave; hd = 8 has no such instance)
+  if (fused && hd <= 6 && QT % 4 == 0 && QT >= 16) return 4;
+  return 2;
 }
 
-// (d_model, head_dim) pairs with a fused kernel; anything else keeps the two-kernel path.
+template <int D, int HD>
+static hipError_t launch_dh(const AttnArgs& a, int q_only, int kspl, int qg, hipStream_t s) {
+  constexpr int NCTF = (3 * HD + 15) / 16;
+  if (kspl) {
+    if (a.stamp != nullptr) return hipErrorInvalidValue;  // (no stamped twin of the split form)
+    if constexpr (2 * HD <= 16 && 3 * HD > 16) {  // (q_only == 2: the caller handed over the kv | q pack)
+      if (q_only == 2) return launch_split_t<D, HD, 2, true>(a, 0, kspl, s);
+    }
+    if (q_only == 2) return hipErrorInvalidValue;
+    return q_only ? launch_split_t<D, HD, 1>(a, 1, kspl, s) : launch_split_t<D, HD, NCTF>(a, 0, kspl, s);
+  }
+  if (q_only == 2) return hipErrorInvalidValue;  // the kv | q pack is the split form's only
+  if (q_only && a.stamp != nullptr) return hipErrorInvalidValue;
+  // (instances in the order they were first named in: the device code keeps its layout)
+#define FFD_QG(g, nct) if (qg == g) return launch_t<D, HD, g, nct>(a, q_only, s);
+  if (q_only) {
+    FFD_QG(1, 1) FFD_QG(3, 1)
+    if constexpr (HD <= 6) {
+      FFD_QG(4, 1)
+    }
+    FFD_QG(2, 1)
+    return hipErrorInvalidValue;
+  }
+  FFD_QG(2, NCTF) FFD_QG(1, NCTF) FFD_QG(3, NCTF)
+  if constexpr (HD <= 6) {  // (hd = 8 would spill at four query groups)
+    FFD_QG(4, NCTF)
+  }
+#undef FFD_QG
+  return hipErrorInvalidValue;
+}
+
+// (d_model, head_dim) pairs with a fused kernel, X2: with a two-heads-per-workgroup instance as well; anything else
+// keeps the two-kernel path.
+#define FFD_QKV_LIST(X, X2) X2(72, 6) X2(60, 5) X(24, 6) X(8, 2) X(64, 8) X2(48, 4) X(32, 8) X(16, 4) X(24, 3)
+#define FFD_QKV_IS(dd, hh) if (D == dd && hd == hh) return true;
+#define FFD_QKV_SKIP(dd, hh)
+
 bool qkv_attention_supported(int D, int hd) {
-  return (D == 72 && hd == 6) || (D == 60 && hd == 5) || (D == 24 && hd == 6) || (D == 8 && hd == 2) ||
-         (D == 64 && hd == 8) || (D == 48 && hd == 4) || (D == 32 && hd == 8) || (D == 16 && hd == 4) ||
-         (D == 24 && hd == 3);
+  FFD_QKV_LIST(FFD_QKV_IS, FFD_QKV_IS)
+  return false;
+}
+static bool qkv_attention_two_heads(int D, int hd) {
+  FFD_QKV_LIST(FFD_QKV_SKIP, FFD_QKV_IS)
+  return false;
 }
 
 // heads per workgroup of the one-workgroup-per-head(-pair) kernels for this shape (the caller passes the matching pack)
 int qkv_attention_hpw(int D, int hd, int L) {
-  const bool mh2 = ((D == 72 && hd == 6) || (D == 60 && hd == 5) || (D == 48 && hd == 4)) && L <= 192;
-  return (g_attn_hpw == 1 || !mh2) ? 1 : 2;
+  return (g_attn_hpw == 1 || !qkv_attention_two_heads(D, hd) || L > 192) ? 1 : 2;
 }
 
-hipError_t launch_qkv_attention(const float* x, const float* awp, int hpw, int q_only, const float* kt,
-                                const float* vt, float* kt_out, float* vt_out, float* out, int B, int L, int D, int hd,
-                                int n_own, int kspl, hipStream_t s, unsigned long long* stamp) {
-  if (B <= 0) return hipSuccess;
+hipError_t launch_qkv_attention(const AttnArgs& a, int D, int hd, int hpw, int q_only, int kspl, int qg, hipStream_t s) {
+  if (a.B <= 0) return hipSuccess;
   if (hpw == 2) {
-    if (D == 72 && hd == 6) return launch_mh2<72, 6>(x, awp, q_only, kt, vt, kt_out, vt_out, out, B, L, n_own, s, stamp);
-    if (D == 60 && hd == 5) return launch_mh2<60, 5>(x, awp, q_only, kt, vt, kt_out, vt_out, out, B, L, n_own, s, stamp);
-    if (D == 48 && hd == 4) return launch_mh2<48, 4>(x, awp, q_only, kt, vt, kt_out, vt_out, out, B, L, n_own, s, stamp);
+#define FFD_QA2(dd, hh) if (D == dd && hd == hh) return launch_mh2<dd, hh>(a, q_only, qg, s);
+    FFD_QKV_LIST(FFD_QKV_SKIP, FFD_QA2)
+#undef FFD_QA2
     return hipErrorInvalidValue;
   }
-#define FFD_QA(dd, hh) \
-  if (D == dd && hd == hh) return launch_dh<dd, hh>(x, awp, q_only, kt, vt, kt_out, vt_out, out, B, L, n_own, kspl, s, stamp);
-  FFD_QA(72, 6)
-  FFD_QA(60, 5)
-  FFD_QA(24, 6)
-  FFD_QA(8, 2)
-  FFD_QA(64, 8)
-  FFD_QA(48, 4)
-  FFD_QA(32, 8)
-  FFD_QA(16, 4)
-  FFD_QA(24, 3)
+#define FFD_QA(dd, hh) if (D == dd && hd == hh) return launch_dh<dd, hh>(a, q_only, kspl, qg, s);
+  FFD_QKV_LIST(FFD_QA, FFD_QA)
 #undef FFD_QA
   return hipErrorInvalidValue;
 }

@@ -445,6 +445,30 @@ def test_supported_shapes_vs_oracle(ffd, shape, variant):
     m.disable_caching()
 
 
+def test_forced_q_tile_groups_and_remainder_instances_vs_oracle(ffd):
+    """The instances that only ffd_tune "attn_qg" and "ffn_rem" reach.  d_model 72 (two remainder groups in GEMM2) at
+    L = 70: three q-tiles, so the heuristics take QG = 3; attn_hpw = 1 keeps the two-heads form (which ignores the knob
+    at L <= 192) out of the way.  k_ffn_ln at 48- and 64-row tiles runs with the remainder rows on the 4x4x1 MFMA and
+    without."""
+    from fastfourierdiffusion_amd import _native as N
+
+    lib = N.lib()
+    d, H, L, C, NL, B = 72, 12, 70, 2, 2, 3
+    c = dict(kind="transformer", d=d, H=H, NL=NL, L=L, C=C, sde="vp", sde_kwargs=cases.VP, fourier=True, wseed=600 + d + L)
+    m, _ = make_model(ffd, c)
+    x = torch.from_numpy(next(synthetic.noise_stream((B, L, C), 1, 9000 + d)))
+    ref = O.score_forward(x, torch.full((B,), 0.7, dtype=torch.float32), make_sd(c), NL, H)
+    fused = [dict(attn_small=0, attn_hpw=1, attn_qg=qg) for qg in (1, 2)]
+    two_kernel = [dict(attn_fused=0, attn_qg=qg) for qg in (1, 2, 3)]
+    ffn = [dict(ffn_rows=0, small_path=0, mid_path=0, ffn_height=0, ffn_mb=mb, ffn_rem=rem) for mb in (3, 4) for rem in (0, 1)]
+    for knobs in fused + two_kernel + ffn:
+        for key, v in knobs.items():
+            assert lib.ffd_tune(key.encode(), v) == 0, (key, v)
+        out = m(batch_of(x.cuda(), 0.7)).cpu()
+        assert lib.ffd_tune(b"reset", 0) == 0
+        assert rel_err(out, ref) < TOL_SCORE, knobs
+
+
 def test_model_full_batch_properties(ffd):
     """BASELINE configs[1] batch (B=512): sample independence (a size-independent
     property of the path) -- every sample of a big batch equals its own B=1 evaluation
