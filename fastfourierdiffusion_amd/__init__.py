@@ -12,6 +12,7 @@ sub-modules mirror the reference's import paths
     fdiff.utils.extraction.{get_best_checkpoint,get_model_type,flatten_config} -> .utils.extraction
     fdiff.sampling.metrics.{MetricCollection,SlicedWasserstein,MarginalWasserstein} -> .sampling.metrics
     fdiff.utils.wasserstein.WassersteinDistances, fdiff.utils.tensors.check_flat_array -> .utils.{wasserstein,tensors}
+    fdiff.utils.losses.get_sde_loss_fn (evaluation only) -> .utils.losses
 
 and ``install_as_fdiff()`` registers them under the ``fdiff.*`` names so that existing
 scripts and Hydra ``_target_`` strings resolve unchanged.  All arithmetic runs in
@@ -35,6 +36,7 @@ _MIRROR = {
     "fdiff.utils.caching": "fastfourierdiffusion_amd.utils.caching",
     "fdiff.utils.fourier": "fastfourierdiffusion_amd.utils.fourier",
     "fdiff.utils.fresca": "fastfourierdiffusion_amd.utils.fresca",
+    "fdiff.utils.losses": "fastfourierdiffusion_amd.utils.losses",
     "fdiff.utils.dataclasses": "fastfourierdiffusion_amd.utils.dataclasses",
     "fdiff.utils.extraction": "fastfourierdiffusion_amd.utils.extraction",
     "fdiff.utils.tensors": "fastfourierdiffusion_amd.utils.tensors",

@@ -105,6 +105,7 @@ struct ffd_ctx {
   ffd_crf_capture_cfg crf_cap{};
   ffd_fresca_cfg fcfg{};
   Grow<float> score2, fwork;
+  Grow<float> sm_noisy;  // the perturbed batch of ffd_sm_eval_batch
   // cache
   bool cache_enabled = false;
   ffd_cache_cfg ccfg{5, 10};
@@ -902,6 +903,27 @@ int ffd_score_forward_ts(ffd_ctx* ctx, const float* x, const float* timesteps, f
   }
   return score_forward(ctx, x, timesteps, 0.f, score_out, n_recompute >= 0 ? crf_out : nullptr, B,
                        n_recompute >= 0 ? n_recompute : -1, stream);
+}
+
+// loss_fn's body for one batch (losses.py:65-122): perturb -> score network at the per-sample times -> per-sample loss
+int ffd_sm_eval_batch(ffd_ctx* ctx, const float* x0, const float* timesteps, const float* mean_coeff, const float* sigma,
+                      const float* z, uint64_t seed, uint64_t sample_offset, int likelihood_weighting, int reduce_mean,
+                      double* per_sample_out, int B, void* stream) {
+  if (!ctx) return FFD_ERR_INVALID;
+  if (int rc = check_ready(ctx, B)) return rc;
+  if (!x0 || !timesteps || !mean_coeff || !sigma || !per_sample_out) return ctx->fail(FFD_ERR_INVALID, "null buffer");
+  const ffd_model_desc& m = ctx->desc;
+  const int L = m.max_len, C = m.n_channels;
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (int rc = ensure_workspace(ctx, B)) return rc;
+  if (int rc = ensure(ctx, ctx->sm_noisy, (size_t)B * L * C)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHECK(launch_sm_perturb(x0, ctx->sm_noisy.p, mean_coeff, sigma, ctx->G_dev, z, seed, sample_offset, B, L, C, s));
+  if (int rc = time_embed(ctx, timesteps, 0.f, B, ctx->temb_b.p, s)) return rc;
+  if (int rc = forward_impl(ctx, ctx->sm_noisy.p, ctx->temb_b.p, m.d_model, ctx->score.p, nullptr, B, -1, s)) return rc;
+  HIPCHECK(launch_sm_loss(ctx->score.p, sigma, ctx->G_dev, z, seed, sample_offset, likelihood_weighting, reduce_mean,
+                          per_sample_out, B, L, C, s));
+  return FFD_OK;
 }
 
 int ffd_fresca_enable(ffd_ctx* ctx, const ffd_fresca_cfg* cfg) {

@@ -36,6 +36,76 @@ __device__ __forceinline__ float relu_bits(float x) {
   return __builtin_bit_cast(float, i > 0 ? i : 0);
 }
 
+// ---- Philox4x32-10 + Box-Muller: the on-device N(0,1) / U[0,1) draws (SDE step, prior, score-matching loss) ----
+struct U4 {
+  uint32_t x, y, z, w;
+};
+
+__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
+  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    // one 32 x 32 -> 64 multiply per product (v_mad_u64_u32) instead of a mul_hi / mul_lo pair: the generator is the
+    // ALU floor of the noise-drawing kernels (k_prior writes 4 B per element and nothing else)
+    const uint64_t p0 = (uint64_t)M0 * c.x, p1 = (uint64_t)M1 * c.z;
+    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
+    U4 n = {hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
+    c = n;
+    k0 += W0;
+    k1 += W1;
+  }
+  return c;
+}
+
+// Two N(0,1) draws from two 32-bit words.  The hardware transcendentals (v_log_f32 = log2, v_sin_f32 / v_cos_f32 take
+// their argument in revolutions, i.e. u2 itself) keep the generator off the critical path of the HBM-bound step
+// kernel: the library logf / sincosf cost ~10x the instructions and made the step ALU-bound (2.8 TB/s).
+__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
+  const float u1 = ((float)(a >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)
+  const float u2 = ((float)(b >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float r = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));  // sqrt(-2 ln u1)
+  z0 = r * __builtin_amdgcn_cosf(u2);
+  z1 = r * __builtin_amdgcn_sinf(u2);
+}
+
+// N(0,1) for global element index g at (seed, stream tag `step`): slot g&3 of Philox(counter g>>2).
+__device__ __forceinline__ void normal4(uint64_t g4, uint64_t seed, uint32_t step, float out[4]) {
+  U4 c = {(uint32_t)g4, (uint32_t)(g4 >> 32), step, 0x46464446u /* "FFDF" */};
+  U4 r = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  box_muller(r.x, r.y, out[0], out[1]);
+  box_muller(r.z, r.w, out[2], out[3]);
+}
+
+// the (up to) 4 draws of elements i0 .. i0+3 (global index elem_offset + i0, any alignment), or injected ones
+__device__ __forceinline__ void load_normals(const float* z, size_t i0, int n, uint64_t seed, uint64_t elem_offset,
+                                             uint32_t step, float zz[4]) {
+  if (z) {
+    for (int j = 0; j < n; ++j) zz[j] = z[i0 + j];
+    return;
+  }
+  uint64_t g0 = elem_offset + i0;
+  float a[4], b[4] = {0.f, 0.f, 0.f, 0.f};
+  normal4(g0 >> 2, seed, step, a);
+  const int sh = (int)(g0 & 3);
+  if (sh) normal4((g0 >> 2) + 1, seed, step, b);
+  // zz[j] = (a | b)[sh + j] as selects on static indices (indexed by sh the two arrays lived in scratch: 48 B per lane)
+  const float c[7] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2]};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) zz[j] = sh == 0 ? c[j] : sh == 1 ? c[j + 1] : sh == 2 ? c[j + 2] : c[j + 3];
+}
+
+// Sum over a 256-thread workgroup as a fixed-order fp64 tree in LDS (red: 256 doubles); every thread gets the total
+__device__ __forceinline__ double block_sum(double v, double* red) {  // fixed-order tree over 256 threads
+  __syncthreads();
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
 // ---- ffd_tune knobs: each a thread_local int (a thread's knobs select the kernels of the launches it makes; a new
 // thread starts from the defaults).  I(key, variable, default, accepted values of v); B(key, variable, default): any
 // value, stored as 0 / 1.  ffd_tune, ffd_tune_get, "reset" and the definitions are generated from this table.
@@ -167,6 +237,18 @@ bool unembed_sde_supported(int C, int D);
 hipError_t launch_unembed_sde(const float* h, const float* Wu, const float* bu, float* x, const float* z, const float* G,
                               SdeParams p, uint64_t seed, uint64_t elem_offset, uint32_t step, int B, int L, int C,
                               int D, hipStream_t s);
+
+// Denoising score-matching loss (ffd_loss.hip; losses.py:54-125).  Sample b of the call is global sample
+// sample_offset + b: with z == nullptr both kernels take the draw of global element g from slot g & 3 of Philox block
+// g >> 2 under SM_TAG_NOISE, so the loss regenerates what the perturbation drew.
+constexpr uint32_t SM_TAG_NOISE = 0xFFFFFFFEu, SM_TAG_TIMES = 0xFFFFFFFDu;  // (0xFFFFFFFF: the prior; below 2^31: step indices)
+// x_noisy[b,l,c] = mean_coeff[b] * x0[b,l,c] + (sigma[b] * G[l]) * z[b,l,c]
+hipError_t launch_sm_perturb(const float* x0, float* x_noisy, const float* mean_coeff, const float* sigma, const float* G,
+                             const float* z, uint64_t seed, uint64_t sample_offset, int B, int L, int C, hipStream_t s);
+// out[b] = the reduced, weighted squared error of sample b (B doubles)
+hipError_t launch_sm_loss(const float* score, const float* sigma, const float* G, const float* z, uint64_t seed,
+                          uint64_t sample_offset, int likelihood_weighting, int reduce_mean, double* out, int B, int L,
+                          int C, hipStream_t s);
 
 // Y[M x N] (row stride ldy) = X[M x D] Wp^T + b ; Wp is dpack of the N x D weight.
 hipError_t launch_linear(const float* X, const float* Wp, const float* bias, float* Y, int M, int N, int D, int ldy,

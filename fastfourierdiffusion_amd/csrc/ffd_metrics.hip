@@ -227,17 +227,6 @@ static hipError_t launch_w2_sort(float* rows, float* scratch, int N, int Kb, hip
 }
 
 // ---- quantile integral -----------------------------------------------------------------------------------------
-__device__ __forceinline__ double block_sum(double v, double* red) {  // fixed-order tree over 256 threads
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // One workgroup per direction.  `big` is the longer of the two sorted rows (nb >= ns): element i covers the grid
 // interval [i ns, (i + 1) ns) of the n m grid, which meets at most two elements of `small` (breakpoints at multiples
 // of nb).  Thread t takes i = t, t + 256, ...: the same terms in the same order whichever set is the original.

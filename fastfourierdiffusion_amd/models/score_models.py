@@ -10,7 +10,8 @@ initialisation, so reference checkpoints load and equal seeds give equal weights
 The torch modules only *hold* parameters.  ``forward`` hands raw device pointers to
 libffd (include/ffd.h), whose HIP kernels evaluate the network; nothing here calls a
 torch operator on activations, and a tensor that is not on a gfx950 device raises.
-Training hooks (training_step, configure_optimizers, losses) are out of scope.
+``validation_step`` evaluates the denoising score-matching loss forward-only (utils/losses.py); the training
+hooks (training_step, configure_optimizers) are out of scope: there is no backward pass.
 """
 from __future__ import annotations
 
@@ -24,6 +25,7 @@ from .. import _native as N
 from ..schedulers.sde import SDE, VEScheduler, VPScheduler
 from ..utils.caching import E2CRFCache
 from ..utils.dataclasses import DiffusableBatch
+from ..utils.losses import get_sde_loss_fn
 from .transformer import GaussianFourierProjection, PositionalEncoding
 
 
@@ -101,6 +103,7 @@ class ScoreModule(nn.Module):
         self.cached_backbone = None  # truthy once enable_caching ran (score_models.py:232)
         self._first_cache: Optional[E2CRFCache] = None
         self._native: Optional[_NativeContext] = None
+        self.training_loss_fn, self.validation_loss_fn = self.set_loss_fn()
 
     def _build_backbone(self) -> None:
         layer = nn.TransformerEncoderLayer(d_model=self.d_model, nhead=self.n_head, batch_first=True)
@@ -208,6 +211,18 @@ class ScoreModule(nn.Module):
                                              crf.data_ptr() if crf is not None else None, B, n, stream),
                 ctx.handle, "ffd_score_forward_ts")
         return (score, crf) if return_crf else score
+
+    # ------------------------------------------------------------------
+    def set_loss_fn(self):
+        """score_models.py:326-351: (training_loss_fn, validation_loss_fn).  The training loss is None -- training is
+        out of scope (get_sde_loss_fn(train=True) raises)."""
+        return None, get_sde_loss_fn(scheduler=self.noise_scheduler, train=False,
+                                     likelihood_weighting=self.likelihood_weighting)
+
+    def validation_step(self, batch: DiffusableBatch, batch_idx: int, dataloader_idx: int = 0) -> torch.Tensor:
+        """score_models.py:304-316.  Returns the loss (a 0-dim device tensor); the reference logs it as ``val/loss``
+        through Lightning and returns None -- there is no logger here."""
+        return self.validation_loss_fn(self, batch)
 
     # ------------------------------------------------------------------
     def enable_caching(self, cache: Optional[E2CRFCache] = None, **cache_kwargs) -> None:

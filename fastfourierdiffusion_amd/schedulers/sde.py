@@ -67,6 +67,12 @@ class SDE(abc.ABC):
         ...
 
     @abc.abstractmethod
+    def marginal_coeffs(self, t: torch.Tensor):
+        """(mean_coeff, sigma), both shaped like ``t``: the per-sample factors of ``marginal_prob`` --
+        mean = mean_coeff * x and std = sigma[:, None] * G -- formed by its own expressions on the device ``t`` lives
+        on.  The score-matching loss kernels (csrc/ffd_loss.hip) take them as inputs."""
+
+    @abc.abstractmethod
     def _sde_ab(self) -> tuple:
         ...
 
@@ -151,6 +157,11 @@ class VEScheduler(SDE):
         std = (sigma_min * (sigma_max / sigma_min) ** t).view(-1, 1) * self.G.to(x.device)
         return x, std
 
+    def marginal_coeffs(self, t: torch.Tensor):
+        sigma_min = torch.tensor(self.sigma_min).type_as(t)
+        sigma_max = torch.tensor(self.sigma_max).type_as(t)
+        return torch.ones_like(t), sigma_min * (sigma_max / sigma_min) ** t
+
 
 class VPScheduler(SDE):
     """sde.py:168-246."""
@@ -177,3 +188,7 @@ class VPScheduler(SDE):
         mean = torch.exp(log_mean_coeff[(...,) + (None,) * len(x.shape[1:])]) * x
         std = torch.sqrt((1.0 - torch.exp(2.0 * log_mean_coeff.view(-1, 1)))) * self.G.to(x.device)
         return mean, std
+
+    def marginal_coeffs(self, t: torch.Tensor):
+        log_mean_coeff = -0.25 * t ** 2 * (self.beta_1 - self.beta_0) - 0.5 * t * self.beta_0
+        return torch.exp(log_mean_coeff), torch.sqrt(1.0 - torch.exp(2.0 * log_mean_coeff))

@@ -292,6 +292,42 @@ int ffd_col_mean(const float* x, int n, int D, float* mean_out, void* work, size
 int ffd_w2_bench_kernels(const float* x, int n, int D, const float* dirs, int K, float* rows, float* scratch,
                          const float* other_rows, int m, double* dist, int iters, float* ms_out, void* stream);
 
+/* ---- denoising score-matching loss: the `val/loss` of ScoreModule.validation_step (src/fdiff/utils/losses.py) ----
+ * Per sample b, with std[b,l] = sigma[b] * G[l] and n = L * C (losses.py:68-80, sde.py:106-123,187-210):
+ *   x_noisy = mean_coeff[b] * x0 + std[b,l] * z                  r = score + z / std[b,l]
+ *   default:               loss_b = reduce(w[b] * r^2),  w[b] = 1 / sum_l (1 / std[b,l]^2)     (losses.py:92-109)
+ *   likelihood_weighting:  loss_b = reduce((std[b,l] * r)^2)                                    (losses.py:111-122)
+ *   reduce = the mean over the n elements, or 0.5 * the sum when reduce_mean == 0               (losses.py:33-37)
+ * mean_coeff, sigma: (B) fp32 on the device, SUPPLIED BY THE CALLER like the timestep grid of ffd_sample_batch --
+ * VP: exp(lmc) and sqrt(1 - exp(2 lmc)), VE: 1 and sigma_min (sigma_max / sigma_min)^t.  The reference forms them in
+ * fp32 and 1 - exp(2 lmc) is ill-conditioned at small t (one ulp of exp moves sigma by 3e-5 relative at t = 0.01), so a
+ * library that recomputed them could not reproduce a reference value.  G: (L) fp32 on the device (ffd_host_noise_scaling).
+ * Tensors are dense fp32 (B, L, C); everything is stream ordered without host synchronisation and without atomics; the
+ * reductions are fixed-order fp64 trees (fp32 terms), so results are bit-identical from run to run.
+ * z (B, L, C) injects the N(0,1) draws; z == NULL draws them on the device: Philox4x32-10 keyed by seed under stream tag
+ * 0xFFFFFFFE, counted by the global element index (sample_offset + b) * L * C + i as in ffd_sde_step, so a shard draws
+ * what the unsharded call draws, and the loss kernel regenerates what the perturbation drew for the same
+ * (seed, sample_offset): no z buffer exists on that path.
+ * FFD_ERR_INVALID: a null pointer (z excepted), B, L, C < 1, eps >= T, x0 == x_noisy; checked before any device work. */
+
+/* losses.py:60-63: t_out[b] = u * (T - eps) + eps in fp32, u in [0, 1) from Philox (stream tag 0xFFFFFFFD) counted by
+ * the global sample index sample_offset + b. */
+int ffd_sm_draw_times(float* t_out, int B, double eps, double T, uint64_t seed, uint64_t sample_offset, void* stream);
+/* SDE.marginal_prob + SDE.add_noise on Sigma^{1/2} z (losses.py:68-85, sde.py:66-77). */
+int ffd_sm_perturb(const float* x0, float* x_noisy, const float* mean_coeff, const float* sigma, const float* G,
+                   const float* z, uint64_t seed, uint64_t sample_offset, int B, int L, int C, void* stream);
+/* The weighted squared error and its reduction over the data dimensions (losses.py:92-122): per_sample_out = B doubles
+ * on the device.  The batch mean (losses.py:124) is element 0 of ffd_w2_summary over them. */
+int ffd_sm_loss(const float* score, const float* sigma, const float* G, const float* z, uint64_t seed,
+                uint64_t sample_offset, int likelihood_weighting, int reduce_mean, double* per_sample_out, int B, int L,
+                int C, void* stream);
+/* loss_fn's body for one batch (losses.py:65-122) on a context: the perturbation into a context workspace, the score
+ * network at the per-sample `timesteps` (B, device; the uncached path of ffd_score_forward_ts, every backbone) and the
+ * loss, with the context's G table.  Does not touch the E2-CRF cache. */
+int ffd_sm_eval_batch(ffd_ctx* ctx, const float* x0, const float* timesteps, const float* mean_coeff, const float* sigma,
+                      const float* z, uint64_t seed, uint64_t sample_offset, int likelihood_weighting, int reduce_mean,
+                      double* per_sample_out, int B, void* stream);
+
 /* CRF capture inside ffd_sample_batch (the reference's cache.update_crf call, sampler.py:70-73):
  * on cached steps whose global step g satisfies g % every == 0 the (NL, L, d) CRF (score_models.py:181-194)
  * is written to ring slot (g / every) % n_slots; `last` receives the CRF of the last step of each
