@@ -87,6 +87,7 @@ SIGNATURES = {
     "ffd_host_noise_scaling": (C.c_int, [C.c_int, C.c_int, _F]),
     "ffd_host_timesteps": (C.c_int, [C.c_int, C.c_double, _F, _F]),
     "ffd_host_gate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ffd_host_attn_score_bound": (C.c_int, [_F, _F, _F, _F, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "ffd_score_forward": (C.c_int, [_P, _P, C.c_float, _P, C.c_int, _P]),
     "ffd_score_forward_cached": (C.c_int, [_P, _P, C.c_float, _P, _P, C.c_int, C.c_int, _P]),
     "ffd_sde_step": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, C.c_double, C.c_float, _P, C.c_uint64, C.c_uint64,

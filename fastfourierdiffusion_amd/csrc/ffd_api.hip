@@ -245,6 +245,9 @@ LayerPlan plan_layer(const ffd_model_desc& m, int B, CacheMode mode, const PackS
            : p.hpw == 2                                         ? cdiv(QT, 2)
            : !p.q_only && (g_attn_qg == 1 || g_attn_qg == 2)    ? g_attn_qg
                                                                 : attn_qg(QT, hd, true);
+    // without the per-launch score bound where the layer's weights give it -- unless the launch reads K/V tables, whose
+    // rows are projections of another step's hidden state
+    p.attn_static = g_attn_static_bound && (mode == CACHE_STD || mode == CACHE_FULL);
   } else {
     p.qg = QT == 1 ? 1 : g_attn_qg ? g_attn_qg : attn_qg(QT, hd, false);
   }
@@ -377,6 +380,71 @@ int ffd_host_gate(int step, int max_len, int K, int R) {
     return n < 0 ? 0 : n;
   }
   return 0;
+}
+
+// Upper bound of the largest eigenvalue of the symmetric n x n matrix a (row-major, overwritten): cyclic Jacobi sweeps
+// until the off-diagonal part is negligible, then Gershgorin's bound max_i (a_ii + sum_j |a_ij|) of the rotated matrix.
+// The rotations are similarity transforms, so that maximum bounds the largest eigenvalue from above however far the
+// sweeps got (an iteration from below, such as the power method, could stop short of it); at convergence the
+// off-diagonal sum is rounding noise and the bound is tight.  The relative 1e-12 covers the rotations' own rounding.
+static double sym_eig_max_upper(std::vector<double>& a, int n) {
+  for (int sweep = 0; sweep < 64; ++sweep) {
+    double off = 0.0, diag = 0.0;
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) (i == j ? diag : off) += a[i * n + j] * a[i * n + j];
+    if (off <= 1e-30 * diag) break;
+    for (int p = 0; p < n; ++p)
+      for (int q = p + 1; q < n; ++q) {
+        const double apq = a[p * n + q];
+        if (apq == 0.0) continue;
+        const double theta = (a[q * n + q] - a[p * n + p]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+        for (int k = 0; k < n; ++k) {  // A <- A J
+          const double akp = a[k * n + p], akq = a[k * n + q];
+          a[k * n + p] = c * akp - sn * akq, a[k * n + q] = sn * akp + c * akq;
+        }
+        for (int k = 0; k < n; ++k) {  // A <- J^T A
+          const double apk = a[p * n + k], aqk = a[q * n + k];
+          a[p * n + k] = c * apk - sn * aqk, a[q * n + k] = sn * apk + c * aqk;
+        }
+      }
+  }
+  double best = 0.0;
+  for (int i = 0; i < n; ++i) {
+    double r = a[i * n + i];
+    for (int j = 0; j < n; ++j)
+      if (j != i) r += fabs(a[i * n + j]);
+    best = std::max(best, r);
+  }
+  return best * (1.0 + 1e-12);
+}
+
+int ffd_host_attn_score_bound(const float* in_w, const float* in_b, const float* ln_w, const float* ln_b, int d, int hd,
+                              double q_scale, double* bound_out) {
+  if (!in_w || !in_b || !ln_w || !ln_b || !bound_out || d < 1 || hd < 1 || d % hd != 0) return FFD_ERR_INVALID;
+  // |LayerNorm(v)| <= sqrt(d) max|gamma| + |beta|: the normalised row has squared norm d var / (var + eps) <= d.  The
+  // kernels' LayerNorm is fp32 (mean, variance, rsqrt, one FMA per element: a few ulp each); the relative 1e-4 is three
+  // orders of magnitude above that and also covers the fp32 rounding of the projections that follow.
+  constexpr double kLnSlack = 1e-4;
+  double gmax = 0.0, b2 = 0.0;
+  for (int i = 0; i < d; ++i) gmax = std::max(gmax, fabs((double)ln_w[i])), b2 += (double)ln_b[i] * ln_b[i];
+  const double R = (sqrt((double)d) * gmax + sqrt(b2)) * (1.0 + kLnSlack);
+  std::vector<double> gram((size_t)hd * hd);
+  // sigma(W) R + |b| >= |W x + b| for |x| <= R, with sigma(W)^2 the largest eigenvalue of the head's Gram matrix W W^T
+  auto reach = [&](int row0) {
+    for (int i = 0; i < hd; ++i)
+      for (int j = 0; j < hd; ++j) {
+        double acc = 0.0;
+        for (int k = 0; k < d; ++k) acc += (double)in_w[(size_t)(row0 + i) * d + k] * in_w[(size_t)(row0 + j) * d + k];
+        gram[(size_t)i * hd + j] = acc;
+      }
+    double bb = 0.0;
+    for (int i = 0; i < hd; ++i) bb += (double)in_b[row0 + i] * in_b[row0 + i];
+    return sqrt(sym_eig_max_upper(gram, hd)) * R + sqrt(bb);
+  };
+  for (int h = 0; h < d / hd; ++h) bound_out[h] = q_scale * reach(h * hd) * reach(d + h * hd);
+  return FFD_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -572,6 +640,24 @@ int ffd_finalize_weights(ffd_ctx* ctx) {
       }
       if (l.w1s) HIPCHECK(launch_pack_ffn_split(l.w1, l.w2, l.w1s, l.w2s, d, F, s));
     }
+    // which layers' attention scores are bounded by the weights alone: the input of layer i >= 1 is layer i - 1's norm2
+    // output (layer 0 reads the embedding of unbounded data and keeps measuring)
+    const int hd = d / m.n_head;
+    std::vector<float> in_w((size_t)3 * d * d), in_b(3 * d), g(d), be(d);
+    std::vector<double> bound(m.n_head);
+    for (size_t i = 0; i < ctx->layers.size(); ++i) {
+      LayerWeights& l = ctx->layers[i];
+      l.attn_bounded = false;
+      if (i == 0 || !l.aw_full) continue;
+      HIPCHECK(hipMemcpy(in_w.data(), l.in_w, in_w.size() * sizeof(float), hipMemcpyDeviceToHost));
+      HIPCHECK(hipMemcpy(in_b.data(), l.in_b, in_b.size() * sizeof(float), hipMemcpyDeviceToHost));
+      HIPCHECK(hipMemcpy(g.data(), ctx->layers[i - 1].n2w, d * sizeof(float), hipMemcpyDeviceToHost));
+      HIPCHECK(hipMemcpy(be.data(), ctx->layers[i - 1].n2b, d * sizeof(float), hipMemcpyDeviceToHost));
+      if (ffd_host_attn_score_bound(in_w.data(), in_b.data(), g.data(), be.data(), d, hd, attn_q_scale(hd), bound.data()))
+        continue;
+      l.attn_bounded = true;
+      for (double v : bound) l.attn_bounded = l.attn_bounded && v <= (double)ATTN_SCORE_T;  // (a NaN weight: not bounded)
+    }
   } else if (m.kind == FFD_MODEL_LSTM) {
     for (LstmLayer& l : ctx->lstm) {
       if (!l.wih_p) {  // first time: the packs
@@ -650,8 +736,9 @@ static hipError_t run_attention(const ffd_ctx* ctx, const LayerPlan& p, const La
     const float* pack = p.q_only == 2 ? w.aw_kvq
                         : p.hpw == 2  ? (p.q_only ? w.aw_q2 : w.aw_full2)
                                       : (p.q_only ? w.aw_q : w.aw_full);
-    return launch_qkv_attention(AttnArgs{x, pack, kt, vt, kt_out, vt_out, out, B, L, n_own, stamp}, d, hd, p.hpw, p.q_only,
-                                p.kspl, p.qg, s);
+    return launch_qkv_attention(AttnArgs{x, pack, kt, vt, kt_out, vt_out, out, B, L, n_own, stamp,
+                                         p.attn_static && w.attn_bounded && kt == nullptr},
+                                d, hd, p.hpw, p.q_only, p.kspl, p.qg, s);
   }
   if (stamp != nullptr) return hipErrorInvalidValue;
   // q / k / v regions, head-major (B,H,L,hd)
@@ -1235,7 +1322,11 @@ const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cac
       break;
     case FFD_K_ATTN:  // in-projection (Q only on a pure-cache step) + QK^T + PV; x in, attention output out
       if (tr) {
-        name = p.attn == ATTN_FUSED ? "k_qkv_attention" : "k_linear_hm + k_attention_mfma";
+        bool any_static = false;  // some layer runs the instance without the per-launch score bound
+        for (const LayerWeights& l : ctx->layers) any_static = any_static || (p.attn_static && l.attn_bounded);
+        name = p.attn != ATTN_FUSED ? "k_linear_hm + k_attention_mfma"
+               : any_static         ? "k_qkv_attention<static bound>"
+                                    : "k_qkv_attention";
         fl = M * (2.0 * d * (cache_hit ? d : 3.0 * d) + 4.0 * L * d);
         by = 4.0 * (2.0 * M * d + 3.0 * d * d + (cache_hit ? 2.0 * L * d : 0.0));
         if (p.attn == ATTN_TWO_KERNEL) by += 4.0 * 2.0 * M * (cache_hit ? d : 3.0 * d);  // q / k / v through HBM
@@ -1415,8 +1506,9 @@ int ffd_probe_attn(ffd_ctx* ctx, int B, int n_recompute, double warm_seconds, in
   hipLaunchKernelGGL(k_fill_hash, dim3(1024), dim3(256), 0, s, ctx->h1.p, (size_t)B * L * d, 0x9E3779B9u);  // random rows
   HIPCHECK(hipGetLastError());
   // (MIXED: the recomputed rows of batch element 0 are NOT written back -- the probe leaves the tables as they are)
+  // (layer 1 where there is one: layer 0 never takes the static-bound instance the other layers may run)
   auto launch = [&](unsigned long long* st) {
-    return run_attention(ctx, p, ctx->layers[0], ctx->h1.p, cu.tables ? ctx->kt : nullptr, cu.tables ? ctx->vt : nullptr,
+    return run_attention(ctx, p, ctx->layers[m.num_layers > 1 ? 1 : 0], ctx->h1.p, cu.tables ? ctx->kt : nullptr, cu.tables ? ctx->vt : nullptr,
                          nullptr, nullptr, B, cu.n_own, s, st);
   };
   if ((rc = time_launches(ctx, s, [&]() { return launch(nullptr); }, 20, warm_seconds, iters, ms_out))) return rc;

@@ -428,8 +428,8 @@ __global__ __launch_bounds__(64 * NW, 3) void k_ffn_rows(const float* __restrict
     lnp[i] = i < D ? b2[i] : i < 2 * D ? gam[i - D] : i < 3 * D ? bet[i - 2 * D]
            : i < 4 * D ? bo[i - 3 * D] : i < 5 * D ? gam1[i - 4 * D] : bet1[i - 5 * D];
   {
-    const float* src = slot_src(0) + lane * 4;  // (the out-projection slot has NFP fragment groups, the rest is padding)
-    for (int g = wave; g < (OP ? C::NFPP : C::SLOT_G); g += NW) dma_piece(src + g * 256, ring_base + g * 1024);
+    const float* src = slot_src(0);  // (the out-projection slot has NFP fragment groups, the rest is padding)
+    for (int g = wave; g < (OP ? C::NFPP : C::SLOT_G); g += NW) dma_piece_sbase(src + g * 256, lane * 16, ring_base + g * 1024);
   }
   float4 rin[CTA][4], rinrem[NRA];  // fused form: the layer input rows (LN1's residual)
   load_rows(X, xv, xrem);
@@ -440,12 +440,12 @@ __global__ __launch_bounds__(64 * NW, 3) void k_ffn_rows(const float* __restrict
 #pragma unroll
   for (int j = 1; j < C::AHEAD; ++j)
     if (j < total) {  // NPW pieces per wave (a piece index past the slot wraps: fetched twice), like the slots after it
-      const float* src = slot_src(j % NSL) + lane * 4;
+      const float* src = slot_src(j % NSL);
       const unsigned dst = ring_base + (unsigned)(j % NSLOT) * (C::SLOT_FLOATS * 4);
 #pragma unroll
       for (int i = 0; i < C::NPW; ++i) {
         const int g0 = wave + i * NW, g = g0 < C::SLOT_G ? g0 : g0 - C::SLOT_G;
-        dma_piece(src + g * 256, dst + g * 1024);
+        dma_piece_sbase(src + g * 256, lane * 16, dst + g * 1024);
       }
     }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the LN parameter writes
@@ -481,13 +481,14 @@ __global__ __launch_bounds__(64 * NW, 3) void k_ffn_rows(const float* __restrict
   const float* slot = ringl + (it % NSLOT) * C::SLOT_FLOATS;                                                           \
   const float* nslot = ringl + ((it + 1) % NSLOT) * C::SLOT_FLOATS;                                                    \
   const bool dma_on = it + C::AHEAD < total;                                                                           \
-  const float* dma_src = slot_src(wnext) + lane_i * 4;                                                                 \
+  const float* dma_src = slot_src(wnext); /* wave-uniform: the pieces' addresses are scalar arithmetic */              \
+  const unsigned dma_lane = (unsigned)lane_i * 16u;                                                                    \
   const unsigned dma_dst = ring_base + (unsigned)((it + C::AHEAD) % NSLOT) * (C::SLOT_FLOATS * 4);                     \
   int dma_g = wave; /* next piece of the slot this wave issues */                                                      \
   auto issue_piece = [&]() { /* (a piece index past the slot wraps to a piece some other wave also fetches) */         \
     if (dma_on) {                                                                                                      \
       const int g = dma_g < C::SLOT_G ? dma_g : dma_g - C::SLOT_G;                                                     \
-      dma_piece(dma_src + g * 256, dma_dst + g * 1024);                                                                \
+      dma_piece_sbase(dma_src + g * 256, dma_lane, dma_dst + g * 1024);                                                \
       dma_g += NW;                                                                                                     \
     }                                                                                                                  \
   }

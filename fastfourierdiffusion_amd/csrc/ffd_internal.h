@@ -129,6 +129,7 @@ __device__ __forceinline__ double block_sum(double v, double* red) {  // fixed-o
   I("attn_hpw", g_attn_hpw, 0, v >= 0 && v <= 2)          /* heads per attention workgroup: 0 heuristic | 1 / 2 */ \
   I("attn_qg", g_attn_qg, 0, v >= 0 && v <= 3)            /* q-tile group size of the attention kernels: 0 heuristic | 1 / 2 / 3 */ \
   B("attn_kvq", g_attn_kvq, 1)                            /* small-batch split attention on the kv | q pack (q projected for own q-tiles only) */ \
+  B("attn_static_bound", g_attn_static_bound, 1)          /* fused attention without the per-launch score bound in layers whose weights bound the scores (LayerWeights::attn_bounded) */ \
   B("embed_ldsx", g_embed_ldsx, 1)                        /* embedding: the wave's x rows through LDS (1) | per-lane loads (0) */ \
   I("embed_threads", g_embed_threads, 262144, v >= 256)   /* threads the embed grid aims at (tools/probes/embed_sweep.py: 114 us at 256 k, 118 at 512 k, 137 at 128 k on the config-5 shape) */ \
   I("lstm_wave", g_lstm_wave, 1, v >= 0 && v <= 2)        /* LSTM layers as a wavefront (1, 2 the same) | 0 the per-layer kernels k_linear_rm + k_lstm_layer */ \
@@ -157,6 +158,13 @@ __device__ __forceinline__ void wait_vm() {
 __device__ __forceinline__ void dma_piece(const float* g, unsigned lds_byte) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_byte), "v"(g)
                : "memory");  // (m0 is a reserved register: hipcc keeps nothing in it across statements)
+}
+// The same piece from a wave-uniform base (an SGPR pair) + a 32-bit per-lane byte offset (lane x 16 for a contiguous
+// piece): the address of each piece is then scalar arithmetic, where the per-lane 64-bit pointer above costs a vector
+// 64-bit add per piece (k_ffn_rows: fp32 vector instructions add to its matrix time).
+__device__ __forceinline__ void dma_piece_sbase(const float* base, unsigned lane_byte, unsigned lds_byte) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_byte), "v"(lane_byte), "s"(base)
+               : "memory");
 }
 __device__ __forceinline__ unsigned lds_addr(const float* p) {
   return (unsigned)(unsigned long)((const __attribute__((address_space(3))) float*)p);
@@ -199,6 +207,9 @@ struct LayerWeights {
   float *aw_full = nullptr, *aw_q = nullptr;    // per-head packs of the fused in-projection + attention kernel
   float *aw_full2 = nullptr, *aw_q2 = nullptr;  // same, per pair of heads (two-head workgroups)
   float* aw_kvq = nullptr;                      // per head, tile 0 = k | v, tile 1 = q (the split small-batch form)
+  // every head's static score bound (ffd_host_attn_score_bound, from the norm2 of the layer in front) is within the
+  // attention kernels' threshold: set by ffd_finalize_weights; layer 0 (input: the embedding) never
+  bool attn_bounded = false;
 };
 
 hipError_t launch_pack_dweight(const float* W, float* Wp, int N, int D, hipStream_t s);
@@ -308,6 +319,10 @@ hipError_t launch_pack_ffn_split(const float* W1, const float* W2, void* w1s, vo
 hipError_t launch_ffn_ln_split(const float* X, const LayerWeights& w, float* Y, int M, int D, int F, hipStream_t s,
                                unsigned long long* stamp = nullptr);
 // fused in-projection + attention (ffd_qkvattn.hip)
+// scores (log2 domain) may sit this far from the softmax reference before it is refreshed; a head whose |q| |k| stays
+// within it needs no running maximum (head_norms per launch, or LayerWeights::attn_bounded from the weights)
+constexpr float ATTN_SCORE_T = 64.0f;
+float attn_q_scale(int hd);  // log2(e) / sqrt(hd), as launch_pack_attn folds it into the q rows of the packs
 size_t attn_pack_floats(int D, int H, int hpw, int q_only);  // q_only = pack mode: 0 q | k | v, 1 q only, 2 tile 0 = k | v, tile 1 = q
 bool attn_kvq_supported(int hd);                              // head dims with a mode-2 pack (the split small-batch form's)
 hipError_t launch_pack_attn(const float* in_w, const float* in_b, float* pack, int D, int H, int hpw, int q_only,
@@ -324,6 +339,7 @@ struct AttnArgs {
   float* out;               // (M x d) row-major
   int B, L, n_own;          // tokens >= n_own take K/V from the tables
   unsigned long long* stamp;
+  bool static_bound = false;  // the layer's scores are bounded by its weights: the instance without head_norms (kt == nullptr only)
 };
 // kspl > 0: the small-batch split form with that many key pieces per q-tile (hpw 1; no stamped twin); else qg q-tiles per
 // wave (hpw 2: per wave pair)
@@ -382,6 +398,7 @@ struct LayerPlan {
   int q_only;  // 0 q | k | v pack, 1 q only (pure cache hit), 2 kv | q pack
   int kspl;    // key pieces of the small-batch split form, 0 = one workgroup per head (pair)
   int qg;      // q-tiles per wave (per wave pair at hpw 2; 1 in the split form)
+  bool attn_static;  // fused kernels: layers with LayerWeights::attn_bounded run the instances without head_norms
   FfnForm ffn;
   int mb;              // FFN_LN_OPROJ / FFN_LN: 16-row tiles per workgroup
   bool rem;            //   GEMM2's remainder rows on the 4x4x1 MFMA

@@ -130,12 +130,14 @@ size_t attn_pack_floats(int D, int H, int hpw, int q_only) {
   return (size_t)(H / hpw) * nct * ((D + 15) / 16) * 256 + (size_t)(H / hpw) * nct * 16;
 }
 
+float attn_q_scale(int hd) { return 1.4426950408889634f / sqrtf((float)hd); }
+
 hipError_t launch_pack_attn(const float* in_w, const float* in_b, float* pack, int D, int H, int hpw, int q_only,
                             hipStream_t s) {
   const int hd = D / H;
   const int nct = attn_nct(hd, hpw, q_only);
   float* abp = pack + (size_t)(H / hpw) * nct * ((D + 15) / 16) * 256;
-  const float qscale = 1.4426950408889634f / sqrtf((float)hd);
+  const float qscale = attn_q_scale(hd);
   hipLaunchKernelGGL(k_pack_attn, dim3(64), dim3(256), 0, s, in_w, in_b, pack, abp, D, H, hd, hpw, nct, q_only, qscale);
   return hipGetLastError();
 }
@@ -189,7 +191,7 @@ struct HeadDims {
   static constexpr int SX = HD / 2;         // the -m_ref step's index
   static constexpr int HX = HD & 1;         // ... and the half that carries it
   static constexpr int HP = (HD + 1) / 2;   // output feature pairs per row
-  static constexpr float T = 64.0f;  // scores (log2 domain) may sit this far from the reference before it is refreshed
+  static constexpr float T = ATTN_SCORE_T;  // scores (log2 domain) may sit this far from the reference before it is refreshed
   static constexpr size_t floats(int LS) { return (size_t)LS * (8 + 4 * KST); }  // V | K^T | Q^T
 };
 
@@ -284,13 +286,44 @@ typedef const float lds_f32;
 typedef const float4 lds_f32x4;
 #endif
 
+// ---- phase 1's store plan ----------------------------------------------------------------------------
+// Where a lane's feature of a 16-token projection tile goes.  The lane holds the feature for four consecutive tokens;
+// in a Q^T / K^T row they are 4 bytes apart, in the V image ([token][8]) 32.  Both shapes are four ds_write_b32 at
+// a, a + s, a + 2 s, a + 3 s with per-lane a and s; left to the compiler, it re-derives a and the three offsets with
+// selects on the lane's kind in every tile (~ 9 vector instructions per feature tile).  Here the byte address of the
+// wave's first tile, the three offsets and the step to the wave's next tile are worked out once in front of the tile
+// loop and made opaque (the empty asm), so that a tile costs three adds for the addresses and one for the step.
+// Same values to the same addresses in the same order.  (k_qkv_attention_mh only: in k_qkv_attention the five registers
+// per feature tile cost its 128-register instances scratch and two others a wave of occupancy.)
+struct StorePlan {
+  unsigned a, s1, s2, s3, step;
+  // image_float: float index of the feature's token 0 in LDS (V row: of its column); tok: first token of the lane's four
+  // in the wave's first tile; tile_tokens: tokens between two tiles of the wave
+  __device__ __forceinline__ void init(const float* lds0, int image_float, bool vrow, int tok, int tile_tokens) {
+    unsigned s = vrow ? 32u : 4u;
+    asm("" : "+v"(s));  // (one select; the rest is arithmetic on it)
+    a = lds_addr(lds0) + 4u * (unsigned)image_float + (unsigned)tok * s;
+    s1 = s, s2 = s + s, s3 = s2 + s, step = (unsigned)tile_tokens * s;
+    asm("" : "+v"(a), "+v"(s1), "+v"(s2), "+v"(s3), "+v"(step));
+  }
+  __device__ __forceinline__ void store(float x, float y, float z, float w) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(3))) float lds_w32;
+    *(lds_w32*)(a) = x, *(lds_w32*)(a + s1) = y, *(lds_w32*)(a + s2) = z, *(lds_w32*)(a + s3) = w;
+#endif
+  }
+  __device__ __forceinline__ void next_tile() { a += step; }
+};
+
 // ---- phase 2: attention ------------------------------------------------------------------------------
 // One wave attends q-tiles qt0 = q_first, q_first + q_step, ... < q_end, QG at a time, over key tiles [t_lo, t_hi) of
 // the head's LDS images.  Their row stride is LSC where the kernel has a compile-time one (0: the run-time LSR), so
 // that the LDS addresses are per-lane bases + immediate offsets.  STORE: normalise and write query row q to
 // orow0 + q * ostride; otherwise (the split form's key pieces) the last q-group's rows are returned unnormalised for
-// the caller to merge.
-template <int HD, int QG, bool STAMP, bool STORE, int LSC>
+// the caller to merge.  BOUNDED: the head's scores are known to be within T (the layer's static bound), so the reference
+// stays 0 for good and its refresh, the -m_ref k-step and their state compile out; the arithmetic that remains is the
+// head_bounded = true path's, instruction for instruction.
+template <int HD, int QG, bool STAMP, bool STORE, int LSC, bool BOUNDED = false>
 __device__ __forceinline__ QRows<HD, QG> attend_qtiles(lds_f32* vs, lds_f32* kts, lds_f32* qts, int LSR,
                                                        int q_first, int q_step, int q_end, int t_lo, int t_hi,
                                                        bool head_bounded, int L, float* orow0, int ostride,
@@ -385,7 +418,7 @@ __device__ __forceinline__ QRows<HD, QG> attend_qtiles(lds_f32* vs, lds_f32* kts
 #pragma unroll
       for (int g = 0; g < QG; ++g) {
         // while the head's bound stays within T and no lane of the wave uses a reference, nothing below can trigger
-        if (ref_on || !head_bounded) {
+        if (!BOUNDED && (ref_on || !head_bounded)) {
         float bm = __builtin_fmaxf(__builtin_fmaxf(sc[g][0], sc[g][1]), sc[g][2]);
 #pragma unroll
         for (int r = 3; r < 15; r += 2) bm = __builtin_fmaxf(__builtin_fmaxf(bm, sc[g][r]), sc[g][r + 1]);
@@ -491,7 +524,10 @@ __device__ __forceinline__ QRows<HD, QG> attend_qtiles(lds_f32* vs, lds_f32* kts
 // LDS and are merged in piece order, so the result does not depend on timing.
 // KVQ (split form with the kv | q pack, NCT = 2): tile 0 holds the head's k and v features, tile 1 its q features, and a
 // workgroup projects tile 1 only for the tokens of its own q-tiles -- the other q-tiles' workgroups project theirs.
-template <int D, int HD, int QG, int NCT, bool SPLIT = false, bool STAMP = false, bool KVQ = false>
+// SB (static bound; launches without K/V tables only): the layer's weights bound every score within T
+// (LayerWeights::attn_bounded), so the norm words, head_norms and the barrier behind it are not there and the attention
+// phase is the BOUNDED one.
+template <int D, int HD, int QG, int NCT, bool SPLIT = false, bool STAMP = false, bool KVQ = false, bool SB = false>
 __global__ __launch_bounds__(256, (SPLIT && NCT >= 2 ? 2 : QG <= 2 ? 4 : 3)) void k_qkv_attention(
     const float* __restrict__ x, const float* __restrict__ awp, const float* __restrict__ kt,
     const float* __restrict__ vt, float* __restrict__ kt_out, float* __restrict__ vt_out, float* __restrict__ out,
@@ -524,7 +560,9 @@ __global__ __launch_bounds__(256, (SPLIT && NCT >= 2 ? 2 : QG <= 2 ? 4 : 3)) voi
   float* qts = kts + (size_t)2 * KST * LS;       // Q^T [2*KST][LS]   (already scaled by log2(e)/sqrt(hd))
   constexpr int PS = 2 + 2 * HeadDims<HD>::HP;  // SPLIT partials per query row: reference exponent, row sum, output
   unsigned* nrm = reinterpret_cast<unsigned*>(lds + HeadDims<HD>::floats(LS) + (SPLIT ? 4 * 32 * PS : 0));  // see head_norms
-  if (threadIdx.x < 2) nrm[threadIdx.x] = 0u;  // (ordered before head_norms by the barrier behind the projection)
+  if constexpr (!SB) {
+    if (threadIdx.x < 2) nrm[threadIdx.x] = 0u;  // (ordered before head_norms by the barrier behind the projection)
+  }
 
   if constexpr (HD % 2 == 1) {  // odd head dims read one pad row / pad column: keep them zero
     for (int idx = threadIdx.x; idx < LS * (8 + 4 * KST); idx += blockDim.x) vs[idx] = 0.f;
@@ -703,31 +741,36 @@ __global__ __launch_bounds__(256, (SPLIT && NCT >= 2 ? 2 : QG <= 2 ? 4 : 3)) voi
     }
   }
   if constexpr (STAMP) st.t[3] = FFD_STAMP_T();
-  if (kt != nullptr) fill_from_tables<HD>(vs, kts, LS, kt, vt, h, L, Lp, n_own, q_only, threadIdx.x, blockDim.x);
-  __syncthreads();
-  {  // (q rows outside the projected token range were never written: they stay out of the bound)
-    int jq0 = 0, jq1 = Lp;
-    if constexpr (SPLIT) {
-      if (q_only || KVQ) {
-        const int qpw = nwaves / kspl;
-        jq0 = min(32 * qs * qpw, Lp), jq1 = min(jq0 + 32 * qpw, Lp);
-      }
-    }
-    head_norms<HD>(kts, qts, nrm, Lp, LS, threadIdx.x, blockDim.x, jq0, jq1);
+  if constexpr (!SB) {
+    if (kt != nullptr) fill_from_tables<HD>(vs, kts, LS, kt, vt, h, L, Lp, n_own, q_only, threadIdx.x, blockDim.x);
   }
-  if (kt_out != nullptr && b == 0 && qs == 0)
-    publish_kv<HD>(vs, kts, LS, kt_out, vt_out, h, L, n_own, threadIdx.x, blockDim.x);
+  __syncthreads();  // the LDS images
+  bool bounded = true;
+  if constexpr (!SB) {
+    {  // (q rows outside the projected token range were never written: they stay out of the bound)
+      int jq0 = 0, jq1 = Lp;
+      if constexpr (SPLIT) {
+        if (q_only || KVQ) {
+          const int qpw = nwaves / kspl;
+          jq0 = min(32 * qs * qpw, Lp), jq1 = min(jq0 + 32 * qpw, Lp);
+        }
+      }
+      head_norms<HD>(kts, qts, nrm, Lp, LS, threadIdx.x, blockDim.x, jq0, jq1);
+    }
+    if (kt_out != nullptr && b == 0 && qs == 0)
+      publish_kv<HD>(vs, kts, LS, kt_out, vt_out, h, L, n_own, threadIdx.x, blockDim.x);
 
-  __syncthreads();  // the tile norms
+    __syncthreads();  // the tile norms
+    bounded = head_bounded<HD>(nrm);
+  }
   if constexpr (STAMP) st.t[4] = FFD_STAMP_T();
-  const bool bounded = head_bounded<HD>(nrm);
   float* orow0 = out + (size_t)b * L * D + h * HD;  // the head's output row for query token q: orow0 + q * D
   if constexpr (SPLIT) {  // one (q-tile, key piece) per wave
     const int qpw = nwaves / kspl, kps = (KT + kspl - 1) / kspl;
     const int qt = qs * qpw + wave / kspl, t_lo = (wave % kspl) * kps;
     int t_hi = min(KT, t_lo + kps);
     if (qt >= KT) t_hi = t_lo;  // ragged last workgroup: an empty piece (every wave reaches the merge)
-    const QRows<HD, 1> r = attend_qtiles<HD, 1, STAMP, false, 0>((lds_f32*)vs, (lds_f32*)kts, (lds_f32*)qts, LS, qt, 1,
+    const QRows<HD, 1> r = attend_qtiles<HD, 1, STAMP, false, 0, SB>((lds_f32*)vs, (lds_f32*)kts, (lds_f32*)qts, LS, qt, 1,
                                                                  qt + 1, t_lo, t_hi, bounded, L, orow0, D, st);
     const int half = lane >> 5, l31 = lane & 31;
     float* part = lds + HeadDims<HD>::floats(LS);  // [wave][32][PS]
@@ -763,7 +806,7 @@ __global__ __launch_bounds__(256, (SPLIT && NCT >= 2 ? 2 : QG <= 2 ? 4 : 3)) voi
       orow0[(size_t)q * D + e] = ot / lt;
     }
   } else {
-    attend_qtiles<HD, QG, STAMP, true, LSC>((lds_f32*)vs, (lds_f32*)kts, (lds_f32*)qts, LS, wave * QG, nwaves * QG, KT,
+    attend_qtiles<HD, QG, STAMP, true, LSC, SB>((lds_f32*)vs, (lds_f32*)kts, (lds_f32*)qts, LS, wave * QG, nwaves * QG, KT,
                                             0, KT, bounded, L, orow0, D, st);
   }
   if constexpr (STAMP) st.write(stamp, nwaves);
@@ -778,7 +821,8 @@ __global__ __launch_bounds__(256, (SPLIT && NCT >= 2 ? 2 : QG <= 2 ? 4 : 3)) voi
 // staged once in LDS and read as the MFMA B operand from there.  Two heads = 4 waves, one per SIMD: a 6-wave
 // workgroup (3 heads) leaves the CU with a single resident workgroup (two of its waves land on SIMDs 0 and 1,
 // so a second one never fits at 3 waves per SIMD) and was slower.
-template <int D, int HD, int HPW, int QG, int NCT, bool QO, bool STAMP = false>
+// SB: see k_qkv_attention.
+template <int D, int HD, int HPW, int QG, int NCT, bool QO, bool STAMP = false, bool SB = false>
 __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
     const float* __restrict__ x, const float* __restrict__ awp, const float* __restrict__ kt,
     const float* __restrict__ vt, float* __restrict__ kt_out, float* __restrict__ vt_out, float* __restrict__ out,
@@ -813,8 +857,10 @@ __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
   constexpr int RS = HeadDims<HD>::floats(LS);                 // floats per head region: V | K^T | Q^T
   float4* wl = reinterpret_cast<float4*>(lds + (size_t)HPW * RS);  // weight pack [NCT][S4][64] float4
   constexpr int fph = QO ? HD : 3 * HD;                        // features per head in this pack (QO == q_only)
-  if (threadIdx.x < 2 * HPW)  // the heads' norm words (ordered before head_norms by the barriers of the projection)
-    reinterpret_cast<unsigned*>(lds + (size_t)HPW * RS + (size_t)NCT * S4 * 256)[threadIdx.x] = 0u;
+  if constexpr (!SB) {
+    if (threadIdx.x < 2 * HPW)  // the heads' norm words (ordered before head_norms by the barriers of the projection)
+      reinterpret_cast<unsigned*>(lds + (size_t)HPW * RS + (size_t)NCT * S4 * 256)[threadIdx.x] = 0u;
+  }
 
   // ------------------------------------------------------------------ phase 1: projection
   {
@@ -847,16 +893,16 @@ __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
     // where this lane's feature (16 ct + n) goes, worked out once: float index of token 0 in the LDS images -- Q^T / K^T
     // rows take a lane's four tokens as one float4, V rows ([token][8]) as four scalars 8 floats apart; -1 = no feature
     int sbase[NCTM];
-    bool sv[NCTM];
+    StorePlan sp[NCTM];
 #pragma unroll
     for (int ct = 0; ct < NCTM; ++ct) {
       bias[ct] = abp[ct * 16 + n];
       const int fi = 16 * ct + n;
       const int hh = fi / fph, f = fi - hh * fph;
       const int reg = f / HD, e = f - reg * HD;
-      sv[ct] = reg == 2;
       sbase[ct] = hh >= HPW ? -1
                   : hh * RS + (reg == 0 ? LS * 8 + 2 * KST * LS + e * LS : reg == 1 ? LS * 8 + e * LS : e);
+      sp[ct].init(lds, sbase[ct], reg == 2, 16 * wave + 4 * qq, 16 * NW);
     }
     __syncthreads();
     if constexpr (STAMP) st.t[2] = FFD_STAMP_T();
@@ -936,19 +982,12 @@ __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
           }
         }
       }
-      const int t0 = 16 * tt + 4 * qq;  // D: lane holds tokens t0 .. t0+3 of feature 16 ct + n
+      // D: lane holds tokens 16 tt + 4 qq .. + 3 of feature 16 ct + n
 #pragma unroll
       for (int ct = 0; ct < NCTM; ++ct) {
-        const float4 o = float4{acc[ct][0] + bias[ct], acc[ct][1] + bias[ct], acc[ct][2] + bias[ct],
-                                acc[ct][3] + bias[ct]};
-        if (sbase[ct] >= 0) {
-          if (!sv[ct]) {
-            *reinterpret_cast<float4*>(lds + sbase[ct] + t0) = o;
-          } else {
-            float* vp = lds + sbase[ct] + t0 * 8;
-            vp[0] = o.x, vp[8] = o.y, vp[16] = o.z, vp[24] = o.w;
-          }
-        }
+        if (sbase[ct] >= 0)
+          sp[ct].store(acc[ct][0] + bias[ct], acc[ct][1] + bias[ct], acc[ct][2] + bias[ct], acc[ct][3] + bias[ct]);
+        sp[ct].next_tile();
       }
     }
   }
@@ -959,16 +998,22 @@ __global__ __launch_bounds__(128 * HPW, 3) void k_qkv_attention_mh(
   float* vs = lds + (size_t)hh * RS;
   float* kts = vs + LS * 8;
   float* qts = kts + 2 * KST * LS;
-  if (kt != nullptr) fill_from_tables<HD>(vs, kts, LS, kt, vt, h, L, Lp, n_own, q_only, gw * 64 + lane, 128);
-  __syncthreads();
-  unsigned* nrm = reinterpret_cast<unsigned*>(lds + (size_t)HPW * RS + (size_t)NCT * S4 * 256) + 2 * hh;  // this head's pair, see head_norms
-  head_norms<HD>(kts, qts, nrm, Lp, LS, gw * 64 + lane, 128);
-  if (kt_out != nullptr && b == 0) publish_kv<HD>(vs, kts, LS, kt_out, vt_out, h, L, n_own, gw * 64 + lane, 128);
+  if constexpr (!SB) {
+    if (kt != nullptr) fill_from_tables<HD>(vs, kts, LS, kt, vt, h, L, Lp, n_own, q_only, gw * 64 + lane, 128);
+  }
+  __syncthreads();  // the LDS images
+  bool bounded = true;
+  if constexpr (!SB) {
+    unsigned* nrm = reinterpret_cast<unsigned*>(lds + (size_t)HPW * RS + (size_t)NCT * S4 * 256) + 2 * hh;  // this head's pair, see head_norms
+    head_norms<HD>(kts, qts, nrm, Lp, LS, gw * 64 + lane, 128);
+    if (kt_out != nullptr && b == 0) publish_kv<HD>(vs, kts, LS, kt_out, vt_out, h, L, n_own, gw * 64 + lane, 128);
 
-  __syncthreads();  // the tile norms
+    __syncthreads();  // the tile norms
+    bounded = head_bounded<HD>(nrm);
+  }
   if constexpr (STAMP) st.t[4] = FFD_STAMP_T();
-  attend_qtiles<HD, QG, STAMP, true, LS>((lds_f32*)vs, (lds_f32*)kts, (lds_f32*)qts, LS, gw * QG, 2 * QG, KT, 0, KT,
-                                         head_bounded<HD>(nrm), L, out + (size_t)b * L * D + h * HD, D, st);
+  attend_qtiles<HD, QG, STAMP, true, LS, SB>((lds_f32*)vs, (lds_f32*)kts, (lds_f32*)qts, LS, gw * QG, 2 * QG, KT, 0, KT,
+                                             bounded, L, out + (size_t)b * L * D + h * HD, D, st);
   if constexpr (STAMP) st.write(stamp, NW);
 }
 
@@ -978,19 +1023,26 @@ static hipError_t launch_mh_t(const AttnArgs& a, int q_only, hipStream_t s) {
   const int KT = (a.L + 31) / 32;
   const size_t lds = (HPW * HeadDims<HD>::floats(64 * QG + 4) + (size_t)NCT * S4 * 256 + (size_t)HPW * 2) * sizeof(float);
   if (cdiv(2 * KT, 2 * HPW) > 3 || cdiv(KT, 2) > QG) return hipErrorInvalidValue;  // <= 3 token tiles, one q-group per wave
-  if constexpr (D == 72 && HD == 6) {  // (the stamped twin exists for the headline shape only)
+  if (a.static_bound && (QO || a.kt != nullptr)) return hipErrorInvalidValue;  // the static form is the full pack's, without tables
+  auto go = [&](auto kern, unsigned long long* stamp) {
+    hipLaunchKernelGGL(kern, dim3(a.B * (D / HD / HPW)), dim3(128 * HPW), lds, s, a.x, a.pack, a.kt, a.vt, a.kt_out, a.vt_out,
+                       a.out, a.B, a.L, a.n_own, q_only, stamp);
+    return hipGetLastError();
+  };
+  if constexpr (D == 72 && HD == 6) {  // (the stamped twins exist for the headline shape only)
     if (a.stamp != nullptr) {
-      hipLaunchKernelGGL((k_qkv_attention_mh<D, HD, HPW, QG, NCT, QO, true>), dim3(a.B * (D / HD / HPW)), dim3(128 * HPW), lds,
-                         s, a.x, a.pack, a.kt, a.vt, a.kt_out, a.vt_out, a.out, a.B, a.L, a.n_own, q_only, a.stamp);
-      return hipGetLastError();
+      if constexpr (!QO) {
+        if (a.static_bound) return go(k_qkv_attention_mh<D, HD, HPW, QG, NCT, QO, true, true>, a.stamp);
+      }
+      return go(k_qkv_attention_mh<D, HD, HPW, QG, NCT, QO, true>, a.stamp);
     }
   }
   if (a.stamp != nullptr) return hipErrorInvalidValue;
   if (q_only != (QO ? 1 : 0)) return hipErrorInvalidValue;
-  auto kern = k_qkv_attention_mh<D, HD, HPW, QG, NCT, QO>;
-  hipLaunchKernelGGL(kern, dim3(a.B * (D / HD / HPW)), dim3(128 * HPW), lds, s, a.x, a.pack, a.kt, a.vt, a.kt_out, a.vt_out,
-                     a.out, a.B, a.L, a.n_own, q_only, (unsigned long long*)nullptr);
-  return hipGetLastError();
+  if constexpr (!QO) {
+    if (a.static_bound) return go(k_qkv_attention_mh<D, HD, HPW, QG, NCT, QO, false, true>, nullptr);
+  }
+  return go(k_qkv_attention_mh<D, HD, HPW, QG, NCT, QO>, nullptr);
 }
 
 // 2 heads per workgroup, 2 waves per head: L <= 192 (<= 3 q-tiles per wave, 12 token tiles over 4 waves)
@@ -1004,38 +1056,51 @@ static hipError_t launch_mh2(const AttnArgs& a, int q_only, int qg, hipStream_t 
   return hipErrorInvalidValue;
 }
 
-template <int D, int HD, int QG, int NCT>
+// FULL: the q | k | v pack (the only one with a static-bound instance)
+template <int D, int HD, int QG, int NCT, bool FULL>
 static hipError_t launch_t(const AttnArgs& a, int q_only, hipStream_t s) {
   const int KT = (a.L + 31) / 32;
   const size_t lds = (HeadDims<HD>::floats(KT * 32 + 4) + (size_t)2 * KT) * sizeof(float);
   int nwaves = cdiv(KT, QG);
   if (nwaves > 4) nwaves = 4;
   if (cdiv(2 * KT, nwaves) > 8) return hipErrorInvalidValue;  // the projection loop is unrolled for <= 8 token tiles per wave
-  if constexpr (D == 72 && HD == 6 && NCT == 2) {  // (the stamped twin exists for the headline model's full pack only)
+  if (a.static_bound && (!FULL || q_only || a.kt != nullptr)) return hipErrorInvalidValue;
+  auto go = [&](auto kern, unsigned long long* stamp) {
+    hipLaunchKernelGGL(kern, dim3(a.B * (D / HD)), dim3(64 * nwaves), lds, s, a.x, a.pack, a.kt, a.vt, a.kt_out, a.vt_out,
+                       a.out, a.B, a.L, a.n_own, q_only, 1, 1, stamp);
+    return hipGetLastError();
+  };
+  if constexpr (D == 72 && HD == 6 && NCT == 2) {  // (the stamped twins exist for the headline model's full pack only)
     if (a.stamp != nullptr) {
-      hipLaunchKernelGGL((k_qkv_attention<D, HD, QG, NCT, false, true>), dim3(a.B * (D / HD)), dim3(64 * nwaves), lds, s, a.x,
-                         a.pack, a.kt, a.vt, a.kt_out, a.vt_out, a.out, a.B, a.L, a.n_own, q_only, 1, 1, a.stamp);
-      return hipGetLastError();
+      if (a.static_bound) return go(k_qkv_attention<D, HD, QG, NCT, false, true, false, true>, a.stamp);
+      return go(k_qkv_attention<D, HD, QG, NCT, false, true>, a.stamp);
     }
   }
   if (a.stamp != nullptr) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_qkv_attention<D, HD, QG, NCT>), dim3(a.B * (D / HD)), dim3(64 * nwaves), lds, s, a.x, a.pack, a.kt,
-                     a.vt, a.kt_out, a.vt_out, a.out, a.B, a.L, a.n_own, q_only, 1, 1, (unsigned long long*)nullptr);
-  return hipGetLastError();
+  if constexpr (FULL) {
+    if (a.static_bound) return go(k_qkv_attention<D, HD, QG, NCT, false, false, false, true>, nullptr);
+  }
+  return go(k_qkv_attention<D, HD, QG, NCT>, nullptr);
 }
 
 // small batches: 4 waves per workgroup, 4 / kspl q-tiles per workgroup, the key range of each cut into kspl pieces
-template <int D, int HD, int NCT, bool KVQ = false>
+template <int D, int HD, int NCT, bool KVQ = false, bool FULL = false>
 static hipError_t launch_split_t(const AttnArgs& a, int q_only, int kspl, hipStream_t s) {
   const int KT = (a.L + 31) / 32;
   if (cdiv(2 * KT, 4) > 8 || (kspl != 1 && kspl != 2 && kspl != 4)) return hipErrorInvalidValue;
   const int qsplit = cdiv(KT, 4 / kspl);
   const size_t lds =
       (HeadDims<HD>::floats(KT * 32 + 4) + (size_t)4 * 32 * (2 + 2 * HeadDims<HD>::HP) + (size_t)2 * KT) * sizeof(float);
-  hipLaunchKernelGGL((k_qkv_attention<D, HD, 1, NCT, true, false, KVQ>), dim3(a.B * (D / HD) * qsplit), dim3(256), lds, s, a.x,
-                     a.pack, a.kt, a.vt, a.kt_out, a.vt_out, a.out, a.B, a.L, a.n_own, q_only, qsplit, kspl,
-                     (unsigned long long*)nullptr);
-  return hipGetLastError();
+  if (a.static_bound && (!FULL || q_only || a.kt != nullptr)) return hipErrorInvalidValue;
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(a.B * (D / HD) * qsplit), dim3(256), lds, s, a.x, a.pack, a.kt, a.vt, a.kt_out, a.vt_out,
+                       a.out, a.B, a.L, a.n_own, q_only, qsplit, kspl, (unsigned long long*)nullptr);
+    return hipGetLastError();
+  };
+  if constexpr (FULL) {
+    if (a.static_bound) return go(k_qkv_attention<D, HD, 1, NCT, true, false, KVQ, true>);
+  }
+  return go(k_qkv_attention<D, HD, 1, NCT, true, false, KVQ>);
 }
 
 // Key pieces per q-tile of the small-batch split form, 0 when the one-workgroup-per-head(-pair) kernels run: the
@@ -1067,15 +1132,15 @@ static hipError_t launch_dh(const AttnArgs& a, int q_only, int kspl, int qg, hip
   if (kspl) {
     if (a.stamp != nullptr) return hipErrorInvalidValue;  // (no stamped twin of the split form)
     if constexpr (2 * HD <= 16 && 3 * HD > 16) {  // (q_only == 2: the caller handed over the kv | q pack)
-      if (q_only == 2) return launch_split_t<D, HD, 2, true>(a, 0, kspl, s);
+      if (q_only == 2) return launch_split_t<D, HD, 2, true, true>(a, 0, kspl, s);
     }
     if (q_only == 2) return hipErrorInvalidValue;
-    return q_only ? launch_split_t<D, HD, 1>(a, 1, kspl, s) : launch_split_t<D, HD, NCTF>(a, 0, kspl, s);
+    return q_only ? launch_split_t<D, HD, 1>(a, 1, kspl, s) : launch_split_t<D, HD, NCTF, false, true>(a, 0, kspl, s);
   }
   if (q_only == 2) return hipErrorInvalidValue;  // the kv | q pack is the split form's only
   if (q_only && a.stamp != nullptr) return hipErrorInvalidValue;
   // (instances in the order they were first named in: the device code keeps its layout)
-#define FFD_QG(g, nct) if (qg == g) return launch_t<D, HD, g, nct>(a, q_only, s);
+#define FFD_QG(g, nct) if (qg == g) return launch_t<D, HD, g, nct, false>(a, q_only, s);
   if (q_only) {
     FFD_QG(1, 1) FFD_QG(3, 1)
     if constexpr (HD <= 6) {
@@ -1084,6 +1149,8 @@ static hipError_t launch_dh(const AttnArgs& a, int q_only, int kspl, int qg, hip
     FFD_QG(2, 1)
     return hipErrorInvalidValue;
   }
+#undef FFD_QG
+#define FFD_QG(g, nct) if (qg == g) return launch_t<D, HD, g, nct, true>(a, q_only, s);
   FFD_QG(2, NCTF) FFD_QG(1, NCTF) FFD_QG(3, NCTF)
   if constexpr (HD <= 6) {  // (hd = 8 would spill at four query groups)
     FFD_QG(4, NCTF)

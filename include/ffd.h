@@ -122,6 +122,17 @@ int ffd_host_timesteps(int n, double eps, float* ts_out, float* step_size_out);
 /* E2CRFCache.determine_recompute_set (caching.py:131-181): the recompute set is
  * always the prefix [0, n); returns n (>=0) for `step`. */
 int ffd_host_gate(int step, int max_len, int K, int R);
+/* Static bound of one encoder layer's attention scores, from its weights alone (float64).  The layer's input is the
+ * output of a LayerNorm with parameters ln_weight / ln_bias (d_model each), so every input row x has
+ * |x| <= R = (sqrt(d_model) max|ln_weight| + |ln_bias|) (1 + 1e-4), and for head h
+ *   bound_out[h] = (q_scale (sigma(W_q^h) R + |b_q^h|)) (sigma(W_k^h) R + |b_k^h|)  >=  q_scale |q . k|
+ * for every query / key row of that head (W^h: the head's head_dim rows of in_proj_weight (3 d_model, d_model); sigma: an
+ * upper bound of the spectral norm; q_scale: the factor folded into q, log2(e) / sqrt(head_dim) in the fused kernels).
+ * Writes d_model / head_dim values.  ffd_finalize_weights evaluates it for every layer behind a norm2 (layers >= 1):
+ * where no head exceeds the kernels' threshold, the fused attention kernels skip their per-launch measurement of the
+ * same bound. */
+int ffd_host_attn_score_bound(const float* in_proj_weight, const float* in_proj_bias, const float* ln_weight,
+                              const float* ln_bias, int d_model, int head_dim, double q_scale, double* bound_out);
 
 /* ---- single operators (device pointers, stream ordered) ---------------- */
 
@@ -431,6 +442,9 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
  *                                              workgroup's own q-tiles only (head_dim 6 / 8) | the whole head;
  *   "attn_hpw" = 0 (heuristic) | 1 | 2         heads per workgroup of that kernel;
  *   "attn_qg" = 0 (heuristic) | 1 | 2 | 3      query tiles per wave;
+ *   "attn_static_bound" = 1 | 0                layers whose score bound holds from the weights alone (see
+ *                                              ffd_host_attn_score_bound) run the fused kernels' instances without the
+ *                                              per-launch bound (same results bit for bit) | every layer measures it;
  */
 int ffd_tune(const char* key, int value);
 int ffd_tune_get(const char* key, int* value);
