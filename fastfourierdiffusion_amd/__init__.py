@@ -7,7 +7,9 @@ sub-modules mirror the reference's import paths
     fdiff.models.score_models.{ScoreModule,LSTMScoreModule,MLPScoreModule} -> .models.score_models
     fdiff.schedulers.sde.{SDE,VPScheduler,VEScheduler}      -> .schedulers.sde
     fdiff.utils.caching.E2CRFCache               -> .utils.caching
-    fdiff.utils.fourier.{dft,idft,spectral_density,frequency_decompose_*,predict_hermite} -> .utils.fourier
+    fdiff.utils.fourier.{dft,idft,spectral_density,localization_metrics,smooth_frequency,frequency_decompose_*,
+                         predict_hermite} -> .utils.fourier
+    fdiff.visualization.spectral_interpretation.process_dataset (records, no plots) -> .visualization.spectral_interpretation
     fdiff.utils.dataclasses.DiffusableBatch      -> .utils.dataclasses
     fdiff.utils.extraction.{get_best_checkpoint,get_model_type,flatten_config} -> .utils.extraction
     fdiff.sampling.metrics.{MetricCollection,SlicedWasserstein,MarginalWasserstein} -> .sampling.metrics
@@ -42,6 +44,7 @@ _MIRROR = {
     "fdiff.utils.tensors": "fastfourierdiffusion_amd.utils.tensors",
     "fdiff.utils.wasserstein": "fastfourierdiffusion_amd.utils.wasserstein",
     "fdiff.sampling.metrics": "fastfourierdiffusion_amd.sampling.metrics",
+    "fdiff.visualization.spectral_interpretation": "fastfourierdiffusion_amd.visualization.spectral_interpretation",
 }
 
 
@@ -49,7 +52,7 @@ def install_as_fdiff(force: bool = False) -> None:
     """Register this package's modules under the reference's ``fdiff.*`` names."""
     if "fdiff" in sys.modules and not force and not getattr(sys.modules["fdiff"], "__ffd_amd__", False):
         raise RuntimeError("a different `fdiff` package is already imported; pass force=True to shadow it")
-    for pkg in ("fdiff", "fdiff.sampling", "fdiff.models", "fdiff.schedulers", "fdiff.utils"):
+    for pkg in ("fdiff", "fdiff.sampling", "fdiff.models", "fdiff.schedulers", "fdiff.utils", "fdiff.visualization"):
         m = types.ModuleType(pkg)
         m.__path__ = []  # mark as package
         m.__ffd_amd__ = True
@@ -59,7 +62,7 @@ def install_as_fdiff(force: bool = False) -> None:
         sys.modules[alias] = mod
         parent, _, leaf = alias.rpartition(".")
         setattr(sys.modules[parent], leaf, mod)
-    for sub in ("sampling", "models", "schedulers", "utils"):
+    for sub in ("sampling", "models", "schedulers", "utils", "visualization"):
         setattr(sys.modules["fdiff"], sub, sys.modules[f"fdiff.{sub}"])
 
 

@@ -63,6 +63,15 @@ SIGNATURES = {
     "ffd_freq_decompose": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, _P]),
     "ffd_hermite_predict": (C.c_int, [_P, C.POINTER(C.c_double), C.c_double, C.c_int, _P, C.c_int, C.c_size_t, _P]),
     "ffd_spectral_density": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_localization_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ffd_localization": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_smooth_frequency_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ffd_smooth_frequency": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_double, _P]),
+    "ffd_spectral_profile_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ffd_spectral_profile": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_localization_lds_max_len": (C.c_int, []),
+    "ffd_localization_bench": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F,
+                                         _P]),
     "ffd_w2_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]),
     "ffd_w2_sliced": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "ffd_w2_marginal": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

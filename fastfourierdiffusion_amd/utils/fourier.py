@@ -1,5 +1,5 @@
 """``fdiff.utils.fourier`` mirror: ``dft`` / ``idft`` (reference fourier.py:8-94), ``spectral_density``
-(:97-131) and the FreqCa helpers ``frequency_decompose_fft`` / ``_dct`` (:219-305) and ``predict_hermite``
+(:97-131), ``localization_metrics`` (:134-182), ``smooth_frequency`` (:185-216) and the FreqCa helpers ``frequency_decompose_fft`` / ``_dct`` (:219-305) and ``predict_hermite``
 (:397-497).
 
 Packed ortho real FFT along dim 1 of (B, L, C), computed by libffd's LDS-staged
@@ -93,6 +93,48 @@ def spectral_density(x: torch.Tensor, apply_dft: bool = True) -> torch.Tensor:
         xf = xd
     out = torch.empty((B, math.ceil((L + 1) / 2), Cn), device=xd.device, dtype=torch.float32)
     N.check(N.lib().ffd_spectral_density(xf.data_ptr(), out.data_ptr(), B, L, Cn, stream), None, "ffd_spectral_density")
+    return out.to(src_device) if src_device.type != "cuda" else out
+
+
+def _work(nbytes: int, device) -> torch.Tensor:
+    return torch.empty((max(int(nbytes), 8) + 7) // 8, dtype=torch.float64, device=device)  # 8-byte aligned scratch
+
+
+def localization_metrics(X: torch.Tensor):
+    """fourier.py:134-182: ``(X_loc, X_spec_loc)``, the delocalization of every sample of X (B, L, C) in the time and in
+    the frequency domain -- ``min_s sum_t p[t] cyc(t, s)^2`` of the normalized energy over time / over the mirrored
+    frequency axis, the products on the fp32 matrix cores (ffd_localization)."""
+    assert X.dim() == 3, f"expected (batch_size, max_len, n_channels), got {tuple(X.shape)}"
+    src_device = X.device
+    xd = _on_gpu(X, "localization_metrics")
+    B, L, Cn = xd.shape
+    loc = torch.empty((2, B), device=xd.device, dtype=torch.float32)
+    nbytes = N.lib().ffd_localization_work_bytes(B, L, Cn)
+    work = _work(nbytes, xd.device)
+    rc = N.lib().ffd_localization(xd.data_ptr(), loc[0].data_ptr(), loc[1].data_ptr(), work.data_ptr(), work.numel() * 8,
+                                  B, L, Cn, N.current_stream_ptr(xd.device))
+    N.check(rc, None, "ffd_localization")
+    if src_device.type != "cuda":
+        loc = loc.to(src_device)
+    return loc[0], loc[1]
+
+
+def smooth_frequency(X: torch.Tensor, sigma: float) -> torch.Tensor:
+    """fourier.py:185-216: ``idft`` of ``dft(X)`` contracted with the column-normalized Gaussian kernel of width sigma
+    over the packed frequency axis.  Like the reference, only odd ``max_len`` works: for even lengths its kernel has
+    ``max_len - 1`` rows and the einsum raises RuntimeError, and so does this."""
+    assert X.dim() == 3, f"expected (batch_size, max_len, n_channels), got {tuple(X.shape)}"
+    B, L, Cn = X.shape
+    if L % 2 == 0:
+        raise RuntimeError(f"smooth_frequency: the Gaussian kernel of an even max_len = {L} has {L - 1} rows "
+                           "(fourier.py:201-214); only odd lengths are defined")
+    src_device = X.device
+    xd = _on_gpu(X, "smooth_frequency")
+    out = torch.empty_like(xd)
+    work = _work(N.lib().ffd_smooth_frequency_work_bytes(B, L, Cn), xd.device)
+    rc = N.lib().ffd_smooth_frequency(xd.data_ptr(), out.data_ptr(), work.data_ptr(), work.numel() * 8, B, L, Cn,
+                                      float(sigma), N.current_stream_ptr(xd.device))
+    N.check(rc, None, "ffd_smooth_frequency")
     return out.to(src_device) if src_device.type != "cuda" else out
 
 

@@ -257,6 +257,50 @@ int ffd_hermite_predict(const float* history, const double* timesteps, double ta
  * callers with time-domain input run ffd_dft first (apply_dft=True). */
 int ffd_spectral_density(const float* xf, float* out, int B, int L, int C, void* stream);
 
+/* ---- localization metrics, frequency smoothing, spectral profiles (src/fdiff/utils/fourier.py:134-216,
+ * src/fdiff/visualization/spectral_interpretation.py:55-94) ----
+ * x: time-domain series, dense fp32 (B, L, C) on the device.  Context-free, stream ordered, no host synchronisation, no
+ * atomics; every reduction is a fixed-order fp64 tree (inside the matrix product: the fixed chain over t), so results
+ * are bit-identical from run to run and a sample's values do not depend on the other samples of the call.  `work`:
+ * device scratch of at least the matching *_work_bytes (0 for shapes the call refuses), 8-byte aligned.
+ * FFD_ERR_INVALID: a null pointer, B, L, C < 1, work_bytes too small (checked before any device work);
+ * FFD_ERR_UNSUPPORTED: L > 8192 (the FFT's limit), B > 2^24, C > 2^16. */
+
+/* localization_metrics (fourier.py:134-182): per sample the delocalization min_s sum_t p[t] cyc(t, s)^2,
+ * cyc(t, s) = min(|t - s|, L - |t - s|), of p = the energy over time normalized to 1 (deloc_time_out, B floats) and of
+ * p = the spectral density mirrored to the full length-L frequency axis (fourier.py:154-159) normalized to 1
+ * (deloc_freq_out, B floats).  The (B, L) x (L, L) products run on the fp32 matrix cores with cyc^2 (exact in fp32)
+ * made in registers; the minimum is taken in the epilogue.  An all-zero sample gives NaN (0 / 0) in both; L = 1 gives 0. */
+size_t ffd_localization_work_bytes(int B, int L, int C);
+int ffd_localization(const float* x, float* deloc_time_out, float* deloc_freq_out, void* work, size_t work_bytes, int B,
+                     int L, int C, void* stream);
+/* smooth_frequency (fourier.py:185-216): out = idft(dft(x) contracted over the packed axis with the column-normalized
+ * Gaussian kernel W[t, s] = exp(-((k_t - k_s) / sigma)^2 / 2) / sum_t (...), k = [0 .. (L-1)/2, 1 .. (L-1)/2]).  W is
+ * built once per call into `work`; the contraction runs on the fp32 matrix cores.  The reference's k has length L only
+ * for odd L (its einsum raises otherwise): even L, sigma <= 0 or non-finite, x == out are FFD_ERR_INVALID; L > 2047 is
+ * FFD_ERR_UNSUPPORTED.  L = 1 is the identity. */
+size_t ffd_smooth_frequency_work_bytes(int B, int L, int C);
+int ffd_smooth_frequency(const float* x, float* out, void* work, size_t work_bytes, int B, int L, int C, double sigma,
+                         void* stream);
+/* The curves of process_dataset (spectral_interpretation.py:55-94): with d[b, k] = sum_c |X_k|^2 over the L/2 + 1
+ * density bins and e[b, t] = sum_c x^2,
+ *   spec_mean[k]   = mean_b d / (EPS + sum_k d)     spec_se[k]    = std_b (d / sum_k d) / sqrt(B)      (L/2 + 1 floats each)
+ *   energy_mean[t] = mean_b e / (EPS + sum_t e)     energy_std[t] = std_b (e / sum_t e)                (L floats each)
+ * EPS = 1e-15, std unbiased (B = 1: NaN, like torch.std); the temporal "SE" column of the reference is the plain std.
+ * Two passes over fixed slabs of 1024 samples in fp64. */
+size_t ffd_spectral_profile_work_bytes(int B, int L, int C);
+int ffd_spectral_profile(const float* x, float* spec_mean, float* spec_se, float* energy_mean, float* energy_std,
+                         void* work, size_t work_bytes, int B, int L, int C, void* stream);
+/* The longest row (L) whose 32-row block the product kernel of ffd_localization keeps in LDS; above it the rows are
+ * read from L2 per centre tile (same results, a slower path).  Host only. */
+int ffd_localization_lds_max_len(void);
+/* Benchmark helper (replaces nothing in the reference; tools/spectral_bench.py): the stages of ffd_localization with HIP
+ * events between them, `warmup` untimed and `iters` timed runs.  x holds n_inputs consecutive (B, L, C) inputs, run i
+ * reads input i % n_inputs.  ms_out[3 i + 0..2] = mean, minimum, maximum milliseconds of stage i: the time-domain rows,
+ * dft + density + frequency rows, the two product launches.  Synchronous. */
+int ffd_localization_bench(const float* x, int n_inputs, float* deloc_time_out, float* deloc_freq_out, void* work,
+                           size_t work_bytes, int B, int L, int C, int warmup, int iters, float* ms_out, void* stream);
+
 /* ---- sample metrics: sliced / marginal Wasserstein-2 distances (src/fdiff/utils/wasserstein.py) ----
  * For one direction u the two sets are projected (fp32, exact-fp32 MFMA), each projection is sorted, and
  *   W2^2 = integral over t in [0,1] of (a[floor(t n)] - b[floor(t m)])^2
