@@ -7,7 +7,8 @@
 // they come, e.g. 187 = 11 * 17, 251 = 251) and each pass evaluates its radix-R
 // butterflies output-by-output straight from one length-L twiddle table
 //     w_R^{jk} = W_L[(jk mod R) L/R]      w_n^{pk} = W_L[p k s]      (n s = L)
-// computed on the host in double precision.
+// computed on the host in double precision.  A butterfly of more than CHAIN_MAX_RADIX terms is a compensated sum.
+// Lengths: fft_len_supported (ffd_internal.h) -- a power of two up to 8192, any other L up to 6826 (the LDS image).
 //
 // Packed layout (fourier.py:24-47): out[0 .. L/2] = Re X_k, out[L/2+1 ..] = Im X_k for
 // k = 1 .. ceil(L/2)-1; scale 1/sqrt(L) both ways.
@@ -35,6 +36,20 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
+// A radix-R butterfly output is a sum of R products.  Up to CHAIN_MAX_RADIX terms it is one plain fp32 chain (the
+// radices of the dataset lengths, 187 = 11 * 17, 365 = 5 * 73, 251, 509, stay on it: its rounding error there is at most
+// ~6e-7 of the output's max-norm).  The error of a plain chain is a random walk over its R roundings and passes the
+// 2e-6 operator bound near R = 2000, so a longer chain carries the rounding error of every addition along
+// (Kahan's compensated sum, each operation rounded on its own): its error no longer grows with R.
+constexpr int CHAIN_MAX_RADIX = 512;
+
+__device__ __forceinline__ void compensated_add(float& sum, float& lost, float term) {
+  const float y = __fsub_rn(term, lost);
+  const float t = __fadd_rn(sum, y);
+  lost = __fsub_rn(__fsub_rn(t, sum), y);
+  sum = t;
+}
+
 // All Stockham passes of a length-L complex FFT over cg channels (channel-innermost LDS image
 // of stride CG); returns the buffer holding the result.  W holds the (possibly conjugated) twiddles.
 __device__ __forceinline__ float2* stockham(float2* x, float2* y, const float2* W, const FftPlan& plan, int L, int CG,
@@ -54,13 +69,25 @@ __device__ __forceinline__ float2* stockham(float2* x, float2* y, const float2* 
       const int stride = s * m * CG;
       float2 acc = xp[0];
       int tw = 0;  // (j*k mod R) * L/R
-      for (int j = 1; j < R; ++j) {
-        tw += k * LR;
-        if (tw >= L) tw -= L;
-        float2 a = xp[(size_t)j * stride];
-        float2 w = W[tw];
-        acc.x = fmaf(a.x, w.x, fmaf(-a.y, w.y, acc.x));
-        acc.y = fmaf(a.x, w.y, fmaf(a.y, w.x, acc.y));
+      if (R <= CHAIN_MAX_RADIX) {
+        for (int j = 1; j < R; ++j) {
+          tw += k * LR;
+          if (tw >= L) tw -= L;
+          float2 a = xp[(size_t)j * stride];
+          float2 w = W[tw];
+          acc.x = fmaf(a.x, w.x, fmaf(-a.y, w.y, acc.x));
+          acc.y = fmaf(a.x, w.y, fmaf(a.y, w.x, acc.y));
+        }
+      } else {
+        float2 lost = make_float2(0.f, 0.f);  // what the additions so far rounded away
+        for (int j = 1; j < R; ++j) {
+          tw += k * LR;
+          if (tw >= L) tw -= L;
+          float2 a = xp[(size_t)j * stride];
+          float2 w = W[tw];
+          compensated_add(acc.x, lost.x, fmaf(a.x, w.x, -__fmul_rn(a.y, w.y)));
+          compensated_add(acc.y, lost.y, fmaf(a.x, w.y, __fmul_rn(a.y, w.x)));
+        }
       }
       acc = cmul(acc, W[p * k * s]);
       y[(size_t)i * CG + cc] = acc;
@@ -722,16 +749,15 @@ __global__ __launch_bounds__(256) void k_fresca_apply_pow2(const float* __restri
   }
 }
 
-static bool is_pow2(int L) { return L >= 2 && (L & (L - 1)) == 0; }
+static bool is_pow2(int L) { return fft_len_is_pow2(L); }
 
 static Pow2Plan make_pow2_plan(int N) { return pow2_plan(N); }
 
 // channels per workgroup and LDS bytes of the power-of-two path: the whole slab when it fits
 // (<= 64 KiB keeps several workgroups on a CU; up to the CU's 160 KiB before the channels are split)
-static size_t pow2_lds(int L, int CG) { return (size_t)(L + (size_t)L * CG) * sizeof(float2); }
+static size_t pow2_lds(int L, int CG) { return fft_lds_bytes(L, CG); }
 static int pow2_cg(int L, int C) {
-  const size_t cap = 160 * 1024;
-  if (pow2_lds(L, C) <= cap) return C;
+  if (pow2_lds(L, C) <= FFT_LDS_CAP) return C;
   int CG = C;
   while (CG > 1 && pow2_lds(L, CG) > 64 * 1024) CG = (CG + 1) / 2;
   return CG;
@@ -743,7 +769,7 @@ static int ceil_log2(int v) {
 }
 // persistent grid: as many workgroups as the LDS image lets a CU hold (at most 8), times the CU count
 static int persistent_blocks(int B, size_t lds) {
-  int per_cu = (int)((160 * 1024) / lds);
+  int per_cu = (int)(FFT_LDS_CAP / lds);
   per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
   const int cap = 256 * per_cu;
   return B < cap ? B : cap;
@@ -810,7 +836,7 @@ static hipError_t get_twiddles(int L, const float2** out) {
 static hipError_t launch_dft(const float* in, float* out, int B, int L, int C, int inverse, const float* a0, const float* a1,
                              hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  if (L < 1 || C < 1 || L > 8192) return hipErrorInvalidValue;
+  if (C < 1 || !fft_len_supported(L)) return hipErrorInvalidValue;
   if ((a0 == nullptr) != (a1 == nullptr)) return hipErrorInvalidValue;
   const float2* W = nullptr;
   hipError_t e = get_twiddles(L, &W);
@@ -820,7 +846,7 @@ static hipError_t launch_dft(const float* in, float* out, int B, int L, int C, i
     const Pow2Plan plan = make_pow2_plan(L / 2);
     const int CG = pow2_cg(L, C);
     const size_t lds = pow2_lds(L, CG);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > FFT_LDS_CAP) return hipErrorInvalidValue;
     const int lc = ceil_log2(CG);
     const bool vec = CG == C && C % 4 == 0 && aligned16(in) && aligned16(out) && aligned16(a0) && aligned16(a1);
     dim3 grid(persistent_blocks(B, lds), cdiv(C, CG)), block(256);
@@ -841,11 +867,11 @@ static hipError_t launch_dft(const float* in, float* out, int B, int L, int C, i
   }
   FftPlan plan = make_plan(L);
   if (plan.npass > 16) return hipErrorInvalidValue;
-  // channels per workgroup so that twiddles + two slabs fit in 64 KiB of LDS
+  // channels per workgroup so that twiddles + two slabs fit in 64 KiB of LDS (one channel: up to the CU's 160 KiB)
   int CG = C;
-  while (CG > 1 && (size_t)(L + 2 * (size_t)L * CG) * sizeof(float2) > 64 * 1024) CG = (CG + 1) / 2;
-  size_t lds = (size_t)(L + 2 * (size_t)L * CG) * sizeof(float2);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  while (CG > 1 && fft_lds_bytes(L, CG) > 64 * 1024) CG = (CG + 1) / 2;
+  size_t lds = fft_lds_bytes(L, CG);
+  if (lds > FFT_LDS_CAP) return hipErrorInvalidValue;
   dim3 grid(B, cdiv(C, CG)), block(256);
   if (inverse) {
     if ((e = allow_lds(k_fft<true>, lds)) != hipSuccess) return e;
@@ -875,12 +901,12 @@ static hipError_t slab_geom(int L, int C, SlabGeom* g) {
   } else {
     g->plan = make_plan(L);
     int CG = C;
-    while (CG > 1 && (size_t)(L + 2 * (size_t)L * CG) * sizeof(float2) > 64 * 1024) CG = (CG + 1) / 2;
+    while (CG > 1 && fft_lds_bytes(L, CG) > 64 * 1024) CG = (CG + 1) / 2;
     g->CG = CG;
-    g->lds = (size_t)(L + 2 * (size_t)L * CG) * sizeof(float2);
+    g->lds = fft_lds_bytes(L, CG);
     g->lc = 0;
   }
-  return g->lds > 160 * 1024 ? hipErrorInvalidValue : hipSuccess;
+  return g->lds > FFT_LDS_CAP ? hipErrorInvalidValue : hipSuccess;
 }
 
 static hipError_t launch_fresca_apply(const float* in, float* out, const float2* W, const SlabGeom& g, int B, int L, int C,
@@ -914,12 +940,12 @@ static hipError_t launch_fresca_apply(const float* in, float* out, const float2*
 hipError_t launch_fresca(const float* in, float* out, float* work, int B, int L, int C, float low, float high,
                          double cutoff_ratio, int strategy, hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  if (L < 2 || C < 1 || L > 4096) return hipErrorInvalidValue;
-  const float2* W = nullptr;
-  hipError_t e = get_twiddles(L, &W);
-  if (e != hipSuccess) return e;
+  if (L < 2 || C < 1 || !fft_len_supported(L, FFT_MAX_FILTER_LEN)) return hipErrorInvalidValue;
   SlabGeom g;
-  if ((e = slab_geom(L, C, &g)) != hipSuccess) return e;
+  hipError_t e = slab_geom(L, C, &g);
+  if (e != hipSuccess) return e;
+  const float2* W = nullptr;
+  if ((e = get_twiddles(L, &W)) != hipSuccess) return e;
   const int NGc = cdiv(C, g.CG);
   const int nf = L / 2 + 1;
   const float sc = (float)(1.0 / sqrt((double)L));
@@ -964,12 +990,12 @@ hipError_t launch_fresca(const float* in, float* out, float* work, int B, int L,
 static hipError_t launch_freq_decompose(const float* in, float* low, float* high, int B, int L, int D, double low_freq_ratio,
                                         hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  if (L < 2 || D < 1 || L > 4096) return hipErrorInvalidValue;
-  const float2* W = nullptr;
-  hipError_t e = get_twiddles(L, &W);
-  if (e != hipSuccess) return e;
+  if (L < 2 || D < 1 || !fft_len_supported(L, FFT_MAX_FILTER_LEN)) return hipErrorInvalidValue;
   SlabGeom g;
-  if ((e = slab_geom(L, D, &g)) != hipSuccess) return e;
+  hipError_t e = slab_geom(L, D, &g);
+  if (e != hipSuccess) return e;
+  const float2* W = nullptr;
+  if ((e = get_twiddles(L, &W)) != hipSuccess) return e;
   const int nf = L / 2 + 1;
   int n_low = (int)((double)nf * low_freq_ratio);  // fourier.py:249  max(1, int(n_freq * ratio))
   if (n_low < 1) n_low = 1;
@@ -1193,12 +1219,14 @@ extern "C" {
 
 int ffd_dft(const float* in, float* out, int B, int L, int C, void* stream) {
   if (!in || !out || in == out || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  if (!fft_len_supported(L)) return FFD_ERR_UNSUPPORTED;
   hipError_t e = launch_dft(in, out, B, L, C, 0, nullptr, nullptr, (hipStream_t)stream);
   return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
 }
 
 int ffd_idft(const float* in, float* out, int B, int L, int C, void* stream) {
   if (!in || !out || in == out || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  if (!fft_len_supported(L)) return FFD_ERR_UNSUPPORTED;
   hipError_t e = launch_dft(in, out, B, L, C, 1, nullptr, nullptr, (hipStream_t)stream);
   return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
 }
@@ -1206,6 +1234,7 @@ int ffd_idft(const float* in, float* out, int B, int L, int C, void* stream) {
 int ffd_dft_standardize(const float* in, float* out, const float* mean, const float* std, int B, int L, int C,
                         void* stream) {
   if (!in || !out || in == out || !mean || !std || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  if (!fft_len_supported(L)) return FFD_ERR_UNSUPPORTED;
   hipError_t e = launch_dft(in, out, B, L, C, 0, mean, std, (hipStream_t)stream);
   return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
 }
@@ -1213,6 +1242,7 @@ int ffd_dft_standardize(const float* in, float* out, const float* mean, const fl
 int ffd_unstandardize_idft(const float* in, float* out, const float* mean, const float* std, int B, int L, int C,
                            void* stream) {
   if (!in || !out || in == out || !mean || !std || B < 0 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  if (!fft_len_supported(L)) return FFD_ERR_UNSUPPORTED;
   hipError_t e = launch_dft(in, out, B, L, C, 1, std, mean, (hipStream_t)stream);
   return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
 }
@@ -1222,6 +1252,7 @@ int ffd_fresca(const float* in, float* out, float* work, int B, int L, int C, fl
   if (!in || !out || in == out || B < 1 || L < 2 || C < 1) return FFD_ERR_INVALID;
   if (strategy != FFD_FRESCA_SPATIAL && strategy != FFD_FRESCA_ENERGY) return FFD_ERR_INVALID;  // fresca.py:60 ValueError
   if (strategy == FFD_FRESCA_ENERGY && !work) return FFD_ERR_INVALID;
+  if (!fft_len_supported(L, FFT_MAX_FILTER_LEN)) return FFD_ERR_UNSUPPORTED;
   hipError_t e = launch_fresca(in, out, work, B, L, C, low_scale, high_scale, cutoff_ratio, strategy, (hipStream_t)stream);
   return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
 }
@@ -1238,6 +1269,7 @@ int ffd_fresca2d(const float* in, float* out, float* work, int B, int H, int W, 
 int ffd_freq_decompose(const float* x, float* low, float* high, int B, int L, int D, double low_freq_ratio,
                        void* stream) {
   if (!x || !low || !high || x == low || x == high || low == high || B < 1 || L < 2 || D < 1) return FFD_ERR_INVALID;
+  if (!fft_len_supported(L, FFT_MAX_FILTER_LEN)) return FFD_ERR_UNSUPPORTED;
   hipError_t e = launch_freq_decompose(x, low, high, B, L, D, low_freq_ratio, (hipStream_t)stream);
   return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
 }

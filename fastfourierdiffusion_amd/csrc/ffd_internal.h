@@ -375,6 +375,28 @@ hipError_t launch_pack_lstm_wave(const float* wih, const float* whh, const float
 
 hipError_t launch_dense(const float* X, const float* W, const float* b, const float* b2, const float* R, float* Y,
                         int M, int N, int K, int relu, hipStream_t s);
+// ---- lengths of the LDS-resident transforms (ffd_fft.hip): the one statement of the limits, repeated in ffd.h ----
+// A workgroup keeps the length-L twiddle table and two complex slabs of CG >= 1 channels in at most 160 KiB of LDS:
+// (L + L CG) float2 for a power of two (a half-length complex transform), (L + 2 L CG) float2 for any other length.
+// So every power of two up to FFT_MAX_LEN = 8192 is taken, and any other length up to FFT_MAX_MIXED_LEN = 6826
+// (3 * 6826 float2 = 163 824 B; 6827 needs 163 848 B).  FreSca and the decomposition stop at FFT_MAX_FILTER_LEN.
+// Every entry point that transforms asks fft_len_supported before its first device call.
+constexpr int FFT_MAX_LEN = 8192, FFT_MAX_FILTER_LEN = 4096;
+constexpr size_t FFT_LDS_CAP = 160 * 1024;
+constexpr bool fft_len_is_pow2(int L) { return L >= 2 && (L & (L - 1)) == 0; }
+constexpr size_t fft_lds_bytes(int L, int CG) {  // twiddles + two slabs of CG channels
+  return (size_t)L * (fft_len_is_pow2(L) ? 1 + (size_t)CG : 1 + 2 * (size_t)CG) * 8;
+}
+constexpr bool fft_len_supported(int L, int max_len = FFT_MAX_LEN) {
+  return L >= 1 && L <= max_len && fft_lds_bytes(L, 1) <= FFT_LDS_CAP;
+}
+constexpr int fft_max_mixed_len() {  // the longest supported length that is not a power of two
+  int L = FFT_MAX_LEN;
+  while (fft_len_is_pow2(L) || !fft_len_supported(L)) --L;
+  return L;
+}
+constexpr int FFT_MAX_MIXED_LEN = fft_max_mixed_len();
+static_assert(FFT_MAX_MIXED_LEN == 6826, "ffd.h states this length");
 // FreSca spectral scaling of a (B,L,C) score; work: B*(L/2+1) + 1 floats; strategy 0 spatial, 1 energy
 hipError_t launch_fresca(const float* in, float* out, float* work, int B, int L, int C, float low, float high,
                          double cutoff_ratio, int strategy, hipStream_t s);

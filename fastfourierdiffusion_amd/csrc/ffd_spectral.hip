@@ -76,7 +76,11 @@ __device__ __forceinline__ float min_nan(float v, float m) { return (v < m || v 
 // stride ld, zero beyond L and beyond R) and every centre tile re-reads it from there; otherwise (rows too long for
 // LDS) the A values come straight from HBM / L2.  t past L multiplies a zero; a centre past L is never taken into the
 // minimum; rows past R are computed on zeros (LDS) or on a clamped row and never stored.
-constexpr int DL_ROWS = 32;
+// The moment is a sum of L non-negative terms; in one fp32 accumulator chain its rounding error grows like sqrt(L) and
+// reaches 2e-6 .. 5e-6 of the value at L = 6823 .. 8192 (measured), past the 2e-6 the time-domain value is held to.
+// So the chain restarts every DL_SEG positions and the segment sums are added up: ~DL_SEG / sqrt(3 L) + sqrt(L / (3
+// DL_SEG)) roundings' worth, below 3e-7 at every supported length.  L <= DL_SEG: one segment, the same bits as one chain.
+constexpr int DL_ROWS = 32, DL_SEG = 256;
 
 template <bool LDSA>
 __global__ __launch_bounds__(256) void k_deloc(const float* __restrict__ P, float* __restrict__ out, int R, int L, int ld) {
@@ -105,21 +109,27 @@ __global__ __launch_bounds__(256) void k_deloc(const float* __restrict__ P, floa
   for (int st = wave; st < nst; st += 4) {
     const int s = st * 16 + c;
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    for (int t0 = 0; t0 < L; t0 += 4) {
-      const int t = t0 + q;
-      const int d = abs(t - s);
-      const int cy = min(d, L - d);
-      const float bv = (float)(cy * cy);
-      float a0, a1;
-      if (LDSA) {
-        a0 = l0[t];
-        a1 = l1[t];
-      } else {
-        a0 = t < L ? g0[t] : 0.f;
-        a1 = t < L ? g1[t] : 0.f;
+    for (int tb = 0; tb < L; tb += DL_SEG) {  // one accumulator chain per DL_SEG positions, the segments added in order
+      f32x4 seg0 = {0.f, 0.f, 0.f, 0.f}, seg1 = {0.f, 0.f, 0.f, 0.f};
+      const int te = min(tb + DL_SEG, L);
+      for (int t0 = tb; t0 < te; t0 += 4) {
+        const int t = t0 + q;
+        const int d = abs(t - s);
+        const int cy = min(d, L - d);
+        const float bv = (float)(cy * cy);
+        float a0, a1;
+        if (LDSA) {
+          a0 = l0[t];
+          a1 = l1[t];
+        } else {
+          a0 = t < L ? g0[t] : 0.f;
+          a1 = t < L ? g1[t] : 0.f;
+        }
+        seg0 = mfma16(a0, bv, seg0);
+        seg1 = mfma16(a1, bv, seg1);
       }
-      acc0 = mfma16(a0, bv, acc0);
-      acc1 = mfma16(a1, bv, acc1);
+      acc0 += seg0;
+      acc1 += seg1;
     }
     if (s < L) {  // D[i = 4 q + r][j = c]: row 16 a + 4 q + r, centre s
 #pragma unroll
@@ -307,13 +317,14 @@ using namespace ffd;
 
 extern "C" {
 
-// Limits: L <= 8192 (the FFT's own; cyc^2 < 2^24 is exact in fp32), smoothing L <= 2047 (the L x L kernel),
-// B <= 2^24 samples, C <= 2^16 channels per call (FFD_ERR_UNSUPPORTED past them).
-static const int SP_MAX_L = 8192, SP_MAX_SMOOTH_L = 2047, SP_MAX_B = 1 << 24, SP_MAX_C = 1 << 16;
+// Limits: the FFT's own lengths (fft_len_supported: powers of two up to 8192, any other L up to 6826; cyc^2 < 2^24 is
+// exact in fp32 for all of them), smoothing L <= 2047 (the L x L kernel), B <= 2^24 samples, C <= 2^16 channels per
+// call (FFD_ERR_UNSUPPORTED past them, before any device call; the matching *_work_bytes is then 0).
+static const int SP_MAX_L = FFT_MAX_LEN, SP_MAX_SMOOTH_L = 2047, SP_MAX_B = 1 << 24, SP_MAX_C = 1 << 16;
 
-static int sp_check(int B, int L, int C) {
+static int sp_check(int B, int L, int C, int max_len = SP_MAX_L) {
   if (B < 1 || L < 1 || C < 1) return FFD_ERR_INVALID;
-  if (L > SP_MAX_L || B > SP_MAX_B || C > SP_MAX_C) return FFD_ERR_UNSUPPORTED;
+  if (!fft_len_supported(L, max_len) || B > SP_MAX_B || C > SP_MAX_C) return FFD_ERR_UNSUPPORTED;
   return FFD_OK;
 }
 
@@ -368,7 +379,7 @@ int ffd_localization_lds_max_len(void) {
 }
 
 size_t ffd_smooth_frequency_work_bytes(int B, int L, int C) {
-  if (sp_check(B, L, C) != FFD_OK || L > SP_MAX_SMOOTH_L) return 0;
+  if (sp_check(B, L, C, SP_MAX_SMOOTH_L) != FFD_OK || L % 2 == 0 || (long long)B * C > (1LL << 30)) return 0;
   return ((size_t)L * L + (size_t)B * L * C) * sizeof(float);
 }
 
@@ -377,13 +388,12 @@ int ffd_smooth_frequency(const float* x, float* out, void* work, size_t work_byt
   if (!x || !out || !work || x == out) return FFD_ERR_INVALID;
   if (B < 1 || L < 1 || C < 1 || L % 2 == 0) return FFD_ERR_INVALID;  // even L: the reference's einsum raises
   if (!(sigma > 0.0) || !std::isfinite(sigma) || !((float)sigma > 0.f) || !std::isfinite((float)sigma)) return FFD_ERR_INVALID;
-  if (L > SP_MAX_SMOOTH_L || B > SP_MAX_B || C > SP_MAX_C) return FFD_ERR_UNSUPPORTED;
+  const long long N = (long long)B * C;
+  if (sp_check(B, L, C, SP_MAX_SMOOTH_L) != FFD_OK || N > (1LL << 30)) return FFD_ERR_UNSUPPORTED;
   if (work_bytes < ffd_smooth_frequency_work_bytes(B, L, C)) return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   float* W = (float*)work;
   float* y = W + (size_t)L * L;
-  const long long N = (long long)B * C;
-  if (N > (1LL << 30)) return FFD_ERR_UNSUPPORTED;
   if (int rc = ffd_dft(x, out, B, L, C, stream)) return rc;  // the spectrum waits in `out`
   hipLaunchKernelGGL(k_smooth_kernel, dim3(L), dim3(256), 0, s, W, L, (float)sigma);
   hipLaunchKernelGGL(k_smooth_mm, dim3(cdiv((int)N, 16)), dim3(256), 0, s, out, W, y, (int)N, L, C);

@@ -182,8 +182,21 @@ int ffd_sde_step(const ffd_sde_desc* sde, float* x, const float* score, const fl
 int ffd_prior(const ffd_sde_desc* sde, float* x, const float* z, const float* G, uint64_t seed,
               uint64_t sample_offset, int B, int L, int C, void* stream);
 
+/* ---- Supported transform lengths ----
+ * Every Fourier entry point keeps a sample's slab and the twiddle table in one workgroup's 160 KiB of LDS, which
+ * sets the lengths it takes:
+ *   ffd_dft, ffd_idft, ffd_dft_standardize, ffd_unstandardize_idft,
+ *   ffd_localization (and _bench), ffd_spectral_profile:  L a power of two up to 8192, or any other L up to 6826
+ *                                                         (6827 .. 8191 do not fit next to their twiddle table);
+ *   ffd_fresca, ffd_freq_decompose:                       the same set up to L = 4096, L >= 2;
+ *   ffd_smooth_frequency:                                 odd L up to 2047 (its L x L kernel).
+ * Any number of channels: they are split over workgroups down to one channel each.  A length outside its set is
+ * FFD_ERR_UNSUPPORTED, returned before any device call (no allocation, no launch), after the FFD_ERR_INVALID
+ * argument checks; the matching *_work_bytes is 0 for exactly the shapes the call refuses. */
+
 /* fdiff.utils.fourier.dft / idft (fourier.py:8-52, 55-94): packed ortho rFFT and
- * its inverse along dim 1 of (B,L,C).  `in` and `out` may not alias. Context-free. */
+ * its inverse along dim 1 of (B,L,C).  `in` and `out` may not alias. Context-free.
+ * L: see "Supported transform lengths". */
 int ffd_dft(const float* in, float* out, int B, int L, int C, void* stream);
 int ffd_idft(const float* in, float* out, int B, int L, int C, void* stream);
 /* The runner-side wrappers around them, fused into the same kernel (no extra pass over the data):
@@ -211,7 +224,8 @@ int ffd_time_encoding(const float* x, const float* timesteps, const float* W, co
  * strategy 0 "spatial": Rc = cutoff_ratio * (L/2+1); 1 "energy": Rc = first k whose cumulative
  * batch-mean |X_k| reaches cutoff_ratio * total (fresca.py:46-58; a batch-wide statistic, reduced
  * on the device in a fixed order -- no host sync).  `work` = B*C*(L/2+1) + 4 floats of scratch.
- * Context-free; in != out.  low == high == 1 is the caller's early exit (fresca.py:137-138). */
+ * Context-free; in != out.  low == high == 1 is the caller's early exit (fresca.py:137-138).
+ * 2 <= L <= 4096 within the supported transform lengths, else FFD_ERR_UNSUPPORTED. */
 enum { FFD_FRESCA_SPATIAL = 0, FFD_FRESCA_ENERGY = 1 };
 int ffd_fresca(const float* in, float* out, float* work, int B, int L, int C, float low_scale, float high_scale,
                double cutoff_ratio, int strategy, void* stream);
@@ -242,7 +256,7 @@ int ffd_fresca_disable(ffd_ctx* ctx);
 /* frequency_decompose_fft / frequency_decompose_dct (fourier.py:219-286; the dct variant returns the
  * fft result, fourier.py:303): low = irfft(rfft(x)[k < n_low]), high = irfft(rfft(x)[k >= n_low]) along
  * dim 1 of x (B, L, D), n_low = max(1, int((L/2+1) * low_freq_ratio)), ortho norm.  low/high must not
- * alias x. */
+ * alias x.  2 <= L <= 4096 within the supported transform lengths, else FFD_ERR_UNSUPPORTED. */
 int ffd_freq_decompose(const float* x, float* low, float* high, int B, int L, int D, double low_freq_ratio,
                        void* stream);
 
@@ -264,7 +278,8 @@ int ffd_spectral_density(const float* xf, float* out, int B, int L, int C, void*
  * are bit-identical from run to run and a sample's values do not depend on the other samples of the call.  `work`:
  * device scratch of at least the matching *_work_bytes (0 for shapes the call refuses), 8-byte aligned.
  * FFD_ERR_INVALID: a null pointer, B, L, C < 1, work_bytes too small (checked before any device work);
- * FFD_ERR_UNSUPPORTED: L > 8192 (the FFT's limit), B > 2^24, C > 2^16. */
+ * FFD_ERR_UNSUPPORTED: L outside the supported transform lengths (L > 8192, or 6826 < L < 8192), B > 2^24, C > 2^16;
+ * also checked before any device work. */
 
 /* localization_metrics (fourier.py:134-182): per sample the delocalization min_s sum_t p[t] cyc(t, s)^2,
  * cyc(t, s) = min(|t - s|, L - |t - s|), of p = the energy over time normalized to 1 (deloc_time_out, B floats) and of
@@ -278,7 +293,7 @@ int ffd_localization(const float* x, float* deloc_time_out, float* deloc_freq_ou
  * Gaussian kernel W[t, s] = exp(-((k_t - k_s) / sigma)^2 / 2) / sum_t (...), k = [0 .. (L-1)/2, 1 .. (L-1)/2]).  W is
  * built once per call into `work`; the contraction runs on the fp32 matrix cores.  The reference's k has length L only
  * for odd L (its einsum raises otherwise): even L, sigma <= 0 or non-finite, x == out are FFD_ERR_INVALID; L > 2047 is
- * FFD_ERR_UNSUPPORTED.  L = 1 is the identity. */
+ * FFD_ERR_UNSUPPORTED (work_bytes: 0 for both).  L = 1 is the identity. */
 size_t ffd_smooth_frequency_work_bytes(int B, int L, int C);
 int ffd_smooth_frequency(const float* x, float* out, void* work, size_t work_bytes, int B, int L, int C, double sigma,
                          void* stream);

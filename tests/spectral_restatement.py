@@ -35,21 +35,21 @@ def mirrored_density_rows(x):
     return np.concatenate([d, tail[:, ::-1]], axis=1)
 
 
-def cyclic_sq(L):
+def cyclic_sq_row(L):
+    """cyc(t, 0)^2 = min(t, L - t)^2; the column of centre s is this row rolled by s (no L x L matrix: L goes to 8192)."""
     t = np.arange(L, dtype=np.float64)
-    d = np.abs(t[:, None] - t[None, :])
-    return np.minimum(d, L - d) ** 2
+    return np.minimum(t, L - t) ** 2
 
 
 def localization(x):
     """fourier.py:134-182 -> (time delocalization (B), frequency delocalization (B)); 0 / 0 = NaN for a zero sample."""
     L = np.asarray(x).shape[1]
-    cyc2 = cyclic_sq(L)
+    cyc0 = cyclic_sq_row(L)
     out = []
     with np.errstate(invalid="ignore", divide="ignore"):
         for rows in (energy_rows(x), mirrored_density_rows(x)):
             p = rows / rows.sum(axis=1, keepdims=True)
-            moments = np.stack([(p * cyc2[:, s][None, :]).sum(axis=1) for s in range(L)], axis=1)  # (B, L)
+            moments = np.stack([(p * np.roll(cyc0, s)[None, :]).sum(axis=1) for s in range(L)], axis=1)  # (B, L)
             nan = np.isnan(moments).any(axis=1)
             m = np.where(nan, np.nan, np.nanmin(np.where(np.isnan(moments), np.inf, moments), axis=1))
             out.append(m)
