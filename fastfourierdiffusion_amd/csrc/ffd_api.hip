@@ -106,6 +106,8 @@ struct ffd_ctx {
   ffd_fresca_cfg fcfg{};
   Grow<float> score2, fwork;
   Grow<float> sm_noisy;  // the perturbed batch of ffd_sm_eval_batch
+  Grow<float> ode_xp, ode_d1;  // Heun's predicted state and predictor drift (ffd_sample_batch_ode)
+  int tail_solver = FFD_SOLVER_EULER_MARUYAMA;  // the loop entry that ran last (ffd_kernel_work names its FFD_K_SDE tail)
   // cache
   bool cache_enabled = false;
   ffd_cache_cfg ccfg{5, 10};
@@ -1115,6 +1117,65 @@ static bool tail_fusable(const ffd_ctx* ctx) {
   return g_fuse_tail && !ctx->fresca_on && m.kind != FFD_MODEL_MLP && unembed_sde_supported(m.n_channels, m.d_model);
 }
 
+// The steps the two loop entries share.
+// FreSca needs two more score-sized buffers.
+static int ensure_fresca_work(ffd_ctx* ctx, int B) {
+  const ffd_model_desc& m = ctx->desc;
+  if (!ctx->fresca_on) return FFD_OK;
+  if (int rc = ensure(ctx, ctx->score2, (size_t)B * m.max_len * m.n_channels)) return rc;
+  return ensure(ctx, ctx->fwork, (size_t)B * m.n_channels * (m.max_len / 2 + 1) + 4);
+}
+
+// All time embeddings of the trajectory in one launch: t is shared by the batch
+// (sampler.py:59-60).  The table is kept across batches and only rebuilt (with one
+// stream sync) when the timestep grid or the weights changed.
+static int ensure_time_table(ffd_ctx* ctx, const float* timesteps, int n_steps, hipStream_t s) {
+  const int d = ctx->desc.d_model;
+  if ((int)ctx->ts_host.size() == n_steps && memcmp(ctx->ts_host.data(), timesteps, sizeof(float) * n_steps) == 0 &&
+      ctx->temb_epoch == ctx->weight_epoch)
+    return FFD_OK;
+  HIPCHECK(hipStreamSynchronize(s));
+  if (int rc = ensure(ctx, ctx->temb_tab, (size_t)n_steps * d)) return rc;
+  if (int rc = ensure(ctx, ctx->ts_dev, (size_t)n_steps)) return rc;
+  ctx->ts_host.assign(timesteps, timesteps + n_steps);
+  HIPCHECK(hipMemcpy(ctx->ts_dev.p, ctx->ts_host.data(), sizeof(float) * n_steps, hipMemcpyHostToDevice));
+  if (int rc = time_embed(ctx, ctx->ts_dev.p, 0.f, n_steps, ctx->temb_tab.p, s)) return rc;
+  ctx->temb_epoch = ctx->weight_epoch;
+  return FFD_OK;
+}
+
+// cache.update_crf(crf) with current_step == global step (sampler.py:70-73): where the CRF of the evaluation at global
+// step gstep goes (*dst), and a second destination (*copy) when both captures want it; rest = the evaluations of this
+// call that still follow
+static void crf_capture_targets(const ffd_ctx* ctx, int gstep, int rest, float** dst, float** copy) {
+  const ffd_model_desc& m = ctx->desc;
+  const ffd_crf_capture_cfg& cc = ctx->crf_cap;
+  const size_t crf_n = (size_t)m.num_layers * m.max_len * m.d_model;
+  *dst = *copy = nullptr;
+  if (cc.ring && gstep % cc.every == 0) *dst = cc.ring + (size_t)((gstep / cc.every) % cc.n_slots) * crf_n;
+  if (cc.last && gstep % cc.last_every == 0) {
+    const int to_next = cc.last_every - (gstep % cc.last_every);  // is there a later qualifying step in this call?
+    if (to_next > rest) {
+      if (*dst) *copy = cc.last; else *dst = cc.last;
+    }
+  }
+}
+
+// FreSca on ctx->score at time t (sampler.py:79-93 -> fresca.py:220-268): *score = the buffer that holds the result
+static int fresca_score(ffd_ctx* ctx, double t, int B, hipStream_t s, const float** score) {
+  const ffd_model_desc& m = ctx->desc;
+  const ffd_fresca_cfg& f = ctx->fcfg;
+  *score = ctx->score.p;
+  double h = (double)f.high_scale;
+  if (f.num_steps > 0 && h > 1.0) h = (1.0 - t / (double)f.num_steps) * (h - 1.0) + 1.0;
+  if (!((double)f.low_scale == 1.0 && h == 1.0)) {  // fresca.py:137-138 early exit
+    HIPCHECK(launch_fresca(ctx->score.p, ctx->score2.p, ctx->fwork.p, B, m.max_len, m.n_channels, f.low_scale, (float)h,
+                           f.cutoff_ratio, f.strategy, s));
+    *score = ctx->score2.p;
+  }
+  return FFD_OK;
+}
+
 int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
                      int first_step, int n_run, uint64_t seed, uint64_t sample_offset, const float* z_inject,
                      int use_cache, int global_step0, void* stream) {
@@ -1133,23 +1194,9 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
   const ffd_model_desc& m = ctx->desc;
   const int d = m.d_model;
   hipStream_t s = (hipStream_t)stream;
-  if (ctx->fresca_on) {
-    if ((rc = ensure(ctx, ctx->score2, (size_t)B * m.max_len * m.n_channels))) return rc;
-    if ((rc = ensure(ctx, ctx->fwork, (size_t)B * m.n_channels * (m.max_len / 2 + 1) + 4))) return rc;
-  }
-  // All time embeddings of the trajectory in one launch: t is shared by the batch
-  // (sampler.py:59-60).  The table is kept across batches and only rebuilt (with one
-  // stream sync) when the timestep grid or the weights changed.
-  if ((int)ctx->ts_host.size() != n_steps || memcmp(ctx->ts_host.data(), timesteps, sizeof(float) * n_steps) != 0 ||
-      ctx->temb_epoch != ctx->weight_epoch) {
-    HIPCHECK(hipStreamSynchronize(s));
-    if ((rc = ensure(ctx, ctx->temb_tab, (size_t)n_steps * d))) return rc;
-    if ((rc = ensure(ctx, ctx->ts_dev, (size_t)n_steps))) return rc;
-    ctx->ts_host.assign(timesteps, timesteps + n_steps);
-    HIPCHECK(hipMemcpy(ctx->ts_dev.p, ctx->ts_host.data(), sizeof(float) * n_steps, hipMemcpyHostToDevice));
-    if ((rc = time_embed(ctx, ctx->ts_dev.p, 0.f, n_steps, ctx->temb_tab.p, s))) return rc;
-    ctx->temb_epoch = ctx->weight_epoch;
-  }
+  if ((rc = ensure_fresca_work(ctx, B))) return rc;
+  if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
+  ctx->tail_solver = FFD_SOLVER_EULER_MARUYAMA;
   const size_t slab = (size_t)B * m.max_len * m.n_channels;
   const uint64_t elem_off = sample_offset * (uint64_t)m.max_len * m.n_channels;
   // Without FreSca the score is consumed only by the SDE step: unembed inside the step kernel (one launch and a
@@ -1168,19 +1215,7 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
     }
     float* crf_dst = nullptr;
     float* crf_copy = nullptr;
-    if (use_cache && ctx->crf_cap_on) {  // cache.update_crf(crf) with current_step == global step (sampler.py:70-73)
-      const ffd_crf_capture_cfg& cc = ctx->crf_cap;
-      const int gstep = global_step0 + j;
-      const size_t crf_n = (size_t)m.num_layers * m.max_len * d;
-      if (cc.ring && gstep % cc.every == 0) crf_dst = cc.ring + (size_t)((gstep / cc.every) % cc.n_slots) * crf_n;
-      if (cc.last && gstep % cc.last_every == 0) {
-        const int rest = n_run - 1 - j;  // is there a later qualifying step in this call?
-        const int to_next = cc.last_every - (gstep % cc.last_every);
-        if (to_next > rest) {
-          if (crf_dst) crf_copy = cc.last; else crf_dst = cc.last;
-        }
-      }
-    }
+    if (use_cache && ctx->crf_cap_on) crf_capture_targets(ctx, global_step0 + j, n_run - 1 - j, &crf_dst, &crf_copy);
     const float* hidden = nullptr;
     if ((rc = forward_impl(ctx, x, ctx->temb_tab.p + (size_t)i * d, 0, ctx->score.p, crf_dst, B, n_rec, s,
                            fuse_tail ? &hidden : nullptr)))
@@ -1191,16 +1226,7 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
     if (use_cache) ctx->stats.current_step = i;  // sampler.py:73-74 (Q4)
     const double t = (double)timesteps[i];
     const float* score = ctx->score.p;
-    if (ctx->fresca_on) {  // sampler.py:79-93 -> fresca.py:220-268
-      const ffd_fresca_cfg& f = ctx->fcfg;
-      double h = (double)f.high_scale;
-      if (f.num_steps > 0 && h > 1.0) h = (1.0 - t / (double)f.num_steps) * (h - 1.0) + 1.0;
-      if (!((double)f.low_scale == 1.0 && h == 1.0)) {  // fresca.py:137-138 early exit
-        HIPCHECK(launch_fresca(ctx->score.p, ctx->score2.p, ctx->fwork.p, B, m.max_len, m.n_channels, f.low_scale, (float)h,
-                               f.cutoff_ratio, f.strategy, s));
-        score = ctx->score2.p;
-      }
-    }
+    if (ctx->fresca_on && (rc = fresca_score(ctx, t, B, s, &score))) return rc;
     if (hidden)
       TIMED(FFD_K_SDE, launch_unembed_sde(hidden, ctx->model.unembed_w, ctx->model.unembed_b, x,
                                           z_inject ? z_inject + (size_t)j * slab : nullptr, ctx->G_dev,
@@ -1210,6 +1236,84 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
       TIMED(FFD_K_SDE, launch_sde_step(x, score, z_inject ? z_inject + (size_t)j * slab : nullptr, ctx->G_dev,
                                        sde_params(m.sde, m.sde_a, m.sde_b, t, step_size), seed, elem_off, (uint32_t)i, B,
                                        m.max_len, m.n_channels, s));
+  }
+  return FFD_OK;
+}
+
+// One score evaluation of an ODE interval, up to where its tail takes over: the forward at time-table row `row` with
+// recompute-set size n_rec (< 0: no cache), the CRF capture, FreSca.  Fused tail: *hidden = the final hidden rows
+// (unembedded inside the tail kernel); otherwise *score = the buffer that holds the (FreSca-scaled) score.
+static int ode_evaluate(ffd_ctx* ctx, const float* xin, int row, double t, int B, int n_rec, float* crf_dst,
+                        float* crf_copy, bool fuse, hipStream_t s, const float** hidden, const float** score) {
+  const ffd_model_desc& m = ctx->desc;
+  *hidden = nullptr;
+  if (int rc = forward_impl(ctx, xin, ctx->temb_tab.p + (size_t)row * m.d_model, 0, ctx->score.p, crf_dst, B, n_rec, s,
+                            fuse ? hidden : nullptr))
+    return rc;
+  if (crf_copy)
+    HIPCHECK(hipMemcpyAsync(crf_copy, crf_dst, sizeof(float) * (size_t)m.num_layers * m.max_len * m.d_model,
+                            hipMemcpyDeviceToDevice, s));
+  *score = ctx->score.p;
+  if (ctx->fresca_on) return fresca_score(ctx, t, B, s, score);
+  return FFD_OK;
+}
+
+int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                         int first_step, int n_run, int solver, int use_cache, int global_step0, void* stream) {
+  if (!ctx) return FFD_ERR_INVALID;
+  int rc = check_ready(ctx, B);
+  if (rc) return rc;
+  if (!x || !timesteps || n_steps < 2 || first_step < 0 || n_run < 0 || first_step + n_run > n_steps - 1)
+    return ctx->fail(FFD_ERR_INVALID, "bad argument to ffd_sample_batch_ode (n_steps=%d first=%d run=%d: %d intervals)",
+                     n_steps, first_step, n_run, n_steps - 1);
+  if (solver != FFD_SOLVER_ODE_EULER && solver != FFD_SOLVER_ODE_HEUN)
+    return ctx->fail(FFD_ERR_INVALID, "unknown ODE solver %d", solver);
+  if (!(step_size > 0.f)) return ctx->fail(FFD_ERR_INVALID, "step_size must be > 0");
+  if (use_cache && ctx->desc.kind != FFD_MODEL_TRANSFORMER)
+    return ctx->fail(FFD_ERR_UNSUPPORTED, "caching is only defined for the transformer backbone");
+  if (use_cache && !ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "use_cache without ffd_cache_enable");
+  HIPCHECK(hipSetDevice(ctx->device));
+  if ((rc = ensure_workspace(ctx, B))) return rc;
+  const ffd_model_desc& m = ctx->desc;
+  const int L = m.max_len, C = m.n_channels, d = m.d_model;
+  const bool heun = solver == FFD_SOLVER_ODE_HEUN;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = ensure_fresca_work(ctx, B))) return rc;
+  if (heun) {  // the predicted state and the predictor's drift
+    if ((rc = ensure(ctx, ctx->ode_xp, (size_t)B * L * C))) return rc;
+    if ((rc = ensure(ctx, ctx->ode_d1, (size_t)B * L * C))) return rc;
+  }
+  if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
+  ctx->tail_solver = solver;
+  float* const xp = ctx->ode_xp.p;
+  float* const d1 = ctx->ode_d1.p;
+  // the workspace buffers are 16-byte aligned: only the caller's x decides the quad path
+  const bool fuse = tail_fusable(ctx) && (C % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 == 0);
+  auto tail = [&](int which, const float* hidden, const float* score, double t) -> hipError_t {
+    const SdeParams p = sde_params(m.sde, m.sde_a, m.sde_b, t, step_size);
+    if (hidden) return launch_unembed_ode(which, hidden, ctx->model.unembed_w, ctx->model.unembed_b, x, xp, d1, ctx->G_dev, p, B, L, C, d, s);
+    return launch_ode_step(which, x, score, xp, d1, ctx->G_dev, p, B, L, C, s);
+  };
+  for (int j = 0; j < n_run; ++j) {
+    const int i = first_step + j;
+    int n_rec = -1;
+    float *crf_dst = nullptr, *crf_copy = nullptr;
+    if (use_cache) {
+      const int gstep = global_step0 + j;
+      ctx->stats.current_step = gstep;
+      n_rec = ffd_host_gate(gstep, L, ctx->ccfg.K, ctx->ccfg.R);
+      if (ctx->crf_cap_on) crf_capture_targets(ctx, gstep, n_run - 1 - j, &crf_dst, &crf_copy);
+    }
+    const float *hidden, *score;
+    const double t = (double)timesteps[i];
+    if ((rc = ode_evaluate(ctx, x, i, t, B, n_rec, crf_dst, crf_copy, fuse, s, &hidden, &score))) return rc;
+    if (use_cache) ctx->stats.current_step = i;
+    TIMED(FFD_K_SDE, tail(heun ? ODE_PREDICT : ODE_EULER, hidden, score, t));
+    if (!heun) continue;
+    // the corrector's evaluation at (xp, t_{i+1}): with the cache a pure hit
+    const double tn = (double)timesteps[i + 1];
+    if ((rc = ode_evaluate(ctx, xp, i + 1, tn, B, use_cache ? 0 : -1, nullptr, nullptr, fuse, s, &hidden, &score))) return rc;
+    TIMED(FFD_K_SDE, tail(ODE_CORRECT, hidden, score, tn));
   }
   return FFD_OK;
 }
@@ -1350,7 +1454,20 @@ const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cac
     case FFD_K_SDE:
       // x, score in; x out (noise generated on chip): 12 B per element; with the unembedding fused
       // into it the score term is replaced by the hidden row: 4 (d + 2 C) B per row
-      if (tail_fusable(ctx))
+      // The ODE tails of ffd_sample_batch_ode draw nothing.  Euler moves the same bytes; Heun's predictor reads x and
+      // writes xp and d1 (3 C floats per row beside the score / hidden row), its corrector reads xp, x, d1 and
+      // writes x (4 C): the mean of the two launches is given.
+      if (ctx->tail_solver == FFD_SOLVER_ODE_HEUN) {
+        if (tail_fusable(ctx))
+          name = "k_unembed_ode<heun predict | correct>", fl = 2.0 * M * C * d, by = 4.0 * M * (d + 3.5 * C);
+        else
+          name = "k_ode_step<heun predict | correct>", by = 18.0 * M * C;
+      } else if (ctx->tail_solver == FFD_SOLVER_ODE_EULER) {
+        if (tail_fusable(ctx))
+          name = "k_unembed_ode<euler>", fl = 2.0 * M * C * d, by = 4.0 * M * (d + 2.0 * C);
+        else
+          name = "k_ode_step<euler>", by = 12.0 * M * C;
+      } else if (tail_fusable(ctx))
         name = "k_unembed_mfma<sde>", fl = 2.0 * M * C * d, by = 4.0 * M * (d + 2.0 * C);
       else
         name = "k_sde_step", by = 12.0 * M * C;

@@ -2,6 +2,7 @@
 //   - weight packing into MFMA fragment order, nn.Embedding(max_norm) renorm
 //   - Gaussian-Fourier time embedding, channel embed / unembed
 //   - VP / VE reverse Euler-Maruyama step with on-device Philox4x32-10 noise
+//   - probability-flow ODE intervals (Euler, Heun predictor / corrector): no noise draw
 //   - KV-table store
 // All HBM-bound: one pass over the data, coalesced, no re-reads.
 // The entry points that need no context (SDE step, prior, the two encodings, Hermite prediction) follow the kernels.
@@ -452,6 +453,112 @@ hipError_t launch_sde_step(float* x, const float* score, const float* z, const f
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// probability-flow ODE steps (an extension: the reference has Euler-Maruyama only).  Same grid, G, beta(t) and VE
+// sqrt_derivative as the SDE step (sde_params); the drift of the ODE with the SDE's marginals is
+//   d(x, t) = f(x, t) - 1/2 (g(t) G_l)^2 s(x, t),   f = a*x (VP), 0 (VE)
+// and one interval of width dt towards smaller t is
+//   Euler:  x <- x - d(x, t_i) dt
+//   Heun :  d1 = d(x, t_i);  xp = x - d1 dt;  d2 = d(xp, t_{i+1});  x <- x - (1/2 (d1 + d2)) dt
+// No noise draw.  Like sde_update every product / sum is its own fp32 rounding (no FMA contraction).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float ode_drift(float xi, float sc, float Gl, const SdeParams& p) {
+  const float g = __fmul_rn(p.cs, Gl);
+  const float g2 = __fmul_rn(g, g);
+  const float gs = __fmul_rn(g2, sc);
+  const float hgs = __fmul_rn(0.5f, gs);
+  return (p.sde == 0) ? __fsub_rn(__fmul_rn(p.a, xi), hgs) : -hgs;
+}
+
+// One element of a tail.  EULER: returns the new x (xi = x).  PREDICT: returns xp, d1 = the drift at (x, t_i).
+// CORRECT: xi = xp, sc = the score at xp, p = the parameters at t_{i+1}; x0 / d1 = what PREDICT read / wrote; returns
+// the new x.
+template <int TAIL>
+__device__ __forceinline__ float ode_update(float xi, float sc, float Gl, float x0, float& d1, const SdeParams& p) {
+  const float d = ode_drift(xi, sc, Gl, p);
+  if (TAIL == ODE_CORRECT) return __fsub_rn(x0, __fmul_rn(__fmul_rn(0.5f, __fadd_rn(d1, d)), p.dt));
+  if (TAIL == ODE_PREDICT) d1 = d;
+  return __fsub_rn(xi, __fmul_rn(d, p.dt));
+}
+
+// The stand-alone tails (score from HBM): the twins of k_sde_step_v4 / k_sde_step.  Buffers by tail:
+//   EULER    x in / out
+//   PREDICT  x in, xp out, d1 out
+//   CORRECT  xp in (score = the score at xp), x in / out, d1 in
+template <int TAIL>
+__global__ __launch_bounds__(256) void k_ode_step_v4(float* __restrict__ x, const float* __restrict__ score,
+                                                     float* __restrict__ xp, float* __restrict__ d1,
+                                                     const float* __restrict__ G, SdeParams p, size_t nvec, int L,
+                                                     unsigned C4) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
+    const float4 sc = reinterpret_cast<const float4*>(score)[v];
+    const float Gl = G[(v / C4) % (size_t)L];
+    if (TAIL == ODE_CORRECT) {
+      const float4 xi = reinterpret_cast<const float4*>(xp)[v];
+      const float4 x0 = reinterpret_cast<const float4*>(x)[v];
+      float4 dv = reinterpret_cast<const float4*>(d1)[v];
+      reinterpret_cast<float4*>(x)[v] =
+          float4{ode_update<TAIL>(xi.x, sc.x, Gl, x0.x, dv.x, p), ode_update<TAIL>(xi.y, sc.y, Gl, x0.y, dv.y, p),
+                 ode_update<TAIL>(xi.z, sc.z, Gl, x0.z, dv.z, p), ode_update<TAIL>(xi.w, sc.w, Gl, x0.w, dv.w, p)};
+    } else {
+      const float4 xi = reinterpret_cast<const float4*>(x)[v];
+      float4 dv{};
+      const float4 xn = float4{ode_update<TAIL>(xi.x, sc.x, Gl, 0.f, dv.x, p), ode_update<TAIL>(xi.y, sc.y, Gl, 0.f, dv.y, p),
+                               ode_update<TAIL>(xi.z, sc.z, Gl, 0.f, dv.z, p), ode_update<TAIL>(xi.w, sc.w, Gl, 0.f, dv.w, p)};
+      if (TAIL == ODE_PREDICT) {
+        reinterpret_cast<float4*>(xp)[v] = xn;
+        reinterpret_cast<float4*>(d1)[v] = dv;
+      } else {
+        reinterpret_cast<float4*>(x)[v] = xn;
+      }
+    }
+  }
+}
+
+template <int TAIL>
+__global__ void k_ode_step(float* __restrict__ x, const float* __restrict__ score, float* __restrict__ xp,
+                           float* __restrict__ d1, const float* __restrict__ G, SdeParams p, size_t total, int L, int C) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const float Gl = G[(i / (size_t)C) % (size_t)L];
+    if (TAIL == ODE_CORRECT) {
+      float dv = d1[i];
+      x[i] = ode_update<TAIL>(xp[i], score[i], Gl, x[i], dv, p);
+    } else {
+      float dv = 0.f;
+      const float xn = ode_update<TAIL>(x[i], score[i], Gl, 0.f, dv, p);
+      if (TAIL == ODE_PREDICT) xp[i] = xn, d1[i] = dv;
+      else x[i] = xn;
+    }
+  }
+}
+
+template <int TAIL>
+static hipError_t launch_ode_tail(float* x, const float* score, float* xp, float* d1, const float* G, SdeParams p, int B,
+                                  int L, int C, hipStream_t s) {
+  const size_t total = (size_t)B * L * C;
+  if (C % 4 == 0 && ptr16(x) && ptr16(score) && ptr16(xp) && ptr16(d1)) {
+    size_t blocks = (total / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL((k_ode_step_v4<TAIL>), dim3((unsigned)blocks), dim3(256), 0, s, x, score, xp, d1, G, p, total / 4, L,
+                       (unsigned)C / 4);
+  } else {
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL((k_ode_step<TAIL>), dim3((unsigned)blocks), dim3(256), 0, s, x, score, xp, d1, G, p, total, L, C);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_ode_step(int tail, float* x, const float* score, float* xp, float* d1, const float* G, SdeParams p,
+                           int B, int L, int C, hipStream_t s) {
+  switch (tail) {
+    case ODE_EULER: return launch_ode_tail<ODE_EULER>(x, score, nullptr, nullptr, G, p, B, L, C, s);
+    case ODE_PREDICT: return launch_ode_tail<ODE_PREDICT>(x, score, xp, d1, G, p, B, L, C, s);
+    case ODE_CORRECT: return launch_ode_tail<ODE_CORRECT>(x, score, xp, d1, G, p, B, L, C, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 // prior: x = G (.) z  (VE: * sigma_max), sde.py:79-87,125-127
 __device__ __forceinline__ float prior_value(float Gl, float zz, float scale) {
   const float v0 = __fmul_rn(Gl, zz);
@@ -678,6 +785,132 @@ hipError_t launch_unembed_sde(const float* h, const float* Wu, const float* bu, 
   return launch_unembed_mfma<true>(h, Wu, bu, nullptr, x, z, G, p, seed, elem_offset, step, B * L, L, C, D, s);
 }
 
+// The probability-flow ODE tails of the sampling loop: k_unembed_mfma's score tile (same fragments, same MFMA order,
+// same prefetch of the next tile) continued with ode_update in the accumulator registers.  A sibling kernel, so that
+// the two instances above keep their code.  Buffers by tail as in k_ode_step; the quad path (C % 4 == 0) fetches the
+// tile's x (CORRECT: xp, x and d1) together with its h rows.
+template <int D, int TAIL>
+__global__ __launch_bounds__(256) void k_unembed_ode(const float* __restrict__ h, const float* __restrict__ Wu,
+                                                     const float* __restrict__ bu, float* __restrict__ x,
+                                                     float* __restrict__ xp, float* __restrict__ d1,
+                                                     const float* __restrict__ G, SdeParams p, int M, int L, int C) {
+  constexpr int NG = (D + 15) / 16;  // 16-wide k chunks
+  const int lane = threadIdx.x & 63;
+  const int r = lane & 15, q = lane >> 4;
+  const int ntiles = (M + 15) >> 4;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+  float4 wf[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int k = 16 * g + 4 * q;
+    wf[g] = (r < C && k < D) ? *reinterpret_cast<const float4*>(Wu + (size_t)r * D + k) : float4{0.f, 0.f, 0.f, 0.f};
+  }
+  f32x4 bias;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) bias[i] = (4 * q + i < C) ? bu[4 * q + i] : 0.f;
+  auto load_tile = [&](int t, float4 (&hv)[NG]) {
+    const int row = min(16 * t + r, M - 1);
+    const float* hr = h + (size_t)row * D + 4 * q;
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+      hv[g] = (16 * g + 4 * q < D) ? *reinterpret_cast<const float4*>(hr + 16 * g) : float4{0.f, 0.f, 0.f, 0.f};
+  };
+  // u0 = the quad ode_update starts from (x; CORRECT: xp), u1 / u2 = CORRECT's x and d1
+  const bool quad = (C & 3) == 0 && 4 * q < C;
+  auto load_u = [&](int t, float4& u0, float4& u1, float4& u2) {
+    if (quad) {
+      const size_t i0 = (size_t)min(16 * t + r, M - 1) * C + 4 * q;
+      u0 = *reinterpret_cast<const float4*>((TAIL == ODE_CORRECT ? xp : x) + i0);
+      if (TAIL == ODE_CORRECT) {
+        u1 = *reinterpret_cast<const float4*>(x + i0);
+        u2 = *reinterpret_cast<const float4*>(d1 + i0);
+      }
+    }
+  };
+  float4 hv[NG], hn[NG];
+  float4 u0{}, u1{}, u2{}, n0{}, n1{}, n2{};
+  if (wave < ntiles) load_tile(wave, hv), load_u(wave, u0, u1, u2);
+  for (int t = wave; t < ntiles; t += nwaves) {
+    const bool more = t + nwaves < ntiles;
+    if (more) load_tile(t + nwaves, hn), load_u(t + nwaves, n0, n1, n2);
+    f32x4 acc = bias;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      acc = mfma16(wf[g].x, hv[g].x, acc);
+      acc = mfma16(wf[g].y, hv[g].y, acc);
+      acc = mfma16(wf[g].z, hv[g].z, acc);
+      acc = mfma16(wf[g].w, hv[g].w, acc);
+    }
+    const int row = 16 * t + r;
+    const int c0 = 4 * q;
+    if (row < M && c0 < C) {
+      const size_t i0 = (size_t)row * C + c0;
+      const float Gl = G[row % L];
+      if ((C & 3) == 0) {
+        float4 dv = u2;
+        const float4 xn = float4{ode_update<TAIL>(u0.x, acc[0], Gl, u1.x, dv.x, p), ode_update<TAIL>(u0.y, acc[1], Gl, u1.y, dv.y, p),
+                                 ode_update<TAIL>(u0.z, acc[2], Gl, u1.z, dv.z, p), ode_update<TAIL>(u0.w, acc[3], Gl, u1.w, dv.w, p)};
+        if (TAIL == ODE_PREDICT) {
+          *reinterpret_cast<float4*>(xp + i0) = xn;
+          *reinterpret_cast<float4*>(d1 + i0) = dv;
+        } else {
+          *reinterpret_cast<float4*>(x + i0) = xn;
+        }
+      } else {
+        const int n = min(4, C - c0);
+        for (int i = 0; i < n; ++i) {
+          if (TAIL == ODE_CORRECT) {
+            float dv = d1[i0 + i];
+            x[i0 + i] = ode_update<TAIL>(xp[i0 + i], acc[i], Gl, x[i0 + i], dv, p);
+          } else {
+            float dv = 0.f;
+            const float xn = ode_update<TAIL>(x[i0 + i], acc[i], Gl, 0.f, dv, p);
+            if (TAIL == ODE_PREDICT) xp[i0 + i] = xn, d1[i0 + i] = dv;
+            else x[i0 + i] = xn;
+          }
+        }
+      }
+    }
+    if (more) {
+#pragma unroll
+      for (int g = 0; g < NG; ++g) hv[g] = hn[g];
+      u0 = n0, u1 = n1, u2 = n2;
+    }
+  }
+}
+
+template <int TAIL>
+static hipError_t launch_unembed_ode_tail(const float* h, const float* Wu, const float* bu, float* x, float* xp, float* d1,
+                                          const float* G, SdeParams p, int M, int L, int C, int D, hipStream_t s) {
+  int blocks = cdiv(cdiv(M, 16), 4);
+  if (blocks > 2048) blocks = 2048;
+  switch (D) {
+#define X(d)                                                                                                          \
+  case d:                                                                                                             \
+    hipLaunchKernelGGL((k_unembed_ode<d, TAIL>), dim3(blocks), dim3(256), 0, s, h, Wu, bu, x, xp, d1, G, p, M, L, C); \
+    break;
+    FFD_D_LIST(X)
+#undef X
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// tail(x, unembed(h)): the fused tail of an ODE interval (requires unembed_sde_supported(C, D)); xp / d1 as in
+// launch_ode_step (unused by ODE_EULER)
+hipError_t launch_unembed_ode(int tail, const float* h, const float* Wu, const float* bu, float* x, float* xp, float* d1,
+                              const float* G, SdeParams p, int B, int L, int C, int D, hipStream_t s) {
+  if (!unembed_sde_supported(C, D) || !ptr16(h) || !ptr16(Wu)) return hipErrorInvalidValue;
+  if ((C & 3) == 0 && (!ptr16(x) || !ptr16(xp) || !ptr16(d1))) return hipErrorInvalidValue;  // quads
+  if (tail != ODE_EULER && (!xp || !d1)) return hipErrorInvalidValue;
+  switch (tail) {
+    case ODE_EULER: return launch_unembed_ode_tail<ODE_EULER>(h, Wu, bu, x, nullptr, nullptr, G, p, B * L, L, C, D, s);
+    case ODE_PREDICT: return launch_unembed_ode_tail<ODE_PREDICT>(h, Wu, bu, x, xp, d1, G, p, B * L, L, C, D, s);
+    case ODE_CORRECT: return launch_unembed_ode_tail<ODE_CORRECT>(h, Wu, bu, x, xp, d1, G, p, B * L, L, C, D, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // KV table store: table[h][l][:] <- sample 0's head-major K/V rows, l < n (Q1)
 // ---------------------------------------------------------------------------
@@ -753,6 +986,41 @@ int ffd_sde_step(const ffd_sde_desc* sde, float* x, const float* score, const fl
   if (!(step_size > 0.f)) return FFD_ERR_INVALID;  // sde.py:157,238 assert
   hipError_t e = launch_sde_step(x, score, z, G, sde_params(sde->sde, sde->a, sde->b, t, step_size), seed,
                                  sample_offset * (uint64_t)L * C, (uint32_t)step, B, L, C, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+// the argument checks the three ODE operators share (before any device work)
+static int ode_args(const ffd_sde_desc* sde, const void* x, const void* score, const void* G, float step_size, int B, int L,
+                    int C) {
+  if (!sde || !x || !score || !G || B < 1 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  if (!(step_size > 0.f)) return FFD_ERR_INVALID;
+  if (sde->sde != FFD_SDE_VP && sde->sde != FFD_SDE_VE) return FFD_ERR_UNSUPPORTED;
+  return FFD_OK;
+}
+
+int ffd_ode_step(const ffd_sde_desc* sde, float* x, const float* score, const float* G, double t, float step_size, int B,
+                 int L, int C, void* stream) {
+  if (int rc = ode_args(sde, x, score, G, step_size, B, L, C)) return rc;
+  hipError_t e = launch_ode_step(ODE_EULER, x, score, nullptr, nullptr, G, sde_params(sde->sde, sde->a, sde->b, t, step_size),
+                                 B, L, C, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+int ffd_ode_heun_predict(const ffd_sde_desc* sde, const float* x, const float* score, const float* G, double t,
+                         float step_size, float* x_pred_out, float* drift_out, int B, int L, int C, void* stream) {
+  if (int rc = ode_args(sde, x, score, G, step_size, B, L, C)) return rc;
+  if (!x_pred_out || !drift_out || x_pred_out == x || drift_out == x || x_pred_out == drift_out) return FFD_ERR_INVALID;
+  hipError_t e = launch_ode_step(ODE_PREDICT, const_cast<float*>(x), score, x_pred_out, drift_out, G,
+                                 sde_params(sde->sde, sde->a, sde->b, t, step_size), B, L, C, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+int ffd_ode_heun_correct(const ffd_sde_desc* sde, float* x, const float* x_pred, const float* score_pred, const float* drift,
+                         const float* G, double t_next, float step_size, int B, int L, int C, void* stream) {
+  if (int rc = ode_args(sde, x, score_pred, G, step_size, B, L, C)) return rc;
+  if (!x_pred || !drift || x_pred == x || drift == x) return FFD_ERR_INVALID;
+  hipError_t e = launch_ode_step(ODE_CORRECT, x, score_pred, const_cast<float*>(x_pred), const_cast<float*>(drift), G,
+                                 sde_params(sde->sde, sde->a, sde->b, t_next, step_size), B, L, C, (hipStream_t)stream);
   return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
 }
 

@@ -248,6 +248,17 @@ bool unembed_sde_supported(int C, int D);
 hipError_t launch_unembed_sde(const float* h, const float* Wu, const float* bu, float* x, const float* z, const float* G,
                               SdeParams p, uint64_t seed, uint64_t elem_offset, uint32_t step, int B, int L, int C,
                               int D, hipStream_t s);
+// The probability-flow ODE tails (ffd_elem.hip).  p = sde_params at the time of the score evaluation (sqdt unused).
+//   ODE_EULER    x <- x - d(x, score) dt                                       (xp, d1 unused)
+//   ODE_PREDICT  d1 <- d(x, score);  xp <- x - d1 dt                           (x is not modified)
+//   ODE_CORRECT  x <- x - (1/2 (d1 + d(xp, score))) dt, score = the score at xp, p at the interval's end
+// x, xp and d1 are distinct (B, L, C) buffers.
+enum OdeTail { ODE_EULER = 0, ODE_PREDICT = 1, ODE_CORRECT = 2 };
+hipError_t launch_ode_step(int tail, float* x, const float* score, float* xp, float* d1, const float* G, SdeParams p,
+                           int B, int L, int C, hipStream_t s);
+// ... with the unembedding inside (the score stays in registers).  Needs unembed_sde_supported(C, D).
+hipError_t launch_unembed_ode(int tail, const float* h, const float* Wu, const float* bu, float* x, float* xp, float* d1,
+                              const float* G, SdeParams p, int B, int L, int C, int D, hipStream_t s);
 
 // Denoising score-matching loss (ffd_loss.hip; losses.py:54-125).  Sample b of the call is global sample
 // sample_offset + b: with z == nullptr both kernels take the draw of global element g from slot g & 3 of Philox block

@@ -16,6 +16,12 @@ device.  ``rng="philox"`` generates the draws inside the step kernel (Philox4x32
 keyed by (seed, step, global element index)): no z traffic, and the NOISE is invariant
 to how samples are sharded over GPUs.
 
+Solver (extension): ``solver="euler_maruyama"`` (default) is the reference's integrator.  ``"ode_euler"`` and
+``"ode_heun"`` integrate the probability-flow ODE of the same SDE (the same marginals, Song et al. 2021) through
+``ffd_sample_batch_ode``: deterministic given the prior (no step noise is drawn), over the N - 1 intervals of the
+N-point grid, ending exactly at ``eps``; Heun evaluates the model twice per interval and is second order.  Batching,
+cache lifecycle and prior are unchanged; the global step of the cache gate counts intervals.
+
 Two batch-wide statistics of the reference make the SAMPLES depend on the batching all the
 same, sharded or not (they are properties of the reference's algorithm, reproduced here per
 batch / per shard): the E2-CRF tables come from the batch's element 0 (caching.py:326-328), and
@@ -40,13 +46,19 @@ from ..schedulers.sde import SDE
 from ..utils.dataclasses import DiffusableBatch
 
 
+# solver name -> libffd's FFD_SOLVER_*
+SOLVERS = {"euler_maruyama": N.FFD_SOLVER_EULER_MARUYAMA, "ode_euler": N.FFD_SOLVER_ODE_EULER,
+           "ode_heun": N.FFD_SOLVER_ODE_HEUN}
+
+
 class DiffusionSampler:
     def __init__(self, score_model: ScoreModule, sample_batch_size: int, use_cache: bool = False,
                  cache_kwargs: Optional[dict] = None, use_fresca: bool = False, fresca_low_scale: float = 1.0,
                  fresca_high_scale: float = 1.5, fresca_cutoff_ratio: float = 0.5,
                  fresca_cutoff_strategy: Literal["spatial", "energy"] = "energy",
                  rng: Literal["torch", "philox"] = "torch", seed: int = 42, sample_offset: int = 0,
-                 z_chunk_steps: int = 50) -> None:
+                 z_chunk_steps: int = 50,
+                 solver: Literal["euler_maruyama", "ode_euler", "ode_heun"] = "euler_maruyama") -> None:
         self.score_model = score_model
         self.noise_scheduler = score_model.noise_scheduler
         self.sample_batch_size = sample_batch_size
@@ -71,6 +83,9 @@ class DiffusionSampler:
         self.seed = int(seed)
         self.sample_offset = int(sample_offset)
         self.z_chunk_steps = int(z_chunk_steps)
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {sorted(SOLVERS)}, got {solver!r}")
+        self.solver = solver
         self._injected = None
 
     def inject_noise(self, draws) -> None:
@@ -94,10 +109,31 @@ class DiffusionSampler:
         assert timesteps is not None and timesteps.size(0) == len(batch)
         t_lo, t_hi = float(torch.min(timesteps)), float(torch.max(timesteps))
         assert t_lo == t_hi  # sampler.py:59-60
+        sch = self.noise_scheduler
+        t_next = self._heun_next_time(timesteps[0]) if self.solver == "ode_heun" else None
+        score = self._evaluate_score(batch, t_lo, step, recompute_tokens, update_crf=True)
+        if self.solver == "euler_maruyama":
+            output = sch.step(model_output=score, timestep=timesteps[0].item(), sample=X)
+        elif self.solver == "ode_euler":
+            output = sch.ode_step(model_output=score, timestep=timesteps[0].item(), sample=X)
+        else:  # Heun: a second model call at the predicted state and the interval's end (with the cache: a pure hit)
+            X_pred, drift = sch.ode_heun_predict(model_output=score, timestep=timesteps[0].item(), sample=X)
+            batch_pred = DiffusableBatch(X=X_pred, y=batch.y, timesteps=torch.full_like(timesteps, t_next))
+            score_pred = self._evaluate_score(batch_pred, t_next, step, None if recompute_tokens is None else set(),
+                                              update_crf=False)
+            output = sch.ode_heun_correct(model_output_pred=score_pred, timestep_next=t_next, sample=X,
+                                          sample_pred=X_pred, drift=drift)
+        X_prev = output.prev_sample
+        assert isinstance(X_prev, torch.Tensor)
+        return X_prev
+
+    def _evaluate_score(self, batch: DiffusableBatch, t: float, step: int, recompute_tokens: Optional[set],
+                        update_crf: bool) -> torch.Tensor:
+        """One model call of ``reverse_diffusion_step`` with its cache bookkeeping and FreSca (sampler.py:62-93)."""
         if self.use_cache and recompute_tokens is not None:
             score, crf = self.score_model(batch, recompute_tokens=recompute_tokens, step=step, return_crf=True)
-            if self.score_model.cache is not None:
-                self.score_model.cache.update_crf(crf, timestep=t_lo)
+            if self.score_model.cache is not None and update_crf:
+                self.score_model.cache.update_crf(crf, timestep=t)
                 self.score_model.cache.current_step = step
         else:
             score = self.score_model(batch)
@@ -107,11 +143,19 @@ class DiffusionSampler:
             score = apply_fresca_to_score(score, low_scale=self.fresca_low_scale, high_scale=self.fresca_high_scale,
                                           cutoff_ratio=self.fresca_cutoff_ratio,
                                           cutoff_strategy="energy" if self.fresca_cutoff_strategy == "energy" else "spatial",
-                                          timestep=t_lo, num_steps=getattr(self, "_num_diffusion_steps", None))
-        output = self.noise_scheduler.step(model_output=score, timestep=timesteps[0].item(), sample=X)
-        X_prev = output.prev_sample
-        assert isinstance(X_prev, torch.Tensor)
-        return X_prev
+                                          timestep=t, num_steps=getattr(self, "_num_diffusion_steps", None))
+        return score
+
+    def _heun_next_time(self, t: torch.Tensor) -> float:
+        """The grid point after ``t``: Heun's corrector evaluates the model there."""
+        grid = getattr(self.noise_scheduler, "timesteps", None)
+        if grid is None:
+            raise ValueError("solver='ode_heun' needs the scheduler's grid: call noise_scheduler.set_timesteps(n) first")
+        hit = torch.nonzero(grid.to(torch.float32) == t.detach().to(torch.float32).cpu()).flatten()
+        if hit.numel() == 0 or int(hit[0]) >= grid.numel() - 1:
+            raise ValueError(f"solver='ode_heun' steps from a point of the scheduler's grid other than the last one; "
+                             f"got t={float(t)!r}")
+        return float(grid[int(hit[0]) + 1])
 
     # ------------------------------------------------------------------
     def sample(self, num_samples: int, num_diffusion_steps: Optional[int] = None) -> torch.Tensor:
@@ -121,6 +165,11 @@ class DiffusionSampler:
         self.score_model.eval()
         num_diffusion_steps = (self.score_model.num_training_steps if num_diffusion_steps is None
                                else num_diffusion_steps)
+        # Euler-Maruyama takes one step per grid point; the ODE solvers walk the intervals between them and end at eps
+        ode = self.solver != "euler_maruyama"
+        if ode and num_diffusion_steps < 2:
+            raise ValueError("the ODE solvers need a grid of at least two points")
+        n_iter = num_diffusion_steps - 1 if ode else num_diffusion_steps
         self.noise_scheduler.set_timesteps(num_diffusion_steps)
         sch = self.noise_scheduler
         ts = sch.timesteps.to(torch.float32).contiguous()
@@ -155,10 +204,10 @@ class DiffusionSampler:
                     model._native_cache_configure(model.cache)
                 cap = self._crf_capture_begin(ctx, device) if use_cache else None
                 done = 0
-                while done < num_diffusion_steps:
-                    n = num_diffusion_steps - done
+                while done < n_iter:
+                    n = n_iter - done
                     z_ptr = None
-                    if self.rng == "torch" or self._injected is not None:
+                    if not ode and (self.rng == "torch" or self._injected is not None):
                         n = min(n, max(1, self.z_chunk_steps))
                         z = torch.empty((n,) + tuple(X.shape), device=device, dtype=torch.float32)
                         for i in range(n):  # one randn_like per step, as the reference consumes its generator
@@ -167,17 +216,23 @@ class DiffusionSampler:
                             else:
                                 z[i].normal_()
                         z_ptr = z.data_ptr()
-                    rc = ctx.lib.ffd_sample_batch(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
-                                                  step_size, done, n, self.seed, sample_cursor, z_ptr, use_cache,
-                                                  (global_step + done) if use_cache else 0, stream)
-                    N.check(rc, ctx.handle, "ffd_sample_batch")
+                    if ode:  # deterministic given the prior: no step noise is drawn or allocated
+                        rc = ctx.lib.ffd_sample_batch_ode(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
+                                                          step_size, done, n, SOLVERS[self.solver], use_cache,
+                                                          (global_step + done) if use_cache else 0, stream)
+                        N.check(rc, ctx.handle, "ffd_sample_batch_ode")
+                    else:
+                        rc = ctx.lib.ffd_sample_batch(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
+                                                      step_size, done, n, self.seed, sample_cursor, z_ptr, use_cache,
+                                                      (global_step + done) if use_cache else 0, stream)
+                        N.check(rc, ctx.handle, "ffd_sample_batch")
                     if cap is not None:
                         self._crf_capture_collect(cap, global_step + done, n, ts, done)
                     done += n
                 if use_cache:
                     N.check(ctx.lib.ffd_cache_crf_capture(ctx.handle, None), ctx.handle, "ffd_cache_crf_capture")
-                    global_step += num_diffusion_steps
-                    model.cache.current_step = num_diffusion_steps - 1  # sampler.py:73-74 leaves step_idx
+                    global_step += n_iter
+                    model.cache.current_step = n_iter - 1  # sampler.py:73-74 leaves step_idx
                 all_samples.append(X.cpu())
                 # (the copy has drained the stream) a kernel-side time-out of this batch's launches is an error here
                 N.check(ctx.lib.ffd_async_status(ctx.handle), ctx.handle, "sampling loop")

@@ -130,6 +130,53 @@ class SDE(abc.ABC):
         N.check(rc, None, "ffd_sde_step")
         return SamplingOutput(prev_sample=x)
 
+    # -- probability-flow ODE (extension: the reference has ``step`` only) ------
+    def _ode_args(self, sample: torch.Tensor, model_output: torch.Tensor):
+        sample = N.require_gpu_tensor(sample, "sample")
+        model_output = N.require_gpu_tensor(model_output, "model_output")
+        assert self.step_size > 0
+        assert sample.shape == model_output.shape
+        return sample, model_output, self._G_on(sample.device).data_ptr(), N.current_stream_ptr(sample.device)
+
+    def ode_step(self, model_output: torch.Tensor, timestep: float, sample: torch.Tensor) -> SamplingOutput:
+        """One Euler interval of the probability-flow ODE from ``timestep`` down by ``step_size``:
+        x - (f(x, t) - (g(t) G)^2 score / 2) * step_size, with f, g and G of ``step``.  No noise is drawn."""
+        sample, model_output, G, stream = self._ode_args(sample, model_output)
+        B, L, Cn = sample.shape
+        x = sample.clone()
+        desc = self._desc()
+        rc = N.lib().ffd_ode_step(C.byref(desc), x.data_ptr(), model_output.data_ptr(), G, float(timestep),
+                                  float(self.step_size), B, L, Cn, stream)
+        N.check(rc, None, "ffd_ode_step")
+        return SamplingOutput(prev_sample=x)
+
+    def ode_heun_predict(self, model_output: torch.Tensor, timestep: float, sample: torch.Tensor):
+        """Heun's first stage at ``timestep``: (the Euler prediction, the drift there)."""
+        sample, model_output, G, stream = self._ode_args(sample, model_output)
+        B, L, Cn = sample.shape
+        x_pred, drift = torch.empty_like(sample), torch.empty_like(sample)
+        desc = self._desc()
+        rc = N.lib().ffd_ode_heun_predict(C.byref(desc), sample.data_ptr(), model_output.data_ptr(), G, float(timestep),
+                                          float(self.step_size), x_pred.data_ptr(), drift.data_ptr(), B, L, Cn, stream)
+        N.check(rc, None, "ffd_ode_heun_predict")
+        return x_pred, drift
+
+    def ode_heun_correct(self, model_output_pred: torch.Tensor, timestep_next: float, sample: torch.Tensor,
+                         sample_pred: torch.Tensor, drift: torch.Tensor) -> SamplingOutput:
+        """Heun's second stage: ``model_output_pred`` is the score at (``sample_pred``, ``timestep_next``), ``sample``
+        the state ``ode_heun_predict`` started from."""
+        sample, model_output_pred, G, stream = self._ode_args(sample, model_output_pred)
+        sample_pred = N.require_gpu_tensor(sample_pred, "sample_pred")
+        drift = N.require_gpu_tensor(drift, "drift")
+        B, L, Cn = sample.shape
+        x = sample.clone()
+        desc = self._desc()
+        rc = N.lib().ffd_ode_heun_correct(C.byref(desc), x.data_ptr(), sample_pred.data_ptr(), model_output_pred.data_ptr(),
+                                          drift.data_ptr(), G, float(timestep_next), float(self.step_size), B, L, Cn,
+                                          stream)
+        N.check(rc, None, "ffd_ode_heun_correct")
+        return SamplingOutput(prev_sample=x)
+
 
 class VEScheduler(SDE):
     """sde.py:90-165."""

@@ -177,6 +177,30 @@ int ffd_sde_step(const ffd_sde_desc* sde, float* x, const float* score, const fl
                  float step_size, const float* z, uint64_t seed, uint64_t sample_offset, int step, int B,
                  int L, int C, void* stream);
 
+/* ---- probability-flow ODE steps (an extension: the reference integrates with Euler-Maruyama only) ----
+ * Every VP / VE score model has a deterministic ODE with the SDE's marginals (Song et al. 2021).  With the forward SDE
+ * dx = f(x,t) dt + g(t) diag(G) dw (f = -1/2 beta(t) x for VP, 0 for VE; beta(t), the VE sqrt_derivative and G exactly
+ * as in ffd_sde_step) its drift is
+ *     d(x,t) = f(x,t) - 1/2 (g(t) G_l)^2 s(x,t)
+ * and one interval of width step_size towards smaller t is
+ *     Euler:  x <- x - d(x,t) step_size
+ *     Heun :  d1 = d(x,t);  xp = x - d1 step_size;  d2 = d(xp,t_next);  x <- x - (1/2 (d1 + d2)) step_size.
+ * No noise is drawn.  Per element, each a separate fp32 rounding (no FMA contraction), like ffd_sde_step:
+ *     g = cs G_l, g2 = g g, gs = g2 s, hgs = 0.5 gs, d = a x - hgs (VP) | -hgs (VE).
+ * Context-free and stream ordered; all buffers (B,L,C) on the device, none of them may alias another.
+ * FFD_ERR_INVALID before any device work: a null pointer, B, L, C < 1, step_size <= 0, aliased outputs. */
+/* Euler, in place on x. */
+int ffd_ode_step(const ffd_sde_desc* sde, float* x, const float* score, const float* G, double t, float step_size,
+                 int B, int L, int C, void* stream);
+/* Heun's predictor at the interval's start t: drift_out <- d1, x_pred_out <- xp.  x is not modified. */
+int ffd_ode_heun_predict(const ffd_sde_desc* sde, const float* x, const float* score, const float* G, double t,
+                         float step_size, float* x_pred_out, float* drift_out, int B, int L, int C, void* stream);
+/* Heun's corrector at the interval's end t_next: score_pred = the score at (x_pred, t_next), drift = the predictor's
+ * d1; x (the state the predictor read) is updated in place. */
+int ffd_ode_heun_correct(const ffd_sde_desc* sde, float* x, const float* x_pred, const float* score_pred,
+                         const float* drift, const float* G, double t_next, float step_size, int B, int L, int C,
+                         void* stream);
+
 /* SDE.prior_sampling (sde.py:79-87, 125-127): x <- G (.) z  (VE: * sigma_max);
  * z == NULL draws on device (Philox stream tag 0xFFFFFFFF). */
 int ffd_prior(const ffd_sde_desc* sde, float* x, const float* z, const float* G, uint64_t seed,
@@ -446,6 +470,25 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
                      int first_step, int n_run, uint64_t seed, uint64_t sample_offset, const float* z_inject,
                      int use_cache, int global_step0, void* stream);
 
+/* The same loop on the probability-flow ODE (see ffd_ode_step): an extension beyond the reference for sampling with
+ * few score evaluations.  Deterministic: no noise, no seed.  The solvers walk the n_steps - 1 INTERVALS of the grid
+ * t_0 = 1 ... t_{n_steps-1} = eps (interval i: from timesteps[i] to timesteps[i+1], width step_size) and end exactly
+ * at eps; this call runs intervals [first_step, first_step + n_run), first_step + n_run <= n_steps - 1, n_steps >= 2.
+ *   FFD_SOLVER_ODE_EULER  one score evaluation per interval (at timesteps[i]);
+ *   FFD_SOLVER_ODE_HEUN   two: the predictor's at timesteps[i], the corrector's at (x_pred, timesteps[i+1]).
+ * Same time-embedding table, stream ordering and host synchronisation as ffd_sample_batch (none but for a new grid);
+ * with the unembedding fused into the tail (see "fuse_tail") no score reaches HBM.
+ *   use_cache  the predictor evaluation of interval i follows ffd_host_gate at global step global_step0 + (i -
+ *              first_step); Heun's corrector evaluation is a pure cache hit (n_recompute = 0).  Tables, counters and
+ *              the CRF capture (taken from the predictor evaluation) are those of ffd_score_forward_cached calls of
+ *              these sizes in this order.
+ *   FreSca     applied to every evaluated score with h(t) of that evaluation's time.
+ * FFD_ERR_INVALID before any device work: null pointers, B < 1, step_size <= 0, an unknown solver, an interval range
+ * outside the grid. */
+enum { FFD_SOLVER_EULER_MARUYAMA = 0, FFD_SOLVER_ODE_EULER = 1, FFD_SOLVER_ODE_HEUN = 2 };
+int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                         int first_step, int n_run, int solver, int use_cache, int global_step0, void* stream);
+
 /* Tuning knobs for experiments and for the test suite's kernel variants (results stay within the parity tolerance,
  * only the kernel choice / tiling changes).  PER CALLING THREAD since round 4 (thread_local): a knob set on one thread
  * selects kernels for the launches THAT thread makes and is invisible to every other thread, so two samplers on two
@@ -495,7 +538,8 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
  *                                              hold; tests); "lstm_wave_chunk" = 0 | 1 | even n: cell steps per
  *                                              unit where the (tile, layer) pairs outnumber the CUs (0: chosen so that
  *                                              the rounds come out whole, 1: layers walked whole, n: forced);
- *   "fuse_tail" = 1 | 0                        unembedding inside the SDE-step kernel of ffd_sample_batch (no FreSca);
+ *   "fuse_tail" = 1 | 0                        unembedding inside the SDE-step kernel of ffd_sample_batch and the ODE tails
+ *                                              of ffd_sample_batch_ode (no FreSca);
  *   "attn_fused" = 1 | 0                       in-projection + attention in one kernel (k_qkv_attention*);
  *   "attn_kvq" = 1 | 0                         small-batch split attention: tile 0 = k | v, tile 1 = q, q projected for a
  *                                              workgroup's own q-tiles only (head_dim 6 / 8) | the whole head;
@@ -521,7 +565,7 @@ enum {
   FFD_K_OUTPROJ = 2,     /* k_linear_res_ln: out-projection + residual + LayerNorm1 */
   FFD_K_LSTM_REC = 3,    /* k_lstm_*: the L-step recurrence of one residual LSTM layer */
   FFD_K_LSTM_GATES = 4,  /* k_linear_rm: input-gate GEMM of one LSTM layer */
-  FFD_K_SDE = 5,         /* k_sde_step (or the fused unembed + SDE step) */
+  FFD_K_SDE = 5,         /* k_sde_step (or the fused unembed + SDE step); in ffd_sample_batch_ode the ODE tails */
   FFD_K_EMBED = 6,
   FFD_K_UNEMBED = 7,
   FFD_K_COUNT = 8
@@ -544,7 +588,8 @@ int ffd_kernel_timing_get(const ffd_ctx* ctx, int kernel_class, float* avg_ms_ou
 /* Algorithmic work of ONE launch of a kernel class at batch B (SURVEY 8(d) figures: FLOPs for the
  * MFMA-bound classes, HBM bytes for all); cache_hit = 1 for a pure-cache step.  Returns the name of the
  * kernel(s) the forward pass plans for that class under the calling thread's ffd_tune knobs (static
- * string), or NULL for a class the forward does not launch at this batch. */
+ * string), or NULL for a class the forward does not launch at this batch.  FFD_K_SDE names the tail of the loop entry
+ * the context ran last (Euler-Maruyama before any); for Heun, whose two tails differ, the mean of its two launches. */
 const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cache_hit, double* flops_out,
                             double* bytes_out);
 /* Time `iters` runs of layer 0's FFN at batch B as the forward pass plans it (the launches

@@ -1,0 +1,97 @@
+"""Cost of one interval of each solver of the fused sampling loop.
+
+    python3 tools/solver_bench.py [out.json] [--solvers euler_maruyama,ode_euler,ode_heun]
+                                             (default: profiles/solver_steps.json, all three)
+
+ECG (L 187, C 1, d 72, 10 layers) at B = 512 on a 21-point grid: 20 intervals for the ODE solvers
+(ffd_sample_batch_ode), the grid's first 20 steps for Euler-Maruyama (ffd_sample_batch, Philox noise on the device).
+One untimed trajectory per solver warms every shape; then 3 repetitions, the solvers alternating inside each so that a
+drift of the clocks shows as spread instead of as a difference.  A repetition times TRAJ trajectories of 20 intervals
+from a fresh prior draw between two device synchronisations and reports milliseconds per interval and per-sample score
+evaluations per second (Heun evaluates the network twice per interval).  What the numbers do NOT say: how many
+intervals a solver needs for a given sample quality -- that needs a trained checkpoint.
+"""
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+from fastfourierdiffusion_amd import _native as N  # noqa: E402
+
+B, INTERVALS, REPS, TRAJ = 512, 20, 3, 5
+EVALS = {"euler_maruyama": 1, "ode_euler": 1, "ode_heun": 2}
+
+
+def main() -> None:
+    args = sys.argv[1:]
+    solvers = list(EVALS)
+    if "--solvers" in args:
+        i = args.index("--solvers")
+        solvers = args[i + 1].split(",")
+        del args[i:i + 2]
+    assert all(s in EVALS for s in solvers), solvers
+    out_path = args[0] if args else os.path.join(ROOT, "profiles", "solver_steps.json")
+    assert torch.cuda.is_available(), "solver_bench needs an MI355X"
+    dev = torch.device("cuda", 0)
+    model, sch, _ = bench.build_model(dev, "ecg")
+    ctx = model._ctx()
+    lib, hdl = ctx.lib, ctx.handle
+    stream = N.current_stream_ptr(dev)
+    n = INTERVALS + 1
+    sch.set_timesteps(n)
+    ts_c = (C.c_float * n)(*sch.timesteps.tolist())
+    h = float(sch.step_size)
+    from fastfourierdiffusion_amd.sampling.sampler import DiffusionSampler
+
+    prior = DiffusionSampler(model, B, rng="philox", seed=42)
+
+    def trajectory(solver, X):
+        if solver == "euler_maruyama":
+            rc = lib.ffd_sample_batch(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, 42, 0, None, 0, 0, stream)
+        else:
+            code = {"ode_euler": N.FFD_SOLVER_ODE_EULER, "ode_heun": N.FFD_SOLVER_ODE_HEUN}[solver]
+            rc = lib.ffd_sample_batch_ode(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, code, 0, 0, stream)
+        N.check(rc, hdl, solver)
+
+    def timed(solver):
+        X = prior.sample_prior(B)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(TRAJ):
+            trajectory(solver, X)
+        torch.cuda.synchronize(dev)
+        assert torch.isfinite(X).all(), solver
+        return (time.perf_counter() - t0) * 1e3 / (TRAJ * INTERVALS)
+
+    for s in solvers:
+        timed(s)  # warm-up
+    reps = {s: [] for s in solvers}
+    for _ in range(REPS):
+        for s in solvers:
+            reps[s].append(timed(s))
+    res = {"device": torch.cuda.get_device_name(0), "workload": "ecg", "batch": B, "intervals": INTERVALS,
+           "repetitions": REPS, "trajectories_per_repetition": TRAJ, "solvers": {}}
+    for s in solvers:
+        ms = sorted(reps[s])[len(reps[s]) // 2]
+        res["solvers"][s] = {"ms_per_interval": round(ms, 4), "ms_per_interval_repetitions": [round(v, 4) for v in reps[s]],
+                             "score_evaluations_per_interval": EVALS[s],
+                             "sample_score_evaluations_per_s": round(EVALS[s] * B / (ms * 1e-3), 1)}
+    if "euler_maruyama" in solvers:
+        em = res["solvers"]["euler_maruyama"]["ms_per_interval"]
+        for s in solvers:
+            res["solvers"][s]["cost_vs_euler_maruyama_step"] = round(res["solvers"][s]["ms_per_interval"] / em, 4)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
