@@ -16,7 +16,8 @@ LIB_PATH = os.path.join(_HERE, "libffd.so")
 
 FFD_MODEL_TRANSFORMER, FFD_MODEL_LSTM, FFD_MODEL_MLP = 0, 1, 2
 FFD_SDE_VP, FFD_SDE_VE = 0, 1
-FFD_SOLVER_EULER_MARUYAMA, FFD_SOLVER_ODE_EULER, FFD_SOLVER_ODE_HEUN = 0, 1, 2
+FFD_SOLVER_EULER_MARUYAMA, FFD_SOLVER_ODE_EULER, FFD_SOLVER_ODE_HEUN, FFD_SOLVER_PC = 0, 1, 2, 3
+FFD_LANGEVIN_NORM_BATCH, FFD_LANGEVIN_NORM_SAMPLE = 0, 1
 # kernel classes (include/ffd.h FFD_K_*)
 K_FFN, K_ATTN, K_OUTPROJ, K_LSTM_REC, K_LSTM_GATES, K_SDE, K_EMBED, K_UNEMBED = range(8)
 
@@ -107,6 +108,9 @@ SIGNATURES = {
                                        C.c_int, _P]),
     "ffd_ode_heun_correct": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, _P, _P, C.c_double, C.c_float, C.c_int, C.c_int,
                                        C.c_int, _P]),
+    "ffd_langevin_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ffd_langevin_step": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, C.c_double, C.c_float, C.c_float, C.c_int, _P,
+                                    C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "ffd_prior": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_dft": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_idft": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
@@ -128,6 +132,8 @@ SIGNATURES = {
                                    C.c_uint64, _P, C.c_int, C.c_int, _P]),
     "ffd_sample_batch_ode": (C.c_int, [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, _P]),
+    "ffd_sample_batch_pc": (C.c_int, [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float,
+                                      C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int, C.c_int, _P]),
     "ffd_flops_per_sample_step": (C.c_double, [_P, C.c_int]),
     "ffd_ffn_flops_per_launch": (C.c_double, [_P, C.c_int]),
     "ffd_kernel_timing_begin": (C.c_int, [_P, C.c_uint32, C.c_int]),

@@ -107,6 +107,7 @@ struct ffd_ctx {
   Grow<float> score2, fwork;
   Grow<float> sm_noisy;  // the perturbed batch of ffd_sm_eval_batch
   Grow<float> ode_xp, ode_d1;  // Heun's predicted state and predictor drift (ffd_sample_batch_ode)
+  Grow<float> lv_work;  // the Langevin corrector's row squares, norms and step sizes (ffd_sample_batch_pc)
   int tail_solver = FFD_SOLVER_EULER_MARUYAMA;  // the loop entry that ran last (ffd_kernel_work names its FFD_K_SDE tail)
   // cache
   bool cache_enabled = false;
@@ -1318,6 +1319,81 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
   return FFD_OK;
 }
 
+// Predictor-corrector sampling: n_corrector Langevin corrector steps (ffd_langevin.hip), then the Euler-Maruyama
+// predictor of ffd_sample_batch, per reverse step.  Every evaluation after a step's first is a pure cache hit.
+int ffd_sample_batch_pc(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                        int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed,
+                        uint64_t sample_offset, const float* z_inject, int use_cache, int global_step0, void* stream) {
+  if (!ctx) return FFD_ERR_INVALID;
+  if (n_corrector < 0) return ctx->fail(FFD_ERR_INVALID, "n_corrector must be >= 0");
+  if (!(snr > 0.f)) return ctx->fail(FFD_ERR_INVALID, "snr must be > 0");
+  if (norm != FFD_LANGEVIN_NORM_BATCH && norm != FFD_LANGEVIN_NORM_SAMPLE)
+    return ctx->fail(FFD_ERR_INVALID, "unknown corrector norm %d", norm);
+  if (n_corrector == 0)
+    return ffd_sample_batch(ctx, x, B, timesteps, n_steps, step_size, first_step, n_run, seed, sample_offset, z_inject,
+                            use_cache, global_step0, stream);
+  int rc = check_ready(ctx, B);
+  if (rc) return rc;
+  if (!x || !timesteps || n_steps < 1 || first_step < 0 || n_run < 0 || first_step + n_run > n_steps)
+    return ctx->fail(FFD_ERR_INVALID, "bad argument to ffd_sample_batch_pc (n_steps=%d first=%d run=%d)", n_steps,
+                     first_step, n_run);
+  if ((int64_t)n_steps * n_corrector > 0x7FFFFFF0ll)
+    return ctx->fail(FFD_ERR_INVALID, "n_steps * n_corrector exceeds the corrector's Philox tag range");
+  if (!(step_size > 0.f)) return ctx->fail(FFD_ERR_INVALID, "step_size must be > 0 (sde.py:157,238)");
+  if (use_cache && !ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "use_cache without ffd_cache_enable");
+  if (use_cache && ctx->desc.kind != FFD_MODEL_TRANSFORMER)
+    return ctx->fail(FFD_ERR_UNSUPPORTED, "caching is only defined for the transformer backbone");
+  HIPCHECK(hipSetDevice(ctx->device));
+  if ((rc = ensure_workspace(ctx, B))) return rc;
+  const ffd_model_desc& m = ctx->desc;
+  const int L = m.max_len, C = m.n_channels, d = m.d_model;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = ensure_fresca_work(ctx, B))) return rc;
+  if ((rc = ensure(ctx, ctx->lv_work, (langevin_work_bytes(B, L) + sizeof(float) - 1) / sizeof(float)))) return rc;
+  if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
+  ctx->tail_solver = FFD_SOLVER_PC;
+  const size_t slab = (size_t)B * L * C;
+  const uint64_t elem_off = sample_offset * (uint64_t)L * C;
+  // the predictor's tail fuses under ffd_sample_batch's conditions (every slab of z_inject is aligned like the first)
+  const bool fuse_tail = tail_fusable(ctx) && (C % 4 != 0 || elem_off % 4 == 0) &&
+                         (C % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
+                         (!z_inject || C % 4 != 0 || (reinterpret_cast<uintptr_t>(z_inject) % 16 == 0 && slab % 4 == 0));
+  for (int j = 0; j < n_run; ++j) {
+    const int i = first_step + j;
+    const double t = (double)timesteps[i];
+    const float* zj = z_inject ? z_inject + (size_t)j * (n_corrector + 1) * slab : nullptr;
+    for (int k = 0; k <= n_corrector; ++k) {  // k == n_corrector: the predictor
+      const bool predictor = k == n_corrector;
+      int n_rec = use_cache ? 0 : -1;
+      float *crf_dst = nullptr, *crf_copy = nullptr;
+      if (use_cache && k == 0) {
+        const int gstep = global_step0 + j;
+        ctx->stats.current_step = gstep;
+        n_rec = ffd_host_gate(gstep, L, ctx->ccfg.K, ctx->ccfg.R);
+        if (ctx->crf_cap_on) crf_capture_targets(ctx, gstep, n_run - 1 - j, &crf_dst, &crf_copy);
+      }
+      const float *hidden, *score;
+      if ((rc = ode_evaluate(ctx, x, i, t, B, n_rec, crf_dst, crf_copy, predictor && fuse_tail, s, &hidden, &score)))
+        return rc;
+      if (use_cache && k == 0) ctx->stats.current_step = i;  // sampler.py:73-74 (Q4)
+      const float* zk = zj ? zj + (size_t)k * slab : nullptr;
+      if (!predictor)
+        TIMED(FFD_K_SDE, launch_langevin(x, score, zk, ctx->G_dev, langevin_alpha(m.sde, m.sde_a, m.sde_b, t, step_size),
+                                         (double)snr, norm, seed, elem_off,
+                                         0x80000000u + (uint32_t)i * (uint32_t)n_corrector + (uint32_t)k, B, L, C, nullptr,
+                                         ctx->lv_work.p, s));
+      else if (hidden)
+        TIMED(FFD_K_SDE, launch_unembed_sde(hidden, ctx->model.unembed_w, ctx->model.unembed_b, x, zk, ctx->G_dev,
+                                            sde_params(m.sde, m.sde_a, m.sde_b, t, step_size), seed, elem_off, (uint32_t)i,
+                                            B, L, C, d, s));
+      else
+        TIMED(FFD_K_SDE, launch_sde_step(x, score, zk, ctx->G_dev, sde_params(m.sde, m.sde_a, m.sde_b, t, step_size), seed,
+                                         elem_off, (uint32_t)i, B, L, C, s));
+    }
+  }
+  return FFD_OK;
+}
+
 // ---------------------------------------------------------------------------
 // benchmark introspection
 // ---------------------------------------------------------------------------
@@ -1457,7 +1533,14 @@ const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cac
       // The ODE tails of ffd_sample_batch_ode draw nothing.  Euler moves the same bytes; Heun's predictor reads x and
       // writes xp and d1 (3 C floats per row beside the score / hidden row), its corrector reads xp, x, d1 and
       // writes x (4 C): the mean of the two launches is given.
-      if (ctx->tail_solver == FFD_SOLVER_ODE_HEUN) {
+      // ffd_sample_batch_pc: the predictor's tail is ffd_sample_batch's; per corrector step the class also holds the
+      // three (batch norm: four) Langevin launches, which read the score twice and z never: 20 B per element.
+      if (ctx->tail_solver == FFD_SOLVER_PC) {
+        if (tail_fusable(ctx))
+          name = "k_unembed_mfma<sde> + k_lv_rowsq | k_lv_norms | k_lv_update", fl = 2.0 * M * C * d, by = 4.0 * M * (d + 2.0 * C);
+        else
+          name = "k_sde_step + k_lv_rowsq | k_lv_norms | k_lv_update", by = 12.0 * M * C;
+      } else if (ctx->tail_solver == FFD_SOLVER_ODE_HEUN) {
         if (tail_fusable(ctx))
           name = "k_unembed_ode<heun predict | correct>", fl = 2.0 * M * C * d, by = 4.0 * M * (d + 3.5 * C);
         else

@@ -260,6 +260,15 @@ hipError_t launch_ode_step(int tail, float* x, const float* score, float* xp, fl
 hipError_t launch_unembed_ode(int tail, const float* h, const float* Wu, const float* bu, float* x, float* xp, float* d1,
                               const float* G, SdeParams p, int B, int L, int C, int D, hipStream_t s);
 
+// The Langevin corrector (ffd_langevin.hip; include/ffd.h ffd_langevin_step): row squares, step size, update, four
+// launches with the batch norm and three with the sample norm.  alpha = langevin_alpha at the evaluation's time;
+// work = langevin_work_bytes(B, L) bytes, 16-byte aligned; eps_out nullptr or (B).
+size_t langevin_work_bytes(int B, int L);
+double langevin_alpha(int sde, double a, double b, double t, float step_size);
+hipError_t launch_langevin(float* x, const float* score, const float* z, const float* G, double alpha, double snr,
+                           int norm, uint64_t seed, uint64_t elem_offset, uint32_t tag, int B, int L, int C,
+                           float* eps_out, void* work, hipStream_t s);
+
 // Denoising score-matching loss (ffd_loss.hip; losses.py:54-125).  Sample b of the call is global sample
 // sample_offset + b: with z == nullptr both kernels take the draw of global element g from slot g & 3 of Philox block
 // g >> 2 under SM_TAG_NOISE, so the loss regenerates what the perturbation drew.

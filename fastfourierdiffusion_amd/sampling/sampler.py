@@ -22,12 +22,26 @@ Solver (extension): ``solver="euler_maruyama"`` (default) is the reference's int
 N-point grid, ending exactly at ``eps``; Heun evaluates the model twice per interval and is second order.  Batching,
 cache lifecycle and prior are unchanged; the global step of the cache gate counts intervals.
 
+Corrector (extension): ``corrector_steps=n > 0`` makes every Euler-Maruyama step a predictor-corrector step in
+score_sde's order (``ffd_sample_batch_pc``): n Langevin corrector steps at t_i (``SDE.step_correct``: each its own score
+evaluation and its own draw, signal-to-noise ratio ``snr``), then the unchanged predictor at t_i, whose noise is the
+noise it has without correctors.  ``rng="torch"`` and ``inject_noise`` consume n + 1 draws per step in that order.  With
+the cache the first evaluation of a step follows the gate and every later one is a pure hit.  No claim about sample
+quality is made: there is no trained checkpoint to measure it on.
+
 Two batch-wide statistics of the reference make the SAMPLES depend on the batching all the
 same, sharded or not (they are properties of the reference's algorithm, reproduced here per
 batch / per shard): the E2-CRF tables come from the batch's element 0 (caching.py:326-328), and
 FreSca's default ``energy`` cutoff is derived from ``|rfft(score)|.mean(dim=(0, 2))`` over the
-local batch (fresca.py:150-158).  Without the cache and with FreSca off or on its ``spatial``
-cutoff a sharded philox run reproduces the unsharded one: the same noise bit for bit, the samples to fp32 rounding
+local batch (fresca.py:150-158).  The corrector's default ``corrector_norm="batch"`` is a third: its step size
+comes from the norms of score and noise averaged over the local batch, as in score_sde and ``diffusers``.
+``corrector_norm="sample"`` takes them per sample (the paper's form) and is the only shard-invariant one, at the price
+of a stationary variance inflated by O(1 / (L C)): the step is large exactly for the samples near the mode.  Measured in
+float64 on a Gaussian target (VE variance at t = 0.5, Fourier G, snr 0.16, 150 steps, 4096 samples), ratio to the exact
+variance: L x C = 20 x 1: 1.24-1.25 (sample) against 1.02-1.03 (batch); 20 x 4: 1.07 / 1.02; 187 x 1: 1.04-1.05 /
+1.02-1.03; 5 x 1: 2.2 / 1.01-1.05 (1 + eps / 2v ~ 1.025 is the discretisation's own bias).
+Without the cache, with FreSca off or on its ``spatial`` cutoff, and without correctors or with the ``sample`` norm,
+a sharded philox run reproduces the unsharded one: the same noise bit for bit, the samples to fp32 rounding
 (a few 1e-7 relative per score evaluation; the contract the tests hold is 1e-5 of the max-norm over a trajectory) --
 not bit for bit, because the kernels a batch size selects differ in summation order (the F-split small-batch FFN pair,
 the key-split attention, the 32-row-per-wave large-batch FFN, the batch-tiled LSTM recurrence; csrc/ffd_small.hip,
@@ -49,6 +63,7 @@ from ..utils.dataclasses import DiffusableBatch
 # solver name -> libffd's FFD_SOLVER_*
 SOLVERS = {"euler_maruyama": N.FFD_SOLVER_EULER_MARUYAMA, "ode_euler": N.FFD_SOLVER_ODE_EULER,
            "ode_heun": N.FFD_SOLVER_ODE_HEUN}
+CORRECTOR_NORMS = {"batch": N.FFD_LANGEVIN_NORM_BATCH, "sample": N.FFD_LANGEVIN_NORM_SAMPLE}
 
 
 class DiffusionSampler:
@@ -58,7 +73,9 @@ class DiffusionSampler:
                  fresca_cutoff_strategy: Literal["spatial", "energy"] = "energy",
                  rng: Literal["torch", "philox"] = "torch", seed: int = 42, sample_offset: int = 0,
                  z_chunk_steps: int = 50,
-                 solver: Literal["euler_maruyama", "ode_euler", "ode_heun"] = "euler_maruyama") -> None:
+                 solver: Literal["euler_maruyama", "ode_euler", "ode_heun"] = "euler_maruyama",
+                 corrector_steps: int = 0, snr: float = 0.16,
+                 corrector_norm: Literal["batch", "sample"] = "batch") -> None:
         self.score_model = score_model
         self.noise_scheduler = score_model.noise_scheduler
         self.sample_batch_size = sample_batch_size
@@ -86,6 +103,18 @@ class DiffusionSampler:
         if solver not in SOLVERS:
             raise ValueError(f"solver must be one of {sorted(SOLVERS)}, got {solver!r}")
         self.solver = solver
+        if corrector_steps < 0:
+            raise ValueError(f"corrector_steps must be >= 0, got {corrector_steps!r}")
+        if not snr > 0:
+            raise ValueError(f"snr must be > 0, got {snr!r}")
+        if corrector_norm not in CORRECTOR_NORMS:
+            raise ValueError(f"corrector_norm must be one of {sorted(CORRECTOR_NORMS)}, got {corrector_norm!r}")
+        if corrector_steps > 0 and solver != "euler_maruyama":
+            raise ValueError("the ODE solvers are deterministic given the prior: corrector_steps > 0 needs "
+                             "solver='euler_maruyama'")
+        self.corrector_steps = int(corrector_steps)
+        self.snr = float(snr)
+        self.corrector_norm = corrector_norm
         self._injected = None
 
     def inject_noise(self, draws) -> None:
@@ -111,6 +140,8 @@ class DiffusionSampler:
         assert t_lo == t_hi  # sampler.py:59-60
         sch = self.noise_scheduler
         t_next = self._heun_next_time(timesteps[0]) if self.solver == "ode_heun" else None
+        if self.corrector_steps > 0:
+            return self._predictor_corrector_step(batch, t_lo, step, recompute_tokens)
         score = self._evaluate_score(batch, t_lo, step, recompute_tokens, update_crf=True)
         if self.solver == "euler_maruyama":
             output = sch.step(model_output=score, timestep=timesteps[0].item(), sample=X)
@@ -126,6 +157,25 @@ class DiffusionSampler:
         X_prev = output.prev_sample
         assert isinstance(X_prev, torch.Tensor)
         return X_prev
+
+    def _predictor_corrector_step(self, batch: DiffusableBatch, t: float, step: int,
+                                  recompute_tokens: Optional[set]) -> torch.Tensor:
+        """``corrector_steps`` Langevin corrector steps at ``t``, then the Euler-Maruyama predictor at ``t`` on a fresh
+        evaluation.  The step's first evaluation takes ``recompute_tokens`` and updates the CRF; the later ones
+        recompute nothing.  Injected noise is consumed one draw per corrector, then the predictor's."""
+        sch = self.noise_scheduler
+        X = batch.X
+        for k in range(self.corrector_steps + 1):
+            cur = DiffusableBatch(X=X, y=batch.y, timesteps=batch.timesteps)
+            first = k == 0
+            score = self._evaluate_score(cur, t, step, recompute_tokens if first or recompute_tokens is None else set(),
+                                         update_crf=first)
+            noise = self._next_injected(X.shape, X.device) if self._injected is not None else None
+            if k < self.corrector_steps:
+                X = sch.step_correct(score, X, self.snr, t, noise=noise, norm=self.corrector_norm).prev_sample
+            else:
+                X = sch.step(model_output=score, timestep=batch.timesteps[0].item(), sample=X, noise=noise).prev_sample
+        return X
 
     def _evaluate_score(self, batch: DiffusableBatch, t: float, step: int, recompute_tokens: Optional[set],
                         update_crf: bool) -> torch.Tensor:
@@ -207,10 +257,11 @@ class DiffusionSampler:
                 while done < n_iter:
                     n = n_iter - done
                     z_ptr = None
+                    draws = self.corrector_steps + 1  # per step: the correctors' in order, then the predictor's
                     if not ode and (self.rng == "torch" or self._injected is not None):
-                        n = min(n, max(1, self.z_chunk_steps))
-                        z = torch.empty((n,) + tuple(X.shape), device=device, dtype=torch.float32)
-                        for i in range(n):  # one randn_like per step, as the reference consumes its generator
+                        n = min(n, max(1, self.z_chunk_steps // draws))  # the z buffer keeps its size
+                        z = torch.empty((n * draws,) + tuple(X.shape), device=device, dtype=torch.float32)
+                        for i in range(n * draws):  # one randn_like per draw, as the reference consumes its generator
                             if self._injected is not None:
                                 z[i].copy_(self._next_injected(X.shape, device))
                             else:
@@ -221,6 +272,13 @@ class DiffusionSampler:
                                                           step_size, done, n, SOLVERS[self.solver], use_cache,
                                                           (global_step + done) if use_cache else 0, stream)
                         N.check(rc, ctx.handle, "ffd_sample_batch_ode")
+                    elif self.corrector_steps > 0:
+                        rc = ctx.lib.ffd_sample_batch_pc(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
+                                                         step_size, done, n, self.corrector_steps, self.snr,
+                                                         CORRECTOR_NORMS[self.corrector_norm], self.seed, sample_cursor,
+                                                         z_ptr, use_cache, (global_step + done) if use_cache else 0,
+                                                         stream)
+                        N.check(rc, ctx.handle, "ffd_sample_batch_pc")
                     else:
                         rc = ctx.lib.ffd_sample_batch(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
                                                       step_size, done, n, self.seed, sample_cursor, z_ptr, use_cache,

@@ -177,6 +177,43 @@ class SDE(abc.ABC):
         N.check(rc, None, "ffd_ode_heun_correct")
         return SamplingOutput(prev_sample=x)
 
+    # -- Langevin corrector (extension: predictor-corrector sampling) ----------
+    def step_correct(self, model_output: torch.Tensor, sample: torch.Tensor, snr: float, timestep: float,
+                     noise: Optional[torch.Tensor] = None, norm: str = "batch", *, seed: Optional[int] = None,
+                     sample_offset: int = 0, tag: int = 0x80000000, return_step_sizes: bool = False):
+        """One Langevin corrector step at ``timestep`` (Song et al. 2021, Algorithms 4 / 5; the argument order of
+        ``diffusers``' ``ScoreSdeVeScheduler.step_correct``): x + eps G^2 score + sqrt(2 eps) G z with
+        eps = 2 alpha (snr ||G z|| / ||G^2 score||)^2, alpha = 1 (VE) or max(1 - beta(t) step_size, 0) (VP; it needs
+        ``timestep``).  ``norm="batch"`` takes both norms as means over the batch (score_sde / diffusers: the step of a
+        sample depends on its batch), ``norm="sample"`` per sample (the paper's form; its stationary variance is
+        biased by O(1 / (L C))).  ``noise`` injects z; by default z = torch.randn_like(sample) as
+        in ``step``; with ``seed`` the draw is made on the device instead (Philox stream ``tag``, global sample index
+        ``sample_offset`` + b).  ``return_step_sizes`` adds the (B) tensor of eps to the result."""
+        if norm not in ("batch", "sample"):
+            raise ValueError(f"norm must be 'batch' or 'sample', got {norm!r}")
+        if not snr > 0:
+            raise ValueError(f"snr must be > 0, got {snr!r}")
+        sample, model_output, G, stream = self._ode_args(sample, model_output)
+        B, L, Cn = sample.shape
+        if noise is not None:
+            z = N.require_gpu_tensor(noise, "noise")
+            assert z.shape == sample.shape
+        else:
+            z = torch.randn_like(sample) if seed is None else None
+        x = sample.clone()
+        lib = N.lib()
+        work = torch.empty(int(lib.ffd_langevin_work_bytes(B, L)) // 8 + 1, device=sample.device, dtype=torch.float64)
+        eps = torch.empty(B, device=sample.device, dtype=torch.float32)
+        desc = self._desc()
+        rc = lib.ffd_langevin_step(C.byref(desc), x.data_ptr(), model_output.data_ptr(), G, float(timestep),
+                                   float(self.step_size), float(snr),
+                                   N.FFD_LANGEVIN_NORM_BATCH if norm == "batch" else N.FFD_LANGEVIN_NORM_SAMPLE,
+                                   z.data_ptr() if z is not None else None, int(seed or 0), int(sample_offset), int(tag),
+                                   B, L, Cn, eps.data_ptr(), work.data_ptr(), stream)
+        N.check(rc, None, "ffd_langevin_step")
+        out = SamplingOutput(prev_sample=x)
+        return (out, eps) if return_step_sizes else out
+
 
 class VEScheduler(SDE):
     """sde.py:90-165."""

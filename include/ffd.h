@@ -201,6 +201,43 @@ int ffd_ode_heun_correct(const ffd_sde_desc* sde, float* x, const float* x_pred,
                          const float* drift, const float* G, double t_next, float step_size, int B, int L, int C,
                          void* stream);
 
+/* ---- Langevin corrector (an extension: predictor-corrector sampling, Song et al. 2021, Algorithms 4 / 5) ----
+ * Forward SDE dx = f dt + g(t) diag(G) dw exactly as in ffd_sde_step.  One corrector step at time t on sample b, with
+ * the score s = s(x, t) and a draw z ~ N(0, I):
+ *     u = G_l^2 s                      (the score preconditioned by the SDE's noise covariance; G_l = 1: the paper's)
+ *     w = G_l z                        (noise of the SDE's own covariance)
+ *     n_u[b] = ||u[b]||_2,  n_w[b] = ||w[b]||_2                    (over the L C elements of sample b)
+ *     FFD_LANGEVIN_NORM_SAMPLE:  eps[b] = 2 alpha (snr n_w[b] / n_u[b])^2                  (the paper's form)
+ *     FFD_LANGEVIN_NORM_BATCH :  eps[b] = 2 alpha (snr mean_b(n_w) / mean_b(n_u))^2        (score_sde / diffusers)
+ *     x <- x + eps[b] u + sqrt(2 eps[b]) w
+ *     alpha = 1 (VE);  alpha = max(1 - beta(t) step_size, 0) (VP: score_sde's 1 - beta_i, clamped for coarse grids)
+ *     n_u[b] == 0 (batch: mean_b(n_u) == 0):  eps = 0 and the sample is left as it is (never inf / NaN).
+ * With G = 1 this is the published algorithm; with Fourier G it is Langevin preconditioned by diag(G^2), which leaves
+ * the same marginal invariant.  The batch norm makes a sample depend on its batch; the sample norm does not, but its
+ * stationary variance carries an O(1 / (L C)) bias.
+ * Operation order.  Per element, every product / sum a separate fp32 rounding (no FMA contraction):
+ *     g2 = G_l G_l, u = g2 s, w = G_l z;  x' = (x + eps u) + se w,  se = (float) sqrt(2 (double) eps).
+ * Norms: the terms are the fp32 squares u u and w w; a row's C terms are added in fp64 with c ascending; a sample's L
+ * row sums are added in fp64 in an order fixed by l alone (partial k = rows k, k + 256, ... in order, then a pairwise
+ * tree that folds the upper half of the 256 partials onto the lower, 128, 64, ... 1); the square root is taken in
+ * fp64; mean_b adds the B norms in the same fixed order over b and divides by B; eps = (2 alpha) (r r), r = (snr n_w) /
+ * n_u in fp64, rounded once to fp32.  No atomics: the result is bit-identical from run to run, and n_u[b], n_w[b] do
+ * not depend on B or on b.
+ * z == NULL draws on the device: element i of sample b takes slot g & 3 of Philox block g >> 2, g = (sample_offset + b)
+ * L C + i, under stream tag `tag`; the update REGENERATES the draw the norms measured, so no z buffer exists.
+ * ffd_sample_batch_pc uses tag 0x80000000 + step * n_corrector + j (tags below 2^31 are the predictor's step indices,
+ * 0xFFFFFFFD .. 0xFFFFFFFF are taken by the loss and the prior).
+ * In place on x, context-free, stream ordered, no host synchronisation.  work: caller-owned device scratch of
+ * ffd_langevin_work_bytes(B, L) bytes, 16-byte aligned, free again when the call's work on the stream is done.
+ * eps_out: NULL or (B) floats, receives eps.
+ * FFD_ERR_INVALID before any device work: a null pointer (z and eps_out excepted), B, L, C < 1, snr <= 0, step_size <= 0,
+ * an unknown norm, x == score, a misaligned work. */
+enum { FFD_LANGEVIN_NORM_BATCH = 0, FFD_LANGEVIN_NORM_SAMPLE = 1 };
+size_t ffd_langevin_work_bytes(int B, int L);
+int ffd_langevin_step(const ffd_sde_desc* sde, float* x, const float* score, const float* G, double t, float step_size,
+                      float snr, int norm, const float* z, uint64_t seed, uint64_t sample_offset, uint32_t tag, int B,
+                      int L, int C, float* eps_out, void* work, void* stream);
+
 /* SDE.prior_sampling (sde.py:79-87, 125-127): x <- G (.) z  (VE: * sigma_max);
  * z == NULL draws on device (Philox stream tag 0xFFFFFFFF). */
 int ffd_prior(const ffd_sde_desc* sde, float* x, const float* z, const float* G, uint64_t seed,
@@ -489,6 +526,29 @@ enum { FFD_SOLVER_EULER_MARUYAMA = 0, FFD_SOLVER_ODE_EULER = 1, FFD_SOLVER_ODE_H
 int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
                          int first_step, int n_run, int solver, int use_cache, int global_step0, void* stream);
 
+/* Predictor-corrector sampling (see ffd_langevin_step): ffd_sample_batch with n_corrector Langevin corrector steps in
+ * front of every Euler-Maruyama step, in score_sde's order.  Reverse step i:
+ *   1. n_corrector corrector steps at timesteps[i], each with its own score evaluation and its own draw (stream tag
+ *      0x80000000 + i * n_corrector + j for corrector j);
+ *   2. the unchanged Euler-Maruyama predictor at timesteps[i] on a fresh score evaluation (stream tag i: its noise is
+ *      the noise of ffd_sample_batch).
+ * n_corrector == 0 IS ffd_sample_batch (the call is forwarded).  Arguments as there, and
+ *   snr, norm  the corrector's signal-to-noise ratio (> 0) and FFD_LANGEVIN_NORM_*;
+ *   z_inject   NULL or (n_run, n_corrector + 1, B, L, C): per step the correctors' draws in order, then the predictor's;
+ *   use_cache  the FIRST evaluation of step i follows ffd_host_gate at global step global_step0 + (i - first_step) and
+ *              feeds the CRF capture; every later evaluation of the step, the predictor's included, is a pure cache
+ *              hit (n_recompute = 0): Heun's rule of ffd_sample_batch_ode generalised.  Tables and counters are
+ *              those of ffd_score_forward_cached calls of these sizes in this order.
+ *   FreSca     applied to every evaluated score with h(timesteps[i]).
+ * The corrector reads its score from HBM (three small launches behind the unembedding); the predictor keeps the fused
+ * tail ("fuse_tail").
+ * FFD_ERR_INVALID before any device work: as ffd_sample_batch, and n_corrector < 0, snr <= 0, an unknown norm,
+ * n_steps * n_corrector > 0x7FFFFFF0. */
+enum { FFD_SOLVER_PC = 3 };
+int ffd_sample_batch_pc(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                        int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed,
+                        uint64_t sample_offset, const float* z_inject, int use_cache, int global_step0, void* stream);
+
 /* Tuning knobs for experiments and for the test suite's kernel variants (results stay within the parity tolerance,
  * only the kernel choice / tiling changes).  PER CALLING THREAD since round 4 (thread_local): a knob set on one thread
  * selects kernels for the launches THAT thread makes and is invisible to every other thread, so two samplers on two
@@ -538,8 +598,9 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
  *                                              hold; tests); "lstm_wave_chunk" = 0 | 1 | even n: cell steps per
  *                                              unit where the (tile, layer) pairs outnumber the CUs (0: chosen so that
  *                                              the rounds come out whole, 1: layers walked whole, n: forced);
- *   "fuse_tail" = 1 | 0                        unembedding inside the SDE-step kernel of ffd_sample_batch and the ODE tails
- *                                              of ffd_sample_batch_ode (no FreSca);
+ *   "fuse_tail" = 1 | 0                        unembedding inside the SDE-step kernel of ffd_sample_batch (and of the
+ *                                              predictor of ffd_sample_batch_pc) and the ODE tails of
+ *                                              ffd_sample_batch_ode (no FreSca);
  *   "attn_fused" = 1 | 0                       in-projection + attention in one kernel (k_qkv_attention*);
  *   "attn_kvq" = 1 | 0                         small-batch split attention: tile 0 = k | v, tile 1 = q, q projected for a
  *                                              workgroup's own q-tiles only (head_dim 6 / 8) | the whole head;
@@ -565,7 +626,8 @@ enum {
   FFD_K_OUTPROJ = 2,     /* k_linear_res_ln: out-projection + residual + LayerNorm1 */
   FFD_K_LSTM_REC = 3,    /* k_lstm_*: the L-step recurrence of one residual LSTM layer */
   FFD_K_LSTM_GATES = 4,  /* k_linear_rm: input-gate GEMM of one LSTM layer */
-  FFD_K_SDE = 5,         /* k_sde_step (or the fused unembed + SDE step); in ffd_sample_batch_ode the ODE tails */
+  FFD_K_SDE = 5,         /* k_sde_step (or the fused unembed + SDE step); in ffd_sample_batch_ode the ODE tails, in
+                          * ffd_sample_batch_pc also the corrector's launches */
   FFD_K_EMBED = 6,
   FFD_K_UNEMBED = 7,
   FFD_K_COUNT = 8
@@ -589,7 +651,8 @@ int ffd_kernel_timing_get(const ffd_ctx* ctx, int kernel_class, float* avg_ms_ou
  * MFMA-bound classes, HBM bytes for all); cache_hit = 1 for a pure-cache step.  Returns the name of the
  * kernel(s) the forward pass plans for that class under the calling thread's ffd_tune knobs (static
  * string), or NULL for a class the forward does not launch at this batch.  FFD_K_SDE names the tail of the loop entry
- * the context ran last (Euler-Maruyama before any); for Heun, whose two tails differ, the mean of its two launches. */
+ * the context ran last (Euler-Maruyama before any); for Heun, whose two tails differ, the mean of its two launches; after
+ * ffd_sample_batch_pc the predictor's tail (its work figures) followed by the corrector's kernels. */
 const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cache_hit, double* flops_out,
                             double* bytes_out);
 /* Time `iters` runs of layer 0's FFN at batch B as the forward pass plans it (the launches

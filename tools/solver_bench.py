@@ -2,6 +2,9 @@
 
     python3 tools/solver_bench.py [out.json] [--solvers euler_maruyama,ode_euler,ode_heun]
                                              (default: profiles/solver_steps.json, all three)
+    python3 tools/solver_bench.py pc [out.json]
+                                             (predictor-corrector: euler_maruyama, pc1, pc2, pc1_sample ->
+                                             profiles/pc_steps.json)
 
 ECG (L 187, C 1, d 72, 10 layers) at B = 512 on a 21-point grid: 20 intervals for the ODE solvers
 (ffd_sample_batch_ode), the grid's first 20 steps for Euler-Maruyama (ffd_sample_batch, Philox noise on the device).
@@ -10,6 +13,10 @@ drift of the clocks shows as spread instead of as a difference.  A repetition ti
 from a fresh prior draw between two device synchronisations and reports milliseconds per interval and per-sample score
 evaluations per second (Heun evaluates the network twice per interval).  What the numbers do NOT say: how many
 intervals a solver needs for a given sample quality -- that needs a trained checkpoint.
+
+``pc``: ffd_sample_batch_pc on the same grid with 1 and 2 Langevin corrector steps per reverse step (batch norm; pc1_sample:
+1 step, sample norm), Euler-Maruyama measured in the same run.  A corrector step is one more score evaluation plus
+the corrector's three (batch norm: four) small launches, so pcN is expected near (1 + N) Euler-Maruyama steps.
 """
 import ctypes as C
 import json
@@ -25,18 +32,25 @@ import bench  # noqa: E402
 from fastfourierdiffusion_amd import _native as N  # noqa: E402
 
 B, INTERVALS, REPS, TRAJ = 512, 20, 3, 5
-EVALS = {"euler_maruyama": 1, "ode_euler": 1, "ode_heun": 2}
+EVALS = {"euler_maruyama": 1, "ode_euler": 1, "ode_heun": 2, "pc1": 2, "pc2": 3, "pc1_sample": 2}
+PC = {"pc1": (1, N.FFD_LANGEVIN_NORM_BATCH), "pc2": (2, N.FFD_LANGEVIN_NORM_BATCH),
+      "pc1_sample": (1, N.FFD_LANGEVIN_NORM_SAMPLE)}
+SNR = 0.16
 
 
 def main() -> None:
     args = sys.argv[1:]
-    solvers = list(EVALS)
+    solvers = ["euler_maruyama", "ode_euler", "ode_heun"]
+    default_out = "solver_steps.json"
+    if args and args[0] == "pc":
+        solvers, default_out = ["euler_maruyama", "pc1", "pc2", "pc1_sample"], "pc_steps.json"
+        del args[0]
     if "--solvers" in args:
         i = args.index("--solvers")
         solvers = args[i + 1].split(",")
         del args[i:i + 2]
     assert all(s in EVALS for s in solvers), solvers
-    out_path = args[0] if args else os.path.join(ROOT, "profiles", "solver_steps.json")
+    out_path = args[0] if args else os.path.join(ROOT, "profiles", default_out)
     assert torch.cuda.is_available(), "solver_bench needs an MI355X"
     dev = torch.device("cuda", 0)
     model, sch, _ = bench.build_model(dev, "ecg")
@@ -54,6 +68,9 @@ def main() -> None:
     def trajectory(solver, X):
         if solver == "euler_maruyama":
             rc = lib.ffd_sample_batch(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, 42, 0, None, 0, 0, stream)
+        elif solver in PC:
+            rc = lib.ffd_sample_batch_pc(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, PC[solver][0], SNR, PC[solver][1], 42,
+                                         0, None, 0, 0, stream)
         else:
             code = {"ode_euler": N.FFD_SOLVER_ODE_EULER, "ode_heun": N.FFD_SOLVER_ODE_HEUN}[solver]
             rc = lib.ffd_sample_batch_ode(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, code, 0, 0, stream)
