@@ -18,6 +18,7 @@ FFD_MODEL_TRANSFORMER, FFD_MODEL_LSTM, FFD_MODEL_MLP = 0, 1, 2
 FFD_SDE_VP, FFD_SDE_VE = 0, 1
 FFD_SOLVER_EULER_MARUYAMA, FFD_SOLVER_ODE_EULER, FFD_SOLVER_ODE_HEUN, FFD_SOLVER_PC = 0, 1, 2, 3
 FFD_LANGEVIN_NORM_BATCH, FFD_LANGEVIN_NORM_SAMPLE = 0, 1
+FFD_COND_FREQUENCY, FFD_COND_TIME = 0, 1
 # kernel classes (include/ffd.h FFD_K_*)
 K_FFN, K_ATTN, K_OUTPROJ, K_LSTM_REC, K_LSTM_GATES, K_SDE, K_EMBED, K_UNEMBED = range(8)
 
@@ -46,6 +47,12 @@ class FrescaCfg(C.Structure):
 class CrfCaptureCfg(C.Structure):
     _fields_ = [("ring", C.c_void_p), ("n_slots", C.c_int32), ("every", C.c_int32), ("last", C.c_void_p),
                 ("last_every", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CondCfg(C.Structure):
+    """ffd_cond_cfg: the observation of ffd_sample_batch_cond (device pointers; std None or (L, C))."""
+    _fields_ = [("obs", C.c_void_p), ("mask", C.c_void_p), ("std", C.c_void_p), ("obs_batch", C.c_int32),
+                ("domain", C.c_int32), ("final_replace", C.c_int32), ("reserved", C.c_int32)]
 
 
 class CacheCfg(C.Structure):
@@ -111,6 +118,8 @@ SIGNATURES = {
     "ffd_langevin_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "ffd_langevin_step": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, C.c_double, C.c_float, C.c_float, C.c_int, _P,
                                     C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "ffd_cond_project": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, _P, _P, C.c_double, C.c_int, _P, C.c_uint64, C.c_uint64,
+                                   C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_prior": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_dft": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_idft": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
@@ -134,6 +143,8 @@ SIGNATURES = {
                                        C.c_int, _P]),
     "ffd_sample_batch_pc": (C.c_int, [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float,
                                       C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int, C.c_int, _P]),
+    "ffd_sample_batch_cond": (C.c_int, [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float,
+                                        C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int, C.c_int, C.POINTER(CondCfg), _P]),
     "ffd_flops_per_sample_step": (C.c_double, [_P, C.c_int]),
     "ffd_ffn_flops_per_launch": (C.c_double, [_P, C.c_int]),
     "ffd_kernel_timing_begin": (C.c_int, [_P, C.c_uint32, C.c_int]),

@@ -1321,25 +1321,31 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
 
 // Predictor-corrector sampling: n_corrector Langevin corrector steps (ffd_langevin.hip), then the Euler-Maruyama
 // predictor of ffd_sample_batch, per reverse step.  Every evaluation after a step's first is a pure cache hit.
-int ffd_sample_batch_pc(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
-                        int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed,
-                        uint64_t sample_offset, const float* z_inject, int use_cache, int global_step0, void* stream) {
-  if (!ctx) return FFD_ERR_INVALID;
-  if (n_corrector < 0) return ctx->fail(FFD_ERR_INVALID, "n_corrector must be >= 0");
-  if (!(snr > 0.f)) return ctx->fail(FFD_ERR_INVALID, "snr must be > 0");
-  if (norm != FFD_LANGEVIN_NORM_BATCH && norm != FFD_LANGEVIN_NORM_SAMPLE)
-    return ctx->fail(FFD_ERR_INVALID, "unknown corrector norm %d", norm);
-  if (n_corrector == 0)
-    return ffd_sample_batch(ctx, x, B, timesteps, n_steps, step_size, first_step, n_run, seed, sample_offset, z_inject,
-                            use_cache, global_step0, stream);
+// cond != nullptr (ffd_sample_batch_cond): one projection onto the observation behind every update, and z_inject
+// holds two draws per update (its own, then the projection's).  The arguments' first checks are the callers'.
+static int pc_loop(ffd_ctx* ctx, const char* who, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                   int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed, uint64_t sample_offset,
+                   const float* z_inject, int use_cache, int global_step0, const ffd_cond_cfg* cond, void* stream) {
   int rc = check_ready(ctx, B);
   if (rc) return rc;
   if (!x || !timesteps || n_steps < 1 || first_step < 0 || n_run < 0 || first_step + n_run > n_steps)
-    return ctx->fail(FFD_ERR_INVALID, "bad argument to ffd_sample_batch_pc (n_steps=%d first=%d run=%d)", n_steps,
-                     first_step, n_run);
-  if ((int64_t)n_steps * n_corrector > 0x7FFFFFF0ll)
+    return ctx->fail(FFD_ERR_INVALID, "bad argument to %s (n_steps=%d first=%d run=%d)", who, n_steps, first_step, n_run);
+  if (!cond && (int64_t)n_steps * n_corrector > 0x7FFFFFF0ll)
     return ctx->fail(FFD_ERR_INVALID, "n_steps * n_corrector exceeds the corrector's Philox tag range");
+  if (cond) {
+    if ((int64_t)n_steps * ((int64_t)n_corrector + 1) > 0x3FFFFFF0ll)
+      return ctx->fail(FFD_ERR_INVALID, "n_steps * (n_corrector + 1) exceeds the projection's Philox tag range");
+    if (!cond->obs || !cond->mask) return ctx->fail(FFD_ERR_INVALID, "conditioning needs obs and mask");
+    if (cond->obs_batch != 1 && cond->obs_batch != B)
+      return ctx->fail(FFD_ERR_INVALID, "obs_batch must be 1 or B, got %d", cond->obs_batch);
+    if (cond->domain != FFD_COND_FREQUENCY && cond->domain != FFD_COND_TIME)
+      return ctx->fail(FFD_ERR_INVALID, "unknown conditioning domain %d", cond->domain);
+    if (cond->domain == FFD_COND_TIME && cond->std) return ctx->fail(FFD_ERR_INVALID, "std with the time domain");
+    if (x == cond->obs || x == cond->mask) return ctx->fail(FFD_ERR_INVALID, "x aliases obs or mask");
+  }
   if (!(step_size > 0.f)) return ctx->fail(FFD_ERR_INVALID, "step_size must be > 0 (sde.py:157,238)");
+  if (cond && cond->domain == FFD_COND_FREQUENCY && !cond_len_supported(ctx->desc.max_len))
+    return ctx->fail(FFD_ERR_UNSUPPORTED, "frequency-domain conditioning takes 2 <= L <= 4096");
   if (use_cache && !ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "use_cache without ffd_cache_enable");
   if (use_cache && ctx->desc.kind != FFD_MODEL_TRANSFORMER)
     return ctx->fail(FFD_ERR_UNSUPPORTED, "caching is only defined for the transformer backbone");
@@ -1349,19 +1355,31 @@ int ffd_sample_batch_pc(ffd_ctx* ctx, float* x, int B, const float* timesteps, i
   const int L = m.max_len, C = m.n_channels, d = m.d_model;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = ensure_fresca_work(ctx, B))) return rc;
-  if ((rc = ensure(ctx, ctx->lv_work, (langevin_work_bytes(B, L) + sizeof(float) - 1) / sizeof(float)))) return rc;
+  if (n_corrector > 0 &&
+      (rc = ensure(ctx, ctx->lv_work, (langevin_work_bytes(B, L) + sizeof(float) - 1) / sizeof(float))))
+    return rc;
   if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
-  ctx->tail_solver = FFD_SOLVER_PC;
+  ctx->tail_solver = n_corrector > 0 ? FFD_SOLVER_PC : FFD_SOLVER_EULER_MARUYAMA;
   const size_t slab = (size_t)B * L * C;
+  const size_t zstride = cond ? 2 * slab : slab;  // z_inject per update
   const uint64_t elem_off = sample_offset * (uint64_t)L * C;
   // the predictor's tail fuses under ffd_sample_batch's conditions (every slab of z_inject is aligned like the first)
   const bool fuse_tail = tail_fusable(ctx) && (C % 4 != 0 || elem_off % 4 == 0) &&
                          (C % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
                          (!z_inject || C % 4 != 0 || (reinterpret_cast<uintptr_t>(z_inject) % 16 == 0 && slab % 4 == 0));
+  auto project = [&](double t, int noiseless, const float* z, uint32_t tag) -> hipError_t {
+    float mc, sigma;
+    cond_coeffs(m.sde, m.sde_a, m.sde_b, t, noiseless, &mc, &sigma);
+    if (cond->domain == FFD_COND_TIME)
+      return launch_cond_time(x, cond->obs, cond->mask, ctx->G_dev, mc, sigma, noiseless, z, seed, elem_off, tag,
+                              cond->obs_batch, B, L, C, s);
+    return launch_cond_project(x, cond->obs, cond->mask, cond->std, ctx->G_dev, mc, sigma, noiseless, z, seed, elem_off, tag,
+                               cond->obs_batch, B, L, C, s);
+  };
   for (int j = 0; j < n_run; ++j) {
     const int i = first_step + j;
     const double t = (double)timesteps[i];
-    const float* zj = z_inject ? z_inject + (size_t)j * (n_corrector + 1) * slab : nullptr;
+    const float* zj = z_inject ? z_inject + (size_t)j * (n_corrector + 1) * zstride : nullptr;
     for (int k = 0; k <= n_corrector; ++k) {  // k == n_corrector: the predictor
       const bool predictor = k == n_corrector;
       int n_rec = use_cache ? 0 : -1;
@@ -1376,7 +1394,7 @@ int ffd_sample_batch_pc(ffd_ctx* ctx, float* x, int B, const float* timesteps, i
       if ((rc = ode_evaluate(ctx, x, i, t, B, n_rec, crf_dst, crf_copy, predictor && fuse_tail, s, &hidden, &score)))
         return rc;
       if (use_cache && k == 0) ctx->stats.current_step = i;  // sampler.py:73-74 (Q4)
-      const float* zk = zj ? zj + (size_t)k * slab : nullptr;
+      const float* zk = zj ? zj + (size_t)k * zstride : nullptr;
       if (!predictor)
         TIMED(FFD_K_SDE, launch_langevin(x, score, zk, ctx->G_dev, langevin_alpha(m.sde, m.sde_a, m.sde_b, t, step_size),
                                          (double)snr, norm, seed, elem_off,
@@ -1389,9 +1407,47 @@ int ffd_sample_batch_pc(ffd_ctx* ctx, float* x, int B, const float* timesteps, i
       else
         TIMED(FFD_K_SDE, launch_sde_step(x, score, zk, ctx->G_dev, sde_params(m.sde, m.sde_a, m.sde_b, t, step_size), seed,
                                          elem_off, (uint32_t)i, B, L, C, s));
+      if (cond)
+        TIMED(FFD_K_SDE, project(t, 0, zk ? zk + slab : nullptr,
+                                 0xC0000000u + (uint32_t)i * (uint32_t)(n_corrector + 1) + (uint32_t)k));
     }
   }
+  if (cond && cond->final_replace && n_run > 0 && first_step + n_run == n_steps)
+    TIMED(FFD_K_SDE, project((double)timesteps[n_steps - 1], 1, nullptr, 0u));
   return FFD_OK;
+}
+
+int ffd_sample_batch_pc(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                        int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed,
+                        uint64_t sample_offset, const float* z_inject, int use_cache, int global_step0, void* stream) {
+  if (!ctx) return FFD_ERR_INVALID;
+  if (n_corrector < 0) return ctx->fail(FFD_ERR_INVALID, "n_corrector must be >= 0");
+  if (!(snr > 0.f)) return ctx->fail(FFD_ERR_INVALID, "snr must be > 0");
+  if (norm != FFD_LANGEVIN_NORM_BATCH && norm != FFD_LANGEVIN_NORM_SAMPLE)
+    return ctx->fail(FFD_ERR_INVALID, "unknown corrector norm %d", norm);
+  if (n_corrector == 0)
+    return ffd_sample_batch(ctx, x, B, timesteps, n_steps, step_size, first_step, n_run, seed, sample_offset, z_inject,
+                            use_cache, global_step0, stream);
+  return pc_loop(ctx, "ffd_sample_batch_pc", x, B, timesteps, n_steps, step_size, first_step, n_run, n_corrector, snr, norm,
+                 seed, sample_offset, z_inject, use_cache, global_step0, nullptr, stream);
+}
+
+// Conditional sampling by replacement: the predictor-corrector step with one ffd_cond_project behind every update.
+int ffd_sample_batch_cond(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                          int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed,
+                          uint64_t sample_offset, const float* z_inject, int use_cache, int global_step0,
+                          const ffd_cond_cfg* cond, void* stream) {
+  if (!ctx) return FFD_ERR_INVALID;
+  if (!cond)
+    return ffd_sample_batch_pc(ctx, x, B, timesteps, n_steps, step_size, first_step, n_run, n_corrector, snr, norm, seed,
+                               sample_offset, z_inject, use_cache, global_step0, stream);
+  if (n_corrector < 0) return ctx->fail(FFD_ERR_INVALID, "n_corrector must be >= 0");
+  if (!(snr > 0.f)) return ctx->fail(FFD_ERR_INVALID, "snr must be > 0");
+  if (norm != FFD_LANGEVIN_NORM_BATCH && norm != FFD_LANGEVIN_NORM_SAMPLE)
+    return ctx->fail(FFD_ERR_INVALID, "unknown corrector norm %d", norm);
+  if (x && z_inject == x) return ctx->fail(FFD_ERR_INVALID, "x aliases z_inject");
+  return pc_loop(ctx, "ffd_sample_batch_cond", x, B, timesteps, n_steps, step_size, first_step, n_run, n_corrector, snr, norm,
+                 seed, sample_offset, z_inject, use_cache, global_step0, cond, stream);
 }
 
 // ---------------------------------------------------------------------------

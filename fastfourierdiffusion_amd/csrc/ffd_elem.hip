@@ -454,6 +454,46 @@ hipError_t launch_sde_step(float* x, const float* score, const float* z, const f
 }
 
 // ---------------------------------------------------------------------------
+// Conditional sampling by replacement, time-domain models (include/ffd.h ffd_cond_project, FFD_COND_TIME): pointwise
+//   y = (mc obs) + ((sigma G_l) z)   (noiseless: y = obs);   x <- x + mask (y - x)
+// every product / sum its own fp32 rounding; the draws are counted like k_sde_step's.
+// ---------------------------------------------------------------------------
+__global__ void k_cond_time(float* __restrict__ x, const float* __restrict__ obs, const float* __restrict__ mask,
+                            const float* __restrict__ z, const float* __restrict__ G, float mc, float sigma, int noiseless,
+                            uint64_t seed, uint64_t elem_offset, uint32_t tag, int shared_obs, size_t total, int L, int C) {
+  const size_t nvec = (total + 3) / 4, per = (size_t)L * C;
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
+    const size_t i0 = v * 4;
+    const int n = (int)((total - i0) < 4 ? (total - i0) : 4);
+    float zz[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!noiseless) load_normals(z, i0, n, seed, elem_offset, tag, zz);
+    for (int j = 0; j < n; ++j) {
+      const size_t i = i0 + j;
+      const size_t io = shared_obs ? i % per : i;
+      float y = obs[io];
+      if (!noiseless) {
+        const float Gl = G[(i / (size_t)C) % (size_t)L];
+        y = __fadd_rn(__fmul_rn(mc, y), __fmul_rn(__fmul_rn(sigma, Gl), zz[j]));
+      }
+      const float xi = x[i];
+      x[i] = __fadd_rn(xi, __fmul_rn(mask[io], __fsub_rn(y, xi)));
+    }
+  }
+}
+
+hipError_t launch_cond_time(float* x, const float* obs, const float* mask, const float* G, float mc, float sigma,
+                            int noiseless, const float* z, uint64_t seed, uint64_t elem_offset, uint32_t tag, int obs_batch,
+                            int B, int L, int C, hipStream_t s) {
+  const size_t total = (size_t)B * L * C;
+  size_t blocks = ((total + 3) / 4 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_cond_time, dim3((unsigned)blocks), dim3(256), 0, s, x, obs, mask, noiseless ? nullptr : z, G, mc,
+                     sigma, noiseless, seed, elem_offset, tag, (int)(obs_batch == 1 && B > 1), total, L, C);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // probability-flow ODE steps (an extension: the reference has Euler-Maruyama only).  Same grid, G, beta(t) and VE
 // sqrt_derivative as the SDE step (sde_params); the drift of the ODE with the SDE's marginals is
 //   d(x, t) = f(x, t) - 1/2 (g(t) G_l)^2 s(x, t),   f = a*x (VP), 0 (VE)

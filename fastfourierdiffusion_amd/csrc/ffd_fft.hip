@@ -749,6 +749,201 @@ __global__ __launch_bounds__(256) void k_fresca_apply_pow2(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------------------
+// Conditional sampling by replacement (include/ffd.h ffd_cond_project), frequency domain: the mirror image of
+// k_fresca_apply -- inverse FFT -> time-domain mask -> forward FFT, all in LDS, in place on x:
+//   d = ((mc obs + (sigma G_l) z) - x) std;   x <- x + dft(mask (.) idft(d)) / std
+// The Hermitian image of d is built straight from the packed rows while loading (k_fft's inverse branch, each packed
+// element read once); the mask is read from global where it is used; x is re-read for the final sum.
+// ---------------------------------------------------------------------------
+struct CondArgs {
+  float* x;
+  const float *obs, *mask, *std, *G, *z;
+  float mc, sigma;
+  int noiseless, obs_batch;
+  uint64_t seed, elem_offset;  // elem_offset = sample_offset L C
+  uint32_t tag;
+};
+
+// the N(0,1) draw of global element g under (seed, tag): slot g & 3 of Philox block g >> 2
+__device__ __forceinline__ float cond_normal(uint64_t g, uint64_t seed, uint32_t tag) {
+  float n[4];
+  normal4(g >> 2, seed, tag, n);
+  const int sl = (int)(g & 3);
+  return sl == 0 ? n[0] : sl == 1 ? n[1] : sl == 2 ? n[2] : n[3];
+}
+
+// d of one packed element: ob = obs, zz = its draw (unused when noiseless), Gl = G of its packed row, sd = std or 1
+__device__ __forceinline__ float cond_diff(float xv, float ob, float zz, float Gl, float mc, float sigma, bool noiseless,
+                                           bool has_std, float sd) {
+  float y = ob;
+  if (!noiseless) y = __fadd_rn(__fmul_rn(mc, ob), __fmul_rn(__fmul_rn(sigma, Gl), zz));
+  float d = __fsub_rn(y, xv);
+  if (has_std) d = __fmul_rn(d, sd);
+  return d;
+}
+
+// d of packed element (row r, channel c) of sample b, read from global
+__device__ __forceinline__ float cond_load(const CondArgs& a, int b, int r, int c, int L, int C) {
+  const size_t io = (size_t)r * C + c;                 // within the slab
+  const size_t ix = (size_t)b * L * C + io;            // within x / z
+  const size_t iobs = a.obs_batch == 1 ? io : ix;      // within obs
+  float zz = 0.f;
+  if (!a.noiseless) zz = a.z ? a.z[ix] : cond_normal(a.elem_offset + ix, a.seed, a.tag);
+  return cond_diff(a.x[ix], a.obs[iobs], zz, a.G[r], a.mc, a.sigma, a.noiseless != 0, a.std != nullptr,
+                   a.std ? a.std[io] : 1.f);
+}
+
+__global__ __launch_bounds__(256) void k_cond_project(CondArgs a, const float2* __restrict__ Wg, FftPlan plan, int L, int C,
+                                                      int CG, float scale) {
+  extern __shared__ __align__(16) float2 sm[];
+  float2* W = sm;
+  float2* bufA = sm + L;
+  float2* bufB = bufA + L * CG;
+  const int b = blockIdx.x;
+  const int c0 = blockIdx.y * CG;
+  const int cg = min(CG, C - c0);
+  const int n_re = L / 2 + 1;
+  for (int i = threadIdx.x; i < L; i += blockDim.x) {  // conjugated: the inverse transform comes first
+    float2 w = Wg[i];
+    w.y = -w.y;
+    W[i] = w;
+  }
+  // Hermitian image X[k], k = 0..L-1, of d: harmonic kk fills bin kk and its mirror L - kk
+  for (int idx = threadIdx.x; idx < n_re * cg; idx += blockDim.x) {
+    const int kk = idx / cg, cc = idx - kk * cg;
+    const float re = cond_load(a, b, kk, c0 + cc, L, C);
+    float im = 0.f;
+    if (kk >= 1 && kk <= L - n_re) im = cond_load(a, b, n_re + kk - 1, c0 + cc, L, C);
+    bufA[kk * CG + cc] = make_float2(re, im);
+    if (kk >= 1 && L - kk >= n_re) bufA[(L - kk) * CG + cc] = make_float2(re, -im);
+  }
+  __syncthreads();
+  float2* t = stockham(bufA, bufB, W, plan, L, CG, cg);
+  const float* mk = a.mask + (a.obs_batch == 1 ? (size_t)0 : (size_t)b * L * C);
+  for (int idx = threadIdx.x; idx < L * cg; idx += blockDim.x) {
+    const int l = idx / cg, cc = idx - l * cg;
+    const float w = __fmul_rn(t[l * CG + cc].x, scale);
+    t[l * CG + cc] = make_float2(__fmul_rn(mk[(size_t)l * C + c0 + cc], w), 0.f);
+  }
+  for (int i = threadIdx.x; i < L; i += blockDim.x) W[i].y = -W[i].y;  // back to the forward twiddles
+  __syncthreads();
+  float2* X = stockham(t, t == bufA ? bufB : bufA, W, plan, L, CG, cg);
+  float* dst = a.x + (size_t)b * L * C;
+  for (int idx = threadIdx.x; idx < L * cg; idx += blockDim.x) {
+    const int o = idx / cg, cc = idx - o * cg;
+    float v = o < n_re ? X[o * CG + cc].x : X[(o - n_re + 1) * CG + cc].y;
+    const size_t go = (size_t)o * C + c0 + cc;
+    v = __fmul_rn(v, scale);
+    if (a.std) v = __fdiv_rn(v, a.std[go]);
+    dst[go] = __fadd_rn(dst[go], v);
+  }
+}
+
+// Powers of two: pow2_split_inv -> half-length inverse -> mask -> half-length forward -> pow2_split_fwd, persistent
+// over the samples like k_fresca_apply_pow2.  VEC (CG == C, C % 4 == 0, 16-byte aligned pointers): the slab is a flat
+// array of float4, each one Philox block.
+template <bool VEC, int LT, int CT>
+__global__ __launch_bounds__(256) void k_cond_project_pow2(CondArgs a, const float2* __restrict__ Wg, Pow2Plan plan_, int B,
+                                                           int L_, int C_, int CG_, int lc_, float scale) {
+  FFD_POW2_SHAPE
+  extern __shared__ __align__(16) float2 sm[];
+  const int N = L >> 1;
+  float2* T = sm;
+  float2* bufA = sm + L;
+  float2* bufB = bufA + N * CG;
+  const int c0 = blockIdx.y * CG, cg = min(CG, C - c0);
+  const int C4 = C >> 2, n4 = (L * C) >> 2;
+  const bool noiseless = a.noiseless != 0;
+  for (int i = threadIdx.x; i < L; i += blockDim.x) T[i] = Wg[i];
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    const size_t sx = (size_t)b * L * C;
+    const size_t so = a.obs_batch == 1 ? (size_t)0 : sx;
+    float* st = reinterpret_cast<float*>(bufB);  // (L x CG) packed rows of d
+    if (VEC) {
+      const float4* x4 = reinterpret_cast<const float4*>(a.x + sx);
+      const float4* o4 = reinterpret_cast<const float4*>(a.obs + so);
+      for (int f = threadIdx.x; f < n4; f += blockDim.x) {
+        const float4 xv = x4[f], ob = o4[f];
+        float zz[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!noiseless) {
+          if (a.z) {
+            const float4 zv = reinterpret_cast<const float4*>(a.z + sx)[f];
+            zz[0] = zv.x, zz[1] = zv.y, zz[2] = zv.z, zz[3] = zv.w;
+          } else {
+            normal4(((a.elem_offset + sx) >> 2) + f, a.seed, a.tag, zz);  // (elem_offset + sx) % 4 == 0: C % 4 == 0
+          }
+        }
+        float4 sd = make_float4(1.f, 1.f, 1.f, 1.f);
+        if (a.std) sd = reinterpret_cast<const float4*>(a.std)[f];
+        const float Gl = a.G[slab_row(f, C4)];
+        const bool hs = a.std != nullptr;
+        reinterpret_cast<float4*>(st)[f] =
+            make_float4(cond_diff(xv.x, ob.x, zz[0], Gl, a.mc, a.sigma, noiseless, hs, sd.x),
+                        cond_diff(xv.y, ob.y, zz[1], Gl, a.mc, a.sigma, noiseless, hs, sd.y),
+                        cond_diff(xv.z, ob.z, zz[2], Gl, a.mc, a.sigma, noiseless, hs, sd.z),
+                        cond_diff(xv.w, ob.w, zz[3], Gl, a.mc, a.sigma, noiseless, hs, sd.w));
+      }
+    } else {
+      for (int idx = threadIdx.x; idx < L * cg; idx += blockDim.x) {
+        const int r = idx / cg, cc = idx - r * cg;
+        st[r * CG + cc] = cond_load(a, b, r, c0 + cc, L, C);
+      }
+    }
+    __syncthreads();
+    pow2_split_inv(st, bufA, T, N, CG, cg, lc);
+    float2* z = pow2_fft_any<true, LT>(bufA, bufB, T, plan, N, CG, cg, lc);
+    // the z image holds time points 2n (real parts) and 2n + 1 (imaginary parts): scale, multiply by the mask
+    float* zf = reinterpret_cast<float*>(z);
+    const float* mk = a.mask + so;
+    if (VEC) {
+      const float4* m4 = reinterpret_cast<const float4*>(mk);
+      for (int f = threadIdx.x; f < n4; f += blockDim.x) {
+        const int l = slab_row(f, C4), cq = (f - l * C4) << 2;
+        float* p = zf + (((l >> 1) * CG + cq) << 1) + (l & 1);
+        const float4 m = m4[f];
+        p[0] = __fmul_rn(m.x, __fmul_rn(p[0], scale));
+        p[2] = __fmul_rn(m.y, __fmul_rn(p[2], scale));
+        p[4] = __fmul_rn(m.z, __fmul_rn(p[4], scale));
+        p[6] = __fmul_rn(m.w, __fmul_rn(p[6], scale));
+      }
+    } else {
+      for (int idx = threadIdx.x; idx < L * cg; idx += blockDim.x) {
+        const int l = idx / cg, cc = idx - l * cg;
+        float* p = zf + (((l >> 1) * CG + cc) << 1) + (l & 1);
+        *p = __fmul_rn(mk[(size_t)l * C + c0 + cc], __fmul_rn(*p, scale));
+      }
+    }
+    __syncthreads();
+    float2* other = (z == bufA) ? bufB : bufA;
+    float2* Z = pow2_fft_any<false, LT>(z, other, T, plan, N, CG, cg, lc);
+    float* so_ = reinterpret_cast<float*>(Z == bufA ? bufB : bufA);
+    pow2_split_fwd(Z, so_, T, N, CG, cg, lc, scale);
+    float* dst = a.x + sx;
+    if (VEC) {
+      float4* d4 = reinterpret_cast<float4*>(dst);
+      for (int f = threadIdx.x; f < n4; f += blockDim.x) {
+        float4 v = reinterpret_cast<const float4*>(so_)[f];
+        if (a.std) {
+          const float4 sd = reinterpret_cast<const float4*>(a.std)[f];
+          v = make_float4(__fdiv_rn(v.x, sd.x), __fdiv_rn(v.y, sd.y), __fdiv_rn(v.z, sd.z), __fdiv_rn(v.w, sd.w));
+        }
+        const float4 xv = d4[f];
+        d4[f] = make_float4(__fadd_rn(xv.x, v.x), __fadd_rn(xv.y, v.y), __fadd_rn(xv.z, v.z), __fadd_rn(xv.w, v.w));
+      }
+    } else {
+      for (int idx = threadIdx.x; idx < L * cg; idx += blockDim.x) {
+        const int o = idx / cg, cc = idx - o * cg;
+        float v = so_[o * CG + cc];
+        const size_t go = (size_t)o * C + c0 + cc;
+        if (a.std) v = __fdiv_rn(v, a.std[go]);
+        dst[go] = __fadd_rn(dst[go], v);
+      }
+    }
+    __syncthreads();  // the LDS images are rewritten by the next sample
+  }
+}
+
 static bool is_pow2(int L) { return fft_len_is_pow2(L); }
 
 static Pow2Plan make_pow2_plan(int N) { return pow2_plan(N); }
@@ -982,6 +1177,54 @@ hipError_t launch_fresca(const float* in, float* out, float* work, int B, int L,
     rc_host = (float)(cutoff_ratio * (double)nf);
   }
   return launch_fresca_apply(in, out, W, g, B, L, C, rc_dev, rc_host, low, high, sc, s);
+}
+
+bool cond_len_supported(int L) { return L >= 2 && fft_len_supported(L, FFT_MAX_FILTER_LEN); }
+
+void cond_coeffs(int sde, double a, double b, double t, int noiseless, float* mc, float* sigma) {
+  double m = 1.0, sg = 0.0;
+  if (!noiseless) {
+    if (sde == FFD_SDE_VP) {
+      const double lmc = -0.25 * t * t * (b - a) - 0.5 * t * a;
+      m = exp(lmc);
+      sg = sqrt(-expm1(2.0 * lmc));
+    } else {
+      sg = a * pow(b / a, t);
+    }
+  }
+  *mc = (float)m;
+  *sigma = (float)sg;
+}
+
+hipError_t launch_cond_project(float* x, const float* obs, const float* mask, const float* std, const float* G, float mc,
+                               float sigma, int noiseless, const float* z, uint64_t seed, uint64_t elem_offset, uint32_t tag,
+                               int obs_batch, int B, int L, int C, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  if (C < 1 || !cond_len_supported(L)) return hipErrorInvalidValue;
+  SlabGeom g;
+  hipError_t e = slab_geom(L, C, &g);
+  if (e != hipSuccess) return e;
+  const float2* W = nullptr;
+  if ((e = get_twiddles(L, &W)) != hipSuccess) return e;
+  const float sc = (float)(1.0 / sqrt((double)L));
+  const CondArgs a{x, obs, mask, std, G, noiseless ? nullptr : z, mc, sigma, noiseless, obs_batch, seed, elem_offset, tag};
+  dim3 grid(B, cdiv(C, g.CG)), block(256);
+  if (g.pow2) {
+    const bool vec = g.CG == C && C % 4 == 0 && aligned16(x) && aligned16(obs) && aligned16(mask) && aligned16(std) &&
+                     aligned16(a.z) && elem_offset % 4 == 0;
+    grid.x = persistent_blocks(B, g.lds);
+#define FFD_COND(VEC, LT, CT)                                                                                        \
+  do {                                                                                                               \
+    if ((e = allow_lds(k_cond_project_pow2<VEC, LT, CT>, g.lds)) != hipSuccess) return e;                            \
+    hipLaunchKernelGGL((k_cond_project_pow2<VEC, LT, CT>), grid, block, g.lds, s, a, W, g.plan2, B, L, C, g.CG, g.lc, sc); \
+  } while (0)
+    if (vec && L == 512 && C == 8) FFD_COND(true, 512, 8); else if (vec) FFD_COND(true, 0, 0); else FFD_COND(false, 0, 0);
+#undef FFD_COND
+  } else {
+    if ((e = allow_lds(k_cond_project, g.lds)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_cond_project, grid, block, g.lds, s, a, W, g.plan, L, C, g.CG, sc);
+  }
+  return hipGetLastError();
 }
 
 // frequency_decompose_fft (fourier.py:219-286): rfft along L, keep bins k < n_low for the low part and
@@ -1254,6 +1497,27 @@ int ffd_fresca(const float* in, float* out, float* work, int B, int L, int C, fl
   if (strategy == FFD_FRESCA_ENERGY && !work) return FFD_ERR_INVALID;
   if (!fft_len_supported(L, FFT_MAX_FILTER_LEN)) return FFD_ERR_UNSUPPORTED;
   hipError_t e = launch_fresca(in, out, work, B, L, C, low_scale, high_scale, cutoff_ratio, strategy, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
+}
+
+int ffd_cond_project(const ffd_sde_desc* sde, float* x, const float* obs, const float* mask, const float* std,
+                     const float* G, double t, int noiseless, const float* z, uint64_t seed, uint64_t sample_offset,
+                     uint32_t tag, int obs_batch, int domain, int B, int L, int C, void* stream) {
+  if (!sde || !x || !obs || !mask || !G || B < 1 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  if (obs_batch != 1 && obs_batch != B) return FFD_ERR_INVALID;
+  if (domain != FFD_COND_FREQUENCY && domain != FFD_COND_TIME) return FFD_ERR_INVALID;
+  if (domain == FFD_COND_TIME && std) return FFD_ERR_INVALID;
+  if (x == obs || x == mask || x == z) return FFD_ERR_INVALID;
+  if (sde->sde != FFD_SDE_VP && sde->sde != FFD_SDE_VE) return FFD_ERR_UNSUPPORTED;
+  if (domain == FFD_COND_FREQUENCY && !cond_len_supported(L)) return FFD_ERR_UNSUPPORTED;
+  float mc, sigma;
+  cond_coeffs(sde->sde, sde->a, sde->b, t, noiseless, &mc, &sigma);
+  const uint64_t off = sample_offset * (uint64_t)L * C;
+  hipError_t e = domain == FFD_COND_TIME
+                     ? launch_cond_time(x, obs, mask, G, mc, sigma, noiseless, z, seed, off, tag, obs_batch, B, L, C,
+                                        (hipStream_t)stream)
+                     : launch_cond_project(x, obs, mask, std, G, mc, sigma, noiseless, z, seed, off, tag, obs_batch, B, L, C,
+                                           (hipStream_t)stream);
   return e == hipSuccess ? FFD_OK : (e == hipErrorInvalidValue ? FFD_ERR_UNSUPPORTED : FFD_ERR_HIP);
 }
 

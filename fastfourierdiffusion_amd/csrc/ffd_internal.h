@@ -269,6 +269,18 @@ hipError_t launch_langevin(float* x, const float* score, const float* z, const f
                            int norm, uint64_t seed, uint64_t elem_offset, uint32_t tag, int B, int L, int C,
                            float* eps_out, void* work, hipStream_t s);
 
+// Conditional sampling by replacement (include/ffd.h ffd_cond_project).  cond_coeffs: the marginal's (mc, sigma) at t in
+// double, rounded once (noiseless: 1, 0).  launch_cond_project: the frequency-domain projection (ffd_fft.hip), one launch;
+// hipErrorInvalidValue for a length outside cond_len_supported.  launch_cond_time: the pointwise one (ffd_elem.hip).
+void cond_coeffs(int sde, double a, double b, double t, int noiseless, float* mc, float* sigma);
+bool cond_len_supported(int L);
+hipError_t launch_cond_project(float* x, const float* obs, const float* mask, const float* std, const float* G, float mc,
+                               float sigma, int noiseless, const float* z, uint64_t seed, uint64_t elem_offset, uint32_t tag,
+                               int obs_batch, int B, int L, int C, hipStream_t s);
+hipError_t launch_cond_time(float* x, const float* obs, const float* mask, const float* G, float mc, float sigma,
+                            int noiseless, const float* z, uint64_t seed, uint64_t elem_offset, uint32_t tag, int obs_batch,
+                            int B, int L, int C, hipStream_t s);
+
 // Denoising score-matching loss (ffd_loss.hip; losses.py:54-125).  Sample b of the call is global sample
 // sample_offset + b: with z == nullptr both kernels take the draw of global element g from slot g & 3 of Philox block
 // g >> 2 under SM_TAG_NOISE, so the loss regenerates what the perturbation drew.

@@ -29,6 +29,14 @@ noise it has without correctors.  ``rng="torch"`` and ``inject_noise`` consume n
 the cache the first evaluation of a step follows the gate and every later one is a pure hit.  No claim about sample
 quality is made: there is no trained checkpoint to measure it on.
 
+Conditioning (extension): ``sample_conditional`` / ``impute`` draw samples that agree with an observed part of a series
+-- imputation, forecasting (a prefix mask) -- by replacement (Song et al. 2021, Appendix I.2; score_sde's
+``get_inpaint_update_fn``) through ``ffd_sample_batch_cond``: after every state update of the predictor-corrector step
+the observation, noised to the step's time level, is blended into the state under a time-axis mask
+(``SDE.cond_project``; one fused launch for models that diffuse the spectrum).  ``rng="torch"`` and ``inject_noise``
+consume two draws per update: its own, then the projection's.  No claim about sample quality is made: there is no
+trained checkpoint to measure it on.
+
 Two batch-wide statistics of the reference make the SAMPLES depend on the batching all the
 same, sharded or not (they are properties of the reference's algorithm, reproduced here per
 batch / per shard): the E2-CRF tables come from the batch's element 0 (caching.py:326-328), and
@@ -64,6 +72,25 @@ from ..utils.dataclasses import DiffusableBatch
 SOLVERS = {"euler_maruyama": N.FFD_SOLVER_EULER_MARUYAMA, "ode_euler": N.FFD_SOLVER_ODE_EULER,
            "ode_heun": N.FFD_SOLVER_ODE_HEUN}
 CORRECTOR_NORMS = {"batch": N.FFD_LANGEVIN_NORM_BATCH, "sample": N.FFD_LANGEVIN_NORM_SAMPLE}
+
+
+def _observation_and_mask(observed, mask, num_samples: int, L: int, Cn: int, what: str):
+    """The shapes ``sample_conditional`` and ``impute`` take: ``observed`` (L, C) or (num_samples, L, C) -> (1 | n, L, C);
+    ``mask`` (L,), (L, 1), (L, C) or the same with a leading 1 | n -> expanded to ``observed``'s shape.  fp32."""
+    observed = torch.as_tensor(observed, dtype=torch.float32)
+    mask = torch.as_tensor(mask, dtype=torch.float32)
+    if observed.dim() == 2:
+        observed = observed.unsqueeze(0)
+    if observed.dim() != 3 or tuple(observed.shape[1:]) != (L, Cn) or observed.shape[0] not in (1, num_samples):
+        raise ValueError(f"{what} must be (L, C) = {(L, Cn)} or (num_samples, L, C), got {tuple(observed.shape)}")
+    if mask.dim() == 1:
+        mask = mask.unsqueeze(-1)
+    if mask.dim() == 2:
+        mask = mask.unsqueeze(0)
+    if mask.dim() != 3 or mask.shape[1] != L or mask.shape[2] not in (1, Cn) or mask.shape[0] not in (1, observed.shape[0]):
+        raise ValueError(f"mask must be (L,), (L, 1), (L, C) or (num_samples, L, C) matching {what} "
+                         f"{tuple(observed.shape)}, got {tuple(mask.shape)}")
+    return observed, mask.expand(observed.shape)
 
 
 class DiffusionSampler:
@@ -210,6 +237,11 @@ class DiffusionSampler:
     # ------------------------------------------------------------------
     def sample(self, num_samples: int, num_diffusion_steps: Optional[int] = None) -> torch.Tensor:
         """sampler.py:105-215."""
+        return self._sample(num_samples, num_diffusion_steps, None)
+
+    def _sample(self, num_samples: int, num_diffusion_steps: Optional[int], cond: Optional[dict]) -> torch.Tensor:
+        """``sample``; ``cond`` (``sample_conditional``): obs / mask (1 or num_samples, L, C) and std on the device,
+        domain, final_replace."""
         if num_diffusion_steps is not None:
             self._num_diffusion_steps = num_diffusion_steps
         self.score_model.eval()
@@ -258,6 +290,8 @@ class DiffusionSampler:
                     n = n_iter - done
                     z_ptr = None
                     draws = self.corrector_steps + 1  # per step: the correctors' in order, then the predictor's
+                    if cond is not None:
+                        draws *= 2  # per update its own draw, then its projection's
                     if not ode and (self.rng == "torch" or self._injected is not None):
                         n = min(n, max(1, self.z_chunk_steps // draws))  # the z buffer keeps its size
                         z = torch.empty((n * draws,) + tuple(X.shape), device=device, dtype=torch.float32)
@@ -272,6 +306,20 @@ class DiffusionSampler:
                                                           step_size, done, n, SOLVERS[self.solver], use_cache,
                                                           (global_step + done) if use_cache else 0, stream)
                         N.check(rc, ctx.handle, "ffd_sample_batch_ode")
+                    elif cond is not None:
+                        lo = batch_idx * self.sample_batch_size
+                        shared = cond["obs"].shape[0] == 1
+                        obs = cond["obs"] if shared else cond["obs"][lo:lo + batch_size]
+                        msk = cond["mask"] if shared else cond["mask"][lo:lo + batch_size]
+                        cfg = N.CondCfg(obs.data_ptr(), msk.data_ptr(),
+                                        cond["std"].data_ptr() if cond["std"] is not None else None,
+                                        1 if shared else batch_size, cond["domain"], int(cond["final_replace"]), 0)
+                        rc = ctx.lib.ffd_sample_batch_cond(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
+                                                           step_size, done, n, self.corrector_steps, self.snr,
+                                                           CORRECTOR_NORMS[self.corrector_norm], self.seed, sample_cursor,
+                                                           z_ptr, use_cache, (global_step + done) if use_cache else 0,
+                                                           C.byref(cfg), stream)
+                        N.check(rc, ctx.handle, "ffd_sample_batch_cond")
                     elif self.corrector_steps > 0:
                         rc = ctx.lib.ffd_sample_batch_pc(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
                                                          step_size, done, n, self.corrector_steps, self.snr,
@@ -296,6 +344,86 @@ class DiffusionSampler:
                 N.check(ctx.lib.ffd_async_status(ctx.handle), ctx.handle, "sampling loop")
                 sample_cursor += batch_size
         return torch.cat(all_samples, dim=0)
+
+    # ------------------------------------------------------------------
+    # conditional sampling by replacement (extension)
+    def sample_conditional(self, observed: torch.Tensor, mask: torch.Tensor, num_samples: int,
+                           num_diffusion_steps: Optional[int] = None, *, domain: Optional[str] = None,
+                           feature_std: Optional[torch.Tensor] = None, final_replace: bool = True) -> torch.Tensor:
+        """``sample`` conditioned on ``observed`` where ``mask`` is 1: after every state update of every reverse step the
+        observation, noised to that step's time, replaces the observed part of the state (``SDE.cond_project``).
+        ``observed`` lives in the diffused domain (for a spectral model: the packed, standardized spectrum of the series,
+        its unobserved time points filled with anything finite); ``mask`` lives on the time axis.  Both are (L, C) --
+        shared by all samples: many completions of one series -- or (num_samples, L, C), sliced per batch; a mask of
+        shape (L,) or (L, 1) is broadcast over the channels.  ``domain=None`` picks "frequency" when the model scales its
+        noise for the spectrum (``score_model.scale_noise``), else "time".  ``feature_std`` (L, C): the dataset's
+        standardization of the spectrum (frequency domain only).  ``final_replace`` ends with one noiseless
+        replacement, so that the observed points come back exact to transform rounding.  Honours ``corrector_steps``,
+        ``snr``, ``corrector_norm``, ``rng``, ``seed``, ``sample_offset``, ``inject_noise``, the cache and FreSca;
+        batching, cache lifecycle and prior are those of ``sample``.  Returns a CPU tensor in the diffused domain.
+        A forecast is the prefix mask ``mask[:n_known] = 1``."""
+        if self.solver != "euler_maruyama":
+            raise ValueError("conditional sampling by replacement is defined for the predictor-corrector sampler: "
+                             "it needs solver='euler_maruyama'")
+        if domain is None:
+            domain = "frequency" if getattr(self.score_model, "scale_noise", False) else "time"
+        if domain not in ("frequency", "time"):
+            raise ValueError(f"domain must be 'frequency' or 'time', got {domain!r}")
+        if domain == "time" and feature_std is not None:
+            raise ValueError("feature_std belongs to the frequency domain")
+        L, Cn = self.max_len, self.n_channels
+        observed, mask = _observation_and_mask(observed, mask, num_samples, L, Cn, "observed")
+        if feature_std is not None:
+            feature_std = torch.as_tensor(feature_std, dtype=torch.float32)
+            if tuple(feature_std.shape) != (L, Cn):
+                raise ValueError(f"feature_std must be (L, C) = {(L, Cn)}, got {tuple(feature_std.shape)}")
+        device = self.score_model.device
+        cond = dict(obs=observed.to(device).contiguous(), mask=mask.to(device).contiguous(),
+                    std=feature_std.to(device).contiguous() if feature_std is not None else None,
+                    domain=N.FFD_COND_FREQUENCY if domain == "frequency" else N.FFD_COND_TIME,
+                    final_replace=bool(final_replace))
+        return self._sample(num_samples, num_diffusion_steps, cond)
+
+    def impute(self, series_time: torch.Tensor, mask: torch.Tensor, num_samples: int,
+               num_diffusion_steps: Optional[int] = None, *, feature_mean: Optional[torch.Tensor] = None,
+               feature_std: Optional[torch.Tensor] = None, final_replace: bool = True) -> torch.Tensor:
+        """Complete a time series with a model that diffuses its spectrum: ``series_time`` (L, C) or
+        (num_samples, L, C) holds the series, ``mask`` (as in ``sample_conditional``) is 1 at its observed points.
+        The unobserved points are zero-filled, the series goes through ``dft`` (with the dataset's ``feature_mean`` /
+        ``feature_std`` (L, C): ``ffd_dft_standardize``), ``sample_conditional`` runs in the frequency domain, and the
+        samples come back as TIME series (``ffd_unstandardize_idft`` / ``idft``) on the CPU.  Forecasting is the
+        prefix mask: ``mask[:n_known] = 1`` draws ``num_samples`` continuations of the first ``n_known`` points."""
+        if (feature_mean is None) != (feature_std is None):
+            raise ValueError("feature_mean and feature_std go together")
+        L, Cn = self.max_len, self.n_channels
+        series, m = _observation_and_mask(series_time, mask, num_samples, L, Cn, "series_time")
+        device = self.score_model.device
+        if device.type != "cuda":
+            raise N.FFDError("sampling needs an MI355X (gfx950) device; there is no CPU fallback")
+        lib, stream = N.lib(), N.current_stream_ptr(device)
+        filled = (series * m).to(device).contiguous()  # zero fill: the fill does not reach the result beyond rounding
+        obs = torch.empty_like(filled)
+        Bo = filled.shape[0]
+        mean_d = std_d = None
+        if feature_mean is not None:
+            mean_d = torch.as_tensor(feature_mean, dtype=torch.float32).to(device).contiguous()
+            std_d = torch.as_tensor(feature_std, dtype=torch.float32).to(device).contiguous()
+            if tuple(mean_d.shape) != (L, Cn) or tuple(std_d.shape) != (L, Cn):
+                raise ValueError(f"feature_mean / feature_std must be (L, C) = {(L, Cn)}")
+            N.check(lib.ffd_dft_standardize(filled.data_ptr(), obs.data_ptr(), mean_d.data_ptr(), std_d.data_ptr(), Bo, L,
+                                            Cn, stream), None, "ffd_dft_standardize")
+        else:
+            N.check(lib.ffd_dft(filled.data_ptr(), obs.data_ptr(), Bo, L, Cn, stream), None, "ffd_dft")
+        out = self.sample_conditional(obs, m, num_samples, num_diffusion_steps, domain="frequency",
+                                      feature_std=std_d, final_replace=final_replace)
+        xf = out.to(device).contiguous()
+        xt = torch.empty_like(xf)
+        if mean_d is not None:
+            N.check(lib.ffd_unstandardize_idft(xf.data_ptr(), xt.data_ptr(), mean_d.data_ptr(), std_d.data_ptr(),
+                                               xf.shape[0], L, Cn, stream), None, "ffd_unstandardize_idft")
+        else:
+            N.check(lib.ffd_idft(xf.data_ptr(), xt.data_ptr(), xf.shape[0], L, Cn, stream), None, "ffd_idft")
+        return xt.cpu()
 
     # ------------------------------------------------------------------
     # cache.update_crf (sampler.py:70-73) for the fused loop: the native loop writes the CRF of the steps the

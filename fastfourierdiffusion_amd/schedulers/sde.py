@@ -214,6 +214,58 @@ class SDE(abc.ABC):
         out = SamplingOutput(prev_sample=x)
         return (out, eps) if return_step_sizes else out
 
+    # -- conditional sampling by replacement (extension: Song et al. 2021, Appendix I.2) --------
+    def cond_project(self, sample: torch.Tensor, observed: torch.Tensor, mask: torch.Tensor, timestep: float, *,
+                     std: Optional[torch.Tensor] = None, domain: str = "frequency",
+                     noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, sample_offset: int = 0,
+                     tag: int = 0xC0000000, noiseless: bool = False) -> SamplingOutput:
+        """One replacement step at ``timestep``: the observation, noised to the forward SDE's marginal there
+        (y_t = mean_coeff observed + sigma G z), is blended into ``sample`` under a time-axis ``mask`` (1 = observed):
+        ``domain="frequency"``: x + dft(mask * idft((y_t - x) * std)) / std on packed spectra (``std`` the dataset's
+        ``feature_std`` (L, C) or None; its mean cancels); ``domain="time"``: x + mask * (y_t - x).  ``observed`` and
+        ``mask`` are (L, C) / (1, L, C) (shared by the batch) or (B, L, C).  ``noise`` injects z; by default
+        z = torch.randn_like(sample); with ``seed`` the draw is made on the device (Philox stream ``tag``, global
+        sample index ``sample_offset`` + b).  ``noiseless`` blends the observation itself and draws nothing."""
+        if domain not in ("frequency", "time"):
+            raise ValueError(f"domain must be 'frequency' or 'time', got {domain!r}")
+        if domain == "time" and std is not None:
+            raise ValueError("std belongs to the frequency domain (the time-domain blend is pointwise)")
+        sample = N.require_gpu_tensor(sample, "sample")
+        if sample.dim() != 3:
+            raise ValueError(f"sample must be (B, L, C), got {tuple(sample.shape)}")
+        B, L, Cn = sample.shape
+        observed = N.require_gpu_tensor(observed, "observed")
+        mask = N.require_gpu_tensor(mask, "mask")
+        if observed.dim() == 2:
+            observed = observed.unsqueeze(0)
+        if mask.dim() == 2:
+            mask = mask.unsqueeze(0)
+        if tuple(observed.shape) not in ((1, L, Cn), (B, L, Cn)) or mask.shape != observed.shape:
+            raise ValueError(f"observed / mask must both be (L, C), (1, L, C) or (B, L, C) of the sample "
+                             f"{tuple(sample.shape)}; got {tuple(observed.shape)} and {tuple(mask.shape)}")
+        if std is not None:
+            std = N.require_gpu_tensor(std, "std")
+            if tuple(std.shape) != (L, Cn):
+                raise ValueError(f"std must be (L, C) = {(L, Cn)}, got {tuple(std.shape)}")
+        z = None
+        if not noiseless:
+            if noise is not None:
+                z = N.require_gpu_tensor(noise, "noise")
+                if z.shape != sample.shape:
+                    raise ValueError(f"noise must have the sample's shape, got {tuple(z.shape)}")
+            elif seed is None:
+                z = torch.randn_like(sample)
+        x = sample.clone()
+        desc = self._desc()
+        rc = N.lib().ffd_cond_project(C.byref(desc), x.data_ptr(), observed.data_ptr(), mask.data_ptr(),
+                                      std.data_ptr() if std is not None else None, self._G_on(sample.device).data_ptr(),
+                                      float(timestep), int(bool(noiseless)), z.data_ptr() if z is not None else None,
+                                      int(seed or 0), int(sample_offset), int(tag), int(observed.shape[0]),
+                                      N.FFD_COND_FREQUENCY if domain == "frequency" else N.FFD_COND_TIME, B, L, Cn,
+                                      N.current_stream_ptr(sample.device))
+        N.check(rc, None, "ffd_cond_project")
+        return SamplingOutput(prev_sample=x)
+
 
 class VEScheduler(SDE):
     """sde.py:90-165."""

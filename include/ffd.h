@@ -238,6 +238,45 @@ int ffd_langevin_step(const ffd_sde_desc* sde, float* x, const float* score, con
                       float snr, int norm, const float* z, uint64_t seed, uint64_t sample_offset, uint32_t tag, int B,
                       int L, int C, float* eps_out, void* work, void* stream);
 
+/* ---- conditional sampling by replacement (an extension: Song et al. 2021, Appendix I.2; score_sde's
+ * get_inpaint_update_fn) ----
+ * One projection of the state x (B,L,C) onto an observation at time t, in place.  The observation is noised to the
+ * forward SDE's marginal at t, as ffd_sm_perturb forms it,
+ *     y_t = mc obs + (sigma G_l) z
+ *     VP: lmc = -0.25 t^2 (b - a) - 0.5 t a, mc = exp(lmc), sigma = sqrt(-expm1(2 lmc));  VE: mc = 1, sigma = a (b/a)^t
+ *     noiseless != 0: mc = 1, sigma = 0, y_t = obs, and no draw is read or generated
+ * (the coefficients formed on the host in double and rounded once to fp32), and blended into x under a mask that lives
+ * on the TIME axis (1 = observed, fractional values blend), in difference form:
+ *     FFD_COND_FREQUENCY  x <- x + dft( mask (.) idft( (y_t - x) (.) std ) ) / std      (x, obs: packed ortho spectra)
+ *     FFD_COND_TIME       x <- x + mask (.) (y_t - x)                                   (pointwise; std must be NULL)
+ * The standardization mean cancels in the difference; an all-zero mask adds exact zeros (x is untouched); the unobserved
+ * components take no round trip.  Unobserved time points of the series behind `obs` may hold anything finite: by
+ * linearity the fill reaches the result only through rounding.
+ *   obs, mask  (obs_batch, L, C), obs_batch = 1 (shared by the batch) or B;  mask values in [0, 1]
+ *   std        NULL or (L, C), the dataset's feature_std, > 0 (the caller's contract, as for ffd_dft_standardize)
+ *   z          NULL or (B, L, C) injected draws.  NULL draws on the device: element i of sample b takes slot g & 3 of
+ *              Philox block g >> 2, g = (sample_offset + b) L C + i over the packed layout, under stream tag `tag`:
+ *              the counting of ffd_sde_step and ffd_langevin_step, so a shard draws what the unsharded call draws.
+ * Operation order.  Per packed element, every product / sum a separate fp32 rounding (no FMA contraction):
+ *     sg = sigma G_l;  y = (mc obs) + (sg z)  (noiseless: y = obs);  d = y - x;  d = d std (std given)
+ *   time domain:  x' = x + mask d.
+ *   frequency domain:  the Hermitian image of d goes through the inverse butterflies; w = v_l / sqrt(L) per time point,
+ *   then m = mask w; the forward butterflies; per packed element X = V / sqrt(L), X = X / std (std given), x' = x + X.
+ *   The butterflies are those of ffd_idft / ffd_dft at this length (powers of two: the half-length real transform).
+ * One launch: a workgroup owns a sample's (L x channel-group) slab in LDS for both transforms.  x, obs and z are read
+ * once from HBM, the mask once at its point of use, x is re-read (L2) for the final sum and written once.
+ * Context-free, stream ordered, no host synchronisation, no atomics: bit-identical from run to run, and a sample's
+ * result does not depend on B or on its place in the batch.  obs, mask, std and z are not modified.
+ * L: frequency domain see "Supported transform lengths" (2 <= L <= 4096); the time domain takes any L >= 1.
+ * FFD_ERR_INVALID before any device work: a null pointer (z and std excepted), B, L, C < 1, obs_batch not 1 or B, an
+ * unknown domain, std with the time domain, x aliasing obs, mask or z; then FFD_ERR_UNSUPPORTED for an unknown SDE or a
+ * frequency-domain length outside its set.
+ * ffd_sample_batch_cond uses tag 0xC0000000 + step * (n_corrector + 1) + k. */
+enum { FFD_COND_FREQUENCY = 0, FFD_COND_TIME = 1 };
+int ffd_cond_project(const ffd_sde_desc* sde, float* x, const float* obs, const float* mask, const float* std,
+                     const float* G, double t, int noiseless, const float* z, uint64_t seed, uint64_t sample_offset,
+                     uint32_t tag, int obs_batch, int domain, int B, int L, int C, void* stream);
+
 /* SDE.prior_sampling (sde.py:79-87, 125-127): x <- G (.) z  (VE: * sigma_max);
  * z == NULL draws on device (Philox stream tag 0xFFFFFFFF). */
 int ffd_prior(const ffd_sde_desc* sde, float* x, const float* z, const float* G, uint64_t seed,
@@ -249,7 +288,9 @@ int ffd_prior(const ffd_sde_desc* sde, float* x, const float* z, const float* G,
  *   ffd_dft, ffd_idft, ffd_dft_standardize, ffd_unstandardize_idft,
  *   ffd_localization (and _bench), ffd_spectral_profile:  L a power of two up to 8192, or any other L up to 6826
  *                                                         (6827 .. 8191 do not fit next to their twiddle table);
- *   ffd_fresca, ffd_freq_decompose:                       the same set up to L = 4096, L >= 2;
+ *   ffd_fresca, ffd_freq_decompose,
+ *   ffd_cond_project (FFD_COND_FREQUENCY; and so
+ *   ffd_sample_batch_cond):                               the same set up to L = 4096, L >= 2;
  *   ffd_smooth_frequency:                                 odd L up to 2047 (its L x L kernel).
  * Any number of channels: they are split over workgroups down to one channel each.  A length outside its set is
  * FFD_ERR_UNSUPPORTED, returned before any device call (no allocation, no launch), after the FFD_ERR_INVALID
@@ -549,6 +590,37 @@ int ffd_sample_batch_pc(ffd_ctx* ctx, float* x, int B, const float* timesteps, i
                         int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed,
                         uint64_t sample_offset, const float* z_inject, int use_cache, int global_step0, void* stream);
 
+/* Conditional sampling by replacement (see ffd_cond_project): ffd_sample_batch_pc with one projection onto the
+ * observation after every state update.  Reverse step i is the predictor-corrector step as it stands; after each of
+ * its n_corrector + 1 updates (corrector k = 0 .. n_corrector - 1, then the predictor, k = n_corrector) one
+ * ffd_cond_project runs at timesteps[i] -- score_sde's order and time level -- with the context's SDE and G.
+ *   cond       NULL: the call IS ffd_sample_batch_pc (forwarded; with n_corrector == 0 that is ffd_sample_batch).
+ *              Otherwise obs / mask / std / obs_batch / domain as in ffd_cond_project, L and C the model's;
+ *              final_replace != 0: when the call's last step is the grid's last step, one more projection with
+ *              noiseless = 1 (the observed points come back exact to transform rounding).
+ *   z_inject   NULL or (n_run, n_corrector + 1, 2, B, L, C): per update its own draw, then its projection's.
+ * Stream tags: the predictor's i, the corrector's 0x80000000 + i * n_corrector + k, the projection's
+ * 0xC0000000 + i * (n_corrector + 1) + k; n_steps * (n_corrector + 1) <= 0x3FFFFFF0 keeps the three ranges and the
+ * reserved 0xFFFFFFFD .. 0xFFFFFFFF apart.  n_corrector == 0 is allowed (predictor + projection).
+ * Cache gate, CRF capture, FreSca, the predictor's fused tail and ffd_async_status are those of ffd_sample_batch_pc; the
+ * projection is one more launch behind the tail, timed under FFD_K_SDE.  The ODE solvers have no conditional form
+ * (score_sde defines replacement for predictor-corrector samplers only).
+ * FFD_ERR_INVALID before any device work: as ffd_sample_batch_pc and ffd_cond_project, and n_steps * (n_corrector + 1)
+ * > 0x3FFFFFF0; FFD_ERR_UNSUPPORTED: a frequency-domain length outside its set. */
+typedef struct {
+  const float* obs;
+  const float* mask;
+  const float* std;
+  int32_t obs_batch;
+  int32_t domain;        /* FFD_COND_* */
+  int32_t final_replace;
+  int32_t reserved;
+} ffd_cond_cfg;
+int ffd_sample_batch_cond(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                          int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed,
+                          uint64_t sample_offset, const float* z_inject, int use_cache, int global_step0,
+                          const ffd_cond_cfg* cond, void* stream);
+
 /* Tuning knobs for experiments and for the test suite's kernel variants (results stay within the parity tolerance,
  * only the kernel choice / tiling changes).  PER CALLING THREAD since round 4 (thread_local): a knob set on one thread
  * selects kernels for the launches THAT thread makes and is invisible to every other thread, so two samplers on two
@@ -652,7 +724,10 @@ int ffd_kernel_timing_get(const ffd_ctx* ctx, int kernel_class, float* avg_ms_ou
  * kernel(s) the forward pass plans for that class under the calling thread's ffd_tune knobs (static
  * string), or NULL for a class the forward does not launch at this batch.  FFD_K_SDE names the tail of the loop entry
  * the context ran last (Euler-Maruyama before any); for Heun, whose two tails differ, the mean of its two launches; after
- * ffd_sample_batch_pc the predictor's tail (its work figures) followed by the corrector's kernels. */
+ * ffd_sample_batch_pc the predictor's tail (its work figures) followed by the corrector's kernels.  The projections of
+ * ffd_sample_batch_cond (k_cond_project / k_cond_time: about 16 B of HBM traffic per element, 12 B with device draws) are
+ * timed under FFD_K_SDE as well but are NOT in this class's name or figures, which describe the update launches only:
+ * after a conditional loop the mean of ffd_kernel_timing_get covers more launches than the figures do. */
 const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cache_hit, double* flops_out,
                             double* bytes_out);
 /* Time `iters` runs of layer 0's FFN at batch B as the forward pass plans it (the launches

@@ -5,6 +5,9 @@
     python3 tools/solver_bench.py pc [out.json]
                                              (predictor-corrector: euler_maruyama, pc1, pc2, pc1_sample ->
                                              profiles/pc_steps.json)
+    python3 tools/solver_bench.py cond [out.json] [--alongside extra.json]
+                                             (conditional sampling: euler_maruyama, cond0, pc1, cond1 ->
+                                             profiles/cond_steps.json)
 
 ECG (L 187, C 1, d 72, 10 layers) at B = 512 on a 21-point grid: 20 intervals for the ODE solvers
 (ffd_sample_batch_ode), the grid's first 20 steps for Euler-Maruyama (ffd_sample_batch, Philox noise on the device).
@@ -17,6 +20,15 @@ intervals a solver needs for a given sample quality -- that needs a trained chec
 ``pc``: ffd_sample_batch_pc on the same grid with 1 and 2 Langevin corrector steps per reverse step (batch norm; pc1_sample:
 1 step, sample norm), Euler-Maruyama measured in the same run.  A corrector step is one more score evaluation plus
 the corrector's three (batch norm: four) small launches, so pcN is expected near (1 + N) Euler-Maruyama steps.
+
+``cond``: ffd_sample_batch_cond in the frequency domain (one observed series shared by the batch, a prefix mask, the
+dataset's std) with 0 and 1 corrector steps, next to the same steps without conditioning: condN adds one
+k_cond_project launch behind each of its N + 1 updates; ``cost_vs_unconditional`` is cond0 / euler_maruyama and
+cond1 / pc1.
+
+``--alongside FILE``: the JSON object in FILE goes into the result as ``measured_alongside``, unchanged -- what was
+measured next to this run and is not this tool's to measure (the other runs of an alternating series, the parent
+commit's figures, a kernel trace): profiles/cond_steps.json carries its comparison that way.
 """
 import ctypes as C
 import json
@@ -32,9 +44,10 @@ import bench  # noqa: E402
 from fastfourierdiffusion_amd import _native as N  # noqa: E402
 
 B, INTERVALS, REPS, TRAJ = 512, 20, 3, 5
-EVALS = {"euler_maruyama": 1, "ode_euler": 1, "ode_heun": 2, "pc1": 2, "pc2": 3, "pc1_sample": 2}
+EVALS = {"euler_maruyama": 1, "ode_euler": 1, "ode_heun": 2, "pc1": 2, "pc2": 3, "pc1_sample": 2, "cond0": 1, "cond1": 2}
 PC = {"pc1": (1, N.FFD_LANGEVIN_NORM_BATCH), "pc2": (2, N.FFD_LANGEVIN_NORM_BATCH),
       "pc1_sample": (1, N.FFD_LANGEVIN_NORM_SAMPLE)}
+COND = {"cond0": (0, "euler_maruyama"), "cond1": (1, "pc1")}  # corrector steps, the unconditional twin
 SNR = 0.16
 
 
@@ -45,6 +58,15 @@ def main() -> None:
     if args and args[0] == "pc":
         solvers, default_out = ["euler_maruyama", "pc1", "pc2", "pc1_sample"], "pc_steps.json"
         del args[0]
+    elif args and args[0] == "cond":
+        solvers, default_out = ["euler_maruyama", "cond0", "pc1", "cond1"], "cond_steps.json"
+        del args[0]
+    alongside = None
+    if "--alongside" in args:  # a JSON object measured next to this run, carried into the result unchanged
+        i = args.index("--alongside")
+        with open(args[i + 1]) as f:
+            alongside = json.load(f)
+        del args[i:i + 2]
     if "--solvers" in args:
         i = args.index("--solvers")
         solvers = args[i + 1].split(",")
@@ -64,10 +86,22 @@ def main() -> None:
     from fastfourierdiffusion_amd.sampling.sampler import DiffusionSampler
 
     prior = DiffusionSampler(model, B, rng="philox", seed=42)
+    cond = None
+    if any(sv in COND for sv in solvers):  # one observed series for the batch, a prefix mask, a std table
+        L, Cn = model.max_len, model.n_channels
+        g = torch.Generator().manual_seed(7)
+        obs = torch.randn((1, L, Cn), generator=g).to(dev)
+        mask = torch.zeros((1, L, Cn), device=dev)
+        mask[:, :100] = 1.0  # "complete this beat from its first 100 samples"
+        std = (0.5 + 1.5 * torch.rand((L, Cn), generator=g)).to(dev)
+        cond = N.CondCfg(obs.data_ptr(), mask.data_ptr(), std.data_ptr(), 1, N.FFD_COND_FREQUENCY, 1, 0)
 
     def trajectory(solver, X):
         if solver == "euler_maruyama":
             rc = lib.ffd_sample_batch(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, 42, 0, None, 0, 0, stream)
+        elif solver in COND:
+            rc = lib.ffd_sample_batch_cond(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, COND[solver][0], SNR,
+                                           N.FFD_LANGEVIN_NORM_BATCH, 42, 0, None, 0, 0, C.byref(cond), stream)
         elif solver in PC:
             rc = lib.ffd_sample_batch_pc(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, PC[solver][0], SNR, PC[solver][1], 42,
                                          0, None, 0, 0, stream)
@@ -103,6 +137,12 @@ def main() -> None:
         em = res["solvers"]["euler_maruyama"]["ms_per_interval"]
         for s in solvers:
             res["solvers"][s]["cost_vs_euler_maruyama_step"] = round(res["solvers"][s]["ms_per_interval"] / em, 4)
+    for s, (_, twin) in COND.items():
+        if s in solvers and twin in solvers:
+            res["solvers"][s]["cost_vs_unconditional"] = round(res["solvers"][s]["ms_per_interval"] /
+                                                               res["solvers"][twin]["ms_per_interval"], 4)
+    if alongside is not None:
+        res["measured_alongside"] = alongside
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:
         json.dump(res, f, indent=1)
