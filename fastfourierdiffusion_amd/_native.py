@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libffd.so")
 FFD_MODEL_TRANSFORMER, FFD_MODEL_LSTM, FFD_MODEL_MLP = 0, 1, 2
 FFD_SDE_VP, FFD_SDE_VE = 0, 1
 FFD_SOLVER_EULER_MARUYAMA, FFD_SOLVER_ODE_EULER, FFD_SOLVER_ODE_HEUN, FFD_SOLVER_PC = 0, 1, 2, 3
+FFD_SOLVER_ODE_AB2, FFD_SOLVER_DPMPP_2M = 4, 5
 FFD_LANGEVIN_NORM_BATCH, FFD_LANGEVIN_NORM_SAMPLE = 0, 1
 FFD_COND_FREQUENCY, FFD_COND_TIME = 0, 1
 # kernel classes (include/ffd.h FFD_K_*)
@@ -115,6 +116,9 @@ SIGNATURES = {
                                        C.c_int, _P]),
     "ffd_ode_heun_correct": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, _P, _P, C.c_double, C.c_float, C.c_int, C.c_int,
                                        C.c_int, _P]),
+    "ffd_host_multistep_coef": (C.c_int, [C.POINTER(SdeDesc), C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          C.c_int, C.POINTER(C.c_double)]),
+    "ffd_ode_multistep_step": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_langevin_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "ffd_langevin_step": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, C.c_double, C.c_float, C.c_float, C.c_int, _P,
                                     C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

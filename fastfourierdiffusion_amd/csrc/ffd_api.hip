@@ -107,6 +107,10 @@ struct ffd_ctx {
   Grow<float> score2, fwork;
   Grow<float> sm_noisy;  // the perturbed batch of ffd_sm_eval_batch
   Grow<float> ode_xp, ode_d1;  // Heun's predicted state and predictor drift (ffd_sample_batch_ode)
+  Grow<float> ode_hist;        // the multistep solvers' history quantity q of the previous interval
+  // whose history ode_hist holds: the solver and batch of the multistep call that ran last and the interval it ended at
+  // (ms_solver < 0: none; every other loop entry drops it)
+  int ms_solver = -1, ms_B = 0, ms_next = 0;
   Grow<float> lv_work;  // the Langevin corrector's row squares, norms and step sizes (ffd_sample_batch_pc)
   int tail_solver = FFD_SOLVER_EULER_MARUYAMA;  // the loop entry that ran last (ffd_kernel_work names its FFD_K_SDE tail)
   // cache
@@ -1198,6 +1202,7 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
   if ((rc = ensure_fresca_work(ctx, B))) return rc;
   if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
   ctx->tail_solver = FFD_SOLVER_EULER_MARUYAMA;
+  ctx->ms_solver = -1;
   const size_t slab = (size_t)B * m.max_len * m.n_channels;
   const uint64_t elem_off = sample_offset * (uint64_t)m.max_len * m.n_channels;
   // Without FreSca the score is consumed only by the SDE step: unembed inside the step kernel (one launch and a
@@ -1267,16 +1272,34 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
   if (!x || !timesteps || n_steps < 2 || first_step < 0 || n_run < 0 || first_step + n_run > n_steps - 1)
     return ctx->fail(FFD_ERR_INVALID, "bad argument to ffd_sample_batch_ode (n_steps=%d first=%d run=%d: %d intervals)",
                      n_steps, first_step, n_run, n_steps - 1);
-  if (solver != FFD_SOLVER_ODE_EULER && solver != FFD_SOLVER_ODE_HEUN)
+  const bool multistep = solver == FFD_SOLVER_ODE_AB2 || solver == FFD_SOLVER_DPMPP_2M;
+  if (solver != FFD_SOLVER_ODE_EULER && solver != FFD_SOLVER_ODE_HEUN && !multistep)
     return ctx->fail(FFD_ERR_INVALID, "unknown ODE solver %d", solver);
   if (!(step_size > 0.f)) return ctx->fail(FFD_ERR_INVALID, "step_size must be > 0");
   if (use_cache && ctx->desc.kind != FFD_MODEL_TRANSFORMER)
     return ctx->fail(FFD_ERR_UNSUPPORTED, "caching is only defined for the transformer backbone");
   if (use_cache && !ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "use_cache without ffd_cache_enable");
-  HIPCHECK(hipSetDevice(ctx->device));
-  if ((rc = ensure_workspace(ctx, B))) return rc;
   const ffd_model_desc& m = ctx->desc;
   const int L = m.max_len, C = m.n_channels, d = m.d_model;
+  // The multistep solvers: every interval's coefficients, before any device work.  A trajectory continues
+  // (first_step > 0) only on the history the context's previous loop call left for exactly this interval.
+  std::vector<MultistepParams> ms_coef;
+  if (multistep) {
+    if (first_step > 0 && (ctx->ms_solver != solver || ctx->ms_B != B || ctx->ms_next != first_step))
+      return ctx->fail(FFD_ERR_STATE, "first_step=%d continues a multistep trajectory, but the context's previous sampling "
+                       "call did not end there with solver %d and B=%d", first_step, solver, B);
+    for (int j = 0; j < n_run; ++j) {
+      const int i = first_step + j;
+      double c[5];
+      if (multistep_coef(m.sde, m.sde_a, m.sde_b, solver, i > 0 ? (double)timesteps[i - 1] : 0.0, (double)timesteps[i],
+                         (double)timesteps[i + 1], (double)step_size, i > 0, c))
+        return ctx->fail(FFD_ERR_INVALID, "interval %d of the grid has no multistep coefficients (times must decrease "
+                         "strictly and sigma(t) must be > 0)", i);
+      ms_coef.push_back(multistep_params(c));
+    }
+  }
+  HIPCHECK(hipSetDevice(ctx->device));
+  if ((rc = ensure_workspace(ctx, B))) return rc;
   const bool heun = solver == FFD_SOLVER_ODE_HEUN;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = ensure_fresca_work(ctx, B))) return rc;
@@ -1284,8 +1307,10 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
     if ((rc = ensure(ctx, ctx->ode_xp, (size_t)B * L * C))) return rc;
     if ((rc = ensure(ctx, ctx->ode_d1, (size_t)B * L * C))) return rc;
   }
+  if (multistep && (rc = ensure(ctx, ctx->ode_hist, (size_t)B * L * C))) return rc;  // (a continued call: already there)
   if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
   ctx->tail_solver = solver;
+  ctx->ms_solver = -1;  // (multistep: set again once the call's intervals are enqueued)
   float* const xp = ctx->ode_xp.p;
   float* const d1 = ctx->ode_d1.p;
   // the workspace buffers are 16-byte aligned: only the caller's x decides the quad path
@@ -1309,6 +1334,14 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
     const double t = (double)timesteps[i];
     if ((rc = ode_evaluate(ctx, x, i, t, B, n_rec, crf_dst, crf_copy, fuse, s, &hidden, &score))) return rc;
     if (use_cache) ctx->stats.current_step = i;
+    if (multistep) {  // history: every interval but a trajectory's first
+      if (hidden)
+        TIMED(FFD_K_SDE, launch_unembed_multistep(hidden, ctx->model.unembed_w, ctx->model.unembed_b, x, ctx->ode_hist.p,
+                                                  ctx->G_dev, ms_coef[j], i > 0, B, L, C, d, s));
+      else
+        TIMED(FFD_K_SDE, launch_multistep_step(x, score, ctx->ode_hist.p, ctx->G_dev, ms_coef[j], i > 0, B, L, C, s));
+      continue;
+    }
     TIMED(FFD_K_SDE, tail(heun ? ODE_PREDICT : ODE_EULER, hidden, score, t));
     if (!heun) continue;
     // the corrector's evaluation at (xp, t_{i+1}): with the cache a pure hit
@@ -1316,6 +1349,7 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
     if ((rc = ode_evaluate(ctx, xp, i + 1, tn, B, use_cache ? 0 : -1, nullptr, nullptr, fuse, s, &hidden, &score))) return rc;
     TIMED(FFD_K_SDE, tail(ODE_CORRECT, hidden, score, tn));
   }
+  if (multistep && first_step + n_run > 0) ctx->ms_solver = solver, ctx->ms_B = B, ctx->ms_next = first_step + n_run;
   return FFD_OK;
 }
 
@@ -1360,6 +1394,7 @@ static int pc_loop(ffd_ctx* ctx, const char* who, float* x, int B, const float* 
     return rc;
   if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
   ctx->tail_solver = n_corrector > 0 ? FFD_SOLVER_PC : FFD_SOLVER_EULER_MARUYAMA;
+  ctx->ms_solver = -1;
   const size_t slab = (size_t)B * L * C;
   const size_t zstride = cond ? 2 * slab : slab;  // z_inject per update
   const uint64_t elem_off = sample_offset * (uint64_t)L * C;
@@ -1589,6 +1624,9 @@ const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cac
       // The ODE tails of ffd_sample_batch_ode draw nothing.  Euler moves the same bytes; Heun's predictor reads x and
       // writes xp and d1 (3 C floats per row beside the score / hidden row), its corrector reads xp, x, d1 and
       // writes x (4 C): the mean of the two launches is given.
+      // The multistep tails (AB2, DPM-Solver++ 2M: one kernel) also read and write the history q: two more (B, L, C)
+      // arrays than Euler's, 4 C floats per row beside the score / hidden row (a trajectory's first interval reads no
+      // history: 3 C; the figure is the tail's with history).
       // ffd_sample_batch_pc: the predictor's tail is ffd_sample_batch's; per corrector step the class also holds the
       // three (batch norm: four) Langevin launches, which read the score twice and z never: 20 B per element.
       if (ctx->tail_solver == FFD_SOLVER_PC) {
@@ -1601,6 +1639,11 @@ const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cac
           name = "k_unembed_ode<heun predict | correct>", fl = 2.0 * M * C * d, by = 4.0 * M * (d + 3.5 * C);
         else
           name = "k_ode_step<heun predict | correct>", by = 18.0 * M * C;
+      } else if (ctx->tail_solver == FFD_SOLVER_ODE_AB2 || ctx->tail_solver == FFD_SOLVER_DPMPP_2M) {
+        if (tail_fusable(ctx))
+          name = "k_unembed_multistep", fl = 2.0 * M * C * d, by = 4.0 * M * (d + 4.0 * C);
+        else
+          name = "k_multistep_step", by = 20.0 * M * C;
       } else if (ctx->tail_solver == FFD_SOLVER_ODE_EULER) {
         if (tail_fusable(ctx))
           name = "k_unembed_ode<euler>", fl = 2.0 * M * C * d, by = 4.0 * M * (d + 2.0 * C);

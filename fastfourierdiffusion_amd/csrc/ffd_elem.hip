@@ -3,6 +3,7 @@
 //   - Gaussian-Fourier time embedding, channel embed / unembed
 //   - VP / VE reverse Euler-Maruyama step with on-device Philox4x32-10 noise
 //   - probability-flow ODE intervals (Euler, Heun predictor / corrector): no noise draw
+//   - linear multistep ODE intervals (Adams-Bashforth 2, DPM-Solver++ 2M): one operation, coefficients from the host
 //   - KV-table store
 // All HBM-bound: one pass over the data, coalesced, no re-reads.
 // The entry points that need no context (SDE step, prior, the two encodings, Hermite prediction) follow the kernels.
@@ -599,6 +600,78 @@ hipError_t launch_ode_step(int tail, float* x, const float* score, float* xp, fl
   }
 }
 
+// ---------------------------------------------------------------------------
+// linear multistep ODE steps (Adams-Bashforth 2 on the drift above; DPM-Solver++ 2M on the data prediction): second
+// order at one score evaluation per interval.  Both are this one operation (include/ffd.h ffd_ode_multistep_step); the
+// five coefficients come from the host (multistep_coef):
+//   q = qa x + qb G_l^2 s;   x <- x + (cxm1 x + cn q + cp q_prev);   hist <- q
+// PREV = false is a trajectory's first interval: cp = 0 and hist is not read.  Every product / sum is its own fp32
+// rounding, like ode_update.
+// ---------------------------------------------------------------------------
+template <bool PREV>
+__device__ __forceinline__ float multistep_update(float xi, float sc, float Gl, float& hq, const MultistepParams& p) {
+  const float g2 = __fmul_rn(Gl, Gl);
+  const float u = __fmul_rn(g2, sc);
+  const float q = __fadd_rn(__fmul_rn(p.qa, xi), __fmul_rn(p.qb, u));
+  float inc = __fadd_rn(__fmul_rn(p.cxm1, xi), __fmul_rn(p.cn, q));
+  if (PREV) inc = __fadd_rn(inc, __fmul_rn(p.cp, hq));
+  hq = q;
+  return __fadd_rn(xi, inc);
+}
+
+// The stand-alone tails (score from HBM): the twins of k_ode_step_v4 / k_ode_step.  x and hist in / out (PREV = false:
+// hist out only).
+template <bool PREV>
+__global__ __launch_bounds__(256) void k_multistep_step_v4(float* __restrict__ x, const float* __restrict__ score,
+                                                           float* __restrict__ hist, const float* __restrict__ G,
+                                                           MultistepParams p, size_t nvec, int L, unsigned C4) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
+    const float4 sc = reinterpret_cast<const float4*>(score)[v];
+    const float4 xi = reinterpret_cast<const float4*>(x)[v];
+    float4 hv{};
+    if (PREV) hv = reinterpret_cast<const float4*>(hist)[v];
+    const float Gl = G[(v / C4) % (size_t)L];
+    reinterpret_cast<float4*>(x)[v] =
+        float4{multistep_update<PREV>(xi.x, sc.x, Gl, hv.x, p), multistep_update<PREV>(xi.y, sc.y, Gl, hv.y, p),
+               multistep_update<PREV>(xi.z, sc.z, Gl, hv.z, p), multistep_update<PREV>(xi.w, sc.w, Gl, hv.w, p)};
+    reinterpret_cast<float4*>(hist)[v] = hv;
+  }
+}
+
+template <bool PREV>
+__global__ void k_multistep_step(float* __restrict__ x, const float* __restrict__ score, float* __restrict__ hist,
+                                 const float* __restrict__ G, MultistepParams p, size_t total, int L, int C) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const float Gl = G[(i / (size_t)C) % (size_t)L];
+    float hq = PREV ? hist[i] : 0.f;
+    x[i] = multistep_update<PREV>(x[i], score[i], Gl, hq, p);
+    hist[i] = hq;
+  }
+}
+
+template <bool PREV>
+static hipError_t launch_multistep_tail(float* x, const float* score, float* hist, const float* G, MultistepParams p, int B,
+                                        int L, int C, hipStream_t s) {
+  const size_t total = (size_t)B * L * C;
+  if (C % 4 == 0 && ptr16(x) && ptr16(score) && ptr16(hist)) {
+    size_t blocks = (total / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL((k_multistep_step_v4<PREV>), dim3((unsigned)blocks), dim3(256), 0, s, x, score, hist, G, p, total / 4,
+                       L, (unsigned)C / 4);
+  } else {
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL((k_multistep_step<PREV>), dim3((unsigned)blocks), dim3(256), 0, s, x, score, hist, G, p, total, L, C);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_multistep_step(float* x, const float* score, float* hist, const float* G, MultistepParams p,
+                                 int have_prev, int B, int L, int C, hipStream_t s) {
+  if (have_prev) return launch_multistep_tail<true>(x, score, hist, G, p, B, L, C, s);
+  return launch_multistep_tail<false>(x, score, hist, G, p, B, L, C, s);
+}
+
 // prior: x = G (.) z  (VE: * sigma_max), sde.py:79-87,125-127
 __device__ __forceinline__ float prior_value(float Gl, float zz, float scale) {
   const float v0 = __fmul_rn(Gl, zz);
@@ -951,6 +1024,113 @@ hipError_t launch_unembed_ode(int tail, const float* h, const float* Wu, const f
   }
 }
 
+// The multistep tail of the sampling loop: the k_unembed_ode scheme (same fragments, same MFMA order, same prefetch of
+// the next tile) continued with multistep_update in the accumulator registers.  One more sibling, so that the instances
+// above keep their code.  The quad path (C % 4 == 0) fetches the tile's x and (PREV) hist quads together with its h
+// rows; the tail moves two (B, L, C) arrays more than Euler's, 4 (d + 4 C) B per row against 4 (d + 2 C).
+template <int D, bool PREV>
+__global__ __launch_bounds__(256) void k_unembed_multistep(const float* __restrict__ h, const float* __restrict__ Wu,
+                                                           const float* __restrict__ bu, float* __restrict__ x,
+                                                           float* __restrict__ hist, const float* __restrict__ G,
+                                                           MultistepParams p, int M, int L, int C) {
+  constexpr int NG = (D + 15) / 16;  // 16-wide k chunks
+  const int lane = threadIdx.x & 63;
+  const int r = lane & 15, q = lane >> 4;
+  const int ntiles = (M + 15) >> 4;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+  float4 wf[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int k = 16 * g + 4 * q;
+    wf[g] = (r < C && k < D) ? *reinterpret_cast<const float4*>(Wu + (size_t)r * D + k) : float4{0.f, 0.f, 0.f, 0.f};
+  }
+  f32x4 bias;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) bias[i] = (4 * q + i < C) ? bu[4 * q + i] : 0.f;
+  auto load_tile = [&](int t, float4 (&hv)[NG]) {
+    const int row = min(16 * t + r, M - 1);
+    const float* hr = h + (size_t)row * D + 4 * q;
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+      hv[g] = (16 * g + 4 * q < D) ? *reinterpret_cast<const float4*>(hr + 16 * g) : float4{0.f, 0.f, 0.f, 0.f};
+  };
+  const bool quad = (C & 3) == 0 && 4 * q < C;
+  auto load_u = [&](int t, float4& u0, float4& u1) {  // u0 = x, u1 = hist
+    if (quad) {
+      const size_t i0 = (size_t)min(16 * t + r, M - 1) * C + 4 * q;
+      u0 = *reinterpret_cast<const float4*>(x + i0);
+      if (PREV) u1 = *reinterpret_cast<const float4*>(hist + i0);
+    }
+  };
+  float4 hv[NG], hn[NG];
+  float4 u0{}, u1{}, n0{}, n1{};
+  if (wave < ntiles) load_tile(wave, hv), load_u(wave, u0, u1);
+  for (int t = wave; t < ntiles; t += nwaves) {
+    const bool more = t + nwaves < ntiles;
+    if (more) load_tile(t + nwaves, hn), load_u(t + nwaves, n0, n1);
+    f32x4 acc = bias;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      acc = mfma16(wf[g].x, hv[g].x, acc);
+      acc = mfma16(wf[g].y, hv[g].y, acc);
+      acc = mfma16(wf[g].z, hv[g].z, acc);
+      acc = mfma16(wf[g].w, hv[g].w, acc);
+    }
+    const int row = 16 * t + r;
+    const int c0 = 4 * q;
+    if (row < M && c0 < C) {
+      const size_t i0 = (size_t)row * C + c0;
+      const float Gl = G[row % L];
+      if ((C & 3) == 0) {
+        float4 hq = u1;
+        *reinterpret_cast<float4*>(x + i0) =
+            float4{multistep_update<PREV>(u0.x, acc[0], Gl, hq.x, p), multistep_update<PREV>(u0.y, acc[1], Gl, hq.y, p),
+                   multistep_update<PREV>(u0.z, acc[2], Gl, hq.z, p), multistep_update<PREV>(u0.w, acc[3], Gl, hq.w, p)};
+        *reinterpret_cast<float4*>(hist + i0) = hq;
+      } else {
+        const int n = min(4, C - c0);
+        for (int i = 0; i < n; ++i) {
+          float hq = PREV ? hist[i0 + i] : 0.f;
+          x[i0 + i] = multistep_update<PREV>(x[i0 + i], acc[i], Gl, hq, p);
+          hist[i0 + i] = hq;
+        }
+      }
+    }
+    if (more) {
+#pragma unroll
+      for (int g = 0; g < NG; ++g) hv[g] = hn[g];
+      u0 = n0, u1 = n1;
+    }
+  }
+}
+
+template <bool PREV>
+static hipError_t launch_unembed_multistep_tail(const float* h, const float* Wu, const float* bu, float* x, float* hist,
+                                                const float* G, MultistepParams p, int M, int L, int C, int D,
+                                                hipStream_t s) {
+  int blocks = cdiv(cdiv(M, 16), 4);
+  if (blocks > 2048) blocks = 2048;
+  switch (D) {
+#define X(d)                                                                                                             \
+  case d:                                                                                                                \
+    hipLaunchKernelGGL((k_unembed_multistep<d, PREV>), dim3(blocks), dim3(256), 0, s, h, Wu, bu, x, hist, G, p, M, L, C); \
+    break;
+    FFD_D_LIST(X)
+#undef X
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// multistep tail(x, hist, unembed(h)): the fused tail of a multistep interval (requires unembed_sde_supported(C, D))
+hipError_t launch_unembed_multistep(const float* h, const float* Wu, const float* bu, float* x, float* hist, const float* G,
+                                    MultistepParams p, int have_prev, int B, int L, int C, int D, hipStream_t s) {
+  if (!unembed_sde_supported(C, D) || !ptr16(h) || !ptr16(Wu) || !hist) return hipErrorInvalidValue;
+  if ((C & 3) == 0 && (!ptr16(x) || !ptr16(hist))) return hipErrorInvalidValue;  // quads
+  if (have_prev) return launch_unembed_multistep_tail<true>(h, Wu, bu, x, hist, G, p, B * L, L, C, D, s);
+  return launch_unembed_multistep_tail<false>(h, Wu, bu, x, hist, G, p, B * L, L, C, D, s);
+}
+
 // ---------------------------------------------------------------------------
 // KV table store: table[h][l][:] <- sample 0's head-major K/V rows, l < n (Q1)
 // ---------------------------------------------------------------------------
@@ -1012,6 +1192,67 @@ SdeParams sde_params(int sde, double a, double b, double t, float step_size) {
   return p;
 }
 
+// (log alpha, log sigma) of the forward marginal at t (sde.py:106-123, 186-210; without G).  VP: sigma^2 =
+// -expm1(2 log alpha), so that small t loses nothing to 1 - exp(.).
+static void log_alpha_sigma(int sde, double a, double b, double t, double* la, double* ls) {
+  if (sde == FFD_SDE_VP) {
+    *la = -0.25 * t * t * (b - a) - 0.5 * t * a;
+    *ls = 0.5 * log(-expm1(2.0 * *la));
+  } else {
+    *la = 0.0;
+    *ls = log(a) + t * log(b / a);
+  }
+}
+
+int multistep_coef(int sde, double a, double b, int solver, double t_prev, double t, double t_next, double step_size,
+                   int have_prev, double* c) {
+  if (!c || (sde != FFD_SDE_VP && sde != FFD_SDE_VE)) return FFD_ERR_INVALID;
+  if (!(t_next < t) || (have_prev && !(t < t_prev))) return FFD_ERR_INVALID;
+  if (solver == FFD_SOLVER_ODE_AB2) {
+    if (!(step_size > 0.0)) return FFD_ERR_INVALID;
+    double cs;  // f = qa x and g = cs at t, in sde_params' expressions
+    if (sde == FFD_SDE_VP) {
+      const double beta = a + t * (b - a);
+      c[0] = -0.5 * beta, cs = sqrt(beta);
+    } else {
+      const double r = b / a;
+      c[0] = 0.0, cs = a * sqrt(2.0 * log(r)) * pow(r, t);
+    }
+    c[1] = -0.5 * cs * cs;
+    c[2] = 0.0;
+    c[3] = have_prev ? -1.5 * step_size : -step_size;
+    c[4] = have_prev ? 0.5 * step_size : 0.0;
+  } else if (solver == FFD_SOLVER_DPMPP_2M) {
+    double la, ls, lan, lsn;
+    log_alpha_sigma(sde, a, b, t, &la, &ls);
+    log_alpha_sigma(sde, a, b, t_next, &lan, &lsn);
+    if (!std::isfinite(ls) || !std::isfinite(lsn)) return FFD_ERR_INVALID;  // sigma == 0
+    const double h = (lan - lsn) - (la - ls);
+    const double cc = -exp(lan) * expm1(-h);
+    c[0] = exp(-la);
+    c[1] = exp(2.0 * ls - la);
+    c[2] = expm1(lsn - ls);
+    c[3] = cc, c[4] = 0.0;
+    if (have_prev) {
+      double lap, lsp;
+      log_alpha_sigma(sde, a, b, t_prev, &lap, &lsp);
+      if (!std::isfinite(lsp)) return FFD_ERR_INVALID;
+      const double r = ((la - ls) - (lap - lsp)) / h;
+      c[3] = cc * (1.0 + 1.0 / (2.0 * r));
+      c[4] = -cc / (2.0 * r);
+    }
+  } else {
+    return FFD_ERR_INVALID;
+  }
+  for (int i = 0; i < 5; ++i)
+    if (!std::isfinite(c[i])) return FFD_ERR_INVALID;
+  return FFD_OK;
+}
+
+MultistepParams multistep_params(const double* c) {
+  return MultistepParams{(float)c[0], (float)c[1], (float)c[2], (float)c[3], (float)c[4]};
+}
+
 }  // namespace ffd
 
 // ---- C ABI (include/ffd.h): the context-free entry points on these kernels ----
@@ -1061,6 +1302,27 @@ int ffd_ode_heun_correct(const ffd_sde_desc* sde, float* x, const float* x_pred,
   if (!x_pred || !drift || x_pred == x || drift == x) return FFD_ERR_INVALID;
   hipError_t e = launch_ode_step(ODE_CORRECT, x, score_pred, const_cast<float*>(x_pred), const_cast<float*>(drift), G,
                                  sde_params(sde->sde, sde->a, sde->b, t_next, step_size), B, L, C, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+int ffd_host_multistep_coef(const ffd_sde_desc* sde, int solver, double t_prev, double t, double t_next, double step_size,
+                            int have_prev, double* coef_out) {
+  if (!sde || !coef_out) return FFD_ERR_INVALID;
+  double c[5];  // coef_out is written on success only
+  if (int rc = multistep_coef(sde->sde, sde->a, sde->b, solver, t_prev, t, t_next, step_size, have_prev, c)) return rc;
+  for (int i = 0; i < 5; ++i) coef_out[i] = c[i];
+  return FFD_OK;
+}
+
+int ffd_ode_multistep_step(float* x, const float* score, const float* G, float* hist, const double* coef, int have_prev,
+                           int B, int L, int C, void* stream) {
+  if (!x || !score || !G || !hist || !coef || B < 1 || L < 1 || C < 1) return FFD_ERR_INVALID;
+  if (hist == x || hist == score) return FFD_ERR_INVALID;
+  const MultistepParams p = multistep_params(coef);
+  for (float v : {p.qa, p.qb, p.cxm1, p.cn, p.cp})
+    if (!std::isfinite(v)) return FFD_ERR_INVALID;
+  if (!have_prev && coef[4] != 0.0) return FFD_ERR_INVALID;
+  hipError_t e = launch_multistep_step(x, score, hist, G, p, have_prev, B, L, C, (hipStream_t)stream);
   return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
 }
 

@@ -259,6 +259,19 @@ hipError_t launch_ode_step(int tail, float* x, const float* score, float* xp, fl
 // ... with the unembedding inside (the score stays in registers).  Needs unembed_sde_supported(C, D).
 hipError_t launch_unembed_ode(int tail, const float* h, const float* Wu, const float* bu, float* x, float* xp, float* d1,
                               const float* G, SdeParams p, int B, int L, int C, int D, hipStream_t s);
+// The linear multistep tail (ffd_elem.hip; include/ffd.h ffd_ode_multistep_step): AB2 and DPM-Solver++ 2M are this one
+// operation with the five coefficients multistep_coef computes in double and multistep_params rounds once,
+//   q = (qa x) + (qb ((G_l G_l) score));  x <- x + ((cxm1 x) + (cn q) [+ (cp hist)]);  hist <- q.
+// have_prev == 0 (a trajectory's first interval): hist is written only.  x and hist are distinct (B, L, C) buffers.
+struct MultistepParams { float qa, qb, cxm1, cn, cp; };
+int multistep_coef(int sde, double a, double b, int solver, double t_prev, double t, double t_next, double step_size,
+                   int have_prev, double* coef_out);  // FFD_OK | FFD_ERR_INVALID
+MultistepParams multistep_params(const double* coef);
+hipError_t launch_multistep_step(float* x, const float* score, float* hist, const float* G, MultistepParams p,
+                                 int have_prev, int B, int L, int C, hipStream_t s);
+// ... with the unembedding inside (the score stays in registers).  Needs unembed_sde_supported(C, D).
+hipError_t launch_unembed_multistep(const float* h, const float* Wu, const float* bu, float* x, float* hist, const float* G,
+                                    MultistepParams p, int have_prev, int B, int L, int C, int D, hipStream_t s);
 
 // The Langevin corrector (ffd_langevin.hip; include/ffd.h ffd_langevin_step): row squares, step size, update, four
 // launches with the batch norm and three with the sample norm.  alpha = langevin_alpha at the evaluation's time;

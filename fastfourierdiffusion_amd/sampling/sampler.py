@@ -21,6 +21,14 @@ Solver (extension): ``solver="euler_maruyama"`` (default) is the reference's int
 ``ffd_sample_batch_ode``: deterministic given the prior (no step noise is drawn), over the N - 1 intervals of the
 N-point grid, ending exactly at ``eps``; Heun evaluates the model twice per interval and is second order.  Batching,
 cache lifecycle and prior are unchanged; the global step of the cache gate counts intervals.
+``"ode_ab2"`` (Adams-Bashforth 2 on the ODE's drift) and ``"dpmpp_2m"`` (DPM-Solver++ 2M, the exponential two-step form
+on the data prediction) are linear multistep solvers of the same ODE: they reuse the previous interval's evaluation and
+reach second order with ONE model call per interval, the cost of ``"ode_euler"`` (the trajectory's first interval has no
+history and is first order).  Both are one device operation (``SDE.ode_multistep_step``) whose five coefficients the
+host computes in float64; the history lives in the native context across the calls of one trajectory.  On the
+analytic Gaussian case of the tests, at 32 evaluations: VP ``ode_ab2`` 2.40e-3, ``ode_heun`` 3.93e-3, ``dpmpp_2m``
+2.14e-2 (it loses to Heun on this uniform-t grid); VE 5.08e-4 / 4.78e-3 / 5.53e-4.  Which wins on a trained network is
+unmeasured.
 
 Corrector (extension): ``corrector_steps=n > 0`` makes every Euler-Maruyama step a predictor-corrector step in
 score_sde's order (``ffd_sample_batch_pc``): n Langevin corrector steps at t_i (``SDE.step_correct``: each its own score
@@ -71,6 +79,8 @@ from ..utils.dataclasses import DiffusableBatch
 # solver name -> libffd's FFD_SOLVER_*
 SOLVERS = {"euler_maruyama": N.FFD_SOLVER_EULER_MARUYAMA, "ode_euler": N.FFD_SOLVER_ODE_EULER,
            "ode_heun": N.FFD_SOLVER_ODE_HEUN}
+# the linear multistep ODE solvers (kept apart: SOLVERS names the solvers with recorded Euler / Heun cases)
+MULTISTEP_SOLVERS = {"ode_ab2": N.FFD_SOLVER_ODE_AB2, "dpmpp_2m": N.FFD_SOLVER_DPMPP_2M}
 CORRECTOR_NORMS = {"batch": N.FFD_LANGEVIN_NORM_BATCH, "sample": N.FFD_LANGEVIN_NORM_SAMPLE}
 
 
@@ -100,7 +110,7 @@ class DiffusionSampler:
                  fresca_cutoff_strategy: Literal["spatial", "energy"] = "energy",
                  rng: Literal["torch", "philox"] = "torch", seed: int = 42, sample_offset: int = 0,
                  z_chunk_steps: int = 50,
-                 solver: Literal["euler_maruyama", "ode_euler", "ode_heun"] = "euler_maruyama",
+                 solver: Literal["euler_maruyama", "ode_euler", "ode_heun", "ode_ab2", "dpmpp_2m"] = "euler_maruyama",
                  corrector_steps: int = 0, snr: float = 0.16,
                  corrector_norm: Literal["batch", "sample"] = "batch") -> None:
         self.score_model = score_model
@@ -127,8 +137,8 @@ class DiffusionSampler:
         self.seed = int(seed)
         self.sample_offset = int(sample_offset)
         self.z_chunk_steps = int(z_chunk_steps)
-        if solver not in SOLVERS:
-            raise ValueError(f"solver must be one of {sorted(SOLVERS)}, got {solver!r}")
+        if not isinstance(solver, str) or (solver not in SOLVERS and solver not in MULTISTEP_SOLVERS):
+            raise ValueError(f"solver must be one of {sorted(SOLVERS) + sorted(MULTISTEP_SOLVERS)}, got {solver!r}")
         self.solver = solver
         if corrector_steps < 0:
             raise ValueError(f"corrector_steps must be >= 0, got {corrector_steps!r}")
@@ -143,6 +153,7 @@ class DiffusionSampler:
         self.snr = float(snr)
         self.corrector_norm = corrector_norm
         self._injected = None
+        self._multistep = None  # reverse_diffusion_step's (history, t, t_next) of its previous call
 
     def inject_noise(self, draws) -> None:
         """Parity hook: take every N(0,1) draw (one (B,L,C) array for each batch's prior,
@@ -166,7 +177,8 @@ class DiffusionSampler:
         t_lo, t_hi = float(torch.min(timesteps)), float(torch.max(timesteps))
         assert t_lo == t_hi  # sampler.py:59-60
         sch = self.noise_scheduler
-        t_next = self._heun_next_time(timesteps[0]) if self.solver == "ode_heun" else None
+        needs_grid = self.solver == "ode_heun" or self.solver in MULTISTEP_SOLVERS  # the interval's end is read from it
+        t_next = self._heun_next_time(timesteps[0]) if needs_grid else None
         if self.corrector_steps > 0:
             return self._predictor_corrector_step(batch, t_lo, step, recompute_tokens)
         score = self._evaluate_score(batch, t_lo, step, recompute_tokens, update_crf=True)
@@ -174,6 +186,15 @@ class DiffusionSampler:
             output = sch.step(model_output=score, timestep=timesteps[0].item(), sample=X)
         elif self.solver == "ode_euler":
             output = sch.ode_step(model_output=score, timestep=timesteps[0].item(), sample=X)
+        elif self.solver in MULTISTEP_SOLVERS:
+            # the previous call's history continues the trajectory when this call starts where that one ended
+            prev = self._multistep
+            if prev is not None and (prev[2] != t_lo or prev[0].shape != X.shape or prev[0].device != X.device):
+                prev = None
+            output, hist = sch.ode_multistep_step(model_output=score, timestep=t_lo, timestep_next=t_next, sample=X,
+                                                  method=self.solver, history=None if prev is None else prev[0],
+                                                  timestep_prev=None if prev is None else prev[1])
+            self._multistep = (hist, t_lo, t_next)
         else:  # Heun: a second model call at the predicted state and the interval's end (with the cache: a pure hit)
             X_pred, drift = sch.ode_heun_predict(model_output=score, timestep=timesteps[0].item(), sample=X)
             batch_pred = DiffusableBatch(X=X_pred, y=batch.y, timesteps=torch.full_like(timesteps, t_next))
@@ -224,15 +245,20 @@ class DiffusionSampler:
         return score
 
     def _heun_next_time(self, t: torch.Tensor) -> float:
-        """The grid point after ``t``: Heun's corrector evaluates the model there."""
+        """The grid point after ``t``: Heun's corrector evaluates the model there, and the multistep solvers' interval
+        ends there."""
         grid = getattr(self.noise_scheduler, "timesteps", None)
         if grid is None:
-            raise ValueError("solver='ode_heun' needs the scheduler's grid: call noise_scheduler.set_timesteps(n) first")
+            raise ValueError(f"solver={self.solver!r} needs the scheduler's grid: call noise_scheduler.set_timesteps(n) "
+                             "first")
         hit = torch.nonzero(grid.to(torch.float32) == t.detach().to(torch.float32).cpu()).flatten()
         if hit.numel() == 0 or int(hit[0]) >= grid.numel() - 1:
-            raise ValueError(f"solver='ode_heun' steps from a point of the scheduler's grid other than the last one; "
+            raise ValueError(f"solver={self.solver!r} steps from a point of the scheduler's grid other than the last one; "
                              f"got t={float(t)!r}")
         return float(grid[int(hit[0]) + 1])
+
+    def _solver_code(self) -> int:
+        return SOLVERS[self.solver] if self.solver in SOLVERS else MULTISTEP_SOLVERS[self.solver]
 
     # ------------------------------------------------------------------
     def sample(self, num_samples: int, num_diffusion_steps: Optional[int] = None) -> torch.Tensor:
@@ -303,7 +329,7 @@ class DiffusionSampler:
                         z_ptr = z.data_ptr()
                     if ode:  # deterministic given the prior: no step noise is drawn or allocated
                         rc = ctx.lib.ffd_sample_batch_ode(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
-                                                          step_size, done, n, SOLVERS[self.solver], use_cache,
+                                                          step_size, done, n, self._solver_code(), use_cache,
                                                           (global_step + done) if use_cache else 0, stream)
                         N.check(rc, ctx.handle, "ffd_sample_batch_ode")
                     elif cond is not None:
@@ -395,6 +421,9 @@ class DiffusionSampler:
         prefix mask: ``mask[:n_known] = 1`` draws ``num_samples`` continuations of the first ``n_known`` points."""
         if (feature_mean is None) != (feature_std is None):
             raise ValueError("feature_mean and feature_std go together")
+        if self.solver != "euler_maruyama":  # (sample_conditional's refusal, before any device work)
+            raise ValueError("conditional sampling by replacement is defined for the predictor-corrector sampler: "
+                             "it needs solver='euler_maruyama'")
         L, Cn = self.max_len, self.n_channels
         series, m = _observation_and_mask(series_time, mask, num_samples, L, Cn, "series_time")
         device = self.score_model.device

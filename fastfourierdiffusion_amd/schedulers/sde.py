@@ -20,6 +20,8 @@ import torch
 from .. import _native as N
 
 SamplingOutput = namedtuple("SamplingOutput", ["prev_sample"])
+# multistep method name -> libffd's FFD_SOLVER_*
+MULTISTEP_METHODS = {"ode_ab2": N.FFD_SOLVER_ODE_AB2, "dpmpp_2m": N.FFD_SOLVER_DPMPP_2M}
 
 
 class SDE(abc.ABC):
@@ -176,6 +178,52 @@ class SDE(abc.ABC):
                                           stream)
         N.check(rc, None, "ffd_ode_heun_correct")
         return SamplingOutput(prev_sample=x)
+
+    # -- linear multistep ODE steps (extension: second order at one model call per interval) ------
+    def multistep_coefficients(self, method: str, timestep: float, timestep_next: float,
+                               timestep_prev: Optional[float] = None) -> tuple:
+        """The five float64 coefficients (qa, qb, cxm1, cn, cp) of ``ode_multistep_step`` for the interval from
+        ``timestep`` to ``timestep_next`` (``ffd_host_multistep_coef``; needs no device).  ``timestep_prev=None``: the
+        first interval of a trajectory."""
+        if method not in MULTISTEP_METHODS:
+            raise ValueError(f"method must be one of {sorted(MULTISTEP_METHODS)}, got {method!r}")
+        coef = (C.c_double * 5)()
+        desc = self._desc()
+        have_prev = timestep_prev is not None
+        rc = N.lib().ffd_host_multistep_coef(C.byref(desc), MULTISTEP_METHODS[method],
+                                             float(timestep_prev) if have_prev else 0.0, float(timestep),
+                                             float(timestep_next), float(self.step_size), int(have_prev), coef)
+        if rc != 0:
+            raise ValueError(f"no {method} coefficients for t_prev={timestep_prev!r}, t={timestep!r}, "
+                             f"t_next={timestep_next!r}: the times must decrease strictly, with sigma(t) > 0")
+        return tuple(coef)
+
+    def ode_multistep_step(self, model_output: torch.Tensor, timestep: float, timestep_next: float, sample: torch.Tensor,
+                           method: str, history: Optional[torch.Tensor] = None, timestep_prev: Optional[float] = None):
+        """One interval of a linear multistep solver of the probability-flow ODE, from ``timestep`` to
+        ``timestep_next``: ``method="ode_ab2"`` (Adams-Bashforth 2 on the drift of ``ode_step``; uniform grid of width
+        ``step_size``) or ``"dpmpp_2m"`` (DPM-Solver++ 2M on the data prediction).  Both reuse the previous interval's
+        evaluation: ``history`` is the second value this method returned for the interval from ``timestep_prev`` to
+        ``timestep``; without it (a trajectory's first interval) the step is first order.  Returns
+        (SamplingOutput, history for the next interval).  No noise is drawn; the inputs are not modified."""
+        if method not in MULTISTEP_METHODS:
+            raise ValueError(f"method must be one of {sorted(MULTISTEP_METHODS)}, got {method!r}")
+        if (history is None) != (timestep_prev is None):
+            raise ValueError("history and timestep_prev go together")
+        sample, model_output, G, stream = self._ode_args(sample, model_output)
+        coef = (C.c_double * 5)(*self.multistep_coefficients(method, timestep, timestep_next, timestep_prev))
+        B, L, Cn = sample.shape
+        x = sample.clone()
+        if history is not None:
+            history = N.require_gpu_tensor(history, "history")
+            assert history.shape == sample.shape
+            hist = history.clone()
+        else:
+            hist = torch.empty_like(sample)
+        rc = N.lib().ffd_ode_multistep_step(x.data_ptr(), model_output.data_ptr(), G, hist.data_ptr(), coef,
+                                            int(history is not None), B, L, Cn, stream)
+        N.check(rc, None, "ffd_ode_multistep_step")
+        return SamplingOutput(prev_sample=x), hist
 
     # -- Langevin corrector (extension: predictor-corrector sampling) ----------
     def step_correct(self, model_output: torch.Tensor, sample: torch.Tensor, snr: float, timestep: float,

@@ -201,6 +201,34 @@ int ffd_ode_heun_correct(const ffd_sde_desc* sde, float* x, const float* x_pred,
                          const float* drift, const float* G, double t_next, float step_size, int B, int L, int C,
                          void* stream);
 
+/* ---- linear multistep ODE steps: second order at one score evaluation per interval (an extension) ----
+ * Adams-Bashforth 2 on the drift above (FFD_SOLVER_ODE_AB2) and DPM-Solver++ 2M, the exponential two-step form on the
+ * data prediction (FFD_SOLVER_DPMPP_2M; Lu et al. 2022), are ONE device operation.  With the interval's history quantity
+ *     q = qa x + qb G_l^2 s
+ * the update is, in increment form (coefficient rounding only touches the increment),
+ *     x <- x + (cxm1 x + cn q + cp q_prev),    hist <- q
+ * and the solvers differ in the five coefficients (qa, qb, cxm1, cn, cp), which the host computes in float64:
+ *   FFD_SOLVER_ODE_AB2   (uniform grid of width step_size = h)  q = d(x,t): qa = a(t) (VP: -beta(t)/2, VE: 0),
+ *                        qb = -cs(t)^2 / 2, cxm1 = 0; cn = -1.5 h, cp = 0.5 h with history, cn = -h, cp = 0 without.
+ *   FFD_SOLVER_DPMPP_2M  (reads t_prev, t, t_next; step_size unused)  alpha(t), sigma(t) of the forward marginal (without
+ *                        G), lambda = log(alpha / sigma), h = lambda(t_next) - lambda(t), r = (lambda(t) -
+ *                        lambda(t_prev)) / h, c = -alpha(t_next) expm1(-h):  q = (x + sigma^2 G_l^2 s) / alpha, qa = 1 /
+ *                        alpha, qb = sigma^2 / alpha, cxm1 = sigma(t_next) / sigma(t) - 1; cn = c (1 + 1 / (2 r)),
+ *                        cp = -c / (2 r) with history, cn = c, cp = 0 without.  No lower-order final step.
+ * The first interval of a trajectory has no history (have_prev == 0): cp = 0 and hist is written, never read.
+ * ffd_host_multistep_coef: host only (no device needed), float64, coef_out[5] in the order above.  FFD_ERR_INVALID: a null
+ * pointer, an unknown solver or SDE, times that are not strictly decreasing (t_prev is ignored when have_prev == 0),
+ * step_size <= 0 for AB2, (DPM++) a time at which sigma is 0, a non-finite result. */
+int ffd_host_multistep_coef(const ffd_sde_desc* sde, int solver, double t_prev, double t, double t_next, double step_size,
+                            int have_prev, double* coef_out);
+/* The step: coef (host, 5 doubles) is rounded once to fp32; per element, each a separate fp32 rounding (no FMA
+ * contraction):  g2 = G_l G_l, u = g2 s, q = (qa x) + (qb u), inc = (cxm1 x) + (cn q), [have_prev: inc = inc + (cp
+ * hist)], x = x + inc, hist = q.  Context-free and stream ordered; x and hist (B,L,C) are updated in place.
+ * FFD_ERR_INVALID before any device work: a null pointer, B, L, C < 1, hist aliasing x or score, a non-finite
+ * coefficient, coef[4] != 0 with have_prev == 0. */
+int ffd_ode_multistep_step(float* x, const float* score, const float* G, float* hist, const double* coef, int have_prev,
+                           int B, int L, int C, void* stream);
+
 /* ---- Langevin corrector (an extension: predictor-corrector sampling, Song et al. 2021, Algorithms 4 / 5) ----
  * Forward SDE dx = f dt + g(t) diag(G) dw exactly as in ffd_sde_step.  One corrector step at time t on sample b, with
  * the score s = s(x, t) and a draw z ~ N(0, I):
@@ -553,7 +581,16 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
  * t_0 = 1 ... t_{n_steps-1} = eps (interval i: from timesteps[i] to timesteps[i+1], width step_size) and end exactly
  * at eps; this call runs intervals [first_step, first_step + n_run), first_step + n_run <= n_steps - 1, n_steps >= 2.
  *   FFD_SOLVER_ODE_EULER  one score evaluation per interval (at timesteps[i]);
- *   FFD_SOLVER_ODE_HEUN   two: the predictor's at timesteps[i], the corrector's at (x_pred, timesteps[i+1]).
+ *   FFD_SOLVER_ODE_HEUN   two: the predictor's at timesteps[i], the corrector's at (x_pred, timesteps[i+1]);
+ *   FFD_SOLVER_ODE_AB2, FFD_SOLVER_DPMPP_2M  one (at timesteps[i]), reused by the next interval: the multistep solvers of
+ *                         ffd_ode_multistep_step, with ffd_host_multistep_coef(timesteps[i-1], timesteps[i],
+ *                         timesteps[i+1], step_size).  Cache gate, CRF capture and FreSca as for FFD_SOLVER_ODE_EULER.
+ *                         The history q lives in the context.  first_step == 0 starts a trajectory without history;
+ *                         first_step > 0 continues one, and is FFD_ERR_STATE (before any device work) unless the
+ *                         context's previous sampling-loop call was ffd_sample_batch_ode with the same solver and B
+ *                         and ended at interval first_step.  Every other loop entry (ffd_sample_batch, _pc, _cond, the
+ *                         Euler / Heun solvers) drops the history.  A trajectory split into calls gives the bits of
+ *                         one call.
  * Same time-embedding table, stream ordering and host synchronisation as ffd_sample_batch (none but for a new grid);
  * with the unembedding fused into the tail (see "fuse_tail") no score reaches HBM.
  *   use_cache  the predictor evaluation of interval i follows ffd_host_gate at global step global_step0 + (i -
@@ -564,6 +601,7 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
  * FFD_ERR_INVALID before any device work: null pointers, B < 1, step_size <= 0, an unknown solver, an interval range
  * outside the grid. */
 enum { FFD_SOLVER_EULER_MARUYAMA = 0, FFD_SOLVER_ODE_EULER = 1, FFD_SOLVER_ODE_HEUN = 2 };
+enum { FFD_SOLVER_ODE_AB2 = 4, FFD_SOLVER_DPMPP_2M = 5 }; /* (3 is FFD_SOLVER_PC) */
 int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
                          int first_step, int n_run, int solver, int use_cache, int global_step0, void* stream);
 
@@ -672,7 +710,7 @@ int ffd_sample_batch_cond(ffd_ctx* ctx, float* x, int B, const float* timesteps,
  *                                              the rounds come out whole, 1: layers walked whole, n: forced);
  *   "fuse_tail" = 1 | 0                        unembedding inside the SDE-step kernel of ffd_sample_batch (and of the
  *                                              predictor of ffd_sample_batch_pc) and the ODE tails of
- *                                              ffd_sample_batch_ode (no FreSca);
+ *                                              ffd_sample_batch_ode, the multistep ones included (no FreSca);
  *   "attn_fused" = 1 | 0                       in-projection + attention in one kernel (k_qkv_attention*);
  *   "attn_kvq" = 1 | 0                         small-batch split attention: tile 0 = k | v, tile 1 = q, q projected for a
  *                                              workgroup's own q-tiles only (head_dim 6 / 8) | the whole head;
@@ -698,8 +736,8 @@ enum {
   FFD_K_OUTPROJ = 2,     /* k_linear_res_ln: out-projection + residual + LayerNorm1 */
   FFD_K_LSTM_REC = 3,    /* k_lstm_*: the L-step recurrence of one residual LSTM layer */
   FFD_K_LSTM_GATES = 4,  /* k_linear_rm: input-gate GEMM of one LSTM layer */
-  FFD_K_SDE = 5,         /* k_sde_step (or the fused unembed + SDE step); in ffd_sample_batch_ode the ODE tails, in
-                          * ffd_sample_batch_pc also the corrector's launches */
+  FFD_K_SDE = 5,         /* k_sde_step (or the fused unembed + SDE step); in ffd_sample_batch_ode the ODE tails (Euler,
+                          * Heun's two, or the multistep tail), in ffd_sample_batch_pc also the corrector's launches */
   FFD_K_EMBED = 6,
   FFD_K_UNEMBED = 7,
   FFD_K_COUNT = 8
@@ -723,7 +761,8 @@ int ffd_kernel_timing_get(const ffd_ctx* ctx, int kernel_class, float* avg_ms_ou
  * MFMA-bound classes, HBM bytes for all); cache_hit = 1 for a pure-cache step.  Returns the name of the
  * kernel(s) the forward pass plans for that class under the calling thread's ffd_tune knobs (static
  * string), or NULL for a class the forward does not launch at this batch.  FFD_K_SDE names the tail of the loop entry
- * the context ran last (Euler-Maruyama before any); for Heun, whose two tails differ, the mean of its two launches; after
+ * the context ran last (Euler-Maruyama before any); for Heun, whose two tails differ, the mean of its two launches; for the
+ * multistep solvers the tail with history (every interval of a trajectory but its first, which reads no history); after
  * ffd_sample_batch_pc the predictor's tail (its work figures) followed by the corrector's kernels.  The projections of
  * ffd_sample_batch_cond (k_cond_project / k_cond_time: about 16 B of HBM traffic per element, 12 B with device draws) are
  * timed under FFD_K_SDE as well but are NOT in this class's name or figures, which describe the update launches only:

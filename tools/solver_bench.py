@@ -8,6 +8,9 @@
     python3 tools/solver_bench.py cond [out.json] [--alongside extra.json]
                                              (conditional sampling: euler_maruyama, cond0, pc1, cond1 ->
                                              profiles/cond_steps.json)
+    python3 tools/solver_bench.py multistep [out.json] [--alongside extra.json]
+                                             (linear multistep ODE solvers: euler_maruyama, ode_euler, ode_ab2, dpmpp_2m ->
+                                             profiles/multistep_steps.json)
 
 ECG (L 187, C 1, d 72, 10 layers) at B = 512 on a 21-point grid: 20 intervals for the ODE solvers
 (ffd_sample_batch_ode), the grid's first 20 steps for Euler-Maruyama (ffd_sample_batch, Philox noise on the device).
@@ -25,6 +28,10 @@ the corrector's three (batch norm: four) small launches, so pcN is expected near
 dataset's std) with 0 and 1 corrector steps, next to the same steps without conditioning: condN adds one
 k_cond_project launch behind each of its N + 1 updates; ``cost_vs_unconditional`` is cond0 / euler_maruyama and
 cond1 / pc1.
+
+``multistep``: ode_ab2 and dpmpp_2m (one tail kernel, one score evaluation per interval, the previous interval's history
+read and written beside x) next to ode_euler and Euler-Maruyama in the same run; ``cost_vs_ode_euler_interval`` is the
+acceptance figure, expected near 1.00.
 
 ``--alongside FILE``: the JSON object in FILE goes into the result as ``measured_alongside``, unchanged -- what was
 measured next to this run and is not this tool's to measure (the other runs of an alternating series, the parent
@@ -44,7 +51,8 @@ import bench  # noqa: E402
 from fastfourierdiffusion_amd import _native as N  # noqa: E402
 
 B, INTERVALS, REPS, TRAJ = 512, 20, 3, 5
-EVALS = {"euler_maruyama": 1, "ode_euler": 1, "ode_heun": 2, "pc1": 2, "pc2": 3, "pc1_sample": 2, "cond0": 1, "cond1": 2}
+EVALS = {"euler_maruyama": 1, "ode_euler": 1, "ode_heun": 2, "pc1": 2, "pc2": 3, "pc1_sample": 2, "cond0": 1, "cond1": 2,
+         "ode_ab2": 1, "dpmpp_2m": 1}
 PC = {"pc1": (1, N.FFD_LANGEVIN_NORM_BATCH), "pc2": (2, N.FFD_LANGEVIN_NORM_BATCH),
       "pc1_sample": (1, N.FFD_LANGEVIN_NORM_SAMPLE)}
 COND = {"cond0": (0, "euler_maruyama"), "cond1": (1, "pc1")}  # corrector steps, the unconditional twin
@@ -60,6 +68,9 @@ def main() -> None:
         del args[0]
     elif args and args[0] == "cond":
         solvers, default_out = ["euler_maruyama", "cond0", "pc1", "cond1"], "cond_steps.json"
+        del args[0]
+    elif args and args[0] == "multistep":
+        solvers, default_out = ["euler_maruyama", "ode_euler", "ode_ab2", "dpmpp_2m"], "multistep_steps.json"
         del args[0]
     alongside = None
     if "--alongside" in args:  # a JSON object measured next to this run, carried into the result unchanged
@@ -106,7 +117,8 @@ def main() -> None:
             rc = lib.ffd_sample_batch_pc(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, PC[solver][0], SNR, PC[solver][1], 42,
                                          0, None, 0, 0, stream)
         else:
-            code = {"ode_euler": N.FFD_SOLVER_ODE_EULER, "ode_heun": N.FFD_SOLVER_ODE_HEUN}[solver]
+            code = {"ode_euler": N.FFD_SOLVER_ODE_EULER, "ode_heun": N.FFD_SOLVER_ODE_HEUN,
+                    "ode_ab2": N.FFD_SOLVER_ODE_AB2, "dpmpp_2m": N.FFD_SOLVER_DPMPP_2M}[solver]
             rc = lib.ffd_sample_batch_ode(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, code, 0, 0, stream)
         N.check(rc, hdl, solver)
 
@@ -137,6 +149,11 @@ def main() -> None:
         em = res["solvers"]["euler_maruyama"]["ms_per_interval"]
         for s in solvers:
             res["solvers"][s]["cost_vs_euler_maruyama_step"] = round(res["solvers"][s]["ms_per_interval"] / em, 4)
+    if "ode_euler" in solvers:
+        oe = res["solvers"]["ode_euler"]["ms_per_interval"]
+        for s in ("ode_ab2", "dpmpp_2m"):
+            if s in solvers:
+                res["solvers"][s]["cost_vs_ode_euler_interval"] = round(res["solvers"][s]["ms_per_interval"] / oe, 4)
     for s, (_, twin) in COND.items():
         if s in solvers and twin in solvers:
             res["solvers"][s]["cost_vs_unconditional"] = round(res["solvers"][s]["ms_per_interval"] /
