@@ -72,6 +72,7 @@ def __getattr__(name):  # lazy top-level conveniences
         "ScoreModule": ("fastfourierdiffusion_amd.models.score_models", "ScoreModule"),
         "LSTMScoreModule": ("fastfourierdiffusion_amd.models.score_models", "LSTMScoreModule"),
         "MLPScoreModule": ("fastfourierdiffusion_amd.models.score_models", "MLPScoreModule"),
+        "MixtureScoreModule": ("fastfourierdiffusion_amd.models.score_models", "MixtureScoreModule"),
         "VPScheduler": ("fastfourierdiffusion_amd.schedulers.sde", "VPScheduler"),
         "VEScheduler": ("fastfourierdiffusion_amd.schedulers.sde", "VEScheduler"),
         "E2CRFCache": ("fastfourierdiffusion_amd.utils.caching", "E2CRFCache"),

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libffd.so")
 
 FFD_MODEL_TRANSFORMER, FFD_MODEL_LSTM, FFD_MODEL_MLP = 0, 1, 2
+FFD_MODEL_MIXTURE = 3  # the closed-form Gaussian-mixture score (dim_feedforward carries K)
 FFD_SDE_VP, FFD_SDE_VE = 0, 1
 FFD_SOLVER_EULER_MARUYAMA, FFD_SOLVER_ODE_EULER, FFD_SOLVER_ODE_HEUN, FFD_SOLVER_PC = 0, 1, 2, 3
 FFD_SOLVER_ODE_AB2, FFD_SOLVER_DPMPP_2M = 4, 5
@@ -124,6 +125,11 @@ SIGNATURES = {
                                     C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "ffd_cond_project": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, _P, _P, C.c_double, C.c_int, _P, C.c_uint64, C.c_uint64,
                                    C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_mixture_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ffd_mixture_score": (C.c_int, [C.POINTER(SdeDesc), _P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, _P, C.c_size_t, _P]),
+    "ffd_host_mixture_check": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int]),
+    "ffd_mixture_tiling": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ffd_prior": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_dft": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_idft": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),

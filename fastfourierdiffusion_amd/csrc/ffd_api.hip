@@ -44,6 +44,11 @@ struct MlpLayer {
   const float *w0, *b0, *w3, *b3;
 };
 
+// The Gaussian mixture behind FFD_MODEL_MIXTURE: means (K, L, C), log-weights (K), the shared variance (L, C)
+struct MixtureWeights {
+  const float *means, *logw, *var;
+};
+
 struct LstmLayer {
   const float *wih, *whh, *bih, *bhh;
   float *wih_p = nullptr, *bsum = nullptr;
@@ -76,6 +81,8 @@ struct ffd_ctx {
   std::vector<LayerWeights> layers;  // one of the three, by desc.kind (sized by ffd_create: `weights` points into them)
   std::vector<LstmLayer> lstm;
   std::vector<MlpLayer> mlp;
+  MixtureWeights mix{};    // FFD_MODEL_MIXTURE (no layers: the score is closed-form)
+  Grow<float> mix_work;    // the mixture kernel's per-slice partials
   float* G_dev = nullptr;
   std::vector<float> G_host;
   // workspace (ensure_workspace; qkv, ffn_part and the LSTM wavefront's on first use)
@@ -465,6 +472,13 @@ static void bind_weights(ffd_ctx* ctx) {
   const size_t d = m.d_model, C = m.n_channels, L = m.max_len, F = m.dim_feedforward;
   auto bind = [&](const std::string& key, size_t n, const float** field) { ctx->weights.push_back({key, n, field}); };
   ModelWeights& w = ctx->model;
+  if (m.kind == FFD_MODEL_MIXTURE) {  // no network: the three tensors of the mixture (dim_feedforward carries K)
+    const size_t K = std::max(m.dim_feedforward, 0);
+    bind("mixture.means", K * L * C, &ctx->mix.means);
+    bind("mixture.log_weights", K, &ctx->mix.logw);
+    bind("mixture.variance", L * C, &ctx->mix.var);
+    return;
+  }
   if (m.kind == FFD_MODEL_TRANSFORMER) bind("pos_encoder.embedding.weight", L * d, &w.pos);
   bind("time_encoder.W", (d + 1) / 2, &w.time_W);
   bind("time_encoder.dense.weight", d * d, &w.time_dense_w);
@@ -516,11 +530,19 @@ int ffd_create(ffd_ctx** out, const ffd_model_desc* desc, int device) {
   ctx->desc = *desc;
   ctx->device = device;
   *out = ctx;  // returned even on failure so the caller can read the message
+  // the mixture kind has no network: d_model / n_head / num_layers are ignored.  Its "time embedding" is the time
+  // itself, one float per evaluation, so every table and stride the loops size by d_model holds times (d_model = 1).
+  if (ctx->desc.kind == FFD_MODEL_MIXTURE) ctx->desc.d_model = 1, ctx->desc.n_head = 1, ctx->desc.num_layers = 1;
   const ffd_model_desc& m = ctx->desc;
   bind_weights(ctx);
   if (m.n_channels < 1 || m.max_len < 1 || m.num_layers < 1)
     return ctx->fail(FFD_ERR_INVALID, "bad shape: C=%d L=%d NL=%d", m.n_channels, m.max_len, m.num_layers);
-  if (m.kind == FFD_MODEL_MLP) {
+  if (m.kind == FFD_MODEL_MIXTURE) {
+    if (m.dim_feedforward < 1) return ctx->fail(FFD_ERR_INVALID, "mixture: K=%d components", m.dim_feedforward);
+    if (!mixture_shape_supported(1, m.dim_feedforward, m.max_len, m.n_channels))
+      return ctx->fail(FFD_ERR_UNSUPPORTED, "mixture: L * C = %lld (limit %d), K = %d: no kernel for this shape",
+                       (long long)m.max_len * m.n_channels, MIX_MAX_DIM, m.dim_feedforward);
+  } else if (m.kind == FFD_MODEL_MLP) {
     if (m.d_model < 1 || m.dim_feedforward < 1)
       return ctx->fail(FFD_ERR_INVALID, "mlp: d_model=%d d_mlp=%d", m.d_model, m.dim_feedforward);
   } else if (!d_supported(m.d_model)) {
@@ -534,7 +556,7 @@ int ffd_create(ffd_ctx** out, const ffd_model_desc* desc, int device) {
     if (m.dim_feedforward < 64 || m.dim_feedforward % 64 != 0)
       return ctx->fail(FFD_ERR_UNSUPPORTED, "dim_feedforward=%d must be a positive multiple of 64", m.dim_feedforward);
     if (m.max_len > 512) return ctx->fail(FFD_ERR_UNSUPPORTED, "max_len=%d > 512 (attention kernel limit)", m.max_len);
-  } else if (m.kind != FFD_MODEL_LSTM && m.kind != FFD_MODEL_MLP) {
+  } else if (m.kind != FFD_MODEL_LSTM && m.kind != FFD_MODEL_MLP && m.kind != FFD_MODEL_MIXTURE) {
     return ctx->fail(FFD_ERR_UNSUPPORTED, "model kind %d", m.kind);
   }
   if (m.sde != FFD_SDE_VP && m.sde != FFD_SDE_VE) return ctx->fail(FFD_ERR_UNSUPPORTED, "sde kind %d", m.sde);
@@ -593,11 +615,23 @@ int ffd_finalize_weights(ffd_ctx* ctx) {
   if (!ctx) return FFD_ERR_INVALID;
   const ffd_model_desc& m = ctx->desc;
   for (const WeightSlot& w : ctx->weights)
-    if (!w.dev) return ctx->fail(FFD_ERR_STATE, "missing parameter '%s'", w.key.c_str());
+    if (!w.dev)  // (the mixture's tensors are its definition, not a load order: a missing one is a bad argument)
+      return ctx->fail(m.kind == FFD_MODEL_MIXTURE ? FFD_ERR_INVALID : FFD_ERR_STATE, "missing parameter '%s'", w.key.c_str());
   HIPCHECK(hipSetDevice(ctx->device));
   const int d = m.d_model, F = m.dim_feedforward;
   hipStream_t s = nullptr;
-  if (m.kind == FFD_MODEL_TRANSFORMER) {
+  if (m.kind == FFD_MODEL_MIXTURE) {
+    // the values are checked once, on the host: a NaN mean or an all -inf weight vector would otherwise surface as NaN
+    // samples many steps later
+    const size_t D = (size_t)m.max_len * m.n_channels, K = m.dim_feedforward;
+    std::vector<float> mu(K * D), lw(K), var(D);
+    HIPCHECK(hipMemcpy(mu.data(), ctx->mix.means, mu.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(lw.data(), ctx->mix.logw, lw.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(var.data(), ctx->mix.var, var.size() * sizeof(float), hipMemcpyDeviceToHost));
+    const char* why = "";
+    if (int rc = mixture_check(mu.data(), lw.data(), var.data(), (int)K, m.max_len, m.n_channels, &why))
+      return ctx->fail(rc, "mixture: %s", why);
+  } else if (m.kind == FFD_MODEL_TRANSFORMER) {
     // (the one parameter the library writes: nn.Embedding(max_norm) renormalises its rows, transformer.py:13-15)
     HIPCHECK(launch_renorm_rows(const_cast<float*>(ctx->model.pos), m.max_len, d, sqrtf((float)d), s));
     for (LayerWeights& l : ctx->layers) {
@@ -696,6 +730,11 @@ static int ensure_workspace(ffd_ctx* ctx, int B) {
   const ffd_model_desc& m = ctx->desc;
   const size_t M = (size_t)B * m.max_len, d = m.d_model;
   int rc;
+  if (m.kind == FFD_MODEL_MIXTURE) {  // no hidden state: the score, the per-sample times and the slices' partials
+    if ((rc = ensure(ctx, ctx->score, M * m.n_channels))) return rc;
+    if ((rc = ensure(ctx, ctx->temb_b, (size_t)B))) return rc;
+    return ensure(ctx, ctx->mix_work, mixture_work_floats(B, m.dim_feedforward, m.max_len, m.n_channels));
+  }
   if ((rc = ensure(ctx, ctx->h0, M * d))) return rc;
   if ((rc = ensure(ctx, ctx->score, M * m.n_channels))) return rc;
   if ((rc = ensure(ctx, ctx->temb_b, (size_t)B * d))) return rc;
@@ -818,6 +857,14 @@ static int forward_impl(ffd_ctx* ctx, const float* x, const float* temb, int tem
   const ffd_model_desc& m = ctx->desc;
   const int L = m.max_len, C = m.n_channels, d = m.d_model, M = B * L;
   const ModelWeights& mw = ctx->model;
+  if (m.kind == FFD_MODEL_MIXTURE) {
+    // the closed-form score (ffd_mixture.hip): `temb` holds the evaluation's time(s) -- one float shared by the batch
+    // (a row of the trajectory's table, which for this kind is the timestep grid itself) or one per sample
+    TIMED(FFD_K_ATTN, launch_mixture_score(m.sde, m.sde_a, m.sde_b, x, temb, temb_stride ? 1 : 0, ctx->mix.means,
+                                           ctx->mix.logw, ctx->mix.var, ctx->G_dev, score_out, B, m.dim_feedforward, L, C,
+                                           ctx->mix_work.p, s));
+    return FFD_OK;
+  }
   if (m.kind == FFD_MODEL_MLP) {  // MLPScoreModule.forward, score_models.py:406-440
     const int io = L * C, F = m.dim_feedforward;
     // flatten "b t c -> b (t c)" is the memory layout already; time encoding is one (d,) vector per step
@@ -937,12 +984,19 @@ static int check_ready(ffd_ctx* ctx, int B) {
   if (B < 1) return ctx->fail(FFD_ERR_INVALID, "batch size %d", B);
   if ((double)B * ctx->desc.max_len * 4 * ctx->desc.d_model > 2.0e9)
     return ctx->fail(FFD_ERR_UNSUPPORTED, "batch %d too large for 32-bit row indexing; shard the batch", B);
+  if (ctx->desc.kind == FFD_MODEL_MIXTURE &&
+      !mixture_shape_supported(B, ctx->desc.dim_feedforward, ctx->desc.max_len, ctx->desc.n_channels))
+    return ctx->fail(FFD_ERR_UNSUPPORTED, "batch %d too large for the mixture kernel's indexing; shard the batch", B);
   return FFD_OK;
 }
 
 // temb[n][d] for the n timesteps ts on the device, or (ts == nullptr, n = 1) for the scalar t
 static int time_embed(ffd_ctx* ctx, const float* ts, float t, int n, float* temb, hipStream_t s) {
   const ModelWeights& w = ctx->model;
+  if (ctx->desc.kind == FFD_MODEL_MIXTURE) {  // the closed-form score reads the time itself
+    HIPCHECK(launch_mixture_times(ts, t, n, temb, s));
+    return FFD_OK;
+  }
   HIPCHECK(launch_time_embed(ts, t, n, w.time_W, w.time_dense_w, w.time_dense_b, temb, ctx->desc.d_model, s));
   return FFD_OK;
 }
@@ -1119,7 +1173,8 @@ int ffd_cache_tables_read(ffd_ctx* ctx, float* k_out, float* v_out, void* stream
 // Can this model's sampling step unembed inside the SDE-step kernel?  (ffd_sample_batch adds its arguments' alignment.)
 static bool tail_fusable(const ffd_ctx* ctx) {
   const ffd_model_desc& m = ctx->desc;
-  return g_fuse_tail && !ctx->fresca_on && m.kind != FFD_MODEL_MLP && unembed_sde_supported(m.n_channels, m.d_model);
+  return g_fuse_tail && !ctx->fresca_on && m.kind != FFD_MODEL_MLP && m.kind != FFD_MODEL_MIXTURE &&
+         unembed_sde_supported(m.n_channels, m.d_model);
 }
 
 // The steps the two loop entries share.
@@ -1494,6 +1549,9 @@ double ffd_flops_per_sample_step(const ffd_ctx* ctx, int cache_hit) {
   const double L = m.max_len, d = m.d_model, C = m.n_channels, NL = m.num_layers, F = m.dim_feedforward;
   if (m.kind == FFD_MODEL_LSTM) return NL * 2.0 * L * (2.0 * 4.0 * d * d) + 4.0 * L * C * d + 2.0 * d * d;
   if (m.kind == FFD_MODEL_MLP) return NL * 4.0 * d * F + 4.0 * L * C * d + 2.0 * d * d;
+  // mixture (F carries K): per (component, coordinate) the difference FMA, the product with 1 / c and the sum FMA on
+  // the vector pipe (5) and one multiply-add on the matrix cores (2)
+  if (m.kind == FFD_MODEL_MIXTURE) return 7.0 * F * L * C;
   double per_layer = 2.0 * L * d * 3.0 * d + 2.0 * L * L * d + 2.0 * L * L * d + 2.0 * L * d * d + 4.0 * L * d * F;
   if (cache_hit) per_layer -= 2.0 * L * d * 2.0 * d;
   return NL * per_layer + 4.0 * L * C * d + 2.0 * d * d;
@@ -1602,6 +1660,14 @@ const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cac
         by = 4.0 * (2.0 * M * d + 3.0 * d * d + (cache_hit ? 2.0 * L * d : 0.0));
         if (p.attn == ATTN_TWO_KERNEL) by += 4.0 * 2.0 * M * (cache_hit ? d : 3.0 * d);  // q / k / v through HBM
       }
+      if (m.kind == FFD_MODEL_MIXTURE) {
+        // the closed-form mixture score (F carries K): 7 FLOP per (row, component, coordinate); every row tile streams
+        // the means once (mostly from L2 / the Infinity Cache), x in, score out, the slices' partials out and in
+        const double K = F, D = L * C, tiles = cdiv(B, MIX_ROW_TILE), slices = cdiv((int)F, MIX_SLICE);
+        name = "k_mixture_part + k_mixture_merge";
+        fl = 7.0 * B * K * D;
+        by = 4.0 * (tiles * K * D + 2.0 * B * D + 2.0 * slices * B * (D + 2.0));
+      }
       break;
     case FFD_K_OUTPROJ:  // attention output + residual in, LN1 output out
       if (tr && p.oproj_separate) name = "k_linear_res_ln", fl = 2.0 * M * d * d, by = 4.0 * (3.0 * M * d + d * d);
@@ -1655,10 +1721,10 @@ const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cac
         name = "k_sde_step", by = 12.0 * M * C;
       break;
     case FFD_K_EMBED:
-      if (m.kind != FFD_MODEL_MLP) name = "k_embed", fl = 2.0 * M * C * d, by = 4.0 * M * (C + d);
+      if (m.kind != FFD_MODEL_MLP && m.kind != FFD_MODEL_MIXTURE) name = "k_embed", fl = 2.0 * M * C * d, by = 4.0 * M * (C + d);
       break;
     case FFD_K_UNEMBED:
-      if (m.kind != FFD_MODEL_MLP) name = "k_unembed", fl = 2.0 * M * C * d, by = 4.0 * M * (C + d);
+      if (m.kind != FFD_MODEL_MLP && m.kind != FFD_MODEL_MIXTURE) name = "k_unembed", fl = 2.0 * M * C * d, by = 4.0 * M * (C + d);
       break;
     default: break;
   }

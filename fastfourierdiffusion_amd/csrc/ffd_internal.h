@@ -446,6 +446,23 @@ static_assert(FFT_MAX_MIXED_LEN == 6826, "ffd.h states this length");
 hipError_t launch_fresca(const float* in, float* out, float* work, int B, int L, int C, float low, float high,
                          double cutoff_ratio, int strategy, hipStream_t s);
 
+// ---- the closed-form Gaussian-mixture score (ffd_mixture.hip; include/ffd.h ffd_mixture_score) ----
+// Tiling: 16 rows x 16 components per step, slices of 512 components per workgroup column, L * C up to 1024.  The
+// tiling depends on K and L * C alone (never on B): a row's bits do not depend on the batch it is evaluated in.
+constexpr int MIX_ROW_TILE = 16, MIX_COMP_TILE = 16, MIX_SLICE = 512, MIX_MAX_DIM = 1024;
+bool mixture_shape_supported(int B, int K, int L, int C);
+size_t mixture_work_floats(int B, int K, int L, int C);  // 0 for a shape the launch refuses
+// t: device, row r reads t[r * t_stride] (t_stride 0 | 1); var nullptr: v = 0; work: mixture_work_floats floats.
+// hipErrorInvalidValue for an unsupported shape.
+hipError_t launch_mixture_score(int sde, double sa, double sb, const float* x, const float* t, int t_stride,
+                                const float* means, const float* logw, const float* var, const float* G, float* out, int B,
+                                int K, int L, int C, float* work, hipStream_t s);
+// out[i] = ts[i] (ts == nullptr: the immediate t_imm), n floats: the mixture kind's "time embedding" is the time itself
+hipError_t launch_mixture_times(const float* ts, float t_imm, int n, float* out, hipStream_t s);
+// host: FFD_OK | FFD_ERR_INVALID (non-finite mean, negative / non-finite variance, NaN / +inf log-weight, all -inf) |
+// FFD_ERR_UNSUPPORTED (L * C over MIX_MAX_DIM); *why (may be nullptr) names the reason (static string)
+int mixture_check(const float* means, const float* logw, const float* var, int K, int L, int C, const char** why);
+
 // ---- the kernels of one transformer layer / of the LSTM stack at a batch (ffd_api.hip) --------------------------
 // plan_layer is the one place that orders the forms and picks their instances; each heuristic above answers for its own
 // form only, and the launchers map the plan to a kernel without reading a knob.

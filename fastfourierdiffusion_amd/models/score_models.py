@@ -1,4 +1,5 @@
-"""``fdiff.models.score_models`` mirror: ``ScoreModule`` and ``LSTMScoreModule``.
+"""``fdiff.models.score_models`` mirror: ``ScoreModule``, ``LSTMScoreModule`` and ``MLPScoreModule``; and, beyond the
+reference, ``MixtureScoreModule``: the closed-form score of a diffused Gaussian mixture.
 
 Drop-in for the *sampling* surface of the reference classes
 (src/fdiff/models/score_models.py:24-289, 443-511): same constructor arguments,
@@ -350,4 +351,123 @@ class MLPScoreModule(ScoreModule):
 
     def forward(self, batch: DiffusableBatch) -> torch.Tensor:  # type: ignore[override]
         """score_models.py:406-440 (no recompute_tokens / caching, Q9)."""
+        return super().forward(batch)
+
+
+class _MixtureTensors(nn.Module):
+    """Holds the three tensors of a Gaussian mixture under the ``mixture.*`` state_dict keys."""
+
+    def __init__(self, means: torch.Tensor, log_weights: torch.Tensor, variance: torch.Tensor) -> None:
+        super().__init__()
+        self.means = nn.Parameter(means, requires_grad=False)
+        self.log_weights = nn.Parameter(log_weights, requires_grad=False)
+        self.variance = nn.Parameter(variance, requires_grad=False)
+
+
+class MixtureScoreModule(ScoreModule):
+    """The exact score of a diffused Gaussian mixture (an extension; no counterpart in the reference): the data
+    distribution is ``sum_i w_i N(means_i, diag(variance))`` in the diffused domain, and ``forward`` returns the score of
+    its marginal at each sample's time in closed form (include/ffd.h ``ffd_mixture_score``) -- the "optimal denoiser"
+    every trained score network approximates.  ``variance = 0`` is the empirical distribution of the rows of ``means``.
+    No network is built: the three tensors are the module's only state (``mixture.means``, ``mixture.log_weights``,
+    ``mixture.variance``).  It is accepted wherever a score model is: ``DiffusionSampler`` (every solver, correctors,
+    conditioning), ``evaluate_loss`` / ``validation_step``, sharding.  There is no cache (``enable_caching`` raises as for
+    the LSTM)."""
+
+    _kind = N.FFD_MODEL_MIXTURE
+
+    def __init__(self, n_channels: int, max_len: int, noise_scheduler: SDE, means: torch.Tensor,
+                 log_weights: Optional[torch.Tensor] = None, variance: Optional[torch.Tensor] = None,
+                 fourier_noise_scaling: bool = True, num_training_steps: int = 1000,
+                 likelihood_weighting: bool = False) -> None:
+        nn.Module.__init__(self)
+        if not isinstance(noise_scheduler, SDE):
+            raise NotImplementedError(f"Scheduler {noise_scheduler} not implemented yet")
+        means = torch.as_tensor(means, dtype=torch.float32)
+        if means.dim() != 3 or means.shape[0] < 1 or tuple(means.shape[1:]) != (max_len, n_channels):
+            raise ValueError(f"means must be (K >= 1, {max_len}, {n_channels}), got {tuple(means.shape)}")
+        K = means.shape[0]
+        if log_weights is None:
+            log_weights = torch.full((K,), -float(torch.log(torch.tensor(float(K)))))
+        log_weights = torch.as_tensor(log_weights, dtype=torch.float32)
+        if tuple(log_weights.shape) != (K,):
+            raise ValueError(f"log_weights must be ({K},), got {tuple(log_weights.shape)}")
+        if variance is None:
+            variance = torch.zeros(max_len, n_channels)
+        variance = torch.as_tensor(variance, dtype=torch.float32)
+        if tuple(variance.shape) != (max_len, n_channels):
+            raise ValueError(f"variance must be ({max_len}, {n_channels}), got {tuple(variance.shape)}")
+        if not bool(torch.isfinite(means).all()):
+            raise ValueError("means must be finite")
+        if not bool((torch.isfinite(variance) & (variance >= 0)).all()):
+            raise ValueError("variance must be finite and >= 0")
+        if bool(torch.isnan(log_weights).any()) or bool((log_weights == float("inf")).any()) or \
+                not bool((log_weights > -float("inf")).any()):
+            raise ValueError("log_weights must be free of NaN and +inf, and not all -inf")
+        self.max_len = max_len
+        self.n_channels = n_channels
+        self.noise_scheduler = noise_scheduler
+        self.num_warmup_steps = num_training_steps // 10
+        self.num_training_steps = num_training_steps
+        self.lr_max = 0.0
+        self.scale_noise = fourier_noise_scaling
+        self.likelihood_weighting = likelihood_weighting
+        self.n_components = K
+        self.d_model, self.n_head, self.num_layers = 1, 1, 1  # (ignored by the native kind)
+        self.dim_feedforward = K                              # ffd_model_desc.dim_feedforward carries K
+        self.mixture = _MixtureTensors(means.detach().clone().contiguous(), log_weights.detach().clone().contiguous(),
+                                       variance.detach().clone().contiguous())
+        self.cache = None
+        self.use_cache = False
+        self.cached_backbone = None
+        self._first_cache = None
+        self._native = None
+        self.training_loss_fn, self.validation_loss_fn = self.set_loss_fn()
+
+    @classmethod
+    def from_data(cls, X: torch.Tensor, noise_scheduler: SDE, bandwidth=0.0, weights: Optional[torch.Tensor] = None,
+                  **kw) -> "MixtureScoreModule":
+        """The (kernel-smoothed) empirical distribution of a dataset: ``X`` (N, L, C), already in the diffused domain,
+        becomes the means; ``weights`` (N,) > 0 are normalised (default: uniform); ``bandwidth``, a float or an (L, C)
+        tensor of standard deviations, gives ``variance = bandwidth ** 2``."""
+        X = torch.as_tensor(X, dtype=torch.float32)
+        if X.dim() != 3:
+            raise ValueError(f"X must be (N, L, C), got {tuple(X.shape)}")
+        _, L, Cn = X.shape
+        bw = torch.as_tensor(bandwidth, dtype=torch.float32)
+        if bw.dim() == 0:
+            bw = bw.expand(L, Cn)
+        if tuple(bw.shape) != (L, Cn):
+            raise ValueError(f"bandwidth must be a float or ({L}, {Cn}), got {tuple(bw.shape)}")
+        log_w = None
+        if weights is not None:
+            w = torch.as_tensor(weights, dtype=torch.float64)
+            if tuple(w.shape) != (X.shape[0],) or not bool((w >= 0).all()) or not float(w.sum()) > 0:
+                raise ValueError("weights must be (N,), >= 0 and not all zero")
+            log_w = torch.log(w / w.sum()).to(torch.float32)
+        return cls(n_channels=Cn, max_len=L, noise_scheduler=noise_scheduler, means=X, log_weights=log_w,
+                   variance=(bw * bw).contiguous(), **kw)
+
+    @classmethod
+    def load_from_checkpoint(cls, checkpoint_path, map_location=None, hparams_file=None, strict: bool = True,
+                             weights_only=None, **kwargs):
+        """As ScoreModule.load_from_checkpoint; the mixture's tensors come from the ``state_dict`` itself."""
+        import inspect
+
+        from ..schedulers import sde as _sde
+
+        with torch.serialization.safe_globals([_sde.VPScheduler, _sde.VEScheduler]):
+            ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
+        hp = dict(ckpt.get("hyper_parameters", {}))
+        hp.update(kwargs)
+        sd = ckpt["state_dict"]
+        accepted = set(inspect.signature(cls.__init__).parameters) - {"self", "means", "log_weights", "variance"}
+        model = cls(means=sd["mixture.means"], log_weights=sd["mixture.log_weights"], variance=sd["mixture.variance"],
+                    **{k: v for k, v in hp.items() if k in accepted})
+        model.load_state_dict(sd, strict=strict)
+        if map_location is not None:
+            model = model.to(map_location)
+        return model
+
+    def forward(self, batch: DiffusableBatch) -> torch.Tensor:  # type: ignore[override]
         return super().forward(batch)

@@ -47,6 +47,10 @@ typedef enum {
 } ffd_status;
 
 enum { FFD_MODEL_TRANSFORMER = 0, FFD_MODEL_LSTM = 1, FFD_MODEL_MLP = 2 };
+/* No network: the exact score of a diffused Gaussian mixture (see ffd_mixture_score), an extension beyond the reference.
+ * Weights: mixture.means (K L C), mixture.log_weights (K), mixture.variance (L C).  Every entry point that takes a score
+ * model takes it; the E2-CRF cache is FFD_ERR_UNSUPPORTED, as for the other non-transformer kinds. */
+enum { FFD_MODEL_MIXTURE = 3 };
 enum { FFD_SDE_VP = 0, FFD_SDE_VE = 1 };
 
 /* Model + scheduler hyper-parameters.
@@ -60,7 +64,8 @@ typedef struct {
   int32_t d_model;         /* d   (8, 16, 24, 32, 48, 60, 64 or 72 in this build; d / n_head in {2,3,4,5,6,8}; any d for mlp) */
   int32_t n_head;          /* H   (ignored for lstm) */
   int32_t num_layers;      /* NL */
-  int32_t dim_feedforward; /* F   (PyTorch default 2048, score_models.py:61-63); multiple of 64.  mlp: d_mlp (any >= 1) */
+  int32_t dim_feedforward; /* F   (PyTorch default 2048, score_models.py:61-63); multiple of 64.  mlp: d_mlp (any >= 1).
+                            * mixture: K, the number of components (>= 1); d_model, n_head, num_layers are ignored */
   int32_t sde;             /* FFD_SDE_* */
   double sde_a;            /* VP: beta_min   | VE: sigma_min */
   double sde_b;            /* VP: beta_max   | VE: sigma_max */
@@ -106,11 +111,13 @@ const char* ffd_version(void);
  *   backbone.layers.{i}.self_attn.{in_proj_weight (3d,d),in_proj_bias,out_proj.weight,out_proj.bias}
  *   backbone.layers.{i}.{linear1,linear2}.{weight,bias}  backbone.layers.{i}.{norm1,norm2}.{weight,bias}
  *   backbone.{i}.{weight_ih_l0 (4d,d),weight_hh_l0 (4d,d),bias_ih_l0,bias_hh_l0}   (lstm)
+ *   mixture.means (K L C)   mixture.log_weights (K)   mixture.variance (L C)         (mixture: these three and no others)
  * Replaces nn.Module.load_state_dict / load_from_checkpoint (cmd/sample.py:68-75). Synchronous. */
 int ffd_load_weight(ffd_ctx* ctx, const char* name, const float* data, size_t n);
 /* Validate that every parameter was supplied, apply the nn.Embedding(max_norm)
  * renormalisation to its fixed point (transformer.py:13-15) and
- * re-pack GEMM weights into MFMA fragment order.  Synchronous. */
+ * re-pack GEMM weights into MFMA fragment order.  Synchronous.
+ * Mixture: FFD_ERR_INVALID for a missing tensor and for values ffd_host_mixture_check refuses. */
 int ffd_finalize_weights(ffd_ctx* ctx);
 
 /* ---- scheduler tables (host only; no device needed) --------------------- */
@@ -304,6 +311,43 @@ enum { FFD_COND_FREQUENCY = 0, FFD_COND_TIME = 1 };
 int ffd_cond_project(const ffd_sde_desc* sde, float* x, const float* obs, const float* mask, const float* std,
                      const float* G, double t, int noiseless, const float* z, uint64_t seed, uint64_t sample_offset,
                      uint32_t tag, int obs_batch, int domain, int B, int L, int C, void* stream);
+
+/* ---- the closed-form score of a diffused Gaussian mixture (an extension: the "optimal denoiser" every trained score
+ * network approximates; the backbone behind FFD_MODEL_MIXTURE) ----
+ * Data distribution p_0 = sum_i w_i N(mu_i, diag(v)): means (K, L, C), log_weights (K), one shared per-coordinate
+ * variance (L, C) >= 0 (NULL: v = 0, the empirical distribution of the rows of `means`).  Under the forward marginal
+ * x_t = alpha(t) x_0 + sigma(t) G_l z of the SDE (alpha, sigma as in ffd_cond_project; G as in ffd_sde_step), per row
+ * of x (B, L, C):
+ *     c_lc    = alpha^2 v_lc + sigma^2 G_l^2
+ *     logit_i = log w_i - 1/2 sum_lc (x_lc - alpha mu_i,lc)^2 / c_lc
+ *     r       = softmax_i(logit)
+ *     d_lc    = alpha sum_i r_i mu_i,lc - x_lc,        score_out = d / c.
+ * Row b reads its time from t[b * t_stride] (device fp32; t_stride 0: one time shared by the batch, 1: per sample --
+ * one code path, the same bits).  The time is widened to double; alpha and sigma^2 are formed in double (VP: sigma^2 =
+ * -expm1(2 log alpha)) and rounded once.  The logits are evaluated in DIFFERENCE form in fp32 -- t = x - alpha mu (one
+ * FMA), then sum t (t / c) -- never as |x|^2 - 2 x . alpha mu + |alpha mu|^2, which cancels catastrophically at small t
+ * (1.6e-4 of the data scale against 5e-7).  The softmax subtracts the running maximum: a component
+ * with log w = -inf is ignored exactly, logits of -1e8 and below give no NaN or Inf (the nearest component wins), K = 1
+ * works.  sum_i r_i mu_i runs on the fp32 matrix cores (exact fp32).
+ * Launches: rows in tiles of 16 x components in slices of 512 (ffd_mixture_tiling), each leaving (max, sum, weighted sum)
+ * per row in `work`; then one merge launch combines the slices in ascending order.  No atomics: bit-identical from run
+ * to run; the tiling depends on K and L C alone, so a row's result does not depend on B or on its place in the batch.
+ * work: device scratch of at least ffd_mixture_work_floats(B, K, L, C) floats (0 for a shape the call refuses), free
+ * again when the call's work on the stream is done.  score_out may be x.  Context-free, stream ordered, no host
+ * synchronisation.  c must be > 0 (t > 0, G != 0).
+ * FFD_ERR_INVALID before any device work: a null pointer (variance excepted), B, K, L, C < 1, t_stride not 0 or 1,
+ * work_floats too small; FFD_ERR_UNSUPPORTED: an unknown SDE, L * C > 1024, K > 33 million, B * L * C >= 2^31.
+ * The values are the caller's contract here; ffd_host_mixture_check (host arrays; what ffd_finalize_weights applies)
+ * returns FFD_ERR_INVALID for a non-finite mean, a negative or non-finite variance, a NaN or +inf log-weight, or
+ * log-weights that are all -inf, and FFD_ERR_UNSUPPORTED for L * C over the limit. */
+size_t ffd_mixture_work_floats(int B, int K, int L, int C);
+int ffd_mixture_score(const ffd_sde_desc* sde, const float* x, const float* t, int t_stride, const float* means,
+                      const float* log_weights, const float* variance, const float* G, float* score_out, int B, int K,
+                      int L, int C, float* work, size_t work_floats, void* stream);
+int ffd_host_mixture_check(const float* means, const float* log_weights, const float* variance, int K, int L, int C);
+/* Host only: the kernel's rows per tile, components per tile, components per slice and the largest L * C (any pointer
+ * may be NULL). */
+int ffd_mixture_tiling(int* row_tile, int* comp_tile, int* slice, int* max_dim);
 
 /* SDE.prior_sampling (sde.py:79-87, 125-127): x <- G (.) z  (VE: * sigma_max);
  * z == NULL draws on device (Philox stream tag 0xFFFFFFFF). */
