@@ -93,7 +93,13 @@ SIGNATURES = {
     "ffd_col_mean_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "ffd_col_mean": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "ffd_w2_bench_kernels": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _F, _P]),
-    "ffd_sm_draw_times": (C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_uint64, C.c_uint64, _P]),
+    "ffd_ens_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]),
+    "ffd_ens_pointwise": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
+                                    _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ffd_ens_energy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_ens_bench_energy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, C.c_int,
+                                       _F, _P]),
+    "ffd_sm_draw_times":(C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_uint64, C.c_uint64, _P]),
     "ffd_sm_perturb": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_sm_loss": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_sm_eval_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, C.c_int, _P]),

@@ -463,6 +463,13 @@ hipError_t launch_mixture_times(const float* ts, float t_imm, int n, float* out,
 // FFD_ERR_UNSUPPORTED (L * C over MIX_MAX_DIM); *why (may be nullptr) names the reason (static string)
 int mixture_check(const float* means, const float* logw, const float* var, int K, int L, int C, const char** why);
 
+// ---- pieces of the sample metrics (ffd_metrics.hip) that the ensemble scores (ffd_ensemble.hip) run as they are ----
+// P (Kb, N) = columns [f0, f0 + Kb) of X (N, D): the tiled transpose through LDS; Kb <= 32768 * 32
+hipError_t launch_w2_columns(const float* X, float* P, int N, int D, int f0, int Kb, hipStream_t s);
+// Sort the Kb <= 65535 rows of `rows` (Kb, N) ascending in place (8192-key chunks, then merge passes; -0.0 before +0.0);
+// `scratch` holds Kb * N more words
+hipError_t launch_w2_sort(float* rows, float* scratch, int N, int Kb, hipStream_t s);
+
 // ---- the kernels of one transformer layer / of the LSTM stack at a batch (ffd_api.hip) --------------------------
 // plan_layer is the one place that orders the forms and picks their instances; each heuristic above answers for its own
 // form only, and the launchers map the plan to a kernel without reading a knob.

@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void k_w2_columns(const float* __restrict__ X,
 }
 
 // P (Kb, N) = columns [f0, f0 + Kb) of X (N, D)
-static hipError_t launch_w2_columns(const float* X, float* P, int N, int D, int f0, int Kb, hipStream_t s) {
+hipError_t launch_w2_columns(const float* X, float* P, int N, int D, int f0, int Kb, hipStream_t s) {
   dim3 grid(cdiv(N, 32), cdiv(Kb, 32));
   hipLaunchKernelGGL(k_w2_columns, grid, dim3(256), 0, s, X, P, N, D, f0, Kb);
   return hipGetLastError();
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256) void k_w2_merge(const uint32_t* __restrict__ i
 }
 
 // Sort the Kb rows of `rows` (Kb, N) ascending in place; `scratch` holds Kb * N more words.
-static hipError_t launch_w2_sort(float* rows, float* scratch, int N, int Kb, hipStream_t s) {
+hipError_t launch_w2_sort(float* rows, float* scratch, int N, int Kb, hipStream_t s) {
   int passes = 0;
   for (long long R = SORT_CHUNK; R < N; R <<= 1) ++passes;
   uint32_t* buf[2] = {(uint32_t*)rows, (uint32_t*)scratch};

@@ -1,0 +1,1 @@
+from .forecast import ensemble_scores  # noqa: F401

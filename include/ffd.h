@@ -536,6 +536,47 @@ int ffd_col_mean(const float* x, int n, int D, float* mean_out, void* work, size
 int ffd_w2_bench_kernels(const float* x, int n, int D, const float* dirs, int K, float* rows, float* scratch,
                          const float* other_rows, int m, double* dist, int iters, float* ms_out, void* stream);
 
+/* ---- scores of a forecast / imputation ensemble against the truth (an extension beyond the reference) ----
+ * ens (S, m, D): S series, m members each, D = L * C coordinates as the samplers return them; truth (S, D);
+ * weight NULL (all ones) or (weight_batch, D) with weight_batch 1 (shared) or S, entries 0 or 1: a coordinate with
+ * weight 0 (an observed one) is excluded from every score and its per-point outputs are written as 0.  All fp32 on the
+ * device, dense row-major.  With x_(1) <= ... <= x_(m) the sorted members of one point and y its truth:
+ *   crps[s,d]     = (1/m) sum_i |x_i - y| - (1/Z) sum_i (2 i - m - 1) x_(i);  Z = m^2, or m (m - 1) with fair != 0
+ *                   (Ferro's unbiased estimator, needs m >= 2)
+ *   crps_mean[s]  = the mean of crps[s,:] over the coordinates with weight 1 (0 if there is none)
+ *   quant[q,s,d]  = numpy's default (type 7, linear) quantile of the m members at level levels[q] in [0, 1]: with
+ *                   h = (m - 1) p the value x_(floor(h)+1) + (h - floor(h)) (x_(floor(h)+2) - x_(floor(h)+1)), in fp64 with
+ *                   numpy's own rounding order (levels 0 and 1: the minimum and maximum themselves); 1 <= n_q <= 64
+ *   below, equal  = the number of members < y and == y (the caller forms rank / PIT and coverage from them)
+ *   energy[s]     = (1/m) sum_i ||x_i - y||_w - (1/(2Z)) sum_i sum_j ||x_i - x_j||_w,  ||v||_w = sqrt(sum_d w_d v_d^2)
+ * crps, below, equal: (S, D); quant: (n_q, S, D); crps_mean, energy: (S); doubles / int32 on the device.  `levels` is a
+ * HOST array of n_q doubles.  Any output pointer of ffd_ens_pointwise may be NULL: that output is skipped.
+ * Per point: the tiled transpose and the segmented sort of the Wasserstein metrics, then one kernel that reads a sorted
+ * row once.  Energy: the pair term from the Gram matrix (exact-fp32 MFMA) of the rows centred on the series' ensemble
+ * mean -- uncentred it cancels for a tight ensemble far from the origin -- the truth term in difference form in fp64.
+ * Every reduction is a fixed-order fp64 tree without atomics and every tiling depends on (m, D) alone: a series' outputs
+ * depend on its own data only, are bit-identical from run to run, for a series scored alone or inside a batch, and for
+ * every work_bytes.  NaN input: unspecified.  Context-free, stream ordered, no host synchronisation.
+ * `work`: device scratch, 16-byte aligned, of ffd_ens_work_bytes(S, m, D, n_q, budget) bytes, which serves both calls:
+ * the larger of 8 S D + 8 m rb (rb = the rows (s, d) sorted at once) and sb * (the energy score's need per series: about
+ * 4 m (16 ceil(D / 16) + 3) bytes), with rb, sb as large as `budget_bytes` allows, at least 1: a smaller buffer means more
+ * blocks, never other results.  0 for arguments the calls refuse.
+ * FFD_ERR_INVALID before any device work: a null pointer (weight and skipped outputs excepted), S, m, D < 1, fair with
+ * m < 2, a level outside [0, 1], n_q > 64, weight_batch not 1 or S, work_bytes below one block's need;
+ * FFD_ERR_UNSUPPORTED: S, m or D > 2^20. */
+size_t ffd_ens_work_bytes(int S, int m, int D, int n_q, size_t budget_bytes);
+int ffd_ens_pointwise(const float* ens, const float* truth, const float* weight, int weight_batch, int S, int m, int D,
+                      const double* levels, int n_q, int fair, double* crps_out, double* crps_mean_out, double* quant_out,
+                      int* below_out, int* equal_out, void* work, size_t work_bytes, void* stream);
+int ffd_ens_energy(const float* ens, const float* truth, const float* weight, int weight_batch, int S, int m, int D, int fair,
+                   double* energy_out, void* work, size_t work_bytes, void* stream);
+/* Benchmark helper (tools/ensemble_bench.py): ffd_ens_energy with HIP events between its stages, `iters` times after one
+ * warm-up; the workspace must take all S series in one block (FFD_ERR_INVALID otherwise).  ms_out[0] = mean milliseconds
+ * of the ensemble mean + centring + truth term, ms_out[1] = of the pair kernel.  Synchronous. */
+int ffd_ens_bench_energy(const float* ens, const float* truth, const float* weight, int weight_batch, int S, int m, int D,
+                         int fair, double* energy_out, void* work, size_t work_bytes, int iters, float* ms_out,
+                         void* stream);
+
 /* ---- denoising score-matching loss: the `val/loss` of ScoreModule.validation_step (src/fdiff/utils/losses.py) ----
  * Per sample b, with std[b,l] = sigma[b] * G[l] and n = L * C (losses.py:68-80, sde.py:106-123,187-210):
  *   x_noisy = mean_coeff[b] * x0 + std[b,l] * z                  r = score + z / std[b,l]
