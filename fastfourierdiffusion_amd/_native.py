@@ -131,6 +131,9 @@ SIGNATURES = {
                                     C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "ffd_cond_project": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, _P, _P, C.c_double, C.c_int, _P, C.c_uint64, C.c_uint64,
                                    C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_host_transition_coef": (C.c_int, [C.POINTER(SdeDesc), C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "ffd_forward_transition": (C.c_int, [C.POINTER(SdeDesc), _P, _P, C.c_double, C.c_double, _P, C.c_uint64, C.c_uint64,
+                                         C.c_uint32, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_mixture_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ffd_mixture_score": (C.c_int, [C.POINTER(SdeDesc), _P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int,
                                     C.c_int, _P, C.c_size_t, _P]),
@@ -161,6 +164,10 @@ SIGNATURES = {
                                       C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int, C.c_int, _P]),
     "ffd_sample_batch_cond": (C.c_int, [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float,
                                         C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int, C.c_int, C.POINTER(CondCfg), _P]),
+    "ffd_host_resample_visits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "ffd_host_resample_visit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ffd_sample_batch_resample": (C.c_int, [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, _P, C.POINTER(CondCfg), _P]),
     "ffd_flops_per_sample_step": (C.c_double, [_P, C.c_int]),
     "ffd_ffn_flops_per_launch": (C.c_double, [_P, C.c_int]),
     "ffd_kernel_timing_begin": (C.c_int, [_P, C.c_uint32, C.c_int]),

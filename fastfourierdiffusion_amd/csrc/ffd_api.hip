@@ -1408,22 +1408,58 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
   return FFD_OK;
 }
 
+// The visit schedule of resampled conditional sampling (include/ffd.h ffd_host_resample_visit).  Blocks of `jump` grid
+// indices (the last may be shorter), each run `resample` times in a row: all blocks before block k are full, so block k
+// starts at visit k r j.  *q_out: how many transitions precede this visit's own (the ordinal of the one behind it).
+static int resample_visit(int n_steps, int jump, int resample, int visit, int* step_out, int* back_to_out, int* q_out) {
+  const int64_t j = jump < n_steps ? jump : n_steps, r = resample, n_blocks = (n_steps + j - 1) / j;
+  int64_t k = visit / (r * j);
+  if (k > n_blocks - 1) k = n_blocks - 1;
+  const int64_t i0 = k * j, len = n_steps - i0 < j ? n_steps - i0 : j, w = visit - k * r * j;
+  const int64_t pass = w / len, pos = w % len;
+  *step_out = (int)(i0 + pos);
+  *back_to_out = pos == len - 1 && pass < r - 1 ? (int)i0 : -1;
+  *q_out = (int)(k * (r - 1) + pass);
+  return FFD_OK;
+}
+
+int ffd_host_resample_visits(int n_steps, int jump, int resample) {
+  if (n_steps < 1 || jump < 1 || resample < 1 || (int64_t)n_steps * resample > 0x7FFFFFFFll) return FFD_ERR_INVALID;
+  return n_steps * resample;
+}
+
+int ffd_host_resample_visit(int n_steps, int jump, int resample, int visit, int* step_out, int* back_to_out) {
+  const int n = ffd_host_resample_visits(n_steps, jump, resample);
+  if (n < 1 || visit < 0 || visit >= n || !step_out || !back_to_out) return FFD_ERR_INVALID;
+  int q;
+  return resample_visit(n_steps, jump, resample, visit, step_out, back_to_out, &q);
+}
+
 // Predictor-corrector sampling: n_corrector Langevin corrector steps (ffd_langevin.hip), then the Euler-Maruyama
 // predictor of ffd_sample_batch, per reverse step.  Every evaluation after a step's first is a pure cache hit.
 // cond != nullptr (ffd_sample_batch_cond): one projection onto the observation behind every update, and z_inject
-// holds two draws per update (its own, then the projection's).  The arguments' first checks are the callers'.
+// holds two draws per update (its own, then the projection's).  resample > 1 (ffd_sample_batch_resample): first_step and
+// n_run count VISITS of the schedule above, and a visit that ends a pass of its block is followed by one forward
+// transition back to the block's first time level (one more slab of z_inject).  The arguments' first checks are the
+// callers'.
 static int pc_loop(ffd_ctx* ctx, const char* who, float* x, int B, const float* timesteps, int n_steps, float step_size,
                    int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed, uint64_t sample_offset,
-                   const float* z_inject, int use_cache, int global_step0, const ffd_cond_cfg* cond, void* stream) {
+                   const float* z_inject, int use_cache, int global_step0, const ffd_cond_cfg* cond, int jump, int resample,
+                   void* stream) {
   int rc = check_ready(ctx, B);
   if (rc) return rc;
-  if (!x || !timesteps || n_steps < 1 || first_step < 0 || n_run < 0 || first_step + n_run > n_steps)
-    return ctx->fail(FFD_ERR_INVALID, "bad argument to %s (n_steps=%d first=%d run=%d)", who, n_steps, first_step, n_run);
+  const int n_visits = n_steps < 1 ? 0 : ffd_host_resample_visits(n_steps, jump, resample);
+  if (!x || !timesteps || n_visits < 1 || first_step < 0 || n_run < 0 || n_run > n_visits - first_step)
+    return ctx->fail(FFD_ERR_INVALID, "bad argument to %s (n_steps=%d jump=%d resample=%d first=%d run=%d)", who, n_steps,
+                     jump, resample, first_step, n_run);
   if (!cond && (int64_t)n_steps * n_corrector > 0x7FFFFFF0ll)
     return ctx->fail(FFD_ERR_INVALID, "n_steps * n_corrector exceeds the corrector's Philox tag range");
   if (cond) {
     if ((int64_t)n_steps * ((int64_t)n_corrector + 1) > 0x3FFFFFF0ll)
       return ctx->fail(FFD_ERR_INVALID, "n_steps * (n_corrector + 1) exceeds the projection's Philox tag range");
+    for (int i = 0; resample > 1 && i < n_steps; ++i)  // a transition runs from a later grid point (or 0) back to an earlier
+      if (!(timesteps[i] >= 0.f) || !std::isfinite(timesteps[i]) || (i > 0 && timesteps[i] > timesteps[i - 1]))
+        return ctx->fail(FFD_ERR_INVALID, "resampling needs finite, non-increasing timesteps >= 0 (index %d)", i);
     if (!cond->obs || !cond->mask) return ctx->fail(FFD_ERR_INVALID, "conditioning needs obs and mask");
     if (cond->obs_batch != 1 && cond->obs_batch != B)
       return ctx->fail(FFD_ERR_INVALID, "obs_batch must be 1 or B, got %d", cond->obs_batch);
@@ -1466,10 +1502,15 @@ static int pc_loop(ffd_ctx* ctx, const char* who, float* x, int B, const float* 
     return launch_cond_project(x, cond->obs, cond->mask, cond->std, ctx->G_dev, mc, sigma, noiseless, z, seed, elem_off, tag,
                                cond->obs_batch, B, L, C, s);
   };
+  const float* znext = z_inject;  // flat, in execution order: a visit's updates, then its transition's slab
   for (int j = 0; j < n_run; ++j) {
-    const int i = first_step + j;
+    // visit u of the schedule runs grid index i; without resampling the two are the same.  The Philox tags count visits.
+    const int u = first_step + j;
+    int i = u, back_to = -1, q = 0;
+    if (resample > 1) resample_visit(n_steps, jump, resample, u, &i, &back_to, &q);
     const double t = (double)timesteps[i];
-    const float* zj = z_inject ? z_inject + (size_t)j * (n_corrector + 1) * zstride : nullptr;
+    const float* zj = znext;
+    if (znext) znext += (size_t)(n_corrector + 1) * zstride + (back_to >= 0 ? slab : 0);
     for (int k = 0; k <= n_corrector; ++k) {  // k == n_corrector: the predictor
       const bool predictor = k == n_corrector;
       int n_rec = use_cache ? 0 : -1;
@@ -1488,21 +1529,29 @@ static int pc_loop(ffd_ctx* ctx, const char* who, float* x, int B, const float* 
       if (!predictor)
         TIMED(FFD_K_SDE, launch_langevin(x, score, zk, ctx->G_dev, langevin_alpha(m.sde, m.sde_a, m.sde_b, t, step_size),
                                          (double)snr, norm, seed, elem_off,
-                                         0x80000000u + (uint32_t)i * (uint32_t)n_corrector + (uint32_t)k, B, L, C, nullptr,
+                                         0x80000000u + (uint32_t)u * (uint32_t)n_corrector + (uint32_t)k, B, L, C, nullptr,
                                          ctx->lv_work.p, s));
       else if (hidden)
         TIMED(FFD_K_SDE, launch_unembed_sde(hidden, ctx->model.unembed_w, ctx->model.unembed_b, x, zk, ctx->G_dev,
-                                            sde_params(m.sde, m.sde_a, m.sde_b, t, step_size), seed, elem_off, (uint32_t)i,
+                                            sde_params(m.sde, m.sde_a, m.sde_b, t, step_size), seed, elem_off, (uint32_t)u,
                                             B, L, C, d, s));
       else
         TIMED(FFD_K_SDE, launch_sde_step(x, score, zk, ctx->G_dev, sde_params(m.sde, m.sde_a, m.sde_b, t, step_size), seed,
-                                         elem_off, (uint32_t)i, B, L, C, s));
+                                         elem_off, (uint32_t)u, B, L, C, s));
       if (cond)
         TIMED(FFD_K_SDE, project(t, 0, zk ? zk + slab : nullptr,
-                                 0xC0000000u + (uint32_t)i * (uint32_t)(n_corrector + 1) + (uint32_t)k));
+                                 0xC0000000u + (uint32_t)u * (uint32_t)(n_corrector + 1) + (uint32_t)k));
+    }
+    if (back_to >= 0) {  // the block [back_to, i] runs again: diffuse forward from its end level to its first
+      double c[2];
+      const double s_end = i + 1 == n_steps ? 0.0 : (double)timesteps[i + 1];
+      transition_coef(m.sde, m.sde_a, m.sde_b, s_end, (double)timesteps[back_to], c);  // (0 <= s_end <= t: checked above)
+      TIMED(FFD_K_SDE, launch_forward_transition(x, ctx->G_dev, (float)c[0], (float)c[1],
+                                                 zj ? zj + (size_t)(n_corrector + 1) * zstride : nullptr, seed, elem_off,
+                                                 0xE0000000u + (uint32_t)q, B, L, C, s));
     }
   }
-  if (cond && cond->final_replace && n_run > 0 && first_step + n_run == n_steps)
+  if (cond && cond->final_replace && n_run > 0 && first_step + n_run == n_visits)
     TIMED(FFD_K_SDE, project((double)timesteps[n_steps - 1], 1, nullptr, 0u));
   return FFD_OK;
 }
@@ -1519,7 +1568,7 @@ int ffd_sample_batch_pc(ffd_ctx* ctx, float* x, int B, const float* timesteps, i
     return ffd_sample_batch(ctx, x, B, timesteps, n_steps, step_size, first_step, n_run, seed, sample_offset, z_inject,
                             use_cache, global_step0, stream);
   return pc_loop(ctx, "ffd_sample_batch_pc", x, B, timesteps, n_steps, step_size, first_step, n_run, n_corrector, snr, norm,
-                 seed, sample_offset, z_inject, use_cache, global_step0, nullptr, stream);
+                 seed, sample_offset, z_inject, use_cache, global_step0, nullptr, 1, 1, stream);
 }
 
 // Conditional sampling by replacement: the predictor-corrector step with one ffd_cond_project behind every update.
@@ -1537,7 +1586,27 @@ int ffd_sample_batch_cond(ffd_ctx* ctx, float* x, int B, const float* timesteps,
     return ctx->fail(FFD_ERR_INVALID, "unknown corrector norm %d", norm);
   if (x && z_inject == x) return ctx->fail(FFD_ERR_INVALID, "x aliases z_inject");
   return pc_loop(ctx, "ffd_sample_batch_cond", x, B, timesteps, n_steps, step_size, first_step, n_run, n_corrector, snr, norm,
-                 seed, sample_offset, z_inject, use_cache, global_step0, cond, stream);
+                 seed, sample_offset, z_inject, use_cache, global_step0, cond, 1, 1, stream);
+}
+
+// Resampled conditional sampling ("time travel", RePaint): the conditional loop over the visit schedule above.
+int ffd_sample_batch_resample(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                              int first_visit, int n_visits, int jump, int resample, int n_corrector, float snr, int norm,
+                              uint64_t seed, uint64_t sample_offset, const float* z_inject, const ffd_cond_cfg* cond,
+                              void* stream) {
+  if (!ctx) return FFD_ERR_INVALID;
+  if (!cond) return ctx->fail(FFD_ERR_INVALID, "ffd_sample_batch_resample needs an observation (cond)");
+  if (jump < 1 || resample < 1) return ctx->fail(FFD_ERR_INVALID, "jump and resample must be >= 1");
+  if (n_corrector < 0) return ctx->fail(FFD_ERR_INVALID, "n_corrector must be >= 0");
+  if (!(snr > 0.f)) return ctx->fail(FFD_ERR_INVALID, "snr must be > 0");
+  if (norm != FFD_LANGEVIN_NORM_BATCH && norm != FFD_LANGEVIN_NORM_SAMPLE)
+    return ctx->fail(FFD_ERR_INVALID, "unknown corrector norm %d", norm);
+  if (x && z_inject == x) return ctx->fail(FFD_ERR_INVALID, "x aliases z_inject");
+  const int64_t visits = (int64_t)n_steps * resample;  // the projections' tags stay below the transitions' 0xE0000000
+  if (visits > 0x1FFFFFF0ll || (visits > 0 && visits * ((int64_t)n_corrector + 1) > 0x1FFFFFF0ll))
+    return ctx->fail(FFD_ERR_INVALID, "visits * (n_corrector + 1) reaches the transitions' Philox tags");
+  return pc_loop(ctx, "ffd_sample_batch_resample", x, B, timesteps, n_steps, step_size, first_visit, n_visits, n_corrector,
+                 snr, norm, seed, sample_offset, z_inject, 0, 0, cond, jump, resample, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -495,6 +495,74 @@ hipError_t launch_cond_time(float* x, const float* obs, const float* mask, const
 }
 
 // ---------------------------------------------------------------------------
+// Forward transition of the SDE from time s to t >= s (include/ffd.h ffd_forward_transition; the re-noising of resampled
+// conditional sampling):  x' = (a x) + ((sg G_l) z), every product / sum its own fp32 rounding; the draws are counted
+// like k_sde_step's.  noisy == 0 (sg == 0): x' = a x and no draw is read or generated.  8 B per element with device
+// draws, 12 B with injected ones: HBM bound, grid-stride over float4s like k_sde_step_v4.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float transition_update(float xi, float Gl, float zz, float a, float sg, int noisy) {
+  const float ax = __fmul_rn(a, xi);
+  return noisy ? __fadd_rn(ax, __fmul_rn(__fmul_rn(sg, Gl), zz)) : ax;
+}
+
+__global__ __launch_bounds__(256) void k_forward_transition_v4(float* __restrict__ x, const float* __restrict__ z,
+                                                               const float* __restrict__ G, float a, float sg, int noisy,
+                                                               uint64_t seed, uint64_t elem_offset, uint32_t tag,
+                                                               size_t nvec, int L, unsigned C4) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
+    const float4 xi = reinterpret_cast<const float4*>(x)[v];
+    float zz[4] = {0.f, 0.f, 0.f, 0.f};
+    if (noisy) {
+      if (z) {
+        const float4 zv = reinterpret_cast<const float4*>(z)[v];
+        zz[0] = zv.x, zz[1] = zv.y, zz[2] = zv.z, zz[3] = zv.w;
+      } else {
+        normal4((elem_offset >> 2) + v, seed, tag, zz);  // elem_offset is a multiple of 4
+      }
+    }
+    const float Gl = G[(v / C4) % (size_t)L];
+    reinterpret_cast<float4*>(x)[v] =
+        float4{transition_update(xi.x, Gl, zz[0], a, sg, noisy), transition_update(xi.y, Gl, zz[1], a, sg, noisy),
+               transition_update(xi.z, Gl, zz[2], a, sg, noisy), transition_update(xi.w, Gl, zz[3], a, sg, noisy)};
+  }
+}
+
+__global__ __launch_bounds__(256) void k_forward_transition(float* __restrict__ x, const float* __restrict__ z,
+                                                            const float* __restrict__ G, float a, float sg, int noisy,
+                                                            uint64_t seed, uint64_t elem_offset, uint32_t tag, size_t total,
+                                                            int L, int C) {
+  const size_t nvec = (total + 3) / 4;
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
+    const size_t i0 = v * 4;
+    const int n = (int)((total - i0) < 4 ? (total - i0) : 4);
+    float zz[4] = {0.f, 0.f, 0.f, 0.f};
+    if (noisy) load_normals(z, i0, n, seed, elem_offset, tag, zz);
+    for (int j = 0; j < n; ++j) {
+      const size_t i = i0 + j;
+      x[i] = transition_update(x[i], G[(i / (size_t)C) % (size_t)L], zz[j], a, sg, noisy);
+    }
+  }
+}
+
+hipError_t launch_forward_transition(float* x, const float* G, float a, float sg, const float* z, uint64_t seed,
+                                     uint64_t elem_offset, uint32_t tag, int B, int L, int C, hipStream_t s) {
+  const int noisy = sg != 0.f;
+  if (!noisy && a == 1.f) return hipSuccess;  // s == t: x is untouched bit for bit (a x + 0 would turn -0 into +0)
+  if (!noisy) z = nullptr;
+  const size_t total = (size_t)B * L * C;
+  size_t blocks = ((total + 3) / 4 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  if (C % 4 == 0 && ptr16(x) && ptr16(z) && elem_offset % 4 == 0)
+    hipLaunchKernelGGL(k_forward_transition_v4, dim3((unsigned)blocks), dim3(256), 0, s, x, z, G, a, sg, noisy, seed,
+                       elem_offset, tag, total / 4, L, (unsigned)C / 4);
+  else
+    hipLaunchKernelGGL(k_forward_transition, dim3((unsigned)blocks), dim3(256), 0, s, x, z, G, a, sg, noisy, seed,
+                       elem_offset, tag, total, L, C);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // probability-flow ODE steps (an extension: the reference has Euler-Maruyama only).  Same grid, G, beta(t) and VE
 // sqrt_derivative as the SDE step (sde_params); the drift of the ODE with the SDE's marginals is
 //   d(x, t) = f(x, t) - 1/2 (g(t) G_l)^2 s(x, t),   f = a*x (VP), 0 (VE)
@@ -1253,6 +1321,30 @@ MultistepParams multistep_params(const double* c) {
   return MultistepParams{(float)c[0], (float)c[1], (float)c[2], (float)c[3], (float)c[4]};
 }
 
+// (a, sg) of the forward transition s -> t in double (include/ffd.h ffd_host_transition_coef).  One operation per
+// statement: the float64 restatement of the tests repeats them in this order.
+int transition_coef(int sde, double a, double b, double s, double t, double* c) {
+  if (!c || !std::isfinite(s) || !std::isfinite(t) || s < 0.0 || t < s) return FFD_ERR_INVALID;
+  if (sde != FFD_SDE_VP && sde != FFD_SDE_VE) return FFD_ERR_UNSUPPORTED;
+  c[0] = 1.0, c[1] = 0.0;
+  if (s == t) return FFD_OK;
+  if (sde == FFD_SDE_VP) {
+    const double lt = -0.25 * t * t * (b - a) - 0.5 * t * a;
+    const double ls = -0.25 * s * s * (b - a) - 0.5 * s * a;
+    const double d = lt - ls;
+    c[0] = exp(d);
+    c[1] = sqrt(-expm1(2.0 * d));
+  } else {
+    const double st = a * pow(b / a, t);
+    const double ss = a * pow(b / a, s);
+    const double vt = st * st;
+    const double vs = ss * ss;
+    const double v = vt - vs;
+    c[1] = sqrt(v > 0.0 ? v : 0.0);
+  }
+  return FFD_OK;
+}
+
 }  // namespace ffd
 
 // ---- C ABI (include/ffd.h): the context-free entry points on these kernels ----
@@ -1267,6 +1359,21 @@ int ffd_sde_step(const ffd_sde_desc* sde, float* x, const float* score, const fl
   if (!(step_size > 0.f)) return FFD_ERR_INVALID;  // sde.py:157,238 assert
   hipError_t e = launch_sde_step(x, score, z, G, sde_params(sde->sde, sde->a, sde->b, t, step_size), seed,
                                  sample_offset * (uint64_t)L * C, (uint32_t)step, B, L, C, (hipStream_t)stream);
+  return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+int ffd_host_transition_coef(const ffd_sde_desc* sde, double s, double t, double coef_out[2]) {
+  if (!sde) return FFD_ERR_INVALID;
+  return transition_coef(sde->sde, sde->a, sde->b, s, t, coef_out);
+}
+
+int ffd_forward_transition(const ffd_sde_desc* sde, float* x, const float* G, double s, double t, const float* z,
+                           uint64_t seed, uint64_t sample_offset, uint32_t tag, int B, int L, int C, void* stream) {
+  if (!sde || !x || !G || B < 1 || L < 1 || C < 1 || x == z) return FFD_ERR_INVALID;
+  double c[2];
+  if (int rc = transition_coef(sde->sde, sde->a, sde->b, s, t, c)) return rc;
+  hipError_t e = launch_forward_transition(x, G, (float)c[0], (float)c[1], z, seed, sample_offset * (uint64_t)L * C, tag, B,
+                                           L, C, (hipStream_t)stream);
   return e == hipSuccess ? FFD_OK : FFD_ERR_HIP;
 }
 

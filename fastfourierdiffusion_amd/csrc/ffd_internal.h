@@ -293,6 +293,11 @@ hipError_t launch_cond_project(float* x, const float* obs, const float* mask, co
 hipError_t launch_cond_time(float* x, const float* obs, const float* mask, const float* G, float mc, float sigma,
                             int noiseless, const float* z, uint64_t seed, uint64_t elem_offset, uint32_t tag, int obs_batch,
                             int B, int L, int C, hipStream_t s);
+// The forward transition s -> t of the SDE (include/ffd.h ffd_forward_transition; ffd_elem.hip).  transition_coef: (a, sg)
+// in double, FFD_ERR_INVALID / FFD_ERR_UNSUPPORTED as ffd_host_transition_coef.  The launch is skipped for (1, 0).
+int transition_coef(int sde, double a, double b, double s, double t, double* coef);
+hipError_t launch_forward_transition(float* x, const float* G, float a, float sg, const float* z, uint64_t seed,
+                                     uint64_t elem_offset, uint32_t tag, int B, int L, int C, hipStream_t s);
 
 // Denoising score-matching loss (ffd_loss.hip; losses.py:54-125).  Sample b of the call is global sample
 // sample_offset + b: with z == nullptr both kernels take the draw of global element g from slot g & 3 of Philox block

@@ -45,6 +45,19 @@ the observation, noised to the step's time level, is blended into the state unde
 consume two draws per update: its own, then the projection's.  No claim about sample quality is made: there is no
 trained checkpoint to measure it on.
 
+Resampling (extension): replacement draws the observed part independently of the unobserved part, and on a forecast
+that error stays however fine the grid.  ``sample_conditional(..., resample=r, jump=j)`` is the
+"time travel" of RePaint (Lugmayr et al. 2022) through ``ffd_sample_batch_resample``.  Schedule: the N reverse steps
+are cut into blocks [0, j), [j, 2j), ... (the last may be shorter; j > N is one block) and every block runs r times;
+between two passes of the block [i0, e) the whole state is diffused forward from ``timesteps[e]`` (0 behind the last
+step) to ``timesteps[i0]`` with the SDE's exact transition kernel (``SDE.forward_transition``), with no projection
+behind it.  That is r N visits and (r - 1) ceil(N / j) transitions.  Draw order under ``rng="torch"`` and
+``inject_noise``: per visit what a conditional step consumes (per update its own draw, then its projection's), then
+one more draw if a transition follows the visit; under ``rng="philox"`` the visit ordinal replaces the step index in
+the stream tags and transition q draws under 0xE0000000 + q.  Cost: r times the score evaluations of the plain run.
+``resample=1`` takes the replacement path unchanged.  It does not run with the cache (whose gate assumes that time only
+falls) or under the ODE solvers.
+
 Two batch-wide statistics of the reference make the SAMPLES depend on the batching all the
 same, sharded or not (they are properties of the reference's algorithm, reproduced here per
 batch / per shard): the E2-CRF tables come from the batch's element 0 (caching.py:326-328), and
@@ -296,6 +309,18 @@ class DiffusionSampler:
             N.check(ctx.lib.ffd_fresca_disable(ctx.handle), ctx.handle, "ffd_fresca_disable")
         device = model.device
         stream = N.current_stream_ptr(device)
+        # resampled conditional sampling walks the visits of the host schedule: followed[u] = a transition follows visit u
+        resample, jump = (cond["resample"], cond["jump"]) if cond is not None else (1, 1)
+        followed = None
+        if resample > 1:
+            n_iter = ctx.lib.ffd_host_resample_visits(num_diffusion_steps, jump, resample)
+            N.check(min(n_iter, 0), ctx.handle, "ffd_host_resample_visits")
+            followed = []
+            step_out, back_to = C.c_int(), C.c_int()
+            for u in range(n_iter):
+                N.check(ctx.lib.ffd_host_resample_visit(num_diffusion_steps, jump, resample, u, C.byref(step_out),
+                                                        C.byref(back_to)), ctx.handle, "ffd_host_resample_visit")
+                followed.append(back_to.value >= 0)
         all_samples = []
         num_batches = max(1, num_samples // self.sample_batch_size)  # remainder dropped (Q10)
         global_step = 0
@@ -320,8 +345,16 @@ class DiffusionSampler:
                         draws *= 2  # per update its own draw, then its projection's
                     if not ode and (self.rng == "torch" or self._injected is not None):
                         n = min(n, max(1, self.z_chunk_steps // draws))  # the z buffer keeps its size
-                        z = torch.empty((n * draws,) + tuple(X.shape), device=device, dtype=torch.float32)
-                        for i in range(n * draws):  # one randn_like per draw, as the reference consumes its generator
+                        n_draws = n * draws
+                        if followed is not None:  # a visit's draws, then its transition's: whole visits up to the size
+                            n, n_draws = 0, 0
+                            while done + n < n_iter:
+                                more = draws + int(followed[done + n])
+                                if n > 0 and n_draws + more > self.z_chunk_steps:
+                                    break
+                                n, n_draws = n + 1, n_draws + more
+                        z = torch.empty((n_draws,) + tuple(X.shape), device=device, dtype=torch.float32)
+                        for i in range(n_draws):  # one randn_like per draw, as the reference consumes its generator
                             if self._injected is not None:
                                 z[i].copy_(self._next_injected(X.shape, device))
                             else:
@@ -340,6 +373,15 @@ class DiffusionSampler:
                         cfg = N.CondCfg(obs.data_ptr(), msk.data_ptr(),
                                         cond["std"].data_ptr() if cond["std"] is not None else None,
                                         1 if shared else batch_size, cond["domain"], int(cond["final_replace"]), 0)
+                        if resample > 1:
+                            rc = ctx.lib.ffd_sample_batch_resample(ctx.handle, X.data_ptr(), batch_size, ts_c,
+                                                                   num_diffusion_steps, step_size, done, n, jump, resample,
+                                                                   self.corrector_steps, self.snr,
+                                                                   CORRECTOR_NORMS[self.corrector_norm], self.seed,
+                                                                   sample_cursor, z_ptr, C.byref(cfg), stream)
+                            N.check(rc, ctx.handle, "ffd_sample_batch_resample")
+                            done += n
+                            continue
                         rc = ctx.lib.ffd_sample_batch_cond(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
                                                            step_size, done, n, self.corrector_steps, self.snr,
                                                            CORRECTOR_NORMS[self.corrector_norm], self.seed, sample_cursor,
@@ -373,9 +415,18 @@ class DiffusionSampler:
 
     # ------------------------------------------------------------------
     # conditional sampling by replacement (extension)
+    def _check_resampling(self, resample, jump) -> None:
+        for name, v in (("resample", resample), ("jump", jump)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        if resample > 1 and self.use_cache:
+            raise ValueError("resample > 1 cannot run with use_cache=True: the E2-CRF cache's gate and tables assume that "
+                             "the diffusion time only falls, and resampling moves it back up")
+
     def sample_conditional(self, observed: torch.Tensor, mask: torch.Tensor, num_samples: int,
-                           num_diffusion_steps: Optional[int] = None, *, domain: Optional[str] = None,
-                           feature_std: Optional[torch.Tensor] = None, final_replace: bool = True) -> torch.Tensor:
+                           num_diffusion_steps: Optional[int] = None, resample: int = 1, jump: int = 1, *,
+                           domain: Optional[str] = None, feature_std: Optional[torch.Tensor] = None,
+                           final_replace: bool = True) -> torch.Tensor:
         """``sample`` conditioned on ``observed`` where ``mask`` is 1: after every state update of every reverse step the
         observation, noised to that step's time, replaces the observed part of the state (``SDE.cond_project``).
         ``observed`` lives in the diffused domain (for a spectral model: the packed, standardized spectrum of the series,
@@ -387,10 +438,13 @@ class DiffusionSampler:
         replacement, so that the observed points come back exact to transform rounding.  Honours ``corrector_steps``,
         ``snr``, ``corrector_norm``, ``rng``, ``seed``, ``sample_offset``, ``inject_noise``, the cache and FreSca;
         batching, cache lifecycle and prior are those of ``sample``.  Returns a CPU tensor in the diffused domain.
-        A forecast is the prefix mask ``mask[:n_known] = 1``."""
+        A forecast is the prefix mask ``mask[:n_known] = 1``.  ``resample=r > 1`` runs every block of ``jump`` steps r
+        times with a forward transition in between (the module docstring's "Resampling"), at r times the evaluations;
+        ``resample=1`` is plain replacement whatever ``jump`` is."""
         if self.solver != "euler_maruyama":
             raise ValueError("conditional sampling by replacement is defined for the predictor-corrector sampler: "
                              "it needs solver='euler_maruyama'")
+        self._check_resampling(resample, jump)
         if domain is None:
             domain = "frequency" if getattr(self.score_model, "scale_noise", False) else "time"
         if domain not in ("frequency", "time"):
@@ -407,20 +461,23 @@ class DiffusionSampler:
         cond = dict(obs=observed.to(device).contiguous(), mask=mask.to(device).contiguous(),
                     std=feature_std.to(device).contiguous() if feature_std is not None else None,
                     domain=N.FFD_COND_FREQUENCY if domain == "frequency" else N.FFD_COND_TIME,
-                    final_replace=bool(final_replace))
+                    final_replace=bool(final_replace), resample=resample, jump=jump)
         return self._sample(num_samples, num_diffusion_steps, cond)
 
     def impute(self, series_time: torch.Tensor, mask: torch.Tensor, num_samples: int,
-               num_diffusion_steps: Optional[int] = None, *, feature_mean: Optional[torch.Tensor] = None,
-               feature_std: Optional[torch.Tensor] = None, final_replace: bool = True) -> torch.Tensor:
+               num_diffusion_steps: Optional[int] = None, resample: int = 1, jump: int = 1, *,
+               feature_mean: Optional[torch.Tensor] = None, feature_std: Optional[torch.Tensor] = None,
+               final_replace: bool = True) -> torch.Tensor:
         """Complete a time series with a model that diffuses its spectrum: ``series_time`` (L, C) or
         (num_samples, L, C) holds the series, ``mask`` (as in ``sample_conditional``) is 1 at its observed points.
         The unobserved points are zero-filled, the series goes through ``dft`` (with the dataset's ``feature_mean`` /
         ``feature_std`` (L, C): ``ffd_dft_standardize``), ``sample_conditional`` runs in the frequency domain, and the
         samples come back as TIME series (``ffd_unstandardize_idft`` / ``idft``) on the CPU.  Forecasting is the
-        prefix mask: ``mask[:n_known] = 1`` draws ``num_samples`` continuations of the first ``n_known`` points."""
+        prefix mask: ``mask[:n_known] = 1`` draws ``num_samples`` continuations of the first ``n_known`` points.
+        ``resample`` / ``jump``: as in ``sample_conditional``."""
         if (feature_mean is None) != (feature_std is None):
             raise ValueError("feature_mean and feature_std go together")
+        self._check_resampling(resample, jump)  # (sample_conditional's refusals, before any device work)
         if self.solver != "euler_maruyama":  # (sample_conditional's refusal, before any device work)
             raise ValueError("conditional sampling by replacement is defined for the predictor-corrector sampler: "
                              "it needs solver='euler_maruyama'")
@@ -444,7 +501,7 @@ class DiffusionSampler:
         else:
             N.check(lib.ffd_dft(filled.data_ptr(), obs.data_ptr(), Bo, L, Cn, stream), None, "ffd_dft")
         out = self.sample_conditional(obs, m, num_samples, num_diffusion_steps, domain="frequency",
-                                      feature_std=std_d, final_replace=final_replace)
+                                      feature_std=std_d, final_replace=final_replace, resample=resample, jump=jump)
         xf = out.to(device).contiguous()
         xt = torch.empty_like(xf)
         if mean_d is not None:

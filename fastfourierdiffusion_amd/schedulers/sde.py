@@ -314,6 +314,45 @@ class SDE(abc.ABC):
         N.check(rc, None, "ffd_cond_project")
         return SamplingOutput(prev_sample=x)
 
+    def transition_coeffs(self, timestep_from: float, timestep_to: float):
+        """(a, sg) of the forward transition x_t = a x_s + (sg G) z from s = ``timestep_from`` to t = ``timestep_to`` >= s,
+        in float64 on the host (``ffd_host_transition_coef``; no device needed)."""
+        out = (C.c_double * 2)()
+        desc = self._desc()
+        rc = N.lib().ffd_host_transition_coef(C.byref(desc), float(timestep_from), float(timestep_to), out)
+        N.check(rc, None, "ffd_host_transition_coef")
+        return float(out[0]), float(out[1])
+
+    def forward_transition(self, sample: torch.Tensor, timestep_from: float, timestep_to: float,
+                           noise: Optional[torch.Tensor] = None, *, seed: Optional[int] = None, sample_offset: int = 0,
+                           tag: int = 0xE0000000) -> SamplingOutput:
+        """Diffuse ``sample`` (B, L, C), a state at ``timestep_from`` = s, FORWARD to ``timestep_to`` = t >= s with the
+        SDE's exact transition kernel: x_t = a x_s + (sg G) z (``transition_coeffs``); the re-noising step of resampled
+        conditional sampling (``DiffusionSampler.sample_conditional(resample=...)``).  ``noise`` injects z; by default
+        z = torch.randn_like(sample); with ``seed`` the draw is made on the device (Philox stream ``tag``, global sample
+        index ``sample_offset`` + b).  s == t returns the sample bit for bit."""
+        if not (0.0 <= float(timestep_from) <= float(timestep_to)):
+            raise ValueError(f"need 0 <= timestep_from <= timestep_to, got {timestep_from!r}, {timestep_to!r}")
+        sample = N.require_gpu_tensor(sample, "sample")
+        if sample.dim() != 3:
+            raise ValueError(f"sample must be (B, L, C), got {tuple(sample.shape)}")
+        B, L, Cn = sample.shape
+        z = None
+        if noise is not None:
+            z = N.require_gpu_tensor(noise, "noise")
+            if z.shape != sample.shape:
+                raise ValueError(f"noise must have the sample's shape, got {tuple(z.shape)}")
+        elif seed is None:
+            z = torch.randn_like(sample)
+        x = sample.clone()
+        desc = self._desc()
+        rc = N.lib().ffd_forward_transition(C.byref(desc), x.data_ptr(), self._G_on(sample.device).data_ptr(),
+                                            float(timestep_from), float(timestep_to), z.data_ptr() if z is not None else None,
+                                            int(seed or 0), int(sample_offset), int(tag), B, L, Cn,
+                                            N.current_stream_ptr(sample.device))
+        N.check(rc, None, "ffd_forward_transition")
+        return SamplingOutput(prev_sample=x)
+
 
 class VEScheduler(SDE):
     """sde.py:90-165."""

@@ -312,6 +312,33 @@ int ffd_cond_project(const ffd_sde_desc* sde, float* x, const float* obs, const 
                      const float* G, double t, int noiseless, const float* z, uint64_t seed, uint64_t sample_offset,
                      uint32_t tag, int obs_batch, int domain, int B, int L, int C, void* stream);
 
+/* ---- the forward transition of the SDE (an extension: the re-noising step of resampled conditional sampling, see
+ * ffd_sample_batch_resample) ----
+ * For 0 <= s <= t the forward SDE of ffd_sde_step takes x_s to
+ *     x_t = a x_s + (sg G_l) z,      z ~ N(0, I)
+ *     VP: a = exp(lmc(t) - lmc(s)), sg = sqrt(-expm1(2 (lmc(t) - lmc(s)))), lmc as in ffd_cond_project
+ *     VE: a = 1, sg = sqrt(sigma(t)^2 - sigma(s)^2), sigma(t) = a_ve (b / a_ve)^t
+ * the same SDE, G and coefficient conventions as ffd_cond_project, ffd_sm_perturb and ffd_sde_step; s = 0 gives the
+ * marginal's (mc, sigma) for VP.  Transitions compose: a(r,t) = a(r,s) a(s,t), sg(r,t)^2 = a(s,t)^2 sg(r,s)^2 + sg(s,t)^2.
+ * ffd_host_transition_coef: host only (no device needed), float64, coef_out = (a, sg); s == t gives exactly (1, 0).
+ * FFD_ERR_INVALID: a null pointer, non-finite times, s < 0, t < s; then FFD_ERR_UNSUPPORTED for an unknown SDE. */
+int ffd_host_transition_coef(const ffd_sde_desc* sde, double s, double t, double coef_out[2]);
+/* The operator, in place on x (B,L,C).  The coefficients are formed on the host in double and rounded once to fp32; per
+ * element, every product / sum a separate fp32 rounding (no FMA contraction):  x' = (a x) + ((sg G_l) z).
+ * z == NULL draws on the device: element i of sample b takes slot g & 3 of Philox block g >> 2, g = (sample_offset + b)
+ * L C + i, under stream tag `tag` -- the counting of ffd_sde_step, ffd_langevin_step and ffd_cond_project, so a shard
+ * draws what the unsharded call draws.  With sg == 0 (fp32) no draw is read or generated and x' = a x; with a == 1 as
+ * well nothing is launched and x is untouched bit for bit.  One float4 of x (and z) per thread and iteration where
+ * C % 4 == 0, the buffers are 16-byte aligned and the element offset is a multiple of 4 (one Philox block per float4);
+ * a scalar kernel with the same bits otherwise.  8 B of HBM traffic per element with device draws, 12 B with z.
+ * Context-free, stream ordered, no host synchronisation, no atomics: bit-identical from run to run, and a sample's
+ * result does not depend on B or on its place in the batch.  z and G are not modified.
+ * FFD_ERR_INVALID before any device work: a null pointer (z excepted), B, L, C < 1, t < s, s < 0, non-finite times, x
+ * aliasing z; then FFD_ERR_UNSUPPORTED for an unknown SDE.
+ * ffd_sample_batch_resample uses tag 0xE0000000 + q for transition q. */
+int ffd_forward_transition(const ffd_sde_desc* sde, float* x, const float* G, double s, double t, const float* z,
+                           uint64_t seed, uint64_t sample_offset, uint32_t tag, int B, int L, int C, void* stream);
+
 /* ---- the closed-form score of a diffused Gaussian mixture (an extension: the "optimal denoiser" every trained score
  * network approximates; the backbone behind FFD_MODEL_MIXTURE) ----
  * Data distribution p_0 = sum_i w_i N(mu_i, diag(v)): means (K, L, C), log_weights (K), one shared per-coordinate
@@ -744,6 +771,37 @@ int ffd_sample_batch_cond(ffd_ctx* ctx, float* x, int B, const float* timesteps,
                           uint64_t sample_offset, const float* z_inject, int use_cache, int global_step0,
                           const ffd_cond_cfg* cond, void* stream);
 
+/* Resampled conditional sampling ("time travel": RePaint, Lugmayr et al. 2022; an extension).  Replacement draws the
+ * observed part of the state independently of the unobserved part, which on a forecast leaves an error that more steps
+ * do not remove.  Here the grid's N = n_steps reverse steps are cut into blocks [0, j), [j, 2j), ... (j = jump; the last
+ * block may be shorter, jump > N is one block) and every block is run r = resample times: between two passes of the
+ * block [i0, e) the whole state is diffused forward again, by one ffd_forward_transition from s = timesteps[e] (0 when
+ * e == N) to t = timesteps[i0].  No projection follows the transition: its observed part is a valid noised observation.
+ * The schedule has U = r N visits and (r - 1) ceil(N / j) transitions; a transition belongs to the visit it follows.
+ * ffd_host_resample_visits returns U.  ffd_host_resample_visit: *step_out = the grid index visit `visit` runs,
+ * *back_to_out = -1 or the grid index i0 the state is re-noised to after it.  Host only; FFD_ERR_INVALID: n_steps, jump,
+ * resample < 1, U > INT_MAX, a visit outside [0, U), a null pointer.
+ * ffd_sample_batch_resample walks visits [first_visit, first_visit + n_visits).  A visit IS reverse step
+ * timesteps[step] of ffd_sample_batch_cond -- correctors, predictor with its fused tail, one projection behind every
+ * update -- with the visit ordinal u in place of the step index in the three stream tags; transition q (counted in
+ * schedule order from 0) draws under tag 0xE0000000 + q, and U (n_corrector + 1) <= 0x1FFFFFF0 keeps the projections'
+ * tags below it.  The transition is timed under FFD_K_SDE.
+ *   z_inject   NULL or flat in execution order: per visit (n_corrector + 1, 2, B, L, C) as for ffd_sample_batch_cond,
+ *              then one more (B, L, C) slab if a transition follows the visit; the pointer starts at first_visit.
+ *   cond       required (FFD_ERR_INVALID when NULL); final_replace runs after visit U - 1 only.
+ * resample == 1 is ffd_sample_batch_cond(use_cache = 0) bit for bit, and a run split over calls at any visit boundary
+ * is bit-identical to the unsplit run.  There is no cache argument: the E2-CRF gate and tables assume that time only
+ * falls; the context's cache state is left untouched.  The ODE solvers have no resampled form.
+ * FFD_ERR_INVALID before any device work: as ffd_sample_batch_cond, and jump, resample < 1, a visit range outside
+ * [0, U], U (n_corrector + 1) > 0x1FFFFFF0, and -- checked for resample > 1 only, where transitions run -- timesteps
+ * that are not finite, not non-increasing (equal neighbours are accepted) or below 0. */
+int ffd_host_resample_visits(int n_steps, int jump, int resample);
+int ffd_host_resample_visit(int n_steps, int jump, int resample, int visit, int* step_out, int* back_to_out);
+int ffd_sample_batch_resample(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                              int first_visit, int n_visits, int jump, int resample, int n_corrector, float snr, int norm,
+                              uint64_t seed, uint64_t sample_offset, const float* z_inject, const ffd_cond_cfg* cond,
+                              void* stream);
+
 /* Tuning knobs for experiments and for the test suite's kernel variants (results stay within the parity tolerance,
  * only the kernel choice / tiling changes).  PER CALLING THREAD since round 4 (thread_local): a knob set on one thread
  * selects kernels for the launches THAT thread makes and is invisible to every other thread, so two samplers on two
@@ -849,7 +907,8 @@ int ffd_kernel_timing_get(const ffd_ctx* ctx, int kernel_class, float* avg_ms_ou
  * the context ran last (Euler-Maruyama before any); for Heun, whose two tails differ, the mean of its two launches; for the
  * multistep solvers the tail with history (every interval of a trajectory but its first, which reads no history); after
  * ffd_sample_batch_pc the predictor's tail (its work figures) followed by the corrector's kernels.  The projections of
- * ffd_sample_batch_cond (k_cond_project / k_cond_time: about 16 B of HBM traffic per element, 12 B with device draws) are
+ * ffd_sample_batch_cond (k_cond_project / k_cond_time: about 16 B of HBM traffic per element, 12 B with device draws) and
+ * the transitions of ffd_sample_batch_resample (k_forward_transition: 12 B per element, 8 B with device draws) are
  * timed under FFD_K_SDE as well but are NOT in this class's name or figures, which describe the update launches only:
  * after a conditional loop the mean of ffd_kernel_timing_get covers more launches than the figures do. */
 const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cache_hit, double* flops_out,

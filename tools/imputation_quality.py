@@ -15,6 +15,9 @@ bandwidth noise: here the exact conditional is the true one and its score is the
 the first half observed) and a random 50 % mask (an imputation), M completions of every truth are drawn
   (a) by ``sample_conditional`` (replacement, domain="time") at several step counts, without and with one Langevin
       corrector step per reverse step, Philox draws, three seeds;
+  (a') by ``sample_conditional(..., resample=r, jump=j)`` (resampling, "time travel") without corrector at EQUAL SCORE
+      EVALUATIONS as rows of (a): 20 steps x r = 10 and 50 x 4 against the 200-evaluation rows, 200 x 5 against the
+      1000-evaluation row, each with jump 1, 2 and 10;
   (b) from the exact conditional, three seeds: the FLOOR, its spread the resolution of the comparison,
 and scored against the truth with ``ensemble_scores``: the mean CRPS over the unobserved points and the energy score,
 averaged over the truths, and the share of unobserved truths inside the 5 % .. 95 % band.  Replacement is known to be an
@@ -37,6 +40,8 @@ N_HELD, M = 32, 256
 STEPS = (20, 50, 200, 1000)
 SEEDS = (1, 2, 3)
 SNR = 0.16
+RESAMPLED = ((20, 10), (50, 4), (200, 5))  # (steps, resample): 200, 200 and 1000 score evaluations
+JUMPS = (1, 2, 10)
 
 
 def masks():
@@ -95,7 +100,9 @@ def main(out_path):
                       "per series, and the share of unobserved truths inside the 5 % .. 95 % band; mean / min / max over "
                       "three seeds.  floor: draws of the exact conditional; replacement: sample_conditional, domain time",
               "L": L, "C": CH, "n_components": int(train.shape[0]), "bandwidth": BANDWIDTH, "sde": "vp", "n_held_out": N_HELD,
-              "members": M, "steps": list(STEPS), "seeds": list(SEEDS), "snr": SNR, "truths": {}}
+              "members": M, "steps": list(STEPS), "seeds": list(SEEDS), "snr": SNR,
+              "resampled": "sample_conditional(resample=r, jump=j), no corrector: steps x r score evaluations",
+              "resampled_steps_r": [list(v) for v in RESAMPLED], "jumps": list(JUMPS), "truths": {}}
     for kind, name, mask in [(k, n, mk) for k in truths for n, mk in masks().items()]:
         held = truths[kind]
         floor_rows, ess = [], None
@@ -120,6 +127,20 @@ def main(out_path):
                 print(kind, name, f"corrector_steps={n_corr}", steps,
                       {k: round(v["mean"], 5) for k, v in table[str(steps)].items() if isinstance(v, dict)}, flush=True)
             entry["replacement"][f"corrector_steps_{n_corr}"] = table
+        entry["resampled"] = {}
+        for steps, r in RESAMPLED:
+            table = {}
+            for jump in JUMPS:
+                rows = []
+                for seed in SEEDS:
+                    s = DiffusionSampler(score_model=model, sample_batch_size=N_HELD * M, rng="philox", seed=seed)
+                    out = s.sample_conditional(observed, mask, N_HELD * M, steps, resample=r, jump=jump, domain="time",
+                                               final_replace=True)
+                    rows.append(score(out.reshape(N_HELD, M, L, CH), held, mask))
+                table[f"jump_{jump}"] = {"score_evaluations": steps * r, **spread(rows)}
+                print(kind, name, f"resampled steps={steps} r={r} jump={jump}",
+                      {k: round(v["mean"], 5) for k, v in table[f"jump_{jump}"].items() if isinstance(v, dict)}, flush=True)
+            entry["resampled"][f"steps_{steps}_r_{r}"] = table
         result["truths"].setdefault(kind, {})[name] = entry
     os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
     with open(out_path, "w") as f:

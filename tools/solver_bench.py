@@ -8,6 +8,9 @@
     python3 tools/solver_bench.py cond [out.json] [--alongside extra.json]
                                              (conditional sampling: euler_maruyama, cond0, pc1, cond1 ->
                                              profiles/cond_steps.json)
+    python3 tools/solver_bench.py resample [out.json] [--alongside extra.json]
+                                             (resampled conditional sampling: cond0, res0_j2, res0_j10, cond1, res1_j2 ->
+                                             profiles/resample_steps.json)
     python3 tools/solver_bench.py multistep [out.json] [--alongside extra.json]
                                              (linear multistep ODE solvers: euler_maruyama, ode_euler, ode_ab2, dpmpp_2m ->
                                              profiles/multistep_steps.json)
@@ -33,6 +36,12 @@ cond1 / pc1.
 read and written beside x) next to ode_euler and Euler-Maruyama in the same run; ``cost_vs_ode_euler_interval`` is the
 acceptance figure, expected near 1.00.
 
+``resample``: ffd_sample_batch_resample with resample = 2 over the whole 21-point grid (U = 42 visits; jump 2: 11
+transitions, jump 10: 3) next to ffd_sample_batch_cond's steps in the same process, the same observation.  A visit is a
+conditional step, so ``cost_vs_conditional_step`` (ms per visit / ms per step of the twin) is expected near 1.00 plus a
+transition's share.  ``operator_us_per_launch``: ffd_forward_transition and ffd_cond_project on the loop's own (512, 187,
+1) state, 400 back-to-back launches each between two events (device draws) -- launch spacing, not a kernel trace.
+
 ``--alongside FILE``: the JSON object in FILE goes into the result as ``measured_alongside``, unchanged -- what was
 measured next to this run and is not this tool's to measure (the other runs of an alternating series, the parent
 commit's figures, a kernel trace): profiles/cond_steps.json carries its comparison that way.
@@ -52,10 +61,11 @@ from fastfourierdiffusion_amd import _native as N  # noqa: E402
 
 B, INTERVALS, REPS, TRAJ = 512, 20, 3, 5
 EVALS = {"euler_maruyama": 1, "ode_euler": 1, "ode_heun": 2, "pc1": 2, "pc2": 3, "pc1_sample": 2, "cond0": 1, "cond1": 2,
-         "ode_ab2": 1, "dpmpp_2m": 1}
+         "ode_ab2": 1, "dpmpp_2m": 1, "res0_j2": 1, "res0_j10": 1, "res1_j2": 2}
 PC = {"pc1": (1, N.FFD_LANGEVIN_NORM_BATCH), "pc2": (2, N.FFD_LANGEVIN_NORM_BATCH),
       "pc1_sample": (1, N.FFD_LANGEVIN_NORM_SAMPLE)}
 COND = {"cond0": (0, "euler_maruyama"), "cond1": (1, "pc1")}  # corrector steps, the unconditional twin
+RES = {"res0_j2": (0, 2, 2, "cond0"), "res0_j10": (0, 10, 2, "cond0"), "res1_j2": (1, 2, 2, "cond1")}  # correctors, jump, r
 SNR = 0.16
 
 
@@ -68,6 +78,9 @@ def main() -> None:
         del args[0]
     elif args and args[0] == "cond":
         solvers, default_out = ["euler_maruyama", "cond0", "pc1", "cond1"], "cond_steps.json"
+        del args[0]
+    elif args and args[0] == "resample":
+        solvers, default_out = ["cond0", "res0_j2", "res0_j10", "cond1", "res1_j2"], "resample_steps.json"
         del args[0]
     elif args and args[0] == "multistep":
         solvers, default_out = ["euler_maruyama", "ode_euler", "ode_ab2", "dpmpp_2m"], "multistep_steps.json"
@@ -98,7 +111,7 @@ def main() -> None:
 
     prior = DiffusionSampler(model, B, rng="philox", seed=42)
     cond = None
-    if any(sv in COND for sv in solvers):  # one observed series for the batch, a prefix mask, a std table
+    if any(sv in COND or sv in RES for sv in solvers):  # one observed series for the batch, a prefix mask, a std table
         L, Cn = model.max_len, model.n_channels
         g = torch.Generator().manual_seed(7)
         obs = torch.randn((1, L, Cn), generator=g).to(dev)
@@ -113,6 +126,10 @@ def main() -> None:
         elif solver in COND:
             rc = lib.ffd_sample_batch_cond(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, COND[solver][0], SNR,
                                            N.FFD_LANGEVIN_NORM_BATCH, 42, 0, None, 0, 0, C.byref(cond), stream)
+        elif solver in RES:  # the whole schedule over the n-point grid
+            n_corr, jump, r, _ = RES[solver]
+            rc = lib.ffd_sample_batch_resample(hdl, X.data_ptr(), B, ts_c, n, h, 0, r * n, jump, r, n_corr, SNR,
+                                               N.FFD_LANGEVIN_NORM_BATCH, 42, 0, None, C.byref(cond), stream)
         elif solver in PC:
             rc = lib.ffd_sample_batch_pc(hdl, X.data_ptr(), B, ts_c, n, h, 0, INTERVALS, PC[solver][0], SNR, PC[solver][1], 42,
                                          0, None, 0, 0, stream)
@@ -130,7 +147,7 @@ def main() -> None:
             trajectory(solver, X)
         torch.cuda.synchronize(dev)
         assert torch.isfinite(X).all(), solver
-        return (time.perf_counter() - t0) * 1e3 / (TRAJ * INTERVALS)
+        return (time.perf_counter() - t0) * 1e3 / (TRAJ * (RES[solver][2] * n if solver in RES else INTERVALS))
 
     for s in solvers:
         timed(s)  # warm-up
@@ -158,6 +175,34 @@ def main() -> None:
         if s in solvers and twin in solvers:
             res["solvers"][s]["cost_vs_unconditional"] = round(res["solvers"][s]["ms_per_interval"] /
                                                                res["solvers"][twin]["ms_per_interval"], 4)
+    for s, (n_corr, jump, r, twin) in RES.items():
+        if s in solvers and twin in solvers:
+            res["solvers"][s].update(visits=r * n, transitions=(r - 1) * -(-n // jump), jump=jump, resample=r,
+                                     cost_vs_conditional_step=round(res["solvers"][s]["ms_per_interval"] /
+                                                                    res["solvers"][twin]["ms_per_interval"], 4))
+    if any(s in RES for s in solvers):  # the two operators alone, on the loop's state shape
+        L, Cn = model.max_len, model.n_channels
+        X = prior.sample_prior(B)
+        desc, G = sch._desc(), sch._G_on(dev)
+
+        def launches(fn, count=400):
+            for _ in range(20):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(count):
+                fn()
+            e1.record()
+            torch.cuda.synchronize(dev)
+            return round(e0.elapsed_time(e1) * 1e3 / count, 3)
+
+        res["operator_us_per_launch"] = {
+            "note": "back-to-back launches between two events, device draws, (512, 187, 1): launch spacing, not a kernel trace",
+            "ffd_forward_transition": launches(lambda: N.check(lib.ffd_forward_transition(
+                C.byref(desc), X.data_ptr(), G.data_ptr(), 0.25, 0.5, None, 42, 0, 0xE0000000, B, L, Cn, stream), None, "transition")),
+            "ffd_cond_project": launches(lambda: N.check(lib.ffd_cond_project(
+                C.byref(desc), X.data_ptr(), obs.data_ptr(), mask.data_ptr(), std.data_ptr(), G.data_ptr(), 0.5, 0, None, 42, 0,
+                0xC0000000, 1, N.FFD_COND_FREQUENCY, B, L, Cn, stream), None, "project"))}
     if alongside is not None:
         res["measured_alongside"] = alongside
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
