@@ -68,6 +68,8 @@ class CacheStats(C.Structure):
 
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
+# how every ffd_sample_batch* entry begins: ctx, x, B, timesteps, n_steps, step_size, first, n_run
+_LOOP = [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int]
 
 # name -> (restype, argtypes); must list every symbol include/ffd.h declares
 SIGNATURES = {
@@ -156,18 +158,15 @@ SIGNATURES = {
     "ffd_cache_reset": (C.c_int, [_P]),
     "ffd_cache_stats_get": (C.c_int, [_P, C.POINTER(CacheStats)]),
     "ffd_cache_tables_read": (C.c_int, [_P, _P, _P, _P]),
-    "ffd_sample_batch": (C.c_int, [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_uint64,
-                                   C.c_uint64, _P, C.c_int, C.c_int, _P]),
-    "ffd_sample_batch_ode": (C.c_int, [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
-                                       C.c_int, _P]),
-    "ffd_sample_batch_pc": (C.c_int, [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float,
-                                      C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int, C.c_int, _P]),
-    "ffd_sample_batch_cond": (C.c_int, [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float,
-                                        C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int, C.c_int, C.POINTER(CondCfg), _P]),
+    "ffd_sample_batch": (C.c_int, _LOOP + [C.c_uint64, C.c_uint64, _P, C.c_int, C.c_int, _P]),
+    "ffd_sample_batch_ode": (C.c_int, _LOOP + [C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_sample_batch_pc": (C.c_int, _LOOP + [C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int, C.c_int, _P]),
+    "ffd_sample_batch_cond": (C.c_int, _LOOP + [C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int, C.c_int,
+                                                C.POINTER(CondCfg), _P]),
     "ffd_host_resample_visits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "ffd_host_resample_visit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "ffd_sample_batch_resample": (C.c_int, [_P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, _P, C.POINTER(CondCfg), _P]),
+    "ffd_sample_batch_resample": (C.c_int, _LOOP + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, _P,
+                                                    C.POINTER(CondCfg), _P]),
     "ffd_flops_per_sample_step": (C.c_double, [_P, C.c_int]),
     "ffd_ffn_flops_per_launch": (C.c_double, [_P, C.c_int]),
     "ffd_kernel_timing_begin": (C.c_int, [_P, C.c_uint32, C.c_int]),

@@ -1170,14 +1170,25 @@ int ffd_cache_tables_read(ffd_ctx* ctx, float* k_out, float* v_out, void* stream
 // ---------------------------------------------------------------------------
 // the sampling loop (sampler.py:156-210)
 // ---------------------------------------------------------------------------
-// Can this model's sampling step unembed inside the SDE-step kernel?  (ffd_sample_batch adds its arguments' alignment.)
+// Can this model's sampling step unembed inside the step kernel?  (The loops add their arguments' alignment.)
 static bool tail_fusable(const ffd_ctx* ctx) {
   const ffd_model_desc& m = ctx->desc;
   return g_fuse_tail && !ctx->fresca_on && m.kind != FFD_MODEL_MLP && m.kind != FFD_MODEL_MIXTURE &&
          unembed_sde_supported(m.n_channels, m.d_model);
 }
 
-// The steps the two loop entries share.
+// ... and do this call's arguments allow it?  Without FreSca the score is consumed only by the step: unembedding inside
+// the step kernel saves one launch and a (B, L, C) round trip per step; FreSca needs the
+// whole score (FFT along L).  At C % 4 == 0 the fused kernels read float4 rows: x, the Philox element offset and every
+// slab of the injected noise (each aligned like the first) must then sit on 16 bytes.  The ODE tails draw nothing:
+// z_inject = nullptr, elem_off = 0; the workspace buffers they also touch are 16-byte aligned.
+static bool tail_fuses(const ffd_ctx* ctx, const float* x, const float* z_inject, uint64_t elem_off, size_t slab) {
+  if (!tail_fusable(ctx)) return false;
+  if (ctx->desc.n_channels % 4 != 0) return true;
+  return elem_off % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 &&
+         (!z_inject || (reinterpret_cast<uintptr_t>(z_inject) % 16 == 0 && slab % 4 == 0));
+}
+
 // FreSca needs two more score-sized buffers.
 static int ensure_fresca_work(ffd_ctx* ctx, int B) {
   const ffd_model_desc& m = ctx->desc;
@@ -1236,77 +1247,53 @@ static int fresca_score(ffd_ctx* ctx, double t, int B, hipStream_t s, const floa
   return FFD_OK;
 }
 
-int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
-                     int first_step, int n_run, uint64_t seed, uint64_t sample_offset, const float* z_inject,
-                     int use_cache, int global_step0, void* stream) {
-  if (!ctx) return FFD_ERR_INVALID;
+}  // extern "C" (a template follows)
+
+// How every sampling loop starts.  The checks the entries share, in this order: the context, x / timesteps / the range
+// [first, first + n_run) within the n_iter iterations the grid offers (steps, intervals or visits), step_size, the
+// cache.  Then entry_checks(): the caller's own argument checks, which may rely on the shared ones (a non-zero status
+// ends the call).  Only then the device: the workspace, FreSca's buffers, the time table; no multistep history is
+// current until the ODE loop says so.  who: the public entry, for the messages.
+template <class EntryChecks>
+static int loop_begin(ffd_ctx* ctx, const char* who, const float* x, int B, const float* timesteps, int n_steps, int n_iter,
+                      int first, int n_run, float step_size, int use_cache, hipStream_t s, EntryChecks entry_checks) {
   int rc = check_ready(ctx, B);
   if (rc) return rc;
-  if (!x || !timesteps || n_steps < 1 || first_step < 0 || n_run < 0 || first_step + n_run > n_steps)
-    return ctx->fail(FFD_ERR_INVALID, "bad argument to ffd_sample_batch (n_steps=%d first=%d run=%d)", n_steps,
-                     first_step, n_run);
-  if (!(step_size > 0.f)) return ctx->fail(FFD_ERR_INVALID, "step_size must be > 0 (sde.py:157,238)");
-  if (use_cache && !ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "use_cache without ffd_cache_enable");
+  if (!x || !timesteps || n_iter < 1 || first < 0 || n_run < 0 || n_run > n_iter - first)
+    return ctx->fail(FFD_ERR_INVALID, "bad argument to %s (n_steps=%d first=%d run=%d of %d)", who, n_steps, first, n_run,
+                     n_iter);
+  if (!(step_size > 0.f)) return ctx->fail(FFD_ERR_INVALID, "%s: step_size must be > 0 (sde.py:157,238)", who);
   if (use_cache && ctx->desc.kind != FFD_MODEL_TRANSFORMER)
-    return ctx->fail(FFD_ERR_UNSUPPORTED, "caching is only defined for the transformer backbone");
+    return ctx->fail(FFD_ERR_UNSUPPORTED, "%s: caching is only defined for the transformer backbone", who);
+  if (use_cache && !ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "%s: use_cache without ffd_cache_enable", who);
+  if ((rc = entry_checks())) return rc;
   HIPCHECK(hipSetDevice(ctx->device));
   if ((rc = ensure_workspace(ctx, B))) return rc;
-  const ffd_model_desc& m = ctx->desc;
-  const int d = m.d_model;
-  hipStream_t s = (hipStream_t)stream;
   if ((rc = ensure_fresca_work(ctx, B))) return rc;
   if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
-  ctx->tail_solver = FFD_SOLVER_EULER_MARUYAMA;
   ctx->ms_solver = -1;
-  const size_t slab = (size_t)B * m.max_len * m.n_channels;
-  const uint64_t elem_off = sample_offset * (uint64_t)m.max_len * m.n_channels;
-  // Without FreSca the score is consumed only by the SDE step: unembed inside the step kernel (one launch and a
-  // (B, L, C) round trip less per step).  FreSca needs the whole score (FFT along L).
-  const bool fuse_tail = tail_fusable(ctx) && (m.n_channels % 4 != 0 || elem_off % 4 == 0) &&
-                         (m.n_channels % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 == 0) &&  // float4 x rows
-                         (!z_inject || m.n_channels % 4 != 0 ||  // float4 reads of the injected noise only when C % 4 == 0
-                          (reinterpret_cast<uintptr_t>(z_inject) % 16 == 0 && slab % 4 == 0));
-  for (int j = 0; j < n_run; ++j) {
-    const int i = first_step + j;
-    int n_rec = -1;
-    if (use_cache) {
-      const int gstep = global_step0 + j;
-      ctx->stats.current_step = gstep;
-      n_rec = ffd_host_gate(gstep, m.max_len, ctx->ccfg.K, ctx->ccfg.R);
-    }
-    float* crf_dst = nullptr;
-    float* crf_copy = nullptr;
-    if (use_cache && ctx->crf_cap_on) crf_capture_targets(ctx, global_step0 + j, n_run - 1 - j, &crf_dst, &crf_copy);
-    const float* hidden = nullptr;
-    if ((rc = forward_impl(ctx, x, ctx->temb_tab.p + (size_t)i * d, 0, ctx->score.p, crf_dst, B, n_rec, s,
-                           fuse_tail ? &hidden : nullptr)))
-      return rc;
-    if (crf_copy)
-      HIPCHECK(hipMemcpyAsync(crf_copy, crf_dst, sizeof(float) * (size_t)m.num_layers * m.max_len * d,
-                              hipMemcpyDeviceToDevice, s));
-    if (use_cache) ctx->stats.current_step = i;  // sampler.py:73-74 (Q4)
-    const double t = (double)timesteps[i];
-    const float* score = ctx->score.p;
-    if (ctx->fresca_on && (rc = fresca_score(ctx, t, B, s, &score))) return rc;
-    if (hidden)
-      TIMED(FFD_K_SDE, launch_unembed_sde(hidden, ctx->model.unembed_w, ctx->model.unembed_b, x,
-                                          z_inject ? z_inject + (size_t)j * slab : nullptr, ctx->G_dev,
-                                          sde_params(m.sde, m.sde_a, m.sde_b, t, step_size), seed, elem_off, (uint32_t)i,
-                                          B, m.max_len, m.n_channels, d, s));
-    else
-      TIMED(FFD_K_SDE, launch_sde_step(x, score, z_inject ? z_inject + (size_t)j * slab : nullptr, ctx->G_dev,
-                                       sde_params(m.sde, m.sde_a, m.sde_b, t, step_size), seed, elem_off, (uint32_t)i, B,
-                                       m.max_len, m.n_channels, s));
-  }
   return FFD_OK;
 }
+extern "C" {
 
-// One score evaluation of an ODE interval, up to where its tail takes over: the forward at time-table row `row` with
-// recompute-set size n_rec (< 0: no cache), the CRF capture, FreSca.  Fused tail: *hidden = the final hidden rows
-// (unembedded inside the tail kernel); otherwise *score = the buffer that holds the (FreSca-scaled) score.
-static int ode_evaluate(ffd_ctx* ctx, const float* xin, int row, double t, int B, int n_rec, float* crf_dst,
-                        float* crf_copy, bool fuse, hipStream_t s, const float** hidden, const float** score) {
+// One score evaluation of a sampling step, up to where the step's tail takes over: the forward of xin at time-table
+// row `row` (time t), the CRF capture, FreSca.  With the cache, a step's first evaluation is `gated`: the gate at global
+// step gstep picks its recompute set, its CRF goes where the capture wants it (rest = the gated evaluations of this
+// call that still follow), and stats.current_step reads gstep during the forward and the grid index behind it
+// (sampler.py:70-74, Q4).  Every later evaluation of the step (Heun's second, the correctors' and the predictor's
+// behind them) is a pure hit.  fuse: *hidden = the final hidden rows, which the tail kernel unembeds; otherwise
+// *hidden = nullptr and *score = the buffer that holds the (FreSca-scaled) score.
+static int loop_evaluate(ffd_ctx* ctx, const float* xin, int row, double t, int B, bool use_cache, bool gated, int gstep,
+                         int rest, bool fuse, hipStream_t s, const float** hidden, const float** score) {
   const ffd_model_desc& m = ctx->desc;
+  int n_rec = use_cache ? 0 : -1;
+  float *crf_dst = nullptr, *crf_copy = nullptr;
+  gated = gated && use_cache;
+  if (gated) {
+    ctx->stats.current_step = gstep;
+    n_rec = ffd_host_gate(gstep, m.max_len, ctx->ccfg.K, ctx->ccfg.R);
+    if (ctx->crf_cap_on) crf_capture_targets(ctx, gstep, rest, &crf_dst, &crf_copy);
+  }
   *hidden = nullptr;
   if (int rc = forward_impl(ctx, xin, ctx->temb_tab.p + (size_t)row * m.d_model, 0, ctx->score.p, crf_dst, B, n_rec, s,
                             fuse ? hidden : nullptr))
@@ -1314,6 +1301,7 @@ static int ode_evaluate(ffd_ctx* ctx, const float* xin, int row, double t, int B
   if (crf_copy)
     HIPCHECK(hipMemcpyAsync(crf_copy, crf_dst, sizeof(float) * (size_t)m.num_layers * m.max_len * m.d_model,
                             hipMemcpyDeviceToDevice, s));
+  if (gated) ctx->stats.current_step = row;
   *score = ctx->score.p;
   if (ctx->fresca_on) return fresca_score(ctx, t, B, s, score);
   return FFD_OK;
@@ -1322,24 +1310,19 @@ static int ode_evaluate(ffd_ctx* ctx, const float* xin, int row, double t, int B
 int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
                          int first_step, int n_run, int solver, int use_cache, int global_step0, void* stream) {
   if (!ctx) return FFD_ERR_INVALID;
-  int rc = check_ready(ctx, B);
-  if (rc) return rc;
-  if (!x || !timesteps || n_steps < 2 || first_step < 0 || n_run < 0 || first_step + n_run > n_steps - 1)
-    return ctx->fail(FFD_ERR_INVALID, "bad argument to ffd_sample_batch_ode (n_steps=%d first=%d run=%d: %d intervals)",
-                     n_steps, first_step, n_run, n_steps - 1);
   const bool multistep = solver == FFD_SOLVER_ODE_AB2 || solver == FFD_SOLVER_DPMPP_2M;
-  if (solver != FFD_SOLVER_ODE_EULER && solver != FFD_SOLVER_ODE_HEUN && !multistep)
-    return ctx->fail(FFD_ERR_INVALID, "unknown ODE solver %d", solver);
-  if (!(step_size > 0.f)) return ctx->fail(FFD_ERR_INVALID, "step_size must be > 0");
-  if (use_cache && ctx->desc.kind != FFD_MODEL_TRANSFORMER)
-    return ctx->fail(FFD_ERR_UNSUPPORTED, "caching is only defined for the transformer backbone");
-  if (use_cache && !ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "use_cache without ffd_cache_enable");
+  const bool heun = solver == FFD_SOLVER_ODE_HEUN;
   const ffd_model_desc& m = ctx->desc;
   const int L = m.max_len, C = m.n_channels, d = m.d_model;
-  // The multistep solvers: every interval's coefficients, before any device work.  A trajectory continues
-  // (first_step > 0) only on the history the context's previous loop call left for exactly this interval.
+  hipStream_t s = (hipStream_t)stream;
   std::vector<MultistepParams> ms_coef;
-  if (multistep) {
+  int rc = loop_begin(ctx, "ffd_sample_batch_ode", x, B, timesteps, n_steps, n_steps > 1 ? n_steps - 1 : 0, first_step,
+                      n_run, step_size, use_cache, s, [&]() -> int {
+    if (solver != FFD_SOLVER_ODE_EULER && !heun && !multistep)
+      return ctx->fail(FFD_ERR_INVALID, "unknown ODE solver %d", solver);
+    if (!multistep) return FFD_OK;
+    // The multistep solvers: every interval's coefficients.  A trajectory continues (first_step > 0) only on the
+    // history the context's previous loop call left for exactly this interval.
     if (first_step > 0 && (ctx->ms_solver != solver || ctx->ms_B != B || ctx->ms_next != first_step))
       return ctx->fail(FFD_ERR_STATE, "first_step=%d continues a multistep trajectory, but the context's previous sampling "
                        "call did not end there with solver %d and B=%d", first_step, solver, B);
@@ -1352,24 +1335,18 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
                          "strictly and sigma(t) must be > 0)", i);
       ms_coef.push_back(multistep_params(c));
     }
-  }
-  HIPCHECK(hipSetDevice(ctx->device));
-  if ((rc = ensure_workspace(ctx, B))) return rc;
-  const bool heun = solver == FFD_SOLVER_ODE_HEUN;
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = ensure_fresca_work(ctx, B))) return rc;
+    return FFD_OK;
+  });
+  if (rc) return rc;
   if (heun) {  // the predicted state and the predictor's drift
     if ((rc = ensure(ctx, ctx->ode_xp, (size_t)B * L * C))) return rc;
     if ((rc = ensure(ctx, ctx->ode_d1, (size_t)B * L * C))) return rc;
   }
   if (multistep && (rc = ensure(ctx, ctx->ode_hist, (size_t)B * L * C))) return rc;  // (a continued call: already there)
-  if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
-  ctx->tail_solver = solver;
-  ctx->ms_solver = -1;  // (multistep: set again once the call's intervals are enqueued)
+  ctx->tail_solver = solver;  // (multistep: ms_solver is set again once the call's intervals are enqueued)
   float* const xp = ctx->ode_xp.p;
   float* const d1 = ctx->ode_d1.p;
-  // the workspace buffers are 16-byte aligned: only the caller's x decides the quad path
-  const bool fuse = tail_fusable(ctx) && (C % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 == 0);
+  const bool fuse = tail_fuses(ctx, x, nullptr, 0, 0);
   auto tail = [&](int which, const float* hidden, const float* score, double t) -> hipError_t {
     const SdeParams p = sde_params(m.sde, m.sde_a, m.sde_b, t, step_size);
     if (hidden) return launch_unembed_ode(which, hidden, ctx->model.unembed_w, ctx->model.unembed_b, x, xp, d1, ctx->G_dev, p, B, L, C, d, s);
@@ -1377,18 +1354,10 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
   };
   for (int j = 0; j < n_run; ++j) {
     const int i = first_step + j;
-    int n_rec = -1;
-    float *crf_dst = nullptr, *crf_copy = nullptr;
-    if (use_cache) {
-      const int gstep = global_step0 + j;
-      ctx->stats.current_step = gstep;
-      n_rec = ffd_host_gate(gstep, L, ctx->ccfg.K, ctx->ccfg.R);
-      if (ctx->crf_cap_on) crf_capture_targets(ctx, gstep, n_run - 1 - j, &crf_dst, &crf_copy);
-    }
     const float *hidden, *score;
     const double t = (double)timesteps[i];
-    if ((rc = ode_evaluate(ctx, x, i, t, B, n_rec, crf_dst, crf_copy, fuse, s, &hidden, &score))) return rc;
-    if (use_cache) ctx->stats.current_step = i;
+    if ((rc = loop_evaluate(ctx, x, i, t, B, use_cache, true, global_step0 + j, n_run - 1 - j, fuse, s, &hidden, &score)))
+      return rc;
     if (multistep) {  // history: every interval but a trajectory's first
       if (hidden)
         TIMED(FFD_K_SDE, launch_unembed_multistep(hidden, ctx->model.unembed_w, ctx->model.unembed_b, x, ctx->ode_hist.p,
@@ -1401,7 +1370,7 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
     if (!heun) continue;
     // the corrector's evaluation at (xp, t_{i+1}): with the cache a pure hit
     const double tn = (double)timesteps[i + 1];
-    if ((rc = ode_evaluate(ctx, xp, i + 1, tn, B, use_cache ? 0 : -1, nullptr, nullptr, fuse, s, &hidden, &score))) return rc;
+    if ((rc = loop_evaluate(ctx, xp, i + 1, tn, B, use_cache, false, 0, 0, fuse, s, &hidden, &score))) return rc;
     TIMED(FFD_K_SDE, tail(ODE_CORRECT, hidden, score, tn));
   }
   if (multistep && first_step + n_run > 0) ctx->ms_solver = solver, ctx->ms_B = B, ctx->ms_next = first_step + n_run;
@@ -1435,26 +1404,25 @@ int ffd_host_resample_visit(int n_steps, int jump, int resample, int visit, int*
   return resample_visit(n_steps, jump, resample, visit, step_out, back_to_out, &q);
 }
 
-// Predictor-corrector sampling: n_corrector Langevin corrector steps (ffd_langevin.hip), then the Euler-Maruyama
-// predictor of ffd_sample_batch, per reverse step.  Every evaluation after a step's first is a pure cache hit.
-// cond != nullptr (ffd_sample_batch_cond): one projection onto the observation behind every update, and z_inject
-// holds two draws per update (its own, then the projection's).  resample > 1 (ffd_sample_batch_resample): first_step and
-// n_run count VISITS of the schedule above, and a visit that ends a pass of its block is followed by one forward
-// transition back to the block's first time level (one more slab of z_inject).  The arguments' first checks are the
-// callers'.
-static int pc_loop(ffd_ctx* ctx, const char* who, float* x, int B, const float* timesteps, int n_steps, float step_size,
-                   int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed, uint64_t sample_offset,
-                   const float* z_inject, int use_cache, int global_step0, const ffd_cond_cfg* cond, int jump, int resample,
-                   void* stream) {
-  int rc = check_ready(ctx, B);
-  if (rc) return rc;
+// The stochastic loop behind ffd_sample_batch and its _pc / _cond / _resample forms.  Per reverse step: n_corrector
+// Langevin corrector steps (ffd_langevin.hip), then the Euler-Maruyama predictor; with n_corrector == 0 that is plain
+// Euler-Maruyama.  cond != nullptr (ffd_sample_batch_cond): one projection onto the observation behind every update, and
+// z_inject holds two draws per update (its own, then the projection's).  resample > 1 (ffd_sample_batch_resample):
+// first_step and n_run count VISITS of the schedule above, and a visit that ends a pass of its block is followed by one
+// forward transition back to the block's first time level (one more slab of z_inject).  The entries check what only
+// they take before they call this.
+static int sde_loop(ffd_ctx* ctx, const char* who, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                    int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed, uint64_t sample_offset,
+                    const float* z_inject, int use_cache, int global_step0, const ffd_cond_cfg* cond, int jump, int resample,
+                    void* stream) {
+  const ffd_model_desc& m = ctx->desc;
+  const int L = m.max_len, C = m.n_channels, d = m.d_model;
+  hipStream_t s = (hipStream_t)stream;
   const int n_visits = n_steps < 1 ? 0 : ffd_host_resample_visits(n_steps, jump, resample);
-  if (!x || !timesteps || n_visits < 1 || first_step < 0 || n_run < 0 || n_run > n_visits - first_step)
-    return ctx->fail(FFD_ERR_INVALID, "bad argument to %s (n_steps=%d jump=%d resample=%d first=%d run=%d)", who, n_steps,
-                     jump, resample, first_step, n_run);
-  if (!cond && (int64_t)n_steps * n_corrector > 0x7FFFFFF0ll)
-    return ctx->fail(FFD_ERR_INVALID, "n_steps * n_corrector exceeds the corrector's Philox tag range");
-  if (cond) {
+  int rc = loop_begin(ctx, who, x, B, timesteps, n_steps, n_visits, first_step, n_run, step_size, use_cache, s, [&]() -> int {
+    if (!cond && (int64_t)n_steps * n_corrector > 0x7FFFFFF0ll)
+      return ctx->fail(FFD_ERR_INVALID, "n_steps * n_corrector exceeds the corrector's Philox tag range");
+    if (!cond) return FFD_OK;
     if ((int64_t)n_steps * ((int64_t)n_corrector + 1) > 0x3FFFFFF0ll)
       return ctx->fail(FFD_ERR_INVALID, "n_steps * (n_corrector + 1) exceeds the projection's Philox tag range");
     for (int i = 0; resample > 1 && i < n_steps; ++i)  // a transition runs from a later grid point (or 0) back to an earlier
@@ -1467,32 +1435,19 @@ static int pc_loop(ffd_ctx* ctx, const char* who, float* x, int B, const float* 
       return ctx->fail(FFD_ERR_INVALID, "unknown conditioning domain %d", cond->domain);
     if (cond->domain == FFD_COND_TIME && cond->std) return ctx->fail(FFD_ERR_INVALID, "std with the time domain");
     if (x == cond->obs || x == cond->mask) return ctx->fail(FFD_ERR_INVALID, "x aliases obs or mask");
-  }
-  if (!(step_size > 0.f)) return ctx->fail(FFD_ERR_INVALID, "step_size must be > 0 (sde.py:157,238)");
-  if (cond && cond->domain == FFD_COND_FREQUENCY && !cond_len_supported(ctx->desc.max_len))
-    return ctx->fail(FFD_ERR_UNSUPPORTED, "frequency-domain conditioning takes 2 <= L <= 4096");
-  if (use_cache && !ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "use_cache without ffd_cache_enable");
-  if (use_cache && ctx->desc.kind != FFD_MODEL_TRANSFORMER)
-    return ctx->fail(FFD_ERR_UNSUPPORTED, "caching is only defined for the transformer backbone");
-  HIPCHECK(hipSetDevice(ctx->device));
-  if ((rc = ensure_workspace(ctx, B))) return rc;
-  const ffd_model_desc& m = ctx->desc;
-  const int L = m.max_len, C = m.n_channels, d = m.d_model;
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = ensure_fresca_work(ctx, B))) return rc;
+    if (cond->domain == FFD_COND_FREQUENCY && !cond_len_supported(L))
+      return ctx->fail(FFD_ERR_UNSUPPORTED, "frequency-domain conditioning takes 2 <= L <= 4096");
+    return FFD_OK;
+  });
+  if (rc) return rc;
   if (n_corrector > 0 &&
       (rc = ensure(ctx, ctx->lv_work, (langevin_work_bytes(B, L) + sizeof(float) - 1) / sizeof(float))))
     return rc;
-  if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
   ctx->tail_solver = n_corrector > 0 ? FFD_SOLVER_PC : FFD_SOLVER_EULER_MARUYAMA;
-  ctx->ms_solver = -1;
   const size_t slab = (size_t)B * L * C;
   const size_t zstride = cond ? 2 * slab : slab;  // z_inject per update
   const uint64_t elem_off = sample_offset * (uint64_t)L * C;
-  // the predictor's tail fuses under ffd_sample_batch's conditions (every slab of z_inject is aligned like the first)
-  const bool fuse_tail = tail_fusable(ctx) && (C % 4 != 0 || elem_off % 4 == 0) &&
-                         (C % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
-                         (!z_inject || C % 4 != 0 || (reinterpret_cast<uintptr_t>(z_inject) % 16 == 0 && slab % 4 == 0));
+  const bool fuse_tail = tail_fuses(ctx, x, z_inject, elem_off, slab);  // (the predictor's; the correctors read the score)
   auto project = [&](double t, int noiseless, const float* z, uint32_t tag) -> hipError_t {
     float mc, sigma;
     cond_coeffs(m.sde, m.sde_a, m.sde_b, t, noiseless, &mc, &sigma);
@@ -1513,18 +1468,10 @@ static int pc_loop(ffd_ctx* ctx, const char* who, float* x, int B, const float* 
     if (znext) znext += (size_t)(n_corrector + 1) * zstride + (back_to >= 0 ? slab : 0);
     for (int k = 0; k <= n_corrector; ++k) {  // k == n_corrector: the predictor
       const bool predictor = k == n_corrector;
-      int n_rec = use_cache ? 0 : -1;
-      float *crf_dst = nullptr, *crf_copy = nullptr;
-      if (use_cache && k == 0) {
-        const int gstep = global_step0 + j;
-        ctx->stats.current_step = gstep;
-        n_rec = ffd_host_gate(gstep, L, ctx->ccfg.K, ctx->ccfg.R);
-        if (ctx->crf_cap_on) crf_capture_targets(ctx, gstep, n_run - 1 - j, &crf_dst, &crf_copy);
-      }
       const float *hidden, *score;
-      if ((rc = ode_evaluate(ctx, x, i, t, B, n_rec, crf_dst, crf_copy, predictor && fuse_tail, s, &hidden, &score)))
+      if ((rc = loop_evaluate(ctx, x, i, t, B, use_cache, k == 0, global_step0 + j, n_run - 1 - j, predictor && fuse_tail,
+                              s, &hidden, &score)))
         return rc;
-      if (use_cache && k == 0) ctx->stats.current_step = i;  // sampler.py:73-74 (Q4)
       const float* zk = zj ? zj + (size_t)k * zstride : nullptr;
       if (!predictor)
         TIMED(FFD_K_SDE, launch_langevin(x, score, zk, ctx->G_dev, langevin_alpha(m.sde, m.sde_a, m.sde_b, t, step_size),
@@ -1556,19 +1503,33 @@ static int pc_loop(ffd_ctx* ctx, const char* who, float* x, int B, const float* 
   return FFD_OK;
 }
 
-int ffd_sample_batch_pc(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
-                        int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed,
-                        uint64_t sample_offset, const float* z_inject, int use_cache, int global_step0, void* stream) {
+int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                     int first_step, int n_run, uint64_t seed, uint64_t sample_offset, const float* z_inject,
+                     int use_cache, int global_step0, void* stream) {
   if (!ctx) return FFD_ERR_INVALID;
+  return sde_loop(ctx, "ffd_sample_batch", x, B, timesteps, n_steps, step_size, first_step, n_run, 0, 0.f, 0, seed,
+                  sample_offset, z_inject, use_cache, global_step0, nullptr, 1, 1, stream);
+}
+
+// what the entries with correctors check first
+static int check_corrector(ffd_ctx* ctx, int n_corrector, float snr, int norm) {
   if (n_corrector < 0) return ctx->fail(FFD_ERR_INVALID, "n_corrector must be >= 0");
   if (!(snr > 0.f)) return ctx->fail(FFD_ERR_INVALID, "snr must be > 0");
   if (norm != FFD_LANGEVIN_NORM_BATCH && norm != FFD_LANGEVIN_NORM_SAMPLE)
     return ctx->fail(FFD_ERR_INVALID, "unknown corrector norm %d", norm);
+  return FFD_OK;
+}
+
+int ffd_sample_batch_pc(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
+                        int first_step, int n_run, int n_corrector, float snr, int norm, uint64_t seed,
+                        uint64_t sample_offset, const float* z_inject, int use_cache, int global_step0, void* stream) {
+  if (!ctx) return FFD_ERR_INVALID;
+  if (int rc = check_corrector(ctx, n_corrector, snr, norm)) return rc;
   if (n_corrector == 0)
     return ffd_sample_batch(ctx, x, B, timesteps, n_steps, step_size, first_step, n_run, seed, sample_offset, z_inject,
                             use_cache, global_step0, stream);
-  return pc_loop(ctx, "ffd_sample_batch_pc", x, B, timesteps, n_steps, step_size, first_step, n_run, n_corrector, snr, norm,
-                 seed, sample_offset, z_inject, use_cache, global_step0, nullptr, 1, 1, stream);
+  return sde_loop(ctx, "ffd_sample_batch_pc", x, B, timesteps, n_steps, step_size, first_step, n_run, n_corrector, snr,
+                  norm, seed, sample_offset, z_inject, use_cache, global_step0, nullptr, 1, 1, stream);
 }
 
 // Conditional sampling by replacement: the predictor-corrector step with one ffd_cond_project behind every update.
@@ -1580,13 +1541,10 @@ int ffd_sample_batch_cond(ffd_ctx* ctx, float* x, int B, const float* timesteps,
   if (!cond)
     return ffd_sample_batch_pc(ctx, x, B, timesteps, n_steps, step_size, first_step, n_run, n_corrector, snr, norm, seed,
                                sample_offset, z_inject, use_cache, global_step0, stream);
-  if (n_corrector < 0) return ctx->fail(FFD_ERR_INVALID, "n_corrector must be >= 0");
-  if (!(snr > 0.f)) return ctx->fail(FFD_ERR_INVALID, "snr must be > 0");
-  if (norm != FFD_LANGEVIN_NORM_BATCH && norm != FFD_LANGEVIN_NORM_SAMPLE)
-    return ctx->fail(FFD_ERR_INVALID, "unknown corrector norm %d", norm);
+  if (int rc = check_corrector(ctx, n_corrector, snr, norm)) return rc;
   if (x && z_inject == x) return ctx->fail(FFD_ERR_INVALID, "x aliases z_inject");
-  return pc_loop(ctx, "ffd_sample_batch_cond", x, B, timesteps, n_steps, step_size, first_step, n_run, n_corrector, snr, norm,
-                 seed, sample_offset, z_inject, use_cache, global_step0, cond, 1, 1, stream);
+  return sde_loop(ctx, "ffd_sample_batch_cond", x, B, timesteps, n_steps, step_size, first_step, n_run, n_corrector, snr,
+                  norm, seed, sample_offset, z_inject, use_cache, global_step0, cond, 1, 1, stream);
 }
 
 // Resampled conditional sampling ("time travel", RePaint): the conditional loop over the visit schedule above.
@@ -1597,16 +1555,13 @@ int ffd_sample_batch_resample(ffd_ctx* ctx, float* x, int B, const float* timest
   if (!ctx) return FFD_ERR_INVALID;
   if (!cond) return ctx->fail(FFD_ERR_INVALID, "ffd_sample_batch_resample needs an observation (cond)");
   if (jump < 1 || resample < 1) return ctx->fail(FFD_ERR_INVALID, "jump and resample must be >= 1");
-  if (n_corrector < 0) return ctx->fail(FFD_ERR_INVALID, "n_corrector must be >= 0");
-  if (!(snr > 0.f)) return ctx->fail(FFD_ERR_INVALID, "snr must be > 0");
-  if (norm != FFD_LANGEVIN_NORM_BATCH && norm != FFD_LANGEVIN_NORM_SAMPLE)
-    return ctx->fail(FFD_ERR_INVALID, "unknown corrector norm %d", norm);
+  if (int rc = check_corrector(ctx, n_corrector, snr, norm)) return rc;
   if (x && z_inject == x) return ctx->fail(FFD_ERR_INVALID, "x aliases z_inject");
   const int64_t visits = (int64_t)n_steps * resample;  // the projections' tags stay below the transitions' 0xE0000000
   if (visits > 0x1FFFFFF0ll || (visits > 0 && visits * ((int64_t)n_corrector + 1) > 0x1FFFFFF0ll))
     return ctx->fail(FFD_ERR_INVALID, "visits * (n_corrector + 1) reaches the transitions' Philox tags");
-  return pc_loop(ctx, "ffd_sample_batch_resample", x, B, timesteps, n_steps, step_size, first_visit, n_visits, n_corrector,
-                 snr, norm, seed, sample_offset, z_inject, 0, 0, cond, jump, resample, stream);
+  return sde_loop(ctx, "ffd_sample_batch_resample", x, B, timesteps, n_steps, step_size, first_visit, n_visits, n_corrector,
+                  snr, norm, seed, sample_offset, z_inject, 0, 0, cond, jump, resample, stream);
 }
 
 // ---------------------------------------------------------------------------

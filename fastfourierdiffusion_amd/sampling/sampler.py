@@ -191,7 +191,7 @@ class DiffusionSampler:
         assert t_lo == t_hi  # sampler.py:59-60
         sch = self.noise_scheduler
         needs_grid = self.solver == "ode_heun" or self.solver in MULTISTEP_SOLVERS  # the interval's end is read from it
-        t_next = self._heun_next_time(timesteps[0]) if needs_grid else None
+        t_next = self._next_grid_time(timesteps[0]) if needs_grid else None
         if self.corrector_steps > 0:
             return self._predictor_corrector_step(batch, t_lo, step, recompute_tokens)
         score = self._evaluate_score(batch, t_lo, step, recompute_tokens, update_crf=True)
@@ -257,7 +257,7 @@ class DiffusionSampler:
                                           timestep=t, num_steps=getattr(self, "_num_diffusion_steps", None))
         return score
 
-    def _heun_next_time(self, t: torch.Tensor) -> float:
+    def _next_grid_time(self, t: torch.Tensor) -> float:
         """The grid point after ``t``: Heun's corrector evaluates the model there, and the multistep solvers' interval
         ends there."""
         grid = getattr(self.noise_scheduler, "timesteps", None)
@@ -321,6 +321,11 @@ class DiffusionSampler:
                 N.check(ctx.lib.ffd_host_resample_visit(num_diffusion_steps, jump, resample, u, C.byref(step_out),
                                                         C.byref(back_to)), ctx.handle, "ffd_host_resample_visit")
                 followed.append(back_to.value >= 0)
+        # the draws the host hands over per iteration: every update's own (the correctors' in order, then the predictor's)
+        # and, conditioned, its projection's behind it.  The ODE solvers draw nothing; philox draws inside the kernels.
+        draws = 0
+        if not ode and (self.rng == "torch" or self._injected is not None):
+            draws = (self.corrector_steps + 1) * (2 if cond is not None else 1)
         all_samples = []
         num_batches = max(1, num_samples // self.sample_batch_size)  # remainder dropped (Q10)
         global_step = 0
@@ -336,70 +341,22 @@ class DiffusionSampler:
                 if use_cache:  # the gate reads K, R of the current cache object (sampler.py:179-200)
                     model._native_cache_configure(model.cache)
                 cap = self._crf_capture_begin(ctx, device) if use_cache else None
+                cond_cfg = None
+                if cond is not None:  # this batch's slice of the observation
+                    lo = batch_idx * self.sample_batch_size
+                    shared = cond["obs"].shape[0] == 1
+                    obs = cond["obs"] if shared else cond["obs"][lo:lo + batch_size]
+                    msk = cond["mask"] if shared else cond["mask"][lo:lo + batch_size]
+                    cond_cfg = N.CondCfg(obs.data_ptr(), msk.data_ptr(),
+                                         cond["std"].data_ptr() if cond["std"] is not None else None,
+                                         1 if shared else batch_size, cond["domain"], int(cond["final_replace"]), 0)
                 done = 0
                 while done < n_iter:
-                    n = n_iter - done
-                    z_ptr = None
-                    draws = self.corrector_steps + 1  # per step: the correctors' in order, then the predictor's
-                    if cond is not None:
-                        draws *= 2  # per update its own draw, then its projection's
-                    if not ode and (self.rng == "torch" or self._injected is not None):
-                        n = min(n, max(1, self.z_chunk_steps // draws))  # the z buffer keeps its size
-                        n_draws = n * draws
-                        if followed is not None:  # a visit's draws, then its transition's: whole visits up to the size
-                            n, n_draws = 0, 0
-                            while done + n < n_iter:
-                                more = draws + int(followed[done + n])
-                                if n > 0 and n_draws + more > self.z_chunk_steps:
-                                    break
-                                n, n_draws = n + 1, n_draws + more
-                        z = torch.empty((n_draws,) + tuple(X.shape), device=device, dtype=torch.float32)
-                        for i in range(n_draws):  # one randn_like per draw, as the reference consumes its generator
-                            if self._injected is not None:
-                                z[i].copy_(self._next_injected(X.shape, device))
-                            else:
-                                z[i].normal_()
-                        z_ptr = z.data_ptr()
-                    if ode:  # deterministic given the prior: no step noise is drawn or allocated
-                        rc = ctx.lib.ffd_sample_batch_ode(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
-                                                          step_size, done, n, self._solver_code(), use_cache,
-                                                          (global_step + done) if use_cache else 0, stream)
-                        N.check(rc, ctx.handle, "ffd_sample_batch_ode")
-                    elif cond is not None:
-                        lo = batch_idx * self.sample_batch_size
-                        shared = cond["obs"].shape[0] == 1
-                        obs = cond["obs"] if shared else cond["obs"][lo:lo + batch_size]
-                        msk = cond["mask"] if shared else cond["mask"][lo:lo + batch_size]
-                        cfg = N.CondCfg(obs.data_ptr(), msk.data_ptr(),
-                                        cond["std"].data_ptr() if cond["std"] is not None else None,
-                                        1 if shared else batch_size, cond["domain"], int(cond["final_replace"]), 0)
-                        if resample > 1:
-                            rc = ctx.lib.ffd_sample_batch_resample(ctx.handle, X.data_ptr(), batch_size, ts_c,
-                                                                   num_diffusion_steps, step_size, done, n, jump, resample,
-                                                                   self.corrector_steps, self.snr,
-                                                                   CORRECTOR_NORMS[self.corrector_norm], self.seed,
-                                                                   sample_cursor, z_ptr, C.byref(cfg), stream)
-                            N.check(rc, ctx.handle, "ffd_sample_batch_resample")
-                            done += n
-                            continue
-                        rc = ctx.lib.ffd_sample_batch_cond(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
-                                                           step_size, done, n, self.corrector_steps, self.snr,
-                                                           CORRECTOR_NORMS[self.corrector_norm], self.seed, sample_cursor,
-                                                           z_ptr, use_cache, (global_step + done) if use_cache else 0,
-                                                           C.byref(cfg), stream)
-                        N.check(rc, ctx.handle, "ffd_sample_batch_cond")
-                    elif self.corrector_steps > 0:
-                        rc = ctx.lib.ffd_sample_batch_pc(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
-                                                         step_size, done, n, self.corrector_steps, self.snr,
-                                                         CORRECTOR_NORMS[self.corrector_norm], self.seed, sample_cursor,
-                                                         z_ptr, use_cache, (global_step + done) if use_cache else 0,
-                                                         stream)
-                        N.check(rc, ctx.handle, "ffd_sample_batch_pc")
-                    else:
-                        rc = ctx.lib.ffd_sample_batch(ctx.handle, X.data_ptr(), batch_size, ts_c, num_diffusion_steps,
-                                                      step_size, done, n, self.seed, sample_cursor, z_ptr, use_cache,
-                                                      (global_step + done) if use_cache else 0, stream)
-                        N.check(rc, ctx.handle, "ffd_sample_batch")
+                    n, n_draws = self._next_chunk(done, n_iter, draws, followed)
+                    z = self._draw(n_draws, X.shape, device) if n_draws else None
+                    self._loop_call(ctx, X, (ts_c, num_diffusion_steps, step_size), done, n,
+                                    (self.seed, sample_cursor, z.data_ptr() if z is not None else None),
+                                    (use_cache, (global_step + done) if use_cache else 0), cond_cfg, resample, jump, stream)
                     if cap is not None:
                         self._crf_capture_collect(cap, global_step + done, n, ts, done)
                     done += n
@@ -413,6 +370,49 @@ class DiffusionSampler:
                 sample_cursor += batch_size
         return torch.cat(all_samples, dim=0)
 
+    def _next_chunk(self, done: int, n_iter: int, draws: int, followed: Optional[list]):
+        """(iterations, draws) of the next loop call, which starts at iteration ``done``: whole iterations -- each
+        ``draws`` draws, one more when a transition follows it (``followed``: resampling's visits) -- for as long as
+        the z buffer stays within ``z_chunk_steps`` draws, and one at the least.  Nothing to hand over: all that is left."""
+        if draws == 0:
+            return n_iter - done, 0
+        n = n_draws = 0
+        while done + n < n_iter:
+            more = draws + (int(followed[done + n]) if followed is not None else 0)
+            if n > 0 and n_draws + more > self.z_chunk_steps:
+                break
+            n, n_draws = n + 1, n_draws + more
+        return n, n_draws
+
+    def _draw(self, n_draws: int, shape, device) -> torch.Tensor:
+        """``n_draws`` N(0, 1) slabs in consumption order: the injected ones, or one ``normal_`` per draw, as the
+        reference consumes its generator."""
+        z = torch.empty((n_draws,) + tuple(shape), device=device, dtype=torch.float32)
+        for i in range(n_draws):
+            if self._injected is not None:
+                z[i].copy_(self._next_injected(shape, device))
+            else:
+                z[i].normal_()
+        return z
+
+    def _loop_call(self, ctx, X, grid, first: int, n: int, noise, cache, cfg, resample: int, jump: int, stream) -> None:
+        """Iterations [first, first + n) of the native loop on ``X``, through the entry this sampler's configuration
+        selects.  ``grid``: (timesteps, n_steps, step_size); ``noise``: (seed, sample_offset, z_inject); ``cache``:
+        (use_cache, global_step0); ``cfg``: the batch's ``CondCfg`` or None."""
+        corrector = (self.corrector_steps, self.snr, CORRECTOR_NORMS[self.corrector_norm])
+        if self.solver != "euler_maruyama":  # deterministic given the prior: no noise arguments
+            name, rest = "ffd_sample_batch_ode", (self._solver_code(), *cache)
+        elif cfg is not None and resample > 1:  # (no cache: _check_resampling)
+            name, rest = "ffd_sample_batch_resample", (jump, resample, *corrector, *noise, C.byref(cfg))
+        elif cfg is not None:
+            name, rest = "ffd_sample_batch_cond", (*corrector, *noise, *cache, C.byref(cfg))
+        elif self.corrector_steps > 0:
+            name, rest = "ffd_sample_batch_pc", (*corrector, *noise, *cache)
+        else:
+            name, rest = "ffd_sample_batch", (*noise, *cache)
+        rc = getattr(ctx.lib, name)(ctx.handle, X.data_ptr(), X.shape[0], *grid, first, n, *rest, stream)
+        N.check(rc, ctx.handle, name)
+
     # ------------------------------------------------------------------
     # conditional sampling by replacement (extension)
     def _check_resampling(self, resample, jump) -> None:
@@ -422,6 +422,13 @@ class DiffusionSampler:
         if resample > 1 and self.use_cache:
             raise ValueError("resample > 1 cannot run with use_cache=True: the E2-CRF cache's gate and tables assume that "
                              "the diffusion time only falls, and resampling moves it back up")
+
+    def _check_conditional(self, resample, jump) -> None:
+        """What ``sample_conditional`` and ``impute`` refuse before any device work."""
+        if self.solver != "euler_maruyama":
+            raise ValueError("conditional sampling by replacement is defined for the predictor-corrector sampler: "
+                             "it needs solver='euler_maruyama'")
+        self._check_resampling(resample, jump)
 
     def sample_conditional(self, observed: torch.Tensor, mask: torch.Tensor, num_samples: int,
                            num_diffusion_steps: Optional[int] = None, resample: int = 1, jump: int = 1, *,
@@ -441,10 +448,7 @@ class DiffusionSampler:
         A forecast is the prefix mask ``mask[:n_known] = 1``.  ``resample=r > 1`` runs every block of ``jump`` steps r
         times with a forward transition in between (the module docstring's "Resampling"), at r times the evaluations;
         ``resample=1`` is plain replacement whatever ``jump`` is."""
-        if self.solver != "euler_maruyama":
-            raise ValueError("conditional sampling by replacement is defined for the predictor-corrector sampler: "
-                             "it needs solver='euler_maruyama'")
-        self._check_resampling(resample, jump)
+        self._check_conditional(resample, jump)
         if domain is None:
             domain = "frequency" if getattr(self.score_model, "scale_noise", False) else "time"
         if domain not in ("frequency", "time"):
@@ -477,10 +481,7 @@ class DiffusionSampler:
         ``resample`` / ``jump``: as in ``sample_conditional``."""
         if (feature_mean is None) != (feature_std is None):
             raise ValueError("feature_mean and feature_std go together")
-        self._check_resampling(resample, jump)  # (sample_conditional's refusals, before any device work)
-        if self.solver != "euler_maruyama":  # (sample_conditional's refusal, before any device work)
-            raise ValueError("conditional sampling by replacement is defined for the predictor-corrector sampler: "
-                             "it needs solver='euler_maruyama'")
+        self._check_conditional(resample, jump)  # (sample_conditional's refusals, before the transform below)
         L, Cn = self.max_len, self.n_channels
         series, m = _observation_and_mask(series_time, mask, num_samples, L, Cn, "series_time")
         device = self.score_model.device
@@ -550,27 +551,18 @@ class DiffusionSampler:
             raise NotImplementedError("Scheduler not recognized.")
         device = self.score_model.device
         shape = (batch_size, self.max_len, self.n_channels)
-        if self._injected is not None:
-            if device.type != "cuda":
-                raise N.FFDError("sampling needs an MI355X (gfx950) device; there is no CPU fallback")
-            sch = self.noise_scheduler
-            z = self._next_injected(shape, device)
-            X = torch.empty(shape, device=device, dtype=torch.float32)
-            desc = sch._desc()
-            rc = N.lib().ffd_prior(C.byref(desc), X.data_ptr(), z.data_ptr(), sch._G_on(device).data_ptr(), 0, 0,
-                                   batch_size, self.max_len, self.n_channels, N.current_stream_ptr(device))
-            N.check(rc, None, "ffd_prior")
-        elif self.rng == "torch":
+        if self._injected is None and self.rng == "torch":
             X = self.noise_scheduler.prior_sampling(shape, device=device)
-        else:
+        else:  # ffd_prior: from the injected draw, or (philox) drawn in the kernel under (seed, sample offset)
             if device.type != "cuda":
                 raise N.FFDError("sampling needs an MI355X (gfx950) device; there is no CPU fallback")
             sch = self.noise_scheduler
+            z = self._next_injected(shape, device) if self._injected is not None else None
+            z_ptr, seed, offset = (z.data_ptr(), 0, 0) if z is not None else (None, self.seed, _sample_offset)
             X = torch.empty(shape, device=device, dtype=torch.float32)
             desc = sch._desc()
-            rc = N.lib().ffd_prior(C.byref(desc), X.data_ptr(), None, sch._G_on(device).data_ptr(), self.seed,
-                                   _sample_offset, batch_size, self.max_len, self.n_channels,
-                                   N.current_stream_ptr(device))
+            rc = N.lib().ffd_prior(C.byref(desc), X.data_ptr(), z_ptr, sch._G_on(device).data_ptr(), seed, offset,
+                                   batch_size, self.max_len, self.n_channels, N.current_stream_ptr(device))
             N.check(rc, None, "ffd_prior")
         assert isinstance(X, torch.Tensor)
         return X

@@ -672,18 +672,30 @@ int ffd_cache_stats_get(const ffd_ctx* ctx, ffd_cache_stats* out);
  * caller-owned device buffers; stream ordered.  Requires ffd_cache_enable. */
 int ffd_cache_tables_read(ffd_ctx* ctx, float* k_out, float* v_out, void* stream);
 
-/* One batch of DiffusionSampler.sample's inner loop (sampler.py:156-210): runs steps
- * [first_step, first_step + n_run) of an n_steps-step reverse diffusion on x (B,L,C) in
- * place, enqueuing every kernel on `stream` with no host synchronisation (one sync only
- * when the timestep grid differs from the previous call's).
- *   timesteps host array (n_steps) = noise_scheduler.timesteps (sde.py:62-64); the caller
- *             supplies it because torch.linspace's last-ulp rounding depends on the host's
- *             vector width; step_size = timesteps[0]-timesteps[1] in fp32.
- *   z_inject  NULL, or (n_run,B,L,C) injected N(0,1) draws for the steps of this call;
- *             NULL = Philox on device keyed (seed, step index) as in ffd_sde_step.
- *   use_cache 0/1 (requires ffd_cache_enable); `global_step0` is the reference's
- *             global_step (sampler.py:130,210) at `first_step`.
- * x must already hold the prior sample (ffd_prior) or the state after step first_step-1. */
+/* THE RULES EVERY LOOP ENTRY SHARES (ffd_sample_batch and its _ode, _pc, _cond and _resample forms; each entry's own
+ * comment states only what it adds).  An entry runs iterations [first, first + n_run) of its grid -- reverse steps,
+ * the ODE's intervals, or resampling's visits -- on x (B,L,C) in place, enqueuing every kernel on `stream` with no host
+ * synchronisation (one sync only when the timestep grid differs from the previous call's).  A run split into calls at
+ * any iteration boundary gives the bits of one call.
+ *   Arguments.  timesteps: host array (n_steps) = noise_scheduler.timesteps (sde.py:62-64); the caller supplies it
+ *     because torch.linspace's last-ulp rounding depends on the host's vector width; step_size = timesteps[0] -
+ *     timesteps[1] in fp32.  x must already hold the prior sample (ffd_prior) or the state after iteration first - 1.
+ *   Draws.  z_inject == NULL: Philox on the device, keyed (seed, stream tag, global element index) as in ffd_sde_step;
+ *     the predictor's tag is the iteration's index, the other updates' tags are their entries'.  Otherwise z_inject holds
+ *     one (B,L,C) slab of N(0,1) draws per update, flat, in the order the call consumes them, starting at `first`.
+ *   Cache gate.  use_cache 0/1 (requires ffd_cache_enable; the transformer only); global_step0 is the reference's
+ *     global_step (sampler.py:130,210) at `first`.  An iteration's FIRST score evaluation follows
+ *     ffd_host_gate at global step global_step0 + (iteration - first); every later evaluation of the iteration (Heun's
+ *     second, the correctors' behind the first, the predictor's behind them) is a pure cache hit (n_recompute = 0).
+ *     Tables and counters are those of ffd_score_forward_cached calls of these sizes in this order.
+ *   CRF capture (ffd_cache_crf_capture).  Taken from the gated evaluation only, at its global step.
+ *   FreSca (ffd_fresca_enable).  Applied to every evaluated score with h(t) of that evaluation's time.
+ *   Errors.  FFD_ERR_INVALID -- null pointers, B < 1, a range outside the grid, step_size <= 0, what the entry adds --
+ *     FFD_ERR_UNSUPPORTED (use_cache on another backbone) and FFD_ERR_STATE (use_cache without ffd_cache_enable) come
+ *     back before any device work: nothing is launched and x stays as it is.
+ *
+ * ffd_sample_batch: one batch of DiffusionSampler.sample's inner loop (sampler.py:156-210), Euler-Maruyama steps
+ * [first_step, first_step + n_run) of an n_steps-step reverse diffusion; one draw per step, z_inject (n_run,B,L,C). */
 int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
                      int first_step, int n_run, uint64_t seed, uint64_t sample_offset, const float* z_inject,
                      int use_cache, int global_step0, void* stream);
@@ -703,15 +715,10 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
  *                         and ended at interval first_step.  Every other loop entry (ffd_sample_batch, _pc, _cond, the
  *                         Euler / Heun solvers) drops the history.  A trajectory split into calls gives the bits of
  *                         one call.
- * Same time-embedding table, stream ordering and host synchronisation as ffd_sample_batch (none but for a new grid);
- * with the unembedding fused into the tail (see "fuse_tail") no score reaches HBM.
- *   use_cache  the predictor evaluation of interval i follows ffd_host_gate at global step global_step0 + (i -
- *              first_step); Heun's corrector evaluation is a pure cache hit (n_recompute = 0).  Tables, counters and
- *              the CRF capture (taken from the predictor evaluation) are those of ffd_score_forward_cached calls of
- *              these sizes in this order.
- *   FreSca     applied to every evaluated score with h(t) of that evaluation's time.
- * FFD_ERR_INVALID before any device work: null pointers, B < 1, step_size <= 0, an unknown solver, an interval range
- * outside the grid. */
+ * Time-embedding table, stream ordering, cache gate, CRF capture and FreSca: the shared rules above (the global step
+ * counts intervals; Heun's corrector evaluation is the pure hit).  With the unembedding fused into the tail (see
+ * "fuse_tail") no score reaches HBM.
+ * FFD_ERR_INVALID before any device work: the shared cases, and an unknown solver. */
 enum { FFD_SOLVER_EULER_MARUYAMA = 0, FFD_SOLVER_ODE_EULER = 1, FFD_SOLVER_ODE_HEUN = 2 };
 enum { FFD_SOLVER_ODE_AB2 = 4, FFD_SOLVER_DPMPP_2M = 5 }; /* (3 is FFD_SOLVER_PC) */
 int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
@@ -725,12 +732,8 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
  *      the noise of ffd_sample_batch).
  * n_corrector == 0 IS ffd_sample_batch (the call is forwarded).  Arguments as there, and
  *   snr, norm  the corrector's signal-to-noise ratio (> 0) and FFD_LANGEVIN_NORM_*;
- *   z_inject   NULL or (n_run, n_corrector + 1, B, L, C): per step the correctors' draws in order, then the predictor's;
- *   use_cache  the FIRST evaluation of step i follows ffd_host_gate at global step global_step0 + (i - first_step) and
- *              feeds the CRF capture; every later evaluation of the step, the predictor's included, is a pure cache
- *              hit (n_recompute = 0): Heun's rule of ffd_sample_batch_ode generalised.  Tables and counters are
- *              those of ffd_score_forward_cached calls of these sizes in this order.
- *   FreSca     applied to every evaluated score with h(timesteps[i]).
+ *   z_inject   NULL or (n_run, n_corrector + 1, B, L, C): per step the correctors' draws in order, then the predictor's.
+ * Cache gate, CRF capture and FreSca: the shared rules above (the first corrector's evaluation is the gated one).
  * The corrector reads its score from HBM (three small launches behind the unembedding); the predictor keeps the fused
  * tail ("fuse_tail").
  * FFD_ERR_INVALID before any device work: as ffd_sample_batch, and n_corrector < 0, snr <= 0, an unknown norm,

@@ -497,6 +497,83 @@ def test_no_corrector_is_the_existing_loop(ffd, name):
         assert torch.equal(a, b) and not torch.equal(a, x0)
 
 
+def test_plain_entry_is_the_shared_loop_under_every_option(ffd):
+    """ffd_sample_batch, ffd_sample_batch_pc(n_corrector = 0) and ffd_sample_batch_cond(cond = NULL) with the cache
+    (K = 5, R = 2), the CRF capture (``last`` every 2nd step, a 2-slot ring every step: step 4 goes to both) and FreSca all
+    on: the state, both capture buffers and the cache statistics agree bit for bit, with device and with injected draws,
+    under fuse_tail 1 and 0; steps [0, 2) + [2, 3) + [3, 6) equal one call of 6; FFD_K_SDE counts one launch per step."""
+    from fastfourierdiffusion_amd import _native as N
+
+    c = dict(_TF24, L=21, C=3, B=3)
+    m, sch, sd = build(c, "vp")
+    m.enable_caching(K=5, R=2)
+    B, L, Cn, n = c["B"], c["L"], c["C"], TRAJ_N
+    sch.set_timesteps(n)
+    ctx = m._ctx()
+    lib, hdl, stream = ctx.lib, ctx.handle, N.current_stream_ptr(m.device)
+    ts_c = (C_.c_float * n)(*sch.timesteps.tolist())
+    h = float(sch.step_size)
+    fresca = N.FrescaCfg(0.9, 1.2, 0.4, 0, n)
+    assert lib.ffd_fresca_enable(hdl, C_.byref(fresca)) == 0
+    crf_shape = (c["NL"], L, c["d"])
+    last = torch.empty(crf_shape, device="cuda")
+    ring = torch.empty((2,) + crf_shape, device="cuda")
+    cap = N.CrfCaptureCfg(ring.data_ptr(), 2, 1, last.data_ptr(), 2, 0)
+    assert lib.ffd_cache_crf_capture(hdl, C_.byref(cap)) == 0
+    x0 = torch.from_numpy(next(synthetic.noise_stream((B, L, Cn), 1, 77))).cuda()
+    zs = torch.from_numpy(np.stack(list(synthetic.noise_stream((B, L, Cn), n, 78)))).cuda()
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+
+    entries = {
+        "plain": lambda x, first, count, z: lib.ffd_sample_batch(hdl, x.data_ptr(), B, ts_c, n, h, first, count, 9, 5, ptr(z),
+                                                                 1, first, stream),
+        "pc": lambda x, first, count, z: lib.ffd_sample_batch_pc(hdl, x.data_ptr(), B, ts_c, n, h, first, count, 0, SNR, 0, 9,
+                                                                 5, ptr(z), 1, first, stream),
+        "cond": lambda x, first, count, z: lib.ffd_sample_batch_cond(hdl, x.data_ptr(), B, ts_c, n, h, first, count, 0, SNR,
+                                                                     0, 9, 5, ptr(z), 1, first, None, stream),
+    }
+
+    def run(entry, z, cuts, count_launches=False):
+        """(state, last, ring, statistics) after the calls [cuts[k], cuts[k + 1]) from a reset cache"""
+        assert lib.ffd_cache_reset(hdl) == 0
+        last.fill_(float("nan"))
+        ring.fill_(float("nan"))
+        x = x0.clone()
+        if count_launches:
+            assert lib.ffd_kernel_timing_begin(hdl, 1 << N.K_SDE, 64) == 0
+        for first, end in zip(cuts[:-1], cuts[1:]):
+            assert entries[entry](x, first, end - first, None if z is None else z[first:]) == 0
+        if count_launches:
+            assert lib.ffd_kernel_timing_end(hdl) == 0
+            ms, launches = C_.c_float(), C_.c_int()
+            assert lib.ffd_kernel_timing_get(hdl, N.K_SDE, C_.byref(ms), C_.byref(launches)) == 0
+            assert launches.value == n
+        st = N.CacheStats()
+        assert lib.ffd_cache_stats_get(hdl, C_.byref(st)) == 0
+        return x, last.clone(), ring.clone(), (st.recompute_count, st.cache_hit_count, st.current_step, st.table_allocated)
+
+    def same(a, b):
+        return all(torch.equal(p, q) for p, q in zip(a[:3], b[:3])) and a[3] == b[3]
+
+    res = {}
+    for fuse in (1, 0):
+        assert lib.ffd_tune(b"fuse_tail", fuse) == 0
+        for how, z in (("philox", None), ("inject", zs)):
+            one = run("plain", z, (0, n), count_launches=True)
+            assert all(bool(torch.isfinite(t).all()) for t in one[:3]) and not torch.equal(one[0], x0)
+            # the gate recomputes every token at global step 0 and none at steps 1..5 (the periodic refresh is 500 apart)
+            assert one[3] == (L * c["NL"], (n - 1) * L * c["NL"], n - 1, 1), one[3]
+            for entry in entries:
+                assert same(one, run(entry, z, (0, n))), (fuse, how, entry)
+                assert same(one, run(entry, z, (0, 2, 3, n))), (fuse, how, entry, "split")
+            res[(fuse, how)] = one
+    for how in ("philox", "inject"):  # (FreSca reads the whole score: both settings take the stand-alone tail)
+        assert same(res[(1, how)], res[(0, how)]), how
+    assert not torch.equal(res[(1, "philox")][0], res[(1, "inject")][0])
+
+
 # ------------------------------------------------------------------ 7. stationarity ----
 # tests/test_pc_host.py RECORDED_BAND (the restatement's 8-seed min / max), widened on each side by its own width: a
 # wrong factor 2 (0.52 / 2.02 VE, 0.58 / 1.62 VP) or a wrong power of G (0.75 / 0.82) stays outside, another RNG inside
