@@ -11,7 +11,7 @@
 
 #include <algorithm>
 
-#include "ffd_internal.h"
+#include "ffd_step.h"
 
 namespace ffd {
 
@@ -398,66 +398,36 @@ __device__ __forceinline__ float sde_update(float xi, float sc, float Gl, float 
   return __fadd_rn(t1, __fmul_rn(p.sqdt, __fmul_rn(g, zz)));
 }
 
-// C % 4 == 0, 16-byte aligned buffers: one float4 of x / score (/ z) per thread and iteration; the four elements
-// share their row, so G[l] is one load; the draws of an aligned quad are one Philox block.  12 B per element.
-__global__ __launch_bounds__(256) void k_sde_step_v4(float* __restrict__ x, const float* __restrict__ score,
-                                                     const float* __restrict__ z, const float* __restrict__ G,
-                                                     SdeParams p, uint64_t seed, uint64_t elem_offset, uint32_t step,
-                                                     size_t nvec, int L, unsigned C4) {
-  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
-    const float4 xi = reinterpret_cast<const float4*>(x)[v];
-    const float4 sc = reinterpret_cast<const float4*>(score)[v];
-    float zz[4];
-    if (z) {
-      const float4 zv = reinterpret_cast<const float4*>(z)[v];
-      zz[0] = zv.x, zz[1] = zv.y, zz[2] = zv.z, zz[3] = zv.w;
-    } else {
-      normal4((elem_offset >> 2) + v, seed, step, zz);  // elem_offset is a multiple of C
-    }
-    const float Gl = G[(v / C4) % (size_t)L];
-    reinterpret_cast<float4*>(x)[v] = float4{sde_update(xi.x, sc.x, Gl, zz[0], p), sde_update(xi.y, sc.y, Gl, zz[1], p),
-                                             sde_update(xi.z, sc.z, Gl, zz[2], p), sde_update(xi.w, sc.w, Gl, zz[3], p)};
+// The stand-alone step kernels are k_step_v4<Op> / k_step<Op> (ffd_step.h) on the ops below.  12 B per element.
+struct OpSde {
+  static constexpr bool DRAWS = true, SAMPLE = false;
+  float* x;
+  const float* score;
+  SdeParams p;
+  Draws d;
+  static constexpr int NIN = 2;  // x, score
+  bool aligned() const { return ptr16(x) && ptr16(score); }
+  template <int W>
+  __device__ void load(size_t i, float (&in)[NIN][W]) const {
+    ld<W>(x, i, in[0]), ld<W>(score, i, in[1]);
   }
-}
-
-__global__ void k_sde_step(float* __restrict__ x, const float* __restrict__ score, const float* __restrict__ z,
-                           const float* __restrict__ G, SdeParams p, uint64_t seed, uint64_t elem_offset,
-                           uint32_t step, size_t total, int L, int C) {
-  size_t nvec = (total + 3) / 4;
-  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
-    size_t i0 = v * 4;
-    int n = (int)((total - i0) < 4 ? (total - i0) : 4);
-    float zz[4];
-    load_normals(z, i0, n, seed, elem_offset, step, zz);
-    for (int j = 0; j < n; ++j) {
-      size_t i = i0 + j;
-      const int l = (int)((i / (size_t)C) % (size_t)L);
-      x[i] = sde_update(x[i], score[i], G[l], zz[j], p);
-    }
+  template <int W>
+  __device__ void update(size_t i, float (&in)[NIN][W], float Gl, const float (&zz)[W], size_t) const {
+#pragma unroll
+    for (int j = 0; j < W; ++j) in[0][j] = sde_update(in[0][j], in[1][j], Gl, zz[j], p);
+    st<W>(x, i, in[0]);
   }
-}
-
-static bool ptr16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+};
 
 hipError_t launch_sde_step(float* x, const float* score, const float* z, const float* G, SdeParams p, uint64_t seed,
                            uint64_t elem_offset, uint32_t step, int B, int L, int C, hipStream_t s) {
-  size_t total = (size_t)B * L * C;
-  size_t blocks = ((total + 3) / 4 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  if (C % 4 == 0 && ptr16(x) && ptr16(score) && ptr16(z) && elem_offset % 4 == 0)
-    hipLaunchKernelGGL(k_sde_step_v4, dim3((unsigned)blocks), dim3(256), 0, s, x, score, z, G, p, seed, elem_offset, step,
-                       total / 4, L, (unsigned)C / 4);
-  else
-    hipLaunchKernelGGL(k_sde_step, dim3((unsigned)blocks), dim3(256), 0, s, x, score, z, G, p, seed, elem_offset, step,
-                       total, L, C);
-  return hipGetLastError();
+  return launch_step(OpSde{x, score, p, Draws{z, seed, elem_offset, step}}, G, B, L, C, s);
 }
 
 // ---------------------------------------------------------------------------
 // Conditional sampling by replacement, time-domain models (include/ffd.h ffd_cond_project, FFD_COND_TIME): pointwise
 //   y = (mc obs) + ((sigma G_l) z)   (noiseless: y = obs);   x <- x + mask (y - x)
-// every product / sum its own fp32 rounding; the draws are counted like k_sde_step's.
+// every product / sum its own fp32 rounding; the draws are counted like the SDE step's (OpSde).
 // ---------------------------------------------------------------------------
 __global__ void k_cond_time(float* __restrict__ x, const float* __restrict__ obs, const float* __restrict__ mask,
                             const float* __restrict__ z, const float* __restrict__ G, float mc, float sigma, int noiseless,
@@ -497,69 +467,41 @@ hipError_t launch_cond_time(float* x, const float* obs, const float* mask, const
 // ---------------------------------------------------------------------------
 // Forward transition of the SDE from time s to t >= s (include/ffd.h ffd_forward_transition; the re-noising of resampled
 // conditional sampling):  x' = (a x) + ((sg G_l) z), every product / sum its own fp32 rounding; the draws are counted
-// like k_sde_step's.  noisy == 0 (sg == 0): x' = a x and no draw is read or generated.  8 B per element with device
-// draws, 12 B with injected ones: HBM bound, grid-stride over float4s like k_sde_step_v4.
+// like the SDE step's.  noisy == 0 (sg == 0): x' = a x and no draw is read or generated.  8 B per element with device
+// draws, 12 B with injected ones.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float transition_update(float xi, float Gl, float zz, float a, float sg, int noisy) {
   const float ax = __fmul_rn(a, xi);
   return noisy ? __fadd_rn(ax, __fmul_rn(__fmul_rn(sg, Gl), zz)) : ax;
 }
 
-__global__ __launch_bounds__(256) void k_forward_transition_v4(float* __restrict__ x, const float* __restrict__ z,
-                                                               const float* __restrict__ G, float a, float sg, int noisy,
-                                                               uint64_t seed, uint64_t elem_offset, uint32_t tag,
-                                                               size_t nvec, int L, unsigned C4) {
-  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
-    const float4 xi = reinterpret_cast<const float4*>(x)[v];
-    float zz[4] = {0.f, 0.f, 0.f, 0.f};
-    if (noisy) {
-      if (z) {
-        const float4 zv = reinterpret_cast<const float4*>(z)[v];
-        zz[0] = zv.x, zz[1] = zv.y, zz[2] = zv.z, zz[3] = zv.w;
-      } else {
-        normal4((elem_offset >> 2) + v, seed, tag, zz);  // elem_offset is a multiple of 4
-      }
-    }
-    const float Gl = G[(v / C4) % (size_t)L];
-    reinterpret_cast<float4*>(x)[v] =
-        float4{transition_update(xi.x, Gl, zz[0], a, sg, noisy), transition_update(xi.y, Gl, zz[1], a, sg, noisy),
-               transition_update(xi.z, Gl, zz[2], a, sg, noisy), transition_update(xi.w, Gl, zz[3], a, sg, noisy)};
+// NOISY = false is there for callers of launch_forward_transition alone: transition_coef never gives an fp32 sg == 0
+// with a != 1, so neither ffd_forward_transition nor the loop reaches it.
+template <bool NOISY>
+struct OpTransition {
+  static constexpr bool DRAWS = NOISY, SAMPLE = false;
+  float* x;
+  float a, sg;
+  Draws d;  // (NOISY)
+  static constexpr int NIN = 1;  // x
+  bool aligned() const { return ptr16(x); }
+  template <int W>
+  __device__ void load(size_t i, float (&in)[NIN][W]) const {
+    ld<W>(x, i, in[0]);
   }
-}
-
-__global__ __launch_bounds__(256) void k_forward_transition(float* __restrict__ x, const float* __restrict__ z,
-                                                            const float* __restrict__ G, float a, float sg, int noisy,
-                                                            uint64_t seed, uint64_t elem_offset, uint32_t tag, size_t total,
-                                                            int L, int C) {
-  const size_t nvec = (total + 3) / 4;
-  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
-    const size_t i0 = v * 4;
-    const int n = (int)((total - i0) < 4 ? (total - i0) : 4);
-    float zz[4] = {0.f, 0.f, 0.f, 0.f};
-    if (noisy) load_normals(z, i0, n, seed, elem_offset, tag, zz);
-    for (int j = 0; j < n; ++j) {
-      const size_t i = i0 + j;
-      x[i] = transition_update(x[i], G[(i / (size_t)C) % (size_t)L], zz[j], a, sg, noisy);
-    }
+  template <int W>
+  __device__ void update(size_t i, float (&in)[NIN][W], float Gl, const float (&zz)[W], size_t) const {
+#pragma unroll
+    for (int j = 0; j < W; ++j) in[0][j] = transition_update(in[0][j], Gl, zz[j], a, sg, NOISY);
+    st<W>(x, i, in[0]);
   }
-}
+};
 
 hipError_t launch_forward_transition(float* x, const float* G, float a, float sg, const float* z, uint64_t seed,
                                      uint64_t elem_offset, uint32_t tag, int B, int L, int C, hipStream_t s) {
-  const int noisy = sg != 0.f;
-  if (!noisy && a == 1.f) return hipSuccess;  // s == t: x is untouched bit for bit (a x + 0 would turn -0 into +0)
-  if (!noisy) z = nullptr;
-  const size_t total = (size_t)B * L * C;
-  size_t blocks = ((total + 3) / 4 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  if (C % 4 == 0 && ptr16(x) && ptr16(z) && elem_offset % 4 == 0)
-    hipLaunchKernelGGL(k_forward_transition_v4, dim3((unsigned)blocks), dim3(256), 0, s, x, z, G, a, sg, noisy, seed,
-                       elem_offset, tag, total / 4, L, (unsigned)C / 4);
-  else
-    hipLaunchKernelGGL(k_forward_transition, dim3((unsigned)blocks), dim3(256), 0, s, x, z, G, a, sg, noisy, seed,
-                       elem_offset, tag, total, L, C);
-  return hipGetLastError();
+  if (sg != 0.f) return launch_step(OpTransition<true>{x, a, sg, Draws{z, seed, elem_offset, tag}}, G, B, L, C, s);
+  if (a == 1.f) return hipSuccess;  // s == t: x is untouched bit for bit (a x + 0 would turn -0 into +0)
+  return launch_step(OpTransition<false>{x, a, sg, Draws{}}, G, B, L, C, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -590,80 +532,42 @@ __device__ __forceinline__ float ode_update(float xi, float sc, float Gl, float 
   return __fsub_rn(xi, __fmul_rn(d, p.dt));
 }
 
-// The stand-alone tails (score from HBM): the twins of k_sde_step_v4 / k_sde_step.  Buffers by tail:
+// Buffers by tail:
 //   EULER    x in / out
 //   PREDICT  x in, xp out, d1 out
 //   CORRECT  xp in (score = the score at xp), x in / out, d1 in
 template <int TAIL>
-__global__ __launch_bounds__(256) void k_ode_step_v4(float* __restrict__ x, const float* __restrict__ score,
-                                                     float* __restrict__ xp, float* __restrict__ d1,
-                                                     const float* __restrict__ G, SdeParams p, size_t nvec, int L,
-                                                     unsigned C4) {
-  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
-    const float4 sc = reinterpret_cast<const float4*>(score)[v];
-    const float Gl = G[(v / C4) % (size_t)L];
-    if (TAIL == ODE_CORRECT) {
-      const float4 xi = reinterpret_cast<const float4*>(xp)[v];
-      const float4 x0 = reinterpret_cast<const float4*>(x)[v];
-      float4 dv = reinterpret_cast<const float4*>(d1)[v];
-      reinterpret_cast<float4*>(x)[v] =
-          float4{ode_update<TAIL>(xi.x, sc.x, Gl, x0.x, dv.x, p), ode_update<TAIL>(xi.y, sc.y, Gl, x0.y, dv.y, p),
-                 ode_update<TAIL>(xi.z, sc.z, Gl, x0.z, dv.z, p), ode_update<TAIL>(xi.w, sc.w, Gl, x0.w, dv.w, p)};
-    } else {
-      const float4 xi = reinterpret_cast<const float4*>(x)[v];
-      float4 dv{};
-      const float4 xn = float4{ode_update<TAIL>(xi.x, sc.x, Gl, 0.f, dv.x, p), ode_update<TAIL>(xi.y, sc.y, Gl, 0.f, dv.y, p),
-                               ode_update<TAIL>(xi.z, sc.z, Gl, 0.f, dv.z, p), ode_update<TAIL>(xi.w, sc.w, Gl, 0.f, dv.w, p)};
-      if (TAIL == ODE_PREDICT) {
-        reinterpret_cast<float4*>(xp)[v] = xn;
-        reinterpret_cast<float4*>(d1)[v] = dv;
-      } else {
-        reinterpret_cast<float4*>(x)[v] = xn;
-      }
+struct OpOde {
+  static constexpr bool DRAWS = false, SAMPLE = false;
+  float* x;
+  const float* score;
+  float *xp, *d1;
+  SdeParams p;
+  static constexpr int NIN = 4;  // what ode_update starts from (x; CORRECT: xp), score, CORRECT's x and d1
+  bool aligned() const { return ptr16(x) && ptr16(score) && ptr16(xp) && ptr16(d1); }
+  template <int W>
+  __device__ void load(size_t i, float (&in)[NIN][W]) const {
+    ld<W>(TAIL == ODE_CORRECT ? xp : x, i, in[0]), ld<W>(score, i, in[1]);
+    if (TAIL == ODE_CORRECT) ld<W>(x, i, in[2]), ld<W>(d1, i, in[3]);
+  }
+  template <int W>
+  __device__ void update(size_t i, float (&in)[NIN][W], float Gl, const float (&)[W], size_t) const {
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      if (TAIL != ODE_CORRECT) in[2][j] = in[3][j] = 0.f;
+      in[0][j] = ode_update<TAIL>(in[0][j], in[1][j], Gl, in[2][j], in[3][j], p);
     }
+    st<W>(TAIL == ODE_PREDICT ? xp : x, i, in[0]);
+    if (TAIL == ODE_PREDICT) st<W>(d1, i, in[3]);
   }
-}
-
-template <int TAIL>
-__global__ void k_ode_step(float* __restrict__ x, const float* __restrict__ score, float* __restrict__ xp,
-                           float* __restrict__ d1, const float* __restrict__ G, SdeParams p, size_t total, int L, int C) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const float Gl = G[(i / (size_t)C) % (size_t)L];
-    if (TAIL == ODE_CORRECT) {
-      float dv = d1[i];
-      x[i] = ode_update<TAIL>(xp[i], score[i], Gl, x[i], dv, p);
-    } else {
-      float dv = 0.f;
-      const float xn = ode_update<TAIL>(x[i], score[i], Gl, 0.f, dv, p);
-      if (TAIL == ODE_PREDICT) xp[i] = xn, d1[i] = dv;
-      else x[i] = xn;
-    }
-  }
-}
-
-template <int TAIL>
-static hipError_t launch_ode_tail(float* x, const float* score, float* xp, float* d1, const float* G, SdeParams p, int B,
-                                  int L, int C, hipStream_t s) {
-  const size_t total = (size_t)B * L * C;
-  if (C % 4 == 0 && ptr16(x) && ptr16(score) && ptr16(xp) && ptr16(d1)) {
-    size_t blocks = (total / 4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((k_ode_step_v4<TAIL>), dim3((unsigned)blocks), dim3(256), 0, s, x, score, xp, d1, G, p, total / 4, L,
-                       (unsigned)C / 4);
-  } else {
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((k_ode_step<TAIL>), dim3((unsigned)blocks), dim3(256), 0, s, x, score, xp, d1, G, p, total, L, C);
-  }
-  return hipGetLastError();
-}
+};
 
 hipError_t launch_ode_step(int tail, float* x, const float* score, float* xp, float* d1, const float* G, SdeParams p,
                            int B, int L, int C, hipStream_t s) {
   switch (tail) {
-    case ODE_EULER: return launch_ode_tail<ODE_EULER>(x, score, nullptr, nullptr, G, p, B, L, C, s);
-    case ODE_PREDICT: return launch_ode_tail<ODE_PREDICT>(x, score, xp, d1, G, p, B, L, C, s);
-    case ODE_CORRECT: return launch_ode_tail<ODE_CORRECT>(x, score, xp, d1, G, p, B, L, C, s);
+    case ODE_EULER: return launch_step(OpOde<ODE_EULER>{x, score, nullptr, nullptr, p}, G, B, L, C, s);
+    case ODE_PREDICT: return launch_step(OpOde<ODE_PREDICT>{x, score, xp, d1, p}, G, B, L, C, s);
+    case ODE_CORRECT: return launch_step(OpOde<ODE_CORRECT>{x, score, xp, d1, p}, G, B, L, C, s);
     default: return hipErrorInvalidValue;
   }
 }
@@ -687,57 +591,36 @@ __device__ __forceinline__ float multistep_update(float xi, float sc, float Gl, 
   return __fadd_rn(xi, inc);
 }
 
-// The stand-alone tails (score from HBM): the twins of k_ode_step_v4 / k_ode_step.  x and hist in / out (PREV = false:
-// hist out only).
+// x and hist in / out (PREV = false: hist out only)
 template <bool PREV>
-__global__ __launch_bounds__(256) void k_multistep_step_v4(float* __restrict__ x, const float* __restrict__ score,
-                                                           float* __restrict__ hist, const float* __restrict__ G,
-                                                           MultistepParams p, size_t nvec, int L, unsigned C4) {
-  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
-    const float4 sc = reinterpret_cast<const float4*>(score)[v];
-    const float4 xi = reinterpret_cast<const float4*>(x)[v];
-    float4 hv{};
-    if (PREV) hv = reinterpret_cast<const float4*>(hist)[v];
-    const float Gl = G[(v / C4) % (size_t)L];
-    reinterpret_cast<float4*>(x)[v] =
-        float4{multistep_update<PREV>(xi.x, sc.x, Gl, hv.x, p), multistep_update<PREV>(xi.y, sc.y, Gl, hv.y, p),
-               multistep_update<PREV>(xi.z, sc.z, Gl, hv.z, p), multistep_update<PREV>(xi.w, sc.w, Gl, hv.w, p)};
-    reinterpret_cast<float4*>(hist)[v] = hv;
+struct OpMultistep {
+  static constexpr bool DRAWS = false, SAMPLE = false;
+  float* x;
+  const float* score;
+  float* hist;
+  MultistepParams p;
+  static constexpr int NIN = 3;  // x, score, hist
+  bool aligned() const { return ptr16(x) && ptr16(score) && ptr16(hist); }
+  template <int W>
+  __device__ void load(size_t i, float (&in)[NIN][W]) const {
+    ld<W>(x, i, in[0]), ld<W>(score, i, in[1]);
+    if (PREV) ld<W>(hist, i, in[2]);
   }
-}
-
-template <bool PREV>
-__global__ void k_multistep_step(float* __restrict__ x, const float* __restrict__ score, float* __restrict__ hist,
-                                 const float* __restrict__ G, MultistepParams p, size_t total, int L, int C) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const float Gl = G[(i / (size_t)C) % (size_t)L];
-    float hq = PREV ? hist[i] : 0.f;
-    x[i] = multistep_update<PREV>(x[i], score[i], Gl, hq, p);
-    hist[i] = hq;
+  template <int W>
+  __device__ void update(size_t i, float (&in)[NIN][W], float Gl, const float (&)[W], size_t) const {
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      if (!PREV) in[2][j] = 0.f;
+      in[0][j] = multistep_update<PREV>(in[0][j], in[1][j], Gl, in[2][j], p);
+    }
+    st<W>(x, i, in[0]), st<W>(hist, i, in[2]);
   }
-}
-
-template <bool PREV>
-static hipError_t launch_multistep_tail(float* x, const float* score, float* hist, const float* G, MultistepParams p, int B,
-                                        int L, int C, hipStream_t s) {
-  const size_t total = (size_t)B * L * C;
-  if (C % 4 == 0 && ptr16(x) && ptr16(score) && ptr16(hist)) {
-    size_t blocks = (total / 4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((k_multistep_step_v4<PREV>), dim3((unsigned)blocks), dim3(256), 0, s, x, score, hist, G, p, total / 4,
-                       L, (unsigned)C / 4);
-  } else {
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((k_multistep_step<PREV>), dim3((unsigned)blocks), dim3(256), 0, s, x, score, hist, G, p, total, L, C);
-  }
-  return hipGetLastError();
-}
+};
 
 hipError_t launch_multistep_step(float* x, const float* score, float* hist, const float* G, MultistepParams p,
                                  int have_prev, int B, int L, int C, hipStream_t s) {
-  if (have_prev) return launch_multistep_tail<true>(x, score, hist, G, p, B, L, C, s);
-  return launch_multistep_tail<false>(x, score, hist, G, p, B, L, C, s);
+  if (have_prev) return launch_step(OpMultistep<true>{x, score, hist, p}, G, B, L, C, s);
+  return launch_step(OpMultistep<false>{x, score, hist, p}, G, B, L, C, s);
 }
 
 // prior: x = G (.) z  (VE: * sigma_max), sde.py:79-87,125-127
@@ -746,71 +629,145 @@ __device__ __forceinline__ float prior_value(float Gl, float zz, float scale) {
   return (scale == 1.0f) ? v0 : __fmul_rn(scale, v0);
 }
 
-__global__ __launch_bounds__(256) void k_prior_v4(float* __restrict__ x, const float* __restrict__ z,
-                                                  const float* __restrict__ G, float scale, uint64_t seed,
-                                                  uint64_t elem_offset, size_t nvec, int L, unsigned C4) {
-  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
-    float zz[4];
-    if (z) {
-      const float4 zv = reinterpret_cast<const float4*>(z)[v];
-      zz[0] = zv.x, zz[1] = zv.y, zz[2] = zv.z, zz[3] = zv.w;
-    } else {
-      normal4((elem_offset >> 2) + v, seed, 0xFFFFFFFFu, zz);
-    }
-    const float Gl = G[(v / C4) % (size_t)L];
-    reinterpret_cast<float4*>(x)[v] = float4{prior_value(Gl, zz[0], scale), prior_value(Gl, zz[1], scale),
-                                             prior_value(Gl, zz[2], scale), prior_value(Gl, zz[3], scale)};
+struct OpPrior {
+  static constexpr bool DRAWS = true, SAMPLE = false;
+  float* x;
+  float scale;
+  Draws d;
+  static constexpr int NIN = 1;  // (nothing is read)
+  bool aligned() const { return ptr16(x); }
+  template <int W>
+  __device__ void load(size_t, float (&)[NIN][W]) const {}
+  template <int W>
+  __device__ void update(size_t i, float (&in)[NIN][W], float Gl, const float (&zz)[W], size_t) const {
+#pragma unroll
+    for (int j = 0; j < W; ++j) in[0][j] = prior_value(Gl, zz[j], scale);
+    st<W>(x, i, in[0]);
   }
-}
-
-__global__ void k_prior(float* __restrict__ x, const float* __restrict__ z, const float* __restrict__ G, float scale,
-                        uint64_t seed, uint64_t elem_offset, size_t total, int L, int C) {
-  size_t nvec = (total + 3) / 4;
-  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
-    size_t i0 = v * 4;
-    int n = (int)((total - i0) < 4 ? (total - i0) : 4);
-    float zz[4];
-    load_normals(z, i0, n, seed, elem_offset, 0xFFFFFFFFu, zz);
-    for (int j = 0; j < n; ++j) {
-      size_t i = i0 + j;
-      const int l = (int)((i / (size_t)C) % (size_t)L);
-      x[i] = prior_value(G[l], zz[j], scale);
-    }
-  }
-}
+};
 
 static hipError_t launch_prior(float* x, const float* z, const float* G, float scale, uint64_t seed, uint64_t elem_offset,
                                int B, int L, int C, hipStream_t s) {
-  size_t total = (size_t)B * L * C;
-  size_t blocks = ((total + 3) / 4 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  if (C % 4 == 0 && ptr16(x) && ptr16(z) && elem_offset % 4 == 0)
-    hipLaunchKernelGGL(k_prior_v4, dim3((unsigned)blocks), dim3(256), 0, s, x, z, G, scale, seed, elem_offset, total / 4, L,
-                       (unsigned)C / 4);
-  else
-    hipLaunchKernelGGL(k_prior, dim3((unsigned)blocks), dim3(256), 0, s, x, z, G, scale, seed, elem_offset, total, L, C);
-  return hipGetLastError();
+  return launch_step(OpPrior{x, scale, Draws{z, seed, elem_offset, 0xFFFFFFFFu}}, G, B, L, C, s);
 }
 
 // ---------------------------------------------------------------------------
 // unembed: score[row][c] = bu[c] + h[row][:] . Wu[c][:]     (score_models.py:113)
-// and, fused, the reverse SDE step on that score (the score never reaches HBM).
+// and, fused, a sampler's update of x on that score (the score never reaches HBM).
 // ---------------------------------------------------------------------------
 // HBM-bound on the read of h (4 D bytes per row against 4 C written).  One wave owns 16 rows per iteration and forms
 // score^T (C x 16) on the exact-fp32 matrix core: A = the unembedder weight (channel on the row index, rows >= C
 // zero), B = the h rows, each lane loading FOUR consecutive k of its row as one float4 per 16-wide k chunk (the
 // MFMA's k index is then a permutation of the chunk's 16 k values, the same for A and B; the qkv kernel's trick).
 // The accumulator leaves lane l with channels 4 (l >> 4) .. +3 of row (l & 15): exactly one float4 of score / x
-// when C % 4 == 0.  SDE = true continues with the Euler-Maruyama update of x in those registers (same sde_update,
-// same Philox indexing as k_sde_step); SDE = false stores the score.  The next tile's h is prefetched under the
-// current tile's MFMAs and epilogue.
-template <int D, bool SDE>
+// when C % 4 == 0.  The next tile's h is prefetched under the current tile's MFMAs and epilogue.
+//
+// What happens to the score quad is the Tail's, a struct passed by value with its arrays and parameters:
+//   Regs                      the operand quads it wants fetched together with a tile's h rows (may be empty)
+//   NEEDS_G                   whether it reads G[row % L]
+//   load(i0, regs)            fetch them for the quad at element i0 (C % 4 == 0 only)
+//   quad(i0, acc, Gl, regs)   C % 4 == 0: the update of the float4 at i0
+//   ragged(i0, n, acc, Gl)    otherwise: the update of elements i0 .. i0 + n - 1, operands from HBM
+// The tails use the update functions and the Philox indexing of the stand-alone ops above, so fused and unfused steps
+// agree bit for bit.
+struct TailStore {  // score <- unembed(h)
+  struct Regs {};
+  static constexpr bool NEEDS_G = false;
+  float* score;
+  __device__ void load(size_t, Regs&) const {}
+  __device__ void quad(size_t i0, f32x4 acc, float, const Regs&) const {
+    *reinterpret_cast<float4*>(score + i0) = float4{acc[0], acc[1], acc[2], acc[3]};
+  }
+  __device__ void ragged(size_t i0, int n, f32x4 acc, float) const {
+    for (int i = 0; i < n; ++i) score[i0 + i] = acc[i];
+  }
+};
+
+struct TailSde {  // Euler-Maruyama (OpSde)
+  struct Regs { float4 x, z; };
+  static constexpr bool NEEDS_G = true;
+  float* x;
+  SdeParams p;
+  Draws d;
+  __device__ void load(size_t i0, Regs& u) const {
+    u.x = *reinterpret_cast<const float4*>(x + i0);
+    if (d.z) u.z = *reinterpret_cast<const float4*>(d.z + i0);
+  }
+  __device__ void quad(size_t i0, f32x4 acc, float Gl, const Regs& u) const {
+    float zz[4];
+    if (d.z) zz[0] = u.z.x, zz[1] = u.z.y, zz[2] = u.z.z, zz[3] = u.z.w;
+    else normal4((d.elem_offset + i0) >> 2, d.seed, d.tag, zz);
+    *reinterpret_cast<float4*>(x + i0) = float4{sde_update(u.x.x, acc[0], Gl, zz[0], p), sde_update(u.x.y, acc[1], Gl, zz[1], p),
+                                                sde_update(u.x.z, acc[2], Gl, zz[2], p), sde_update(u.x.w, acc[3], Gl, zz[3], p)};
+  }
+  __device__ void ragged(size_t i0, int n, f32x4 acc, float Gl) const {
+    float zz[4];
+    load_normals(d.z, i0, n, d.seed, d.elem_offset, d.tag, zz);
+    for (int i = 0; i < n; ++i) x[i0 + i] = sde_update(x[i0 + i], acc[i], Gl, zz[i], p);
+  }
+};
+
+template <int TAIL>
+struct TailOde {  // OpOde<TAIL>; u0 = the quad ode_update starts from (x; CORRECT: xp), u1 / u2 = CORRECT's x and d1
+  struct Regs { float4 u0, u1, u2; };
+  static constexpr bool NEEDS_G = true;
+  float *x, *xp, *d1;
+  SdeParams p;
+  __device__ void load(size_t i0, Regs& u) const {
+    u.u0 = *reinterpret_cast<const float4*>((TAIL == ODE_CORRECT ? xp : x) + i0);
+    if (TAIL == ODE_CORRECT) {
+      u.u1 = *reinterpret_cast<const float4*>(x + i0);
+      u.u2 = *reinterpret_cast<const float4*>(d1 + i0);
+    }
+  }
+  __device__ void quad(size_t i0, f32x4 acc, float Gl, const Regs& u) const {
+    float4 dv = u.u2;
+    const float4 xn = float4{ode_update<TAIL>(u.u0.x, acc[0], Gl, u.u1.x, dv.x, p), ode_update<TAIL>(u.u0.y, acc[1], Gl, u.u1.y, dv.y, p),
+                             ode_update<TAIL>(u.u0.z, acc[2], Gl, u.u1.z, dv.z, p), ode_update<TAIL>(u.u0.w, acc[3], Gl, u.u1.w, dv.w, p)};
+    *reinterpret_cast<float4*>((TAIL == ODE_PREDICT ? xp : x) + i0) = xn;
+    if (TAIL == ODE_PREDICT) *reinterpret_cast<float4*>(d1 + i0) = dv;
+  }
+  __device__ void ragged(size_t i0, int n, f32x4 acc, float Gl) const {
+    for (int i = 0; i < n; ++i) {
+      float dv = TAIL == ODE_CORRECT ? d1[i0 + i] : 0.f;
+      const float x0 = TAIL == ODE_CORRECT ? x[i0 + i] : 0.f;
+      const float xn = ode_update<TAIL>((TAIL == ODE_CORRECT ? xp : x)[i0 + i], acc[i], Gl, x0, dv, p);
+      (TAIL == ODE_PREDICT ? xp : x)[i0 + i] = xn;
+      if (TAIL == ODE_PREDICT) d1[i0 + i] = dv;
+    }
+  }
+};
+
+template <bool PREV>
+struct TailMultistep {  // OpMultistep<PREV>; moves two (B, L, C) arrays more than Euler's: 4 (d + 4 C) B per row
+  struct Regs { float4 x, hist; };
+  static constexpr bool NEEDS_G = true;
+  float *x, *hist;
+  MultistepParams p;
+  __device__ void load(size_t i0, Regs& u) const {
+    u.x = *reinterpret_cast<const float4*>(x + i0);
+    if (PREV) u.hist = *reinterpret_cast<const float4*>(hist + i0);
+  }
+  __device__ void quad(size_t i0, f32x4 acc, float Gl, const Regs& u) const {
+    float4 hq = u.hist;
+    *reinterpret_cast<float4*>(x + i0) =
+        float4{multistep_update<PREV>(u.x.x, acc[0], Gl, hq.x, p), multistep_update<PREV>(u.x.y, acc[1], Gl, hq.y, p),
+               multistep_update<PREV>(u.x.z, acc[2], Gl, hq.z, p), multistep_update<PREV>(u.x.w, acc[3], Gl, hq.w, p)};
+    *reinterpret_cast<float4*>(hist + i0) = hq;
+  }
+  __device__ void ragged(size_t i0, int n, f32x4 acc, float Gl) const {
+    for (int i = 0; i < n; ++i) {
+      float hq = PREV ? hist[i0 + i] : 0.f;
+      x[i0 + i] = multistep_update<PREV>(x[i0 + i], acc[i], Gl, hq, p);
+      hist[i0 + i] = hq;
+    }
+  }
+};
+
+template <int D, class Tail>
 __global__ __launch_bounds__(256) void k_unembed_mfma(const float* __restrict__ h, const float* __restrict__ Wu,
-                                                      const float* __restrict__ bu, float* __restrict__ score,
-                                                      float* __restrict__ x, const float* __restrict__ z,
-                                                      const float* __restrict__ G, SdeParams p, uint64_t seed,
-                                                      uint64_t elem_offset, uint32_t step, int M, int L, int C) {
+                                                      const float* __restrict__ bu, const float* __restrict__ G, Tail tail,
+                                                      int M, int L, int C) {
   constexpr int NG = (D + 15) / 16;  // 16-wide k chunks
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, q = lane >> 4;
@@ -825,28 +782,23 @@ __global__ __launch_bounds__(256) void k_unembed_mfma(const float* __restrict__ 
   f32x4 bias;
 #pragma unroll
   for (int i = 0; i < 4; ++i) bias[i] = (4 * q + i < C) ? bu[4 * q + i] : 0.f;
-  auto load_tile = [&](int t, float4 (&hv)[NG]) {
+  // a tile's h rows and, where the lane holds a whole quad (C % 4 == 0), the tail's operands
+  const bool quad = (C & 3) == 0 && 4 * q < C;
+  auto load_tile = [&](int t, float4 (&hv)[NG], typename Tail::Regs& u) {
     const int row = min(16 * t + r, M - 1);
     const float* hr = h + (size_t)row * D + 4 * q;
 #pragma unroll
     for (int g = 0; g < NG; ++g)
       hv[g] = (16 * g + 4 * q < D) ? *reinterpret_cast<const float4*>(hr + 16 * g) : float4{0.f, 0.f, 0.f, 0.f};
-  };
-  // (SDE, C % 4 == 0) the tile's x / injected z quad is fetched together with its h rows
-  const bool quad = SDE && (C & 3) == 0 && 4 * q < C;
-  auto load_xz = [&](int t, float4& xv, float4& zv) {
-    if (quad) {
-      const size_t i0 = (size_t)min(16 * t + r, M - 1) * C + 4 * q;
-      xv = *reinterpret_cast<const float4*>(x + i0);
-      if (z) zv = *reinterpret_cast<const float4*>(z + i0);
-    }
+    if (quad) tail.load((size_t)row * C + 4 * q, u);
   };
   float4 hv[NG], hn[NG];
-  float4 xv{}, zv{}, xnx{}, znx{};
-  if (wave < ntiles) load_tile(wave, hv), load_xz(wave, xv, zv);
+  typename Tail::Regs u{};
+  if (wave < ntiles) load_tile(wave, hv, u);
   for (int t = wave; t < ntiles; t += nwaves) {
     const bool more = t + nwaves < ntiles;
-    if (more) load_tile(t + nwaves, hn), load_xz(t + nwaves, xnx, znx);
+    typename Tail::Regs un{};
+    if (more) load_tile(t + nwaves, hn, un);
     f32x4 acc = bias;
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
@@ -859,33 +811,14 @@ __global__ __launch_bounds__(256) void k_unembed_mfma(const float* __restrict__ 
     const int c0 = 4 * q;
     if (row < M && c0 < C) {
       const size_t i0 = (size_t)row * C + c0;
-      const int n = min(4, C - c0);
-      if (!SDE) {
-        if ((C & 3) == 0) *reinterpret_cast<float4*>(score + i0) = float4{acc[0], acc[1], acc[2], acc[3]};
-        else
-          for (int i = 0; i < n; ++i) score[i0 + i] = acc[i];
-      } else {
-        const float Gl = G[row % L];
-        float zz[4];
-        if ((C & 3) == 0) {
-          const float4 xi = xv;
-          if (z) {
-            zz[0] = zv.x, zz[1] = zv.y, zz[2] = zv.z, zz[3] = zv.w;
-          } else {
-            normal4((elem_offset + i0) >> 2, seed, step, zz);
-          }
-          *reinterpret_cast<float4*>(x + i0) = float4{sde_update(xi.x, acc[0], Gl, zz[0], p), sde_update(xi.y, acc[1], Gl, zz[1], p),
-                                                      sde_update(xi.z, acc[2], Gl, zz[2], p), sde_update(xi.w, acc[3], Gl, zz[3], p)};
-        } else {
-          load_normals(z, i0, n, seed, elem_offset, step, zz);
-          for (int i = 0; i < n; ++i) x[i0 + i] = sde_update(x[i0 + i], acc[i], Gl, zz[i], p);
-        }
-      }
+      const float Gl = Tail::NEEDS_G ? G[row % L] : 0.f;
+      if ((C & 3) == 0) tail.quad(i0, acc, Gl, u);
+      else tail.ragged(i0, min(4, C - c0), acc, Gl);
     }
     if (more) {
 #pragma unroll
       for (int g = 0; g < NG; ++g) hv[g] = hn[g];
-      xv = xnx, zv = znx;
+      u = un;
     }
   }
 }
@@ -926,17 +859,16 @@ bool unembed_sde_supported(int C, int D) {
   return false;
 }
 
-template <bool SDE>
-static hipError_t launch_unembed_mfma(const float* h, const float* Wu, const float* bu, float* score, float* x,
-                                      const float* z, const float* G, SdeParams p, uint64_t seed, uint64_t elem_offset,
-                                      uint32_t step, int M, int L, int C, int D, hipStream_t s) {
+// every tail's launch (requires unembed_sde_supported(C, D))
+template <class Tail>
+static hipError_t launch_unembed_tail(Tail tail, const float* h, const float* Wu, const float* bu, const float* G, int M,
+                                      int L, int C, int D, hipStream_t s) {
   int blocks = cdiv(cdiv(M, 16), 4);
   if (blocks > 2048) blocks = 2048;
   switch (D) {
-#define X(d)                                                                                                     \
-  case d:                                                                                                        \
-    hipLaunchKernelGGL((k_unembed_mfma<d, SDE>), dim3(blocks), dim3(256), 0, s, h, Wu, bu, score, x, z, G, p, seed, \
-                       elem_offset, step, M, L, C);                                                              \
+#define X(d)                                                                                                          \
+  case d:                                                                                                             \
+    hipLaunchKernelGGL((k_unembed_mfma<d, Tail>), dim3(blocks), dim3(256), 0, s, h, Wu, bu, G, tail, M, L, C); \
     break;
     FFD_D_LIST(X)
 #undef X
@@ -948,7 +880,7 @@ static hipError_t launch_unembed_mfma(const float* h, const float* Wu, const flo
 hipError_t launch_unembed(const float* h, const float* Wu, const float* bu, float* score, int M, int C, int D,
                           hipStream_t s) {
   if (unembed_sde_supported(C, D) && ptr16(h) && ptr16(Wu) && ptr16(score))
-    return launch_unembed_mfma<false>(h, Wu, bu, score, nullptr, nullptr, nullptr, SdeParams{}, 0, 0, 0, M, 1, C, D, s);
+    return launch_unembed_tail(TailStore{score}, h, Wu, bu, nullptr, M, 1, C, D, s);
   if (D > 128 || (size_t)C * D * sizeof(float) > 64 * 1024) return hipErrorInvalidValue;
   int blocks = cdiv(M, 16);
   if (blocks > 4096) blocks = 4096;
@@ -963,118 +895,7 @@ hipError_t launch_unembed_sde(const float* h, const float* Wu, const float* bu, 
   if (!unembed_sde_supported(C, D) || !ptr16(h) || !ptr16(Wu)) return hipErrorInvalidValue;
   if ((C & 3) == 0 && (!ptr16(x) || !ptr16(z))) return hipErrorInvalidValue;  // x / z quads
   if ((C & 3) == 0 && (elem_offset & 3)) return hipErrorInvalidValue;
-  return launch_unembed_mfma<true>(h, Wu, bu, nullptr, x, z, G, p, seed, elem_offset, step, B * L, L, C, D, s);
-}
-
-// The probability-flow ODE tails of the sampling loop: k_unembed_mfma's score tile (same fragments, same MFMA order,
-// same prefetch of the next tile) continued with ode_update in the accumulator registers.  A sibling kernel, so that
-// the two instances above keep their code.  Buffers by tail as in k_ode_step; the quad path (C % 4 == 0) fetches the
-// tile's x (CORRECT: xp, x and d1) together with its h rows.
-template <int D, int TAIL>
-__global__ __launch_bounds__(256) void k_unembed_ode(const float* __restrict__ h, const float* __restrict__ Wu,
-                                                     const float* __restrict__ bu, float* __restrict__ x,
-                                                     float* __restrict__ xp, float* __restrict__ d1,
-                                                     const float* __restrict__ G, SdeParams p, int M, int L, int C) {
-  constexpr int NG = (D + 15) / 16;  // 16-wide k chunks
-  const int lane = threadIdx.x & 63;
-  const int r = lane & 15, q = lane >> 4;
-  const int ntiles = (M + 15) >> 4;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-  float4 wf[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const int k = 16 * g + 4 * q;
-    wf[g] = (r < C && k < D) ? *reinterpret_cast<const float4*>(Wu + (size_t)r * D + k) : float4{0.f, 0.f, 0.f, 0.f};
-  }
-  f32x4 bias;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) bias[i] = (4 * q + i < C) ? bu[4 * q + i] : 0.f;
-  auto load_tile = [&](int t, float4 (&hv)[NG]) {
-    const int row = min(16 * t + r, M - 1);
-    const float* hr = h + (size_t)row * D + 4 * q;
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-      hv[g] = (16 * g + 4 * q < D) ? *reinterpret_cast<const float4*>(hr + 16 * g) : float4{0.f, 0.f, 0.f, 0.f};
-  };
-  // u0 = the quad ode_update starts from (x; CORRECT: xp), u1 / u2 = CORRECT's x and d1
-  const bool quad = (C & 3) == 0 && 4 * q < C;
-  auto load_u = [&](int t, float4& u0, float4& u1, float4& u2) {
-    if (quad) {
-      const size_t i0 = (size_t)min(16 * t + r, M - 1) * C + 4 * q;
-      u0 = *reinterpret_cast<const float4*>((TAIL == ODE_CORRECT ? xp : x) + i0);
-      if (TAIL == ODE_CORRECT) {
-        u1 = *reinterpret_cast<const float4*>(x + i0);
-        u2 = *reinterpret_cast<const float4*>(d1 + i0);
-      }
-    }
-  };
-  float4 hv[NG], hn[NG];
-  float4 u0{}, u1{}, u2{}, n0{}, n1{}, n2{};
-  if (wave < ntiles) load_tile(wave, hv), load_u(wave, u0, u1, u2);
-  for (int t = wave; t < ntiles; t += nwaves) {
-    const bool more = t + nwaves < ntiles;
-    if (more) load_tile(t + nwaves, hn), load_u(t + nwaves, n0, n1, n2);
-    f32x4 acc = bias;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      acc = mfma16(wf[g].x, hv[g].x, acc);
-      acc = mfma16(wf[g].y, hv[g].y, acc);
-      acc = mfma16(wf[g].z, hv[g].z, acc);
-      acc = mfma16(wf[g].w, hv[g].w, acc);
-    }
-    const int row = 16 * t + r;
-    const int c0 = 4 * q;
-    if (row < M && c0 < C) {
-      const size_t i0 = (size_t)row * C + c0;
-      const float Gl = G[row % L];
-      if ((C & 3) == 0) {
-        float4 dv = u2;
-        const float4 xn = float4{ode_update<TAIL>(u0.x, acc[0], Gl, u1.x, dv.x, p), ode_update<TAIL>(u0.y, acc[1], Gl, u1.y, dv.y, p),
-                                 ode_update<TAIL>(u0.z, acc[2], Gl, u1.z, dv.z, p), ode_update<TAIL>(u0.w, acc[3], Gl, u1.w, dv.w, p)};
-        if (TAIL == ODE_PREDICT) {
-          *reinterpret_cast<float4*>(xp + i0) = xn;
-          *reinterpret_cast<float4*>(d1 + i0) = dv;
-        } else {
-          *reinterpret_cast<float4*>(x + i0) = xn;
-        }
-      } else {
-        const int n = min(4, C - c0);
-        for (int i = 0; i < n; ++i) {
-          if (TAIL == ODE_CORRECT) {
-            float dv = d1[i0 + i];
-            x[i0 + i] = ode_update<TAIL>(xp[i0 + i], acc[i], Gl, x[i0 + i], dv, p);
-          } else {
-            float dv = 0.f;
-            const float xn = ode_update<TAIL>(x[i0 + i], acc[i], Gl, 0.f, dv, p);
-            if (TAIL == ODE_PREDICT) xp[i0 + i] = xn, d1[i0 + i] = dv;
-            else x[i0 + i] = xn;
-          }
-        }
-      }
-    }
-    if (more) {
-#pragma unroll
-      for (int g = 0; g < NG; ++g) hv[g] = hn[g];
-      u0 = n0, u1 = n1, u2 = n2;
-    }
-  }
-}
-
-template <int TAIL>
-static hipError_t launch_unembed_ode_tail(const float* h, const float* Wu, const float* bu, float* x, float* xp, float* d1,
-                                          const float* G, SdeParams p, int M, int L, int C, int D, hipStream_t s) {
-  int blocks = cdiv(cdiv(M, 16), 4);
-  if (blocks > 2048) blocks = 2048;
-  switch (D) {
-#define X(d)                                                                                                          \
-  case d:                                                                                                             \
-    hipLaunchKernelGGL((k_unembed_ode<d, TAIL>), dim3(blocks), dim3(256), 0, s, h, Wu, bu, x, xp, d1, G, p, M, L, C); \
-    break;
-    FFD_D_LIST(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return launch_unembed_tail(TailSde{x, p, Draws{z, seed, elem_offset, step}}, h, Wu, bu, G, B * L, L, C, D, s);
 }
 
 // tail(x, unembed(h)): the fused tail of an ODE interval (requires unembed_sde_supported(C, D)); xp / d1 as in
@@ -1085,109 +906,11 @@ hipError_t launch_unembed_ode(int tail, const float* h, const float* Wu, const f
   if ((C & 3) == 0 && (!ptr16(x) || !ptr16(xp) || !ptr16(d1))) return hipErrorInvalidValue;  // quads
   if (tail != ODE_EULER && (!xp || !d1)) return hipErrorInvalidValue;
   switch (tail) {
-    case ODE_EULER: return launch_unembed_ode_tail<ODE_EULER>(h, Wu, bu, x, nullptr, nullptr, G, p, B * L, L, C, D, s);
-    case ODE_PREDICT: return launch_unembed_ode_tail<ODE_PREDICT>(h, Wu, bu, x, xp, d1, G, p, B * L, L, C, D, s);
-    case ODE_CORRECT: return launch_unembed_ode_tail<ODE_CORRECT>(h, Wu, bu, x, xp, d1, G, p, B * L, L, C, D, s);
+    case ODE_EULER: return launch_unembed_tail(TailOde<ODE_EULER>{x, nullptr, nullptr, p}, h, Wu, bu, G, B * L, L, C, D, s);
+    case ODE_PREDICT: return launch_unembed_tail(TailOde<ODE_PREDICT>{x, xp, d1, p}, h, Wu, bu, G, B * L, L, C, D, s);
+    case ODE_CORRECT: return launch_unembed_tail(TailOde<ODE_CORRECT>{x, xp, d1, p}, h, Wu, bu, G, B * L, L, C, D, s);
     default: return hipErrorInvalidValue;
   }
-}
-
-// The multistep tail of the sampling loop: the k_unembed_ode scheme (same fragments, same MFMA order, same prefetch of
-// the next tile) continued with multistep_update in the accumulator registers.  One more sibling, so that the instances
-// above keep their code.  The quad path (C % 4 == 0) fetches the tile's x and (PREV) hist quads together with its h
-// rows; the tail moves two (B, L, C) arrays more than Euler's, 4 (d + 4 C) B per row against 4 (d + 2 C).
-template <int D, bool PREV>
-__global__ __launch_bounds__(256) void k_unembed_multistep(const float* __restrict__ h, const float* __restrict__ Wu,
-                                                           const float* __restrict__ bu, float* __restrict__ x,
-                                                           float* __restrict__ hist, const float* __restrict__ G,
-                                                           MultistepParams p, int M, int L, int C) {
-  constexpr int NG = (D + 15) / 16;  // 16-wide k chunks
-  const int lane = threadIdx.x & 63;
-  const int r = lane & 15, q = lane >> 4;
-  const int ntiles = (M + 15) >> 4;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-  float4 wf[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const int k = 16 * g + 4 * q;
-    wf[g] = (r < C && k < D) ? *reinterpret_cast<const float4*>(Wu + (size_t)r * D + k) : float4{0.f, 0.f, 0.f, 0.f};
-  }
-  f32x4 bias;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) bias[i] = (4 * q + i < C) ? bu[4 * q + i] : 0.f;
-  auto load_tile = [&](int t, float4 (&hv)[NG]) {
-    const int row = min(16 * t + r, M - 1);
-    const float* hr = h + (size_t)row * D + 4 * q;
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-      hv[g] = (16 * g + 4 * q < D) ? *reinterpret_cast<const float4*>(hr + 16 * g) : float4{0.f, 0.f, 0.f, 0.f};
-  };
-  const bool quad = (C & 3) == 0 && 4 * q < C;
-  auto load_u = [&](int t, float4& u0, float4& u1) {  // u0 = x, u1 = hist
-    if (quad) {
-      const size_t i0 = (size_t)min(16 * t + r, M - 1) * C + 4 * q;
-      u0 = *reinterpret_cast<const float4*>(x + i0);
-      if (PREV) u1 = *reinterpret_cast<const float4*>(hist + i0);
-    }
-  };
-  float4 hv[NG], hn[NG];
-  float4 u0{}, u1{}, n0{}, n1{};
-  if (wave < ntiles) load_tile(wave, hv), load_u(wave, u0, u1);
-  for (int t = wave; t < ntiles; t += nwaves) {
-    const bool more = t + nwaves < ntiles;
-    if (more) load_tile(t + nwaves, hn), load_u(t + nwaves, n0, n1);
-    f32x4 acc = bias;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      acc = mfma16(wf[g].x, hv[g].x, acc);
-      acc = mfma16(wf[g].y, hv[g].y, acc);
-      acc = mfma16(wf[g].z, hv[g].z, acc);
-      acc = mfma16(wf[g].w, hv[g].w, acc);
-    }
-    const int row = 16 * t + r;
-    const int c0 = 4 * q;
-    if (row < M && c0 < C) {
-      const size_t i0 = (size_t)row * C + c0;
-      const float Gl = G[row % L];
-      if ((C & 3) == 0) {
-        float4 hq = u1;
-        *reinterpret_cast<float4*>(x + i0) =
-            float4{multistep_update<PREV>(u0.x, acc[0], Gl, hq.x, p), multistep_update<PREV>(u0.y, acc[1], Gl, hq.y, p),
-                   multistep_update<PREV>(u0.z, acc[2], Gl, hq.z, p), multistep_update<PREV>(u0.w, acc[3], Gl, hq.w, p)};
-        *reinterpret_cast<float4*>(hist + i0) = hq;
-      } else {
-        const int n = min(4, C - c0);
-        for (int i = 0; i < n; ++i) {
-          float hq = PREV ? hist[i0 + i] : 0.f;
-          x[i0 + i] = multistep_update<PREV>(x[i0 + i], acc[i], Gl, hq, p);
-          hist[i0 + i] = hq;
-        }
-      }
-    }
-    if (more) {
-#pragma unroll
-      for (int g = 0; g < NG; ++g) hv[g] = hn[g];
-      u0 = n0, u1 = n1;
-    }
-  }
-}
-
-template <bool PREV>
-static hipError_t launch_unembed_multistep_tail(const float* h, const float* Wu, const float* bu, float* x, float* hist,
-                                                const float* G, MultistepParams p, int M, int L, int C, int D,
-                                                hipStream_t s) {
-  int blocks = cdiv(cdiv(M, 16), 4);
-  if (blocks > 2048) blocks = 2048;
-  switch (D) {
-#define X(d)                                                                                                             \
-  case d:                                                                                                                \
-    hipLaunchKernelGGL((k_unembed_multistep<d, PREV>), dim3(blocks), dim3(256), 0, s, h, Wu, bu, x, hist, G, p, M, L, C); \
-    break;
-    FFD_D_LIST(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
 }
 
 // multistep tail(x, hist, unembed(h)): the fused tail of a multistep interval (requires unembed_sde_supported(C, D))
@@ -1195,8 +918,8 @@ hipError_t launch_unembed_multistep(const float* h, const float* Wu, const float
                                     MultistepParams p, int have_prev, int B, int L, int C, int D, hipStream_t s) {
   if (!unembed_sde_supported(C, D) || !ptr16(h) || !ptr16(Wu) || !hist) return hipErrorInvalidValue;
   if ((C & 3) == 0 && (!ptr16(x) || !ptr16(hist))) return hipErrorInvalidValue;  // quads
-  if (have_prev) return launch_unembed_multistep_tail<true>(h, Wu, bu, x, hist, G, p, B * L, L, C, D, s);
-  return launch_unembed_multistep_tail<false>(h, Wu, bu, x, hist, G, p, B * L, L, C, D, s);
+  if (have_prev) return launch_unembed_tail(TailMultistep<true>{x, hist, p}, h, Wu, bu, G, B * L, L, C, D, s);
+  return launch_unembed_tail(TailMultistep<false>{x, hist, p}, h, Wu, bu, G, B * L, L, C, D, s);
 }
 
 // ---------------------------------------------------------------------------

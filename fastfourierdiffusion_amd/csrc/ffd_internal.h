@@ -25,6 +25,9 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 
 constexpr __host__ __device__ int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// float4 access through p is allowed (nullptr: an absent array)
+inline bool ptr16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // relu as ONE vector instruction (v_max_i32): max of the bit pattern, as a signed integer, with 0.  Negative floats
 // and -0.0 are negative integers -> +0.0; +0.0, positive floats and +inf are themselves: for every non-NaN x the bits
 // of fmaxf(x, 0).  (A float max / med3 of an MFMA result costs two: hipcc cannot prove the accumulator canonical and
@@ -46,7 +49,7 @@ __device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
 #pragma unroll
   for (int i = 0; i < 10; ++i) {
     // one 32 x 32 -> 64 multiply per product (v_mad_u64_u32) instead of a mul_hi / mul_lo pair: the generator is the
-    // ALU floor of the noise-drawing kernels (k_prior writes 4 B per element and nothing else)
+    // ALU floor of the noise-drawing kernels (the prior writes 4 B per element and nothing else)
     const uint64_t p0 = (uint64_t)M0 * c.x, p1 = (uint64_t)M1 * c.z;
     const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
     U4 n = {hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};

@@ -6,17 +6,15 @@
 //   1. k_lv_rowsq    rowsq[row] = (sum_c u^2, sum_c w^2): fp32 squares summed in fp64, c ascending
 //   2. k_lv_norms    per sample a fixed-order fp64 tree over its L row partials -> n_u, n_w (and eps, sample norm)
 //      k_lv_eps_batch  (batch norm only) a fixed-order mean over b -> eps
-//   3. k_lv_update   the update; on the Philox path it REGENERATES stage 1's draw (the ffd_loss.hip precedent): the
+//   3. k_step<OpLangevin>  the update; on the Philox path it REGENERATES stage 1's draw (the ffd_loss.hip precedent): the
 //      draw of global element g is slot g & 3 of Philox block g >> 2 whichever kernel asks, so no z buffer exists
 // No atomics anywhere: the order of every sum is fixed by the element index (row l, then channel c), not by the
 // thread layout, the batch size or the sample's place in the batch.
 #include <math.h>
 
-#include "ffd_internal.h"
+#include "ffd_step.h"
 
 namespace ffd {
-
-static bool ptr16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // the two fp32 squares of one element, each product its own rounding
 __device__ __forceinline__ void lv_terms(float sc, float zz, float Gl, float g2, double& su, double& sw) {
@@ -125,55 +123,29 @@ __device__ __forceinline__ float lv_update(float xi, float sc, float zz, float G
   return __fadd_rn(__fadd_rn(xi, __fmul_rn(e, u)), __fmul_rn(s, w));
 }
 
-// Stage 3, the twins of k_sde_step_v4 / k_sde_step.  A sample with eps == 0 is not touched.
-__global__ __launch_bounds__(256) void k_lv_update_v4(float* __restrict__ x, const float* __restrict__ score,
-                                                      const float* __restrict__ z, const float* __restrict__ G,
-                                                      const float* __restrict__ eps, const float* __restrict__ se,
-                                                      uint64_t seed, uint64_t elem_offset, uint32_t tag, size_t nvec,
-                                                      int L, unsigned C4) {
-  const size_t per = (size_t)L * C4;  // float4 per sample
-  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
-    const size_t b = v / per;
-    const float e = eps[b];
-    if (e == 0.f) continue;
-    const float s = se[b];
-    const float4 xi = reinterpret_cast<const float4*>(x)[v];
-    const float4 sc = reinterpret_cast<const float4*>(score)[v];
-    float zz[4];
-    if (z) {
-      const float4 zv = reinterpret_cast<const float4*>(z)[v];
-      zz[0] = zv.x, zz[1] = zv.y, zz[2] = zv.z, zz[3] = zv.w;
-    } else {
-      normal4((elem_offset >> 2) + v, seed, tag, zz);  // elem_offset % 4 == 0
-    }
-    const float Gl = G[(v / C4) % (size_t)L];
-    const float g2 = __fmul_rn(Gl, Gl);
-    reinterpret_cast<float4*>(x)[v] = float4{lv_update(xi.x, sc.x, zz[0], Gl, g2, e, s), lv_update(xi.y, sc.y, zz[1], Gl, g2, e, s),
-                                             lv_update(xi.z, sc.z, zz[2], Gl, g2, e, s), lv_update(xi.w, sc.w, zz[3], Gl, g2, e, s)};
+// Stage 3: the op of k_step_v4 / k_step (ffd_step.h), the only one with per-sample parameters.  A sample with
+// eps == 0 is not touched.
+struct OpLangevin {
+  static constexpr bool DRAWS = true, SAMPLE = true;
+  float* x;
+  const float* score;
+  const float *eps, *se;
+  Draws d;
+  static constexpr int NIN = 2;  // x, score
+  bool aligned() const { return ptr16(x) && ptr16(score); }
+  __device__ bool skip(size_t b) const { return eps[b] == 0.f; }
+  template <int W>
+  __device__ void load(size_t i, float (&in)[NIN][W]) const {
+    ld<W>(x, i, in[0]), ld<W>(score, i, in[1]);
   }
-}
-
-__global__ __launch_bounds__(256) void k_lv_update(float* __restrict__ x, const float* __restrict__ score,
-                                                   const float* __restrict__ z, const float* __restrict__ G,
-                                                   const float* __restrict__ eps, const float* __restrict__ se,
-                                                   uint64_t seed, uint64_t elem_offset, uint32_t tag, size_t total, int L,
-                                                   int C) {
-  const size_t nvec = (total + 3) / 4, per = (size_t)L * C;
-  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
-    const size_t i0 = v * 4;
-    const int n = (int)((total - i0) < 4 ? (total - i0) : 4);
-    float zz[4];
-    load_normals(z, i0, n, seed, elem_offset, tag, zz);
-    for (int j = 0; j < n; ++j) {
-      const size_t i = i0 + j;
-      const size_t b = i / per;
-      const float e = eps[b];
-      if (e == 0.f) continue;
-      const float Gl = G[(i / (size_t)C) % (size_t)L];
-      x[i] = lv_update(x[i], score[i], zz[j], Gl, __fmul_rn(Gl, Gl), e, se[b]);
-    }
+  template <int W>
+  __device__ void update(size_t i, float (&in)[NIN][W], float Gl, const float (&zz)[W], size_t b) const {
+    const float e = eps[b], s = se[b], g2 = __fmul_rn(Gl, Gl);
+#pragma unroll
+    for (int j = 0; j < W; ++j) in[0][j] = lv_update(in[0][j], in[1][j], zz[j], Gl, g2, e, s);
+    st<W>(x, i, in[0]);
   }
-}
+};
 
 size_t langevin_work_bytes(int B, int L) {
   return sizeof(double2) * (size_t)B * L + sizeof(double2) * (size_t)B + 2 * sizeof(float) * (size_t)B;
@@ -183,7 +155,7 @@ hipError_t launch_langevin(float* x, const float* score, const float* z, const f
                            int norm, uint64_t seed, uint64_t elem_offset, uint32_t tag, int B, int L, int C,
                            float* eps_out, void* work, hipStream_t s) {
   if (reinterpret_cast<uintptr_t>(work) & 15) return hipErrorInvalidValue;
-  const size_t M = (size_t)B * L, total = M * C;
+  const size_t M = (size_t)B * L;
   double2* rowsq = static_cast<double2*>(work);
   double2* nrm = rowsq + M;
   float* eps = reinterpret_cast<float*>(nrm + B);
@@ -203,15 +175,7 @@ hipError_t launch_langevin(float* x, const float* score, const float* z, const f
     hipLaunchKernelGGL(k_lv_norms<false>, dim3((unsigned)B), dim3(256), 0, s, rowsq, nrm, snr, alpha, eps, se, eps_out, L);
     hipLaunchKernelGGL(k_lv_eps_batch, dim3(1), dim3(256), 0, s, nrm, snr, alpha, eps, se, eps_out, B);
   }
-  blocks = ((total + 3) / 4 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (vec)
-    hipLaunchKernelGGL(k_lv_update_v4, dim3((unsigned)blocks), dim3(256), 0, s, x, score, z, G, eps, se, seed, elem_offset, tag,
-                       total / 4, L, (unsigned)C / 4);
-  else
-    hipLaunchKernelGGL(k_lv_update, dim3((unsigned)blocks), dim3(256), 0, s, x, score, z, G, eps, se, seed, elem_offset, tag,
-                       total, L, C);
-  return hipGetLastError();
+  return launch_step(OpLangevin{x, score, eps, se, Draws{z, seed, elem_offset, tag}}, G, B, L, C, s);
 }
 
 double langevin_alpha(int sde, double a, double b, double t, float step_size) {

@@ -14,8 +14,6 @@
 
 namespace ffd {
 
-static bool ptr16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 __global__ __launch_bounds__(256) void k_sm_draw_times(float* __restrict__ t, int B, float span, float eps, float T,
                                                        uint64_t seed, uint64_t sample_offset) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

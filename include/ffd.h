@@ -882,7 +882,7 @@ enum {
   FFD_K_OUTPROJ = 2,     /* k_linear_res_ln: out-projection + residual + LayerNorm1 */
   FFD_K_LSTM_REC = 3,    /* k_lstm_*: the L-step recurrence of one residual LSTM layer */
   FFD_K_LSTM_GATES = 4,  /* k_linear_rm: input-gate GEMM of one LSTM layer */
-  FFD_K_SDE = 5,         /* k_sde_step (or the fused unembed + SDE step); in ffd_sample_batch_ode the ODE tails (Euler,
+  FFD_K_SDE = 5,         /* the SDE step (or the fused unembed + SDE step); in ffd_sample_batch_ode the ODE tails (Euler,
                           * Heun's two, or the multistep tail), in ffd_sample_batch_pc also the corrector's launches */
   FFD_K_EMBED = 6,
   FFD_K_UNEMBED = 7,
@@ -911,8 +911,8 @@ int ffd_kernel_timing_get(const ffd_ctx* ctx, int kernel_class, float* avg_ms_ou
  * multistep solvers the tail with history (every interval of a trajectory but its first, which reads no history); after
  * ffd_sample_batch_pc the predictor's tail (its work figures) followed by the corrector's kernels.  The projections of
  * ffd_sample_batch_cond (k_cond_project / k_cond_time: about 16 B of HBM traffic per element, 12 B with device draws) and
- * the transitions of ffd_sample_batch_resample (k_forward_transition: 12 B per element, 8 B with device draws) are
- * timed under FFD_K_SDE as well but are NOT in this class's name or figures, which describe the update launches only:
+ * the transitions of ffd_sample_batch_resample (the step kernel's OpTransition: 12 B per element, 8 B with device draws)
+ * are timed under FFD_K_SDE as well but are NOT in this class's name or figures, which describe the update launches only:
  * after a conditional loop the mean of ffd_kernel_timing_get covers more launches than the figures do. */
 const char* ffd_kernel_work(const ffd_ctx* ctx, int kernel_class, int B, int cache_hit, double* flops_out,
                             double* bytes_out);

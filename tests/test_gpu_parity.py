@@ -1250,8 +1250,8 @@ def test_pow2_real_fft_paths_vs_oracle(ffd, shape):
 
 @pytest.mark.parametrize("name", ["ecg", "small", "syn", "nasa_lstm"])
 def test_fused_unembed_sde_tail_equals_two_kernels(ffd, name):
-    """ffd_sample_batch unembeds inside the SDE-step kernel (k_unembed_mfma<D, true>): same MFMA sequence for the
-    score, same sde_update, same Philox indexing as unembed + k_sde_step -> bit-identical trajectories, with
+    """ffd_sample_batch unembeds inside the SDE-step kernel (k_unembed_mfma<D, TailSde>): same MFMA sequence for the
+    score, same sde_update, same Philox indexing as unembed + k_step<OpSde> -> bit-identical trajectories, with
     on-device Philox noise and with injected draws, C = 1 / 3 / 4 / 8."""
     import ctypes as C
 
@@ -1908,8 +1908,8 @@ def test_failed_workspace_growth_leaves_no_stale_capacity(ffd):
 #                transposed weight staged in LDS)
 #   unembedding  C <= 16: k_unembed_mfma, lane quad q = 0 .. 3 carries channels 4q .. 4q + 3, float4 stores where
 #                C % 4 == 0, scalar ones otherwise | C > 16: k_unembed (16 lanes per row, weight in LDS)
-#   sampling     C <= 16: the unembedding fused into the step kernel, quad or scalar Philox draws | C > 16: k_sde_step_v4
-#                (C % 4 == 0) or k_sde_step behind the unembedding
+#   sampling     C <= 16: the step is k_unembed_mfma's tail (TailSde), quad or scalar Philox draws | C > 16:
+#                k_step_v4<OpSde> (C % 4 == 0) or k_step<OpSde> behind the unembedding
 def _channel_branches(C):
     embed = ("reg_xvec" if C in (4, 8) else "reg") if C <= 8 else "lds"
     if C <= 16:
@@ -1966,7 +1966,7 @@ def test_dataset_model_golden(ffd, golden, c, variant):
 @pytest.mark.parametrize("c", cases.DATASET_TRAJ_CASES, ids=lambda c: f"{c['name']}-{_channel_branches(c['C'])}")
 def test_dataset_traj_golden(ffd, golden, c):
     """G15 trajectories with injected noise: the sampling tail at C = 5 / 13 (unembedding fused into the step kernel,
-    scalar draws) and C = 40 (k_unembed + k_sde_step_v4), against the unmodified reference."""
+    scalar draws) and C = 40 (k_unembed + k_step_v4<OpSde>), against the unmodified reference."""
     from fastfourierdiffusion_amd.sampling.sampler import DiffusionSampler
 
     g = golden["g15_datasets"]
@@ -1987,7 +1987,7 @@ def test_dataset_traj_golden(ffd, golden, c):
 @pytest.mark.parametrize("strategy", ["energy", "spatial"])
 def test_droughts_fresca_trajectory_vs_oracle(ffd, strategy):
     """FreSca in every step at the droughts shape: the score goes through the generic FFT in two channel groups
-    (7 + 6 of 13) and the unfused k_sde_step (C % 4 != 0), against the oracle's sampler on the same draws."""
+    (7 + 6 of 13) and the unfused k_step<OpSde> (C % 4 != 0), against the oracle's sampler on the same draws."""
     from fastfourierdiffusion_amd.sampling.sampler import DiffusionSampler
 
     c = next(c for c in cases.DATASET_MODEL_CASES if c["name"] == "droughts_tf")
@@ -2045,7 +2045,7 @@ def test_channel_sweep_vs_oracle(ffd, base, C, variant):
 
 # (name, model, sample offset): C = 5 / 13 take the fused tail with scalar stores and draws at an element offset
 # elem_off = offset * L * C with elem_off % 4 != 0 (115 % 4 = 3; 4745 % 4 = 1); C = 16 takes it with float4 quads in all
-# four lane quads; C = 40 has no fused form (k_unembed + k_sde_step_v4)
+# four lane quads; C = 40 has no fused form (k_unembed + k_step_v4<OpSde>)
 _TAIL_CASES = [
     ("C5_L23_off1", dict(kind="transformer", d=24, H=4, NL=2, L=23, C=5), 1),
     ("C13_L365_off1", dict(kind="transformer", d=72, H=12, NL=2, L=365, C=13), 1),

@@ -72,8 +72,8 @@ torch.cuda.synchronize()
 d = 72
 print(json.dumps({"B": B, "L": L, "C": Cn, "B_score": Bs, "algorithmic_bytes": {
     "k_fft<false>": 8 * n, "k_fft<true>": 8 * n, "k_rfft_pow2": 8 * n,
-    "k_sde_step": 12 * n, "k_prior": 4 * n,
+    "<ffd::OpSde>": 12 * n, "<ffd::OpPrior>": 4 * n,
     "k_fresca_apply": 8 * n, "k_fresca_spectrum": 4 * n,
-    "k_embed": 4 * Bs * L * (Cn + d), "k_unembed_mfma<72, false>": 4 * Bs * L * (Cn + d), "k_unembed(": 4 * Bs * L * (Cn + d),
-    "k_unembed_mfma<72, true>": 4 * Bs * L * (d + 2 * Cn),
+    "k_embed": 4 * Bs * L * (Cn + d), "k_unembed_mfma<72, ffd::TailStore>": 4 * Bs * L * (Cn + d), "k_unembed(": 4 * Bs * L * (Cn + d),
+    "k_unembed_mfma<72, ffd::TailSde>": 4 * Bs * L * (d + 2 * Cn),
     "k_linear_res_ln": 4 * Bs * L * 3 * d}}))

@@ -6,8 +6,8 @@ import collections, csv, glob, json, os, sys
 prefix, fdir, wdir = sys.argv[1:4]
 out = sys.argv[4] if len(sys.argv) > 4 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r04_traffic.json")
 NAMES = [("k_ffn_rows", "k_ffn_rows"), ("k_lstm_wave", "k_lstm_wave"), ("k_ffn_ln", "k_ffn_ln"), ("k_qkv_attention", "k_qkv_attention"), ("k_linear_res_ln", "k_linear_res_ln"),
-         ("k_embed", "k_embed"), ("k_unembed_mfma<72, true>", "k_unembed_mfma<sde>"), ("k_unembed_mfma<72, false>", "k_unembed"),
-         ("k_lstm_mfma", "k_lstm_mfma"), ("k_lstm_layer", "k_lstm_layer"), ("k_linear_rm", "k_linear_rm"), ("k_sde_step", "k_sde_step"),
+         ("k_embed", "k_embed"), ("k_unembed_mfma<72, ffd::TailSde>", "k_unembed_mfma<sde>"), ("k_unembed_mfma<72, ffd::TailStore>", "k_unembed"),
+         ("k_lstm_mfma", "k_lstm_mfma"), ("k_lstm_layer", "k_lstm_layer"), ("k_linear_rm", "k_linear_rm"), ("<ffd::OpSde>", "k_sde_step"),
          ("k_rfft_pow2", "k_rfft_pow2")]
 def means(d, counter):
     f = glob.glob(d + "/**/*counter_collection.csv", recursive=True)[0]
