@@ -21,6 +21,7 @@ FFD_SOLVER_EULER_MARUYAMA, FFD_SOLVER_ODE_EULER, FFD_SOLVER_ODE_HEUN, FFD_SOLVER
 FFD_SOLVER_ODE_AB2, FFD_SOLVER_DPMPP_2M = 4, 5
 FFD_LANGEVIN_NORM_BATCH, FFD_LANGEVIN_NORM_SAMPLE = 0, 1
 FFD_COND_FREQUENCY, FFD_COND_TIME = 0, 1
+FFD_LOGLIK_EULER, FFD_LOGLIK_PREDICT, FFD_LOGLIK_CORRECT = 0, 1, 2
 # kernel classes (include/ffd.h FFD_K_*)
 K_FFN, K_ATTN, K_OUTPROJ, K_LSTM_REC, K_LSTM_GATES, K_SDE, K_EMBED, K_UNEMBED = range(8)
 
@@ -142,6 +143,15 @@ SIGNATURES = {
     "ffd_host_mixture_check": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int]),
     "ffd_mixture_tiling": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ffd_prior": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_host_loglik_h": (C.c_int, [C.POINTER(SdeDesc), C.c_double, C.c_double, _F]),
+    "ffd_prior_logp": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_loglik_perturb": (C.c_int, [_P, _P, C.c_float, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint32, _P, C.c_int,
+                                     C.c_int, C.c_int, _P]),
+    "ffd_loglik_tail": (C.c_int, [C.POINTER(SdeDesc), C.c_int, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_float,
+                                  C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint32, _P, _P, _P, C.c_int, C.c_int, C.c_int,
+                                  _P]),
+    "ffd_loglik_batch": (C.c_int, [_P, _P, _P, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P,
+                                   C.c_uint64, C.c_uint64, _P]),
     "ffd_dft": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_idft": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_unstandardize_idft": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -119,6 +119,7 @@ struct ffd_ctx {
   // (ms_solver < 0: none; every other loop entry drops it)
   int ms_solver = -1, ms_B = 0, ms_next = 0;
   Grow<float> lv_work;  // the Langevin corrector's row squares, norms and step sizes (ffd_sample_batch_pc)
+  Grow<float> ll_stack, ll_v1;  // ffd_loglik_batch: the stacked batch of (1 + 2 k) B rows; Heun's v1 (B doubles)
   int tail_solver = FFD_SOLVER_EULER_MARUYAMA;  // the loop entry that ran last (ffd_kernel_work names its FFD_K_SDE tail)
   // cache
   bool cache_enabled = false;
@@ -1374,6 +1375,90 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
     TIMED(FFD_K_SDE, tail(ODE_CORRECT, hidden, score, tn));
   }
   if (multistep && first_step + n_run > 0) ctx->ms_solver = solver, ctx->ms_B = B, ctx->ms_next = first_step + n_run;
+  return FFD_OK;
+}
+
+// The probability-flow ODE walked UPWARD with the divergence of its drift accumulated (include/ffd.h ffd_loglik_batch).
+// Interval j runs from timesteps[n - 1 - j] to timesteps[n - 2 - j]; every divergence evaluation is one forward at the
+// stacked batch of (1 + 2 k) B rows between a perturbation and a tail launch (ffd_loglik.hip).  The workspace, the
+// 32-bit row check and the time table are those of a sampling loop at that many rows.
+int ffd_loglik_batch(ffd_ctx* ctx, float* x, double* delta, int B, const float* timesteps, int n_steps, int first_interval,
+                     int n_run, int solver, int n_probes, double fd_rel, const float* probe_inject, uint64_t seed,
+                     uint64_t sample_offset, void* stream) {
+  if (!ctx) return FFD_ERR_INVALID;
+  const ffd_model_desc& m = ctx->desc;
+  const int L = m.max_len, C = m.n_channels;
+  const bool heun = solver == FFD_SOLVER_ODE_HEUN;
+  if (B < 1 || n_probes < 1) return ctx->fail(FFD_ERR_INVALID, "ffd_loglik_batch: B=%d, n_probes=%d (both must be >= 1)", B, n_probes);
+  if (!loglik_shape_supported(n_probes, B, L, C))
+    return ctx->fail(FFD_ERR_UNSUPPORTED, "ffd_loglik_batch: (1 + 2 n_probes) B L C reaches 2^31; shard the batch");
+  const int rows = (1 + 2 * n_probes) * B;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<float> hs;  // the finite-difference step of every evaluation of the call, in consumption order
+  int rc = loop_begin(ctx, "ffd_loglik_batch", x, rows, timesteps, n_steps, n_steps > 1 ? n_steps - 1 : 0, first_interval,
+                      n_run, 1.f, 0, s, [&]() -> int {
+    if (!delta) return ctx->fail(FFD_ERR_INVALID, "ffd_loglik_batch: null delta");
+    if (solver != FFD_SOLVER_ODE_EULER && !heun)
+      return ctx->fail(FFD_ERR_INVALID, "ffd_loglik_batch: solver %d is neither FFD_SOLVER_ODE_EULER nor FFD_SOLVER_ODE_HEUN", solver);
+    if (!(fd_rel > 0.0 && fd_rel <= 1.7e308)) return ctx->fail(FFD_ERR_INVALID, "ffd_loglik_batch: fd_rel must be > 0 and finite");
+    if (ctx->fresca_on)
+      return ctx->fail(FFD_ERR_STATE, "ffd_loglik_batch: FreSca is on (call ffd_fresca_disable): a rescaled score is not "
+                       "the model's probability-flow ODE");
+    if (n_run > 0) {  // the probes' tags of this run stay inside their family (include/ffd.h)
+      const int64_t e_max = heun ? 2 * (int64_t)(first_interval + n_run - 1) + 1 : first_interval + n_run - 1;
+      if (e_max * n_probes + (n_probes - 1) >= 0x0FFFFFF0ll)
+        return ctx->fail(FFD_ERR_INVALID, "ffd_loglik_batch: evaluations x n_probes reaches 0x0FFFFFF0, the end of the "
+                         "probes' stream tags");
+    }
+    const ffd_sde_desc sd{m.sde, 0, m.sde_a, m.sde_b};
+    for (int j = 0; j < n_run; ++j) {
+      const int lo = n_steps - 1 - (first_interval + j);
+      const double t = (double)timesteps[lo], tn = (double)timesteps[lo - 1], dt = tn - t;
+      float h0 = 0.f, h1 = 0.f;
+      if (!(dt > 0.0) || !((double)(float)dt > 0.0) || ffd_host_loglik_h(&sd, t, fd_rel, &h0) ||
+          (heun && ffd_host_loglik_h(&sd, tn, fd_rel, &h1)))
+        return ctx->fail(FFD_ERR_INVALID, "ffd_loglik_batch: interval %d of the grid cannot be walked (times must be "
+                         "finite, >= 0 and strictly decreasing, with sigma(t) fd_rel > 0 in fp32)", first_interval + j);
+      hs.push_back(h0);
+      if (heun) hs.push_back(h1);
+    }
+    return FFD_OK;
+  });
+  if (rc) return rc;
+  const size_t n = (size_t)B * L * C;
+  if ((rc = ensure(ctx, ctx->ll_stack, (size_t)rows * L * C))) return rc;
+  if (heun) {
+    if ((rc = ensure(ctx, ctx->ode_xp, n))) return rc;
+    if ((rc = ensure(ctx, ctx->ode_d1, n))) return rc;
+    if ((rc = ensure(ctx, ctx->ll_v1, 2 * (size_t)B))) return rc;
+  }
+  float *const stack = ctx->ll_stack.p, *const xp = ctx->ode_xp.p, *const d1 = ctx->ode_d1.p;
+  double* const v1 = reinterpret_cast<double*>(ctx->ll_v1.p);
+  const int per = heun ? 2 : 1;  // evaluations per interval
+  // evaluation `ev` of the call (ordinal e of the trajectory) at grid row `row`: perturb `at`, forward, tail
+  auto evaluate = [&](int stage, const float* at, int ev, int row) -> int {
+    const int64_t e = (int64_t)first_interval * per + ev;
+    const LoglikProbes pr{probe_inject ? probe_inject + (size_t)ev * n_probes * n : nullptr, seed,
+                          sample_offset * (uint64_t)L * C, (uint32_t)(0xF0000000u + (uint32_t)(e * n_probes)), n_probes};
+    const double t = (double)timesteps[row];
+    const int lo = stage == LL_CORRECT ? row + 1 : row;  // the interval's start row
+    const double dt = (double)timesteps[lo - 1] - (double)timesteps[lo];
+    TIMED(FFD_K_SDE, launch_loglik_perturb(at, stack, ctx->G_dev, hs[ev], pr, B, L, C, s));
+    if (int r = forward_impl(ctx, stack, ctx->temb_tab.p + (size_t)row * m.d_model, 0, ctx->score.p, nullptr, rows, -1, s))
+      return r;
+    TIMED(FFD_K_SDE, launch_loglik_tail(stage, m.sde, m.sde_a, m.sde_b, t, dt, hs[ev], x, xp, d1, ctx->score.p, ctx->G_dev, pr,
+                                        delta, v1, nullptr, B, L, C, s));
+    return FFD_OK;
+  };
+  for (int j = 0; j < n_run; ++j) {
+    const int lo = n_steps - 1 - (first_interval + j);
+    if (!heun) {
+      if ((rc = evaluate(LL_EULER, x, j, lo))) return rc;
+      continue;
+    }
+    if ((rc = evaluate(LL_PREDICT, x, 2 * j, lo))) return rc;
+    if ((rc = evaluate(LL_CORRECT, xp, 2 * j + 1, lo - 1))) return rc;
+  }
   return FFD_OK;
 }
 

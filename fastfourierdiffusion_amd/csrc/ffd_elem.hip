@@ -512,15 +512,8 @@ hipError_t launch_forward_transition(float* x, const float* G, float a, float sg
 //   Euler:  x <- x - d(x, t_i) dt
 //   Heun :  d1 = d(x, t_i);  xp = x - d1 dt;  d2 = d(xp, t_{i+1});  x <- x - (1/2 (d1 + d2)) dt
 // No noise draw.  Like sde_update every product / sum is its own fp32 rounding (no FMA contraction).
+// (ode_drift: ffd_step.h, shared with the likelihood tail of ffd_loglik.hip)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float ode_drift(float xi, float sc, float Gl, const SdeParams& p) {
-  const float g = __fmul_rn(p.cs, Gl);
-  const float g2 = __fmul_rn(g, g);
-  const float gs = __fmul_rn(g2, sc);
-  const float hgs = __fmul_rn(0.5f, gs);
-  return (p.sde == 0) ? __fsub_rn(__fmul_rn(p.a, xi), hgs) : -hgs;
-}
-
 // One element of a tail.  EULER: returns the new x (xi = x).  PREDICT: returns xp, d1 = the drift at (x, t_i).
 // CORRECT: xi = xp, sc = the score at xp, p = the parameters at t_{i+1}; x0 / d1 = what PREDICT read / wrote; returns
 // the new x.

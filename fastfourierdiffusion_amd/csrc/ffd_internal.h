@@ -285,6 +285,27 @@ hipError_t launch_langevin(float* x, const float* score, const float* z, const f
                            int norm, uint64_t seed, uint64_t elem_offset, uint32_t tag, int B, int L, int C,
                            float* eps_out, void* work, hipStream_t s);
 
+// Log-likelihoods through the probability-flow ODE (ffd_loglik.hip; include/ffd.h ffd_loglik_tail).  One divergence
+// evaluation: launch_loglik_perturb writes the stacked batch of (1 + 2 k) B rows, the caller evaluates the score there,
+// launch_loglik_tail reduces the probes' terms per sample, updates the state from block 0's score and accumulates
+// delta (LL_EULER, LL_CORRECT) or keeps v1 (LL_PREDICT).  Probes: injected (k, B, L, C), or Rademacher draws under tags
+// tag0 + m at global element elem_offset + i.  dt: the interval's width in double (the state moves by (float)dt).
+enum LoglikStage { LL_EULER = 0, LL_PREDICT = 1, LL_CORRECT = 2 };  // = FFD_LOGLIK_*
+struct LoglikProbes {
+  const float* inject;
+  uint64_t seed, elem_offset;
+  uint32_t tag0;
+  int k;
+};
+double loglik_sigma(int sde, double a, double b, double t);  // the marginal's standard deviation without G, in double
+bool loglik_shape_supported(int n_probes, int B, int L, int C);  // (1 + 2 k) B L C < 2^31
+hipError_t launch_loglik_perturb(const float* x, float* stack, const float* G, float h, LoglikProbes pr, int B, int L, int C,
+                                 hipStream_t s);
+hipError_t launch_loglik_tail(int stage, int sde, double a, double b, double t, double dt, float h, float* x, float* xp,
+                              float* d1, const float* score, const float* G, LoglikProbes pr, double* delta, double* v1,
+                              double* v_out, int B, int L, int C, hipStream_t s);
+hipError_t launch_prior_logp(const float* x, const float* G, float scale, double* out, int B, int L, int C, hipStream_t s);
+
 // Conditional sampling by replacement (include/ffd.h ffd_cond_project).  cond_coeffs: the marginal's (mc, sigma) at t in
 // double, rounded once (noiseless: 1, 0).  launch_cond_project: the frequency-domain projection (ffd_fft.hip), one launch;
 // hipErrorInvalidValue for a length outside cond_len_supported.  launch_cond_time: the pointwise one (ffd_elem.hip).

@@ -35,6 +35,16 @@ __device__ __forceinline__ void st(float* p, size_t i, const float (&a)[W]) {
   else p[i] = a[0];
 }
 
+// The probability-flow ODE's drift d(x, t) = f(x, t) - 1/2 (g(t) G_l)^2 s of one element (include/ffd.h ffd_ode_step),
+// every product / sum its own fp32 rounding: the sampling tails (ffd_elem.hip) and the likelihood tail (ffd_loglik.hip)
+__device__ __forceinline__ float ode_drift(float xi, float sc, float Gl, const SdeParams& p) {
+  const float g = __fmul_rn(p.cs, Gl);
+  const float g2 = __fmul_rn(g, g);
+  const float gs = __fmul_rn(g2, sc);
+  const float hgs = __fmul_rn(0.5f, gs);
+  return (p.sde == 0) ? __fsub_rn(__fmul_rn(p.a, xi), hgs) : -hgs;
+}
+
 // C % 4 == 0, 16-byte aligned arrays, elem_offset % 4 == 0: one float4 per array, thread and iteration; the four
 // elements share their row, so G[l] is one load, and their draws are one Philox block.
 template <class Op>

@@ -115,6 +115,24 @@ class SDE(abc.ABC):
     def _prior_scale(self) -> float:
         return 1.0
 
+    def prior_logp(self, x: torch.Tensor) -> torch.Tensor:
+        """log-density of ``x`` (B, L, C) under the distribution ``prior_sampling`` draws from (extension):
+        sum over (l, c) of log N(x; 0, (sigma_p G_l)^2), sigma_p = 1 (VP) or ``sigma_max`` (VE).  fp32 terms summed in
+        float64 in a fixed order (``ffd_prior_logp``); returns a (B,) float64 tensor on ``x``'s device."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 3:
+            raise ValueError(f"x must be a (B, L, C) tensor, got {tuple(getattr(x, 'shape', ()))}")
+        B, L, Cn = x.shape
+        if self.G is None or self.G.numel() != L:
+            raise ValueError(f"x has length {L}, but the noise scaling is set for "
+                             f"{None if self.G is None else self.G.numel()}: call set_noise_scaling({L}) first")
+        x = N.require_gpu_tensor(x, "x")
+        out = torch.empty(B, device=x.device, dtype=torch.float64)
+        desc = self._desc()
+        rc = N.lib().ffd_prior_logp(C.byref(desc), x.data_ptr(), self._G_on(x.device).data_ptr(), out.data_ptr(), B, L, Cn,
+                                    N.current_stream_ptr(x.device))
+        N.check(rc, None, "ffd_prior_logp")
+        return out
+
     def step(self, model_output: torch.Tensor, timestep: float, sample: torch.Tensor,
              noise: Optional[torch.Tensor] = None) -> SamplingOutput:
         """sde.py:129-165 / 215-246.  ``noise`` (extension) injects z; by default

@@ -381,6 +381,61 @@ int ffd_mixture_tiling(int* row_tile, int* comp_tile, int* slice, int* max_dim);
 int ffd_prior(const ffd_sde_desc* sde, float* x, const float* z, const float* G, uint64_t seed,
               uint64_t sample_offset, int B, int L, int C, void* stream);
 
+/* ---- log-likelihoods through the probability-flow ODE (an extension: Song et al. 2021, section 4.3 / appendix D.2) ----
+ * Forward SDE and drift as in ffd_sde_step / ffd_ode_step: d(x,t) = a(t) x - 1/2 (cs(t) G_l)^2 s(x,t), a = -beta(t)/2 (VP)
+ * or 0 (VE).  Along the ODE's solution from eps up to T = 1, by the instantaneous change of variables,
+ *     log p_eps(x(eps)) = log p_T(x(1)) + integral of v dt,      v(x,t) = a(t) L C - 1/2 cs(t)^2 tr(diag(G^2) ds/dx).
+ * No gradient of the network exists: the trace is estimated by Hutchinson probes with a central finite difference of the
+ * score.  With probes eps_1 .. eps_k of shape (B, L, C), w_m = G_l eps_m, h = fd_rel sigma(t) (sigma: the marginal's
+ * standard deviation without G, as in ffd_cond_project),
+ *     tr ~ (1/k) sum_m sum_lc w_m (s(x + h w_m, t) - s(x - h w_m, t)) / (2 h),
+ * which uses tr(G^2 J) = E[(G eps)^T J (G eps)]: the perturbation has the SDE's own noise covariance.  eps_j = sqrt(D) e_j
+ * with k = D = L C makes the sum the exact trace (of the finite difference).
+ * One divergence evaluation is ffd_loglik_perturb, the caller's score evaluation at the stacked batch, ffd_loglik_tail.
+ * Rounding contract.  Per element, each product / sum its own fp32 rounding (no FMA contraction):
+ *     w = G_l eps, hw = h w, x+ = x + hw, x- = x - hw;        diff = s+ - s-, term = w diff.
+ * A sample's terms are added in fp64 in an order fixed by the probe index m and the element index i = l C + c alone:
+ * partial p (0 .. 255) adds, for m ascending, the terms of elements p, p + 256, ... in ascending order, then the 256
+ * partials go through a pairwise tree that folds the upper half onto the lower (128, 64, ... 1).  No atomics: bit-
+ * identical from run to run, independent of B and of the sample's place in the batch.  In fp64, with a(t), cs(t) the
+ * DOUBLE values ffd_ode_step rounds to fp32 and h the fp32 step widened:
+ *     tr = sum / ((2 h) k),    v = a(t) (L C) + (-1/2 cs(t)^2) tr.
+ * The state moves with ffd_ode_step's per-element rounding and the sign of an UPWARD step of width dt (fp32: (float)dt):
+ *     FFD_LOGLIK_EULER    x <- x + d dt;                                   delta[b] <- delta[b] + dt v
+ *     FFD_LOGLIK_PREDICT  drift <- d1 = d(x,t), x_pred <- x + d1 dt;       v1[b] <- v              (x, delta untouched)
+ *     FFD_LOGLIK_CORRECT  (score_stack: at x_pred and t = the interval's end)
+ *                         x <- x + (1/2 (d1 + d(x_pred,t))) dt;            delta[b] <- delta[b] + (dt / 2) (v1[b] + v)
+ * delta, v1, v_out: (B) doubles on the device; dt in double for delta.  The drift reads block 0 of the score stack.
+ * Probes.  `probes` (n_probes, B, L, C): injected, any finite values.  NULL: Rademacher draws from the Philox plan of
+ * ffd_sde_step -- the word of global element g = (sample_offset + b) L C + i is slot g & 3 of block g >> 2 under (seed,
+ * tag0 + m) for probe m; eps = +1 if bit 31 of the word is clear, else -1.  The tail REGENERATES what the perturbation
+ * drew, so no probe buffer exists.  ffd_loglik_batch uses tag0 = 0xF0000000 + e n_probes for divergence evaluation e
+ * (Euler: e = j for interval j; Heun: e = 2 j at the interval's start, 2 j + 1 at its end); the largest e n_probes + m of a
+ * run must stay below 0x0FFFFFF0, which keeps the family clear of the reserved 0xFFFFFFFD .. 0xFFFFFFFF.  The family
+ * 0xF0000000 .. overlaps the transition family 0xE0000000 + q of ffd_sample_batch_resample from q = 2^28 on: the two
+ * entries never draw in one run (a likelihood draws probes only, a resampled run no probes), so no draw is shared.
+ * Stacked batch: block 0 = x, block 2 m - 1 = x + h w_m, block 2 m = x - h w_m for m = 1 .. n_probes, (1 + 2 n_probes) B
+ * rows of (L, C).
+ * ffd_prior_logp: logp_out[b] = sum_lc log N(x; 0, (sigma_p G_l)^2), sigma_p = 1 (VP) or sigma_max (VE): the density
+ * ffd_prior draws from.  Per element sg = sigma_p G_l, q = x / sg, term = (-0.5 (q q)) - (float)(log sg + log(2 pi) / 2),
+ * each its own fp32 rounding (the logarithm in fp64, rounded once); the sum in fp64 in the order above (one "probe").
+ * ffd_host_loglik_h: host only; *h_out = (float)(fd_rel sigma(t)) with sigma in double.
+ * All three device operators: context-free, stream ordered, no host synchronisation, one launch each (one workgroup per
+ * sample in the tail and the prior).  FFD_ERR_INVALID before any device work: a null pointer (probes, v_out and the
+ * buffers a stage does not use excepted), B, L, C < 1, n_probes < 1, h, fd_rel or dt that is <= 0 or non-finite, a
+ * negative or non-finite t, an unknown stage or SDE, a written buffer that shares an address with another buffer of the
+ * call; then FFD_ERR_UNSUPPORTED for (1 + 2 n_probes) B L C >= 2^31. */
+enum { FFD_LOGLIK_EULER = 0, FFD_LOGLIK_PREDICT = 1, FFD_LOGLIK_CORRECT = 2 };
+int ffd_host_loglik_h(const ffd_sde_desc* sde, double t, double fd_rel, float* h_out);
+int ffd_prior_logp(const ffd_sde_desc* sde, const float* x, const float* G, double* logp_out, int B, int L, int C,
+                   void* stream);
+int ffd_loglik_perturb(const float* x, const float* G, float h, int n_probes, const float* probes, uint64_t seed,
+                       uint64_t sample_offset, uint32_t tag0, float* stack_out, int B, int L, int C, void* stream);
+int ffd_loglik_tail(const ffd_sde_desc* sde, int stage, float* x, float* x_pred, float* drift, const float* score_stack,
+                    const float* G, double t, double dt, float h, int n_probes, const float* probes, uint64_t seed,
+                    uint64_t sample_offset, uint32_t tag0, double* delta, double* v1, double* v_out, int B, int L, int C,
+                    void* stream);
+
 /* ---- Supported transform lengths ----
  * Every Fourier entry point keeps a sample's slab and the twiddle table in one workgroup's 160 KiB of LDS, which
  * sets the lengths it takes:
@@ -723,6 +778,35 @@ enum { FFD_SOLVER_EULER_MARUYAMA = 0, FFD_SOLVER_ODE_EULER = 1, FFD_SOLVER_ODE_H
 enum { FFD_SOLVER_ODE_AB2 = 4, FFD_SOLVER_DPMPP_2M = 5 }; /* (3 is FFD_SOLVER_PC) */
 int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, int n_steps, float step_size,
                          int first_step, int n_run, int solver, int use_cache, int global_step0, void* stream);
+
+/* The log-likelihood loop (see ffd_loglik_tail): the probability-flow ODE integrated the OTHER way, from eps up to 1,
+ * with the divergence of its drift accumulated.  x (B,L,C) holds the series in the diffused domain at eps and is advanced
+ * in place (after the grid's last interval it is the latent x_T); delta (B doubles, device) is ACCUMULATED, not zeroed,
+ * so a trajectory can be split over calls at any interval boundary (the bits of one call).  log p(x) = ffd_prior_logp(x_T)
+ * + delta.  The scheduler's descending fp32 grid timesteps[0..n_steps) is walked from its last point to its first:
+ * interval j runs from timesteps[n_steps-1-j] to timesteps[n_steps-2-j]; its width is the difference of the two fp32
+ * values formed in double (no scalar step_size: a non-uniform grid works).  This call runs intervals [first_interval,
+ * first_interval + n_run), first_interval + n_run <= n_steps - 1, n_steps >= 2.
+ *   solver        FFD_SOLVER_ODE_EULER (one divergence evaluation per interval) or FFD_SOLVER_ODE_HEUN (two, on the
+ *                 augmented state (x, delta); v1 per sample in double) only;
+ *   n_probes      k >= 1; every evaluation is ONE score evaluation at the stacked batch of (1 + 2 k) B rows, which must
+ *                 pass the context's batch limits;  fd_rel: h = fd_rel sigma(t) per evaluation (ffd_host_loglik_h);
+ *   probe_inject  NULL: fresh Rademacher draws per evaluation under (seed, sample_offset) and the tag plan above -- on a
+ *                 fixed grid independent errors average out -- or one (n_probes, B, L, C) slab set per evaluation, flat, in
+ *                 consumption order, starting at first_interval.
+ * Every backbone.  No fused tail: the tail reads the stacked score from HBM (one pass over (rows, L, C) per evaluation,
+ * far less than the forward it follows).  The perturbation and tail launches are timed under FFD_K_SDE; the tail that
+ * ffd_kernel_work names is left as the last sampling loop set it.
+ * FFD_ERR_INVALID before any device work: the shared cases (a null pointer, B < 1, a range outside the grid), n_probes
+ * < 1, a solver outside the two, fd_rel <= 0 or non-finite, times of the run that are not finite, >= 0 and strictly
+ * decreasing, a run whose largest e n_probes + m reaches 0x0FFFFFF0; FFD_ERR_UNSUPPORTED: (1 + 2 k) B L C >= 2^31 or a
+ * stacked batch over the context's limit; FFD_ERR_STATE: FreSca on (a rescaled score is not the model's ODE; call
+ * ffd_fresca_disable).  There is no cache argument, as for ffd_sample_batch_resample: the E2-CRF gate and tables assume
+ * that time only falls, every evaluation here is the uncached forward, and the context's cache state -- enabled or not --
+ * is left untouched. */
+int ffd_loglik_batch(ffd_ctx* ctx, float* x, double* delta, int B, const float* timesteps, int n_steps, int first_interval,
+                     int n_run, int solver, int n_probes, double fd_rel, const float* probe_inject, uint64_t seed,
+                     uint64_t sample_offset, void* stream);
 
 /* Predictor-corrector sampling (see ffd_langevin_step): ffd_sample_batch with n_corrector Langevin corrector steps in
  * front of every Euler-Maruyama step, in score_sde's order.  Reverse step i:
