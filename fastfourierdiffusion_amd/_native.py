@@ -67,6 +67,12 @@ class CacheStats(C.Structure):
                 ("table_allocated", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AdamWCfg(C.Structure):
+    """ffd_adamw_cfg: one AdamW step's scalars (step counts from 1)."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("max_norm", C.c_double), ("step", C.c_longlong)]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 # how every ffd_sample_batch* entry begins: ctx, x, B, timesteps, n_steps, step_size, first, n_run
@@ -106,6 +112,30 @@ SIGNATURES = {
     "ffd_sm_perturb": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_sm_loss": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_sm_eval_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "ffd_dense_dgrad": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_dense_wgrad_chunks": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "ffd_dense_wgrad_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ffd_dense_wgrad": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "ffd_sm_loss_grad": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
+                                   _P]),
+    "ffd_sm_draw_times_at": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.c_uint64, C.c_uint64, _P]),
+    "ffd_layernorm_stats_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P]),
+    "ffd_layernorm_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "ffd_attention_lse_fwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_attention_bwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ffd_adamw": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.POINTER(AdamWCfg), _P]),
+    "ffd_host_lr_schedule": (C.c_double, [C.c_double, C.c_longlong, C.c_longlong, C.c_longlong]),
+    "ffd_train_create": (C.c_int, [C.POINTER(_P), C.POINTER(ModelDesc), C.c_double, C.c_int]),
+    "ffd_train_destroy": (None, [_P]),
+    "ffd_train_last_error": (C.c_char_p, [_P]),
+    "ffd_train_work_bytes": (C.c_size_t, [C.POINTER(ModelDesc), C.c_int]),
+    "ffd_train_bind": (C.c_int, [_P, C.c_char_p, _P, _P, _P, _P, C.c_size_t]),
+    "ffd_train_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "ffd_train_loss_grad": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, C.c_int, _P]),
+    "ffd_train_grad_sqnorm": (C.c_int, [_P, _P, _P]),
+    "ffd_train_adamw": (C.c_int, [_P, _P, C.POINTER(AdamWCfg), _P]),
+    "ffd_train_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, C.c_int,
+                                 C.POINTER(AdamWCfg), _P]),
     "ffd_cache_crf_capture": (C.c_int, [_P, C.POINTER(CrfCaptureCfg)]),
     "ffd_create": (C.c_int, [C.POINTER(_P), C.POINTER(ModelDesc), C.c_int]),
     "ffd_destroy": (None, [_P]),

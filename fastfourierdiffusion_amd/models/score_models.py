@@ -11,8 +11,9 @@ initialisation, so reference checkpoints load and equal seeds give equal weights
 The torch modules only *hold* parameters.  ``forward`` hands raw device pointers to
 libffd (include/ffd.h), whose HIP kernels evaluate the network; nothing here calls a
 torch operator on activations, and a tensor that is not on a gfx950 device raises.
-``validation_step`` evaluates the denoising score-matching loss forward-only (utils/losses.py); the training
-hooks (training_step, configure_optimizers) are out of scope: there is no backward pass.
+``validation_step`` evaluates the denoising score-matching loss forward-only (utils/losses.py).  ``training_step``
+fills the parameters' ``.grad`` through libffd's backward pass (training.py) where one exists: the transformer and the
+MLP backbone; the LSTM and the mixture raise ``NotImplementedError``.
 """
 from __future__ import annotations
 
@@ -215,8 +216,8 @@ class ScoreModule(nn.Module):
 
     # ------------------------------------------------------------------
     def set_loss_fn(self):
-        """score_models.py:326-351: (training_loss_fn, validation_loss_fn).  The training loss is None -- training is
-        out of scope (get_sde_loss_fn(train=True) raises)."""
+        """score_models.py:326-351: (training_loss_fn, validation_loss_fn).  The training loss is None: training goes
+        through ``training_step`` / ``training.Trainer``, not through a closure (get_sde_loss_fn(train=True) raises)."""
         return None, get_sde_loss_fn(scheduler=self.noise_scheduler, train=False,
                                      likelihood_weighting=self.likelihood_weighting)
 
@@ -224,6 +225,23 @@ class ScoreModule(nn.Module):
         """score_models.py:304-316.  Returns the loss (a 0-dim device tensor); the reference logs it as ``val/loss``
         through Lightning and returns None -- there is no logger here."""
         return self.validation_loss_fn(self, batch)
+
+    def training_step(self, batch: DiffusableBatch, batch_idx: int) -> torch.Tensor:
+        """score_models.py:290-302 minus the logging: returns the loss (a 0-dim device tensor) and leaves its gradient in
+        the parameters' ``.grad``; no optimizer runs.  The module keeps one ``training.Trainer(seed=0)`` for this hook.
+        Times (when ``batch.timesteps`` is None) and noise are on-device Philox draws keyed by a count of the calls made
+        so far, not by ``batch_idx`` (which restarts at 0 every epoch and would repeat the draws).  For a whole training
+        run with its own seed, schedule and checkpoints use ``Trainer`` directly.  Backbones without a backward pass raise
+        ``NotImplementedError``."""
+        from ..training import Trainer
+
+        tr = getattr(self, "_trainer", None)
+        if tr is None or tr.model is not self:
+            tr = Trainer(self)
+            object.__setattr__(self, "_trainer", tr)
+        loss = tr.loss_and_grad(batch.X, timesteps=batch.timesteps)
+        tr.global_step += 1  # the next call's draw key
+        return loss
 
     # ------------------------------------------------------------------
     def enable_caching(self, cache: Optional[E2CRFCache] = None, **cache_kwargs) -> None:

@@ -3,8 +3,8 @@
 ``get_sde_loss_fn`` has the reference's signature (src/fdiff/utils/losses.py:12-17) and its evaluation behaviour
 (losses.py:39-125): the perturbation, the score network and the weighted squared-error reduction are one stream-ordered
 ``ffd_sm_eval_batch`` call (csrc/ffd_loss.hip + the forward pass), and the batch mean is ``ffd_w2_summary``.  The only
-torch arithmetic is the scheduler's ``marginal_coeffs`` on the (B,) timesteps.  ``train=True`` is refused: libffd has no
-backward pass.
+torch arithmetic is the scheduler's ``marginal_coeffs`` on the (B,) timesteps.  ``train=True`` is refused: a closure
+cannot own optimizer state, and the training surface is ``training.Trainer``.
 
 ``evaluate_loss`` runs a whole data set through the same entry point in batches without a host synchronisation.
 """
@@ -61,8 +61,9 @@ def get_sde_loss_fn(scheduler: SDE, train: bool, reduce_mean: bool = True, likel
     the kernels from (``seed``, ``sample_offset`` + position in the batch), and no z tensor exists."""
     if train:
         raise NotImplementedError(
-            "get_sde_loss_fn(train=True): training is out of scope -- libffd evaluates the score network forward only "
-            "(there is no backward pass); use train=False for the evaluation loss")
+            "get_sde_loss_fn(train=True): a training loss closure is out of scope -- it could not own the optimizer "
+            "state; train with fastfourierdiffusion_amd.training.Trainer, use train=False for the "
+            "evaluation loss")
     if rng not in ("torch", "philox"):
         raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
 

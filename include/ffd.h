@@ -695,6 +695,119 @@ int ffd_sm_eval_batch(ffd_ctx* ctx, const float* x0, const float* timesteps, con
                       const float* z, uint64_t seed, uint64_t sample_offset, int likelihood_weighting, int reduce_mean,
                       double* per_sample_out, int B, void* stream);
 
+/* ---- training (csrc/ffd_train.hip): backward pass, gradient norm, AdamW -- score_models.py:290-324 without dropout ----
+ * Built for the transformer (FFD_MODEL_TRANSFORMER: head_dim <= 8, max_len <= 512, any d_model, dim_feedforward, C, B)
+ * and the MLP backbone (FFD_MODEL_MLP).  The LSTM has no backpropagation through time and the mixture nothing to train:
+ * ffd_train_create answers FFD_ERR_UNSUPPORTED for them, as for dropout != 0.
+ * The transformer's training forward is a second implementation of the forward from generic pieces (launch_dense, the
+ * LayerNorm and attention operators below) that keeps, per layer: the layer input, qkv, the attention output before the
+ * out-projection, the normalised LN1 rows, the LN1 output, both LayerNorms' rstd, the post-ReLU hidden activation and each
+ * attention row's log-sum-exp.  Its positional table is nn.Embedding(max_norm = sqrt(d_model)): every batch call first
+ * renormalises the bound PARAMETER's rows in place (k_renorm_rows, as torch's lookup does without gradient), and the
+ * table's gradient sum_b dh0[b, l, :] is taken with respect to the renormalised rows.  The time encoder's dense layer
+ * gets dtemb[b, :] = sum_l dh0[b, l, :] against the sin / cos features; time_encoder.W is frozen.
+ * Everything is exact fp32 on v_mfma_f32_16x16x4_f32, stream ordered, without atomics and, once the object's
+ * workspace and tensor table exist (below), without a host synchronisation; every reduction is a fixed-order tree (fp64 where it adds many fp32 terms): results are bit-identical
+ * from run to run.  All argument errors are returned before any device work. */
+
+/* Dense backward, row-major fp32, any M, N, K >= 1 (FFD_ERR_UNSUPPORTED when M N, M K or N K reaches 2^31, or N or K
+ * exceeds 65 535 * 64):
+ *   dgrad  dX[M,K] = mask(dY[M,N] . W[N,K]) + R    act (M, K) or NULL: the saved post-ReLU activation, dX = 0 where it
+ *                                                  is not positive;  R (M, K) or NULL is added after the mask
+ *   wgrad  dW[N,K] = dY^T . X[M,K];  db[N] (or NULL) = the column sums of dY in fp64
+ * wgrad cuts M into the chunks the query below counts -- a function of the shape alone: at most 1024 rows each, finer
+ * (down to 64 rows) where N x K has few 64 x 64 tiles, at most 64 chunks -- runs them as independent workgroups and adds
+ * their partial results in chunk order in fp64.  `work` holds the partials: the bytes the query gives (0 for one chunk),
+ * 8-byte aligned. */
+int ffd_dense_dgrad(const float* dY, const float* W, const float* act, const float* R, float* dX, int M, int N, int K,
+                    void* stream);
+int ffd_dense_wgrad_chunks(int M, int N, int K);
+size_t ffd_dense_wgrad_work_bytes(int M, int N, int K);
+int ffd_dense_wgrad(const float* dY, const float* X, float* dW, float* db, int M, int N, int K, void* work,
+                    size_t work_bytes, void* stream);
+
+/* The per-sample losses of ffd_sm_loss (reduce_mean = 1, the same bits) together with the gradient of their batch mean:
+ *   default:               dscore = 2 w[b] r / (L C B)          likelihood_weighting:  dscore = 2 std[b,l]^2 r / (L C B)
+ * z == NULL regenerates the draws of the perturbation under the same stream tag 0xFFFFFFFE, counted by the global sample
+ * sample_offset + (index ? index[b] : b); index: (B) int64 on the device or NULL.  score, sigma, z, dscore: batch order. */
+int ffd_sm_loss_grad(const float* score, const float* sigma, const float* G, const float* z, uint64_t seed,
+                     uint64_t sample_offset, const int64_t* index, int likelihood_weighting, double* per_sample_out,
+                     float* dscore, int B, int L, int C, void* stream);
+
+/* The rows index[b] of ffd_sm_draw_times: t_out[b] = the draw of global sample sample_offset + index[b] (index: (B) int64
+ * on the device), so a shuffled batch draws B times, not the data set's. */
+int ffd_sm_draw_times_at(float* t_out, const int64_t* index, int B, double eps, double T, uint64_t seed,
+                         uint64_t sample_offset, void* stream);
+
+/* Operators of the transformer's training forward and backward, callable on their own.  LayerNorm over the last dimension of x (M, D), biased variance: the forward also stores the
+ * normalised rows xhat (M, D) and every row's reciprocal deviation rstd (M); the backward takes them,
+ *   dx = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma;  dgamma = sum_m dy xhat, dbeta = sum_m dy (fp64, fixed order).
+ * Attention for head_dim <= 8 and L <= 512 (FFD_ERR_UNSUPPORTED beyond) on the in-projection's row-major output
+ * qkv (B L, 3 H hd) = q | k | v with head h at columns h hd of each third: out (B L, H hd) = softmax(q k^T / sqrt(hd)) v
+ * and lse (B, H, L), each row's log-sum-exp of the scaled scores; the backward recomputes the probabilities from lse and
+ * writes dqkv (B L, 3 H hd), every element once (nothing accumulates across workgroups). */
+int ffd_layernorm_stats_fwd(const float* x, const float* gamma, const float* beta, float* y, float* xhat, float* rstd,
+                            int M, int D, double eps, void* stream);
+int ffd_layernorm_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, float* dx, float* dgamma,
+                      float* dbeta, int M, int D, void* stream);
+int ffd_attention_lse_fwd(const float* qkv, float* out, float* lse, int B, int L, int H, int hd, void* stream);
+int ffd_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int B, int L,
+                      int H, int hd, void* stream);
+
+/* torch.optim.AdamW's arithmetic in its order (decoupled decay, moments, bias corrections, update) at step >= 1 (the
+ * count including this step), on the gradient times the clip coefficient min(1, max_norm / (sqrt(*sqnorm) + 1e-6))
+ * (torch.nn.utils.clip_grad_norm_).  sqnorm: one double on the device, read by the kernel; NULL or max_norm <= 0: no
+ * clipping.  The gradient buffer is not modified (it keeps the unclipped gradient). */
+typedef struct {
+  double lr, beta1, beta2, eps, weight_decay, max_norm;
+  long long step;
+} ffd_adamw_cfg;
+int ffd_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, const double* sqnorm,
+              const ffd_adamw_cfg* cfg, void* stream);
+
+/* The learning rate at `step` (host only): lr_max step / max(1, warm-up) below the warm-up, then
+ * lr_max max(0, (1 + cos(pi progress)) / 2), progress = (step - warm-up) / max(1, total - warm-up). */
+double ffd_host_lr_schedule(double lr_max, long long step, long long num_warmup_steps, long long num_training_steps);
+
+/* The training object.  Separate from ffd_ctx (which keeps packed copies of the weights): it works on the caller's
+ * tensors in place -- ffd_train_bind gives the device pointers of one named parameter (the state_dict key), its
+ * gradient and the two Adam moments, n elements each; no second set of weights exists.  time_encoder.W is frozen
+ * (requires_grad=False): its gradient and moments are ignored and may be NULL.  FFD_ERR_STATE: a call that needs a
+ * tensor that is not bound.  ffd_train_create returns the object even on failure so that the message can be read
+ * (ffd_train_last_error); FFD_ERR_HIP without a device, after the descriptor's own errors.
+ * The workspace (activations kept for the backward, gradients of activations, wgrad partials) belongs to the object and
+ * grows with B; its size is the query's.  The first batch call at a larger B than any before reallocates it, and the
+ * first call after a bind rebuilds the tensor table: both synchronise with the device once (hipDeviceSynchronize,
+ * hipFree, hipMalloc, one blocking copy).  Every other call only enqueues. */
+typedef struct ffd_train ffd_train;
+int ffd_train_create(ffd_train** out, const ffd_model_desc* desc, double dropout, int device);
+void ffd_train_destroy(ffd_train* tr);
+const char* ffd_train_last_error(const ffd_train* tr);
+size_t ffd_train_work_bytes(const ffd_model_desc* desc, int B);
+int ffd_train_bind(ffd_train* tr, const char* name, float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n);
+/* The training forward (it keeps what the backward needs) at x (B, L, C) and the per-sample times: a second
+ * implementation of ffd_score_forward_ts on the bound parameters, for tests. */
+int ffd_train_forward(ffd_train* tr, const float* x, const float* timesteps, float* score_out, int B, void* stream);
+/* Forward + backward for one batch: perturbation, training forward, per-sample losses (B doubles, as ffd_sm_eval_batch
+ * with reduce_mean = 1) and the gradient of their mean into every bound gradient buffer (overwritten, not accumulated).
+ * timesteps, mean_coeff, sigma: (B), in batch order.  index == NULL: x0 is (B, L, C) and sample b draws as global sample
+ * sample_offset + b.  index (B) int64 on the device: x0 is the DATA SET and sample b is its row index[b], drawing as
+ * global sample sample_offset + index[b] -- a row's noise does not depend on the batch it is in, and a shuffled batch
+ * needs no gather (its times: ffd_sm_draw_times_at).  Every index must lie within the data set's rows (the caller's
+ * contract, like a buffer's length: it is not checked on the device).  z (B, L, C) or NULL is in batch order. */
+int ffd_train_loss_grad(ffd_train* tr, const float* x0, const int64_t* index, const float* timesteps,
+                        const float* mean_coeff, const float* sigma, const float* z, uint64_t seed, uint64_t sample_offset,
+                        int likelihood_weighting, double* per_sample_out, int B, void* stream);
+/* The squared 2-norm of all bound gradients: one double on the device (two fixed-order fp64 trees). */
+int ffd_train_grad_sqnorm(ffd_train* tr, double* sqnorm_out, void* stream);
+/* AdamW on every bound trainable tensor in one launch (the arithmetic of ffd_adamw). */
+int ffd_train_adamw(ffd_train* tr, const double* sqnorm, const ffd_adamw_cfg* cfg, void* stream);
+/* A whole training step: the three calls above in order, the norm kept in the object.  The same bits as the calls made
+ * separately. */
+int ffd_train_step(ffd_train* tr, const float* x0, const int64_t* index, const float* timesteps, const float* mean_coeff,
+                   const float* sigma, const float* z, uint64_t seed, uint64_t sample_offset, int likelihood_weighting,
+                   double* per_sample_out, int B, const ffd_adamw_cfg* cfg, void* stream);
+
 /* CRF capture inside ffd_sample_batch (the reference's cache.update_crf call, sampler.py:70-73):
  * on cached steps whose global step g satisfies g % every == 0 the (NL, L, d) CRF (score_models.py:181-194)
  * is written to ring slot (g / every) % n_slots; `last` receives the CRF of the last step of each
