@@ -212,6 +212,8 @@ SIGNATURES = {
     "ffd_kernel_timing_begin": (C.c_int, [_P, C.c_uint32, C.c_int]),
     "ffd_kernel_timing_end": (C.c_int, [_P]),
     "ffd_kernel_timing_get": (C.c_int, [_P, C.c_int, _F, C.POINTER(C.c_int)]),
+    "ffd_host_cu_masks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    "ffd_partition_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "ffd_kernel_work": (C.c_char_p, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ffd_score_forward_ts": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "ffd_cache_configure": (C.c_int, [_P, C.POINTER(CacheCfg)]),

@@ -121,6 +121,12 @@ struct ffd_ctx {
   Grow<float> lv_work;  // the Langevin corrector's row squares, norms and step sizes (ffd_sample_batch_pc)
   Grow<float> ll_stack, ll_v1;  // ffd_loglik_batch: the stacked batch of (1 + 2 k) B rows; Heun's v1 (B doubles)
   int tail_solver = FFD_SOLVER_EULER_MARUYAMA;  // the loop entry that ran last (ffd_kernel_work names its FFD_K_SDE tail)
+  // CU partitions (ffd_tune "partitions"; run_partitioned): two streams confined to disjoint halves of the CUs, one fork
+  // event and a join event per half, made on first use
+  hipStream_t part_stream[2] = {nullptr, nullptr};
+  hipEvent_t part_fork = nullptr, part_join[2] = {nullptr, nullptr};
+  int part_budget = 0;  // CUs per partition; 0: not made yet, -1: this device's CUs cannot be halved that way
+  int last_parts = 1;   // partitions the last sampling loop ran as (ffd_partition_status)
   // cache
   bool cache_enabled = false;
   ffd_cache_cfg ccfg{5, 10};
@@ -467,6 +473,25 @@ int ffd_host_attn_score_bound(const float* in_w, const float* in_b, const float*
 // ---------------------------------------------------------------------------
 // Every parameter of the state dict, in the order ffd_finalize_weights reports a missing one, bound to the field the
 // launch sites read.  The one place that spells the keys.  (Runs before ffd_create has checked the shape.)
+int ffd_host_cu_masks(int n_cus, int n_xcds, int layout, int parts, uint32_t* masks_out) {
+  if (!masks_out || n_cus < 1 || n_xcds < 1 || parts < 1 || n_cus % n_xcds != 0) return FFD_ERR_INVALID;
+  const int per_xcd = n_cus / n_xcds, words = (n_cus + 31) / 32;
+  if (layout == FFD_CU_LAYOUT_SPREAD ? per_xcd % parts != 0 : layout == FFD_CU_LAYOUT_XCD ? n_xcds % parts != 0 : true)
+    return FFD_ERR_INVALID;
+  for (int i = 0; i < parts * words; ++i) masks_out[i] = 0u;
+  for (int b = 0; b < n_cus; ++b) {  // mask bit b: CU b / n_xcds of XCD b % n_xcds
+    const int part = layout == FFD_CU_LAYOUT_SPREAD ? (b / n_xcds) / (per_xcd / parts) : (b % n_xcds) / (n_xcds / parts);
+    masks_out[part * words + b / 32] |= 1u << (b % 32);
+  }
+  return FFD_OK;
+}
+
+int ffd_partition_status(const ffd_ctx* ctx, int* parts_out) {
+  if (!ctx || !parts_out) return FFD_ERR_INVALID;
+  *parts_out = ctx->last_parts;
+  return FFD_OK;
+}
+
 static void bind_weights(ffd_ctx* ctx) {
   const ffd_model_desc& m = ctx->desc;
   const int NL = std::max(m.num_layers, 0);
@@ -591,6 +616,11 @@ void ffd_destroy(ffd_ctx* ctx) {
   for (WeightSlot& w : ctx->weights) (void)hipFree(w.dev);
   for (void* p : ctx->owned) (void)hipFree(p);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
+  for (int p = 0; p < 2; ++p) {
+    if (ctx->part_stream[p]) (void)hipStreamDestroy(ctx->part_stream[p]);
+    if (ctx->part_join[p]) (void)hipEventDestroy(ctx->part_join[p]);
+  }
+  if (ctx->part_fork) (void)hipEventDestroy(ctx->part_fork);
   if (ctx->async_err) (void)hipHostFree(ctx->async_err);
   delete ctx;
 }
@@ -1273,7 +1303,114 @@ static int loop_begin(ffd_ctx* ctx, const char* who, const float* x, int B, cons
   if ((rc = ensure_fresca_work(ctx, B))) return rc;
   if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
   ctx->ms_solver = -1;
+  ctx->last_parts = 1;  // (run_partitioned says otherwise once both halves are enqueued)
   return FFD_OK;
+}
+
+// ---- CU partitions: the batch as two halves that run out of phase ----
+// Samples share nothing in the plain Euler-Maruyama loop and in the Euler ODE loop (no cache, no batch statistic, Philox
+// counted by the global sample index), so the loop may run as two half-batches, each on a stream confined to its own half
+// of every XCD's CUs.  A half is today's launch structure on half the chip; only the memory system couples the two, and
+// their load and store bursts no longer fall together.  Ordering is by events alone: a fork on the caller's stream, a
+// join per half back onto it.
+
+constexpr int PART_XCDS = 8;  // MI355X; a device whose CU count does not split this way runs single-stream
+
+// The workspace rows of samples [b0, ...) and a CU budget, for the time the calling thread enqueues that half
+struct PartScope {
+  ffd_ctx* ctx;
+  size_t rows, elems;
+  PartScope(ffd_ctx* c, int b0, int budget)
+      : ctx(c), rows((size_t)b0 * c->desc.max_len * c->desc.d_model), elems((size_t)b0 * c->desc.max_len * c->desc.n_channels) {
+    shift(ctx->h0, rows), shift(ctx->h1, rows), shift(ctx->attn, rows), shift(ctx->score, elems);
+    g_cu_budget = budget;
+  }
+  ~PartScope() {
+    g_cu_budget = 0;
+    shift(ctx->h0, 0 - rows), shift(ctx->h1, 0 - rows), shift(ctx->attn, 0 - rows), shift(ctx->score, 0 - elems);
+  }
+  static void shift(Grow<float>& g, size_t n) { g.p += (ptrdiff_t)n, g.cap -= n; }
+};
+
+static int ensure_partitions(ffd_ctx* ctx) {
+  if (ctx->part_budget) return FFD_OK;
+  ctx->part_budget = -1;
+  hipDeviceProp_t prop;
+  HIPCHECK(hipGetDeviceProperties(&prop, ctx->device));
+  const int n = prop.multiProcessorCount, words = (n + 31) / 32;
+  std::vector<uint32_t> masks(2 * (size_t)words);
+  if (ffd_host_cu_masks(n, PART_XCDS, FFD_CU_LAYOUT_SPREAD, 2, masks.data()) != FFD_OK) return FFD_OK;
+  HIPCHECK(hipEventCreateWithFlags(&ctx->part_fork, hipEventDisableTiming));
+  for (int p = 0; p < 2; ++p) {
+    HIPCHECK(hipExtStreamCreateWithCUMask(&ctx->part_stream[p], (uint32_t)words, masks.data() + (size_t)p * words));
+    HIPCHECK(hipEventCreateWithFlags(&ctx->part_join[p], hipEventDisableTiming));
+  }
+  ctx->part_budget = n / 2;
+  return FFD_OK;
+}
+
+// CUs per half if this loop call runs partitioned, else 0.  The entry must be one whose loop shares nothing across
+// samples (the callers see to that); here: a transformer without cache, FreSca or armed kernel timing, a stream that is
+// not being captured, and both halves planned -- for half the CUs -- to the fused attention and an FFN form that keeps no
+// partial rows in the shared workspace (ffn_part) and makes no packs on first use.  "partitions" = 1 also wants the
+// row-owning FFN with every pass of a half's tiles filling at least 0.9 of its CUs (measured at ECG B = 512 only: 125
+// tiles on 128 CUs per half).  Arguments the entry would refuse make the call ineligible, so the single-stream path
+// reports them.
+static int partition_budget(ffd_ctx* ctx, const float* x, int B, const float* timesteps, int n_steps, int n_run,
+                            float step_size, int use_cache, hipStream_t s) {
+  if (g_partitions == 0 || g_cu_budget > 0 || B < 2 || !x || !timesteps || n_steps < 1 || n_run < 1 || !(step_size > 0.f)) return 0;
+  if (ctx->desc.kind != FFD_MODEL_TRANSFORMER || !ctx->finalized || !ctx->packs_made() || use_cache || ctx->fresca_on ||
+      ctx->time_mask)
+    return 0;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return 0;
+  if (hipSetDevice(ctx->device) != hipSuccess || ensure_partitions(ctx) != FFD_OK || ctx->part_budget <= 0) return 0;
+  const int budget = ctx->part_budget;
+  g_cu_budget = budget;
+  bool ok = true;
+  for (int nb : {(B + 1) / 2, B / 2}) {
+    const LayerPlan p = plan_of(ctx, nb, CACHE_STD);
+    const bool rows = p.ffn == FFN_ROWS_OPROJ || p.ffn == FFN_ROWS;
+    ok = ok && p.attn == ATTN_FUSED && p.part_floats == 0 && p.ffn != FFN_SPLIT;
+    if (ok && g_partitions == 1) {
+      const int last = rows ? cdiv(nb * ctx->desc.max_len, 32 * p.nw) % budget : -1;
+      ok = last == 0 || 10 * last >= 9 * budget;
+    }
+  }
+  g_cu_budget = 0;
+  return ok ? budget : 0;
+}
+
+// run(b0, nb, first, count, stream): `count` iterations from `first` of the entry's own loop on samples [b0, b0 + nb) with
+// their global offsets.  Everything a loop does on first use (workspace growth, the time table and its one
+// synchronisation) happens here for the whole batch, on the caller's stream, before the fork; a half then finds it done.
+// The halves are enqueued PART_CHUNK iterations at a time, in turn: a hardware queue holds a few thousand launches, and
+// the host would otherwise sit in the first half's queue until that half had nearly finished -- the halves then run one
+// after the other (10.1 against 5.1 ms per step at ECG B = 512, 1000 steps per call).  A chunk that fails its checks has
+// enqueued nothing; the chunks behind it are dropped.
+constexpr int PART_CHUNK = 2;
+template <class Run>
+static int run_partitioned(ffd_ctx* ctx, int budget, int B, const float* timesteps, int n_steps, int first, int n_run,
+                           hipStream_t s, Run run) {
+  if (int rc = check_ready(ctx, B)) return rc;
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (int rc = ensure_workspace(ctx, B)) return rc;
+  if (int rc = ensure_time_table(ctx, timesteps, n_steps, s)) return rc;
+  HIPCHECK(hipEventRecord(ctx->part_fork, s));
+  const int nb0 = (B + 1) / 2;
+  int rc = FFD_OK;
+  for (int p = 0; p < 2; ++p) HIPCHECK(hipStreamWaitEvent(ctx->part_stream[p], ctx->part_fork, 0));
+  for (int j = 0; j < n_run && rc == FFD_OK; j += PART_CHUNK)
+    for (int p = 0; p < 2 && rc == FFD_OK; ++p) {
+      PartScope scope(ctx, p ? nb0 : 0, budget);
+      rc = run(p ? nb0 : 0, p ? B - nb0 : nb0, first + j, n_run - j < PART_CHUNK ? n_run - j : PART_CHUNK, ctx->part_stream[p]);
+    }
+  for (int p = 0; p < 2; ++p) {
+    HIPCHECK(hipEventRecord(ctx->part_join[p], ctx->part_stream[p]));
+    HIPCHECK(hipStreamWaitEvent(s, ctx->part_join[p], 0));
+  }
+  if (rc == FFD_OK) ctx->last_parts = 2;
+  return rc;
 }
 extern "C" {
 
@@ -1316,6 +1453,13 @@ int ffd_sample_batch_ode(ffd_ctx* ctx, float* x, int B, const float* timesteps, 
   const ffd_model_desc& m = ctx->desc;
   const int L = m.max_len, C = m.n_channels, d = m.d_model;
   hipStream_t s = (hipStream_t)stream;
+  if (solver == FFD_SOLVER_ODE_EULER)  // (Heun's and the multistep solvers' state buffers stay whole-batch: single-stream)
+    if (const int budget = partition_budget(ctx, x, B, timesteps, n_steps, n_run, step_size, use_cache, s))
+      return run_partitioned(ctx, budget, B, timesteps, n_steps, first_step, n_run, s,
+                             [&](int b0, int nb, int first, int count, hipStream_t ps) {
+        return ffd_sample_batch_ode(ctx, x + (size_t)b0 * L * C, nb, timesteps, n_steps, step_size, first, count, solver,
+                                    use_cache, global_step0 + (first - first_step), ps);
+      });
   std::vector<MultistepParams> ms_coef;
   int rc = loop_begin(ctx, "ffd_sample_batch_ode", x, B, timesteps, n_steps, n_steps > 1 ? n_steps - 1 : 0, first_step,
                       n_run, step_size, use_cache, s, [&]() -> int {
@@ -1592,6 +1736,16 @@ int ffd_sample_batch(ffd_ctx* ctx, float* x, int B, const float* timesteps, int 
                      int first_step, int n_run, uint64_t seed, uint64_t sample_offset, const float* z_inject,
                      int use_cache, int global_step0, void* stream) {
   if (!ctx) return FFD_ERR_INVALID;
+  // plain Euler-Maruyama with device draws: a sample's trajectory depends on its global index alone
+  if (!z_inject)
+    if (const int budget = partition_budget(ctx, x, B, timesteps, n_steps, n_run, step_size, use_cache, (hipStream_t)stream)) {
+      const size_t LC = (size_t)ctx->desc.max_len * ctx->desc.n_channels;
+      return run_partitioned(ctx, budget, B, timesteps, n_steps, first_step, n_run, (hipStream_t)stream,
+                             [&](int b0, int nb, int first, int count, hipStream_t ps) {
+        return sde_loop(ctx, "ffd_sample_batch", x + b0 * LC, nb, timesteps, n_steps, step_size, first, count, 0, 0.f, 0, seed,
+                        sample_offset + (uint64_t)b0, nullptr, use_cache, global_step0 + (first - first_step), nullptr, 1, 1, ps);
+      });
+    }
   return sde_loop(ctx, "ffd_sample_batch", x, B, timesteps, n_steps, step_size, first_step, n_run, 0, 0.f, 0, seed,
                   sample_offset, z_inject, use_cache, global_step0, nullptr, 1, 1, stream);
 }

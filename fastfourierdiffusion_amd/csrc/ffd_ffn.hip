@@ -519,7 +519,9 @@ __global__ __launch_bounds__(256, (MB <= 4 ? 2 : 1)) void k_ffn_ln(const float* 
   }
 }
 
+thread_local int g_cu_budget = 0;
 int num_cus() {
+  if (g_cu_budget > 0) return g_cu_budget;
   static int n = 0;
   if (n == 0) {
     int dev = 0;

@@ -142,6 +142,7 @@ __device__ __forceinline__ double block_sum(double v, double* red) {  // fixed-o
   I("lstm_wave_fault", g_lstm_wave_fault, 0, v >= 0)      /* tests: unit (v - 1) of k_lstm_wave never publishes its progress */ \
   I("lstm_wave_spin_ms", g_lstm_wave_spin_ms, 2000, v >= 1 && v <= 20000)  /* time limit of one wait on a progress word */ \
   B("fuse_tail", g_fuse_tail, 1)                          /* unembed inside the SDE-step kernel of ffd_sample_batch */ \
+  I("partitions", g_partitions, 1, v >= 0 && v <= 2)      /* the batch as two halves on CU-masked streams: 0 never | 1 where a half fills its CUs | 2 wherever eligible */ \
   I("fail_alloc_after", g_fail_alloc_after, 0, v >= 0)    /* tests: the n-th device allocation from now fails with FFD_ERR_NOMEM (0 off) */
 
 #define FFD_KNOB_DECL(key, var, ...) extern thread_local int var;
@@ -405,7 +406,10 @@ bool qkv_attention_supported(int D, int hd);
 int qkv_attention_hpw(int D, int hd, int L);
 int qkv_attention_small_split(int B, int H, int L);
 int attn_qg(int QT, int hd, bool fused);  // q-tiles per wave at QT q-tiles: of k_qkv_attention (fused), else of k_attention_mfma
-int num_cus();  // compute units of the current device (256 on MI355X); ffd_ffn.hip
+int num_cus();  // compute units the calling thread's launches may count on: g_cu_budget, else the current device's (256 on MI355X); ffd_ffn.hip
+// > 0 while the calling thread enqueues one CU partition's half of a batch (ffd_api.hip run_partitioned): the planner, the
+// form pickers and the grids then size themselves for that many CUs
+extern thread_local int g_cu_budget;
 struct AttnArgs {
   const float *x, *pack;    // the layer's input rows; the in-projection pack that (hpw, q_only) name
   const float *kt, *vt;     // the layer's K/V tables to read (cached modes), else nullptr

@@ -141,6 +141,18 @@ int ffd_host_gate(int step, int max_len, int K, int R);
 int ffd_host_attn_score_bound(const float* in_proj_weight, const float* in_proj_bias, const float* ln_weight,
                               const float* ln_bias, int d_model, int head_dim, double q_scale, double* bound_out);
 
+/* CU masks of `parts` stream partitions (hipExtStreamCreateWithCUMask) for a chip of n_cus compute units in n_xcds XCDs.
+ * Mask bit b names CU b / n_xcds of XCD b % n_xcds (measured on MI355X, tools/partition_probe.py: 256 bits, 8 XCDs).
+ *   FFD_CU_LAYOUT_SPREAD  part p owns CUs [p, p + 1) n_cus / (n_xcds parts) of EVERY XCD (the layout the sampling loops use);
+ *   FFD_CU_LAYOUT_XCD     part p owns the whole XCDs [p, p + 1) n_xcds / parts.  The masks are well formed, but the driver
+ *                         runs an XCD's share of a grid on ANY of its CUs when the mask names none of them, so streams made
+ *                         from these masks overlap on the whole chip: kept for the record, not used.
+ * masks_out: parts x ceil(n_cus / 32) words, part-major; the parts' masks are disjoint, cover bits [0, n_cus) and (SPREAD)
+ * hold the same number of CUs of every XCD.  FFD_ERR_INVALID: a null pointer, a count < 1, n_cus not a multiple of n_xcds,
+ * CUs per XCD (SPREAD) or XCDs (XCD) not a multiple of parts, an unknown layout. */
+enum { FFD_CU_LAYOUT_SPREAD = 0, FFD_CU_LAYOUT_XCD = 1 };
+int ffd_host_cu_masks(int n_cus, int n_xcds, int layout, int parts, uint32_t* masks_out);
+
 /* ---- single operators (device pointers, stream ordered) ---------------- */
 
 /* ScoreModule.forward / LSTMScoreModule.forward (score_models.py:79-119, 486-511)
@@ -1002,6 +1014,10 @@ int ffd_sample_batch_resample(ffd_ctx* ctx, float* x, int B, const float* timest
                               uint64_t seed, uint64_t sample_offset, const float* z_inject, const ffd_cond_cfg* cond,
                               void* stream);
 
+/* How the context's last sampling-loop call ran: *parts_out = 2 as two CU partitions (ffd_tune "partitions"), 1 on the
+ * caller's stream alone. */
+int ffd_partition_status(const ffd_ctx* ctx, int* parts_out);
+
 /* Tuning knobs for experiments and for the test suite's kernel variants (results stay within the parity tolerance,
  * only the kernel choice / tiling changes).  PER CALLING THREAD since round 4 (thread_local): a knob set on one thread
  * selects kernels for the launches THAT thread makes and is invisible to every other thread, so two samplers on two
@@ -1059,6 +1075,13 @@ int ffd_sample_batch_resample(ffd_ctx* ctx, float* x, int B, const float* timest
  *                                              workgroup's own q-tiles only (head_dim 6 / 8) | the whole head;
  *   "attn_hpw" = 0 (heuristic) | 1 | 2         heads per workgroup of that kernel;
  *   "attn_qg" = 0 (heuristic) | 1 | 2 | 3      query tiles per wave;
+ *   "partitions" = 1 | 0 | 2                   ffd_sample_batch (device draws) and ffd_sample_batch_ode (FFD_SOLVER_ODE_EULER) on a
+ *                                              transformer without cache / FreSca / armed kernel timing: samples [0, ceil(B/2))
+ *                                              and the rest as two chains on streams confined to disjoint halves of every
+ *                                              XCD's CUs, forked from and joined to the caller's stream by events (same
+ *                                              results bit for bit; every other case runs on the caller's stream).  1: where
+ *                                              both halves take the row-owning FFN and fill their CUs; 2: wherever both
+ *                                              halves take it; 0: never.  ffd_partition_status tells which path ran;
  *   "attn_static_bound" = 1 | 0                layers whose score bound holds from the weights alone (see
  *                                              ffd_host_attn_score_bound) run the fused kernels' instances without the
  *                                              per-launch bound (same results bit for bit) | every layer measures it;
