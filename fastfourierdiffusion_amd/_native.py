@@ -62,6 +62,18 @@ class CacheCfg(C.Structure):
     _fields_ = [("K", C.c_int32), ("R", C.c_int32)]
 
 
+class PartitionHalf(C.Structure):
+    """ffd_partition_half: one plan of ffd_partition_plan (a half for half the CUs, or the whole batch)."""
+    _fields_ = [("nb", C.c_int), ("nw", C.c_int), ("cps", C.c_int), ("mb", C.c_int), ("persist", C.c_int), ("hpw", C.c_int),
+                ("qg", C.c_int), ("kspl", C.c_int), ("ffn_tiles", C.c_int), ("ffn_grid", C.c_int), ("one_per_tile", C.c_int),
+                ("part_floats", C.c_longlong), ("ffn", C.c_char * 64), ("attn", C.c_char * 48)]
+
+
+class PartitionInfo(C.Structure):
+    _fields_ = [("parts", C.c_int), ("cu_budget", C.c_int), ("halves_planned", C.c_int), ("whole_planned", C.c_int),
+                ("half", PartitionHalf * 2), ("whole", PartitionHalf)]
+
+
 class CacheStats(C.Structure):
     _fields_ = [("recompute_count", C.c_int64), ("cache_hit_count", C.c_int64), ("current_step", C.c_int64),
                 ("table_allocated", C.c_int32), ("reserved", C.c_int32)]
@@ -214,6 +226,7 @@ SIGNATURES = {
     "ffd_kernel_timing_get": (C.c_int, [_P, C.c_int, _F, C.POINTER(C.c_int)]),
     "ffd_host_cu_masks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     "ffd_partition_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "ffd_partition_plan": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(PartitionInfo)]),
     "ffd_kernel_work": (C.c_char_p, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ffd_score_forward_ts": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "ffd_cache_configure": (C.c_int, [_P, C.POINTER(CacheCfg)]),

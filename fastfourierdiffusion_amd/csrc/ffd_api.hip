@@ -1316,12 +1316,17 @@ static int loop_begin(ffd_ctx* ctx, const char* who, const float* x, int B, cons
 
 constexpr int PART_XCDS = 8;  // MI355X; a device whose CU count does not split this way runs single-stream
 
-// The workspace rows of samples [b0, ...) and a CU budget, for the time the calling thread enqueues that half
+// The workspace rows of samples [b0, ...) and a CU budget, for the time the calling thread enqueues that half.  The score
+// rows start on the next 16-byte boundary (run_partitioned allocates the PART_SCORE_PAD floats that may take): the launchers
+// pick a kernel by their pointers' alignment (launch_unembed: the MFMA form or, for a score that is not 16-byte aligned,
+// the generic one, which sums in another order), and b0 L C need not be a multiple of 4.
+constexpr size_t PART_SCORE_PAD = 3;
 struct PartScope {
   ffd_ctx* ctx;
   size_t rows, elems;
   PartScope(ffd_ctx* c, int b0, int budget)
-      : ctx(c), rows((size_t)b0 * c->desc.max_len * c->desc.d_model), elems((size_t)b0 * c->desc.max_len * c->desc.n_channels) {
+      : ctx(c), rows((size_t)b0 * c->desc.max_len * c->desc.d_model),
+        elems(((size_t)b0 * c->desc.max_len * c->desc.n_channels + PART_SCORE_PAD) & ~PART_SCORE_PAD) {
     shift(ctx->h0, rows), shift(ctx->h1, rows), shift(ctx->attn, rows), shift(ctx->score, elems);
     g_cu_budget = budget;
   }
@@ -1356,20 +1361,26 @@ static int ensure_partitions(ffd_ctx* ctx) {
 // row-owning FFN with every pass of a half's tiles filling at least 0.9 of its CUs (measured at ECG B = 512 only: 125
 // tiles on 128 CUs per half).  Arguments the entry would refuse make the call ineligible, so the single-stream path
 // reports them.
-static int partition_budget(ffd_ctx* ctx, const float* x, int B, const float* timesteps, int n_steps, int n_run,
-                            float step_size, int use_cache, hipStream_t s) {
-  if (g_partitions == 0 || g_cu_budget > 0 || B < 2 || !x || !timesteps || n_steps < 1 || n_run < 1 || !(step_size > 0.f)) return 0;
+// The decision without the call's own arguments (partition_budget adds them; ffd_partition_plan reports it): budget > 0
+// to run partitioned; planned: half[] holds the two halves' plans for half the CUs, whatever was decided.
+struct PartDecision {
+  int budget;
+  bool planned;
+  LayerPlan half[2];
+};
+static PartDecision partition_decide(ffd_ctx* ctx, int B, int use_cache) {
+  PartDecision d{};
+  if (g_partitions == 0 || g_cu_budget > 0 || B < 2) return d;
   if (ctx->desc.kind != FFD_MODEL_TRANSFORMER || !ctx->finalized || !ctx->packs_made() || use_cache || ctx->fresca_on ||
       ctx->time_mask)
-    return 0;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return 0;
-  if (hipSetDevice(ctx->device) != hipSuccess || ensure_partitions(ctx) != FFD_OK || ctx->part_budget <= 0) return 0;
+    return d;
+  if (hipSetDevice(ctx->device) != hipSuccess || ensure_partitions(ctx) != FFD_OK || ctx->part_budget <= 0) return d;
   const int budget = ctx->part_budget;
   g_cu_budget = budget;
   bool ok = true;
+  int i = 0;
   for (int nb : {(B + 1) / 2, B / 2}) {
-    const LayerPlan p = plan_of(ctx, nb, CACHE_STD);
+    const LayerPlan p = d.half[i++] = plan_of(ctx, nb, CACHE_STD);
     const bool rows = p.ffn == FFN_ROWS_OPROJ || p.ffn == FFN_ROWS;
     ok = ok && p.attn == ATTN_FUSED && p.part_floats == 0 && p.ffn != FFN_SPLIT;
     if (ok && g_partitions == 1) {
@@ -1378,7 +1389,16 @@ static int partition_budget(ffd_ctx* ctx, const float* x, int B, const float* ti
     }
   }
   g_cu_budget = 0;
-  return ok ? budget : 0;
+  d.planned = true;
+  d.budget = ok ? budget : 0;
+  return d;
+}
+static int partition_budget(ffd_ctx* ctx, const float* x, int B, const float* timesteps, int n_steps, int n_run,
+                            float step_size, int use_cache, hipStream_t s) {
+  if (g_partitions == 0 || g_cu_budget > 0 || B < 2 || !x || !timesteps || n_steps < 1 || n_run < 1 || !(step_size > 0.f)) return 0;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return 0;
+  return partition_decide(ctx, B, use_cache).budget;
 }
 
 // run(b0, nb, first, count, stream): `count` iterations from `first` of the entry's own loop on samples [b0, b0 + nb) with
@@ -1394,6 +1414,7 @@ static int run_partitioned(ffd_ctx* ctx, int budget, int B, const float* timeste
                            hipStream_t s, Run run) {
   if (int rc = check_ready(ctx, B)) return rc;
   HIPCHECK(hipSetDevice(ctx->device));
+  if (int rc = ensure(ctx, ctx->score, (size_t)B * ctx->desc.max_len * ctx->desc.n_channels + PART_SCORE_PAD)) return rc;
   if (int rc = ensure_workspace(ctx, B)) return rc;
   if (int rc = ensure_time_table(ctx, timesteps, n_steps, s)) return rc;
   HIPCHECK(hipEventRecord(ctx->part_fork, s));
@@ -1412,7 +1433,63 @@ static int run_partitioned(ffd_ctx* ctx, int budget, int B, const float* timeste
   if (rc == FFD_OK) ctx->last_parts = 2;
   return rc;
 }
+
+// One plan at nb samples as ffd_partition_plan reports it, for the CUs num_cus() names right now: the names
+// ffd_kernel_work gives and the FFN grid the launcher itself computes (RowsArgs::grid_only, ffn_ln_grid)
+static void describe_plan(const ffd_ctx* ctx, const LayerPlan& p, int nb, ffd_partition_half* h) {
+  const ffd_model_desc& m = ctx->desc;
+  const int M = nb * m.max_len;
+  h->nb = nb;
+  snprintf(h->ffn, sizeof(h->ffn), "%s", kFfnForms[p.ffn].name);
+  snprintf(h->attn, sizeof(h->attn), "%s", p.attn == ATTN_FUSED ? "k_qkv_attention" : "k_linear_hm + k_attention_mfma");
+  const bool rows = p.ffn == FFN_ROWS_OPROJ || p.ffn == FFN_ROWS, sliced = p.ffn == FFN_ROWS_SLICED_OPROJ || p.ffn == FFN_ROWS_SLICED;
+  const bool ln = p.ffn == FFN_LN || p.ffn == FFN_LN_OPROJ;
+  h->nw = rows || sliced ? p.nw : 0, h->cps = rows || sliced ? p.cps : 0;
+  h->mb = ln ? p.mb : 0, h->persist = p.ffn == FFN_LN ? p.persist : 0;
+  h->hpw = p.hpw, h->qg = p.qg, h->kspl = p.kspl;
+  h->part_floats = (long long)p.part_floats;
+  h->ffn_tiles = h->ffn_grid = 0;
+  if (rows || sliced) {
+    RowsGrid g{};
+    const bool fused = p.ffn == FFN_ROWS_SLICED_OPROJ || p.ffn == FFN_ROWS_OPROJ;
+    const RowsArgs a{nullptr, nullptr, &ctx->layers[0], nullptr, M, m.d_model, m.dim_feedforward, p.nw, p.cps, fused,
+                     sliced ? p.nslice : 0, nullptr, &g};
+    if (launch_ffn_rows(a, nullptr) == hipSuccess) h->ffn_grid = g.grid, h->ffn_tiles = g.ntiles;
+  } else if (p.ffn == FFN_LN) {
+    h->ffn_grid = ffn_ln_grid(M, p.mb, p.persist, &h->ffn_tiles);
+  } else if (p.ffn == FFN_LN_OPROJ) {
+    h->ffn_grid = h->ffn_tiles = cdiv(M, 16 * p.mb);  // (launch_oproj_ffn_ln: a workgroup per tile, always)
+  }
+  h->one_per_tile = h->ffn_grid > 0 && h->ffn_grid == h->ffn_tiles;
+}
 extern "C" {
+
+int ffd_partition_plan(ffd_ctx* ctx, int B, int entry, ffd_partition_info* info) {
+  if (!ctx) return FFD_ERR_INVALID;
+  if (!info || B < 1) return ctx->fail(FFD_ERR_INVALID, "bad argument to ffd_partition_plan (B=%d)", B);
+  if (entry < FFD_SOLVER_EULER_MARUYAMA || entry > FFD_SOLVER_DPMPP_2M)
+    return ctx->fail(FFD_ERR_INVALID, "ffd_partition_plan: entry %d names no sampling loop", entry);
+  *info = ffd_partition_info{};
+  info->parts = 1;
+  info->half[0].nb = (B + 1) / 2, info->half[1].nb = B / 2, info->whole.nb = B;
+  // (the loops with state that stays whole-batch never ask: Heun, the multistep solvers, the correctors' entries)
+  const bool asks = entry == FFD_SOLVER_EULER_MARUYAMA || entry == FFD_SOLVER_ODE_EULER;
+  const PartDecision dec = asks ? partition_decide(ctx, B, 0) : PartDecision{};
+  info->cu_budget = ctx->part_budget > 0 ? ctx->part_budget : 0;
+  if (dec.budget > 0) info->parts = 2;
+  if (dec.planned) {
+    g_cu_budget = ctx->part_budget;
+    for (int i = 0; i < 2; ++i) describe_plan(ctx, dec.half[i], info->half[i].nb, &info->half[i]);
+    g_cu_budget = 0;
+    info->halves_planned = 1;
+  }
+  if (ctx->desc.kind == FFD_MODEL_TRANSFORMER && ctx->finalized && ctx->packs_made() && g_cu_budget == 0) {
+    if (hipSetDevice(ctx->device) != hipSuccess) return ctx->fail(FFD_ERR_HIP, "ffd_partition_plan: hipSetDevice failed");
+    describe_plan(ctx, plan_of(ctx, B, CACHE_STD), B, &info->whole);
+    info->whole_planned = 1;
+  }
+  return FFD_OK;
+}
 
 // One score evaluation of a sampling step, up to where the step's tail takes over: the forward of xin at time-table
 // row `row` (time t), the CRF capture, FreSca.  With the cache, a step's first evaluation is `gated`: the gate at global

@@ -552,16 +552,19 @@ int ffn_height_plan(int M, int D, int F) {
 // some (ffd_tune "ffn_rem" turns it off)
 bool ffn_rem_rows(int D, int mb) { return mb >= 3 && D >= 16 && w2rem_groups(D) > 0; }
 
+// MB >= 4 is persistent: as many workgroups as the chip holds (two per CU at MB = 4, one at MB = 8)
+int ffn_ln_grid(int M, int mb, int persist, int* ntiles_out) {
+  const int resident = num_cus() * (mb == 4 ? 2 : 1) * (persist > 0 ? persist : 1);
+  const int ntiles = cdiv(M, 16 * mb);
+  if (ntiles_out) *ntiles_out = ntiles;
+  return (mb >= 4 && persist != 0 && ntiles > resident) ? resident : ntiles;
+}
+
 template <int D>
 static hipError_t launch_ffn_d(const float* X, const LayerWeights& w, float* Y, int M, int F, int mb, bool rem, int persist,
                                hipStream_t s, unsigned long long* stamp) {
   dim3 block(256);
-  // MB >= 4 is persistent: as many workgroups as the chip holds (two per CU at MB = 4, one at MB = 8)
-  const int resident = num_cus() * (mb == 4 ? 2 : 1) * (persist > 0 ? persist : 1);
-  auto grid_of = [&](int mbv) {
-    const int ntiles = cdiv(M, 16 * mbv);
-    return dim3((mbv >= 4 && persist != 0 && ntiles > resident) ? resident : ntiles);
-  };
+  auto grid_of = [&](int mbv) { return dim3(ffn_ln_grid(M, mbv, persist, nullptr)); };
 #define FFD_LAUNCH_FFN(MBV)                                                                                       \
   do {                                                                                                            \
     if (rem)                                                                                                      \

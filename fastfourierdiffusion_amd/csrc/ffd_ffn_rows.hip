@@ -841,6 +841,10 @@ static hipError_t launch_rows_cfg(const RowsArgs& a, hipStream_t s) {
   const int slots = per_cu * num_cus();
   const int gsl = a.nslice > 0 ? (slots / a.nslice < ntiles ? slots / a.nslice : ntiles) : 0;  // tiles in flight, sliced form
   const int grid = a.nslice > 0 ? gsl * a.nslice : ntiles < slots ? ntiles : slots;
+  if (a.grid_only) {
+    *a.grid_only = RowsGrid{grid, ntiles};
+    return hipSuccess;
+  }
   const LayerWeights& w = *a.w;
   constexpr int PRV = NW > 4 ? 1 : 0;  // descending wave priority through a barrier interval: with > 1 wave per SIMD
 #define FFD_ROWS_LAUNCH2(PR, OP, SL, ONE)                                                                              \

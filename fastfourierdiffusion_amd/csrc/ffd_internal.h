@@ -359,6 +359,9 @@ bool ffn_rows_selected(int M, int D, int F);
 size_t ffn_ring_floats(int D, int F);
 hipError_t launch_pack_ffn_ring(const float* W1, const float* b1, const float* W2, float* out, int D, int F, hipStream_t s);
 // One k_ffn_rows launch as the plan says: nw waves per workgroup, cps 32-unit chunks per ring slot
+struct RowsGrid {
+  int grid, ntiles;  // workgroups of the launch; row tiles of 32 nw rows (grid == ntiles: the one-workgroup-per-tile instance)
+};
 struct RowsArgs {
   const float *X, *Rin;  // fused: attention output + layer input; else the FFN input (Rin unused)
   const LayerWeights* w;
@@ -368,6 +371,7 @@ struct RowsArgs {
   bool fused;  // out-proj + LN1 + FFN + LN2 in one launch: Y = LN2(x1 + FFN(x1)), x1 = LN1(Rin + Wo X + bo)
   int nslice;  // >= 2: the sliced form of mid-size M, tiles x nslice units (Y = [nslice][M][D]); 0: whole rows
   unsigned long long* stamp;
+  RowsGrid* grid_only = nullptr;  // the launcher reports the grid it would launch here and launches nothing (ffd_partition_plan)
 };
 int rows_waves(int M);  // waves per workgroup of the unsliced forms
 hipError_t launch_ffn_rows(const RowsArgs& a, hipStream_t s);
@@ -406,6 +410,8 @@ bool qkv_attention_supported(int D, int hd);
 int qkv_attention_hpw(int D, int hd, int L);
 int qkv_attention_small_split(int B, int H, int L);
 int attn_qg(int QT, int hd, bool fused);  // q-tiles per wave at QT q-tiles: of k_qkv_attention (fused), else of k_attention_mfma
+// workgroups of launch_ffn_ln's grid (the launcher's own rule); *ntiles_out: the 16 mb-row tiles
+int ffn_ln_grid(int M, int mb, int persist, int* ntiles_out);
 int num_cus();  // compute units the calling thread's launches may count on: g_cu_budget, else the current device's (256 on MI355X); ffd_ffn.hip
 // > 0 while the calling thread enqueues one CU partition's half of a batch (ffd_api.hip run_partitioned): the planner, the
 // form pickers and the grids then size themselves for that many CUs

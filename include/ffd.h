@@ -1018,6 +1018,40 @@ int ffd_sample_batch_resample(ffd_ctx* ctx, float* x, int B, const float* timest
  * caller's stream alone. */
 int ffd_partition_status(const ffd_ctx* ctx, int* parts_out);
 
+/* What a sampling-loop call of B samples WOULD do under the calling thread's knobs, by the decision and the layer
+ * planner the loops themselves run; nothing is launched (the first call on a context creates the two CU-masked streams
+ * and their events, as the first eligible loop call would).  entry: FFD_SOLVER_EULER_MARUYAMA = ffd_sample_batch with
+ * device draws, FFD_SOLVER_ODE_EULER = ffd_sample_batch_ode's Euler solver; every other FFD_SOLVER_* value names a loop
+ * that never partitions (parts = 1, halves not planned).  The call's own state -- z_inject, use_cache, a capturing
+ * stream -- is not part of the question: such a call stays single-stream whatever this reports.
+ *   parts            2: as two CU partitions | 1: on the caller's stream (ffd_partition_status's encoding);
+ *   cu_budget        CUs per half (128 on MI355X); 0 where no partitions exist (the device's CUs do not halve, or the
+ *                    question never got that far: "partitions" = 0, B < 2, another backbone, cache / FreSca / timing on);
+ *   half[0], half[1] samples [0, ceil(B/2)) and the rest, planned for cu_budget CUs (halves_planned = 1; else only nb is
+ *                    set).  They are planned -- and reported -- also where the decision is 1 because of them;
+ *   whole            the single-stream plan of all B samples for the device's CUs (whole_planned = 1: a finalized transformer).
+ * Per plan: nb samples; ffn / attn: the form names ffd_kernel_work gives ("k_qkv_attention" without its static-bound
+ * suffix); nw waves per workgroup and cps chunks per ring slot (k_ffn_rows forms, else 0); mb 16-row tiles per workgroup
+ * (k_ffn_ln forms, else 0) and the persist factor (k_ffn_ln behind k_linear_res_ln); hpw heads per attention workgroup,
+ * qg q-tiles per wave, kspl key pieces of the small-batch split attention (0: one workgroup per head or head pair);
+ * part_floats: partial rows the form keeps in the shared workspace (non-zero: never partitioned); ffn_tiles / ffn_grid:
+ * row tiles and workgroups of the FFD_K_FFN launch as its launcher computes them (k_ffn_rows and k_ffn_ln forms; 0 for
+ * the others), one_per_tile = 1 where they are equal, else the grid is the persistent one sized from the CU count.
+ * FFD_ERR_INVALID: ctx or info NULL, B < 1, entry outside the FFD_SOLVER_* values. */
+typedef struct ffd_partition_half {
+  int nb;
+  int nw, cps, mb, persist;
+  int hpw, qg, kspl;
+  int ffn_tiles, ffn_grid, one_per_tile;
+  long long part_floats;
+  char ffn[64], attn[48];
+} ffd_partition_half;
+typedef struct ffd_partition_info {
+  int parts, cu_budget, halves_planned, whole_planned;
+  ffd_partition_half half[2], whole;
+} ffd_partition_info;
+int ffd_partition_plan(ffd_ctx* ctx, int B, int entry, ffd_partition_info* info);
+
 /* Tuning knobs for experiments and for the test suite's kernel variants (results stay within the parity tolerance,
  * only the kernel choice / tiling changes).  PER CALLING THREAD since round 4 (thread_local): a knob set on one thread
  * selects kernels for the launches THAT thread makes and is invisible to every other thread, so two samplers on two

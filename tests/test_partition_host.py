@@ -71,3 +71,19 @@ def test_knob_and_status_getter_exist():
     assert lib.ffd_tune(b"partitions", 3) == -1 and lib.ffd_tune(b"partitions", -1) == -1
     assert lib.ffd_tune(b"reset", 0) == 0
     assert lib.ffd_partition_status(None, C.byref(v)) == -1
+
+
+def test_plan_query_exists_and_refuses_a_null_context():
+    """ffd_partition_plan without a context is FFD_ERR_INVALID whatever the other arguments, and leaves *info alone (the
+    argument errors that need a context -- info NULL, B < 1, an entry that names no loop -- are asserted on the device, in
+    tests/test_partition_plans_gpu.py)."""
+    lib = N.lib()
+    info = N.PartitionInfo()
+    info.parts = 77
+    for B, entry in ((2, N.FFD_SOLVER_EULER_MARUYAMA), (0, N.FFD_SOLVER_ODE_EULER), (2, 99)):
+        assert lib.ffd_partition_plan(None, B, entry, C.byref(info)) == -1
+    assert lib.ffd_partition_plan(None, 2, N.FFD_SOLVER_EULER_MARUYAMA, None) == -1
+    assert info.parts == 77
+    # the layout include/ffd.h declares: eleven ints, the long long on its 8-byte boundary, the two names
+    assert C.sizeof(N.PartitionHalf) == 168 and N.PartitionHalf.part_floats.offset == 48 and N.PartitionHalf.ffn.offset == 56
+    assert C.sizeof(N.PartitionInfo) == 16 + 3 * 168 and N.PartitionInfo.whole.offset == 16 + 2 * 168
