@@ -58,6 +58,12 @@ class CondCfg(C.Structure):
                 ("domain", C.c_int32), ("final_replace", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GuideCfg(C.Structure):
+    """ffd_guide_cfg: lambda(t) = scale / (obs_var + rho sigma^2 / (alpha^2 + sigma^2)) of ffd_sample_batch_guided."""
+    _fields_ = [("scale", C.c_double), ("obs_var", C.c_double), ("rho", C.c_double), ("replace", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class CacheCfg(C.Structure):
     _fields_ = [("K", C.c_int32), ("R", C.c_int32)]
 
@@ -143,6 +149,8 @@ SIGNATURES = {
     "ffd_train_work_bytes": (C.c_size_t, [C.POINTER(ModelDesc), C.c_int]),
     "ffd_train_bind": (C.c_int, [_P, C.c_char_p, _P, _P, _P, _P, C.c_size_t]),
     "ffd_train_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "ffd_train_bind_params": (C.c_int, [_P, C.c_char_p, _P, C.c_size_t]),
+    "ffd_train_input_vjp": (C.c_int, [_P, _P, _P, C.c_int, _P]),
     "ffd_train_loss_grad": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, C.c_int, _P]),
     "ffd_train_grad_sqnorm": (C.c_int, [_P, _P, _P]),
     "ffd_train_adamw": (C.c_int, [_P, _P, C.POINTER(AdamWCfg), _P]),
@@ -183,6 +191,14 @@ SIGNATURES = {
     "ffd_mixture_score": (C.c_int, [C.POINTER(SdeDesc), _P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int,
                                     C.c_int, _P, C.c_size_t, _P]),
     "ffd_host_mixture_check": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int]),
+    "ffd_mixture_vjp_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ffd_mixture_score_vjp": (C.c_int, [C.POINTER(SdeDesc), _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "ffd_guide_seed": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, _P, _P, _P, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_int, _P, _P, _P, _P, _P]),
+    "ffd_guide_combine": (C.c_int, [_P, _P, _P, C.c_float, C.c_float, _P, C.c_size_t, _P]),
+    "ffd_host_guide_coef": (C.c_int, [C.POINTER(SdeDesc), C.c_double, C.c_double, C.c_double, C.c_double,
+                                      C.POINTER(C.c_double)]),
     "ffd_mixture_tiling": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ffd_prior": (C.c_int, [C.POINTER(SdeDesc), _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_host_loglik_h": (C.c_int, [C.POINTER(SdeDesc), C.c_double, C.c_double, _F]),
@@ -219,6 +235,8 @@ SIGNATURES = {
     "ffd_host_resample_visit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ffd_sample_batch_resample": (C.c_int, _LOOP + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, _P,
                                                     C.POINTER(CondCfg), _P]),
+    "ffd_sample_batch_guided": (C.c_int, [_P, _P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_uint64,
+                                          C.c_uint64, _P, C.POINTER(CondCfg), C.POINTER(GuideCfg), _P, _P]),
     "ffd_flops_per_sample_step": (C.c_double, [_P, C.c_int]),
     "ffd_ffn_flops_per_launch": (C.c_double, [_P, C.c_int]),
     "ffd_kernel_timing_begin": (C.c_int, [_P, C.c_uint32, C.c_int]),

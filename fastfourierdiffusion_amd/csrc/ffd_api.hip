@@ -119,6 +119,7 @@ struct ffd_ctx {
   // (ms_solver < 0: none; every other loop entry drops it)
   int ms_solver = -1, ms_B = 0, ms_next = 0;
   Grow<float> lv_work;  // the Langevin corrector's row squares, norms and step sizes (ffd_sample_batch_pc)
+  Grow<float> guide;  // ffd_sample_batch_guided: u, v and J^T v, one (B, L, C) slab each
   Grow<float> ll_stack, ll_v1;  // ffd_loglik_batch: the stacked batch of (1 + 2 k) B rows; Heun's v1 (B doubles)
   int tail_solver = FFD_SOLVER_EULER_MARUYAMA;  // the loop entry that ran last (ffd_kernel_work names its FFD_K_SDE tail)
   // CU partitions (ffd_tune "partitions"; run_partitioned): two streams confined to disjoint halves of the CUs, one fork
@@ -1878,6 +1879,108 @@ int ffd_sample_batch_resample(ffd_ctx* ctx, float* x, int B, const float* timest
     return ctx->fail(FFD_ERR_INVALID, "visits * (n_corrector + 1) reaches the transitions' Philox tags");
   return sde_loop(ctx, "ffd_sample_batch_resample", x, B, timesteps, n_steps, step_size, first_visit, n_visits, n_corrector,
                   snr, norm, seed, sample_offset, z_inject, 0, 0, cond, jump, resample, stream);
+}
+
+// Guided conditional sampling (include/ffd.h ffd_sample_batch_guided): per step the score, the seed of the reconstruction
+// loss's gradient, the score model's input VJP, the guided score, the stand-alone Euler-Maruyama step and, with
+// guide->replace, one projection.  The mixture evaluates both the score and the VJP in closed form; the transformer and
+// the MLP take them from `net`, a training object on the same parameters (its forward keeps the activations).
+int ffd_sample_batch_guided(ffd_ctx* ctx, ffd_train* net, float* x, int B, const float* timesteps, int n_steps,
+                            float step_size, int first_step, int n_run, uint64_t seed, uint64_t sample_offset,
+                            const float* z_inject, const ffd_cond_cfg* cond, const ffd_guide_cfg* guide, double* loss_out,
+                            void* stream) {
+  if (!ctx) return FFD_ERR_INVALID;
+  const ffd_model_desc& m = ctx->desc;
+  const int L = m.max_len, C = m.n_channels;
+  const bool mixture = m.kind == FFD_MODEL_MIXTURE;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<double> coef;  // (alpha, sigma^2, lambda) of every step of the run
+  int rc = loop_begin(ctx, "ffd_sample_batch_guided", x, B, timesteps, n_steps, n_steps, first_step, n_run, step_size, 0, s,
+                      [&]() -> int {
+    if (!cond || !guide) return ctx->fail(FFD_ERR_INVALID, "ffd_sample_batch_guided needs an observation (cond) and guide");
+    if (m.kind == FFD_MODEL_LSTM)
+      return ctx->fail(FFD_ERR_UNSUPPORTED, "ffd_sample_batch_guided: the LSTM has no backward pass");
+    if (!mixture) {
+      if (!net) return ctx->fail(FFD_ERR_STATE, "ffd_sample_batch_guided: this backbone needs an ffd_train (net) for its VJP");
+      const ffd_model_desc& n = train_desc(net);
+      if (n.kind != m.kind || n.n_channels != C || n.max_len != L || n.d_model != m.d_model || n.n_head != m.n_head ||
+          n.num_layers != m.num_layers || n.dim_feedforward != m.dim_feedforward || n.sde != m.sde || n.sde_a != m.sde_a ||
+          n.sde_b != m.sde_b || n.fourier_noise_scaling != m.fourier_noise_scaling || n.eps != m.eps)
+        return ctx->fail(FFD_ERR_INVALID, "ffd_sample_batch_guided: net's descriptor differs from the context's");
+    }
+    if (ctx->fresca_on)
+      return ctx->fail(FFD_ERR_STATE, "ffd_sample_batch_guided: FreSca is on (call ffd_fresca_disable): the VJP is the "
+                       "unscaled score's");
+    if (n_steps > 0x3FFFFFF0) return ctx->fail(FFD_ERR_INVALID, "n_steps exceeds the projection's Philox tag range");
+    if (!cond->obs || !cond->mask) return ctx->fail(FFD_ERR_INVALID, "conditioning needs obs and mask");
+    if (cond->obs_batch != 1 && cond->obs_batch != B)
+      return ctx->fail(FFD_ERR_INVALID, "obs_batch must be 1 or B, got %d", cond->obs_batch);
+    if (cond->domain != FFD_COND_FREQUENCY && cond->domain != FFD_COND_TIME)
+      return ctx->fail(FFD_ERR_INVALID, "unknown conditioning domain %d", cond->domain);
+    if (cond->domain == FFD_COND_TIME && cond->std) return ctx->fail(FFD_ERR_INVALID, "std with the time domain");
+    if (x == cond->obs || x == cond->mask || x == z_inject) return ctx->fail(FFD_ERR_INVALID, "x aliases obs, mask or z_inject");
+    for (int j = 0; j < n_run; ++j) {
+      double c[3];
+      if (guide_coef(m.sde, m.sde_a, m.sde_b, (double)timesteps[first_step + j], guide->scale, guide->obs_var, guide->rho, c))
+        return ctx->fail(FFD_ERR_INVALID, "ffd_sample_batch_guided: scale, obs_var and rho must be finite and >= 0, the time "
+                         "of step %d finite and >= 0 and lambda's denominator there > 0", first_step + j);
+      coef.insert(coef.end(), c, c + 3);
+    }
+    if (cond->domain == FFD_COND_FREQUENCY && !cond_len_supported(L))
+      return ctx->fail(FFD_ERR_UNSUPPORTED, "frequency-domain conditioning takes 2 <= L <= 4096");
+    return FFD_OK;
+  });
+  if (rc) return rc;
+  const size_t slab = (size_t)B * L * C;
+  if ((rc = ensure(ctx, ctx->guide, 3 * ((slab + 3) & ~(size_t)3)))) return rc;
+  if (mixture && (rc = ensure(ctx, ctx->mix_work, mixture_vjp_work_floats(B, m.dim_feedforward, L, C)))) return rc;
+  ctx->tail_solver = FFD_SOLVER_EULER_MARUYAMA;
+  float* const u = ctx->guide.p;
+  float* const v = u + ((slab + 3) & ~(size_t)3);
+  float* const jtv = v + ((slab + 3) & ~(size_t)3);
+  float* const score = ctx->score.p;
+  float* const times = ctx->temb_b.p;  // the network's per-sample times (B floats of the (B, d) block)
+  const uint64_t elem_off = sample_offset * (uint64_t)L * C;
+  auto project = [&](double t, int noiseless, const float* z, uint32_t tag) -> hipError_t {
+    float mc, sigma;
+    cond_coeffs(m.sde, m.sde_a, m.sde_b, t, noiseless, &mc, &sigma);
+    if (cond->domain == FFD_COND_TIME)
+      return launch_cond_time(x, cond->obs, cond->mask, ctx->G_dev, mc, sigma, noiseless, z, seed, elem_off, tag,
+                              cond->obs_batch, B, L, C, s);
+    return launch_cond_project(x, cond->obs, cond->mask, cond->std, ctx->G_dev, mc, sigma, noiseless, z, seed, elem_off, tag,
+                               cond->obs_batch, B, L, C, s);
+  };
+  auto net_call = [&](int r) { return r ? ctx->fail(r, "ffd_sample_batch_guided: net: %s", ffd_train_last_error(net)) : FFD_OK; };
+  for (int j = 0; j < n_run; ++j) {
+    const int i = first_step + j;
+    const double t = (double)timesteps[i];
+    const float* tdev = ctx->temb_tab.p + i;  // the mixture's time table is the grid itself (d_model = 1)
+    const float* zj = z_inject ? z_inject + (size_t)j * 2 * slab : nullptr;
+    if (mixture) {
+      if ((rc = forward_impl(ctx, x, tdev, 0, score, nullptr, B, -1, s))) return rc;
+    } else {
+      HIPCHECK(launch_mixture_times(nullptr, timesteps[i], B, times, s));
+      if ((rc = net_call(ffd_train_forward(net, x, times, score, B, stream)))) return rc;
+    }
+    const GuideArgs ga{x, score, cond->obs, cond->mask, cond->std, ctx->G_dev, u, v, nullptr,
+                       loss_out ? loss_out + (size_t)j * B : nullptr, (float)coef[3 * j], (float)coef[3 * j + 1],
+                       cond->obs_batch};
+    TIMED(FFD_K_SDE, cond->domain == FFD_COND_TIME ? launch_guide_seed_time(ga, B, L, C, s)
+                                                   : launch_guide_seed_freq(ga, B, L, C, s));
+    if (mixture)
+      TIMED(FFD_K_ATTN, launch_mixture_score_vjp(m.sde, m.sde_a, m.sde_b, x, tdev, 0, ctx->mix.means, ctx->mix.logw,
+                                                 ctx->mix.var, ctx->G_dev, v, jtv, B, m.dim_feedforward, L, C,
+                                                 ctx->mix_work.p, s));
+    else if ((rc = net_call(ffd_train_input_vjp(net, v, jtv, B, stream))))
+      return rc;
+    TIMED(FFD_K_SDE, launch_guide_combine(score, u, jtv, (float)coef[3 * j], (float)coef[3 * j + 2], score, slab, s));
+    TIMED(FFD_K_SDE, launch_sde_step(x, score, zj, ctx->G_dev, sde_params(m.sde, m.sde_a, m.sde_b, t, step_size), seed,
+                                     elem_off, (uint32_t)i, B, L, C, s));
+    if (guide->replace) TIMED(FFD_K_SDE, project(t, 0, zj ? zj + slab : nullptr, 0xC0000000u + (uint32_t)i));
+  }
+  if (cond->final_replace && n_run > 0 && first_step + n_run == n_steps)
+    TIMED(FFD_K_SDE, project((double)timesteps[n_steps - 1], 1, nullptr, 0u));
+  return FFD_OK;
 }
 
 // ---------------------------------------------------------------------------

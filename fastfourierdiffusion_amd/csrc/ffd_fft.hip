@@ -840,6 +840,80 @@ __global__ __launch_bounds__(256) void k_cond_project(CondArgs a, const float2* 
   }
 }
 
+// The seed of reconstruction guidance in the frequency domain (include/ffd.h ffd_guide_seed): k_cond_project's two
+// transforms around the mask, on d = (x0hat - obs) std with x0hat = (x + c s) / alpha, ending in the loss's gradient
+//   r = mask (.) idft(d);   loss = 1/2 sum r^2;   u = std (.) W (.) dft(mask (.) r);   v = c (.) u
+// instead of an update of x.  W: the packed layout holds a bin other than DC / Nyquist once where the Hermitian image
+// holds it twice, so idft's adjoint weighs those rows by 2.  One workgroup per sample walks the channel groups in order
+// and sums the loss in fp64 (per-thread partials in element order, then block_sum's tree).  LDS: 256 doubles for that
+// tree in front of the twiddles and the two slabs.
+constexpr size_t GUIDE_RED_BYTES = 256 * sizeof(double);
+
+// d of packed element (row r, channel c) of sample b; the denoised estimate goes out on the way (each element is loaded once)
+__device__ __forceinline__ float guide_load(const GuideArgs& a, int b, int r, int c, int L, int C) {
+  const size_t io = (size_t)r * C + c;
+  const size_t ix = (size_t)b * L * C + io;
+  const float xh = guide_x0hat(a, ix, guide_c(a, r));
+  if (a.x0hat) a.x0hat[ix] = xh;
+  float d = __fsub_rn(xh, a.obs[a.obs_batch == 1 ? io : ix]);
+  if (a.std) d = __fmul_rn(d, a.std[io]);
+  return d;
+}
+
+__global__ __launch_bounds__(256) void k_guide_seed(GuideArgs a, const float2* __restrict__ Wg, FftPlan plan, int L, int C,
+                                                    int CG, float scale) {
+  extern __shared__ __align__(16) float2 sm[];
+  double* red = reinterpret_cast<double*>(sm);
+  float2* W = sm + GUIDE_RED_BYTES / sizeof(float2);
+  float2* bufA = W + L;
+  float2* bufB = bufA + L * CG;
+  const int b = blockIdx.x;
+  const int n_re = L / 2 + 1;
+  const float* mk = a.mask + (a.obs_batch == 1 ? (size_t)0 : (size_t)b * L * C);
+  double part = 0.0;
+  for (int c0 = 0; c0 < C; c0 += CG) {
+    const int cg = min(CG, C - c0);
+    for (int i = threadIdx.x; i < L; i += blockDim.x) {  // conjugated: the inverse transform comes first
+      float2 w = Wg[i];
+      w.y = -w.y;
+      W[i] = w;
+    }
+    for (int idx = threadIdx.x; idx < n_re * cg; idx += blockDim.x) {
+      const int kk = idx / cg, cc = idx - kk * cg;
+      const float re = guide_load(a, b, kk, c0 + cc, L, C);
+      float im = 0.f;
+      if (kk >= 1 && kk <= L - n_re) im = guide_load(a, b, n_re + kk - 1, c0 + cc, L, C);
+      bufA[kk * CG + cc] = make_float2(re, im);
+      if (kk >= 1 && L - kk >= n_re) bufA[(L - kk) * CG + cc] = make_float2(re, -im);
+    }
+    __syncthreads();
+    float2* t = stockham(bufA, bufB, W, plan, L, CG, cg);
+    for (int idx = threadIdx.x; idx < L * cg; idx += blockDim.x) {
+      const int l = idx / cg, cc = idx - l * cg;
+      const float m = mk[(size_t)l * C + c0 + cc];
+      const float r = __fmul_rn(m, __fmul_rn(t[l * CG + cc].x, scale));
+      part += (double)r * (double)r;
+      t[l * CG + cc] = make_float2(__fmul_rn(m, r), 0.f);
+    }
+    for (int i = threadIdx.x; i < L; i += blockDim.x) W[i].y = -W[i].y;  // back to the forward twiddles
+    __syncthreads();
+    float2* X = stockham(t, t == bufA ? bufB : bufA, W, plan, L, CG, cg);
+    for (int idx = threadIdx.x; idx < L * cg; idx += blockDim.x) {
+      const int o = idx / cg, cc = idx - o * cg;
+      float v = o < n_re ? X[o * CG + cc].x : X[(o - n_re + 1) * CG + cc].y;
+      const size_t io = (size_t)o * C + c0 + cc, go = (size_t)b * L * C + io;
+      v = __fmul_rn(v, scale);
+      if (!(o == 0 || 2 * o == L)) v = __fmul_rn(v, 2.f);
+      if (a.std) v = __fmul_rn(v, a.std[io]);
+      a.u[go] = v;
+      a.v[go] = __fmul_rn(guide_c(a, o), v);
+    }
+    __syncthreads();  // the LDS images are rewritten by the next channel group
+  }
+  const double total = block_sum(part, red);
+  if (a.loss && threadIdx.x == 0) a.loss[b] = 0.5 * total;
+}
+
 // Powers of two: pow2_split_inv -> half-length inverse -> mask -> half-length forward -> pow2_split_fwd, persistent
 // over the samples like k_fresca_apply_pow2.  VEC (CG == C, C % 4 == 0, 16-byte aligned pointers): the slab is a flat
 // array of float4, each one Philox block.
@@ -1224,6 +1298,24 @@ hipError_t launch_cond_project(float* x, const float* obs, const float* mask, co
     if ((e = allow_lds(k_cond_project, g.lds)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_cond_project, grid, block, g.lds, s, a, W, g.plan, L, C, g.CG, sc);
   }
+  return hipGetLastError();
+}
+
+// One k_guide_seed launch at any length of cond_len_supported (the general-length butterflies, powers of two included):
+// as many channels per workgroup as keep its LDS image within 64 KiB, one channel up to the CU's 160 KiB.
+hipError_t launch_guide_seed_freq(const GuideArgs& a, int B, int L, int C, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  if (C < 1 || !cond_len_supported(L)) return hipErrorInvalidValue;
+  auto lds_bytes = [&](int CG) { return GUIDE_RED_BYTES + (size_t)L * (1 + 2 * (size_t)CG) * sizeof(float2); };
+  int CG = C;
+  while (CG > 1 && lds_bytes(CG) > 64 * 1024) CG = (CG + 1) / 2;
+  const size_t lds = lds_bytes(CG);
+  if (lds > FFT_LDS_CAP) return hipErrorInvalidValue;
+  const float2* W = nullptr;
+  hipError_t e = get_twiddles(L, &W);
+  if (e != hipSuccess) return e;
+  if ((e = allow_lds(k_guide_seed, lds)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_guide_seed, dim3(B), dim3(256), lds, s, a, W, make_plan(L), L, C, CG, (float)(1.0 / sqrt((double)L)));
   return hipGetLastError();
 }
 

@@ -318,6 +318,31 @@ hipError_t launch_cond_project(float* x, const float* obs, const float* mask, co
 hipError_t launch_cond_time(float* x, const float* obs, const float* mask, const float* G, float mc, float sigma,
                             int noiseless, const float* z, uint64_t seed, uint64_t elem_offset, uint32_t tag, int obs_batch,
                             int B, int L, int C, hipStream_t s);
+// Reconstruction guidance (include/ffd.h ffd_guide_seed; ffd_guide.hip, the frequency-domain seed next to
+// k_cond_project in ffd_fft.hip).  guide_coef: (alpha, sigma^2, lambda) at t in double, FFD_ERR_INVALID as
+// ffd_host_guide_coef (the SDE kind is the caller's to check).
+struct GuideArgs {
+  const float *x, *score, *obs, *mask, *std, *G;
+  float *u, *v, *x0hat;  // x0hat: nullptr or the denoised estimate
+  double* loss;          // nullptr or B doubles
+  float alpha, sigma2;
+  int obs_batch;
+};
+// c = sigma^2 (G_l G_l) of packed row r and x0hat = (x + c s) / alpha, every operation its own fp32 rounding
+__device__ __forceinline__ float guide_c(const GuideArgs& a, int r) {
+  const float g = a.G[r];
+  return __fmul_rn(a.sigma2, __fmul_rn(g, g));
+}
+__device__ __forceinline__ float guide_x0hat(const GuideArgs& a, size_t ix, float c) {
+  return __fdiv_rn(__fadd_rn(a.x[ix], __fmul_rn(c, a.score[ix])), a.alpha);
+}
+int guide_coef(int sde, double a, double b, double t, double scale, double obs_var, double rho, double coef[3]);
+hipError_t launch_guide_seed_time(const GuideArgs& a, int B, int L, int C, hipStream_t s);
+hipError_t launch_guide_seed_freq(const GuideArgs& a, int B, int L, int C, hipStream_t s);  // hipErrorInvalidValue: length
+hipError_t launch_guide_combine(const float* score, const float* u, const float* jtv, float alpha, float coef, float* out,
+                                size_t n, hipStream_t s);
+// the descriptor a training object was created with (ffd_train.hip; ffd_sample_batch_guided compares it with the context's)
+const ffd_model_desc& train_desc(const ffd_train* tr);
 // The forward transition s -> t of the SDE (include/ffd.h ffd_forward_transition; ffd_elem.hip).  transition_coef: (a, sg)
 // in double, FFD_ERR_INVALID / FFD_ERR_UNSUPPORTED as ffd_host_transition_coef.  The launch is skipped for (1, 0).
 int transition_coef(int sde, double a, double b, double s, double t, double* coef);
@@ -496,6 +521,11 @@ size_t mixture_work_floats(int B, int K, int L, int C);  // 0 for a shape the la
 hipError_t launch_mixture_score(int sde, double sa, double sb, const float* x, const float* t, int t_stride,
                                 const float* means, const float* logw, const float* var, const float* G, float* out, int B,
                                 int K, int L, int C, float* work, hipStream_t s);
+// out = J^T v, J = d score / d x (symmetric), v (B, L, C); work: mixture_vjp_work_floats floats; out may be v or x.
+size_t mixture_vjp_work_floats(int B, int K, int L, int C);  // 0 for a shape the launch refuses
+hipError_t launch_mixture_score_vjp(int sde, double sa, double sb, const float* x, const float* t, int t_stride,
+                                    const float* means, const float* logw, const float* var, const float* G, const float* v,
+                                    float* out, int B, int K, int L, int C, float* work, hipStream_t s);
 // out[i] = ts[i] (ts == nullptr: the immediate t_imm), n floats: the mixture kind's "time embedding" is the time itself
 hipError_t launch_mixture_times(const float* ts, float t_imm, int n, float* out, hipStream_t s);
 // host: FFD_OK | FFD_ERR_INVALID (non-finite mean, negative / non-finite variance, NaN / +inf log-weight, all -inf) |

@@ -531,6 +531,7 @@ struct ffd_train {
   float* G_dev = nullptr;
   float* work = nullptr;
   size_t work_bytes = 0;
+  int fwd_B = 0;  // the batch whose activations the workspace holds (ffd_train_input_vjp); 0: none
   TrainSeg* segs = nullptr;  // the bound trainable tensors in segments of TRAIN_SEG, rebuilt after a bind
   int nseg = 0;
   bool segs_stale = true;
@@ -624,9 +625,20 @@ static int train_ready(ffd_train* tr) {
   return FFD_OK;
 }
 
+// what training adds to train_ready: a trainable tensor bound by ffd_train_bind_params has no gradient and no moments
+static int train_trainable(ffd_train* tr) {
+  if (int rc = train_ready(tr)) return rc;
+  for (const auto& x : tr->t)
+    if (!x.frozen && !x.g)
+      return tr->fail(FFD_ERR_STATE, "tensor %s is bound without gradient and moments (ffd_train_bind_params): the object "
+                      "serves inference only", x.key.c_str());
+  return FFD_OK;
+}
+
 // the transformer's path (behind the LayerNorm and attention operators at the end of this file)
 static size_t tf_work_bytes(const ffd_model_desc& m, int B);
 static int tf_forward(ffd_train* tr, const float* xn, const float* tb, int B, hipStream_t s);
+static int tf_input_vjp(ffd_train* tr, const float* v, float* dx, int B, hipStream_t s);
 static int tf_loss_grad(ffd_train* tr, const float* x0, const int64_t* index, const float* timesteps, const float* mean_coeff,
                         const float* sigma, const float* z, uint64_t seed, uint64_t sample_offset, int lw,
                         double* per_sample_out, int B, hipStream_t s);
@@ -641,7 +653,7 @@ static int train_workspace(ffd_train* tr, int B) {
   if (tr->work) {
     (void)hipDeviceSynchronize();
     (void)hipFree(tr->work);
-    tr->work = nullptr, tr->work_bytes = 0;
+    tr->work = nullptr, tr->work_bytes = 0, tr->fwd_B = 0;
   }
   if (hipMalloc((void**)&tr->work, need + 256) != hipSuccess)
     return tr->fail(FFD_ERR_NOMEM, "hipMalloc(%zu bytes) of the training workspace failed", need);
@@ -715,14 +727,37 @@ static int mlp_train_backward(ffd_train* tr, const MlpWork& w, int B, hipStream_
   return FFD_OK;
 }
 
+// The MLP's backward chain for the input alone: no wgrad, and one more dgrad through embedder.weight
+static int mlp_input_vjp(ffd_train* tr, const float* v, float* dx, const MlpWork& w, int B, hipStream_t s) {
+  const ffd_model_desc& m = tr->desc;
+  const int io = m.max_len * m.n_channels, d = m.d_model, F = m.dim_feedforward, NL = m.num_layers;
+  float* W = tr->work;
+  float *dh = W + w.dh0, *dh_alt = W + w.dh1;
+  TRCHECK(launch_dense_dgrad(v, tr->par("unembedder.weight"), nullptr, nullptr, dh, B, io, d, s));
+  for (int i = NL - 1; i >= 0; --i) {
+    const std::string p = "backbone." + std::to_string(i) + ".";
+    const float* ui = W + w.u + (size_t)i * B * F;
+    TRCHECK(launch_dense_dgrad(dh, tr->par(p + "3.weight"), ui, nullptr, W + w.du, B, d, F, s));
+    TRCHECK(launch_dense_dgrad(W + w.du, tr->par(p + "0.weight"), nullptr, dh, dh_alt, B, F, d, s));  // + the residual path
+    std::swap(dh, dh_alt);
+  }
+  TRCHECK(launch_dense_dgrad(dh, tr->par("embedder.weight"), nullptr, nullptr, dx, B, d, io, s));
+  return FFD_OK;
+}
+
 static int train_loss_grad(ffd_train* tr, const float* x0, const int64_t* index, const float* timesteps,
                            const float* mean_coeff, const float* sigma, const float* z, uint64_t seed,
                            uint64_t sample_offset, int lw, double* per_sample_out, int B, hipStream_t s) {
   const ffd_model_desc& m = tr->desc;
   TRCHECK(hipSetDevice(tr->device));
   if (int rc = train_workspace(tr, B)) return rc;
-  if (m.kind == FFD_MODEL_TRANSFORMER)
-    return tf_loss_grad(tr, x0, index, timesteps, mean_coeff, sigma, z, seed, sample_offset, lw, per_sample_out, B, s);
+  tr->fwd_B = 0;  // (B again once everything is enqueued: the forward's activations are what ffd_train_input_vjp reads)
+  if (m.kind == FFD_MODEL_TRANSFORMER) {
+    if (int rc = tf_loss_grad(tr, x0, index, timesteps, mean_coeff, sigma, z, seed, sample_offset, lw, per_sample_out, B, s))
+      return rc;
+    tr->fwd_B = B;
+    return FFD_OK;
+  }
   const MlpWork w = mlp_work(m, B);
   float* W = tr->work;
   hipLaunchKernelGGL(k_train_perturb, dim3((unsigned)B), dim3(256), 0, s, x0, W + w.xn, timesteps, mean_coeff, sigma,
@@ -732,7 +767,9 @@ static int train_loss_grad(ffd_train* tr, const float* x0, const int64_t* index,
   if (int rc = mlp_train_forward(tr, W + w.xn, W + w.tb, w, B, s)) return rc;
   TRCHECK(launch_sm_loss_grad(W + w.score, W + w.sgb, tr->G_dev, z, seed, sample_offset, index, lw, per_sample_out,
                               W + w.dscore, B, m.max_len, m.n_channels, s));
-  return mlp_train_backward(tr, w, B, s);
+  if (int rc = mlp_train_backward(tr, w, B, s)) return rc;
+  tr->fwd_B = B;
+  return FFD_OK;
 }
 
 static int train_batch_args(ffd_train* tr, const float* x0, const float* timesteps, const float* mean_coeff,
@@ -743,8 +780,12 @@ static int train_batch_args(ffd_train* tr, const float* x0, const float* timeste
       (double)B * tr->desc.dim_feedforward * (tr->desc.kind == FFD_MODEL_TRANSFORMER ? tr->desc.max_len : 1) >= 2147483648.0 ||
       (double)B * tr->desc.max_len * tr->desc.d_model * 3 >= 2147483648.0)
     return tr->fail(FFD_ERR_UNSUPPORTED, "B=%d: a batch's activations are indexed in 32 bits", B);
-  return train_ready(tr);
+  return train_trainable(tr);
 }
+
+namespace ffd {
+const ffd_model_desc& train_desc(const ffd_train* tr) { return tr->desc; }
+}  // namespace ffd
 
 extern "C" {
 
@@ -802,6 +843,18 @@ int ffd_train_bind(ffd_train* tr, const char* name, float* param, float* grad, f
   return FFD_OK;
 }
 
+int ffd_train_bind_params(ffd_train* tr, const char* name, float* param, size_t n) {
+  if (!tr) return FFD_ERR_INVALID;
+  if (!name || !param) return tr->fail(FFD_ERR_INVALID, "null name or parameter");
+  TrainTensor* x = tr->find(name);
+  if (!x) return tr->fail(FFD_ERR_INVALID, "unknown tensor %s", name);
+  if (n != x->n) return tr->fail(FFD_ERR_INVALID, "%s has %zu elements, the model takes %zu", name, n, x->n);
+  x->p = param;
+  x->g = x->m = x->v = nullptr;
+  tr->segs_stale = true;
+  return FFD_OK;
+}
+
 int ffd_train_forward(ffd_train* tr, const float* x, const float* timesteps, float* score_out, int B, void* stream) {
   if (!tr) return FFD_ERR_INVALID;
   if (!x || !timesteps || !score_out) return tr->fail(FFD_ERR_INVALID, "null buffer");
@@ -809,18 +862,34 @@ int ffd_train_forward(ffd_train* tr, const float* x, const float* timesteps, flo
   if (int rc = train_ready(tr)) return rc;
   TRCHECK(hipSetDevice(tr->device));
   if (int rc = train_workspace(tr, B)) return rc;
+  tr->fwd_B = 0;  // (B again once the forward is enqueued)
   hipStream_t s = (hipStream_t)stream;
   if (tr->desc.kind == FFD_MODEL_TRANSFORMER) {
     if (int rc = tf_forward(tr, x, timesteps, B, s)) return rc;
     TRCHECK(hipMemcpyAsync(score_out, tf_score(tr, B), sizeof(float) * (size_t)B * tr->desc.max_len * tr->desc.n_channels,
                            hipMemcpyDeviceToDevice, s));
+    tr->fwd_B = B;
     return FFD_OK;
   }
   const MlpWork w = mlp_work(tr->desc, B);
   if (int rc = mlp_train_forward(tr, x, timesteps, w, B, s)) return rc;
   TRCHECK(hipMemcpyAsync(score_out, tr->work + w.score, sizeof(float) * (size_t)B * tr->desc.max_len * tr->desc.n_channels,
                          hipMemcpyDeviceToDevice, s));
+  tr->fwd_B = B;
   return FFD_OK;
+}
+
+int ffd_train_input_vjp(ffd_train* tr, const float* v, float* dx_out, int B, void* stream) {
+  if (!tr) return FFD_ERR_INVALID;
+  if (!v || !dx_out || v == dx_out) return tr->fail(FFD_ERR_INVALID, "null or aliased buffer");
+  if (B < 1) return tr->fail(FFD_ERR_INVALID, "B=%d", B);
+  if (int rc = train_ready(tr)) return rc;
+  if (tr->fwd_B != B)
+    return tr->fail(FFD_ERR_STATE, "ffd_train_input_vjp at B=%d: the workspace holds %s", B,
+                    tr->fwd_B ? "the activations of another batch size" : "no forward's activations");
+  TRCHECK(hipSetDevice(tr->device));
+  if (tr->desc.kind == FFD_MODEL_TRANSFORMER) return tf_input_vjp(tr, v, dx_out, B, (hipStream_t)stream);
+  return mlp_input_vjp(tr, v, dx_out, mlp_work(tr->desc, B), B, (hipStream_t)stream);
 }
 
 int ffd_train_loss_grad(ffd_train* tr, const float* x0, const int64_t* index, const float* timesteps,
@@ -835,7 +904,7 @@ int ffd_train_loss_grad(ffd_train* tr, const float* x0, const int64_t* index, co
 int ffd_train_grad_sqnorm(ffd_train* tr, double* sqnorm_out, void* stream) {
   if (!tr) return FFD_ERR_INVALID;
   if (!sqnorm_out) return tr->fail(FFD_ERR_INVALID, "null buffer");
-  if (int rc = train_ready(tr)) return rc;
+  if (int rc = train_trainable(tr)) return rc;
   TRCHECK(hipSetDevice(tr->device));
   if (int rc = train_segments(tr)) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -850,9 +919,10 @@ int ffd_train_adamw(ffd_train* tr, const double* sqnorm, const ffd_adamw_cfg* cf
   AdamScalars S;
   if (adam_scalars(cfg, &S)) return tr->fail(FFD_ERR_INVALID, "bad AdamW configuration");
   if (cfg->max_norm > 0.0 && !sqnorm) return tr->fail(FFD_ERR_INVALID, "clipping needs the squared gradient norm");
-  if (int rc = train_ready(tr)) return rc;
+  if (int rc = train_trainable(tr)) return rc;
   TRCHECK(hipSetDevice(tr->device));
   if (int rc = train_segments(tr)) return rc;
+  tr->fwd_B = 0;  // the parameters move: the activations a forward kept are no longer theirs (ffd_train_input_vjp)
   hipLaunchKernelGGL(k_adamw_seg, dim3(tr->nseg), dim3(256), 0, (hipStream_t)stream, tr->segs, sqnorm, S);
   TRCHECK(hipGetLastError());
   return FFD_OK;
@@ -870,6 +940,7 @@ int ffd_train_step(ffd_train* tr, const float* x0, const int64_t* index, const f
   if (int rc = train_loss_grad(tr, x0, index, timesteps, mean_coeff, sigma, z, seed, sample_offset, likelihood_weighting,
                                per_sample_out, B, (hipStream_t)stream))
     return rc;
+  tr->fwd_B = 0;  // the update below moves the parameters: the kept activations are no longer theirs
   double* sq = tr->partial + tr->nseg;
   if (int rc = ffd_train_grad_sqnorm(tr, sq, stream)) return rc;
   return ffd_train_adamw(tr, sq, cfg, stream);
@@ -1283,6 +1354,32 @@ static int tf_backward(ffd_train* tr, int B, hipStream_t s) {
   TRLAUNCH(k_sum_over_l, dim3(cdiv(B * d, 256)), dim3(256), 0, s, dh, W + w.dtemb, B, L, d);
   TRCHECK(launch_dense_wgrad(W + w.dtemb, W + w.emb, tr->grd("time_encoder.dense.weight"), tr->grd("time_encoder.dense.bias"), B, d,
                              d, wg, s));
+  return FFD_OK;
+}
+
+// tf_backward for the input alone: no wgrad, no LayerNorm parameter gradient, no sums over the batch or the length; one
+// more dgrad through embedder.weight at the end
+static int tf_input_vjp(ffd_train* tr, const float* v, float* dx, int B, hipStream_t s) {
+  const ffd_model_desc& m = tr->desc;
+  const int L = m.max_len, C = m.n_channels, d = m.d_model, F = m.dim_feedforward, NL = m.num_layers, H = m.n_head, hd = d / H;
+  const int M = B * L;
+  const TfWork w = tf_work(m, B);
+  float* W = tr->work;
+  float *dh = W + w.dA, *t1 = W + w.dB, *t2 = W + w.dC;
+  TRCHECK(launch_dense_dgrad(v, tr->par("unembedder.weight"), nullptr, nullptr, dh, M, C, d, s));
+  for (int i = NL - 1; i >= 0; --i) {
+    const TfLayer p = tf_layer(tr, i, false);
+    float* lw = W + w.layer + (size_t)i * w.layer_size;
+    TRLAUNCH(k_ln_bwd, dim3(cdiv(M, 4)), dim3(256), 0, s, dh, lw + w.xh2, lw + w.rs2, p.n2w, t1, M, d);
+    TRCHECK(launch_dense_dgrad(t1, p.w2, lw + w.u, nullptr, W + w.du, M, d, F, s));
+    TRCHECK(launch_dense_dgrad(W + w.du, p.w1, nullptr, t1, t2, M, F, d, s));
+    TRLAUNCH(k_ln_bwd, dim3(cdiv(M, 4)), dim3(256), 0, s, t2, lw + w.xh1, lw + w.rs1, p.n1w, dh, M, d);
+    TRCHECK(launch_dense_dgrad(dh, p.out_w, nullptr, nullptr, t1, M, d, d, s));
+    TRLAUNCH(k_attn_bwd, dim3((unsigned)(B * H)), dim3(256), 0, s, lw + w.qkv, lw + w.o, t1, lw + w.lse, W + w.dqkv, L, H, hd);
+    TRCHECK(launch_dense_dgrad(W + w.dqkv, p.in_w, nullptr, dh, t2, M, 3 * d, d, s));
+    std::swap(dh, t2);
+  }
+  TRCHECK(launch_dense_dgrad(dh, tr->par("embedder.weight"), nullptr, nullptr, dx, M, d, C, s));
   return FFD_OK;
 }
 

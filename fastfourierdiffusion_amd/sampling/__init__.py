@@ -1,1 +1,2 @@
 from .forecast import ensemble_scores  # noqa: F401
+from .guidance import Guidance  # noqa: F401

@@ -58,6 +58,16 @@ the stream tags and transition q draws under 0xE0000000 + q.  Cost: r times the 
 ``resample=1`` takes the replacement path unchanged.  It does not run with the cache (whose gate assumes that time only
 falls) or under the ODE solvers.
 
+Guidance (extension): ``sample_conditional(..., guidance=Guidance(...))`` / ``impute(..., guidance=...)`` steer every
+Euler-Maruyama step by the gradient of the reconstruction loss through the score model (``sampling/guidance.py``;
+``ffd_sample_batch_guided``): per step the score, the seed of the gradient (``ffd_guide_seed``), the model's input
+vector-Jacobian product -- closed form for ``MixtureScoreModule``, the training backward without weight gradients for
+``ScoreModule`` and ``MLPScoreModule`` through a parameter-only native training object that the sampler owns -- and the
+guided score.  Draws as a conditional step without correctors: the predictor's, then the projection's slab (read only with
+``Guidance.replace``).  ``guidance=None`` is the replacement path, untouched.  It raises ``NotImplementedError`` for
+``LSTMScoreModule``, ``corrector_steps > 0``, an ODE solver, the cache, FreSca and ``resample > 1``.  What it buys on a
+forecast, and what a step costs, is in DESIGN.md section 6.
+
 Likelihoods (extension): ``log_likelihood`` integrates the same ODE the other way, from ``eps`` up to 1, with the
 divergence of its drift accumulated (Song et al. 2021, section 4.3), through ``ffd_loglik_batch``: log p(x) =
 ``SDE.prior_logp`` of the latent + the accumulated ``delta``.  No gradient of the network is taken: Hutchinson probes
@@ -97,6 +107,7 @@ from .. import _native as N
 from ..models.score_models import ScoreModule
 from ..schedulers.sde import SDE
 from ..utils.dataclasses import DiffusableBatch
+from .guidance import Guidance
 
 
 # solver name -> libffd's FFD_SOLVER_*
@@ -196,6 +207,7 @@ class DiffusionSampler:
         self.corrector_norm = corrector_norm
         self._injected = None
         self._multistep = None  # reverse_diffusion_step's (history, t, t_next) of its previous call
+        self._guide_net = None  # guided sampling: the model's parameter-only native training object and what it is bound to
 
     def inject_noise(self, draws) -> None:
         """Parity hook: take every N(0,1) draw (one (B,L,C) array for each batch's prior,
@@ -370,7 +382,7 @@ class DiffusionSampler:
                 if use_cache:  # the gate reads K, R of the current cache object (sampler.py:179-200)
                     model._native_cache_configure(model.cache)
                 cap = self._crf_capture_begin(ctx, device) if use_cache else None
-                cond_cfg = None
+                cond_cfg = guide = None
                 if cond is not None:  # this batch's slice of the observation
                     lo = batch_idx * self.sample_batch_size
                     shared = cond["obs"].shape[0] == 1
@@ -379,13 +391,18 @@ class DiffusionSampler:
                     cond_cfg = N.CondCfg(obs.data_ptr(), msk.data_ptr(),
                                          cond["std"].data_ptr() if cond["std"] is not None else None,
                                          1 if shared else batch_size, cond["domain"], int(cond["final_replace"]), 0)
+                    if cond.get("guide") is not None:
+                        g = cond["guide"]
+                        guide = (N.GuideCfg(float(g.scale), float(g.obs_var), float(g.rho), int(g.replace), 0),
+                                 self._guide_net_handle())
                 done = 0
                 while done < n_iter:
                     n, n_draws = self._next_chunk(done, n_iter, draws, followed)
                     z = self._draw(n_draws, X.shape, device) if n_draws else None
                     self._loop_call(ctx, X, (ts_c, num_diffusion_steps, step_size), done, n,
                                     (self.seed, sample_cursor, z.data_ptr() if z is not None else None),
-                                    (use_cache, (global_step + done) if use_cache else 0), cond_cfg, resample, jump, stream)
+                                    (use_cache, (global_step + done) if use_cache else 0), cond_cfg, resample, jump, stream,
+                                    guide)
                     if cap is not None:
                         self._crf_capture_collect(cap, global_step + done, n, ts, done)
                     done += n
@@ -424,11 +441,18 @@ class DiffusionSampler:
                 z[i].normal_()
         return z
 
-    def _loop_call(self, ctx, X, grid, first: int, n: int, noise, cache, cfg, resample: int, jump: int, stream) -> None:
+    def _loop_call(self, ctx, X, grid, first: int, n: int, noise, cache, cfg, resample: int, jump: int, stream,
+                   guide=None) -> None:
         """Iterations [first, first + n) of the native loop on ``X``, through the entry this sampler's configuration
         selects.  ``grid``: (timesteps, n_steps, step_size); ``noise``: (seed, sample_offset, z_inject); ``cache``:
         (use_cache, global_step0); ``cfg``: the batch's ``CondCfg`` or None."""
         corrector = (self.corrector_steps, self.snr, CORRECTOR_NORMS[self.corrector_norm])
+        if guide is not None:  # guided sampling: (GuideCfg, the network's training object or None)
+            guide_cfg, net = guide
+            rc = ctx.lib.ffd_sample_batch_guided(ctx.handle, net, X.data_ptr(), X.shape[0], *grid, first, n, *noise,
+                                                 C.byref(cfg), C.byref(guide_cfg), None, stream)
+            N.check(rc, ctx.handle, "ffd_sample_batch_guided")
+            return
         if self.solver != "euler_maruyama":  # deterministic given the prior: no noise arguments
             name, rest = "ffd_sample_batch_ode", (self._solver_code(), *cache)
         elif cfg is not None and resample > 1:  # (no cache: _check_resampling)
@@ -557,10 +581,73 @@ class DiffusionSampler:
                              "it needs solver='euler_maruyama'")
         self._check_resampling(resample, jump)
 
+    def _check_guidance(self, guidance, resample) -> None:
+        """What guided sampling refuses before any device work."""
+        if guidance is None:
+            return
+        if not isinstance(guidance, Guidance):
+            raise TypeError(f"guidance must be a Guidance or None, got {type(guidance).__name__}")
+        kind = getattr(self.score_model, "_kind", None)
+        if kind == N.FFD_MODEL_LSTM:
+            raise NotImplementedError("guided sampling needs the gradient through the score model: LSTMScoreModule has no "
+                                      "backward pass")
+        if kind not in (N.FFD_MODEL_TRANSFORMER, N.FFD_MODEL_MLP, N.FFD_MODEL_MIXTURE):
+            raise NotImplementedError(f"guided sampling is not defined for {type(self.score_model).__name__}")
+        if self.corrector_steps > 0:
+            raise NotImplementedError("guided sampling runs without correctors: corrector_steps must be 0")
+        if self.solver != "euler_maruyama":
+            raise NotImplementedError("guided sampling is an Euler-Maruyama step: it needs solver='euler_maruyama'")
+        if self.use_cache:
+            raise NotImplementedError("guided sampling cannot run with use_cache=True: the vector-Jacobian product is the "
+                                      "uncached network's")
+        if self.use_fresca:
+            raise NotImplementedError("guided sampling cannot run with use_fresca=True: the vector-Jacobian product is the "
+                                      "unscaled score's")
+        if resample > 1:
+            raise NotImplementedError("guided sampling has no resampled form: resample must be 1")
+
+    def _guide_net_handle(self):
+        """The native training object guided sampling takes the network's forward and input VJP from: one per sampler
+        (its model), bound to the parameters alone (``ffd_train_bind_params``) and bound again when their storage has
+        moved.  The mixture evaluates both in closed form: None."""
+        model = self.score_model
+        if getattr(model, "_kind", None) == N.FFD_MODEL_MIXTURE:
+            return None
+        lib = N.lib()
+
+        def check(rc, what):
+            if rc:
+                raw = lib.ffd_train_last_error(self._guide_net["handle"])
+                exc = {-1: AssertionError, -2: NotImplementedError}.get(rc, N.FFDError)
+                raise exc(f"libffd {what} failed (status {rc}): {raw.decode() if raw else ''}")
+
+        if self._guide_net is None:
+            dev = model.device
+            self._guide_net = {"handle": C.c_void_p(), "bound": None}
+            idx = dev.index if dev.index is not None else torch.cuda.current_device()
+            check(lib.ffd_train_create(C.byref(self._guide_net["handle"]), C.byref(model._desc()), 0.0, idx), "ffd_train_create")
+        ptrs = [(name, p.data_ptr()) for name, p in model.named_parameters()]
+        if ptrs != self._guide_net["bound"]:
+            for name, p in model.named_parameters():
+                if p.dtype != torch.float32 or not p.is_contiguous():
+                    raise AssertionError(f"{name} must be contiguous float32")
+                check(lib.ffd_train_bind_params(self._guide_net["handle"], name.encode(), p.data_ptr(), p.numel()),
+                      f"ffd_train_bind_params({name})")
+            self._guide_net["bound"] = ptrs
+        return self._guide_net["handle"]
+
+    def __del__(self):
+        try:
+            if self._guide_net is not None and self._guide_net["handle"]:
+                N.lib().ffd_train_destroy(self._guide_net["handle"])
+                self._guide_net = None
+        except Exception:
+            pass
+
     def sample_conditional(self, observed: torch.Tensor, mask: torch.Tensor, num_samples: int,
                            num_diffusion_steps: Optional[int] = None, resample: int = 1, jump: int = 1, *,
                            domain: Optional[str] = None, feature_std: Optional[torch.Tensor] = None,
-                           final_replace: bool = True) -> torch.Tensor:
+                           final_replace: bool = True, **extensions) -> torch.Tensor:
         """``sample`` conditioned on ``observed`` where ``mask`` is 1: after every state update of every reverse step the
         observation, noised to that step's time, replaces the observed part of the state (``SDE.cond_project``).
         ``observed`` lives in the diffused domain (for a spectral model: the packed, standardized spectrum of the series,
@@ -574,7 +661,15 @@ class DiffusionSampler:
         batching, cache lifecycle and prior are those of ``sample``.  Returns a CPU tensor in the diffused domain.
         A forecast is the prefix mask ``mask[:n_known] = 1``.  ``resample=r > 1`` runs every block of ``jump`` steps r
         times with a forward transition in between (the module docstring's "Resampling"), at r times the evaluations;
-        ``resample=1`` is plain replacement whatever ``jump`` is."""
+        ``resample=1`` is plain replacement whatever ``jump`` is.
+        ``guidance=None`` (keyword only, the one name ``extensions`` takes: a ``Guidance``; the module docstring's
+        "Guidance") steers every step by the gradient of the reconstruction loss through the score model instead of (or,
+        with ``Guidance.replace``, before) the replacement; ``final_replace`` still ends the run with one noiseless
+        replacement.  None: the replacement path, untouched."""
+        guidance = extensions.pop("guidance", None)
+        if extensions:
+            raise TypeError(f"sample_conditional() got an unexpected keyword argument {next(iter(extensions))!r}")
+        self._check_guidance(guidance, resample)
         self._check_conditional(resample, jump)
         if domain is None:
             domain = "frequency" if getattr(self.score_model, "scale_noise", False) else "time"
@@ -592,22 +687,23 @@ class DiffusionSampler:
         cond = dict(obs=observed.to(device).contiguous(), mask=mask.to(device).contiguous(),
                     std=feature_std.to(device).contiguous() if feature_std is not None else None,
                     domain=N.FFD_COND_FREQUENCY if domain == "frequency" else N.FFD_COND_TIME,
-                    final_replace=bool(final_replace), resample=resample, jump=jump)
+                    final_replace=bool(final_replace), resample=resample, jump=jump, guide=guidance)
         return self._sample(num_samples, num_diffusion_steps, cond)
 
     def impute(self, series_time: torch.Tensor, mask: torch.Tensor, num_samples: int,
                num_diffusion_steps: Optional[int] = None, resample: int = 1, jump: int = 1, *,
                feature_mean: Optional[torch.Tensor] = None, feature_std: Optional[torch.Tensor] = None,
-               final_replace: bool = True) -> torch.Tensor:
+               final_replace: bool = True, guidance: Optional[Guidance] = None) -> torch.Tensor:
         """Complete a time series with a model that diffuses its spectrum: ``series_time`` (L, C) or
         (num_samples, L, C) holds the series, ``mask`` (as in ``sample_conditional``) is 1 at its observed points.
         The unobserved points are zero-filled, the series goes through ``dft`` (with the dataset's ``feature_mean`` /
         ``feature_std`` (L, C): ``ffd_dft_standardize``), ``sample_conditional`` runs in the frequency domain, and the
         samples come back as TIME series (``ffd_unstandardize_idft`` / ``idft``) on the CPU.  Forecasting is the
         prefix mask: ``mask[:n_known] = 1`` draws ``num_samples`` continuations of the first ``n_known`` points.
-        ``resample`` / ``jump``: as in ``sample_conditional``."""
+        ``resample`` / ``jump`` / ``guidance``: as in ``sample_conditional``."""
         if (feature_mean is None) != (feature_std is None):
             raise ValueError("feature_mean and feature_std go together")
+        self._check_guidance(guidance, resample)
         self._check_conditional(resample, jump)  # (sample_conditional's refusals, before the transform below)
         L, Cn = self.max_len, self.n_channels
         series, m = _observation_and_mask(series_time, mask, num_samples, L, Cn, "series_time")
@@ -629,7 +725,8 @@ class DiffusionSampler:
         else:
             N.check(lib.ffd_dft(filled.data_ptr(), obs.data_ptr(), Bo, L, Cn, stream), None, "ffd_dft")
         out = self.sample_conditional(obs, m, num_samples, num_diffusion_steps, domain="frequency",
-                                      feature_std=std_d, final_replace=final_replace, resample=resample, jump=jump)
+                                      feature_std=std_d, final_replace=final_replace, resample=resample, jump=jump,
+                                      guidance=guidance)
         xf = out.to(device).contiguous()
         xt = torch.empty_like(xf)
         if mean_d is not None:

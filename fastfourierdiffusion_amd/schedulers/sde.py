@@ -332,6 +332,29 @@ class SDE(abc.ABC):
         N.check(rc, None, "ffd_cond_project")
         return SamplingOutput(prev_sample=x)
 
+    # -- reconstruction guidance (extension; sampling/guidance.py) --------
+    def guide_coeffs(self, timestep: float, scale: float = 1.0, obs_var: float = 1e-2, rho: float = 1.0):
+        """(alpha, sigma^2, lambda) at ``timestep`` in float64 on the host (``ffd_host_guide_coef``; no device needed):
+        the marginal's mean coefficient and variance (without G) and the guidance weight
+        lambda = scale / (obs_var + rho sigma^2 / (alpha^2 + sigma^2))."""
+        out = (C.c_double * 3)()
+        desc = self._desc()
+        rc = N.lib().ffd_host_guide_coef(C.byref(desc), float(timestep), float(scale), float(obs_var), float(rho), out)
+        N.check(rc, None, "ffd_host_guide_coef")
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def denoise(self, score: torch.Tensor, timestep: float, sample: torch.Tensor) -> torch.Tensor:
+        """Tweedie's estimate of the clean sample from a score at ``timestep``: x0hat = (x + sigma^2 G_l^2 score) / alpha,
+        (B, L, C) on the sample's device: a convenience in plain tensor arithmetic (alpha and sigma^2 from
+        ``guide_coeffs`` in float64), not the sampling path -- the guided loop forms the estimate inside ``ffd_guide_seed``,
+        whose ``x0hat_out`` has that kernel's own roundings."""
+        if sample.dim() != 3 or score.shape != sample.shape:
+            raise ValueError(f"score and sample must both be (B, L, C), got {tuple(score.shape)} and {tuple(sample.shape)}")
+        alpha, sigma2, _ = self.guide_coeffs(timestep)
+        G = self.G.to(device=sample.device, dtype=sample.dtype)
+        c = (sigma2 * (G * G)).reshape(1, -1, 1)
+        return (sample + c * score) / alpha
+
     def transition_coeffs(self, timestep_from: float, timestep_to: float):
         """(a, sg) of the forward transition x_t = a x_s + (sg G) z from s = ``timestep_from`` to t = ``timestep_to`` >= s,
         in float64 on the host (``ffd_host_transition_coef``; no device needed)."""

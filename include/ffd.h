@@ -384,9 +384,65 @@ int ffd_mixture_score(const ffd_sde_desc* sde, const float* x, const float* t, i
                       const float* log_weights, const float* variance, const float* G, float* score_out, int B, int K,
                       int L, int C, float* work, size_t work_floats, void* stream);
 int ffd_host_mixture_check(const float* means, const float* log_weights, const float* variance, int K, int L, int C);
+/* The vector-Jacobian product of that score with respect to x: out = J^T v, J = d score / d x, v and out (B, L, C).
+ * J is symmetric, J_jk = alpha^2 Cov_r(mu_j, mu_k) / (c_j c_k) - delta_jk / c_j, so with q = v / c
+ *     J^T v = (alpha^2 / c) (.) (sum_i r_i mu_i p_i - m sum_i r_i p_i) - q,   p_i = (mu_i - x / alpha) . q,   m = sum_i r_i mu_i
+ * (the covariance does not see the shift inside p_i, and p_i = -(x - alpha mu_i) . q / alpha reuses the difference the
+ * logit forms).  A pass of its own with the tiling, the online softmax and the slice order of ffd_mixture_score: it
+ * carries sum e p and, on the fp32 matrix cores, sum e p mu next to that call's sums, so it is bit-identical from run
+ * to run and a row's result does not depend on B.  work: at least ffd_mixture_vjp_work_floats(B, K, L, C) floats (0 for
+ * a shape the call refuses).  out may be v or x.  Arguments, limits and error codes as ffd_mixture_score (v must not be
+ * NULL). */
+size_t ffd_mixture_vjp_work_floats(int B, int K, int L, int C);
+int ffd_mixture_score_vjp(const ffd_sde_desc* sde, const float* x, const float* t, int t_stride, const float* means,
+                          const float* log_weights, const float* variance, const float* G, const float* v, float* out,
+                          int B, int K, int L, int C, float* work, size_t work_floats, void* stream);
 /* Host only: the kernel's rows per tile, components per tile, components per slice and the largest L * C (any pointer
  * may be NULL). */
 int ffd_mixture_tiling(int* row_tile, int* comp_tile, int* slice, int* max_dim);
+
+/* ---- reconstruction guidance (an extension: Ho et al. 2022, Chung et al. 2023 "DPS", Kollovieh et al. 2023
+ * "observation self-guidance"; the conditioning that needs the gradient through the score model) ----
+ * At time t, with alpha(t), sigma(t) as in ffd_cond_project, c_l = sigma^2 G_l^2 and s = score(x, t):
+ *     x0hat = (x + c (.) s) / alpha                                   Tweedie's denoised estimate
+ *     r     = mask (.) (x0hat - obs)                                  FFD_COND_TIME
+ *     r     = mask (.) idft((x0hat - obs) (.) std)                    FFD_COND_FREQUENCY (std may be NULL)
+ *     loss  = 1/2 sum r^2                                             per sample
+ *     u     = d loss / d x0hat = mask (.) r                           time domain
+ *     u     = std (.) W (.) dft(mask (.) r)                           frequency domain
+ *     g     = grad_x loss = (u + J^T (c (.) u)) / alpha,  J = d s / d x
+ *     s~    = s - lambda g,   lambda(t) = scale / (obs_var + rho sigma^2 / (alpha^2 + sigma^2))
+ * The packed layout is not orthonormal: a bin other than DC (and Nyquist, even L) appears once where the Hermitian
+ * image holds it twice, so the adjoint of idft is W (.) dft with W = 1 on the DC row, 1 on the Nyquist row of an even L
+ * and 2 on every other packed row (real and imaginary parts alike).
+ *
+ * ffd_guide_seed writes u and v = c (.) u, the cotangent of the score model's input VJP (ffd_mixture_score_vjp,
+ * ffd_train_input_vjp).  One launch: a workgroup owns a sample's (L x channel-group) slab in LDS for both transforms --
+ * the Hermitian image, the butterflies and the 1 / sqrt(L) factors of ffd_cond_project's general-length kernel, at
+ * every length -- and walks the sample's channel groups in order.  Per packed element, every product / sum a separate
+ * fp32 rounding: c = sigma^2 (G_l G_l); x0hat = (x + c s) / alpha; d = x0hat - obs; d = d std (std given); r = mask w
+ * (w = d in the time domain, the scaled inverse transform otherwise); u = mask r, or (V / sqrt(L)) W std behind the
+ * forward transform; v = c u.  alpha and sigma^2 are formed on the host in double at t and rounded once (VE: alpha = 1).
+ *   loss_out   NULL or B doubles: 1/2 sum r^2 in fp64, per-thread partial sums in a fixed element order, then a fixed
+ *              tree: bit-identical from run to run
+ *   x0hat_out  NULL or (B, L, C): the denoised estimate in the domain of x
+ * obs, mask, std, obs_batch, domain as in ffd_cond_project.  A zero mask gives exact zeros and loss 0.  Context-free,
+ * stream ordered, no host synchronisation, no atomics; a sample's result does not depend on B, on its place in the batch
+ * or on obs_batch.
+ * FFD_ERR_INVALID before any device work: a null pointer (std, loss_out and x0hat_out excepted), B, L, C < 1, obs_batch
+ * not 1 or B, an unknown domain, std with the time domain, a non-finite or negative t, an output aliasing an input or
+ * another output; then FFD_ERR_UNSUPPORTED for an unknown SDE or a frequency-domain length outside ffd_cond_project's. */
+int ffd_guide_seed(const ffd_sde_desc* sde, const float* x, const float* score, const float* obs, const float* mask,
+                   const float* std, const float* G, double t, int obs_batch, int domain, int B, int L, int C,
+                   float* u_out, float* v_out, double* loss_out, float* x0hat_out, void* stream);
+/* score_out = score - coef ((u + jtv) / alpha), pointwise over n elements, every product / sum / quotient a separate
+ * fp32 rounding; score_out may be score.  FFD_ERR_INVALID: a null pointer, n < 1, alpha not finite or 0, coef not
+ * finite. */
+int ffd_guide_combine(const float* score, const float* u, const float* jtv, float alpha, float coef, float* score_out,
+                      size_t n, void* stream);
+/* Host only, float64: coef_out = (alpha(t), sigma(t)^2, lambda(t)).  FFD_ERR_INVALID: a null pointer, a non-finite or
+ * negative t, scale, obs_var or rho, or a zero denominator; then FFD_ERR_UNSUPPORTED for an unknown SDE. */
+int ffd_host_guide_coef(const ffd_sde_desc* sde, double t, double scale, double obs_var, double rho, double coef_out[3]);
 
 /* SDE.prior_sampling (sde.py:79-87, 125-127): x <- G (.) z  (VE: * sigma_max);
  * z == NULL draws on device (Philox stream tag 0xFFFFFFFF). */
@@ -800,6 +856,18 @@ int ffd_train_bind(ffd_train* tr, const char* name, float* param, float* grad, f
 /* The training forward (it keeps what the backward needs) at x (B, L, C) and the per-sample times: a second
  * implementation of ffd_score_forward_ts on the bound parameters, for tests. */
 int ffd_train_forward(ffd_train* tr, const float* x, const float* timesteps, float* score_out, int B, void* stream);
+/* A parameter-only binding, for inference use of the training forward and of ffd_train_input_vjp: no gradient and no
+ * moments.  While any trainable tensor is bound this way, ffd_train_loss_grad, ffd_train_step, ffd_train_adamw and
+ * ffd_train_grad_sqnorm answer FFD_ERR_STATE before any device work.  ffd_train_bind binds the tensor fully again. */
+int ffd_train_bind_params(ffd_train* tr, const char* name, float* param, size_t n);
+/* The vector-Jacobian product of the score with respect to its INPUT: dx_out = J^T v, J = d score / d x, v and dx_out
+ * (B, L, C), through the activations that the object's last ffd_train_forward or ffd_train_loss_grad at this B left
+ * in the workspace; FFD_ERR_STATE if there was none, if it failed, if B differs, or if ffd_train_adamw / ffd_train_step
+ * has updated the parameters since (the activations are then no longer those of the weights the dgrads read).
+ * It is the backward chain of ffd_train_loss_grad without any weight gradient, plus one more dense dgrad through
+ * embedder.weight (the MLP: M = B, K = L C).  It reads parameters only: no gradient buffer, moment or parameter is
+ * written.  v is not modified; dx_out must not be v.  Stream ordered, no host synchronisation. */
+int ffd_train_input_vjp(ffd_train* tr, const float* v, float* dx_out, int B, void* stream);
 /* Forward + backward for one batch: perturbation, training forward, per-sample losses (B doubles, as ffd_sm_eval_batch
  * with reduce_mean = 1) and the gradient of their mean into every bound gradient buffer (overwritten, not accumulated).
  * timesteps, mean_coeff, sigma: (B), in batch order.  index == NULL: x0 is (B, L, C) and sample b draws as global sample
@@ -1013,6 +1081,39 @@ int ffd_sample_batch_resample(ffd_ctx* ctx, float* x, int B, const float* timest
                               int first_visit, int n_visits, int jump, int resample, int n_corrector, float snr, int norm,
                               uint64_t seed, uint64_t sample_offset, const float* z_inject, const ffd_cond_cfg* cond,
                               void* stream);
+
+/* Guided conditional sampling (see ffd_guide_seed): Euler-Maruyama steps whose score is steered by the gradient of
+ * the reconstruction loss through the score model.  Reverse step i at t = timesteps[i]:
+ *   1. s = score(x, t);  2. ffd_guide_seed -> u, v, the loss;  3. jtv = J^T v (the score model's input VJP);
+ *   4. ffd_guide_combine with ffd_host_guide_coef(t)'s alpha and lambda -> s~;  5. the stand-alone ffd_sde_step with s~
+ *   (stream tag i);  6. guide->replace != 0: one ffd_cond_project at t (stream tag 0xC0000000 + i).
+ * The tags are those of ffd_sample_batch_cond with n_corrector = 0.  When the call's last step is the grid's last step
+ * and cond->final_replace != 0, one noiseless projection ends the run.
+ *   ctx        the SDE and G; for FFD_MODEL_MIXTURE also the score and its VJP (net is ignored)
+ *   net        the transformer and the MLP: an ffd_train bound to the context's parameters (ffd_train_bind_params is
+ *              enough) supplies the forward and the VJP -- FFD_ERR_STATE when NULL, FFD_ERR_INVALID when its descriptor
+ *              differs from the context's.  The LSTM has no backward: FFD_ERR_UNSUPPORTED.
+ *   cond       required: obs / mask / std / obs_batch / domain / final_replace as in ffd_sample_batch_cond
+ *   guide      required: scale, obs_var, rho >= 0 of lambda(t); obs_var is in the units of the diffused domain
+ *   z_inject   NULL or (n_run, 1, 2, B, L, C): per step the predictor's draw, then the projection's slab (read only with
+ *              replace)
+ *   loss_out   NULL or (n_run, B) doubles on the device: the loss BEFORE each step of the call
+ * The shared loop rules hold: no host synchronisation, and a run split over calls at any step boundary gives the bits
+ * of one call.  scale = 0 with replace is ffd_sample_batch_cond(n_corrector = 0, use_cache = 0) bit for bit on the
+ * mixture.  No cache argument (the context's cache state is left untouched), no correctors, ODE solvers or resampling;
+ * FFD_ERR_STATE before any device work while FreSca is on.
+ * FFD_ERR_INVALID before any device work: the shared cases, a NULL cond or guide, ffd_cond_project's cases, a
+ * non-finite or negative scale, obs_var or rho, a step of the run whose lambda has a zero denominator, n_steps >
+ * 0x3FFFFFF0, x aliasing z_inject. */
+typedef struct {
+  double scale, obs_var, rho;
+  int32_t replace;
+  int32_t reserved;
+} ffd_guide_cfg;
+int ffd_sample_batch_guided(ffd_ctx* ctx, ffd_train* net, float* x, int B, const float* timesteps, int n_steps,
+                            float step_size, int first_step, int n_run, uint64_t seed, uint64_t sample_offset,
+                            const float* z_inject, const ffd_cond_cfg* cond, const ffd_guide_cfg* guide, double* loss_out,
+                            void* stream);
 
 /* How the context's last sampling-loop call ran: *parts_out = 2 as two CU partitions (ffd_tune "partitions"), 1 on the
  * caller's stream alone. */

@@ -1,6 +1,7 @@
 """How far conditional sampling by replacement is from the true conditional, where the true conditional is known.
 
     python3 tools/imputation_quality.py [out.json]            (default: profiles/imputation_quality.json)
+    python3 tools/imputation_quality.py --guided-only [out.json]   the guided rows alone, merged into the file's other rows
 
 The synthetic set of tools/solver_quality.py (4096 series, L = 187, C = 1, four families of sinusoid sums) defines a
 Gaussian mixture in the TIME domain: ``MixtureScoreModule.from_data`` with a bandwidth, no Fourier noise scaling, so the
@@ -18,6 +19,10 @@ the first half observed) and a random 50 % mask (an imputation), M completions o
   (a') by ``sample_conditional(..., resample=r, jump=j)`` (resampling, "time travel") without corrector at EQUAL SCORE
       EVALUATIONS as rows of (a): 20 steps x r = 10 and 50 x 4 against the 200-evaluation rows, 200 x 5 against the
       1000-evaluation row, each with jump 1, 2 and 10;
+  (a'') by ``sample_conditional(..., guidance=Guidance(scale, obs_var = bandwidth^2, rho = 1, replace))`` (reconstruction
+      guidance through the score's closed-form Jacobian) without corrector: 50 / 200 / 1000 steps at scale 1, scale 0.5 and
+      2 at 200 steps, each with and without the replacement behind the step, the same seeds; a guided step is one score
+      evaluation and one vector-Jacobian product;
   (b) from the exact conditional, three seeds: the FLOOR, its spread the resolution of the comparison,
 and scored against the truth with ``ensemble_scores``: the mean CRPS over the unobserved points and the energy score,
 averaged over the truths, and the share of unobserved truths inside the 5 % .. 95 % band.  Replacement is known to be an
@@ -42,6 +47,7 @@ SEEDS = (1, 2, 3)
 SNR = 0.16
 RESAMPLED = ((20, 10), (50, 4), (200, 5))  # (steps, resample): 200, 200 and 1000 score evaluations
 JUMPS = (1, 2, 10)
+GUIDED = ((50, 1.0), (200, 1.0), (1000, 1.0), (200, 0.5), (200, 2.0))  # (steps, scale)
 
 
 def masks():
@@ -73,9 +79,9 @@ def spread(rows):
                 "max": float(max(r[k] for r in rows))} for k in rows[0]}
 
 
-def main(out_path):
+def main(out_path, guided_only=False):
     from fastfourierdiffusion_amd.models.score_models import MixtureScoreModule
-    from fastfourierdiffusion_amd.sampling import ensemble_scores
+    from fastfourierdiffusion_amd.sampling import Guidance, ensemble_scores
     from fastfourierdiffusion_amd.sampling.sampler import DiffusionSampler
     from fastfourierdiffusion_amd.schedulers.sde import VPScheduler
 
@@ -103,8 +109,33 @@ def main(out_path):
               "members": M, "steps": list(STEPS), "seeds": list(SEEDS), "snr": SNR,
               "resampled": "sample_conditional(resample=r, jump=j), no corrector: steps x r score evaluations",
               "resampled_steps_r": [list(v) for v in RESAMPLED], "jumps": list(JUMPS), "truths": {}}
+    if guided_only:  # every other row stays what the file holds
+        with open(out_path) as f:
+            result = json.load(f)
+    result["guided"] = ("sample_conditional(guidance=Guidance(scale, obs_var=bandwidth^2, rho=1, replace)), no corrector: "
+                        "one score evaluation and one vector-Jacobian product per step")
+    result["guided_steps_scale"] = [list(v) for v in GUIDED]
     for kind, name, mask in [(k, n, mk) for k in truths for n, mk in masks().items()]:
         held = truths[kind]
+        observed = held[:, None].expand(N_HELD, M, L, CH).reshape(N_HELD * M, L, CH).contiguous()
+        guided = {}
+        for replace in (False, True):
+            table = {}
+            for steps, scale in GUIDED:
+                rows = []
+                for seed in SEEDS:
+                    s = DiffusionSampler(score_model=model, sample_batch_size=N_HELD * M, rng="philox", seed=seed)
+                    out = s.sample_conditional(observed, mask, N_HELD * M, steps, domain="time", final_replace=True,
+                                               guidance=Guidance(scale, BANDWIDTH ** 2, 1.0, replace))
+                    rows.append(score(out.reshape(N_HELD, M, L, CH), held, mask))
+                table[f"steps_{steps}_scale_{scale:g}"] = {"score_evaluations": steps, "vjps": steps, **spread(rows)}
+                print(kind, name, f"guided replace={replace} steps={steps} scale={scale:g}",
+                      {k: round(v["mean"], 5) for k, v in table[f"steps_{steps}_scale_{scale:g}"].items() if isinstance(v, dict)},
+                      flush=True)
+            guided[f"replace_{int(replace)}"] = table
+        if guided_only:
+            result["truths"][kind][name]["guided"] = guided
+            continue
         floor_rows, ess = [], None
         for seed in SEEDS:
             draws, r = exact_conditional(train, held, mask, seed)
@@ -113,7 +144,6 @@ def main(out_path):
         entry = {"observed_points": int(mask.sum()), "posterior_effective_components_mean": ess,
                  "floor": spread(floor_rows), "replacement": {}}
         print(kind, name, "floor", {k: round(v["mean"], 5) for k, v in entry["floor"].items()}, flush=True)
-        observed = held[:, None].expand(N_HELD, M, L, CH).reshape(N_HELD * M, L, CH).contiguous()
         for n_corr in (0, 1):
             table = {}
             for steps in STEPS:
@@ -141,6 +171,7 @@ def main(out_path):
                 print(kind, name, f"resampled steps={steps} r={r} jump={jump}",
                       {k: round(v["mean"], 5) for k, v in table[f"jump_{jump}"].items() if isinstance(v, dict)}, flush=True)
             entry["resampled"][f"steps_{steps}_r_{r}"] = table
+        entry["guided"] = guided
         result["truths"].setdefault(kind, {})[name] = entry
     os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
     with open(out_path, "w") as f:
@@ -150,4 +181,5 @@ def main(out_path):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "imputation_quality.json"))
+    argv = [a for a in sys.argv[1:] if a != "--guided-only"]
+    main(argv[0] if argv else os.path.join(ROOT, "profiles", "imputation_quality.json"), "--guided-only" in sys.argv[1:])
