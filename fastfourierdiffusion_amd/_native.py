@@ -64,6 +64,13 @@ class GuideCfg(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class ClassCfg(C.Structure):
+    """ffd_class_cfg: the table (device, read live), the device labels with their host copy (both None: every sample
+    null), and the classifier-free guidance scale g of s_u + g (s_c - s_u)."""
+    _fields_ = [("table", C.c_void_p), ("labels", C.c_void_p), ("labels_host", C.c_void_p), ("n_classes", C.c_int32),
+                ("n_labels", C.c_int32), ("guidance_scale", C.c_float), ("reserved", C.c_int32)]
+
+
 class CacheCfg(C.Structure):
     _fields_ = [("K", C.c_int32), ("R", C.c_int32)]
 
@@ -237,6 +244,14 @@ SIGNATURES = {
                                                     C.POINTER(CondCfg), _P]),
     "ffd_sample_batch_guided": (C.c_int, [_P, _P, _P, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_int, C.c_uint64,
                                           C.c_uint64, _P, C.POINTER(CondCfg), C.POINTER(GuideCfg), _P, _P]),
+    "ffd_class_enable": (C.c_int, [_P, C.POINTER(ClassCfg)]),
+    "ffd_class_disable": (C.c_int, [_P]),
+    "ffd_class_temb": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "ffd_cfg_combine": (C.c_int, [_P, _P, C.c_float, C.c_size_t, _P]),
+    "ffd_class_drop": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_uint64, C.c_uint64, _P, _P]),
+    "ffd_class_table_grad": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "ffd_train_classes": (C.c_int, [_P, C.c_int]),
+    "ffd_train_labels": (C.c_int, [_P, _P, C.c_size_t, C.c_double]),
     "ffd_flops_per_sample_step": (C.c_double, [_P, C.c_int]),
     "ffd_ffn_flops_per_launch": (C.c_double, [_P, C.c_int]),
     "ffd_kernel_timing_begin": (C.c_int, [_P, C.c_uint32, C.c_int]),

@@ -112,6 +112,10 @@ struct ffd_ctx {
   ffd_crf_capture_cfg crf_cap{};
   ffd_fresca_cfg fcfg{};
   Grow<float> score2, fwork;
+  // class conditioning / classifier-free guidance (ffd_class_enable): the table and the labels stay the caller's
+  bool class_on = false;
+  ffd_class_cfg ccls{};
+  Grow<float> cls_temb, cls_x;  // (B | 2 B, d) embedding rows of one evaluation; the stacked batch (2 B, L, C)
   Grow<float> sm_noisy;  // the perturbed batch of ffd_sm_eval_batch
   Grow<float> ode_xp, ode_d1;  // Heun's predicted state and predictor drift (ffd_sample_batch_ode)
   Grow<float> ode_hist;        // the multistep solvers' history quantity q of the previous interval
@@ -1022,6 +1026,33 @@ static int check_ready(ffd_ctx* ctx, int B) {
   return FFD_OK;
 }
 
+// Class conditioning (include/ffd.h ffd_class_enable): does an evaluation run the stacked batch of 2 B rows, what an
+// entry that honours the state checks before anything else, and what the entries without a class form answer
+static bool class_stacked(const ffd_ctx* ctx) {
+  return ctx->class_on && ctx->ccls.guidance_scale != 1.f && ctx->ccls.guidance_scale != 0.f;
+}
+static int class_check(ffd_ctx* ctx, const char* who, int B, bool cached) {
+  if (!ctx->class_on) return FFD_OK;
+  if (cached)
+    return ctx->fail(FFD_ERR_STATE, "%s: class conditioning is on (ffd_class_disable): the E2-CRF cache shares batch element "
+                     "0's rows, which carry that sample's label", who);
+  if (ctx->ccls.labels && ctx->ccls.n_labels != B)
+    return ctx->fail(FFD_ERR_INVALID, "%s: %d labels for a batch of %d", who, ctx->ccls.n_labels, B);
+  return FFD_OK;
+}
+static int class_refuse(ffd_ctx* ctx, const char* who) {
+  if (!ctx->class_on) return FFD_OK;
+  return ctx->fail(FFD_ERR_STATE, "%s has no class-conditional form: class conditioning is on (call ffd_class_disable)", who);
+}
+// per-sample embeddings (B, d) -> + table[label_b], in place (the conditional branch)
+static int class_add_rows(ffd_ctx* ctx, float* temb, int B, hipStream_t s) {
+  if (!ctx->class_on) return FFD_OK;
+  const ffd_class_cfg& c = ctx->ccls;
+  HIPCHECK(launch_class_temb(temb, ctx->desc.d_model, c.table, c.n_classes, c.labels, B, ctx->desc.d_model, 0, temb, nullptr,
+                             nullptr, 0, s));
+  return FFD_OK;
+}
+
 // temb[n][d] for the n timesteps ts on the device, or (ts == nullptr, n = 1) for the scalar t
 static int time_embed(ffd_ctx* ctx, const float* ts, float t, int n, float* temb, hipStream_t s) {
   const ModelWeights& w = ctx->model;
@@ -1042,6 +1073,8 @@ static int score_forward(ffd_ctx* ctx, const float* x, const float* ts, float t,
   hipStream_t s = (hipStream_t)stream;
   float* temb = ts ? ctx->temb_b.p : ctx->temb1;
   if (int rc = time_embed(ctx, ts, ts ? 0.f : t, ts ? B : 1, temb, s)) return rc;
+  if (ts)
+    if (int rc = class_add_rows(ctx, temb, B, s)) return rc;
   return forward_impl(ctx, x, temb, ts ? ctx->desc.d_model : 0, score_out, crf_out, B, n_rec, s);
 }
 
@@ -1055,6 +1088,7 @@ static int check_cached(ffd_ctx* ctx) {
 
 int ffd_score_forward(ffd_ctx* ctx, const float* x, float t, float* score_out, int B, void* stream) {
   if (!ctx) return FFD_ERR_INVALID;
+  if (int rc = class_refuse(ctx, "ffd_score_forward (one time for the batch)")) return rc;
   if (int rc = check_ready(ctx, B)) return rc;
   if (!x || !score_out) return ctx->fail(FFD_ERR_INVALID, "null buffer");
   return score_forward(ctx, x, nullptr, t, score_out, nullptr, B, -1, stream);
@@ -1063,6 +1097,7 @@ int ffd_score_forward(ffd_ctx* ctx, const float* x, float t, float* score_out, i
 int ffd_score_forward_cached(ffd_ctx* ctx, const float* x, float t, float* score_out, float* crf_out, int B,
                              int n_recompute, void* stream) {
   if (!ctx) return FFD_ERR_INVALID;
+  if (int rc = class_refuse(ctx, "ffd_score_forward_cached")) return rc;
   if (int rc = check_ready(ctx, B)) return rc;
   if (int rc = check_cached(ctx)) return rc;
   if (!x || !score_out) return ctx->fail(FFD_ERR_INVALID, "null buffer");
@@ -1074,6 +1109,7 @@ int ffd_score_forward_cached(ffd_ctx* ctx, const float* x, float t, float* score
 int ffd_score_forward_ts(ffd_ctx* ctx, const float* x, const float* timesteps, float* score_out, float* crf_out,
                          int B, int n_recompute, void* stream) {
   if (!ctx) return FFD_ERR_INVALID;
+  if (int rc = class_check(ctx, "ffd_score_forward_ts", B, n_recompute >= 0)) return rc;
   if (int rc = check_ready(ctx, B)) return rc;
   if (!x || !timesteps || !score_out) return ctx->fail(FFD_ERR_INVALID, "null buffer");
   if (n_recompute >= 0) {
@@ -1090,6 +1126,7 @@ int ffd_sm_eval_batch(ffd_ctx* ctx, const float* x0, const float* timesteps, con
                       const float* z, uint64_t seed, uint64_t sample_offset, int likelihood_weighting, int reduce_mean,
                       double* per_sample_out, int B, void* stream) {
   if (!ctx) return FFD_ERR_INVALID;
+  if (int rc = class_check(ctx, "ffd_sm_eval_batch", B, false)) return rc;
   if (int rc = check_ready(ctx, B)) return rc;
   if (!x0 || !timesteps || !mean_coeff || !sigma || !per_sample_out) return ctx->fail(FFD_ERR_INVALID, "null buffer");
   const ffd_model_desc& m = ctx->desc;
@@ -1100,6 +1137,7 @@ int ffd_sm_eval_batch(ffd_ctx* ctx, const float* x0, const float* timesteps, con
   hipStream_t s = (hipStream_t)stream;
   HIPCHECK(launch_sm_perturb(x0, ctx->sm_noisy.p, mean_coeff, sigma, ctx->G_dev, z, seed, sample_offset, B, L, C, s));
   if (int rc = time_embed(ctx, timesteps, 0.f, B, ctx->temb_b.p, s)) return rc;
+  if (int rc = class_add_rows(ctx, ctx->temb_b.p, B, s)) return rc;
   if (int rc = forward_impl(ctx, ctx->sm_noisy.p, ctx->temb_b.p, m.d_model, ctx->score.p, nullptr, B, -1, s)) return rc;
   HIPCHECK(launch_sm_loss(ctx->score.p, sigma, ctx->G_dev, z, seed, sample_offset, likelihood_weighting, reduce_mean,
                           per_sample_out, B, L, C, s));
@@ -1119,6 +1157,32 @@ int ffd_fresca_enable(ffd_ctx* ctx, const ffd_fresca_cfg* cfg) {
 int ffd_fresca_disable(ffd_ctx* ctx) {
   if (!ctx) return FFD_ERR_INVALID;
   ctx->fresca_on = false;
+  return FFD_OK;
+}
+
+int ffd_class_enable(ffd_ctx* ctx, const ffd_class_cfg* cfg) {
+  if (!ctx) return FFD_ERR_INVALID;
+  if (!cfg) return ctx->fail(FFD_ERR_INVALID, "null class config");
+  if (ctx->desc.kind == FFD_MODEL_MIXTURE)
+    return ctx->fail(FFD_ERR_UNSUPPORTED, "the mixture kind has no embedding to condition (its classes are its components)");
+  if (!cfg->table || cfg->n_classes < 1) return ctx->fail(FFD_ERR_INVALID, "class config: table and n_classes >= 1 are required");
+  if (!std::isfinite(cfg->guidance_scale)) return ctx->fail(FFD_ERR_INVALID, "guidance_scale must be finite");
+  if (cfg->labels) {
+    if (!cfg->labels_host || cfg->n_labels < 1)
+      return ctx->fail(FFD_ERR_INVALID, "device labels need their host copy (labels_host) and n_labels >= 1");
+    for (int i = 0; i < cfg->n_labels; ++i)
+      if (cfg->labels_host[i] < -1 || cfg->labels_host[i] > cfg->n_classes)
+        return ctx->fail(FFD_ERR_INVALID, "label %d of sample %d outside [-1, %d]", cfg->labels_host[i], i, cfg->n_classes);
+  }
+  ctx->ccls = *cfg;
+  ctx->ccls.labels_host = nullptr;  // (validated, not kept)
+  ctx->class_on = true;
+  return FFD_OK;
+}
+
+int ffd_class_disable(ffd_ctx* ctx) {
+  if (!ctx) return FFD_ERR_INVALID;
+  ctx->class_on = false;
   return FFD_OK;
 }
 
@@ -1289,8 +1353,11 @@ static int fresca_score(ffd_ctx* ctx, double t, int B, hipStream_t s, const floa
 template <class EntryChecks>
 static int loop_begin(ffd_ctx* ctx, const char* who, const float* x, int B, const float* timesteps, int n_steps, int n_iter,
                       int first, int n_run, float step_size, int use_cache, hipStream_t s, EntryChecks entry_checks) {
-  int rc = check_ready(ctx, B);
+  int rc = class_check(ctx, who, B, use_cache != 0);  // (first: raised without a device as well)
   if (rc) return rc;
+  if ((rc = check_ready(ctx, B))) return rc;
+  const int rows = class_stacked(ctx) ? 2 * B : B;  // what one evaluation runs at
+  if (rows != B && (rc = check_ready(ctx, rows))) return rc;
   if (!x || !timesteps || n_iter < 1 || first < 0 || n_run < 0 || n_run > n_iter - first)
     return ctx->fail(FFD_ERR_INVALID, "bad argument to %s (n_steps=%d first=%d run=%d of %d)", who, n_steps, first, n_run,
                      n_iter);
@@ -1300,7 +1367,11 @@ static int loop_begin(ffd_ctx* ctx, const char* who, const float* x, int B, cons
   if (use_cache && !ctx->cache_enabled) return ctx->fail(FFD_ERR_STATE, "%s: use_cache without ffd_cache_enable", who);
   if ((rc = entry_checks())) return rc;
   HIPCHECK(hipSetDevice(ctx->device));
-  if ((rc = ensure_workspace(ctx, B))) return rc;
+  if ((rc = ensure_workspace(ctx, rows))) return rc;
+  if (ctx->class_on) {
+    if ((rc = ensure(ctx, ctx->cls_temb, (size_t)rows * ctx->desc.d_model))) return rc;
+    if (rows != B && (rc = ensure(ctx, ctx->cls_x, (size_t)rows * ctx->desc.max_len * ctx->desc.n_channels))) return rc;
+  }
   if ((rc = ensure_fresca_work(ctx, B))) return rc;
   if ((rc = ensure_time_table(ctx, timesteps, n_steps, s))) return rc;
   ctx->ms_solver = -1;
@@ -1373,7 +1444,7 @@ static PartDecision partition_decide(ffd_ctx* ctx, int B, int use_cache) {
   PartDecision d{};
   if (g_partitions == 0 || g_cu_budget > 0 || B < 2) return d;
   if (ctx->desc.kind != FFD_MODEL_TRANSFORMER || !ctx->finalized || !ctx->packs_made() || use_cache || ctx->fresca_on ||
-      ctx->time_mask)
+      ctx->class_on || ctx->time_mask)
     return d;
   if (hipSetDevice(ctx->device) != hipSuccess || ensure_partitions(ctx) != FFD_OK || ctx->part_budget <= 0) return d;
   const int budget = ctx->part_budget;
@@ -1511,9 +1582,31 @@ static int loop_evaluate(ffd_ctx* ctx, const float* xin, int row, double t, int 
     if (ctx->crf_cap_on) crf_capture_targets(ctx, gstep, rest, &crf_dst, &crf_copy);
   }
   *hidden = nullptr;
-  if (int rc = forward_impl(ctx, xin, ctx->temb_tab.p + (size_t)row * m.d_model, 0, ctx->score.p, crf_dst, B, n_rec, s,
-                            fuse ? hidden : nullptr))
-    return rc;
+  const float* trow = ctx->temb_tab.p + (size_t)row * m.d_model;
+  if (ctx->class_on) {
+    // the evaluation's (rows, d) embeddings from the time-table row: the conditional block (g = 0: null labels), and for
+    // any g but 0 and 1 the null block behind it, with x copied into both halves of the stacked batch in the same launch.
+    // The combine runs on the final hidden rows where the tail is fused, else on the score (the unembedding is affine and
+    // the weights sum to 1); the tail and FreSca then see B rows as ever.  (No cache here: class_check refused it.)
+    const ffd_class_cfg& c = ctx->ccls;
+    const int d = m.d_model;
+    const bool stacked = class_stacked(ctx);
+    const size_t nx = (size_t)B * m.max_len * m.n_channels;
+    HIPCHECK(launch_class_temb(trow, 0, c.table, c.n_classes, c.guidance_scale == 0.f ? nullptr : c.labels, B, d, stacked,
+                               ctx->cls_temb.p, xin, stacked ? ctx->cls_x.p : nullptr, nx, s));
+    if (int rc = forward_impl(ctx, stacked ? ctx->cls_x.p : xin, ctx->cls_temb.p, d, ctx->score.p, nullptr, stacked ? 2 * B : B,
+                              -1, s, fuse ? hidden : nullptr))
+      return rc;
+    if (stacked) {
+      const size_t n = fuse ? (size_t)B * m.max_len * d : nx;
+      float* cond = fuse ? const_cast<float*>(*hidden) : ctx->score.p;
+      HIPCHECK(launch_cfg_combine(cond, cond + n, c.guidance_scale, n, s));
+    }
+    *score = ctx->score.p;
+    if (ctx->fresca_on) return fresca_score(ctx, t, B, s, score);
+    return FFD_OK;
+  }
+  if (int rc = forward_impl(ctx, xin, trow, 0, ctx->score.p, crf_dst, B, n_rec, s, fuse ? hidden : nullptr)) return rc;
   if (crf_copy)
     HIPCHECK(hipMemcpyAsync(crf_copy, crf_dst, sizeof(float) * (size_t)m.num_layers * m.max_len * m.d_model,
                             hipMemcpyDeviceToDevice, s));
@@ -1611,6 +1704,7 @@ int ffd_loglik_batch(ffd_ctx* ctx, float* x, double* delta, int B, const float* 
   const ffd_model_desc& m = ctx->desc;
   const int L = m.max_len, C = m.n_channels;
   const bool heun = solver == FFD_SOLVER_ODE_HEUN;
+  if (int rc = class_refuse(ctx, "ffd_loglik_batch")) return rc;
   if (B < 1 || n_probes < 1) return ctx->fail(FFD_ERR_INVALID, "ffd_loglik_batch: B=%d, n_probes=%d (both must be >= 1)", B, n_probes);
   if (!loglik_shape_supported(n_probes, B, L, C))
     return ctx->fail(FFD_ERR_UNSUPPORTED, "ffd_loglik_batch: (1 + 2 n_probes) B L C reaches 2^31; shard the batch");
@@ -1895,6 +1989,7 @@ int ffd_sample_batch_guided(ffd_ctx* ctx, ffd_train* net, float* x, int B, const
   const bool mixture = m.kind == FFD_MODEL_MIXTURE;
   hipStream_t s = (hipStream_t)stream;
   std::vector<double> coef;  // (alpha, sigma^2, lambda) of every step of the run
+  if (int rc = class_refuse(ctx, "ffd_sample_batch_guided")) return rc;
   int rc = loop_begin(ctx, "ffd_sample_batch_guided", x, B, timesteps, n_steps, n_steps, first_step, n_run, step_size, 0, s,
                       [&]() -> int {
     if (!cond || !guide) return ctx->fail(FFD_ERR_INVALID, "ffd_sample_batch_guided needs an observation (cond) and guide");

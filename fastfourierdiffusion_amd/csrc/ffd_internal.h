@@ -353,6 +353,17 @@ hipError_t launch_forward_transition(float* x, const float* G, float a, float sg
 // sample_offset + b: with z == nullptr both kernels take the draw of global element g from slot g & 3 of Philox block
 // g >> 2 under SM_TAG_NOISE, so the loss regenerates what the perturbation drew.
 constexpr uint32_t SM_TAG_NOISE = 0xFFFFFFFEu, SM_TAG_TIMES = 0xFFFFFFFDu;  // (0xFFFFFFFF: the prior; below 2^31: step indices)
+constexpr uint32_t SM_TAG_CLASS_DROP = 0xFFFFFFFCu;  // the training-time label dropout (loglik's probes end at 0xFFFFFFF0)
+// Class conditioning and classifier-free guidance (ffd_class.hip; include/ffd.h ffd_class_temb ...).
+// launch_class_temb: the (B | 2 B, d) embedding rows; xs != nullptr: the same launch also writes x (nx floats) to both
+// halves of xs (the stacked batch).  labels nullptr: every row null.
+hipError_t launch_class_temb(const float* temb, int temb_stride, const float* table, int n_classes, const int32_t* labels,
+                             int B, int d, int stack, float* out, const float* x, float* xs, size_t nx, hipStream_t s);
+hipError_t launch_cfg_combine(float* c, const float* u, float g, size_t n, hipStream_t s);
+hipError_t launch_class_drop(const int32_t* labels, int n_classes, const int64_t* index, int B, float p_uncond, uint64_t seed,
+                             uint64_t sample_offset, int32_t* out, hipStream_t s);
+hipError_t launch_class_table_grad(const float* dtemb, const int32_t* eff_labels, int n_classes, int B, int d, float* dtable,
+                                   hipStream_t s);
 // x_noisy[b,l,c] = mean_coeff[b] * x0[b,l,c] + (sigma[b] * G[l]) * z[b,l,c]
 hipError_t launch_sm_perturb(const float* x0, float* x_noisy, const float* mean_coeff, const float* sigma, const float* G,
                              const float* z, uint64_t seed, uint64_t sample_offset, int B, int L, int C, hipStream_t s);

@@ -536,6 +536,14 @@ struct ffd_train {
   int nseg = 0;
   bool segs_stale = true;
   double* partial = nullptr;  // nseg doubles + the squared norm of ffd_train_step
+  // classes (ffd_train_classes / ffd_train_labels): the caller's device labels, and the effective labels of the batch in
+  // flight (after the dropout) in a buffer of their own -- outside the workspace, whose size the ABI states
+  int n_classes = 0;
+  const int32_t* labels = nullptr;
+  size_t n_labels = 0;
+  double p_uncond = 0.0;
+  int32_t* eff = nullptr;
+  size_t eff_cap = 0;
   int fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -635,6 +643,40 @@ static int train_trainable(ffd_train* tr) {
   return FFD_OK;
 }
 
+// The effective labels of a batch of B: labels[index[b] | b], dropped to null with probability p under (seed,
+// SM_TAG_CLASS_DROP, global row) -- p = 0 for the plain forward.  Without classes: nothing.
+static int train_eff_labels(ffd_train* tr, const int64_t* index, int B, double p, uint64_t seed, uint64_t sample_offset,
+                            hipStream_t s) {
+  if (!tr->n_classes) return FFD_OK;
+  if (!index && tr->labels && tr->n_labels < (size_t)B)
+    return tr->fail(FFD_ERR_INVALID, "%zu labels for a batch of %d rows (ffd_train_labels)", tr->n_labels, B);
+  if (tr->eff_cap < (size_t)B) {
+    if (tr->eff) {
+      (void)hipDeviceSynchronize();
+      (void)hipFree(tr->eff);
+      tr->eff = nullptr, tr->eff_cap = 0;
+    }
+    if (hipMalloc((void**)&tr->eff, (size_t)B * sizeof(int32_t)) != hipSuccess)
+      return tr->fail(FFD_ERR_NOMEM, "hipMalloc(%d labels) failed", B);
+    tr->eff_cap = (size_t)B;
+  }
+  TRCHECK(launch_class_drop(tr->labels, tr->n_classes, index, B, (float)p, seed, sample_offset, tr->eff, s));
+  return FFD_OK;
+}
+// temb (B, d) += table[eff_label_b], in place, behind the time encoder's dense layer
+static int train_class_rows(ffd_train* tr, float* temb, int B, hipStream_t s) {
+  if (!tr->n_classes) return FFD_OK;
+  const int d = tr->desc.d_model;
+  TRCHECK(launch_class_temb(temb, d, tr->par("class_embedding.weight"), tr->n_classes, tr->eff, B, d, 0, temb, nullptr, nullptr,
+                            0, s));
+  return FFD_OK;
+}
+static int train_class_grad(ffd_train* tr, const float* dtemb, int B, hipStream_t s) {
+  if (!tr->n_classes) return FFD_OK;
+  TRCHECK(launch_class_table_grad(dtemb, tr->eff, tr->n_classes, B, tr->desc.d_model, tr->grd("class_embedding.weight"), s));
+  return FFD_OK;
+}
+
 // the transformer's path (behind the LayerNorm and attention operators at the end of this file)
 static size_t tf_work_bytes(const ffd_model_desc& m, int B);
 static int tf_forward(ffd_train* tr, const float* xn, const float* tb, int B, hipStream_t s);
@@ -691,6 +733,7 @@ static int mlp_train_forward(ffd_train* tr, const float* xn, const float* tb, co
   TRCHECK(hipGetLastError());
   TRCHECK(launch_dense(W + w.emb, tr->par("time_encoder.dense.weight"), tr->par("time_encoder.dense.bias"), nullptr, nullptr,
                        W + w.temb, B, d, d, 0, s));
+  if (int rc = train_class_rows(tr, W + w.temb, B, s)) return rc;
   TRCHECK(launch_dense(xn, tr->par("embedder.weight"), tr->par("embedder.bias"), nullptr, W + w.temb, W + w.h, B, d, io, 0, s));
   for (int i = 0; i < NL; ++i) {
     const std::string p = "backbone." + std::to_string(i) + ".";
@@ -724,7 +767,7 @@ static int mlp_train_backward(ffd_train* tr, const MlpWork& w, int B, hipStream_
   TRCHECK(launch_dense_wgrad(dh, W + w.xn, tr->grd("embedder.weight"), tr->grd("embedder.bias"), B, d, io, wg, s));
   TRCHECK(launch_dense_wgrad(dh, W + w.emb, tr->grd("time_encoder.dense.weight"), tr->grd("time_encoder.dense.bias"), B, d, d,
                              wg, s));
-  return FFD_OK;
+  return train_class_grad(tr, dh, B, s);  // (the (B, d) state's gradient is the time embedding's)
 }
 
 // The MLP's backward chain for the input alone: no wgrad, and one more dgrad through embedder.weight
@@ -752,6 +795,7 @@ static int train_loss_grad(ffd_train* tr, const float* x0, const int64_t* index,
   TRCHECK(hipSetDevice(tr->device));
   if (int rc = train_workspace(tr, B)) return rc;
   tr->fwd_B = 0;  // (B again once everything is enqueued: the forward's activations are what ffd_train_input_vjp reads)
+  if (int rc = train_eff_labels(tr, index, B, tr->p_uncond, seed, sample_offset, s)) return rc;
   if (m.kind == FFD_MODEL_TRANSFORMER) {
     if (int rc = tf_loss_grad(tr, x0, index, timesteps, mean_coeff, sigma, z, seed, sample_offset, lw, per_sample_out, B, s))
       return rc;
@@ -813,10 +857,10 @@ int ffd_train_create(ffd_train** out, const ffd_model_desc* desc, double dropout
 
 void ffd_train_destroy(ffd_train* tr) {
   if (!tr) return;
-  if (tr->G_dev || tr->work || tr->segs || tr->partial) {
+  if (tr->G_dev || tr->work || tr->segs || tr->partial || tr->eff) {
     (void)hipSetDevice(tr->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {(void*)tr->G_dev, (void*)tr->work, (void*)tr->segs, (void*)tr->partial})
+    for (void* p : {(void*)tr->G_dev, (void*)tr->work, (void*)tr->segs, (void*)tr->partial, (void*)tr->eff})
       if (p) (void)hipFree(p);
   }
   delete tr;
@@ -827,6 +871,28 @@ const char* ffd_train_last_error(const ffd_train* tr) { return tr ? tr->err.c_st
 size_t ffd_train_work_bytes(const ffd_model_desc* desc, int B) {
   if (!desc || B < 1 || train_desc_check(desc, 0.0, nullptr) != FFD_OK) return 0;
   return train_work_need(*desc, B);
+}
+
+int ffd_train_classes(ffd_train* tr, int n_classes) {
+  if (!tr) return FFD_ERR_INVALID;
+  if (n_classes < 1) return tr->fail(FFD_ERR_INVALID, "n_classes=%d", n_classes);
+  if (tr->n_classes) return tr->fail(FFD_ERR_INVALID, "the object already has %d classes", tr->n_classes);
+  if (tr->t.empty()) return tr->fail(FFD_ERR_STATE, "the object was not created (ffd_train_create failed)");
+  for (const auto& x : tr->t)
+    if (x.p) return tr->fail(FFD_ERR_STATE, "ffd_train_classes comes before the first bind (%s is bound)", x.key.c_str());
+  tr->t.push_back({"class_embedding.weight", ((size_t)n_classes + 1) * (size_t)tr->desc.d_model, false});
+  tr->n_classes = n_classes;
+  tr->segs_stale = true;
+  return FFD_OK;
+}
+
+int ffd_train_labels(ffd_train* tr, const int32_t* labels, size_t n, double p_uncond) {
+  if (!tr) return FFD_ERR_INVALID;
+  if (!tr->n_classes) return tr->fail(FFD_ERR_STATE, "ffd_train_labels without ffd_train_classes");
+  if (labels && n < 1) return tr->fail(FFD_ERR_INVALID, "labels of length 0");
+  if (!(p_uncond >= 0.0 && p_uncond <= 1.0)) return tr->fail(FFD_ERR_INVALID, "p_uncond=%g outside [0, 1]", p_uncond);
+  tr->labels = labels, tr->n_labels = labels ? n : 0, tr->p_uncond = p_uncond;
+  return FFD_OK;
 }
 
 int ffd_train_bind(ffd_train* tr, const char* name, float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n) {
@@ -864,6 +930,7 @@ int ffd_train_forward(ffd_train* tr, const float* x, const float* timesteps, flo
   if (int rc = train_workspace(tr, B)) return rc;
   tr->fwd_B = 0;  // (B again once the forward is enqueued)
   hipStream_t s = (hipStream_t)stream;
+  if (int rc = train_eff_labels(tr, nullptr, B, 0.0, 0, 0, s)) return rc;
   if (tr->desc.kind == FFD_MODEL_TRANSFORMER) {
     if (int rc = tf_forward(tr, x, timesteps, B, s)) return rc;
     TRCHECK(hipMemcpyAsync(score_out, tf_score(tr, B), sizeof(float) * (size_t)B * tr->desc.max_len * tr->desc.n_channels,
@@ -1290,6 +1357,7 @@ static int tf_forward(ffd_train* tr, const float* xn, const float* tb, int B, hi
   TRLAUNCH(k_time_features, dim3(cdiv(B * d, 256)), dim3(256), 0, s, tb, tr->par("time_encoder.W"), W + w.emb, B, d);
   TRCHECK(launch_dense(W + w.emb, tr->par("time_encoder.dense.weight"), tr->par("time_encoder.dense.bias"), nullptr, nullptr,
                        W + w.temb, B, d, d, 0, s));
+  if (int rc = train_class_rows(tr, W + w.temb, B, s)) return rc;
   TRCHECK(launch_dense(xn, tr->par("embedder.weight"), tr->par("embedder.bias"), nullptr, nullptr, W + w.h, M, d, C, 0, s));
   const size_t Md = (size_t)M * d;
   TRLAUNCH(k_add_pos_temb, dim3((unsigned)((Md + 255) / 256)), dim3(256), 0, s, W + w.h, tr->par("pos_encoder.embedding.weight"),
@@ -1354,7 +1422,7 @@ static int tf_backward(ffd_train* tr, int B, hipStream_t s) {
   TRLAUNCH(k_sum_over_l, dim3(cdiv(B * d, 256)), dim3(256), 0, s, dh, W + w.dtemb, B, L, d);
   TRCHECK(launch_dense_wgrad(W + w.dtemb, W + w.emb, tr->grd("time_encoder.dense.weight"), tr->grd("time_encoder.dense.bias"), B, d,
                              d, wg, s));
-  return FFD_OK;
+  return train_class_grad(tr, W + w.dtemb, B, s);
 }
 
 // tf_backward for the input alone: no wgrad, no LayerNorm parameter gradient, no sums over the batch or the length; one

@@ -1,5 +1,6 @@
 """``fdiff.models.score_models`` mirror: ``ScoreModule``, ``LSTMScoreModule`` and ``MLPScoreModule``; and, beyond the
-reference, ``MixtureScoreModule``: the closed-form score of a diffused Gaussian mixture.
+reference, ``MixtureScoreModule``: the closed-form score of a diffused Gaussian mixture, and
+``ClassConditionalScoreModule``: the transformer with a learned class table (labels, classifier-free guidance).
 
 Drop-in for the *sampling* surface of the reference classes
 (src/fdiff/models/score_models.py:24-289, 443-511): same constructor arguments,
@@ -239,7 +240,8 @@ class ScoreModule(nn.Module):
         if tr is None or tr.model is not self:
             tr = Trainer(self)
             object.__setattr__(self, "_trainer", tr)
-        loss = tr.loss_and_grad(batch.X, timesteps=batch.timesteps)
+        labels = batch.y if getattr(self, "n_classes", None) is not None else None  # (the reference's models ignore y)
+        loss = tr.loss_and_grad(batch.X, timesteps=batch.timesteps, labels=labels)
         tr.global_step += 1  # the next call's draw key
         return loss
 
@@ -370,6 +372,76 @@ class MLPScoreModule(ScoreModule):
     def forward(self, batch: DiffusableBatch) -> torch.Tensor:  # type: ignore[override]
         """score_models.py:406-440 (no recompute_tokens / caching, Q9)."""
         return super().forward(batch)
+
+
+def class_labels(labels, n: int, n_classes: int, device) -> Optional[torch.Tensor]:
+    """``labels`` (None, an int, or ``(n,)`` integers) as the ``(n,)`` int32 device tensor libffd reads; None stays None
+    (every sample null).  Values outside ``[-1, n_classes]`` are an ``AssertionError`` (-1 and ``n_classes``: null)."""
+    if labels is None:
+        return None
+    y = torch.as_tensor(labels)
+    assert not y.dtype.is_floating_point and y.dtype != torch.bool, f"labels must be integers, got {y.dtype}"
+    if y.dim() == 0:
+        y = y.expand(n)
+    assert tuple(y.shape) == (n,), f"labels must be ({n},) or one int, got {tuple(y.shape)}"
+    y = y.to(torch.int64)
+    assert bool(((y >= -1) & (y <= n_classes)).all()), f"labels must lie in [-1, {n_classes}]"
+    return y.to(device=device, dtype=torch.int32).contiguous()
+
+
+class ClassConditionalScoreModule(ScoreModule):
+    """Transformer score model with a class label (an extension; no counterpart in the reference): a learned table
+    ``class_embedding.weight`` (n_classes + 1, d_model) whose last row is the null class, added to the time embedding of
+    every token of a sample -- ``h = embed(x) + pos + temb(t_b) + table[y_b]``.  ``forward(batch)`` reads ``batch.y``
+    (None: null; -1 and ``n_classes``: null).  Trained with label dropout (``Trainer(p_uncond=...)``) it serves
+    classifier-free guidance: ``DiffusionSampler.sample(labels=..., guidance_scale=g)`` runs ``s_u + g (s_c - s_u)``.
+    The table is not part of the native context's weights: libffd reads the parameter's device memory live."""
+
+    def __init__(self, n_channels: int, max_len: int, noise_scheduler: SDE, n_classes: int,
+                 fourier_noise_scaling: bool = True, d_model: int = 60, num_layers: int = 3, n_head: int = 12,
+                 num_training_steps: int = 1000, lr_max: float = 1e-3, likelihood_weighting: bool = False) -> None:
+        assert int(n_classes) >= 1, f"n_classes must be >= 1, got {n_classes}"
+        super().__init__(n_channels=n_channels, max_len=max_len, noise_scheduler=noise_scheduler,
+                         fourier_noise_scaling=fourier_noise_scaling, d_model=d_model, num_layers=num_layers, n_head=n_head,
+                         num_training_steps=num_training_steps, lr_max=lr_max, likelihood_weighting=likelihood_weighting)
+        self.n_classes = int(n_classes)
+        self.class_embedding = nn.Embedding(self.n_classes + 1, d_model)
+        nn.init.normal_(self.class_embedding.weight, mean=0.0, std=0.02)
+
+    def _weight_items(self):
+        for name, p in super()._weight_items():
+            if not name.startswith("class_embedding."):
+                yield name, p
+
+    def class_state(self, labels: Optional[torch.Tensor], guidance_scale: float = 1.0):
+        """Context manager: the native context evaluates with these labels (an int32 device tensor from ``class_labels``
+        or None) until it exits."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            ctx = self._ctx()
+            table = self.class_embedding.weight
+            assert table.device == self.device and table.dtype == torch.float32 and table.is_contiguous()
+            host = labels.cpu() if labels is not None else None  # (kept alive until ffd_class_enable has read it)
+            cfg = N.ClassCfg(table.data_ptr(), labels.data_ptr() if labels is not None else None,
+                             host.data_ptr() if host is not None else None, self.n_classes,
+                             int(labels.numel()) if labels is not None else 0, float(guidance_scale), 0)
+            N.check(ctx.lib.ffd_class_enable(ctx.handle, C.byref(cfg)), ctx.handle, "ffd_class_enable")
+            try:
+                yield ctx
+            finally:
+                ctx.lib.ffd_class_disable(ctx.handle)
+
+        return scope()
+
+    def forward(self, batch: DiffusableBatch, recompute_tokens: Optional[set] = None, step: int = 0,
+                return_crf: bool = False) -> Union[torch.Tensor, tuple]:
+        if self.use_cache and recompute_tokens is not None and self.cached_backbone is not None:
+            raise NotImplementedError("the E2-CRF cache has no class-conditional form")
+        y = class_labels(batch.y, len(batch), self.n_classes, batch.X.device)
+        with self.class_state(y):
+            return super().forward(batch, None, step, return_crf)
 
 
 class _MixtureTensors(nn.Module):

@@ -68,6 +68,14 @@ guided score.  Draws as a conditional step without correctors: the predictor's, 
 ``LSTMScoreModule``, ``corrector_steps > 0``, an ODE solver, the cache, FreSca and ``resample > 1``.  What it buys on a
 forecast, and what a step costs, is in DESIGN.md section 6.
 
+Class labels (extension): with a ``ClassConditionalScoreModule``, ``sample`` / ``sample_conditional`` / ``impute`` take
+``labels`` ((num_samples,) integers or one int, sliced per batch like an observation; -1 / ``n_classes`` / None: the null
+class) and ``guidance_scale`` g: every score evaluation of the loop is ``s_u + g (s_c - s_u)`` (classifier-free guidance,
+Ho & Salimans 2022) -- g = 1 the conditional score, g = 0 the unconditional one, anything else one evaluation at twice
+the rows (``ffd_class_enable`` holds the batch's labels for as long as its loop calls run).  Every solver, the
+correctors, replacement conditioning, resampling and FreSca run with it; ``log_likelihood``, ``Guidance`` and
+``use_cache=True`` raise ``NotImplementedError``, and a model without classes takes no labels (``AssertionError``).
+
 Likelihoods (extension): ``log_likelihood`` integrates the same ODE the other way, from ``eps`` up to 1, with the
 divergence of its drift accumulated (Song et al. 2021, section 4.3), through ``ffd_loglik_batch``: log p(x) =
 ``SDE.prior_logp`` of the latent + the accumulated ``delta``.  No gradient of the network is taken: Hutchinson probes
@@ -97,6 +105,7 @@ ffd_ffn_rows.hip), and a shard may fall into another regime than the whole batch
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from typing import Literal, NamedTuple, Optional
@@ -104,7 +113,7 @@ from typing import Literal, NamedTuple, Optional
 import torch
 
 from .. import _native as N
-from ..models.score_models import ScoreModule
+from ..models.score_models import ScoreModule, class_labels
 from ..schedulers.sde import SDE
 from ..utils.dataclasses import DiffusableBatch
 from .guidance import Guidance
@@ -315,13 +324,41 @@ class DiffusionSampler:
         return SOLVERS[self.solver] if self.solver in SOLVERS else MULTISTEP_SOLVERS[self.solver]
 
     # ------------------------------------------------------------------
-    def sample(self, num_samples: int, num_diffusion_steps: Optional[int] = None) -> torch.Tensor:
-        """sampler.py:105-215."""
-        return self._sample(num_samples, num_diffusion_steps, None)
+    def sample(self, num_samples: int, num_diffusion_steps: Optional[int] = None, *, labels=None,
+               guidance_scale: float = 1.0) -> torch.Tensor:
+        """sampler.py:105-215.  ``labels`` / ``guidance_scale`` (keyword only, an extension; a
+        ``ClassConditionalScoreModule``): ``labels`` is ``(num_samples,)`` integers or one int, sliced per batch like an
+        observation (-1 / ``n_classes`` / None: the null class); the score is ``s_u + g (s_c - s_u)`` -- g = 1 the
+        conditional score, g = 0 the unconditional one, anything else one evaluation at twice the rows per step."""
+        return self._sample(num_samples, num_diffusion_steps, None, self._class_args(labels, guidance_scale, num_samples))
 
-    def _sample(self, num_samples: int, num_diffusion_steps: Optional[int], cond: Optional[dict]) -> torch.Tensor:
+    def _class_args(self, labels, guidance_scale, num_samples: int, guidance=None):
+        """(labels as (num_samples,) int32 on the device or None, g) for a class-conditional model, else None; what
+        labels cannot go with is refused here, before any device work."""
+        n_classes = getattr(self.score_model, "n_classes", None)
+        if n_classes is None:
+            assert labels is None, f"{type(self.score_model).__name__} has no classes: labels must be None"
+            assert float(guidance_scale) == 1.0, f"{type(self.score_model).__name__} has no classes: guidance_scale must be 1"
+            return None
+        if guidance is not None:
+            raise NotImplementedError("a class-conditional model has no guided (reconstruction-guidance) form")
+        if self.use_cache:
+            raise NotImplementedError("a class-conditional model cannot run with use_cache=True: the E2-CRF tables are "
+                                      "batch element 0's, which carry that sample's label")
+        g = float(guidance_scale)
+        if not math.isfinite(g):
+            raise ValueError(f"guidance_scale must be finite, got {guidance_scale!r}")
+        return class_labels(labels, num_samples, n_classes, self.score_model.device), g
+
+    @staticmethod
+    def _label_slice(labels: Optional[torch.Tensor], lo: int, n: int) -> Optional[torch.Tensor]:
+        """the labels of the batch of samples [lo, lo + n)"""
+        return None if labels is None else labels[lo:lo + n].contiguous()
+
+    def _sample(self, num_samples: int, num_diffusion_steps: Optional[int], cond: Optional[dict],
+                cls: Optional[tuple] = None) -> torch.Tensor:
         """``sample``; ``cond`` (``sample_conditional``): obs / mask (1 or num_samples, L, C) and std on the device,
-        domain, final_replace."""
+        domain, final_replace; ``cls`` (``_class_args``): the labels and the guidance scale."""
         if num_diffusion_steps is not None:
             self._num_diffusion_steps = num_diffusion_steps
         self.score_model.eval()
@@ -396,16 +433,21 @@ class DiffusionSampler:
                         guide = (N.GuideCfg(float(g.scale), float(g.obs_var), float(g.rho), int(g.replace), 0),
                                  self._guide_net_handle())
                 done = 0
-                while done < n_iter:
-                    n, n_draws = self._next_chunk(done, n_iter, draws, followed)
-                    z = self._draw(n_draws, X.shape, device) if n_draws else None
-                    self._loop_call(ctx, X, (ts_c, num_diffusion_steps, step_size), done, n,
-                                    (self.seed, sample_cursor, z.data_ptr() if z is not None else None),
-                                    (use_cache, (global_step + done) if use_cache else 0), cond_cfg, resample, jump, stream,
-                                    guide)
-                    if cap is not None:
-                        self._crf_capture_collect(cap, global_step + done, n, ts, done)
-                    done += n
+                scope = contextlib.nullcontext()
+                if cls is not None:  # this batch's labels, for as long as its loop calls run
+                    scope = model.class_state(self._label_slice(cls[0], batch_idx * self.sample_batch_size, batch_size),
+                                              cls[1])
+                with scope:
+                    while done < n_iter:
+                        n, n_draws = self._next_chunk(done, n_iter, draws, followed)
+                        z = self._draw(n_draws, X.shape, device) if n_draws else None
+                        self._loop_call(ctx, X, (ts_c, num_diffusion_steps, step_size), done, n,
+                                        (self.seed, sample_cursor, z.data_ptr() if z is not None else None),
+                                        (use_cache, (global_step + done) if use_cache else 0), cond_cfg, resample, jump,
+                                        stream, guide)
+                        if cap is not None:
+                            self._crf_capture_collect(cap, global_step + done, n, ts, done)
+                        done += n
                 if use_cache:
                     N.check(ctx.lib.ffd_cache_crf_capture(ctx.handle, None), ctx.handle, "ffd_cache_crf_capture")
                     global_step += n_iter
@@ -486,7 +528,8 @@ class DiffusionSampler:
         return z
 
     def log_likelihood(self, X: torch.Tensor, num_diffusion_steps: Optional[int] = None, *, solver: str = "ode_heun",
-                       n_probes: int = 1, fd_rel: float = 1e-2, return_latent: bool = False) -> "LogLikelihood":
+                       n_probes: int = 1, fd_rel: float = 1e-2, return_latent: bool = False,
+                       labels=None) -> "LogLikelihood":
         """log p(x) of every series of ``X`` (n, L, C) under the model, by the instantaneous change of variables along
         the probability-flow ODE (Song et al. 2021, section 4.3): the ODE of ``solver="ode_euler"`` / ``"ode_heun"``
         integrated the other way, from ``eps`` up to 1, over the N - 1 intervals of the scheduler's N-point grid, with
@@ -503,6 +546,8 @@ class DiffusionSampler:
         order; any finite values -- ``sqrt(D) e_j`` with ``n_probes = D`` gives the exact trace).  The sampler's own
         ``solver`` and ``corrector_steps`` are not consulted.  Raises ``ValueError`` with the cache or FreSca: a rescaled
         score is not the model's ODE, and the cache's gate assumes falling time.  Returns a ``LogLikelihood``."""
+        if labels is not None or getattr(self.score_model, "n_classes", None) is not None:
+            raise NotImplementedError("log_likelihood has no class-conditional form")
         if self.use_cache:
             raise ValueError("log_likelihood cannot run with use_cache=True: the E2-CRF cache's gate and tables assume "
                              "that the diffusion time only falls")
@@ -662,15 +707,18 @@ class DiffusionSampler:
         A forecast is the prefix mask ``mask[:n_known] = 1``.  ``resample=r > 1`` runs every block of ``jump`` steps r
         times with a forward transition in between (the module docstring's "Resampling"), at r times the evaluations;
         ``resample=1`` is plain replacement whatever ``jump`` is.
+        ``labels`` / ``guidance_scale`` (keyword only, through ``extensions``): as in ``sample``.
         ``guidance=None`` (keyword only, the one name ``extensions`` takes: a ``Guidance``; the module docstring's
         "Guidance") steers every step by the gradient of the reconstruction loss through the score model instead of (or,
         with ``Guidance.replace``, before) the replacement; ``final_replace`` still ends the run with one noiseless
         replacement.  None: the replacement path, untouched."""
         guidance = extensions.pop("guidance", None)
+        labels, guidance_scale = extensions.pop("labels", None), extensions.pop("guidance_scale", 1.0)
         if extensions:
             raise TypeError(f"sample_conditional() got an unexpected keyword argument {next(iter(extensions))!r}")
         self._check_guidance(guidance, resample)
         self._check_conditional(resample, jump)
+        cls = self._class_args(labels, guidance_scale, num_samples, guidance)
         if domain is None:
             domain = "frequency" if getattr(self.score_model, "scale_noise", False) else "time"
         if domain not in ("frequency", "time"):
@@ -688,23 +736,25 @@ class DiffusionSampler:
                     std=feature_std.to(device).contiguous() if feature_std is not None else None,
                     domain=N.FFD_COND_FREQUENCY if domain == "frequency" else N.FFD_COND_TIME,
                     final_replace=bool(final_replace), resample=resample, jump=jump, guide=guidance)
-        return self._sample(num_samples, num_diffusion_steps, cond)
+        return self._sample(num_samples, num_diffusion_steps, cond, cls)
 
     def impute(self, series_time: torch.Tensor, mask: torch.Tensor, num_samples: int,
                num_diffusion_steps: Optional[int] = None, resample: int = 1, jump: int = 1, *,
                feature_mean: Optional[torch.Tensor] = None, feature_std: Optional[torch.Tensor] = None,
-               final_replace: bool = True, guidance: Optional[Guidance] = None) -> torch.Tensor:
+               final_replace: bool = True, guidance: Optional[Guidance] = None, labels=None,
+               guidance_scale: float = 1.0) -> torch.Tensor:
         """Complete a time series with a model that diffuses its spectrum: ``series_time`` (L, C) or
         (num_samples, L, C) holds the series, ``mask`` (as in ``sample_conditional``) is 1 at its observed points.
         The unobserved points are zero-filled, the series goes through ``dft`` (with the dataset's ``feature_mean`` /
         ``feature_std`` (L, C): ``ffd_dft_standardize``), ``sample_conditional`` runs in the frequency domain, and the
         samples come back as TIME series (``ffd_unstandardize_idft`` / ``idft``) on the CPU.  Forecasting is the
         prefix mask: ``mask[:n_known] = 1`` draws ``num_samples`` continuations of the first ``n_known`` points.
-        ``resample`` / ``jump`` / ``guidance``: as in ``sample_conditional``."""
+        ``resample`` / ``jump`` / ``guidance`` / ``labels`` / ``guidance_scale``: as in ``sample_conditional``."""
         if (feature_mean is None) != (feature_std is None):
             raise ValueError("feature_mean and feature_std go together")
         self._check_guidance(guidance, resample)
         self._check_conditional(resample, jump)  # (sample_conditional's refusals, before the transform below)
+        self._class_args(labels, guidance_scale, num_samples, guidance)
         L, Cn = self.max_len, self.n_channels
         series, m = _observation_and_mask(series_time, mask, num_samples, L, Cn, "series_time")
         device = self.score_model.device
@@ -726,7 +776,7 @@ class DiffusionSampler:
             N.check(lib.ffd_dft(filled.data_ptr(), obs.data_ptr(), Bo, L, Cn, stream), None, "ffd_dft")
         out = self.sample_conditional(obs, m, num_samples, num_diffusion_steps, domain="frequency",
                                       feature_std=std_d, final_replace=final_replace, resample=resample, jump=jump,
-                                      guidance=guidance)
+                                      guidance=guidance, labels=labels, guidance_scale=guidance_scale)
         xf = out.to(device).contiguous()
         xt = torch.empty_like(xf)
         if mean_d is not None:

@@ -36,6 +36,13 @@ class SDE(abc.ABC):
         self.G: Optional[torch.Tensor] = None
         self._G_dev = {}
 
+    def __getstate__(self):
+        """The scheduler travels in a checkpoint's ``hyper_parameters``: without its per-device copies of G, which a load
+        with ``map_location="cpu"`` would bring back as HOST tensors under a device's key."""
+        state = dict(self.__dict__)
+        state["_G_dev"] = {}
+        return state
+
     @property
     def T(self) -> float:
         return 1.0
@@ -87,7 +94,7 @@ class SDE(abc.ABC):
         assert self.G is not None, "call set_noise_scaling(max_len) first (sde.py:113-114 sets it lazily only in marginal_prob)"
         key = str(device)
         g = self._G_dev.get(key)
-        if g is None or g.numel() != self.G.numel():
+        if g is None or g.numel() != self.G.numel() or g.device != torch.device(device):  # (never a pointer off the device)
             g = self.G.to(device=device, dtype=torch.float32).contiguous()
             self._G_dev[key] = g
         return g

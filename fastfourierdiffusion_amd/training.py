@@ -13,6 +13,11 @@ Dropout (p = 0.1 in the reference's blocks) is not implemented: ``dropout`` acce
 0.0, so a model trained here is trained without it.  A model with the E2-CRF cache enabled is refused; FreSca is a property
 of ``DiffusionSampler`` (it rescales the score inside the sampling loop), not of a model, and cannot reach training.
 
+Classes.  A ``ClassConditionalScoreModule`` trains with labels (``step`` / ``loss_and_grad`` / ``fit(..., labels=)``,
+indexed like X): each is dropped to the null class with probability ``p_uncond`` by an on-device draw keyed like the
+times (classifier-free guidance's training recipe), and the table ``class_embedding.weight`` is one more tensor under
+the same norm, clip, AdamW and decay.  Labels with a model without classes are an ``AssertionError``.
+
 Draws.  Step k takes its times and noise from the Philox key ``seed + k * _DRAW_STRIDE`` -- the keying of
 ``evaluate_loss`` -- counted by the data-set row: with ``index`` a row's draw does not depend on the batch it lands in.
 """
@@ -59,8 +64,12 @@ class Trainer:
     the Adam moments in ``exp_avg`` / ``exp_avg_sq`` by parameter name."""
 
     def __init__(self, model, seed: int = 0, grad_clip: float = 1.0, weight_decay: float = 1e-2,
-                 betas=(0.9, 0.999), eps: float = 1e-8, dropout: float = 0.0) -> None:
+                 betas=(0.9, 0.999), eps: float = 1e-8, dropout: float = 0.0, p_uncond: float = 0.1) -> None:
         _refuse(model, dropout)
+        assert 0.0 <= float(p_uncond) <= 1.0, f"p_uncond must lie in [0, 1], got {p_uncond!r}"
+        self.p_uncond = float(p_uncond)  # label dropout of a class-conditional model (classifier-free guidance)
+        self.n_classes = getattr(model, "n_classes", None)
+        self._labels = None  # the int32 device labels libffd reads during the native call in flight
         dev = model.device
         if dev.type != "cuda":
             raise N.FFDError(f"model parameters live on {dev}: training runs only on an MI355X (gfx950) device; "
@@ -85,6 +94,8 @@ class Trainer:
         idx = dev.index if dev.index is not None else torch.cuda.current_device()
         rc = self.lib.ffd_train_create(C.byref(self.handle), C.byref(model._desc()), float(dropout), idx)
         self._check(rc, "ffd_train_create")
+        if self.n_classes is not None:
+            self._check(self.lib.ffd_train_classes(self.handle, int(self.n_classes)), "ffd_train_classes")
         self._bound = None
         self._bind()
 
@@ -159,6 +170,20 @@ class Trainer:
             assert tuple(z.shape) == (B, m.max_len, m.n_channels), "z is (B, L, C) in batch order"
         return X, index, timesteps, mean_coeff, sigma, z, B
 
+    def _set_labels(self, labels, X, trusted: bool = False) -> None:
+        """Hand the labels of the coming native call to libffd: (rows of X,) integers indexed like X (by ``index`` where
+        one is given), one int, or None (every sample null).  A model without classes takes None only.  ``trusted``:
+        ``fit``'s labels, validated once and already int32 on the device."""
+        if self.n_classes is None:
+            assert labels is None, f"{type(self.model).__name__} has no classes: labels must be None"
+            return
+        from .models.score_models import class_labels
+
+        y = labels if trusted else class_labels(labels, X.shape[0], self.n_classes, X.device)
+        self._labels = y
+        self._check(self.lib.ffd_train_labels(self.handle, y.data_ptr() if y is not None else None,
+                                              y.numel() if y is not None else 0, self.p_uncond), "ffd_train_labels")
+
     def _native_args(self, X, index, timesteps, mean_coeff, sigma, z, sample_offset, per_sample, B):
         return (self.handle, X.data_ptr(), index.data_ptr() if index is not None else None, timesteps.data_ptr(),
                 mean_coeff.data_ptr(), sigma.data_ptr(), z.data_ptr() if z is not None else None,
@@ -167,8 +192,11 @@ class Trainer:
 
     # ------------------------------------------------------------------
     def loss_and_grad(self, X: torch.Tensor, sample_offset: int = 0, index: Optional[torch.Tensor] = None,
-                      timesteps: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      timesteps: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None,
+                      labels=None) -> torch.Tensor:
         """Fill every parameter's ``.grad`` with the gradient of the batch's loss and return the loss; no update.
+        ``labels`` (a class-conditional model): indexed like X; each is dropped to the null class with probability
+        ``p_uncond`` by the draw of its global row.
 
         ``index`` None: X (B, L, C) is the batch and sample b draws as global sample ``sample_offset + b``.  ``index``
         (B,) int64 on the device: X (N, L, C) is the data set, the batch is its rows ``index`` and row i draws as global
@@ -176,6 +204,7 @@ class Trainer:
         self.model.train()
         self._bind()
         X, index, timesteps, mean_coeff, sigma, z, B = self._batch(X, sample_offset, index, timesteps, z)
+        self._set_labels(labels, X)
         per_sample = torch.empty(B, device=X.device, dtype=torch.float64)
         args = self._native_args(X, index, timesteps, mean_coeff, sigma, z, sample_offset, per_sample, B)
         self._check(self.lib.ffd_train_loss_grad(*args, N.current_stream_ptr(X.device)), "ffd_train_loss_grad")
@@ -207,13 +236,14 @@ class Trainer:
 
     def step(self, X: torch.Tensor, sample_offset: int = 0, index: Optional[torch.Tensor] = None,
              timesteps: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None,
-             lr: Optional[float] = None, _trusted_index: bool = False) -> torch.Tensor:
+             lr: Optional[float] = None, _trusted_index: bool = False, labels=None) -> torch.Tensor:
         """One training step (loss, gradients, norm, clipped AdamW update) in one native call; returns the loss of the
         batch before the update.  Arguments as ``loss_and_grad``.  Nothing synchronises, except that an ``index`` is
         checked against the rows of X on the host first."""
         self.model.train()
         self._bind()
         X, index, timesteps, mean_coeff, sigma, z, B = self._batch(X, sample_offset, index, timesteps, z, _trusted_index)
+        self._set_labels(labels, X, _trusted_index)
         per_sample = torch.empty(B, device=X.device, dtype=torch.float64)
         args = self._native_args(X, index, timesteps, mean_coeff, sigma, z, sample_offset, per_sample, B)
         cfg = self._cfg(lr)
@@ -229,20 +259,26 @@ class Trainer:
         return np.random.Generator(np.random.PCG64([self.seed, int(epoch)])).permutation(n).astype(np.int64)
 
     def fit(self, X: torch.Tensor, batch_size: int = 64, max_epochs: int = 1, X_val: Optional[torch.Tensor] = None,
-            shuffle: bool = True) -> dict:
+            shuffle: bool = True, labels=None, labels_val=None) -> dict:
         """Train over the data set X (N, L, C), a device tensor already in the diffused domain.  Returns
         ``train_loss`` (steps,) on the device and, with ``X_val``, ``val_loss``: ``evaluate_loss`` after each epoch."""
         X = N.require_gpu_tensor(X, "X")
         assert batch_size >= 1 and max_epochs >= 1
         n = X.shape[0]
+        if self.n_classes is not None:  # validated once (one host read), then handed over as they are every step
+            from .models.score_models import class_labels
+
+            labels = class_labels(labels, n, self.n_classes, X.device)
+        else:
+            assert labels is None and labels_val is None, f"{type(self.model).__name__} has no classes: labels must be None"
         first_epoch = self.global_step // max(1, -(-n // batch_size))
         history, val = [], []
         for epoch in range(first_epoch, first_epoch + max_epochs):
             order = torch.from_numpy(self.epoch_order(n, epoch, shuffle)).to(X.device)
             for i0 in range(0, n, batch_size):
-                history.append(self.step(X, index=order[i0:i0 + batch_size], _trusted_index=True))
+                history.append(self.step(X, index=order[i0:i0 + batch_size], _trusted_index=True, labels=labels))
             if X_val is not None:
-                val.append(evaluate_loss(self.model, X_val, batch_size, seed=self.seed)["loss"])
+                val.append(evaluate_loss(self.model, X_val, batch_size, seed=self.seed, labels=labels_val)["loss"])
         out = {"train_loss": torch.stack(history)}
         if X_val is not None:
             out["val_loss"] = torch.stack(val)
@@ -263,7 +299,7 @@ class Trainer:
                     "optimizer_states": [{"exp_avg": cpu(self.exp_avg), "exp_avg_sq": cpu(self.exp_avg_sq)}],
                     "global_step": self.global_step,
                     "trainer": {"seed": self.seed, "grad_clip": self.grad_clip, "weight_decay": self.weight_decay,
-                                "betas": list(self.betas), "eps": self.eps}}, path)
+                                "betas": list(self.betas), "eps": self.eps, "p_uncond": self.p_uncond}}, path)
 
     def resume(self, path) -> None:
         """Load parameters, moments and the step count of ``save_checkpoint`` in place; training continues bit for bit."""
@@ -282,6 +318,7 @@ class Trainer:
         t = ckpt["trainer"]
         self.seed, self.grad_clip, self.weight_decay = int(t["seed"]), float(t["grad_clip"]), float(t["weight_decay"])
         self.betas, self.eps = (float(t["betas"][0]), float(t["betas"][1])), float(t["eps"])
+        self.p_uncond = float(t.get("p_uncond", self.p_uncond))
         self.global_step = int(ckpt["global_step"])
         if self.model._native is not None:
             self.model._native.weights_key = None

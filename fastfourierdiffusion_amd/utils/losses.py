@@ -24,8 +24,21 @@ _DRAW_STRIDE = 0x9E3779B97F4A7C15  # Philox key of draw k = seed + k * this (mod
 
 def _eval_batch(model, X: torch.Tensor, timesteps: torch.Tensor, z: Optional[torch.Tensor], seed: int,
                 sample_offset: int, likelihood_weighting: bool, reduce_mean: bool, out: torch.Tensor,
-                scheduler: Optional[SDE] = None) -> None:
-    """Per-sample losses of X (B, L, C) at ``timesteps`` (B,) into ``out`` (B doubles, device); enqueue only."""
+                scheduler: Optional[SDE] = None, labels=None) -> None:
+    """Per-sample losses of X (B, L, C) at ``timesteps`` (B,) into ``out`` (B doubles, device); enqueue only.
+    ``labels`` (a class-conditional model: (B,) integers, one int or None = null): the conditional branch, no dropout;
+    their validation reads them on the host once."""
+    if getattr(model, "n_classes", None) is not None:
+        from ..models.score_models import class_labels
+
+        with model.class_state(class_labels(labels, X.shape[0], model.n_classes, X.device)):
+            _eval_batch_native(model, X, timesteps, z, seed, sample_offset, likelihood_weighting, reduce_mean, out, scheduler)
+        return
+    assert labels is None, f"{type(model).__name__} has no classes: labels must be None"
+    _eval_batch_native(model, X, timesteps, z, seed, sample_offset, likelihood_weighting, reduce_mean, out, scheduler)
+
+
+def _eval_batch_native(model, X, timesteps, z, seed, sample_offset, likelihood_weighting, reduce_mean, out, scheduler) -> None:
     ctx = model._ctx()
     scheduler = model.noise_scheduler if scheduler is None else scheduler
     mean_coeff, sigma = scheduler.marginal_coeffs(timesteps)
@@ -84,19 +97,20 @@ def get_sde_loss_fn(scheduler: SDE, train: bool, reduce_mean: bool = True, likel
         z = torch.randn_like(X) if rng == "torch" else None  # losses.py:66
         per_sample = torch.empty(B, device=X.device, dtype=torch.float64)
         _eval_batch(model, X, timesteps, z, seed, sample_offset, likelihood_weighting, reduce_mean, per_sample,
-                    scheduler)
+                    scheduler, labels=batch.y if getattr(model, "n_classes", None) is not None else None)
         return _batch_mean(per_sample).to(torch.float32)
 
     return loss_fn
 
 
 def evaluate_loss(model, X: torch.Tensor, batch_size: int, seed: int = 0, n_draws: int = 1, sample_offset: int = 0,
-                  _return_noisy: bool = False) -> dict:
+                  _return_noisy: bool = False, labels=None) -> dict:
     """The evaluation loss of ``model`` over a data set X (N, L, C) on the device, ``n_draws`` (time, noise) draws per
     sample, with the model's own scheduler and ``likelihood_weighting``.
 
     Times and noise come from the on-device Philox streams, keyed by (``seed``, draw) and counted by the global sample
-    index ``sample_offset + i``: they do not depend on ``batch_size`` or on how X is cut into calls.  Every batch is
+    index ``sample_offset + i``: they do not depend on ``batch_size`` or on how X is cut into calls.  ``labels`` (N,)
+    (a ``ClassConditionalScoreModule`` only; None: the null class) are sliced per batch.  Every batch is
     enqueued on the current stream; nothing is synchronised.  Returns device tensors: ``loss`` (0-dim float64, the mean
     of ``per_sample``), ``per_sample`` (n_draws, N) float64, ``timesteps`` (n_draws, N) float32.  ``_return_noisy``
     (tests) adds ``noisy`` (n_draws, N, L, C): the perturbed inputs, recomputed by ``ffd_sm_perturb``."""
@@ -106,6 +120,12 @@ def evaluate_loss(model, X: torch.Tensor, batch_size: int, seed: int = 0, n_draw
     model.eval()
     sch = model.noise_scheduler
     n = X.shape[0]
+    if getattr(model, "n_classes", None) is not None:
+        from ..models.score_models import class_labels
+
+        labels = class_labels(labels, n, model.n_classes, X.device)
+    else:
+        assert labels is None, f"{type(model).__name__} has no classes: labels must be None"
     per_sample = torch.empty((n_draws, n), device=X.device, dtype=torch.float64)
     times = torch.empty((n_draws, n), device=X.device, dtype=torch.float32)
     noisy = torch.empty((n_draws,) + tuple(X.shape), device=X.device, dtype=torch.float32) if _return_noisy else None
@@ -115,7 +135,7 @@ def evaluate_loss(model, X: torch.Tensor, batch_size: int, seed: int = 0, n_draw
         for i0 in range(0, n, batch_size):
             i1 = min(i0 + batch_size, n)
             _eval_batch(model, X[i0:i1], times[k, i0:i1], None, key, sample_offset + i0, model.likelihood_weighting,
-                        True, per_sample[k, i0:i1])
+                        True, per_sample[k, i0:i1], labels=labels[i0:i1] if labels is not None else None)
         if noisy is not None:
             mean_coeff, sigma = (c.contiguous() for c in sch.marginal_coeffs(times[k]))
             L, Cn = X.shape[1:]

@@ -1115,6 +1115,79 @@ int ffd_sample_batch_guided(ffd_ctx* ctx, ffd_train* net, float* x, int B, const
                             const float* z_inject, const ffd_cond_cfg* cond, const ffd_guide_cfg* guide, double* loss_out,
                             void* stream);
 
+/* ---- class-conditional score models and classifier-free guidance (Ho & Salimans 2022; an extension) ----
+ * A learned table class_embedding.weight (n_classes + 1, d_model) whose row n_classes is the NULL class (unconditional).
+ * Sample b with label y_b evaluates the network with table[y_b] added to its time embedding, i.e. every token is
+ * h = embed(x) + pos + temb(t_b) + table[y_b].  Labels are int32; -1 and n_classes both mean null.  The guided score is
+ * diffusers' convention  s~ = s_u + g (s_c - s_u):  g = 1 the conditional score and g = 0 the unconditional one, one
+ * evaluation of B rows each; any other g one evaluation at the stacked batch of 2 B rows (conditional block first).
+ *
+ * The four operators need no context (ffd_class.hip):
+ *   ffd_class_temb        out[r, :] = temb[r * temb_stride + :] + table[label_r, :] for r < B (temb_stride 0: one shared
+ *                         row, or d); stack = 1: rows B .. 2B - 1 get temb[r - B] + table[null].  labels NULL: every row
+ *                         null.  out may be temb when temb_stride == d and stack == 0.  A label outside [-1, n_classes]
+ *                         reads the null row (the entry points that take labels from a caller refuse it beforehand).
+ *   ffd_cfg_combine       c[i] = fmaf(g, c[i] - u[i], u[i]) over n floats, in place on c (the subtraction rounded on its
+ *                         own); c and u need 4-byte alignment only and must not overlap.  An element's bits do not
+ *                         depend on n or on the alignment.
+ *   ffd_class_drop        the training-time label dropout: out[b] = n_classes where the U[0, 1) draw of global row
+ *                         sample_offset + row_b under (seed, stream tag 0xFFFFFFFC) is < p_uncond, else labels[row_b] (a
+ *                         null label stays n_classes or -1 as given); row_b = index[b], or b when index is NULL: the
+ *                         row keying of ffd_sm_draw_times_at (slot g & 3 of Philox block g >> 2, u = (w >> 8) 2^-24).
+ *                         labels NULL: out[b] = n_classes.  0 <= p_uncond <= 1 (1: every row dropped).
+ *   ffd_class_table_grad  dtable[c, j] = sum over {b : eff_label_b == c} of dtemb[b, j], b in order, accumulated in fp64,
+ *                         no atomics; labels -1 count as n_classes; all n_classes + 1 rows are written (absent: 0).
+ * FFD_ERR_INVALID: a null pointer (labels / index where optional excepted), B, d or n_classes < 1, temb_stride not 0 or
+ * d, an in-place ffd_class_temb that is not the allowed one, a non-finite g, n == 0, p_uncond outside [0, 1].
+ *
+ * Context state: ffd_class_enable / ffd_class_disable, the same kind of state as FreSca.  The table pointer is read
+ * live at every evaluation and never copied (a training update is seen); labels_host is the host copy of `labels`
+ * that ffd_class_enable validates -- it is not kept.  labels == NULL: every sample null (n_labels and labels_host are
+ * then ignored).  While the state is on:
+ *   - all three network kinds honour it in ffd_sample_batch, _ode (every solver), _pc, _cond and _resample: each
+ *     evaluation builds the (B or 2 B, d) embedding table from the time-table row, evaluates B or 2 B rows, combines
+ *     -- on the final hidden rows where the tail is fused, else on the score: the unembedding is affine and the two
+ *     weights sum to 1, so that is exact in real arithmetic -- and hands B rows to the unchanged tail and FreSca.  The
+ *     batch limit and the workspace are those of 2 B rows when g is neither 0 nor 1.  These loops run single-stream
+ *     (no CU partitions).
+ *   - ffd_score_forward_ts and ffd_sm_eval_batch evaluate the conditional branch only (guidance_scale is ignored).
+ * FFD_ERR_INVALID (ffd_class_enable): a NULL cfg or table, n_classes < 1, labels without labels_host, n_labels < 1, a
+ * label outside [-1, n_classes], a non-finite guidance_scale; FFD_ERR_UNSUPPORTED: the mixture kind.
+ * Refused before any device work while the state is on: FFD_ERR_INVALID n_labels != B (loops, ffd_score_forward_ts,
+ * ffd_sm_eval_batch); FFD_ERR_STATE use_cache (or a cached n_recompute), ffd_score_forward, ffd_score_forward_cached,
+ * ffd_loglik_batch, ffd_sample_batch_guided. */
+typedef struct {
+  const float* table;         /* device (n_classes + 1, d_model) */
+  const int32_t* labels;      /* device (n_labels) or NULL */
+  const int32_t* labels_host; /* host copy of labels (validated, not kept) */
+  int32_t n_classes;
+  int32_t n_labels;
+  float guidance_scale;
+  int32_t reserved;
+} ffd_class_cfg;
+int ffd_class_enable(ffd_ctx* ctx, const ffd_class_cfg* cfg);
+int ffd_class_disable(ffd_ctx* ctx);
+int ffd_class_temb(const float* temb, int temb_stride, const float* table, int n_classes, const int32_t* labels, int B, int d,
+                   int stack, float* out, void* stream);
+int ffd_cfg_combine(float* c, const float* u, float g, size_t n, void* stream);
+int ffd_class_drop(const int32_t* labels, int n_classes, const int64_t* index, int B, double p_uncond, uint64_t seed,
+                   uint64_t sample_offset, int32_t* out, void* stream);
+int ffd_class_table_grad(const float* dtemb, const int32_t* eff_labels, int n_classes, int B, int d, float* dtable,
+                         void* stream);
+
+/* Training with classes.  ffd_train_classes (before the first bind; FFD_ERR_STATE after one, FFD_ERR_INVALID n_classes <
+ * 1 or a second call) appends class_embedding.weight (n_classes + 1, d_model) to the object's tensors: the gradient
+ * norm, the clip and AdamW cover it like any other tensor, decay included.  ffd_train_labels sets the device labels of
+ * the batches that follow, indexed like x0 (by `index` where one is given, else by the batch row), and the dropout
+ * probability; labels NULL: every sample null.  n: the labels' length (rows of the data set or of the batch; the
+ * caller's to keep within).  ffd_train_loss_grad and ffd_train_step use ffd_class_drop's labels (seed and
+ * sample_offset of the call), ffd_train_forward the labels as they are.  The forward adds table[eff_label_b] to the
+ * time encoder's dense output; the backward runs ffd_class_table_grad on the time embedding's gradient.  The
+ * effective labels live outside the workspace: ffd_train_work_bytes does not change.  FFD_ERR_INVALID: n < 1 with
+ * labels, p_uncond outside [0, 1]; FFD_ERR_STATE: ffd_train_labels without ffd_train_classes. */
+int ffd_train_classes(ffd_train* tr, int n_classes);
+int ffd_train_labels(ffd_train* tr, const int32_t* labels, size_t n, double p_uncond);
+
 /* How the context's last sampling-loop call ran: *parts_out = 2 as two CU partitions (ffd_tune "partitions"), 1 on the
  * caller's stream alone. */
 int ffd_partition_status(const ffd_ctx* ctx, int* parts_out);
