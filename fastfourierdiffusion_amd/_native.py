@@ -133,6 +133,11 @@ SIGNATURES = {
     "ffd_ens_energy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "ffd_ens_bench_energy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, C.c_int,
                                        _F, _P]),
+    "ffd_nn_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]),
+    "ffd_nn_search": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "ffd_nn_ball_count": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_nn_radius": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "ffd_nn_scores": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "ffd_sm_draw_times":(C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_uint64, C.c_uint64, _P]),
     "ffd_sm_perturb": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_sm_loss": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -1,0 +1,548 @@
+// Nearest-neighbour statistics between two row sets, on the device: k-nearest-neighbour search of a query set in a
+// reference set, ball counts, and the eight sample-quality numbers built from them (include/ffd.h ffd_nn_search,
+// ffd_nn_ball_count, ffd_nn_scores).  Rows are flat fp32 vectors (n, D); distances are squared Euclidean.
+//
+// Both sets are CENTRED on the reference set's column mean before the Gram form d^2 = (n_i + n_j) - 2 z_i . z_j is taken:
+// uncentred, n is the squared distance from the origin and fp32 resolves it far more coarsely than the distances between
+// neighbours of a cluster away from the origin (the reason k_ens_pairs centres, ffd_ensemble.hip).
+//   k_nn_colpart + k_nn_colmean   the reference set's column mean (fp64 over fixed slabs of 1024 rows, in order)
+//   k_nn_centre    z = x - mean into rows padded to a multiple of 16 columns, n_i = |z_i|^2 (a wave per row)
+//   nn_tile        one 64 x 256 tile of z_q z_r^T on the exact-fp32 16x16x4 MFMA (the operand scheme of k_ens_pairs with
+//                  the reference rows as the A operand: a lane ends with 4 consecutive reference columns of one query
+//                  row).  An element's sum runs over the columns in one order wherever its tile lies, so d^2(i, j) has
+//                  the same bits for every tiling.
+//   k_nn_tile      writes a block of the distance matrix (query rows x a chunk of reference columns) to the workspace
+//   k_nn_merge     a wave per query row merges that chunk into the row's running list of the k smallest (d^2, index),
+//                  ordered by (value, then lower index): a strict total order, so the list is the same for every cut
+//   k_nn_refine    recomputes the k kept pairs in difference form in fp64 on the caller's rows and sorts them again
+//   k_nn_ball      the same tiles with a counting epilogue: integer partial counts per (row, column chunk)
+//   k_nn_count_sum folds the partial counts in chunk order
+//   k_nn_scores    the eight numbers from the search / count arrays, fixed-order fp64 trees
+// No atomics anywhere.
+#include <algorithm>
+#include <climits>
+
+#include "ffd_internal.h"
+
+namespace ffd {
+
+constexpr int NN_SLAB = 1024;  // rows per column-sum slab (fixed: the grid does not change the mean)
+constexpr int NN_I = 64, NN_J = 256, NN_MAX_CHUNKS = 64;
+constexpr int NN_MAX_CBT = 32;              // column tiles of one distance chunk, at most (8192 columns)
+constexpr size_t NN_MAX_UNITS = 1u << 15;   // 64 x 256 tiles of one distance block, at most (2 GiB)
+constexpr size_t NN_UNIT_BYTES = (size_t)NN_I * NN_J * 4;
+constexpr int NN_MAX_ROWS = 1 << 24, NN_MAX_D = 1 << 16;
+
+// ---- centring ----------------------------------------------------------------------------------------------------
+// part[slab][d] = sum of x[i][d] over the slab's rows, fp64, 4 row groups combined in order
+__global__ __launch_bounds__(256) void k_nn_colpart(const float* __restrict__ X, int n, int D, double* __restrict__ part) {
+  __shared__ double red[4][64];
+  const int cl = threadIdx.x & 63, c = blockIdx.x * 64 + cl, g = threadIdx.x >> 6;
+  const int i0 = blockIdx.y * NN_SLAB, i1 = min(i0 + NN_SLAB, n);
+  double a = 0.0;
+  if (c < D)
+    for (int i = i0 + g; i < i1; i += 4) a += (double)X[(size_t)i * D + c];
+  red[g][cl] = a;
+  __syncthreads();
+  if (g == 0 && c < D) part[(size_t)blockIdx.y * D + c] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+}
+__global__ __launch_bounds__(256) void k_nn_colmean(const double* __restrict__ part, int nslab, int n, int D,
+                                                    float* __restrict__ mean) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= D) return;
+  double a = 0.0;
+  for (int i = 0; i < nslab; ++i) a += part[(size_t)i * D + c];
+  mean[c] = (float)(a / (double)n);
+}
+
+__device__ __forceinline__ double nn_wave_sum(double v) {  // a fixed butterfly: every lane gets the same total
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// A wave per row: z[i][d] = x[i][d] - mean[d] (0 for D <= d < Dp), nrm[i] = |z_i|^2
+__global__ __launch_bounds__(256) void k_nn_centre(const float* __restrict__ X, const float* __restrict__ mean,
+                                                   float* __restrict__ Z, float* __restrict__ nrm, int n, int D, int Dp) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const float* x = X + (size_t)i * D;
+  float* z = Z + (size_t)i * Dp;
+  double nn = 0.0;
+  for (int d = lane; d < Dp; d += 64) {
+    const float zv = d < D ? x[d] - mean[d] : 0.f;
+    z[d] = zv;
+    nn += (double)zv * (double)zv;
+  }
+  nn = nn_wave_sum(nn);
+  if (lane == 0) nrm[i] = (float)nn;
+}
+
+// ---- pair tiles --------------------------------------------------------------------------------------------------
+// acc[a][b] of lane (q = lane >> 4, c = lane & 15), register r: z_q(i0 + 16 a + c) . z_r(j0 + 16 b + 4 q + r).  The
+// reference rows are the A operand and the query rows the B operand; lane group q holds k = 16 g + 4 q + {0..3} of both,
+// MFMA step e pairs the e-th of both.  Rows past the sets are clamped for the loads; the callers never use them.
+__device__ __forceinline__ void nn_tile(const float* __restrict__ Zq, int nq, int i0, const float* __restrict__ Zr, int nr,
+                                        int j0, int Dp, int q, int c, f32x4 (&acc)[4][4]) {
+  const float* ar[4];
+  const float* br[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    ar[t] = Zq + (size_t)min(i0 + 16 * t + c, nq - 1) * Dp + 4 * q;
+    br[t] = Zr + (size_t)min(j0 + 16 * t + c, nr - 1) * Dp + 4 * q;
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kb = 0; kb < Dp; kb += 16) {
+    f32x4 av[4], bv[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      av[t] = *(const f32x4*)(ar[t] + kb);
+      bv[t] = *(const f32x4*)(br[t] + kb);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = mfma16(bv[b][e], av[a][e], acc[a][b]);
+  }
+}
+
+// the one statement of the Gram form: both epilogues see the same bits
+__device__ __forceinline__ float nn_d2(float ni, float nj, float g) { return fmaxf(__fmaf_rn(-2.f, g, ni + nj), 0.f); }
+
+// Workgroup blockIdx.x = bt * nct + ct: query rows [ib0 + 64 bt, + 64) against reference columns [jc0 + 256 ct, + 256);
+// wave w owns 64 of the columns.  T: (block rows, cb) floats, row = query row - ib0, column = reference column - jc0.
+__global__ __launch_bounds__(256) void k_nn_tile(const float* __restrict__ Zq, const float* __restrict__ nq_nrm, int nq,
+                                                 const float* __restrict__ Zr, const float* __restrict__ nr_nrm, int nr,
+                                                 int Dp, int ib0, int jc0, int nct, int cb, float* __restrict__ T) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, c = lane & 15;
+  const int bt = blockIdx.x / nct, ct = blockIdx.x - bt * nct;
+  const int i0 = ib0 + bt * NN_I, j0 = jc0 + ct * NN_J + wave * 64;
+  if (j0 >= nr) return;  // (wave-uniform) the merge never reads these columns
+  f32x4 acc[4][4];
+  nn_tile(Zq, nq, i0, Zr, nr, j0, Dp, q, c, acc);
+  float nj[4][4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) nj[b][r] = nr_nrm[min(j0 + 16 * b + 4 * q + r, nr - 1)];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int i = i0 + 16 * a + c;
+    if (i >= nq) continue;
+    const float ni = nq_nrm[i];
+    float* trow = T + (size_t)(i - ib0) * cb + (j0 - jc0) + 4 * q;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      f32x4 o;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = nn_d2(ni, nj[b][r], acc[a][b][r]);
+      *(f32x4*)(trow + 16 * b) = o;
+    }
+  }
+}
+
+// (value, index) order: a strict total order over the pairs of a row
+__device__ __forceinline__ bool nn_before(float v, int j, float w, int i) { return v < w || (v == w && j < i); }
+
+// A wave per query row of the block: lane l < k holds entry l of the row's list, ascending.  The chunk's row is read 256
+// columns at a time; a column that beats the list's last entry is inserted by a shift of the lanes behind its place.
+__global__ __launch_bounds__(256) void k_nn_merge(const float* __restrict__ T, int cb, int rows, int ib0, int jc0, int ncols,
+                                                  int exclude_self, int k, int first, float* __restrict__ cand_d,
+                                                  int* __restrict__ cand_i) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int i = ib0 + row;
+  const float* trow = T + (size_t)row * cb;
+  float lv = __builtin_inff();
+  int li = INT_MAX;
+  if (!first && lane < k) {
+    lv = cand_d[(size_t)i * k + lane];
+    li = cand_i[(size_t)i * k + lane];
+  }
+  float wv = __shfl(lv, k - 1, 64);
+  int wi = __shfl(li, k - 1, 64);
+  for (int jb = 0; jb < ncols; jb += 256) {  // jb + 256 <= cb: the loads stay inside the row, the mask is `ok`
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = trow[jb + 64 * u + lane];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int jl = jb + 64 * u + lane, j = jc0 + jl;
+      const bool ok = jl < ncols && !(exclude_self && j == i);
+      unsigned long long m = __ballot(ok && nn_before(v[u], j, wv, wi));
+      while (m) {  // (wave-uniform)
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const float cv = __shfl(v[u], src, 64);
+        const int cj = jc0 + jb + 64 * u + src;
+        if (!nn_before(cv, cj, wv, wi)) continue;
+        const int p = __popcll(__ballot(nn_before(lv, li, cv, cj)));  // the entries before the new one: a prefix, p < k
+        const float uv = __shfl_up(lv, 1, 64);
+        const int ui = __shfl_up(li, 1, 64);
+        if (lane == p) {
+          lv = cv;
+          li = cj;
+        } else if (lane > p) {
+          lv = uv;
+          li = ui;
+        }
+        wv = __shfl(lv, k - 1, 64);
+        wi = __shfl(li, k - 1, 64);
+      }
+    }
+  }
+  if (lane < k) {
+    cand_d[(size_t)i * k + lane] = lv;
+    cand_i[(size_t)i * k + lane] = li;
+  }
+}
+
+// A wave per query row: candidate c's distance sum_d ((double)a_d - (double)b_d)^2 on the caller's rows (lane l takes
+// d = l, l + 64, ..., then the butterfly), lane c keeps it; the k pairs are ranked by (value, index) and written in order.
+__global__ __launch_bounds__(256) void k_nn_refine(const float* __restrict__ Q, const float* __restrict__ R, int nq, int nr,
+                                                   int D, int k, const int* __restrict__ cand_i,
+                                                   double* __restrict__ dist2, int32_t* __restrict__ index) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= nq) return;
+  const float* a = Q + (size_t)i * D;
+  double myv = 0.0;
+  int myi = INT_MAX;
+  for (int c = 0; c < k; ++c) {
+    const int idx = cand_i[(size_t)i * k + c];
+    const float* b = R + (size_t)min(max(idx, 0), nr - 1) * D;  // (an index outside the set: NaN input only)
+    double s = 0.0;
+    for (int d = lane; d < D; d += 64) {
+      const double t = (double)a[d] - (double)b[d];
+      s += t * t;
+    }
+    s = nn_wave_sum(s);
+    if (lane == c) {
+      myv = s;
+      myi = idx;
+    }
+  }
+  int rank = 0;
+  for (int c = 0; c < k; ++c) {
+    const double ov = __shfl(myv, c, 64);
+    const int oi = __shfl(myi, c, 64);
+    rank += (ov < myv || (ov == myv && oi < myi)) ? 1 : 0;
+  }
+  if (lane < k) {
+    dist2[(size_t)i * k + rank] = myv;
+    index[(size_t)i * k + rank] = myi;
+  }
+}
+
+// Workgroup blockIdx.x = bi * nch + ch: query rows [64 bi, + 64) against the column tiles [ch CH, ch CH + CH);
+// part[ch][i] = #{ j in the chunk : d^2(i, j) <= radius2[j] }
+__global__ __launch_bounds__(256) void k_nn_ball(const float* __restrict__ Zq, const float* __restrict__ nq_nrm, int nq,
+                                                 const float* __restrict__ Zr, const float* __restrict__ nr_nrm, int nr,
+                                                 int Dp, const float* __restrict__ radius2, int exclude_self, int nbj,
+                                                 int CH, int nch, int* __restrict__ part) {
+  __shared__ int red[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, c = lane & 15;
+  const int bi = blockIdx.x / nch, ch = blockIdx.x - bi * nch;
+  const int i0 = bi * NN_I;
+  float ni[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) ni[a] = nq_nrm[min(i0 + 16 * a + c, nq - 1)];
+  int cnt[4] = {0, 0, 0, 0};
+  const int bj_hi = min(ch * CH + CH, nbj);
+  for (int bj = ch * CH; bj < bj_hi; ++bj) {
+    const int j0 = bj * NN_J + wave * 64;
+    if (j0 >= nr) continue;  // (wave-uniform)
+    f32x4 acc[4][4];
+    nn_tile(Zq, nq, i0, Zr, nr, j0, Dp, q, c, acc);
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = j0 + 16 * b + 4 * q + r;
+        const int jc = min(j, nr - 1);
+        const float nj = nr_nrm[jc], rad = radius2[jc];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+          const int i = i0 + 16 * a + c;
+          const bool in = j < nr && !(exclude_self && i == j) && nn_d2(ni[a], nj, acc[a][b][r]) <= rad;
+          cnt[a] += in ? 1 : 0;
+        }
+      }
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    int v = cnt[a];
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    if (q == 0) red[wave][16 * a + c] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int i = i0 + (int)threadIdx.x;
+    if (i < nq)
+      part[(size_t)ch * nq + i] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+  }
+}
+__global__ __launch_bounds__(256) void k_nn_count_sum(const int* __restrict__ part, int nch, int nq,
+                                                      int32_t* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nq) return;
+  int a = 0;
+  for (int ch = 0; ch < nch; ++ch) a += part[(size_t)ch * nq + i];
+  out[i] = a;
+}
+
+// radius2[i] = (float)dist2[i][col]: the ball-count radii from a search result
+__global__ __launch_bounds__(256) void k_nn_radius(const double* __restrict__ dist2, int n, int k, int col,
+                                                   float* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = (float)dist2[(size_t)i * k + col];
+}
+
+__device__ __forceinline__ double nn_block_min(double v, double* red) {  // fixed-order tree over 256 threads
+  __syncthreads();
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] = fmin(red[threadIdx.x], red[threadIdx.x + s]);
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// One workgroup.  Y: the n originals, X: the m samples (include/ffd.h ffd_nn_scores).
+__global__ __launch_bounds__(256) void k_nn_scores(const double* __restrict__ self_y, const double* __restrict__ xy_d2,
+                                                   const int32_t* __restrict__ xy_idx, const double* __restrict__ yx_d2,
+                                                   const int32_t* __restrict__ cnt_x, const int32_t* __restrict__ cnt_y,
+                                                   int n, int m, int k, double* __restrict__ out) {
+  __shared__ double red[256];
+  double prec = 0.0, dens = 0.0, auth = 0.0, nsum = 0.0, copies = 0.0, nmin = __builtin_inf();
+  for (int x = threadIdx.x; x < m; x += 256) {
+    const int cx = cnt_x[x];
+    const double d2 = xy_d2[x];
+    const int y = min(max(xy_idx[x], 0), n - 1);
+    const double d = sqrt(d2);
+    prec += cx > 0 ? 1.0 : 0.0;
+    dens += (double)cx;
+    auth += d2 > self_y[(size_t)y * k] ? 1.0 : 0.0;
+    nsum += d;
+    nmin = fmin(nmin, d);
+    copies += d2 == 0.0 ? 1.0 : 0.0;
+  }
+  double rec = 0.0, cov = 0.0;
+  for (int y = threadIdx.x; y < n; y += 256) {
+    rec += cnt_y[y] > 0 ? 1.0 : 0.0;
+    cov += yx_d2[y] <= self_y[(size_t)y * k + (k - 1)] ? 1.0 : 0.0;
+  }
+  prec = block_sum(prec, red);
+  rec = block_sum(rec, red);
+  dens = block_sum(dens, red);
+  cov = block_sum(cov, red);
+  auth = block_sum(auth, red);
+  nsum = block_sum(nsum, red);
+  copies = block_sum(copies, red);
+  nmin = nn_block_min(nmin, red);
+  if (threadIdx.x == 0) {
+    out[0] = prec / (double)m;
+    out[1] = rec / (double)n;
+    out[2] = dens / ((double)k * (double)m);
+    out[3] = cov / (double)n;
+    out[4] = auth / (double)m;
+    out[5] = nsum / (double)m;
+    out[6] = nmin;
+    out[7] = copies / (double)m;
+  }
+}
+
+// ---- host: workspace, plan ---------------------------------------------------------------------------------------
+static size_t nn_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static size_t nn_pow2_floor(size_t v) {
+  size_t p = 1;
+  while (p * 2 <= v) p *= 2;
+  return p;
+}
+static size_t nn_pow2_ceil(size_t v) {
+  size_t p = 1;
+  while (p < v) p *= 2;
+  return p;
+}
+
+// The fixed part of the workspace, every piece a multiple of 16 bytes: the centred sets, their norms, the mean and its
+// slab sums, then the running lists (search, k >= 1) or the partial counts (ball counts, k == 0).
+struct NNPlan {
+  int Dp, nslab, nbi, nbj;
+  size_t zr, zq, nrm_r, nrm_q, mean, colpart, tail_a, tail_b, fixed;  // byte offsets
+};
+static NNPlan nn_plan(int nq, int nr, int D, int k) {
+  NNPlan p;
+  p.Dp = (int)nn_up(D, 16);
+  p.nslab = cdiv(nr, NN_SLAB);
+  p.nbi = cdiv(nq, NN_I);
+  p.nbj = cdiv(nr, NN_J);
+  size_t o = 0;
+  p.zr = o, o += (size_t)nr * p.Dp * 4;
+  p.zq = o, o += (size_t)nq * p.Dp * 4;
+  p.nrm_r = o, o += nn_up((size_t)nr * 4, 16);
+  p.nrm_q = o, o += nn_up((size_t)nq * 4, 16);
+  p.mean = o, o += (size_t)p.Dp * 4;
+  p.colpart = o, o += nn_up((size_t)p.nslab * D * 8, 16);
+  if (k > 0) {
+    p.tail_a = o, o += nn_up((size_t)nq * k * 4, 16);  // cand_d
+    p.tail_b = o, o += nn_up((size_t)nq * k * 4, 16);  // cand_i
+  } else {
+    p.tail_a = p.tail_b = o, o += nn_up((size_t)std::min(p.nbj, NN_MAX_CHUNKS) * nq * 4, 16);  // part
+  }
+  p.fixed = o;
+  return p;
+}
+// column tiles per chunk and row tiles per block of the distance block that `units` 64 x 256 tiles allow
+static void nn_block(size_t units, const NNPlan& p, int* cbt, int* qbt) {
+  units = nn_pow2_floor(std::max<size_t>(1, std::min(units, NN_MAX_UNITS)));
+  *cbt = (int)std::min(units, std::min<size_t>(nn_pow2_ceil(p.nbj), NN_MAX_CBT));
+  *qbt = (int)std::min<size_t>(units / *cbt, p.nbi);
+}
+static bool nn_shape_ok(int nq, int nr, int D) { return nq >= 1 && nr >= 1 && D >= 1; }
+static bool nn_shape_supported(int nq, int nr, int D) { return nq <= NN_MAX_ROWS && nr <= NN_MAX_ROWS && D <= NN_MAX_D; }
+static size_t nn_search_bytes(int nq, int nr, int D, int k, size_t budget) {
+  const NNPlan p = nn_plan(nq, nr, D, k);
+  int cbt, qbt;
+  nn_block(budget / NN_UNIT_BYTES, p, &cbt, &qbt);
+  return p.fixed + (size_t)cbt * qbt * NN_UNIT_BYTES;
+}
+static size_t nn_ball_bytes(int nq, int nr, int D) { return nn_plan(nq, nr, D, 0).fixed; }
+
+static bool nn_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// the reference mean, then both centred copies (one where the query set is the reference set)
+static hipError_t nn_centre(const float* query, int nq, const float* ref, int nr, int D, const NNPlan& p, char* work,
+                            const float** zq_out, const float** nrm_q_out, hipStream_t s) {
+  float* Zr = (float*)(work + p.zr);
+  float* nrm_r = (float*)(work + p.nrm_r);
+  float* mean = (float*)(work + p.mean);
+  double* colpart = (double*)(work + p.colpart);
+  hipLaunchKernelGGL(k_nn_colpart, dim3(cdiv(D, 64), p.nslab), dim3(256), 0, s, ref, nr, D, colpart);
+  hipLaunchKernelGGL(k_nn_colmean, dim3(cdiv(D, 256)), dim3(256), 0, s, colpart, p.nslab, nr, D, mean);
+  hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(nr, 4)), dim3(256), 0, s, ref, mean, Zr, nrm_r, nr, D, p.Dp);
+  *zq_out = Zr;
+  *nrm_q_out = nrm_r;
+  if (!(query == ref && nq == nr)) {
+    float* Zq = (float*)(work + p.zq);
+    float* nrm_q = (float*)(work + p.nrm_q);
+    hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(nq, 4)), dim3(256), 0, s, query, mean, Zq, nrm_q, nq, D, p.Dp);
+    *zq_out = Zq;
+    *nrm_q_out = nrm_q;
+  }
+  return hipGetLastError();
+}
+
+}  // namespace ffd
+
+// ---- C ABI (include/ffd.h): nearest-neighbour statistics ----
+using namespace ffd;
+
+extern "C" {
+
+size_t ffd_nn_work_bytes(int nq, int nr, int D, int k, size_t budget_bytes) {
+  if (!nn_shape_ok(nq, nr, D) || !nn_shape_supported(nq, nr, D) || k < 1 || k > FFD_NN_MAX_K) return 0;
+  return std::max(nn_search_bytes(nq, nr, D, k, budget_bytes), nn_ball_bytes(nq, nr, D));
+}
+
+int ffd_nn_search(const float* query, int nq, const float* ref, int nr, int D, int k, int exclude_self, double* dist2_out,
+                  int32_t* index_out, void* work, size_t work_bytes, void* stream) {
+  if (!query || !ref || !dist2_out || !index_out || !work || !nn_shape_ok(nq, nr, D)) return FFD_ERR_INVALID;
+  if (k < 1 || k > FFD_NN_MAX_K || (long long)k > (long long)nr - (exclude_self ? 1 : 0)) return FFD_ERR_INVALID;
+  if (exclude_self && (query != ref || nq != nr)) return FFD_ERR_INVALID;
+  if (!nn_shape_supported(nq, nr, D)) return FFD_ERR_UNSUPPORTED;
+  const NNPlan p = nn_plan(nq, nr, D, k);
+  if (((uintptr_t)work & 15) || work_bytes < p.fixed + NN_UNIT_BYTES) return FFD_ERR_INVALID;
+  const size_t qb = (size_t)nq * D * 4, rb = (size_t)nr * D * 4, db = (size_t)nq * k * 8, xb = (size_t)nq * k * 4;
+  if (nn_overlap(dist2_out, db, query, qb) || nn_overlap(dist2_out, db, ref, rb) || nn_overlap(index_out, xb, query, qb) ||
+      nn_overlap(index_out, xb, ref, rb) || nn_overlap(dist2_out, db, index_out, xb) ||
+      nn_overlap(work, work_bytes, query, qb) || nn_overlap(work, work_bytes, ref, rb) ||
+      nn_overlap(work, work_bytes, dist2_out, db) || nn_overlap(work, work_bytes, index_out, xb))
+    return FFD_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  char* w = (char*)work;
+  const float *Zq, *nrm_q;
+  if (nn_centre(query, nq, ref, nr, D, p, w, &Zq, &nrm_q, s) != hipSuccess) return FFD_ERR_HIP;
+  const float* Zr = (const float*)(w + p.zr);
+  const float* nrm_r = (const float*)(w + p.nrm_r);
+  float* cand_d = (float*)(w + p.tail_a);
+  int* cand_i = (int*)(w + p.tail_b);
+  float* T = (float*)(w + p.fixed);
+  int cbt, qbt;
+  nn_block((work_bytes - p.fixed) / NN_UNIT_BYTES, p, &cbt, &qbt);
+  const int cb = cbt * NN_J;
+  for (int bi = 0; bi < p.nbi; bi += qbt) {
+    const int ib0 = bi * NN_I, rows = std::min(qbt * NN_I, nq - ib0), nqt = cdiv(rows, NN_I);
+    for (int bj = 0; bj < p.nbj; bj += cbt) {
+      const int jc0 = bj * NN_J, nct = std::min(cbt, p.nbj - bj), ncols = std::min(cb, nr - jc0);
+      hipLaunchKernelGGL(k_nn_tile, dim3(nqt * nct), dim3(256), 0, s, Zq, nrm_q, nq, Zr, nrm_r, nr, p.Dp, ib0, jc0, nct, cb,
+                         T);
+      hipLaunchKernelGGL(k_nn_merge, dim3(cdiv(rows, 4)), dim3(256), 0, s, T, cb, rows, ib0, jc0, ncols, exclude_self ? 1 : 0,
+                         k, bj == 0 ? 1 : 0, cand_d, cand_i);
+      if (hipGetLastError() != hipSuccess) return FFD_ERR_HIP;
+    }
+  }
+  hipLaunchKernelGGL(k_nn_refine, dim3(cdiv(nq, 4)), dim3(256), 0, s, query, ref, nq, nr, D, k, cand_i, dist2_out, index_out);
+  return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+int ffd_nn_ball_count(const float* query, int nq, const float* ref, int nr, int D, const float* radius2, int exclude_self,
+                      int32_t* count_out, void* work, size_t work_bytes, void* stream) {
+  if (!query || !ref || !radius2 || !count_out || !work || !nn_shape_ok(nq, nr, D)) return FFD_ERR_INVALID;
+  if (exclude_self && (query != ref || nq != nr)) return FFD_ERR_INVALID;
+  if (!nn_shape_supported(nq, nr, D)) return FFD_ERR_UNSUPPORTED;
+  if (((uintptr_t)work & 15) || work_bytes < ffd_nn_work_bytes(nq, nr, D, 1, 0)) return FFD_ERR_INVALID;
+  const size_t qb = (size_t)nq * D * 4, rb = (size_t)nr * D * 4, cbytes = (size_t)nq * 4, radb = (size_t)nr * 4;
+  if (nn_overlap(count_out, cbytes, query, qb) || nn_overlap(count_out, cbytes, ref, rb) ||
+      nn_overlap(count_out, cbytes, radius2, radb) || nn_overlap(work, work_bytes, query, qb) ||
+      nn_overlap(work, work_bytes, ref, rb) || nn_overlap(work, work_bytes, radius2, radb) ||
+      nn_overlap(work, work_bytes, count_out, cbytes))
+    return FFD_ERR_INVALID;
+  const NNPlan p = nn_plan(nq, nr, D, 0);
+  hipStream_t s = (hipStream_t)stream;
+  char* w = (char*)work;
+  const float *Zq, *nrm_q;
+  if (nn_centre(query, nq, ref, nr, D, p, w, &Zq, &nrm_q, s) != hipSuccess) return FFD_ERR_HIP;
+  int* part = (int*)(w + p.tail_a);
+  const int CH = cdiv(p.nbj, NN_MAX_CHUNKS), nch = cdiv(p.nbj, CH);
+  hipLaunchKernelGGL(k_nn_ball, dim3(p.nbi * nch), dim3(256), 0, s, Zq, nrm_q, nq, (const float*)(w + p.zr),
+                     (const float*)(w + p.nrm_r), nr, p.Dp, radius2, exclude_self ? 1 : 0, p.nbj, CH, nch, part);
+  hipLaunchKernelGGL(k_nn_count_sum, dim3(cdiv(nq, 256)), dim3(256), 0, s, part, nch, nq, count_out);
+  return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+int ffd_nn_radius(const double* dist2, int n, int k, int col, float* radius2_out, void* stream) {
+  if (!dist2 || !radius2_out || n < 1 || k < 1 || k > FFD_NN_MAX_K || col < 0 || col >= k) return FFD_ERR_INVALID;
+  if (nn_overlap(dist2, (size_t)n * k * 8, radius2_out, (size_t)n * 4)) return FFD_ERR_INVALID;
+  if (n > NN_MAX_ROWS) return FFD_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(k_nn_radius, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, dist2, n, k, col, radius2_out);
+  return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+int ffd_nn_scores(const double* self_dist2, const double* xy_dist2, const int32_t* xy_index, const double* yx_dist2,
+                  const int32_t* count_x, const int32_t* count_y, int n, int m, int k, double* out8, void* stream) {
+  if (!self_dist2 || !xy_dist2 || !xy_index || !yx_dist2 || !count_x || !count_y || !out8) return FFD_ERR_INVALID;
+  if (n < 1 || m < 1 || k < 1 || k > FFD_NN_MAX_K) return FFD_ERR_INVALID;
+  if (nn_overlap(out8, 64, self_dist2, (size_t)n * k * 8) || nn_overlap(out8, 64, xy_dist2, (size_t)m * 8) ||
+      nn_overlap(out8, 64, xy_index, (size_t)m * 4) || nn_overlap(out8, 64, yx_dist2, (size_t)n * 8) ||
+      nn_overlap(out8, 64, count_x, (size_t)m * 4) || nn_overlap(out8, 64, count_y, (size_t)n * 4))
+    return FFD_ERR_INVALID;
+  if (n > NN_MAX_ROWS || m > NN_MAX_ROWS) return FFD_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(k_nn_scores, dim3(1), dim3(256), 0, (hipStream_t)stream, self_dist2, xy_dist2, xy_index, yx_dist2,
+                     count_x, count_y, n, m, k, out8);
+  return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
+}
+
+}  // extern "C"

@@ -11,6 +11,7 @@ from __future__ import annotations
 from abc import ABC, abstractmethod
 from functools import partial
 
+from ..utils import neighbours
 from ..utils.fourier import dft, spectral_density
 from ..utils.tensors import check_flat_array
 from ..utils.wasserstein import WassersteinDistances, _column_mean, _summary, _to_device
@@ -163,3 +164,47 @@ class MarginalWasserstein(Metric):
     @property
     def name(self) -> str:
         return "marginal_wasserstein"
+
+
+class ManifoldMetrics(Metric):
+    """Nearest-neighbour statistics of a sample set X against the originals Y (``utils.neighbours``; not in the
+    reference, whose metrics are Wasserstein distances only): improved precision / recall (Kynkaanniemi et al. 2019),
+    density / coverage (Naeem et al. 2020), authenticity (Alaa et al. 2022), the distance to the nearest original and
+    the share of exact copies.  With r_k(y) the distance from y to its k-th neighbour inside Y (itself excluded) and
+    rho_k(x) likewise inside X:
+
+    ``precision`` share of x inside some ball (y, r_k(y)); ``recall`` share of y inside some ball (x, rho_k(x));
+    ``density`` the balls (y, r_k(y)) holding x, summed over x, over k m; ``coverage`` share of y whose nearest x lies
+    within r_k(y); ``authenticity`` share of x further from their nearest original y* than r_1(y*);
+    ``nn_distance_mean`` / ``nn_distance_min`` over x of the distance to Y; ``copy_share`` share of x at distance 0.
+
+    The originals' self-search is done once and kept, as ``SlicedWasserstein`` keeps its prepared set.  There is no
+    ``_dummy`` baseline: a single mean sample has no rho_k."""
+
+    def __init__(self, original_samples, k: int = 5) -> None:
+        super().__init__(original_samples=original_samples)
+        assert 1 <= int(k) <= neighbours.MAX_K, f"k must lie in [1, {neighbours.MAX_K}], got {k}"
+        self.k = int(k)
+        assert self.original_samples.shape[0] >= self.k + 1, \
+            f"k = {self.k} needs at least {self.k + 1} original samples, got {self.original_samples.shape[0]}"
+        self._original_self = None
+
+    def __call__(self, other_samples) -> dict:
+        other = check_flat_array(other_samples)
+        assert other.shape[0] >= self.k + 1, f"k = {self.k} needs at least {self.k + 1} samples, got {other.shape[0]}"
+        if self._original_self is None:
+            self._original_self = neighbours.self_search(self._original(), self.k)
+        return neighbours.manifold_scores(self._original(), other, self.k, original_self=self._original_self)
+
+    @property
+    def baseline_metrics(self) -> dict:
+        x = self._original()
+        fold_a, fold_b = x[: x.shape[0] // 2], x[x.shape[0] // 2:]  # the cut of _baseline_sets, without its mean sample
+        for fold in (fold_a, fold_b):
+            assert fold.shape[0] >= self.k + 1, f"k = {self.k} needs at least {self.k + 1} rows in each half, got {fold.shape[0]}"
+        found = neighbours.manifold_scores(fold_a, fold_b, self.k)
+        return {f"{key}_self": value for key, value in found.items()}
+
+    @property
+    def name(self) -> str:
+        return "manifold"

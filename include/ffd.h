@@ -727,6 +727,50 @@ int ffd_ens_bench_energy(const float* ens, const float* truth, const float* weig
                          int fair, double* energy_out, void* work, size_t work_bytes, int iters, float* ms_out,
                          void* stream);
 
+/* ---- nearest-neighbour statistics between two row sets: k-NN search, ball counts, precision / recall / density /
+ * coverage / authenticity (csrc/ffd_neighbours.hip; Kynkaanniemi et al. 2019, Naeem et al. 2020, Alaa et al. 2022) ----
+ * query (nq, D) and ref (nr, D): flat fp32 rows on the device, dense row-major, read only.  Distances are squared
+ * Euclidean.  Both sets are centred on the reference set's column mean (fixed-order fp64) into the workspace and the
+ * pair distances d2(i, j) = (n_i + n_j) - 2 z_i . z_j come from the exact-fp32 MFMA in 64 x 256 tiles, clamped at 0;
+ * uncentred, the Gram form loses the distances between neighbours of a cluster away from the origin.
+ *   search      per query row the k smallest (d2, index) over all reference rows, ordered by (value, then lower index);
+ *               the k kept pairs are then recomputed in difference form in fp64 on the caller's own rows,
+ *               sum_d ((double)a_d - (double)b_d)^2 in a fixed order, and sorted again by (value, index): dist2_out
+ *               (nq, k) doubles ascending (exactly 0.0 for identical rows), index_out (nq, k) int32.
+ *   ball count  count_out[i] = #{ j : d2(i, j) <= radius2[j] } on the same tiles, radius2 (nr) floats; integer partial
+ *               counts per (row, column chunk), added in chunk order.
+ *   exclude_self != 0 skips the pair i == j; legal only when query and ref are the same buffer and nq == nr.
+ * A block of the distance matrix goes through the workspace and one wave per row merges it into the row's running
+ * list.  (value, index) is a strict order and an element's bits do not depend on its tile, so the results are
+ * bit-identical from run to run, for every work_bytes, and for a query set searched whole or in parts.  No atomics.
+ * NaN input: unspecified.  Context-free, stream ordered, no host synchronisation.
+ * `work`: device scratch, 16-byte aligned, of at least the bytes the size query returns for (nq, nr, D, k, budget): both
+ * centred copies (4 (nq + nr) 16 ceil(D / 16) bytes), norms, mean, the running lists, and a distance block of as many
+ * 64 x 256 tiles (a power of two, at least one) as `budget_bytes` holds; the ball count needs what k = 1, budget 0 says.
+ * 0 for arguments the calls refuse.
+ * FFD_ERR_INVALID before any device work, outputs untouched: a null pointer, nq, nr, D < 1, k < 1 or k > FFD_NN_MAX_K,
+ * k > nr - (exclude_self != 0), exclude_self with query != ref or nq != nr, a workspace that is too small or not
+ * 16-byte aligned, an output or the workspace overlapping an input or another output;
+ * FFD_ERR_UNSUPPORTED: nq or nr > 2^24, D > 2^16. */
+enum { FFD_NN_MAX_K = 32 };
+size_t ffd_nn_work_bytes(int nq, int nr, int D, int k, size_t budget_bytes);
+int ffd_nn_search(const float* query, int nq, const float* ref, int nr, int D, int k, int exclude_self, double* dist2_out,
+                  int32_t* index_out, void* work, size_t work_bytes, void* stream);
+int ffd_nn_ball_count(const float* query, int nq, const float* ref, int nr, int D, const float* radius2, int exclude_self,
+                      int32_t* count_out, void* work, size_t work_bytes, void* stream);
+/* radius2_out[i] = (float)dist2[i][col] of a (n, k) search result: the radii of a ball count (0 <= col < k). */
+int ffd_nn_radius(const double* dist2, int n, int k, int col, float* radius2_out, void* stream);
+/* The eight sample-quality numbers of n originals Y and m samples X from six arrays on the device:
+ *   self_dist2 (n, k)   Y searched in itself with exclude_self: column 0 is r_1(y)^2, column k - 1 is r_k(y)^2
+ *   xy_dist2, xy_index (m)   each sample's nearest original;  yx_dist2 (n)   each original's nearest sample
+ *   count_x (m) = #{ y : d(x, y) <= r_k(y) };  count_y (n) = #{ x : d(y, x) <= rho_k(x) }, rho_k inside X
+ * out8 = precision (share of x with count_x > 0), recall (share of y with count_y > 0), density (sum count_x / (k m)),
+ * coverage (share of y with yx_dist2 <= r_k(y)^2), authenticity (share of x with xy_dist2 > r_1(y*)^2, y* = xy_index),
+ * the mean and the minimum over x of sqrt(xy_dist2), and the share of x with xy_dist2 == 0; fixed-order fp64 sums.
+ * FFD_ERR_INVALID: a null pointer, n, m < 1, k outside [1, FFD_NN_MAX_K], out8 overlapping an input. */
+int ffd_nn_scores(const double* self_dist2, const double* xy_dist2, const int32_t* xy_index, const double* yx_dist2,
+                  const int32_t* count_x, const int32_t* count_y, int n, int m, int k, double* out8, void* stream);
+
 /* ---- denoising score-matching loss: the `val/loss` of ScoreModule.validation_step (src/fdiff/utils/losses.py) ----
  * Per sample b, with std[b,l] = sigma[b] * G[l] and n = L * C (losses.py:68-80, sde.py:106-123,187-210):
  *   x_noisy = mean_coeff[b] * x0 + std[b,l] * z                  r = score + z / std[b,l]
