@@ -89,8 +89,8 @@ def run_ball(lib, Q, R, rad, exclude_self=False, same=False):
     return count.cpu().numpy()
 
 
-def check_search(got_d, got_i, Q, R, k, want_d, scale, bar, exclude_self=False):
-    nq, nr = Q.shape[0], R.shape[0]
+def check_search_structure(got_d, got_i, nq, nr, k, exclude_self=False):
+    """What needs no reference, over all rows: shape, fully overwritten, in range, distinct, ascending, never i."""
     assert got_d.shape == (nq, k) and got_i.shape == (nq, k)
     assert not np.isnan(got_d).any() and (got_i >= 0).all() and (got_i < nr).all()  # fully overwritten, in range
     srt = np.sort(got_i, axis=1)
@@ -98,21 +98,37 @@ def check_search(got_d, got_i, Q, R, k, want_d, scale, bar, exclude_self=False):
     if exclude_self:
         assert (got_i != np.arange(nq)[:, None]).all()
     assert (np.diff(got_d, axis=1) >= 0).all()
+
+
+def check_search_values(got_d, got_i, Q, R, k, want, scale, bar, rows=None):
+    """The value checks on the listed query rows (all for None); ``want``: float64's (dist2, index) of those rows."""
+    if rows is not None:
+        got_d, got_i, Q = got_d[rows], got_i[rows], Q[rows]
     own = ((Q.astype(np.float64)[:, None, :] - R.astype(np.float64)[got_i]) ** 2).sum(axis=2)
     assert (np.abs(got_d - own) <= 1e-12 * own).all(), np.abs(got_d - own).max()
     assert (got_d[own == 0.0] == 0.0).all()
-    diff = (got_d - want_d) / scale
+    diff = (got_d - want[0]) / scale
+    same = int((np.sort(got_i, axis=1) == np.sort(want[1], axis=1)).all(axis=1).sum())
     print(f"dist2 - float64 sorted: [{diff.min():.3e}, {diff.max():.3e}] of the scale {scale:.4e}; bar {bar:.3e}; "
-          f"index sets equal in {int((srt == np.sort(NR.knn(Q, R, k, exclude_self)[1], axis=1)).all(axis=1).sum())} of {nq} rows")
+          f"index sets equal in {same} of {len(got_d)} rows")
     assert diff.min() >= -1e-12 and diff.max() <= bar, (diff.min(), diff.max(), bar)
 
 
-def check_ball(got, Q, R, rad, scale, bar, exclude_self=False):
-    lo = NR.ball_counts(Q, R, rad, exclude_self, shift=-bar * scale)
-    hi = NR.ball_counts(Q, R, rad, exclude_self, shift=bar * scale)
+def check_search(got_d, got_i, Q, R, k, want_d, scale, bar, exclude_self=False):
+    check_search_structure(got_d, got_i, Q.shape[0], R.shape[0], k, exclude_self)
+    check_search_values(got_d, got_i, Q, R, k, (want_d, NR.knn(Q, R, k, exclude_self)[1]), scale, bar)
+
+
+def check_ball(got, Q, R, rad, scale, bar, exclude_self=False, rows=None):
+    """``rows``: judge only the listed query rows of the device's counts."""
+    lo = NR.ball_counts(Q, R, rad, exclude_self, shift=-bar * scale, rows=rows)
+    hi = NR.ball_counts(Q, R, rad, exclude_self, shift=bar * scale, rows=rows)
+    assert got.dtype == np.int32 and got.shape == (Q.shape[0],)
+    got = got if rows is None else got[rows]
     print(f"counts: {int((got != lo).sum())} rows above float64's lower count, {int((got != hi).sum())} below its upper, "
-          f"band open for {int((lo != hi).sum())} of {len(got)} rows")
-    assert got.dtype == np.int32 and (lo <= got).all() and (got <= hi).all()
+          f"band open for {int((lo != hi).sum())} of {len(got)} rows, mean count {got.mean():.1f}")
+    assert (lo <= got).all() and (got <= hi).all()
+    return lo, hi
 
 
 # ------------------------------------------------------------------ the contracts ----

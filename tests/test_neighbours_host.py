@@ -1,7 +1,9 @@
 """CPU-side tests of the nearest-neighbour statistics (no GPU): the C surface and its argument checks, the Python surface
 (``utils.neighbours``, ``ManifoldMetrics``: refusals, keys, composition on a fake native layer) and the numpy
 restatement (tests/neighbours_restatement.py) against formulations it shares no code with, the reason the Gram form is
-centred, and the facts about the ball-count band that keep the GPU tests from hiding a failure."""
+centred, and the facts about the ball-count band that keep the GPU tests from hiding a failure -- for the size cases of
+tests/test_neighbours_sizes_gpu.py too: the gapped radii close the band on every row, the row-subset restatement is the
+whole one on its rows, and the integer rows of the limit tests are exact in the fp32 Gram form."""
 import ctypes as C
 import os
 import re
@@ -17,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED = -1, -2
 NAMES = ("ffd_nn_work_bytes", "ffd_nn_search", "ffd_nn_ball_count", "ffd_nn_radius", "ffd_nn_scores")
 ALL_CASES = [(c, f) for f in NR.FAMILIES for c in range(len(NR.CASES))]
+SIZE_CASES = [(i, f) for f in NR.FAMILIES for i in range(len(NR.SIZE_CASES))]
 
 
 @pytest.fixture(scope="module")
@@ -349,6 +352,92 @@ def test_restatement_against_a_python_loop(case):
         assert d[0, 0] == 0.0 and idx[0, 0] == n and idx[n, 0] == 0
         d, idx = NR.knn(R[:1], R2, 2)
         assert d[0].tolist() == [0.0, 0.0] and idx[0].tolist() == [0, n]
+
+
+@pytest.mark.parametrize("case,family", ALL_CASES)
+def test_row_subsets_of_the_restatement(case, family):
+    """``knn_rows`` and ``ball_counts(rows=...)`` are ``knn`` and ``ball_counts`` on their rows, with and without the pair
+    i == i; ``size_radius2`` is ``self_radius2`` up to 8193 rows."""
+    Q, R, k = NR.make_case(case, family)
+    rng = np.random.default_rng(case)
+    for A, kk, excl in ((Q, k, False), (R, min(k, R.shape[0] - 1), True)):
+        rows = np.sort(rng.choice(A.shape[0], size=min(A.shape[0], 7), replace=False))
+        rows[-1] = A.shape[0] - 1
+        want_d, want_i = NR.knn(A, R, kk, exclude_self=excl)
+        got_d, got_i = NR.knn_rows(A, R, kk, rows, exclude_self=excl)
+        assert np.array_equal(got_d, want_d[rows]) and np.array_equal(got_i, want_i[rows]) and got_i.dtype == np.int32
+        rad = NR.self_radius2(R, k)
+        assert np.array_equal(NR.ball_counts(A, R, rad, excl, shift=1e-3, rows=rows), NR.ball_counts(A, R, rad, excl, shift=1e-3)[rows])
+    got = NR.size_radius2(R, k)
+    assert got.dtype == np.float32 and np.array_equal(got, NR.self_radius2(R, k))
+
+
+def test_size_cases_follow_the_recipes_of_make_case():
+    """Generator seed 5200 + i, the draws in the order of ``make_case``; the radii of a set longer than 8193 rows come
+    from a 512-row subsample and still give balls holding a few rows."""
+    assert len(NR.SIZE_CASES) == 8 and NR.SIZE_CASES[2] == (65, 16385, 8, 5)
+    for i in (0, 4):
+        nq, nr, D, k = NR.SIZE_CASES[i]
+        rng = np.random.default_rng(5200 + i)
+        R, Q = rng.standard_normal((nr, D)), rng.standard_normal((nq, D))
+        got = NR.make_size_case(i, "gaussian")
+        assert np.array_equal(got[0], Q.astype(np.float32)) and np.array_equal(got[1], R.astype(np.float32)) and got[2] == k
+        rng = np.random.default_rng(5200 + i)
+        c = 3 * rng.standard_normal((4, D)) + 10
+        R = c[rng.integers(0, 4, nr)] + 0.5 * rng.standard_normal((nr, D))
+        Q = c[rng.integers(0, 4, nq)] + 0.5 * rng.standard_normal((nq, D))
+        got = NR.make_size_case(i, "clustered")
+        assert np.array_equal(got[0], Q.astype(np.float32)) and np.array_equal(got[1], R.astype(np.float32))
+
+
+@pytest.mark.parametrize("i,family", SIZE_CASES)
+def test_gapped_radii_close_every_band(i, family):
+    """At ``gapped_radii`` float64's counts at radius^2 -+ bar scale coincide for EVERY row of every size case, so the GPU
+    test's second ball count is an equality test; at the radii as they are the band is open for the printed rows."""
+    Q, R, k = NR.make_size_case(i, family)
+    assert (*Q.shape, R.shape[0], k) == (NR.SIZE_CASES[i][0], NR.SIZE_CASES[i][2], NR.SIZE_CASES[i][1], NR.SIZE_CASES[i][3])
+    bar, s = NR.bar(Q, R), NR.scale(Q, R)
+    assert 2e-6 <= bar <= 1e-5, bar
+    rad = NR.size_radius2(R, k)
+    n_open = int((NR.ball_counts(Q, R, rad, shift=-bar * s) != NR.ball_counts(Q, R, rad, shift=bar * s)).sum())
+    gapped, moved = NR.gapped_radii(Q, R, rad, bar, s)
+    assert gapped.dtype == np.float32 and (gapped >= rad).all() and int((gapped != rad).sum()) == moved
+    lo, hi = NR.ball_counts(Q, R, gapped, shift=-bar * s), NR.ball_counts(Q, R, gapped, shift=bar * s)
+    mid = NR.ball_counts(Q, R, gapped)
+    print(f"size case {i} {family}: bar {bar:.3e}, scale {s:.4e}, band open for {n_open} of {Q.shape[0]} rows as they are; "
+          f"{moved} of {len(rad)} radii moved, by at most {float((gapped - rad).max() / (4 * bar * s)):.2f} steps; mean count "
+          f"{NR.ball_counts(Q, R, rad).mean():.1f} -> {mid.mean():.1f}")
+    assert np.array_equal(lo, hi) and np.array_equal(lo, mid)
+    d = NR.dist2(Q, R)
+    assert (np.abs(d - gapped.astype(np.float64)[None, :]) > 2.0 * bar * s).all()
+    assert 0 < mid.mean() < R.shape[0]  # neither no ball nor every ball
+
+
+def test_integer_rows_are_exact_in_the_fp32_gram_form():
+    """The inputs of the two limit tests: integers below 1021, D = 1.  The fp32 centred Gram form misses the integer squared
+    distances by less than 0.5 in both directions while distinct ones differ by at least 1, no query of the long query
+    set is equidistant from two reference rows, and every value of the long reference set occurs more than twice."""
+    long_rows = NR.hashed_rows(NR.LIMIT_ROWS)
+    assert long_rows.shape == (NR.LIMIT_ROWS, 1) and long_rows.dtype == np.float32
+    assert long_rows.min() == 0.0 and long_rows.max() == 1020.0 and (long_rows == np.round(long_rows)).all()
+    assert long_rows[:3, 0].tolist() == [0.0, 2654435761 % 1021, (2 * 2654435761 % (1 << 32)) % 1021]
+    few = np.array(NR.LIMIT_REFERENCE, np.float32)[:, None]
+    assert all((a + b) % 2 == 1 and a < b for a, b in zip(NR.LIMIT_REFERENCE, NR.LIMIT_REFERENCE[1:]))
+    worst = 0.0
+    for a in range(0, NR.LIMIT_ROWS, 1 << 21):  # the mean is the 5 rows': a block of queries at a time changes nothing
+        block = long_rows[a:a + (1 << 21)]
+        worst = max(worst, float(np.abs(NR.gram32(block, few).astype(np.float64) - NR.dist2(block, few)).max()))
+    queries = np.array(NR.LIMIT_QUERIES, np.float32)[:, None]
+    worst_r = float(np.abs(NR.gram32(queries, long_rows).astype(np.float64) - NR.dist2(queries, long_rows)).max())
+    s = NR.scale(queries, long_rows)
+    print(f"integer rows: scale {s:.3e}, Gram error {worst:.4f} (long query set), {worst_r:.4f} (long reference set)")
+    assert worst < 0.5 and worst_r < 0.5 and 2.5e5 < s < 2.7e5
+    assert np.bincount(long_rows[:, 0].astype(np.int64), minlength=1021).min() > 2
+    # offset by 2^23 the rows are still integers in fp32; centred on their mean the Gram form is exact, uncentred it is not
+    far = long_rows[:1025] + np.float32(NR.LIMIT_OFFSET)
+    assert np.array_equal(far.astype(np.float64), long_rows[:1025].astype(np.float64) + NR.LIMIT_OFFSET)
+    assert np.abs(NR.gram32(far[:70], far).astype(np.float64) - NR.dist2(far[:70], far)).max() == 0.0
+    assert np.abs(NR.gram32(far[:70], far, centred=False).astype(np.float64) - NR.dist2(far[:70], far)).max() > 0.5
 
 
 @pytest.mark.parametrize("case", [4, 6])
