@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import train_restatement as TR
+import transformer_restatement as R
 from conftest import rel_err
 from oracle import ffd_oracle as O
 from transformer_restatement import TOL_SCORE, bar as forward_bar
@@ -244,12 +245,42 @@ ATTN_SHAPES = [(3, 5, 2, 4), (5, 17, 12, 5), (4, 33, 12, 6), (2, 16, 12, 2), (2,
                (5, 512, 1, 8), (1, 1, 2, 4), (2, 7, 3, 1)]
 
 
-@pytest.mark.parametrize("shape", ATTN_SHAPES, ids=lambda s: "B{}L{}H{}hd{}".format(*s))
+# ... and scores far from zero by a shift common to a query row (list E of tests/transformer_restatement.py): dimension 0 of
+# each of the twelve heads carries head_plan's constant (+- 150 / 200 log2 units), key staircase or per-query offset
+SHIFTED_ATTN_SHAPES = [(2, 33, 12, 5, "shifted"), (2, 187, 12, 5, "shifted"), (2, 33, 12, 6, "shifted"), (2, 187, 12, 6, "shifted")]
+
+
+def shifted_qkv(qkv, B, L, H, hd):
+    """Standard-normal q | k | v rows with dimension 0 of every head's q and k set as shift_state_dict's projections
+    would set them."""
+    d, qs = H * hd, R.LOG2E / np.sqrt(hd)
+    rows = qkv.reshape(B, L, 3 * d)
+    stairs = R.e_inputs(torch.zeros(1, L, 2))[0].numpy()  # (L, 2): the staircase and the -1, 0, 1 pattern
+    for h, (kind, par) in enumerate(R.head_plan(H)):
+        q0, k0 = rows[:, :, h * hd], rows[:, :, d + h * hd]
+        if kind == "const":
+            q0[:], k0[:] = np.sqrt(abs(par) / qs), np.copysign(np.sqrt(abs(par) / qs), par)
+        elif kind == "ramp_k":
+            g = np.sqrt(R.E_RAMP_K / qs)
+            q0[:], k0[:] = g, g * (stairs[None, :, 0] + par + R.E_NOISE * k0)
+        elif kind == "ramp_q":
+            g = np.sqrt(R.E_RAMP_Q / qs)
+            k0[:], q0[:] = g, g * (stairs[None, :, 1] + R.E_NOISE * q0)
+    return qkv
+
+
+@pytest.mark.parametrize("shape", ATTN_SHAPES + SHIFTED_ATTN_SHAPES,
+                         ids=lambda s: "B{}L{}H{}hd{}".format(*s) + ("_shifted" if len(s) > 4 else ""))
 def test_attention_with_lse_and_its_backward(lib, shape):
-    B, L, H, hd = shape
+    B, L, H, hd = shape[:4]
     d = H * hd
     rng = np.random.default_rng(B + 3 * L + 5 * H + 7 * hd)
     qkv, dout = rng.standard_normal((B * L, 3 * d)).astype(np.float32), rng.standard_normal((B * L, d)).astype(np.float32)
+    if len(shape) > 4:
+        qkv = shifted_qkv(qkv, B, L, H, hd)
+        s0 = qkv.reshape(B, L, 3, H, hd).astype(np.float64)
+        top = np.abs(np.einsum("blhe,bmhe->bhlm", s0[:, :, 0], s0[:, :, 1])).max() * R.LOG2E / np.sqrt(hd)
+        assert top > 2 * R.ATTN_T, top
 
     def ref(dt):
         t = torch.from_numpy(qkv).to(dt).requires_grad_(True)
@@ -489,6 +520,28 @@ def test_transformer_training_forward_against_the_inference_forward(lib, case, s
         err = rel_err(got.cpu().numpy(), want)
         print(f"{what}: {err:.2e} (fp32 cpu {e32:.2e}, bar {forward_bar(e32):.2e})")
         assert err <= forward_bar(e32)
+
+
+def test_transformer_training_forward_against_the_inference_forward_on_shifted_scores(lib):
+    """A network off the init scale (list E of tests/transformer_restatement.py, head_dim 5, two key tiles): the training
+    forward (exact row maximum) and the fused inference forward (reference 0, refreshed) agree with float64 and so with
+    each other."""
+    from fastfourierdiffusion_amd.utils.dataclasses import DiffusableBatch
+
+    c = next(c for c in R.E_CASES if c["name"] == "E_d60_hd5_L33_B3")
+    m, rec = c["model"], R.reference(c)[0]
+    assert rec["events"]["first_pos"] and rec["events"]["first_neg"] and rec["events"]["later"]
+    model = TR.tf_model(dict(L=m["L"], C=m["C"], d=m["d"], H=m["H"], NL=m["NL"], F=m["F"], wseed=1), "vp")
+    model.load_state_dict(R.state_dict(m), strict=True)
+    tr = make_trainer(model)
+    dx, dt = R.inputs(c, 0).cuda(), torch.full((c["B"],), c["t"], dtype=torch.float32, device="cuda")
+    inf = model.eval()(DiffusableBatch(X=dx, timesteps=dt))
+    out = torch.empty_like(dx)
+    tr._check(lib.ffd_train_forward(tr.handle, dx.data_ptr(), dt.data_ptr(), out.data_ptr(), c["B"], stream()), "forward")
+    for what, got in (("training forward", out), ("inference forward", inf)):
+        err = rel_err(got.cpu().numpy(), rec["score"].numpy())
+        print(f"{what}: {err:.2e} (fp32 cpu {rec['e32']:.2e}, bar {forward_bar(rec['e32']):.2e})")
+        assert torch.isfinite(got).all() and err <= forward_bar(rec["e32"])
 
 
 class TfRun(TR.MlpRun):

@@ -24,6 +24,8 @@ cache, n: cached with the prefix {0 .. n-1} recomputed -- and the ffd_tune knobs
   B_CASES  dim_feedforward from one ring slot to 64, every FFN form
   C_CASES  L = 1 .. 8
   D_CASES  prefix lengths at the tile edges and at 0.8 L
+  E_CASES  attention scores far from the fused kernels' softmax reference 0, by a shift common to each query row, with
+           the float64 certificate score_events64 of what the kernels' reference rule meets (tests/test_attn_reference_*.py)
 """
 import functools
 import math
@@ -94,8 +96,9 @@ def _attention64(q, k, v, softmax_one):
     return torch.matmul(torch.softmax(s, dim=-1), v)
 
 
-def layer64(src, p, H, layer, table, n, softmax_one=False):
-    """One encoder layer; table None: the plain layer, else the cached mode of |recompute| = n (a prefix)."""
+def layer64(src, p, H, layer, table, n, softmax_one=False, probe=None):
+    """One encoder layer; table None: the plain layer, else the cached mode of |recompute| = n (a prefix).  ``probe``, if
+    given, is called with (layer, q, k) -- the (B, H, L, hd) queries and the keys the attention runs on."""
     B, L, d = src.shape
     hd = d // H
     wq, wk, wv = p["in_w"].split(d, dim=0)
@@ -103,7 +106,10 @@ def layer64(src, p, H, layer, table, n, softmax_one=False):
     heads = lambda x: O._split_heads(x, H)  # noqa: E731
     q = heads(F.linear(src, wq, bq))
     if table is None or n == L or n > 0.8 * L:
-        out = O._post_attention(src, _attention64(q, heads(F.linear(src, wk, bk)), heads(F.linear(src, wv, bv)), softmax_one), p)
+        k_own = heads(F.linear(src, wk, bk))
+        if probe is not None:
+            probe(layer, q, k_own)
+        out = O._post_attention(src, _attention64(q, k_own, heads(F.linear(src, wv, bv)), softmax_one), p)
         if table is not None and n == L:  # FULL: K, V of the layer OUTPUT, batch element 0
             table.k[layer] = heads(F.linear(out, wk, bk))[0]
             table.v[layer] = heads(F.linear(out, wv, bv))[0]
@@ -118,18 +124,20 @@ def layer64(src, p, H, layer, table, n, softmax_one=False):
         table.k[layer][:, :n] = k_full[0, :, :n]
         table.v[layer][:, :n] = v_full[0, :, :n]
         table.recompute_count += n
+    if probe is not None:
+        probe(layer, q, k_full)
     return O._post_attention(src, _attention64(q, k_full, v_full, softmax_one), p)
 
 
-def score_forward64(x, t, sd, num_layers, n_head, table=None, n=None, softmax_one=False):
-    """-> score (B, L, C) float64.  x (B, L, C), t (B,) fp32; ``table`` / ``n`` select the cached path."""
+def score_forward64(x, t, sd, num_layers, n_head, table=None, n=None, softmax_one=False, probe=None):
+    """-> score (B, L, C) float64.  x (B, L, C), t (B,) fp32; ``table`` / ``n`` select the cached path; ``probe``: layer64."""
     s64 = sd64(sd)
     d = s64["embedder.weight"].shape[0]
     h = F.linear(x.to(torch.float64), s64["embedder.weight"], s64["embedder.bias"])
     h = h + renorm_rows64(s64["pos_encoder.embedding.weight"], math.sqrt(d))[None, : x.shape[1], :]
     h = h + time_embedding64(t, sd, s64, d)[:, None, :]
     for i in range(num_layers):
-        h = layer64(h, O._layer_params(s64, i), n_head, i, table if n is not None else None, n, softmax_one)
+        h = layer64(h, O._layer_params(s64, i), n_head, i, table if n is not None else None, n, softmax_one, probe)
     return F.linear(h, s64["unembedder.weight"], s64["unembedder.bias"])
 
 
@@ -340,18 +348,226 @@ D_SEQ50 = (None, 50, 0, 1, 0, 15, 16, 17, 0, 31, 32, 33, 0, 39, 40, 41, 0)  # 40
 D_CASES = [case("d72_hd6_L70_B5", model(72, 6, 70), 5, D_SEQ70), case("d72_hd6_L187_B5", model(72, 6, 187), 5, D_SEQ187),
            case("d60_hd5_L50_B5", model(60, 5, 50), 5, D_SEQ50, forms=("two_heads",))]
 
-ALL_CASES = dict(A=A_CASES, B=B_CASES + B_HEIGHT_CASES + B_TILE_CASES, C=C_CASES, D=D_CASES)
+# E: scores far from the fused kernels' softmax reference 0, by a shift COMMON to a query row's scores -- softmax does not
+# see it, so the differences stay at the init scale and fp32 and float64 agree as on every other list (e32 under
+# E32_LIMIT, held by tests/test_attn_reference_host.py).  A model with ``shift`` (shift_state_dict) has
+#   * the embedding's column space to the data alone: positional rows, embedding bias and time embedding are projected
+#     onto its orthogonal complement, so that u_c . h = x[..., c] exactly for the dual vectors u_c of the embedding;
+#   * per head h, by h mod 6 (h mod 4 where H = 4), in dimension 0 of the head (rows h hd of the q and k blocks):
+#       const    q row = k row = 0, biases a and +- a: every score is +- a^2 / sqrt(hd) (+- S in log2 units) plus the rest,
+#                in EVERY layer and for table rows too (the bias survives the K projection of another hidden state);
+#                S = 200 / 150 (x ``shift``) beyond the threshold T = 64 -- and beyond fp32's exponent range, so that a missing
+#                reference overflows or loses the row --, S = 25 within it;
+#       ramp_k   (layer 0) q row = 0, q bias g, k row = g u_0, k bias g o: score = 72 (x[key, 0] + o) log2 units, the same for
+#                every query; channel 0 of the E inputs is a staircase over the key positions (e_inputs), so the key
+#                tiles' maxima rise by 72 > T from one plateau to the next; o = -2 in the second such head starts the row
+#                with a NEGATIVE reference;
+#       ramp_q   (layer 0) k row = 0, k bias g, q row = g u_1: score = 170 x[query, 1], the same for every key; channel 1 is
+#                -1, 0, 1, -1 ... over the positions, so adjacent query rows of one 32-query tile refresh downwards, not
+#                at all, upwards;
+#       plain    untouched (a head the norm product bounds, next to one it does not).
+# The fp32 error of a score grows with its magnitude (an ulp of 1000 log2 units is 6e-5), so the shifts are no larger than
+# the events need: with constants of 400 and plateaus of 80 up to 320 the oracle's e32 reached 3.3e-6 on some cases; at
+# the values here it is at most 2.1e-6.
+# The kernels' rule on these scores is restated by score_events64; each case names the events it must show.
+LOG2E = 1.4426950408889634
+ATTN_T = 64.0      # ATTN_SCORE_T of csrc/ffd_internal.h
+EVENT_MARGIN = 1.0  # an event counts only where every comparison of its row is this far (log2 units) from its threshold
+E_STEPS = (32, 66, 170, 500)  # channel 0 rises by 1 there: at a tile edge, inside tile 2, in the last tile of L = 187 and of L = 512
+E_NOISE = 0.02     # what is left of the noise in the two channels the ramps read
+E_RAMP_K, E_RAMP_Q = 72.0, 170.0  # (170: outside fp32's exponent range on both sides, like the constants)
+E_KINDS6 = ("const+", "plain", "const-", "ramp_k", "const_small", "ramp_q")
+E_KINDS4 = ("const+", "const-", "ramp_k", "ramp_q")
+EVENTS = ("first_pos", "first_neg", "later", "multi", "none", "last_tile_max", "mixed_qtile", "bound_mixed", "split2_merge",
+          "split4_merge")
+
+
+def head_plan(H, shift=1.0):
+    """[(kind, parameter)] per head: const -> the signed shift in log2 units, ramp_k -> the plateau offset o."""
+    kinds = E_KINDS4 if H < 8 else E_KINDS6
+    plan = []
+    for h in range(H):
+        kind, rep = kinds[h % len(kinds)], h // len(kinds)
+        if kind == "const+":
+            plan.append(("const", shift * (200.0, 150.0)[rep % 2]))
+        elif kind == "const-":
+            plan.append(("const", -shift * (200.0, 150.0)[rep % 2]))
+        elif kind == "const_small":
+            plan.append(("const", (25.0, -25.0)[rep % 2]))
+        elif kind == "ramp_k":
+            plan.append(("ramp_k", (0.0, -2.0)[rep % 2]))
+        else:
+            plan.append((kind, 0.0))
+    return plan
+
+
+def shift_state_dict(sd, m):
+    """The E model of the comment above, in place on a state dict of fp32 tensors."""
+    d, H = m["d"], m["H"]
+    hd, qs = d // H, LOG2E / math.sqrt(d // H)
+    We = sd["embedder.weight"].double()  # (d, C)
+    G = torch.linalg.inv(We.T @ We)
+    U = We @ G  # column c: u_c . (We x) = x[c]
+    Pc = torch.eye(d, dtype=torch.float64) - We @ G @ We.T  # onto the complement of the embedding's column space
+    sd["pos_encoder.embedding.weight"] = (sd["pos_encoder.embedding.weight"].double() @ Pc).float()
+    for key in ("embedder.bias", "time_encoder.dense.weight", "time_encoder.dense.bias"):
+        sd[key] = (Pc @ sd[key].double()).float()
+    for i in range(m["NL"]):
+        W, b = sd[f"backbone.layers.{i}.self_attn.in_proj_weight"], sd[f"backbone.layers.{i}.self_attn.in_proj_bias"]
+        for h, (kind, par) in enumerate(head_plan(H, m["shift"])):
+            rq, rk = h * hd, d + h * hd
+            if kind == "const":
+                a = math.sqrt(abs(par) / qs)
+                W[rq], W[rk], b[rq], b[rk] = 0.0, 0.0, a, math.copysign(a, par)
+            elif kind == "ramp_k" and i == 0:
+                g = math.sqrt(E_RAMP_K / qs)
+                W[rq], b[rq], W[rk], b[rk] = 0.0, g, (g * U[:, 0]).float(), g * par
+            elif kind == "ramp_q" and i == 0:
+                g = math.sqrt(E_RAMP_Q / qs)
+                W[rk], b[rk], W[rq], b[rq] = 0.0, g, (g * U[:, 1]).float(), 0.0
+    return sd
+
+
+def e_inputs(x):
+    """Channel 0: the staircase of E_STEPS; channel 1: -1, 0, 1 over the positions; E_NOISE of the noise on top of both."""
+    pos = torch.arange(x.shape[1])
+    stairs = sum((pos >= s).to(x.dtype) for s in E_STEPS)
+    x = x.clone()
+    x[..., 0] = E_NOISE * x[..., 0] + stairs
+    x[..., 1] = E_NOISE * x[..., 1] + ((pos % 3) - 1).to(x.dtype)
+    return x
+
+
+def _walk(tmax):
+    """The kernels' reference rule over the key tiles of one piece.  tmax (..., nt): the tiles' largest score per query row
+    -> dict(mref, n (refreshes), first_pos, first_neg, later, sure (every comparison EVENT_MARGIN from its threshold))."""
+    shape = tmax.shape[:-1]
+    mref, n = torch.zeros(shape, dtype=torch.float64), torch.zeros(shape, dtype=torch.int64)
+    sure = torch.ones(shape, dtype=torch.bool)
+    first_pos = first_neg = later = torch.zeros(shape, dtype=torch.bool)
+    for t in range(tmax.shape[-1]):
+        b = tmax[..., t] - mref
+        v = b.abs() if t == 0 else b  # the first tile refreshes on |max| > T, later ones on max > T
+        refresh = v > ATTN_T
+        sure = sure & ((v - ATTN_T).abs() >= EVENT_MARGIN)
+        if t == 0:
+            first_pos, first_neg = refresh & (b > 0), refresh & (b < 0)
+        else:
+            later = later | refresh
+        mref = torch.where(refresh, mref + b, mref)
+        n = n + refresh
+    return dict(mref=mref, n=n, first_pos=first_pos, first_neg=first_neg, later=later, sure=sure)
+
+
+def tile_maxima(s):
+    """(..., Lq, Lk) scores -> (..., Lq, KT): the largest score of each 32-key tile (the ragged last one: its live keys)."""
+    Lk = s.shape[-1]
+    KT = -(-Lk // 32)
+    pad = torch.full(s.shape[:-1] + (KT * 32 - Lk,), -math.inf, dtype=s.dtype)
+    return torch.cat([s, pad], dim=-1).reshape(s.shape[:-1] + (KT, 32)).amax(dim=-1)
+
+
+def row_events(tmax):
+    """Event counts of score rows given by their tile maxima (..., Lq, KT), Lq rows making 32-query tiles in order."""
+    KT = tmax.shape[-1]
+    w = _walk(tmax)
+    sure, n = w["sure"], w["n"]
+    ev = dict(first_pos=w["first_pos"] & sure, first_neg=w["first_neg"] & sure, later=w["later"] & sure,
+              multi=(n >= 2) & sure, none=(n == 0) & sure)
+    if KT >= 2:
+        ev["last_tile_max"] = tmax[..., -1] >= tmax[..., :-1].amax(dim=-1) + EVENT_MARGIN
+    out = {k: int(v.sum()) for k, v in ev.items()}
+    Lq = tmax.shape[-2]
+    padq = (-Lq) % 32
+    tiles = lambda a: torch.cat([a, torch.zeros(a.shape[:-1] + (padq,), dtype=torch.bool)], -1).reshape(a.shape[:-1] + (-1, 32))  # noqa: E731
+    out["mixed_qtile"] = int((tiles(ev["none"]).any(-1) & tiles((n >= 1) & sure).any(-1)).sum())
+    for kspl in (2, 4):  # the split form: each key piece starts from reference 0 on its own first tile
+        kps = -(-KT // kspl)
+        pieces = [_walk(tmax[..., p * kps: min(KT, (p + 1) * kps)]) for p in range(kspl) if p * kps < KT]
+        hit = torch.zeros(tmax.shape[:-1], dtype=torch.bool)
+        for i, a in enumerate(pieces):
+            for c in pieces[i + 1:]:
+                gap = (a["mref"] - c["mref"]).abs()
+                hit = hit | (a["sure"] & c["sure"] & (a["mref"] != 0) & (c["mref"] != 0) & (gap > 0) & (gap < 20.0))
+        out[f"split{kspl}_merge"] = int(hit.sum())
+    return out
+
+
+def score_events64(q, k):
+    """The events of one layer's attention: q, k (B, H, L, hd) float64 as layer64's probe hands them over.  Scores in the
+    kernels' log2 domain, q k^T log2(e) / sqrt(hd); bound_mixed: workgroups of heads (2 g, 2 g + 1) of which one is within
+    T by the kernel's product of the largest |q| and the largest |k| (head_bounded) and one is not."""
+    qs = LOG2E / math.sqrt(q.shape[-1])
+    out = row_events(tile_maxima(torch.matmul(q, k.transpose(-2, -1)) * qs))
+    r = qs * q.norm(dim=-1).amax(dim=-1) * k.norm(dim=-1).amax(dim=-1)  # (B, H)
+    inside, outside = r <= ATTN_T - EVENT_MARGIN, r >= ATTN_T + EVENT_MARGIN
+    H2 = q.shape[1] // 2 * 2
+    out["bound_mixed"] = int(((inside[:, 0:H2:2] & outside[:, 1:H2:2]) | (outside[:, 0:H2:2] & inside[:, 1:H2:2])).sum())
+    return out
+
+
+def e_model(d, hd, L, nl=1, shift=1.0):
+    return dict(model(d, hd, L), NL=nl, shift=shift)
+
+
+def e_seq(L):
+    """The uncached evaluation, FULL, PURE, MIXED with a prefix of 17 (of 0.8 L where 17 is no longer MIXED), PURE."""
+    return (None, L, 0, 17 if 17 <= 0.8 * L else int(0.8 * L), 0)
+
+
+def e_events(d, hd, L, split):
+    """The events a case of the pair at length L must show (split: the forms whose key pieces merge)."""
+    ev = ["first_pos", "first_neg", "none", "mixed_qtile"] + (["bound_mixed"] if (d, hd) in TWO_HEAD_PAIRS else [])
+    if L > 32:
+        ev += ["later", "last_tile_max"] + (["split2_merge", "split4_merge"] if split else [])
+    if L > 66:
+        ev += ["multi"]
+    return tuple(ev)
+
+
+E_LENGTHS = (17, 33, 70, 187)  # the first key tile is the ragged last one; one live key in the last tile; 3 and 6 tiles
+E_LONG_PAIRS = ((72, 6), (64, 8))  # ... and L = 512 (16 tiles; four q-tiles per wave at head_dim 6)
+E_NL2_PAIRS = ((60, 5), (24, 3), (72, 6))
+E_CONTROL_PAIRS = ((72, 8), (24, 4))  # no fused kernel: k_attention_mfma's running maximum starts at -inf
+E_CASES = []
+for _d, _hd in FUSED_PAIRS + E_CONTROL_PAIRS:
+    _forms = attn_forms_for(_d, _hd)
+    _split = tuple(f for f in _forms if f.startswith("split"))
+    for _L in E_LENGTHS:
+        E_CASES.append(case(f"E_d{_d}_hd{_hd}_L{_L}_B3", e_model(_d, _hd, _L), 3, e_seq(_L),
+                            forms=tuple(f for f in _forms if f not in _split), events=e_events(_d, _hd, _L, False)))
+        if _split:
+            E_CASES.append(case(f"E_d{_d}_hd{_hd}_L{_L}_B1", e_model(_d, _hd, _L), 1, e_seq(_L), forms=_split,
+                                events=e_events(_d, _hd, _L, True)))
+for _d, _hd in E_LONG_PAIRS:
+    E_CASES.append(case(f"E_d{_d}_hd{_hd}_L512_B3", e_model(_d, _hd, 512), 3, e_seq(512), forms=("default", "one_head"),
+                        events=e_events(_d, _hd, 512, False)))
+for _d, _hd in E_NL2_PAIRS:
+    E_CASES.append(case(f"E_d{_d}_hd{_hd}_L70_B3_NL2", e_model(_d, _hd, 70, nl=2), 3, e_seq(70),
+                        forms=tuple(f for f in attn_forms_for(_d, _hd) if not f.startswith("split")),
+                        events=e_events(_d, _hd, 70, False)))
+# the constant shifts five times as large (up to 1000 log2 units), in every form
+E_CASES.append(case("E_d72_hd6_L187_B3_shift5", e_model(72, 6, 187, shift=5.0), 3, e_seq(187),
+                    forms=("default", "one_head", "two_heads", "two_kernel"), events=e_events(72, 6, 187, False)))
+E_CASES.append(case("E_d72_hd6_L187_B1_shift5", e_model(72, 6, 187, shift=5.0), 1, e_seq(187),
+                    forms=("split2", "split4", "split2_kvq", "split4_kvq"), events=e_events(72, 6, 187, True)))
+E_QG_CASES = [c for c in E_CASES if c["model"]["L"] == 187 and c["B"] == 3 and c["model"]["shift"] == 1.0
+              and (c["model"]["d"], c["model"]["d"] // c["model"]["H"]) in FUSED_PAIRS]  # attn_qg 1 / 2 / 3 forced, one_head form
+
+ALL_CASES = dict(A=A_CASES, B=B_CASES + B_HEIGHT_CASES + B_TILE_CASES, C=C_CASES, D=D_CASES, E=E_CASES)
 
 
 # ---------------------------------------------------------------------------------------------- references
 def state_dict(m):
     sd = synthetic.transformer_state_dict(m["C"], m["L"], m["d"], m["NL"], dim_feedforward=m["F"], seed=m["wseed"])
-    return {k: torch.from_numpy(v.copy()) for k, v in sd.items()}
+    sd = {k: torch.from_numpy(v.copy()) for k, v in sd.items()}
+    return shift_state_dict(sd, m) if "shift" in m else sd
 
 
 def inputs(c, j):
     m = c["model"]
-    return torch.from_numpy(next(synthetic.noise_stream((c["B"], m["L"], m["C"]), 1, c["xseed"] + j)))
+    x = torch.from_numpy(next(synthetic.noise_stream((c["B"], m["L"], m["C"]), 1, c["xseed"] + j)))
+    return e_inputs(x) if "shift" in m else x
 
 
 @functools.lru_cache(maxsize=None)
@@ -366,11 +582,21 @@ def _reference(mkey, B, xseed, t, seq):
     out = []
     for j, n in enumerate(seq):
         x = inputs(c, j)
-        s64 = score_forward64(x, tt, sd, m["NL"], H, tab64, n)
+        events = {}  # list E: score_events64 summed over the layers, with the largest |score| in log2 units
+
+        def probe(layer, q, k):
+            for name, v in score_events64(q, k).items():
+                events[name] = events.get(name, 0) + v
+            top = float((torch.matmul(q, k.transpose(-2, -1)).abs().max()) * LOG2E / math.sqrt(hd))
+            events["max_log2"] = max(events.get("max_log2", 0.0), top)
+
+        s64 = score_forward64(x, tt, sd, m["NL"], H, tab64, n, probe=probe if "shift" in m else None)
         s32 = O.score_forward(x, tt, sd, m["NL"], H, tab32 if n is not None else None, list(range(n)) if n is not None else None)
         rec = dict(n=n, score=s64, e32=float((s32.to(torch.float64) - s64).abs().max() / s64.abs().max()))
         if L == 1:  # attention is the identity on v
             rec["score_identity"] = score_forward64(x, tt, sd, m["NL"], H, tab_id, n, softmax_one=True)
+        if events:
+            rec["events"] = events
         if n is not None:
             rec.update(k=tab64.k.clone(), v=tab64.v.clone(), recompute=tab64.recompute_count, hits=tab64.cache_hit_count)
             assert (tab32.recompute_count, tab32.cache_hit_count) == (tab64.recompute_count, tab64.cache_hit_count)
@@ -380,6 +606,6 @@ def _reference(mkey, B, xseed, t, seq):
 
 def reference(c):
     """Per evaluation of the case: dict(n, score (float64), e32, and with the cache: k, v (the judge's tables after the
-    evaluation), recompute, hits).  Computed once per (model, batch, inputs, sequence); read-only."""
+    evaluation), recompute, hits; list E: events).  Computed once per (model, batch, inputs, sequence); read-only."""
     mkey = tuple(sorted((k, v) for k, v in c["model"].items() if k != "sde_kwargs"))
     return _reference(mkey, c["B"], c["xseed"], c["t"], c["seq"])
