@@ -138,6 +138,17 @@ SIGNATURES = {
     "ffd_nn_ball_count": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
     "ffd_nn_radius": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "ffd_nn_scores": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "ffd_mmd_centre_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ffd_mmd_centre": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_mmd_bandwidth_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ffd_mmd_bandwidth": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_mmd_rowsums_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ffd_mmd_rowsums": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_mmd_scores": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "ffd_mmd_gram_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ffd_mmd_gram": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_size_t, _P]),
+    "ffd_mmd_permute_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ffd_mmd_permute": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
     "ffd_sm_draw_times":(C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_uint64, C.c_uint64, _P]),
     "ffd_sm_perturb": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_sm_loss": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -5,12 +5,10 @@
 // Both sets are CENTRED on the reference set's column mean before the Gram form d^2 = (n_i + n_j) - 2 z_i . z_j is taken:
 // uncentred, n is the squared distance from the origin and fp32 resolves it far more coarsely than the distances between
 // neighbours of a cluster away from the origin (the reason k_ens_pairs centres, ffd_ensemble.hip).
-//   k_nn_colpart + k_nn_colmean   the reference set's column mean (fp64 over fixed slabs of 1024 rows, in order)
-//   k_nn_centre    z = x - mean into rows padded to a multiple of 16 columns, n_i = |z_i|^2 (a wave per row)
-//   nn_tile        one 64 x 256 tile of z_q z_r^T on the exact-fp32 16x16x4 MFMA (the operand scheme of k_ens_pairs with
-//                  the reference rows as the A operand: a lane ends with 4 consecutive reference columns of one query
-//                  row).  An element's sum runs over the columns in one order wherever its tile lies, so d^2(i, j) has
-//                  the same bits for every tiling.
+// The column mean (k_nn_colpart + k_nn_colmean), the centring (k_nn_centre), the 64 x 256 tile of z_q z_r^T on the
+// exact-fp32 16x16x4 MFMA (nn_tile) and the one statement of d^2 (nn_d2) are defined in ffd_pairtile.h, which
+// ffd_mmd.hip shares.  An element's sum runs over the columns in one order wherever its tile lies, so d^2(i, j) has the
+// same bits for every tiling.  Defined here:
 //   k_nn_tile      writes a block of the distance matrix (query rows x a chunk of reference columns) to the workspace
 //   k_nn_merge     a wave per query row merges that chunk into the row's running list of the k smallest (d^2, index),
 //                  ordered by (value, then lower index): a strict total order, so the list is the same for every cut
@@ -22,98 +20,14 @@
 #include <algorithm>
 #include <climits>
 
-#include "ffd_internal.h"
+#include "ffd_pairtile.h"
 
 namespace ffd {
 
-constexpr int NN_SLAB = 1024;  // rows per column-sum slab (fixed: the grid does not change the mean)
-constexpr int NN_I = 64, NN_J = 256, NN_MAX_CHUNKS = 64;
+constexpr int NN_MAX_CHUNKS = 64;  // (the tile, the slab and the limits: ffd_pairtile.h)
 constexpr int NN_MAX_CBT = 32;              // column tiles of one distance chunk, at most (8192 columns)
 constexpr size_t NN_MAX_UNITS = 1u << 15;   // 64 x 256 tiles of one distance block, at most (2 GiB)
 constexpr size_t NN_UNIT_BYTES = (size_t)NN_I * NN_J * 4;
-constexpr int NN_MAX_ROWS = 1 << 24, NN_MAX_D = 1 << 16;
-
-// ---- centring ----------------------------------------------------------------------------------------------------
-// part[slab][d] = sum of x[i][d] over the slab's rows, fp64, 4 row groups combined in order
-__global__ __launch_bounds__(256) void k_nn_colpart(const float* __restrict__ X, int n, int D, double* __restrict__ part) {
-  __shared__ double red[4][64];
-  const int cl = threadIdx.x & 63, c = blockIdx.x * 64 + cl, g = threadIdx.x >> 6;
-  const int i0 = blockIdx.y * NN_SLAB, i1 = min(i0 + NN_SLAB, n);
-  double a = 0.0;
-  if (c < D)
-    for (int i = i0 + g; i < i1; i += 4) a += (double)X[(size_t)i * D + c];
-  red[g][cl] = a;
-  __syncthreads();
-  if (g == 0 && c < D) part[(size_t)blockIdx.y * D + c] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
-}
-__global__ __launch_bounds__(256) void k_nn_colmean(const double* __restrict__ part, int nslab, int n, int D,
-                                                    float* __restrict__ mean) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= D) return;
-  double a = 0.0;
-  for (int i = 0; i < nslab; ++i) a += part[(size_t)i * D + c];
-  mean[c] = (float)(a / (double)n);
-}
-
-__device__ __forceinline__ double nn_wave_sum(double v) {  // a fixed butterfly: every lane gets the same total
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// A wave per row: z[i][d] = x[i][d] - mean[d] (0 for D <= d < Dp), nrm[i] = |z_i|^2
-__global__ __launch_bounds__(256) void k_nn_centre(const float* __restrict__ X, const float* __restrict__ mean,
-                                                   float* __restrict__ Z, float* __restrict__ nrm, int n, int D, int Dp) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= n) return;
-  const float* x = X + (size_t)i * D;
-  float* z = Z + (size_t)i * Dp;
-  double nn = 0.0;
-  for (int d = lane; d < Dp; d += 64) {
-    const float zv = d < D ? x[d] - mean[d] : 0.f;
-    z[d] = zv;
-    nn += (double)zv * (double)zv;
-  }
-  nn = nn_wave_sum(nn);
-  if (lane == 0) nrm[i] = (float)nn;
-}
-
-// ---- pair tiles --------------------------------------------------------------------------------------------------
-// acc[a][b] of lane (q = lane >> 4, c = lane & 15), register r: z_q(i0 + 16 a + c) . z_r(j0 + 16 b + 4 q + r).  The
-// reference rows are the A operand and the query rows the B operand; lane group q holds k = 16 g + 4 q + {0..3} of both,
-// MFMA step e pairs the e-th of both.  Rows past the sets are clamped for the loads; the callers never use them.
-__device__ __forceinline__ void nn_tile(const float* __restrict__ Zq, int nq, int i0, const float* __restrict__ Zr, int nr,
-                                        int j0, int Dp, int q, int c, f32x4 (&acc)[4][4]) {
-  const float* ar[4];
-  const float* br[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    ar[t] = Zq + (size_t)min(i0 + 16 * t + c, nq - 1) * Dp + 4 * q;
-    br[t] = Zr + (size_t)min(j0 + 16 * t + c, nr - 1) * Dp + 4 * q;
-  }
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kb = 0; kb < Dp; kb += 16) {
-    f32x4 av[4], bv[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      av[t] = *(const f32x4*)(ar[t] + kb);
-      bv[t] = *(const f32x4*)(br[t] + kb);
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = mfma16(bv[b][e], av[a][e], acc[a][b]);
-  }
-}
-
-// the one statement of the Gram form: both epilogues see the same bits
-__device__ __forceinline__ float nn_d2(float ni, float nj, float g) { return fmaxf(__fmaf_rn(-2.f, g, ni + nj), 0.f); }
 
 // Workgroup blockIdx.x = bt * nct + ct: query rows [ib0 + 64 bt, + 64) against reference columns [jc0 + 256 ct, + 256);
 // wave w owns 64 of the columns.  T: (block rows, cb) floats, row = query row - ib0, column = reference column - jc0.
@@ -362,7 +276,6 @@ __global__ __launch_bounds__(256) void k_nn_scores(const double* __restrict__ se
 }
 
 // ---- host: workspace, plan ---------------------------------------------------------------------------------------
-static size_t nn_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static size_t nn_pow2_floor(size_t v) {
   size_t p = 1;
   while (p * 2 <= v) p *= 2;
@@ -418,11 +331,6 @@ static size_t nn_search_bytes(int nq, int nr, int D, int k, size_t budget) {
 }
 static size_t nn_ball_bytes(int nq, int nr, int D) { return nn_plan(nq, nr, D, 0).fixed; }
 
-static bool nn_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // the reference mean, then both centred copies (one where the query set is the reference set)
 static hipError_t nn_centre(const float* query, int nq, const float* ref, int nr, int D, const NNPlan& p, char* work,
                             const float** zq_out, const float** nrm_q_out, hipStream_t s) {
@@ -431,7 +339,7 @@ static hipError_t nn_centre(const float* query, int nq, const float* ref, int nr
   float* mean = (float*)(work + p.mean);
   double* colpart = (double*)(work + p.colpart);
   hipLaunchKernelGGL(k_nn_colpart, dim3(cdiv(D, 64), p.nslab), dim3(256), 0, s, ref, nr, D, colpart);
-  hipLaunchKernelGGL(k_nn_colmean, dim3(cdiv(D, 256)), dim3(256), 0, s, colpart, p.nslab, nr, D, mean);
+  hipLaunchKernelGGL(k_nn_colmean<float>, dim3(cdiv(D, 256)), dim3(256), 0, s, colpart, p.nslab, nr, D, mean);
   hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(nr, 4)), dim3(256), 0, s, ref, mean, Zr, nrm_r, nr, D, p.Dp);
   *zq_out = Zr;
   *nrm_q_out = nrm_r;

@@ -1,0 +1,146 @@
+// The pair tile shared by the nearest-neighbour statistics (ffd_neighbours.hip) and the kernel two-sample statistics
+// (ffd_mmd.hip): a set's column mean, rows centred on a mean, one 64 x 256 tile of the centred Gram matrix on the
+// exact-fp32 16x16x4 MFMA, and the one statement of d^2 from it.  Both translation units see the same bits.
+//   k_nn_colpart + k_nn_colmean   a set's column mean (fp64 over fixed slabs of 1024 rows, in order)
+//   k_nn_centre    z = x - mean into rows padded to a multiple of 16 columns, n_i = |z_i|^2 (a wave per row)
+//   nn_tile        one 64 x 256 tile of z_q z_r^T (the operand scheme of k_ens_pairs with the reference rows as the A
+//                  operand: a lane ends with 4 consecutive reference columns of one query row).  An element's sum runs
+//                  over the columns in one order wherever its tile lies, so d^2(i, j) has the same bits for every tiling.
+//   nn_d2          d^2 = (n_i + n_j) - 2 z_i . z_j, clamped at 0
+// The kernels are static: each translation unit that launches one carries its own copy (the library is built without
+// relocatable device code).
+#pragma once
+#include "ffd_internal.h"
+
+namespace ffd {
+
+constexpr int NN_SLAB = 1024;  // rows per column-sum slab (fixed: the grid does not change the mean)
+constexpr int NN_I = 64, NN_J = 256;
+constexpr int NN_MAX_ROWS = 1 << 24, NN_MAX_D = 1 << 16;
+
+// ---- centring ----------------------------------------------------------------------------------------------------
+// part[slab][d] = sum of x[i][d] over the slab's rows, fp64, 4 row groups combined in order
+static __global__ __launch_bounds__(256) void k_nn_colpart(const float* __restrict__ X, int n, int D,
+                                                           double* __restrict__ part) {
+  __shared__ double red[4][64];
+  const int cl = threadIdx.x & 63, c = blockIdx.x * 64 + cl, g = threadIdx.x >> 6;
+  const int i0 = blockIdx.y * NN_SLAB, i1 = min(i0 + NN_SLAB, n);
+  double a = 0.0;
+  if (c < D)
+    for (int i = i0 + g; i < i1; i += 4) a += (double)X[(size_t)i * D + c];
+  red[g][cl] = a;
+  __syncthreads();
+  if (g == 0 && c < D) part[(size_t)blockIdx.y * D + c] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+}
+// T = float: the mean the rows are centred on; T = double: the same sum and quotient, not rounded
+template <typename T>
+static __global__ __launch_bounds__(256) void k_nn_colmean(const double* __restrict__ part, int nslab, int n, int D,
+                                                           T* __restrict__ mean) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= D) return;
+  double a = 0.0;
+  for (int i = 0; i < nslab; ++i) a += part[(size_t)i * D + c];
+  mean[c] = (T)(a / (double)n);
+}
+
+__device__ __forceinline__ double nn_wave_sum(double v) {  // a fixed butterfly: every lane gets the same total
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// A wave per row: z[i][d] = x[i][d] - mean[d] (0 for D <= d < Dp), nrm[i] = |z_i|^2
+static __global__ __launch_bounds__(256) void k_nn_centre(const float* __restrict__ X, const float* __restrict__ mean,
+                                                          float* __restrict__ Z, float* __restrict__ nrm, int n, int D,
+                                                          int Dp) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const float* x = X + (size_t)i * D;
+  float* z = Z + (size_t)i * Dp;
+  double nn = 0.0;
+  for (int d = lane; d < Dp; d += 64) {
+    const float zv = d < D ? x[d] - mean[d] : 0.f;
+    z[d] = zv;
+    nn += (double)zv * (double)zv;
+  }
+  nn = nn_wave_sum(nn);
+  if (lane == 0) nrm[i] = (float)nn;
+}
+
+// ---- pair tiles --------------------------------------------------------------------------------------------------
+// acc[a][b] of lane (q = lane >> 4, c = lane & 15), register r: z_q(i0 + 16 a + c) . z_r(j0 + 16 b + 4 q + r).  The
+// reference rows are the A operand and the query rows the B operand; lane group q holds k = 16 g + 4 q + {0..3} of both,
+// MFMA step e pairs the e-th of both.  Rows past the sets are clamped for the loads; the callers never use them.
+// spill (nullptr: none): 64 x 256 floats of LDS, cell [slot][threadIdx.x] a lane's own.  With it the sum over k is taken
+// in chunks of NN_K_CHUNK: each finished chunk's 64 partial sums are added to the lane's cells and the accumulators start
+// again, so an element is ((c_1 + c_2) + ...) + the last chunk, the same wherever its tile lies, instead of one fp32 chain
+// over up to 65 536 terms.  Rows of at most NN_K_CHUNK padded columns never reach a flush: the same bits as without.
+constexpr int NN_K_CHUNK = 1024;
+constexpr size_t NN_SPILL_BYTES = 64 * 256 * sizeof(float);
+__device__ __forceinline__ void nn_tile(const float* __restrict__ Zq, int nq, int i0, const float* __restrict__ Zr, int nr,
+                                        int j0, int Dp, int q, int c, f32x4 (&acc)[4][4], float* spill = nullptr) {
+  const float* ar[4];
+  const float* br[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    ar[t] = Zq + (size_t)min(i0 + 16 * t + c, nq - 1) * Dp + 4 * q;
+    br[t] = Zr + (size_t)min(j0 + 16 * t + c, nr - 1) * Dp + 4 * q;
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // (the flush sits between two inner loops, not inside one: a branch in the k loop cost a quarter of the tile's rate)
+  const int chunk = spill ? NN_K_CHUNK : Dp;
+  for (int k0 = 0; k0 < Dp; k0 += chunk) {
+    const int k1 = min(k0 + chunk, Dp);
+    for (int kb = k0; kb < k1; kb += 16) {
+      f32x4 av[4], bv[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        av[t] = *(const f32x4*)(ar[t] + kb);
+        bv[t] = *(const f32x4*)(br[t] + kb);
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) acc[a][b] = mfma16(bv[b][e], av[a][e], acc[a][b]);
+    }
+    if (spill && k1 < Dp) {  // (wave-uniform) a chunk ends and more follow
+      const bool first = k0 == 0;
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float* cell = spill + ((a * 4 + b) * 4 + r) * 256 + threadIdx.x;
+            *cell = first ? acc[a][b][r] : *cell + acc[a][b][r];
+            acc[a][b][r] = 0.f;
+          }
+    }
+  }
+  if (spill && Dp > NN_K_CHUNK) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[a][b][r] = spill[((a * 4 + b) * 4 + r) * 256 + threadIdx.x] + acc[a][b][r];
+  }
+}
+
+// the one statement of the Gram form: every epilogue sees the same bits
+__device__ __forceinline__ float nn_d2(float ni, float nj, float g) { return fmaxf(__fmaf_rn(-2.f, g, ni + nj), 0.f); }
+
+// ---- host --------------------------------------------------------------------------------------------------------
+static inline size_t nn_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline bool nn_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+}  // namespace ffd

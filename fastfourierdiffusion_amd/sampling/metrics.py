@@ -11,7 +11,7 @@ from __future__ import annotations
 from abc import ABC, abstractmethod
 from functools import partial
 
-from ..utils import neighbours
+from ..utils import kernel_mmd, neighbours
 from ..utils.fourier import dft, spectral_density
 from ..utils.tensors import check_flat_array
 from ..utils.wasserstein import WassersteinDistances, _column_mean, _summary, _to_device
@@ -208,3 +208,94 @@ class ManifoldMetrics(Metric):
     @property
     def name(self) -> str:
         return "manifold"
+
+
+class KernelMMD(Metric):
+    """Kernel two-sample statistics of a sample set X against the originals Y (``utils.kernel_mmd``; not in the reference):
+    the maximum mean discrepancy with Gaussian kernels exp(-gamma |a - b|^2) (Gretton et al. 2012), per-sample witness
+    values and, on request, a permutation test.  The bandwidths are the ladder gamma_s = 1 / (2 sigma^2 s) over ``scales``
+    around sigma^2, the originals' mean squared distance between two distinct rows; the headline numbers use the mean
+    kernel over the ladder.
+
+    ``mmd2`` the unbiased estimate (expectation 0 when X and Y share a distribution, so it may be negative);
+    ``mmd2_biased`` the biased one (>= 0); ``mmd2_s{scale}`` the unbiased estimate at one bandwidth; ``witness_max`` and
+    ``witness_share_positive`` over the per-sample values w_i = mean_x' k(x_i, x') - mean_y k(x_i, y), large where the
+    samples lie and the originals do not; with ``permutations`` > 0, ``p_value`` = (1 + #{p : T_p >= T_0}) / (P + 1) over
+    P relabelings of the pooled rows drawn on the host from ``random_seed``.
+
+    The originals' centre, sigma^2 and self row sums are computed once and kept, as ``ManifoldMetrics`` keeps its
+    self-search.  There is no ``_dummy`` baseline.  A permutation test takes at most ``kernel_mmd.MAX_POOLED`` rows of both
+    sets together; larger sets are refused, never subsampled silently."""
+
+    def __init__(self, original_samples, scales=kernel_mmd.DEFAULT_SCALES, permutations: int = 0,
+                 random_seed: int = 0) -> None:
+        super().__init__(original_samples=original_samples)
+        self.scales = tuple(float(s) for s in scales)
+        assert 1 <= len(self.scales) <= kernel_mmd.MAX_GAMMAS, \
+            f"between 1 and {kernel_mmd.MAX_GAMMAS} scales, got {len(self.scales)}"
+        assert all(s > 0 for s in self.scales), f"scales must be positive, got {self.scales}"
+        self.permutations = int(permutations)
+        assert 0 <= self.permutations < kernel_mmd.MAX_PERMUTATIONS, \
+            f"permutations must lie in [0, {kernel_mmd.MAX_PERMUTATIONS - 1}], got {permutations}"
+        self.random_seed = int(random_seed)
+        assert self.original_samples.shape[0] >= 2, "KernelMMD needs at least 2 original samples"
+        self._cache = None
+        self._baseline = None
+
+    def _prepared_originals(self):
+        """(centre, gammas, YY row sums) of the originals, computed once."""
+        if self._cache is None:
+            y = self._original()
+            centre = kernel_mmd.column_mean(y)
+            gammas = kernel_mmd.ladder_gammas(float(kernel_mmd.bandwidth(y).item()), self.scales)
+            self._cache = (centre, gammas, kernel_mmd.row_sums(y, y, centre, gammas, exclude_self=True))
+        return self._cache
+
+    def _check_pooled(self, n: int, m: int) -> None:
+        if self.permutations > 0 and n + m > kernel_mmd.MAX_POOLED:
+            raise ValueError(f"a permutation test takes at most {kernel_mmd.MAX_POOLED} rows of both sets together, got "
+                             f"{n} samples + {m} originals; pass subsamples or permutations=0")
+
+    def _evaluate(self, x, y, centre, gammas, rowsum_yy, with_test: bool = True):
+        n, m = x.shape[0], y.shape[0]
+        assert n >= 2 and m >= 2, f"both sets need at least 2 rows, got {n} and {m}"
+        self._check_pooled(n, m)
+        rowsum_xx = kernel_mmd.row_sums(x, x, centre, gammas, exclude_self=True)
+        rowsum_xy = kernel_mmd.row_sums(x, y, centre, gammas)
+        mmd2, witness = kernel_mmd.mmd_scores(rowsum_xx, rowsum_xy, rowsum_yy)
+        unbiased, biased = mmd2.tolist()
+        found = {"mmd2": unbiased[-1], "mmd2_biased": biased[-1]}
+        for scale, value in zip(self.scales, unbiased):
+            found[f"mmd2_s{scale:g}"] = value
+        found["witness_max"] = float(witness.max())  # two reductions where the values live: n doubles stay there
+        found["witness_share_positive"] = float((witness > 0).sum()) / n
+        if with_test and self.permutations > 0:
+            assign = kernel_mmd.permutation_assignments(n, m, self.permutations, self.random_seed)
+            found["p_value"] = kernel_mmd.p_value(kernel_mmd.permutation_test(x, y, centre, gammas, assign))
+        return found, witness
+
+    def __call__(self, other_samples) -> dict:
+        centre, gammas, rowsum_yy = self._prepared_originals()
+        return self._evaluate(_to_device(check_flat_array(other_samples)), self._original(), centre, gammas, rowsum_yy)[0]
+
+    def witness(self, other_samples):
+        """The per-sample witness values of the mean kernel, a float64 (n,) device tensor."""
+        centre, gammas, rowsum_yy = self._prepared_originals()
+        return self._evaluate(_to_device(check_flat_array(other_samples)), self._original(), centre, gammas, rowsum_yy,
+                              with_test=False)[1]
+
+    @property
+    def baseline_metrics(self) -> dict:
+        if self._baseline is None:  # a function of the originals alone: computed once, as their row sums are
+            y = self._original()
+            fold_a, fold_b = y[: y.shape[0] // 2], y[y.shape[0] // 2:]  # the cut of ManifoldMetrics.baseline_metrics
+            centre, gammas, _ = self._prepared_originals()  # the whole set's centre and bandwidths: comparable with __call__
+            fold_a = fold_a.contiguous()
+            found, _ = self._evaluate(fold_b.contiguous(), fold_a, centre, gammas,
+                                      kernel_mmd.row_sums(fold_a, fold_a, centre, gammas, exclude_self=True))
+            self._baseline = {f"{key}_self": value for key, value in found.items()}
+        return dict(self._baseline)
+
+    @property
+    def name(self) -> str:
+        return "kernel_mmd"

@@ -771,6 +771,65 @@ int ffd_nn_radius(const double* dist2, int n, int k, int col, float* radius2_out
 int ffd_nn_scores(const double* self_dist2, const double* xy_dist2, const int32_t* xy_index, const double* yx_dist2,
                   const int32_t* count_x, const int32_t* count_y, int n, int m, int k, double* out8, void* stream);
 
+/* ---- kernel two-sample statistics: Gaussian-kernel row sums, MMD^2, witness values, a bandwidth and a permutation test
+ * (csrc/ffd_mmd.hip; Gretton et al. 2012) ----
+ * k_gamma(a, b) = exp(-gamma |a - b|^2); `gammas`: a HOST array of n_gamma doubles, 1 <= n_gamma <= FFD_MMD_MAX_GAMMAS,
+ * each finite and >= 0.  Row sets are flat fp32 rows on the device, dense row-major, read only.  Both sets of a call
+ * are centred on ONE caller-supplied vector `centre` (D floats on the device; ffd_mmd_centre computes a set's column
+ * mean with the nearest-neighbour kernels' fixed-order fp64 mean) and d2 comes from the same Gram statement as ffd_nn_*:
+ * exact-fp32 MFMA in 64 x 256 tiles, (n_i + n_j) - 2 z_i . z_j clamped at 0.  Kernel values are fp32 (one hardware
+ * exponential per gamma and pair; a doubling ladder is not special-cased) and are added in fp64.
+ *   row sums    rowsum_out[g][i] = sum_j k_gamma_g(a_i, b_j) over all rows of b, (n_gamma, na) doubles.  exclude_self != 0
+ *               skips the pair i == j (never computed and subtracted); legal only when a and b are the same buffer and
+ *               na == nb.  A workgroup owns 64 query rows and walks a run of 4 column tiles (1024 columns; a constant of
+ *               the source) in order; the runs' partial sums are folded in run order.  So a row's sum depends on the
+ *               row, the column set, the centre and the gammas alone: bit-identical from run to run, for a query set
+ *               summed whole or in parts, whatever rows surround it, and for n_gamma gammas at once or one at a time.
+ *               gamma = 0 gives exactly the column count.  No distance block goes through memory.
+ *               For D > 1024 the tile's sum over the coordinates is taken in chunks of 1024 (partial sums kept in LDS and
+ *               added in order): a single fp32 chain over 65 536 terms would miss the accuracy below on kernel values.
+ *   bandwidth   sigma2_out[0] = 2 (n / (n - 1)) mean_j |y_j - ybar|^2, the mean squared distance between two distinct rows,
+ *               from the fp64 column mean and fp64 squared deviations in a fixed order; no pair is formed.  n >= 2.
+ *   scores      from the three row-sum arrays XX (n_gamma, n; self excluded), XY (n_gamma, n) and YY (n_gamma, m; self
+ *               excluded) of n samples X and m originals Y: mmd2_out (2, n_gamma + 1) doubles, row 0 the unbiased
+ *               sum xx / (n (n - 1)) + sum yy / (m (m - 1)) - 2 sum xy / (n m), row 1 the biased one (exactly 1 per row
+ *               added for the diagonal, divided by n^2 and m^2); column g that gamma, column n_gamma the mean kernel over
+ *               the gammas.  witness_out[i] = xx[i] / (n - 1) - xy[i] / m for the mean kernel, n doubles.  n, m >= 2.
+ *               The sums run in ONE workgroup (a fixed-order tree), so the call streams 8 n_gamma (2 n + m) bytes
+ *               through one compute unit: sized for evaluation sets (4.3 MB at 10 000 x 87 554 rows and 5 gammas);
+ *               at the row limit with 8 gammas it is 3 GB and takes accordingly.
+ *   gram        the pooled mean-kernel matrix K of the N = n + m rows (x first), N rows of 64 ceil(N / 64) floats, diagonal
+ *               0, at the start of `work`.
+ *   permute     T_p = a^T K a / (n (n - 1)) + b^T K b / (m (m - 1)) - 2 a^T K b / (n m) for P assignments: `assign` (P, N)
+ *               uint8 on the device with exactly n nonzero entries per row (the caller's to guarantee), b = 1 - a;
+ *               `gram_work` is the workspace ffd_mmd_gram filled.  K A^T runs on the fp64 matrix instruction, where K's
+ *               fp32 entries and the assignments are exact; t_out (P) doubles, fixed-order sums.  The assignment
+ *               (1, ..., 1, 0, ..., 0) gives the unbiased MMD^2 of the mean kernel.
+ * Context-free, stream ordered, no host synchronisation, no atomics.  NaN input: unspecified.
+ * `work`: device scratch, 16-byte aligned, of at least the bytes the matching size query returns; 0 for arguments the
+ * call refuses.
+ * FFD_ERR_INVALID before any device work, outputs untouched: a null pointer, a count < 1 (n, m < 2 for bandwidth, scores,
+ * gram and permute), n_gamma outside [1, 8], a gamma that is negative, not finite or too large for fp32, exclude_self
+ * with a != b or na != nb, a workspace that is too small or not 16-byte aligned, an output or the workspace overlapping
+ * an input or another output;
+ * FFD_ERR_UNSUPPORTED: rows > 2^24, D > 2^16, n + m > FFD_MMD_MAX_POOLED, P > FFD_MMD_MAX_PERMUTATIONS. */
+enum { FFD_MMD_MAX_GAMMAS = 8, FFD_MMD_MAX_POOLED = 16384, FFD_MMD_MAX_PERMUTATIONS = 4096 };
+size_t ffd_mmd_centre_work_bytes(int n, int D);
+int ffd_mmd_centre(const float* x, int n, int D, float* centre_out, void* work, size_t work_bytes, void* stream);
+size_t ffd_mmd_bandwidth_work_bytes(int n, int D);
+int ffd_mmd_bandwidth(const float* y, int n, int D, double* sigma2_out, void* work, size_t work_bytes, void* stream);
+size_t ffd_mmd_rowsums_work_bytes(int na, int nb, int D, int n_gamma);
+int ffd_mmd_rowsums(const float* a, int na, const float* b, int nb, int D, const float* centre, const double* gammas,
+                    int n_gamma, int exclude_self, double* rowsum_out, void* work, size_t work_bytes, void* stream);
+int ffd_mmd_scores(const double* rowsum_xx, const double* rowsum_xy, const double* rowsum_yy, int n, int m, int n_gamma,
+                   double* mmd2_out, double* witness_out, void* stream);
+size_t ffd_mmd_gram_work_bytes(int n, int m, int D);
+int ffd_mmd_gram(const float* x, int n, const float* y, int m, int D, const float* centre, const double* gammas, int n_gamma,
+                 void* work, size_t work_bytes, void* stream);
+size_t ffd_mmd_permute_work_bytes(int n, int m, int P);
+int ffd_mmd_permute(const void* gram_work, int n, int m, const uint8_t* assign, int P, double* t_out, void* work,
+                    size_t work_bytes, void* stream);
+
 /* ---- denoising score-matching loss: the `val/loss` of ScoreModule.validation_step (src/fdiff/utils/losses.py) ----
  * Per sample b, with std[b,l] = sigma[b] * G[l] and n = L * C (losses.py:68-80, sde.py:106-123,187-210):
  *   x_noisy = mean_coeff[b] * x0 + std[b,l] * z                  r = score + z / std[b,l]
