@@ -149,6 +149,11 @@ SIGNATURES = {
     "ffd_mmd_gram": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_size_t, _P]),
     "ffd_mmd_permute_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "ffd_mmd_permute": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_dtw_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]),
+    "ffd_dtw_search": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t,
+                                 _P]),
+    "ffd_dtw_pairs": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "ffd_dtw_scores": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "ffd_sm_draw_times":(C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_uint64, C.c_uint64, _P]),
     "ffd_sm_perturb": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
     "ffd_sm_loss": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),

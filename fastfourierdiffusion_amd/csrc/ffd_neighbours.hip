@@ -8,10 +8,10 @@
 // The column mean (k_nn_colpart + k_nn_colmean), the centring (k_nn_centre), the 64 x 256 tile of z_q z_r^T on the
 // exact-fp32 16x16x4 MFMA (nn_tile) and the one statement of d^2 (nn_d2) are defined in ffd_pairtile.h, which
 // ffd_mmd.hip shares.  An element's sum runs over the columns in one order wherever its tile lies, so d^2(i, j) has the
-// same bits for every tiling.  Defined here:
+// same bits for every tiling.  The merge of a distance block into each row's running list of the k smallest (k_nn_merge,
+// a wave per query row, ordered by (value, then lower index): a strict total order, so the list is the same for every
+// cut) is stated in ffd_pairtile.h as well; ffd_dtw.hip uses it too.  Defined here:
 //   k_nn_tile      writes a block of the distance matrix (query rows x a chunk of reference columns) to the workspace
-//   k_nn_merge     a wave per query row merges that chunk into the row's running list of the k smallest (d^2, index),
-//                  ordered by (value, then lower index): a strict total order, so the list is the same for every cut
 //   k_nn_refine    recomputes the k kept pairs in difference form in fp64 on the caller's rows and sorts them again
 //   k_nn_ball      the same tiles with a counting epilogue: integer partial counts per (row, column chunk)
 //   k_nn_count_sum folds the partial counts in chunk order
@@ -58,63 +58,6 @@ __global__ __launch_bounds__(256) void k_nn_tile(const float* __restrict__ Zq, c
       for (int r = 0; r < 4; ++r) o[r] = nn_d2(ni, nj[b][r], acc[a][b][r]);
       *(f32x4*)(trow + 16 * b) = o;
     }
-  }
-}
-
-// (value, index) order: a strict total order over the pairs of a row
-__device__ __forceinline__ bool nn_before(float v, int j, float w, int i) { return v < w || (v == w && j < i); }
-
-// A wave per query row of the block: lane l < k holds entry l of the row's list, ascending.  The chunk's row is read 256
-// columns at a time; a column that beats the list's last entry is inserted by a shift of the lanes behind its place.
-__global__ __launch_bounds__(256) void k_nn_merge(const float* __restrict__ T, int cb, int rows, int ib0, int jc0, int ncols,
-                                                  int exclude_self, int k, int first, float* __restrict__ cand_d,
-                                                  int* __restrict__ cand_i) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int i = ib0 + row;
-  const float* trow = T + (size_t)row * cb;
-  float lv = __builtin_inff();
-  int li = INT_MAX;
-  if (!first && lane < k) {
-    lv = cand_d[(size_t)i * k + lane];
-    li = cand_i[(size_t)i * k + lane];
-  }
-  float wv = __shfl(lv, k - 1, 64);
-  int wi = __shfl(li, k - 1, 64);
-  for (int jb = 0; jb < ncols; jb += 256) {  // jb + 256 <= cb: the loads stay inside the row, the mask is `ok`
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = trow[jb + 64 * u + lane];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int jl = jb + 64 * u + lane, j = jc0 + jl;
-      const bool ok = jl < ncols && !(exclude_self && j == i);
-      unsigned long long m = __ballot(ok && nn_before(v[u], j, wv, wi));
-      while (m) {  // (wave-uniform)
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const float cv = __shfl(v[u], src, 64);
-        const int cj = jc0 + jb + 64 * u + src;
-        if (!nn_before(cv, cj, wv, wi)) continue;
-        const int p = __popcll(__ballot(nn_before(lv, li, cv, cj)));  // the entries before the new one: a prefix, p < k
-        const float uv = __shfl_up(lv, 1, 64);
-        const int ui = __shfl_up(li, 1, 64);
-        if (lane == p) {
-          lv = cv;
-          li = cj;
-        } else if (lane > p) {
-          lv = uv;
-          li = ui;
-        }
-        wv = __shfl(lv, k - 1, 64);
-        wi = __shfl(li, k - 1, 64);
-      }
-    }
-  }
-  if (lane < k) {
-    cand_d[(size_t)i * k + lane] = lv;
-    cand_i[(size_t)i * k + lane] = li;
   }
 }
 

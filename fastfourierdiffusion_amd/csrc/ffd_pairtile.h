@@ -7,9 +7,13 @@
 //                  operand: a lane ends with 4 consecutive reference columns of one query row).  An element's sum runs
 //                  over the columns in one order wherever its tile lies, so d^2(i, j) has the same bits for every tiling.
 //   nn_d2          d^2 = (n_i + n_j) - 2 z_i . z_j, clamped at 0
+//   k_nn_merge     a block of pair values (rows x a chunk of columns) merged into each row's list of the k smallest,
+//                  ordered by nn_before: (value, then lower index); also used by ffd_dtw.hip
 // The kernels are static: each translation unit that launches one carries its own copy (the library is built without
 // relocatable device code).
 #pragma once
+#include <climits>
+
 #include "ffd_internal.h"
 
 namespace ffd {
@@ -135,6 +139,64 @@ __device__ __forceinline__ void nn_tile(const float* __restrict__ Zq, int nq, in
 
 // the one statement of the Gram form: every epilogue sees the same bits
 __device__ __forceinline__ float nn_d2(float ni, float nj, float g) { return fmaxf(__fmaf_rn(-2.f, g, ni + nj), 0.f); }
+
+// ---- the k smallest of a row ------------------------------------------------------------------------------------
+// (value, index) order: a strict total order over the pairs of a row
+__device__ __forceinline__ bool nn_before(float v, int j, float w, int i) { return v < w || (v == w && j < i); }
+
+// A wave per query row of the block: lane l < k holds entry l of the row's list, ascending.  The chunk's row is read 256
+// columns at a time; a column that beats the list's last entry is inserted by a shift of the lanes behind its place.
+static __global__ __launch_bounds__(256) void k_nn_merge(const float* __restrict__ T, int cb, int rows, int ib0, int jc0, int ncols,
+                                                         int exclude_self, int k, int first,
+                                                         float* __restrict__ cand_d, int* __restrict__ cand_i) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int i = ib0 + row;
+  const float* trow = T + (size_t)row * cb;
+  float lv = __builtin_inff();
+  int li = INT_MAX;
+  if (!first && lane < k) {
+    lv = cand_d[(size_t)i * k + lane];
+    li = cand_i[(size_t)i * k + lane];
+  }
+  float wv = __shfl(lv, k - 1, 64);
+  int wi = __shfl(li, k - 1, 64);
+  for (int jb = 0; jb < ncols; jb += 256) {  // jb + 256 <= cb: the loads stay inside the row, the mask is `ok`
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = trow[jb + 64 * u + lane];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int jl = jb + 64 * u + lane, j = jc0 + jl;
+      const bool ok = jl < ncols && !(exclude_self && j == i);
+      unsigned long long m = __ballot(ok && nn_before(v[u], j, wv, wi));
+      while (m) {  // (wave-uniform)
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const float cv = __shfl(v[u], src, 64);
+        const int cj = jc0 + jb + 64 * u + src;
+        if (!nn_before(cv, cj, wv, wi)) continue;
+        const int p = __popcll(__ballot(nn_before(lv, li, cv, cj)));  // the entries before the new one: a prefix, p < k
+        const float uv = __shfl_up(lv, 1, 64);
+        const int ui = __shfl_up(li, 1, 64);
+        if (lane == p) {
+          lv = cv;
+          li = cj;
+        } else if (lane > p) {
+          lv = uv;
+          li = ui;
+        }
+        wv = __shfl(lv, k - 1, 64);
+        wi = __shfl(li, k - 1, 64);
+      }
+    }
+  }
+  if (lane < k) {
+    cand_d[(size_t)i * k + lane] = lv;
+    cand_i[(size_t)i * k + lane] = li;
+  }
+}
 
 // ---- host --------------------------------------------------------------------------------------------------------
 static inline size_t nn_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

@@ -11,13 +11,16 @@ from __future__ import annotations
 from abc import ABC, abstractmethod
 from functools import partial
 
-from ..utils import kernel_mmd, neighbours
+from ..utils import dtw, kernel_mmd, neighbours
 from ..utils.fourier import dft, spectral_density
 from ..utils.tensors import check_flat_array
 from ..utils.wasserstein import WassersteinDistances, _column_mean, _summary, _to_device
 
 
 class Metric(ABC):
+    # the views of the samples a ``MetricCollection`` builds and calls this metric on
+    views = ("time", "freq")
+
     def __init__(self, original_samples) -> None:
         self.original_samples = check_flat_array(original_samples)
         self._device_set = None
@@ -61,7 +64,8 @@ def _stats(wd: WassersteinDistances, distances, prefix: str, suffix: str = "", s
 
 class MetricCollection:
     """metrics.py:28-97: every metric once on the time series and once on their ``dft``, optionally the marginal
-    metric on the spectral densities; results under ``time_`` / ``freq_`` / ``spectral_`` prefixes, sorted by key."""
+    metric on the spectral densities; results under ``time_`` / ``freq_`` / ``spectral_`` prefixes, sorted by key.
+    A metric class that names fewer ``views`` (``DTWMetrics``: time only) is built and called on those alone."""
 
     def __init__(self, metrics: list, original_samples=None, include_baselines: bool = True,
                  include_spectral_density: bool = False) -> None:
@@ -70,8 +74,11 @@ class MetricCollection:
         assert not todo or original_samples is not None, \
             f"Original samples must be provided for metric {todo[0] if todo else None} to be instantiated."
         in_freq = None if original_samples is None else dft(original_samples)
-        self.metrics_time = [build(original_samples=original_samples) for build in todo]
-        self.metrics_freq = [build(original_samples=in_freq) for build in todo]
+        takes = [getattr(build.func, "views", Metric.views) for build in todo]
+        self.metrics_time = [build(original_samples=original_samples) if "time" in views else None
+                             for build, views in zip(todo, takes)]
+        self.metrics_freq = [build(original_samples=in_freq) if "freq" in views else None
+                             for build, views in zip(todo, takes)]
         self.include_baselines = include_baselines
         self.metric_spectral = None
         if include_spectral_density:
@@ -79,10 +86,13 @@ class MetricCollection:
                                                        random_seed=42, save_all_distances=True)
 
     def _pairs(self):
-        """(prefix, metric) in the reference's update order: time then freq, metric by metric."""
+        """(prefix, metric) in the reference's update order: time then freq, metric by metric; a metric is absent
+        (None) from a view it does not take (``Metric.views``)."""
         for in_time, in_freq in zip(self.metrics_time, self.metrics_freq):
-            yield "time", in_time
-            yield "freq", in_freq
+            if in_time is not None:
+                yield "time", in_time
+            if in_freq is not None:
+                yield "freq", in_freq
 
     def __call__(self, other_samples) -> dict:
         views = {"time": other_samples, "freq": dft(other_samples)}
@@ -299,3 +309,62 @@ class KernelMMD(Metric):
     @property
     def name(self) -> str:
         return "kernel_mmd"
+
+
+class DTWMetrics(Metric):
+    """Dynamic-time-warping statistics of a sample set X against the originals Y (``utils.dtw``; not in the reference): what
+    the flat-vector metrics cannot tell apart, a sample of the wrong shape from one that is only mis-timed.  ``dtw2`` is
+    the squared banded DTW cost at the Sakoe-Chiba half-width ``window`` (an int in samples, or a float share of the
+    length); d(a, S) below is the square root of the smallest ``dtw2`` from a to a row of S (a itself excluded inside its
+    own set).
+
+    ``dtw_nn_distance_mean`` mean over x of d(x, Y); ``dtw_coverage_distance_mean`` mean over y of d(y, X);
+    ``dtw_warp_gain`` 1 - mean over the x with Euclidean nearest-original distance > 0 of d(x, Y) over that Euclidean
+    distance: the share of the nearest-original distance that re-timing removes, in [0, 1], 0 at window 0 and 0.0 when no
+    x qualifies; ``dtw_1nn_accuracy_samples`` share of x with d(x, X) < d(x, Y) and ``dtw_1nn_accuracy_originals`` share
+    of y with d(y, Y) < d(y, X) (strict: a tie counts as the other class); ``dtw_1nn_accuracy`` their mean, the
+    leave-one-out 1-NN two-sample accuracy (Lopez-Paz & Oquab 2017) balanced over the classes: 0.5 means "cannot be told
+    apart".
+
+    The originals must be (n, L, C); samples may be (m, L, C) or (m, L C).  The originals' self-search is done once and
+    kept, as ``ManifoldMetrics`` keeps its own.  The originals are used as given and never subsampled silently: a call
+    computes every pair of five searches, (n + m)^2 L (2 w + 1) cells, and the kept self-search n^2 of them.  Over the
+    packed spectrum DTW means nothing, so a ``MetricCollection`` builds this metric on the time view only.  There is no
+    ``_dummy`` baseline."""
+
+    views = ("time",)
+
+    def __init__(self, original_samples, window=0.1) -> None:
+        shape = tuple(original_samples.shape)
+        assert len(shape) == 3, f"DTWMetrics needs the originals as (n, L, C), got {shape}"
+        super().__init__(original_samples=original_samples)
+        self.length, self.channels = shape[1], shape[2]
+        assert shape[0] >= 2, f"DTWMetrics needs at least 2 original samples, got {shape[0]}"
+        self.window = dtw.resolve_window(window, self.length)
+        self._original_self = None
+
+    def _as_series(self, flat):
+        assert flat.shape[1] == self.length * self.channels, \
+            f"samples of {flat.shape[1]} values against originals of ({self.length}, {self.channels})"
+        return flat.reshape(flat.shape[0], self.length, self.channels)
+
+    def __call__(self, other_samples) -> dict:
+        other = check_flat_array(other_samples)
+        assert other.shape[0] >= 2, f"DTWMetrics needs at least 2 samples, got {other.shape[0]}"
+        y = self._as_series(self._original())
+        if self._original_self is None:
+            self._original_self = dtw.self_search(y, self.window)
+        return dtw.dtw_scores(y, self._as_series(_to_device(other)), self.window, original_self=self._original_self)
+
+    @property
+    def baseline_metrics(self) -> dict:
+        y = self._as_series(self._original())
+        fold_a, fold_b = y[: y.shape[0] // 2], y[y.shape[0] // 2:]  # the cut of ManifoldMetrics.baseline_metrics
+        for fold in (fold_a, fold_b):
+            assert fold.shape[0] >= 2, f"DTWMetrics needs at least 2 rows in each half, got {fold.shape[0]}"
+        found = dtw.dtw_scores(fold_a, fold_b, self.window)
+        return {f"{key}_self": value for key, value in found.items()}
+
+    @property
+    def name(self) -> str:
+        return "dtw"

@@ -830,6 +830,45 @@ size_t ffd_mmd_permute_work_bytes(int n, int m, int P);
 int ffd_mmd_permute(const void* gram_work, int n, int m, const uint8_t* assign, int P, double* t_out, void* work,
                     size_t work_bytes, void* stream);
 
+/* ---- dynamic time warping between two sets of series: banded DTW search, paired DTW, six sample-quality numbers
+ * (csrc/ffd_dtw.hip; Sakoe & Chiba 1978; the 1-NN two-sample accuracy of Lopez-Paz & Oquab 2017) ----
+ * A series is (L, C) fp32, dense row-major; a set is (n, L, C) on the device, read only.  For a half-width `window` = w:
+ *   c(i, j) = sum_ch (a[i,ch] - b[j,ch])^2, fp32, ch = 0 .. C - 1 in order, the product and the sum rounded separately;
+ *   D(0, 0) = c(0, 0), D(i, j) = c(i, j) + min(D(i-1, j), D(i, j-1), D(i-1, j-1)) over the cells with |i - j| <= w,
+ *   one fp32 add per cell, every cell outside the band or the grid +inf;  dtw2(a, b; w) = D(L-1, L-1), a SQUARED cost.
+ * w = 0 is the squared Euclidean distance, w >= L - 1 unconstrained DTW; a window above L - 1 is clipped to L - 1 first.
+ * A cell does not depend on the order of evaluation: dtw2 has the same bits for every tiling, is bitwise symmetric in
+ * (a, b), and a copied row reads exactly 0.0.  Outputs are fp32, as the recurrence is.
+ *   search   per query row the k smallest (dtw2, index) over all reference rows, ordered by (value, then lower index):
+ *            dist2_out (nq, k) floats ascending, index_out (nq, k) int32.  exclude_self != 0 skips the pair i == i; legal
+ *            only when query and ref are the same buffer and nq == nr.  A lane owns one pair; a block of the pair matrix
+ *            goes through the workspace and the nearest-neighbour merge folds it into the running lists, which are the
+ *            outputs themselves.  Bit-identical from run to run, for every work_bytes, for a query set searched whole or
+ *            in parts, and whatever reference rows follow.
+ *   pairs    dist2_out[i] = dtw2(a[i], b[i]; w), n floats.
+ *   scores   from five arrays of n originals Y and m samples X, all fp32 on the device: the k = 1 squared DTW distances
+ *            xx_d2 (m; X in X, self excluded), xy_d2 (m; X in Y), yx_d2 (n; Y in X), yy_d2 (n; Y in Y, self excluded) and
+ *            xy_e2 (m; X in Y at window 0).  out6 doubles: mean_x sqrt(xy_d2); mean_y sqrt(yx_d2); the warp gain
+ *            1 - mean over the x with xy_e2 > 0 of sqrt(xy_d2 / xy_e2) (0.0 when there is none); the share of x with
+ *            xx_d2 < xy_d2; the share of y with yy_d2 < yx_d2 (both strict); the mean of the two shares.  One workgroup,
+ *            fixed-order fp64 trees.  n, m >= 2.
+ * `work`: device scratch, 16-byte aligned, of at least the bytes the size query returns: a distance block of as many
+ * 64 x 256 units (a power of two, at least one) as `budget_bytes` holds.  A smaller budget means more launches, never
+ * other results.  The size query returns 0 for arguments the search refuses.
+ * Context-free, stream ordered, no host synchronisation, no atomics.  NaN input: unspecified.
+ * FFD_ERR_INVALID before any device work, outputs untouched: a null pointer, a count, L or C < 1, window < 0, k < 1,
+ * k > FFD_DTW_MAX_K or k > nr - (exclude_self != 0), exclude_self with query != ref or nq != nr, a workspace that is too
+ * small or not 16-byte aligned, an output or the workspace overlapping an input or another output;
+ * FFD_ERR_UNSUPPORTED: rows > 2^24, L > FFD_DTW_MAX_LEN, C > FFD_DTW_MAX_CHANNELS, L C > 65 536, a clipped window above
+ * FFD_DTW_MAX_WINDOW. */
+enum { FFD_DTW_MAX_WINDOW = 64, FFD_DTW_MAX_LEN = 4096, FFD_DTW_MAX_CHANNELS = 64, FFD_DTW_MAX_K = 32 };
+size_t ffd_dtw_work_bytes(int nq, int nr, int L, int C, int window, int k, size_t budget_bytes);
+int ffd_dtw_search(const float* query, int nq, const float* ref, int nr, int L, int C, int window, int k, int exclude_self,
+                   float* dist2_out, int32_t* index_out, void* work, size_t work_bytes, void* stream);
+int ffd_dtw_pairs(const float* a, const float* b, int n, int L, int C, int window, float* dist2_out, void* stream);
+int ffd_dtw_scores(const float* xx_d2, const float* xy_d2, const float* yx_d2, const float* yy_d2, const float* xy_e2,
+                   int n_original, int m_samples, double* out6, void* stream);
+
 /* ---- denoising score-matching loss: the `val/loss` of ScoreModule.validation_step (src/fdiff/utils/losses.py) ----
  * Per sample b, with std[b,l] = sigma[b] * G[l] and n = L * C (losses.py:68-80, sde.py:106-123,187-210):
  *   x_noisy = mean_coeff[b] * x0 + std[b,l] * z                  r = score + z / std[b,l]
