@@ -149,6 +149,13 @@ SIGNATURES = {
     "ffd_mmd_gram": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_size_t, _P]),
     "ffd_mmd_permute_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "ffd_mmd_permute": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_sinkhorn_softmin_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ffd_sinkhorn_softmin": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_double, _P, _P, _P, C.c_size_t, _P]),
+    "ffd_sinkhorn_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ffd_sinkhorn": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ffd_sinkhorn_diameter2_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ffd_sinkhorn_diameter2": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "ffd_host_sinkhorn_schedule": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int, _P, C.c_int]),
     "ffd_dtw_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]),
     "ffd_dtw_search": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t,
                                  _P]),

@@ -11,7 +11,7 @@ from __future__ import annotations
 from abc import ABC, abstractmethod
 from functools import partial
 
-from ..utils import dtw, kernel_mmd, neighbours
+from ..utils import dtw, kernel_mmd, neighbours, sinkhorn
 from ..utils.fourier import dft, spectral_density
 from ..utils.tensors import check_flat_array
 from ..utils.wasserstein import WassersteinDistances, _column_mean, _summary, _to_device
@@ -309,6 +309,76 @@ class KernelMMD(Metric):
     @property
     def name(self) -> str:
         return "kernel_mmd"
+
+
+class SinkhornDivergence(Metric):
+    """The debiased entropic optimal-transport cost of a sample set X against the originals Y (``utils.sinkhorn``; not in
+    the reference, which slices because the full transport problem is out of reach on a host): the Sinkhorn divergence
+    S_eps(X, Y) = OT_eps(X, Y) - OT_eps(X, X) / 2 - OT_eps(Y, Y) / 2 of the squared Euclidean cost with uniform weights
+    (Genevay, Peyre, Cuturi 2018; Feydy et al. 2019).  It is 0 for equal sets, tends to W_2^2 as eps -> 0 and to an MMD
+    as eps -> infinity.  eps = ``blur``^2 sigma^2 with sigma^2 the originals' mean squared distance between two distinct
+    rows (``kernel_mmd.bandwidth``): ``blur`` is the resolution as a share of the data's own scale.
+
+    ``sinkhorn_divergence`` S; ``sinkhorn_distance`` sqrt(max(S, 0)); ``sinkhorn_ot`` the undebiased OT_eps(X, Y);
+    ``sinkhorn_change`` the largest change of a cross potential in the last damped pass, on the cost's scale: the
+    schedule's own statement of convergence; ``sinkhorn_eps`` the final eps.
+
+    The schedule -- eps from the originals' diameter^2 = 4 max_j |y_j - centre|^2 down by ``scaling``^2 per pass to the
+    final eps, then ``n_final`` passes there -- depends on the originals alone, so their self potential is computed once
+    and kept, as ``ManifoldMetrics`` keeps its self-search.  Samples that spread wider than the data start above the
+    schedule's first eps: that shows as a large ``sinkhorn_change``, never as a silent error.  A call runs the x|y, y|x
+    and x|x softmins per schedule entry, 2 n m + n^2 pairs each time; the originals' m^2 once.  There is no ``_dummy``
+    baseline."""
+
+    def __init__(self, original_samples, blur: float = 0.05, scaling: float = 0.5, n_final: int = 3) -> None:
+        super().__init__(original_samples=original_samples)
+        self.blur, self.scaling, self.n_final = float(blur), float(scaling), int(n_final)
+        assert self.blur > 0.0 and self.blur < float("inf"), f"blur must be positive and finite, got {blur}"
+        assert 0.0 < self.scaling < 1.0, f"scaling must lie in (0, 1), got {scaling}"
+        assert self.n_final >= 1, f"n_final must be at least 1, got {n_final}"
+        assert self.original_samples.shape[0] >= 2, "SinkhornDivergence needs at least 2 original samples"
+        self._cache = None
+        self._baseline = None
+
+    def _prepared_originals(self):
+        """(centre, schedule, self potential) of the originals, computed once."""
+        if self._cache is None:
+            y = self._original()
+            centre = kernel_mmd.column_mean(y)
+            eps = self.blur * self.blur * float(kernel_mmd.bandwidth(y).item())
+            schedule = sinkhorn.schedule(float(sinkhorn.diameter2(y, centre).item()), eps, self.scaling, self.n_final)
+            self._cache = (centre, schedule, sinkhorn.self_potential(y, centre, schedule))
+        return self._cache
+
+    def _evaluate(self, x, y, centre, schedule, q):
+        found = sinkhorn.sinkhorn_divergence(x, y, centre, schedule, q=q)
+        return {"sinkhorn_divergence": found.divergence, "sinkhorn_distance": max(found.divergence, 0.0) ** 0.5,
+                "sinkhorn_ot": found.ot_xy, "sinkhorn_change": found.change, "sinkhorn_eps": float(schedule[-1])}, found
+
+    def __call__(self, other_samples) -> dict:
+        centre, schedule, q = self._prepared_originals()
+        return self._evaluate(_to_device(check_flat_array(other_samples)), self._original(), centre, schedule, q)[0]
+
+    def transport_price(self, other_samples):
+        """f - p per sample, a float64 (n,) device tensor: what moving sample i to the originals costs beyond what moving
+        it inside its own set costs; large where the samples lie and the originals do not."""
+        centre, schedule, q = self._prepared_originals()
+        found = self._evaluate(_to_device(check_flat_array(other_samples)), self._original(), centre, schedule, q)[1]
+        return found.f - found.p
+
+    @property
+    def baseline_metrics(self) -> dict:
+        if self._baseline is None:  # a function of the originals alone: computed once
+            y = self._original()
+            fold_a, fold_b = y[: y.shape[0] // 2], y[y.shape[0] // 2:]  # the cut of ManifoldMetrics.baseline_metrics
+            centre, schedule, _ = self._prepared_originals()  # the whole set's centre and schedule: comparable with __call__
+            found, _ = self._evaluate(fold_b.contiguous(), fold_a.contiguous(), centre, schedule, None)
+            self._baseline = {f"{key}_self": value for key, value in found.items()}
+        return dict(self._baseline)
+
+    @property
+    def name(self) -> str:
+        return "sinkhorn"
 
 
 class DTWMetrics(Metric):

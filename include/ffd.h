@@ -830,6 +830,58 @@ size_t ffd_mmd_permute_work_bytes(int n, int m, int P);
 int ffd_mmd_permute(const void* gram_work, int n, int m, const uint8_t* assign, int P, double* t_out, void* work,
                     size_t work_bytes, void* stream);
 
+/* ---- entropic optimal transport between two row sets: the softmin of the squared-distance cost, the symmetric Sinkhorn
+ * loop and the Sinkhorn divergence (csrc/ffd_sinkhorn.hip; Cuturi 2013; Genevay, Peyre, Cuturi 2018; Feydy et al. 2019) ----
+ * Row sets are flat fp32 rows on the device, dense row-major, read only, with uniform weights.  Both sets of a call are
+ * centred on ONE caller-supplied vector `centre` (D floats on the device, ffd_mmd_centre) and C_ij = |x_i - y_j|^2 comes
+ * from the same Gram statement as ffd_nn_* and ffd_mmd_*: exact-fp32 MFMA in 64 x 256 tiles, (n_i + n_j) - 2 z_i . z_j
+ * clamped at 0, in chunks of 1024 coordinates for D > 1024.  Potentials are doubles on the device.
+ *   softmin   out[i] = -eps log( (1 / nr) sum_j exp((h[j] - C_ij) / eps) ), nq doubles; with `old` (nq doubles, may be
+ *             NULL) the damped update out[i] = (old[i] + that) / 2.  h is rounded once to fp32; the exponent and the
+ *             exponential are fp32 (one hardware exponential per pair; a term within 2^(-1/8) of the row's maximum is
+ *             1 + (2^t - 1) with the difference from its series, so that a large eps, where every term is 1 - x, keeps
+ *             x), a row's running (max, sum) keeps its sum in fp64.
+ *             A workgroup owns 64 query rows and walks a run of 4 column tiles (1024 columns; a constant of the source)
+ *             in order; the lanes', waves' and runs' (max, sum) pairs are merged in fp64 in a fixed order.  So out[i]
+ *             depends on the row, the column set, h, the centre and eps alone: bit-identical from run to run, for a
+ *             query set cut in parts, whatever rows surround it.  No cost block goes through memory.
+ *   loop      the symmetric, Jacobi-ordered iteration over `eps_schedule` (a HOST array of n_eps doubles): all potentials
+ *             start at 0 and in pass e every one is updated from the values of pass e - 1 alone,
+ *               f <- (f + softmin(x | y, g)) / 2     g <- (g + softmin(y | x, f)) / 2
+ *               p <- (p + softmin(x | x, p)) / 2     q <- (q + softmin(y | y, q)) / 2
+ *             (pass 0: the softmin itself), then one undamped pass at the last eps from the last damped values writes
+ *             f_out, p_out (n doubles) and g_out, q_out (m doubles).  out3 = { S = mean (f - p) + mean (g - q),
+ *             OT_eps(x, y) = mean f + mean g, the largest |change| of f and g in the last damped pass }: fixed-order fp64.
+ *             For two sets of equal rows the x|y and x|x problems are the same computation: S is exactly 0.0.
+ *             q_in (m doubles on the device, or NULL): an already converged self potential of y; the y|y passes are
+ *             skipped and q_out is its copy.  q does not depend on x: the q_out of any call on the same y, centre and
+ *             schedule may be handed to the next.
+ *   diameter  diameter2_out[0] = 4 max_j |y_j - centre|^2 (one double on the device): the square of twice the largest
+ *             radius about the centre, an upper bound of every squared distance inside the set; the fp32 differences
+ *             the tile is built from, squared and added in fp64.  Where a schedule starts.
+ *   schedule  ffd_host_sinkhorn_schedule, host only: diameter2, diameter2 scaling^2, diameter2 scaling^4, ... while the
+ *             value is above eps_target, then n_final entries of eps_target.  Returns the count; when it exceeds
+ *             `capacity` nothing is written (out may then be NULL).  FFD_ERR_INVALID: diameter2 or eps_target not finite
+ *             or <= 0, scaling outside (0, 1), n_final < 1, capacity < 0; FFD_ERR_UNSUPPORTED: more than 2^20 entries.
+ * Context-free, stream ordered, no host synchronisation, no atomics, no cross-workgroup waiting.  NaN input: unspecified.
+ * `work`: device scratch, 16-byte aligned, of at least the bytes the matching size query returns; 0 for arguments the
+ * call refuses.
+ * FFD_ERR_INVALID before any device work, outputs untouched: a null pointer (old and q_in excepted), a count < 1, n_eps
+ * < 1, an eps that is not finite, is <= 0 or whose log2(e) / eps is no normal fp32 number, a workspace that is too small
+ * or not 16-byte aligned, an output or the workspace overlapping an input or another output;
+ * FFD_ERR_UNSUPPORTED: rows > 2^24, D > 2^16. */
+size_t ffd_sinkhorn_softmin_work_bytes(int nq, int nr, int D);
+int ffd_sinkhorn_softmin(const float* query, int nq, const float* ref, int nr, int D, const float* centre, const double* h,
+                         double eps, const double* old, double* out, void* work, size_t work_bytes, void* stream);
+size_t ffd_sinkhorn_work_bytes(int n, int m, int D);
+int ffd_sinkhorn(const float* x, int n, const float* y, int m, int D, const float* centre, const double* eps_schedule,
+                 int n_eps, const double* q_in, double* f_out, double* g_out, double* p_out, double* q_out, double* out3,
+                 void* work, size_t work_bytes, void* stream);
+size_t ffd_sinkhorn_diameter2_work_bytes(int n, int D);
+int ffd_sinkhorn_diameter2(const float* y, int n, int D, const float* centre, double* diameter2_out, void* work,
+                           size_t work_bytes, void* stream);
+int ffd_host_sinkhorn_schedule(double diameter2, double eps_target, double scaling, int n_final, double* out, int capacity);
+
 /* ---- dynamic time warping between two sets of series: banded DTW search, paired DTW, six sample-quality numbers
  * (csrc/ffd_dtw.hip; Sakoe & Chiba 1978; the 1-NN two-sample accuracy of Lopez-Paz & Oquab 2017) ----
  * A series is (L, C) fp32, dense row-major; a set is (n, L, C) on the device, read only.  For a half-width `window` = w:
