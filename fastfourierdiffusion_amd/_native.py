@@ -156,6 +156,17 @@ SIGNATURES = {
     "ffd_sinkhorn_diameter2_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "ffd_sinkhorn_diameter2": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "ffd_host_sinkhorn_schedule": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int, _P, C.c_int]),
+    "ffd_cov_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ffd_cov": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "ffd_sym_eig_work_bytes": (C.c_size_t, [C.c_int]),
+    "ffd_sym_eig": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ffd_sym_root_work_bytes": (C.c_size_t, [C.c_int]),
+    "ffd_sym_root": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_frechet_work_bytes": (C.c_size_t, [C.c_int]),
+    "ffd_frechet": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "ffd_pca_variances_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ffd_pca_variances": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "ffd_pca_transform": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     "ffd_dtw_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]),
     "ffd_dtw_search": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t,
                                  _P]),

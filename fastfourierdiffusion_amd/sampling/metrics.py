@@ -11,7 +11,7 @@ from __future__ import annotations
 from abc import ABC, abstractmethod
 from functools import partial
 
-from ..utils import dtw, kernel_mmd, neighbours, sinkhorn
+from ..utils import dtw, kernel_mmd, neighbours, pca, sinkhorn
 from ..utils.fourier import dft, spectral_density
 from ..utils.tensors import check_flat_array
 from ..utils.wasserstein import WassersteinDistances, _column_mean, _summary, _to_device
@@ -379,6 +379,83 @@ class SinkhornDivergence(Metric):
     @property
     def name(self) -> str:
         return "sinkhorn"
+
+
+class FrechetDistance(Metric):
+    """The Frechet distance of a sample set X against the originals Y (``utils.pca``; not in the reference): the exact
+    W_2^2 between the Gaussians fitted to the two sets, the quantity behind FID (Dowson & Landau 1982; Heusel et al. 2017),
+    FD = |mu_x - mu_y|^2 + tr S_x + tr S_y - 2 tr (S_y^1/2 S_x S_y^1/2)^1/2, and the samples' variance along the data's
+    principal axes.  All of it is float64 on the device.
+
+    ``frechet_distance`` FD; ``frechet_w2`` sqrt(max(FD, 0)); ``frechet_mean_term`` and ``frechet_cov_term`` its two
+    parts: whether an error sits in the first or the second moment; ``variance_ratio`` tr S_x / tr S_y;
+    ``pc_variance_ratio_min`` / ``pc_variance_ratio_max`` over the data's top ``components`` axes v_i of
+    v_i^T S_x v_i / lambda_i: under- or over-dispersion per mode (1 for samples that spread as the data does).
+
+    The originals' mean, covariance, eigenpairs and root are computed once and kept, as ``KernelMMD`` keeps its row sums.
+    FD of finite samples is biased upward: ``baseline_metrics`` (the ``_self`` keys, one half of the originals against the
+    other) is its zero point.  There is no ``_dummy`` baseline: a single mean sample has no covariance."""
+
+    def __init__(self, original_samples, components: int = 10) -> None:
+        super().__init__(original_samples=original_samples)
+        self.components = int(components)
+        assert self.components >= 1, f"components must be at least 1, got {components}"
+        n, D = self.original_samples.shape
+        assert n >= 2, "FrechetDistance needs at least 2 original samples"
+        assert D <= pca.MAX_D, f"FrechetDistance takes at most {pca.MAX_D} features, got {D}"
+        self._cache = None
+        self._baseline = None
+
+    @staticmethod
+    def _moments(y):
+        """(mean, covariance, eigenvalues, eigenvectors, root) of a device set."""
+        mean, cov = pca.covariance(y)
+        w, v = pca.eigh(cov)
+        return mean, cov, w, v, pca.sym_root(w, v)
+
+    def _prepared_originals(self):
+        if self._cache is None:
+            self._cache = self._moments(self._original())
+        return self._cache
+
+    def _evaluate(self, x, prepared) -> dict:
+        assert x.shape[0] >= 2, f"FrechetDistance needs at least 2 samples, got {x.shape[0]}"
+        mean_y, cov_y, w, v, root = prepared
+        mean_x, cov_x = pca.covariance(x)
+        found = pca.frechet_distance(mean_x, cov_x, mean_y, cov_y, root_y=root)
+        k = min(self.components, w.shape[0])
+        ratios = pca.pc_variances(cov_x, v, k) / w.flip(0)[:k]
+        return {"frechet_distance": found.distance, "frechet_w2": max(found.distance, 0.0) ** 0.5,
+                "frechet_mean_term": found.mean_term, "frechet_cov_term": found.cov_term,
+                "variance_ratio": found.trace_x / found.trace_y if found.trace_y != 0.0 else float("nan"),
+                "pc_variance_ratio_min": float(ratios.min()), "pc_variance_ratio_max": float(ratios.max())}
+
+    def __call__(self, other_samples) -> dict:
+        return self._evaluate(_to_device(check_flat_array(other_samples)), self._prepared_originals())
+
+    def transform(self, samples, k: int = 2):
+        """The scores of ``samples`` on the data's ``k`` main axes (centred on the data's mean), float64 (n, k) on the
+        device: what the PCA scatter plot shows."""
+        mean_y, _, _, v, _ = self._prepared_originals()
+        return pca.transform(_to_device(check_flat_array(samples)), mean_y, v, k)
+
+    def explained_variance(self):
+        """The data's variance spectrum, the largest first: float64 (D,) on the device."""
+        return self._prepared_originals()[2].flip(0)
+
+    @property
+    def baseline_metrics(self) -> dict:
+        if self._baseline is None:  # a function of the originals alone: computed once
+            y = self._original()
+            fold_a, fold_b = y[: y.shape[0] // 2], y[y.shape[0] // 2:]  # the cut of ManifoldMetrics.baseline_metrics
+            assert fold_a.shape[0] >= 2, f"the baseline needs at least 2 rows in each half, got {fold_a.shape[0]}"
+            found = self._evaluate(fold_b.contiguous(), self._moments(fold_a.contiguous()))
+            self._baseline = {f"{key}_self": value for key, value in found.items()}
+        return dict(self._baseline)
+
+    @property
+    def name(self) -> str:
+        return "frechet"
 
 
 class DTWMetrics(Metric):

@@ -882,6 +882,61 @@ int ffd_sinkhorn_diameter2(const float* y, int n, int D, const float* centre, do
                            size_t work_bytes, void* stream);
 int ffd_host_sinkhorn_schedule(double diameter2, double eps_target, double scaling, int n_final, double* out, int capacity);
 
+/* ---- the first two moments of a row set in float64: covariance, a symmetric eigensolver, the symmetric square root, the
+ * Frechet distance between two fitted Gaussians and principal components (csrc/ffd_pca.hip; Dowson & Landau 1982; Heusel
+ * et al. 2017; Golub & Van Loan, Matrix Computations, 8.5) ----
+ * Row sets are flat fp32 rows (n, D) on the device, dense row-major, read only.  Everything else is float64 on the device,
+ * matrices dense row-major (D, D), and all arithmetic is float64; matrix products run on v_mfma_f64_16x16x4_f64 with k
+ * ascending.  1 <= D <= FFD_PCA_MAX_D, 2 <= n <= 2^24 (ffd_pca_transform: n >= 1).
+ *   cov        mean_out[d] = the column mean (fixed-order fp64 tree over slabs of 1024 rows); cov_out = D^T D / (n - 1) of
+ *              the deviations (double)x - mean, over slabs of 256 rows each summed from zero, the slabs of a run (a count
+ *              that depends on n alone; at most 64 runs) added in slab order and the runs in run order.  Only the upper
+ *              triangle's 64 x 64 tiles are formed and entry (j, i) is entry (i, j): bitwise symmetric, bit-identical from
+ *              run to run.
+ *   sym_eig    all eigenvalues of the symmetric matrix `a` (its upper triangle is read; it may be indefinite), ascending in
+ *              w_out (D), and with v_out (D, D; may be NULL: then no vectors are accumulated and w_out has the same bits)
+ *              the eigenvectors as columns, v_out[d][i] component d of the vector of w_out[i].  Cyclic Jacobi in the
+ *              round-robin order: D - 1 rounds (D for odd D, one index sitting out) of floor(D / 2) disjoint rotations, a
+ *              round two launches.  For a pair p < q with a_pq != 0: tau = (a_qq - a_pp) / (2 a_pq),
+ *              t = sign(tau) / (|tau| + sqrt(1 + tau^2)), c = 1 / sqrt(1 + t^2), s = t c; a_pq == 0 is skipped.  A sweep
+ *              starts only while off(A) > 2^-53 |A|_F; every threshold is relative, so a matrix times a power of two gives
+ *              that power times the same eigenvalues and the same vectors, bit for bit.  The matrix stays bitwise symmetric
+ *              throughout.  max_sweeps caps the sweeps (0: the default, 30).  info3_host: THREE DOUBLES ON THE HOST =
+ *              { sweeps done, the final off(A) / |A|_F, 1.0 if that is <= 2^-53 else 0.0 }: a cap that was hit is FFD_OK
+ *              with info3_host[2] = 0.  The test is one 8-byte read-back per sweep: THIS ENTRY SYNCHRONISES ITS STREAM (so
+ *              does ffd_frechet) and cannot be captured in a graph.
+ *   sym_root   root_out = V diag(sqrt(max(w, 0))) V^T from eigenvalues w (D) and eigenvectors v (D, D, columns); the upper
+ *              triangle mirrored: bitwise symmetric.
+ *   frechet    out5 (five doubles on the device) = { FD, |mean_x - mean_y|^2, tr S_x + tr S_y - 2 sum_i sqrt(max(l_i, 0)),
+ *              tr S_x, tr S_y }, FD the sum of the two terms, l the eigenvalues of M = (P + P^T) / 2, P = R S_x R from two
+ *              products, R = root_y or, when root_y is NULL, the sym_root of sym_eig(cov_y); sums are fixed-order trees.
+ *              info3_host as for sym_eig, the worst of the decompositions the call made.
+ *   variances  out[i] = v_i^T cov v_i for the k eigenvectors of largest eigenvalue, i = 0 the largest (column D - 1 - i of
+ *              v, as sym_eig orders them).
+ *   transform  scores_out (n, k) = ((double)x - mean) V[:, D - 1 - j], column j = 0 the axis of largest eigenvalue.
+ * Context-free, stream ordered, no atomics, no cross-workgroup waiting.  NaN input: unspecified.
+ * `work`: device scratch, 16-byte aligned, of at least the bytes the matching size query returns; the queries are monotone
+ * in every argument and 0 for arguments the call refuses.
+ * FFD_ERR_INVALID before any device work, outputs untouched: a null pointer (v_out and root_y excepted), n < 2 (transform:
+ * n < 1), D < 1, k < 1 or k > D, max_sweeps < 0, a workspace that is too small or not 16-byte aligned, an output or the
+ * workspace overlapping an input or another output; FFD_ERR_UNSUPPORTED: n > 2^24, D > FFD_PCA_MAX_D. */
+enum { FFD_PCA_MAX_D = 1024 };
+size_t ffd_cov_work_bytes(int n, int D);
+int ffd_cov(const float* x, int n, int D, double* mean_out, double* cov_out, void* work, size_t work_bytes, void* stream);
+size_t ffd_sym_eig_work_bytes(int D);
+int ffd_sym_eig(const double* a, int D, int max_sweeps, double* w_out, double* v_out, double* info3_host, void* work,
+                size_t work_bytes, void* stream);
+size_t ffd_sym_root_work_bytes(int D);
+int ffd_sym_root(const double* w, const double* v, int D, double* root_out, void* work, size_t work_bytes, void* stream);
+size_t ffd_frechet_work_bytes(int D);
+int ffd_frechet(const double* mean_x, const double* cov_x, const double* mean_y, const double* cov_y, const double* root_y,
+                int D, int max_sweeps, double* out5, double* info3_host, void* work, size_t work_bytes, void* stream);
+size_t ffd_pca_variances_work_bytes(int D, int k);
+int ffd_pca_variances(const double* cov, const double* v, int D, int k, double* out, void* work, size_t work_bytes,
+                      void* stream);
+int ffd_pca_transform(const float* x, int n, int D, const double* mean, const double* v, int k, double* scores_out,
+                      void* stream);
+
 /* ---- dynamic time warping between two sets of series: banded DTW search, paired DTW, six sample-quality numbers
  * (csrc/ffd_dtw.hip; Sakoe & Chiba 1978; the 1-NN two-sample accuracy of Lopez-Paz & Oquab 2017) ----
  * A series is (L, C) fp32, dense row-major; a set is (n, L, C) on the device, read only.  For a half-width `window` = w:
