@@ -297,13 +297,9 @@ int ffd_dtw_search(const float* query, int nq, const float* ref, int nr, int L, 
   if (k < 1 || k > FFD_DTW_MAX_K || (long long)k > (long long)nr - (exclude_self ? 1 : 0)) return FFD_ERR_INVALID;
   if (exclude_self && (query != ref || nq != nr)) return FFD_ERR_INVALID;
   if (nq > DTW_MAX_ROWS || nr > DTW_MAX_ROWS || !dtw_shape_supported(L, C, window)) return FFD_ERR_UNSUPPORTED;
-  if (((uintptr_t)work & 15) || work_bytes < DTW_UNIT_BYTES) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, DTW_UNIT_BYTES)) return FFD_ERR_INVALID;
   const size_t qb = (size_t)nq * L * C * 4, rb = (size_t)nr * L * C * 4, db = (size_t)nq * k * 4;
-  if (nn_overlap(dist2_out, db, query, qb) || nn_overlap(dist2_out, db, ref, rb) || nn_overlap(index_out, db, query, qb) ||
-      nn_overlap(index_out, db, ref, rb) || nn_overlap(dist2_out, db, index_out, db) ||
-      nn_overlap(work, work_bytes, query, qb) || nn_overlap(work, work_bytes, ref, rb) ||
-      nn_overlap(work, work_bytes, dist2_out, db) || nn_overlap(work, work_bytes, index_out, db))
-    return FFD_ERR_INVALID;
+  if (regions_clash({{dist2_out, db}, {index_out, db}, {work, work_bytes}}, {{query, qb}, {ref, rb}})) return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const int w = dtw_clip(window, L), wp = dtw_pad(w);
   float* T = (float*)work;
@@ -336,7 +332,7 @@ int ffd_dtw_pairs(const float* a, const float* b, int n, int L, int C, int windo
   if (!a || !b || !dist2_out || n < 1 || !dtw_shape_ok(L, C, window)) return FFD_ERR_INVALID;
   if (n > DTW_MAX_ROWS || !dtw_shape_supported(L, C, window)) return FFD_ERR_UNSUPPORTED;
   const size_t rb = (size_t)n * L * C * 4;
-  if (nn_overlap(dist2_out, (size_t)n * 4, a, rb) || nn_overlap(dist2_out, (size_t)n * 4, b, rb)) return FFD_ERR_INVALID;
+  if (regions_clash({{dist2_out, (size_t)n * 4}}, {{a, rb}, {b, rb}})) return FFD_ERR_INVALID;
   const int w = dtw_clip(window, L);
   switch (dtw_pad(w)) {
 #define DTW_CASE(W) \
@@ -354,9 +350,7 @@ int ffd_dtw_scores(const float* xx_d2, const float* xy_d2, const float* yx_d2, c
   if (!xx_d2 || !xy_d2 || !yx_d2 || !yy_d2 || !xy_e2 || !out6 || n_original < 2 || m_samples < 2) return FFD_ERR_INVALID;
   if (n_original > DTW_MAX_ROWS || m_samples > DTW_MAX_ROWS) return FFD_ERR_UNSUPPORTED;
   const size_t mb = (size_t)m_samples * 4, nb = (size_t)n_original * 4;
-  if (nn_overlap(out6, 48, xx_d2, mb) || nn_overlap(out6, 48, xy_d2, mb) || nn_overlap(out6, 48, yx_d2, nb) ||
-      nn_overlap(out6, 48, yy_d2, nb) || nn_overlap(out6, 48, xy_e2, mb))
-    return FFD_ERR_INVALID;
+  if (regions_clash({{out6, 48}}, {{xx_d2, mb}, {xy_d2, mb}, {yx_d2, nb}, {yy_d2, nb}, {xy_e2, mb}})) return FFD_ERR_INVALID;
   hipLaunchKernelGGL(k_dtw_scores, dim3(1), dim3(256), 0, (hipStream_t)stream, xx_d2, xy_d2, yx_d2, yy_d2, xy_e2, n_original,
                      m_samples, out6);
   return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;

@@ -333,8 +333,6 @@ __global__ __launch_bounds__(256) void k_mmd_perm_fold(const double* __restrict_
 }
 
 // ---- host: checks, workspaces --------------------------------------------------------------------------------------
-static bool mmd_shape_ok(int na, int nb, int D) { return na >= 1 && nb >= 1 && D >= 1; }
-static bool mmd_shape_supported(int na, int nb, int D) { return na <= NN_MAX_ROWS && nb <= NN_MAX_ROWS && D <= NN_MAX_D; }
 // FFD_OK and the rounded exponents, or FFD_ERR_INVALID: gammas finite, >= 0, -gamma log2(e) finite in fp32
 static int mmd_gammas(const double* gammas, int n_gamma, MmdGammas* out) {
   if (!gammas || n_gamma < 1 || n_gamma > MMD_MAX_G) return FFD_ERR_INVALID;
@@ -348,33 +346,21 @@ static int mmd_gammas(const double* gammas, int n_gamma, MmdGammas* out) {
   return FFD_OK;
 }
 
-// Dynamic LDS of a tile kernel: the chunked sum's cells for rows of more than NN_K_CHUNK padded columns (the attribute
-// lifts the kernel's limit; a failure shows as the launch's error)
-template <typename K>
-static size_t mmd_spill_bytes(K kernel, int Dp) {
-  if (Dp <= NN_K_CHUNK) return 0;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)NN_SPILL_BYTES);
-  return NN_SPILL_BYTES;
-}
-
+// The row sums' workspace: the centred pair (b the reference, a the query side) and the runs' partial sums
 struct MmdRowPlan {
-  int Dp, nbi, nbj, nruns;
-  size_t za, zb, nrm_a, nrm_b, part, bytes;
+  PairPlan pair;
+  int nbi, nbj, nruns;
+  size_t part, bytes;
 };
 static MmdRowPlan mmd_row_plan(int na, int nb, int D, int n_gamma) {
   MmdRowPlan p;
-  p.Dp = (int)nn_up(D, 16);
   p.nbi = cdiv(na, NN_I);
   p.nbj = cdiv(nb, NN_J);
   p.nruns = cdiv(p.nbj, MMD_RUN);
-  size_t o = 0;
-  p.zb = o, o += (size_t)nb * p.Dp * 4;
-  p.za = o, o += (size_t)na * p.Dp * 4;
-  p.nrm_b = o, o += nn_up((size_t)nb * 4, 16);
-  p.nrm_a = o, o += nn_up((size_t)na * 4, 16);
-  p.part = o, o += nn_up((size_t)p.nruns * n_gamma * na * 8, 16);
-  p.bytes = o;
+  Carver c;
+  p.pair = nn_pair_plan(c, na, nb, D);
+  p.part = c.take((size_t)p.nruns * n_gamma * na * 8);
+  p.bytes = c.total;
   return p;
 }
 
@@ -382,9 +368,9 @@ template <int NG>
 static void mmd_launch_rowsums(const MmdRowPlan& p, const float* Za, const float* nrm_a, int na, const float* Zb,
                                const float* nrm_b, int nb, const MmdGammas& gm, int exclude_self, double* part,
                                hipStream_t s) {
-  const size_t lds = mmd_spill_bytes(k_mmd_rowsums<NG>, p.Dp);
-  hipLaunchKernelGGL(k_mmd_rowsums<NG>, dim3(p.nbi, p.nruns), dim3(256), lds, s, Za, nrm_a, na, Zb, nrm_b, nb, p.Dp, gm,
-                     exclude_self, p.nbj, part);
+  const size_t lds = nn_spill_bytes(k_mmd_rowsums<NG>, p.pair.Dp);
+  hipLaunchKernelGGL(k_mmd_rowsums<NG>, dim3(p.nbi, p.nruns), dim3(256), lds, s, Za, nrm_a, na, Zb, nrm_b, nb, p.pair.Dp,
+                     gm, exclude_self, p.nbj, part);
 }
 
 struct MmdGramPlan {
@@ -396,11 +382,11 @@ static MmdGramPlan mmd_gram_plan(int n, int m, int D) {
   p.N = n + m;
   p.Np = (int)nn_up(p.N, 64);
   p.Dp = (int)nn_up(D, 16);
-  size_t o = 0;
-  p.k = o, o += (size_t)p.N * p.Np * 4;
-  p.z = o, o += (size_t)p.N * p.Dp * 4;
-  p.nrm = o, o += nn_up((size_t)p.N * 4, 16);
-  p.bytes = o;
+  Carver c;
+  p.k = c.take((size_t)p.N * p.Np * 4);
+  p.z = c.take((size_t)p.N * p.Dp * 4);
+  p.nrm = c.take((size_t)p.N * 4);
+  p.bytes = c.total;
   return p;
 }
 struct MmdPermPlan {
@@ -413,11 +399,24 @@ static MmdPermPlan mmd_perm_plan(int n, int m, int P) {
   p.Np = (int)nn_up(p.N, 64);
   p.Pp = (int)nn_up(P, 64);
   p.nib = cdiv(p.N, 64);
-  size_t o = 0;
-  p.ap = o, o += (size_t)p.Pp * p.Np;
-  p.rowtot = o, o += nn_up((size_t)p.N * 8, 16);
-  p.part = o, o += (size_t)p.nib * 3 * p.Pp * 8;
-  p.bytes = o;
+  Carver c;
+  p.ap = c.take((size_t)p.Pp * p.Np);
+  p.rowtot = c.take((size_t)p.N * 8);
+  p.part = c.take((size_t)p.nib * 3 * p.Pp * 8);
+  p.bytes = c.total;
+  return p;
+}
+// The bandwidth's workspace: the slab sums, the fp64 mean, every row's squared deviation
+struct MmdBandPlan {
+  size_t colpart, mean, dev, bytes;
+};
+static MmdBandPlan mmd_band_plan(int n, int D) {
+  MmdBandPlan p;
+  Carver c;
+  p.colpart = c.take(nn_colpart_bytes(n, D));
+  p.mean = c.take((size_t)D * 8);
+  p.dev = c.take((size_t)n * 8);
+  p.bytes = c.total;
   return p;
 }
 static bool mmd_pool_ok(int n, int m) { return n >= 2 && m >= 2; }
@@ -431,86 +430,64 @@ using namespace ffd;
 extern "C" {
 
 size_t ffd_mmd_centre_work_bytes(int n, int D) {
-  if (n < 1 || D < 1 || n > NN_MAX_ROWS || D > NN_MAX_D) return 0;
-  return nn_up((size_t)cdiv(n, NN_SLAB) * D * 8, 16);
+  if (!nn_shape_ok(n, n, D) || !nn_shape_supported(n, n, D)) return 0;
+  return nn_up(nn_colpart_bytes(n, D), 16);
 }
 
 int ffd_mmd_centre(const float* x, int n, int D, float* centre_out, void* work, size_t work_bytes, void* stream) {
-  if (!x || !centre_out || !work || n < 1 || D < 1) return FFD_ERR_INVALID;
-  if (n > NN_MAX_ROWS || D > NN_MAX_D) return FFD_ERR_UNSUPPORTED;
-  if (((uintptr_t)work & 15) || work_bytes < ffd_mmd_centre_work_bytes(n, D)) return FFD_ERR_INVALID;
-  const size_t xb = (size_t)n * D * 4, cb = (size_t)D * 4;
-  if (nn_overlap(centre_out, cb, x, xb) || nn_overlap(work, work_bytes, x, xb) || nn_overlap(work, work_bytes, centre_out, cb))
-    return FFD_ERR_INVALID;
-  hipStream_t s = (hipStream_t)stream;
-  const int nslab = cdiv(n, NN_SLAB);
-  hipLaunchKernelGGL(k_nn_colpart, dim3(cdiv(D, 64), nslab), dim3(256), 0, s, x, n, D, (double*)work);
-  hipLaunchKernelGGL(k_nn_colmean<float>, dim3(cdiv(D, 256)), dim3(256), 0, s, (const double*)work, nslab, n, D, centre_out);
+  if (!x || !centre_out || !work || !nn_shape_ok(n, n, D)) return FFD_ERR_INVALID;
+  if (!nn_shape_supported(n, n, D)) return FFD_ERR_UNSUPPORTED;
+  if (!work_ok(work, work_bytes, ffd_mmd_centre_work_bytes(n, D))) return FFD_ERR_INVALID;
+  if (regions_clash({{centre_out, (size_t)D * 4}, {work, work_bytes}}, {{x, (size_t)n * D * 4}})) return FFD_ERR_INVALID;
+  nn_launch_colmean(x, n, D, (double*)work, centre_out, (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
 }
 
 size_t ffd_mmd_bandwidth_work_bytes(int n, int D) {
-  if (n < 2 || D < 1 || n > NN_MAX_ROWS || D > NN_MAX_D) return 0;
-  return nn_up((size_t)cdiv(n, NN_SLAB) * D * 8, 16) + nn_up((size_t)D * 8, 16) + nn_up((size_t)n * 8, 16);
+  if (n < 2 || !nn_shape_ok(n, n, D) || !nn_shape_supported(n, n, D)) return 0;
+  return mmd_band_plan(n, D).bytes;
 }
 
 int ffd_mmd_bandwidth(const float* y, int n, int D, double* sigma2_out, void* work, size_t work_bytes, void* stream) {
-  if (!y || !sigma2_out || !work || n < 2 || D < 1) return FFD_ERR_INVALID;
-  if (n > NN_MAX_ROWS || D > NN_MAX_D) return FFD_ERR_UNSUPPORTED;
-  if (((uintptr_t)work & 15) || work_bytes < ffd_mmd_bandwidth_work_bytes(n, D)) return FFD_ERR_INVALID;
-  const size_t yb = (size_t)n * D * 4;
-  if (nn_overlap(sigma2_out, 8, y, yb) || nn_overlap(work, work_bytes, y, yb) || nn_overlap(work, work_bytes, sigma2_out, 8))
-    return FFD_ERR_INVALID;
+  if (!y || !sigma2_out || !work || n < 2 || !nn_shape_ok(n, n, D)) return FFD_ERR_INVALID;
+  if (!nn_shape_supported(n, n, D)) return FFD_ERR_UNSUPPORTED;
+  const MmdBandPlan p = mmd_band_plan(n, D);
+  if (!work_ok(work, work_bytes, p.bytes)) return FFD_ERR_INVALID;
+  if (regions_clash({{sigma2_out, 8}, {work, work_bytes}}, {{y, (size_t)n * D * 4}})) return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  const int nslab = cdiv(n, NN_SLAB);
   char* w = (char*)work;
-  double* colpart = (double*)w;
-  double* mean = (double*)(w + nn_up((size_t)nslab * D * 8, 16));
-  double* dev = (double*)((char*)mean + nn_up((size_t)D * 8, 16));
-  hipLaunchKernelGGL(k_nn_colpart, dim3(cdiv(D, 64), nslab), dim3(256), 0, s, y, n, D, colpart);
-  hipLaunchKernelGGL(k_nn_colmean<double>, dim3(cdiv(D, 256)), dim3(256), 0, s, colpart, nslab, n, D, mean);
+  double* mean = (double*)(w + p.mean);
+  double* dev = (double*)(w + p.dev);
+  nn_launch_colmean(y, n, D, (double*)(w + p.colpart), mean, s);
   hipLaunchKernelGGL(k_mmd_sqdev, dim3(cdiv(n, 4)), dim3(256), 0, s, y, mean, n, D, dev);
   hipLaunchKernelGGL(k_mmd_sigma2, dim3(1), dim3(256), 0, s, dev, n, sigma2_out);
   return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
 }
 
 size_t ffd_mmd_rowsums_work_bytes(int na, int nb, int D, int n_gamma) {
-  if (!mmd_shape_ok(na, nb, D) || !mmd_shape_supported(na, nb, D) || n_gamma < 1 || n_gamma > MMD_MAX_G) return 0;
+  if (!nn_shape_ok(na, nb, D) || !nn_shape_supported(na, nb, D) || n_gamma < 1 || n_gamma > MMD_MAX_G) return 0;
   return mmd_row_plan(na, nb, D, n_gamma).bytes;
 }
 
 int ffd_mmd_rowsums(const float* a, int na, const float* b, int nb, int D, const float* centre, const double* gammas,
                     int n_gamma, int exclude_self, double* rowsum_out, void* work, size_t work_bytes, void* stream) {
-  if (!a || !b || !centre || !rowsum_out || !work || !mmd_shape_ok(na, nb, D)) return FFD_ERR_INVALID;
+  if (!a || !b || !centre || !rowsum_out || !work || !nn_shape_ok(na, nb, D)) return FFD_ERR_INVALID;
   MmdGammas gm;
   if (mmd_gammas(gammas, n_gamma, &gm) != FFD_OK) return FFD_ERR_INVALID;
   if (exclude_self && (a != b || na != nb)) return FFD_ERR_INVALID;
-  if (!mmd_shape_supported(na, nb, D)) return FFD_ERR_UNSUPPORTED;
+  if (!nn_shape_supported(na, nb, D)) return FFD_ERR_UNSUPPORTED;
   const MmdRowPlan p = mmd_row_plan(na, nb, D, n_gamma);
-  if (((uintptr_t)work & 15) || work_bytes < p.bytes) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, p.bytes)) return FFD_ERR_INVALID;
   const size_t ab = (size_t)na * D * 4, bb = (size_t)nb * D * 4, cb = (size_t)D * 4, ob = (size_t)n_gamma * na * 8;
-  if (nn_overlap(rowsum_out, ob, a, ab) || nn_overlap(rowsum_out, ob, b, bb) || nn_overlap(rowsum_out, ob, centre, cb) ||
-      nn_overlap(work, work_bytes, a, ab) || nn_overlap(work, work_bytes, b, bb) || nn_overlap(work, work_bytes, centre, cb) ||
-      nn_overlap(work, work_bytes, rowsum_out, ob))
-    return FFD_ERR_INVALID;
+  if (regions_clash({{rowsum_out, ob}, {work, work_bytes}}, {{a, ab}, {b, bb}, {centre, cb}})) return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)work;
-  float* Zb = (float*)(w + p.zb);
-  float* nrm_b = (float*)(w + p.nrm_b);
-  const float* Za = Zb;
-  const float* nrm_a = nrm_b;
-  hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(nb, 4)), dim3(256), 0, s, b, centre, Zb, nrm_b, nb, D, p.Dp);
-  if (!(a == b && na == nb)) {
-    float* Zq = (float*)(w + p.za);
-    float* nrm_q = (float*)(w + p.nrm_a);
-    hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(na, 4)), dim3(256), 0, s, a, centre, Zq, nrm_q, na, D, p.Dp);
-    Za = Zq, nrm_a = nrm_q;
-  }
+  const PairRows z = nn_centre_pair(a, na, b, nb, D, centre, p.pair, w, s);
   double* part = (double*)(w + p.part);
   const int ex = exclude_self ? 1 : 0;
   switch (n_gamma) {
 #define FFD_MMD_CASE(NG) \
-  case NG: mmd_launch_rowsums<NG>(p, Za, nrm_a, na, Zb, nrm_b, nb, gm, ex, part, s); break;
+  case NG: mmd_launch_rowsums<NG>(p, z.Zq, z.nrm_q, na, z.Zr, z.nrm_r, nb, gm, ex, part, s); break;
     FFD_MMD_CASE(1) FFD_MMD_CASE(2) FFD_MMD_CASE(3) FFD_MMD_CASE(4) FFD_MMD_CASE(5) FFD_MMD_CASE(6) FFD_MMD_CASE(7)
     FFD_MMD_CASE(8)
 #undef FFD_MMD_CASE
@@ -527,11 +504,8 @@ int ffd_mmd_scores(const double* rowsum_xx, const double* rowsum_xy, const doubl
   if (n > NN_MAX_ROWS || m > NN_MAX_ROWS) return FFD_ERR_UNSUPPORTED;
   const size_t xb = (size_t)n_gamma * n * 8, yb = (size_t)n_gamma * m * 8, ob = (size_t)(2 * n_gamma + 2) * 8,
                wb = (size_t)n * 8;
-  const void* in[3] = {rowsum_xx, rowsum_xy, rowsum_yy};
-  const size_t inb[3] = {xb, xb, yb};
-  for (int i = 0; i < 3; ++i)
-    if (nn_overlap(mmd2_out, ob, in[i], inb[i]) || nn_overlap(witness_out, wb, in[i], inb[i])) return FFD_ERR_INVALID;
-  if (nn_overlap(mmd2_out, ob, witness_out, wb)) return FFD_ERR_INVALID;
+  if (regions_clash({{mmd2_out, ob}, {witness_out, wb}}, {{rowsum_xx, xb}, {rowsum_xy, xb}, {rowsum_yy, yb}}))
+    return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_mmd_scores, dim3(1), dim3(256), 0, s, rowsum_xx, rowsum_xy, rowsum_yy, n, m, n_gamma, mmd2_out);
   hipLaunchKernelGGL(k_mmd_witness, dim3(cdiv(n, 256)), dim3(256), 0, s, rowsum_xx, rowsum_xy, n, m, n_gamma, witness_out);
@@ -550,10 +524,9 @@ int ffd_mmd_gram(const float* x, int n, const float* y, int m, int D, const floa
   if (mmd_gammas(gammas, n_gamma, &gm) != FFD_OK) return FFD_ERR_INVALID;
   if (!mmd_pool_supported(n, m) || D > NN_MAX_D) return FFD_ERR_UNSUPPORTED;
   const MmdGramPlan p = mmd_gram_plan(n, m, D);
-  if (((uintptr_t)work & 15) || work_bytes < p.bytes) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, p.bytes)) return FFD_ERR_INVALID;
   const size_t xb = (size_t)n * D * 4, yb = (size_t)m * D * 4, cb = (size_t)D * 4;
-  if (nn_overlap(work, work_bytes, x, xb) || nn_overlap(work, work_bytes, y, yb) || nn_overlap(work, work_bytes, centre, cb))
-    return FFD_ERR_INVALID;
+  if (regions_clash({{work, work_bytes}}, {{x, xb}, {y, yb}, {centre, cb}})) return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)work;
   float* K = (float*)(w + p.k);
@@ -562,8 +535,8 @@ int ffd_mmd_gram(const float* x, int n, const float* y, int m, int D, const floa
   hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(n, 4)), dim3(256), 0, s, x, centre, Z, nrm, n, D, p.Dp);
   hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(m, 4)), dim3(256), 0, s, y, centre, Z + (size_t)n * p.Dp, nrm + n, m, D, p.Dp);
   const int nbi = cdiv(p.N, NN_I), nbj = cdiv(p.Np, NN_J);
-  hipLaunchKernelGGL(k_mmd_gram, dim3(nbi * nbj), dim3(256), mmd_spill_bytes(k_mmd_gram, p.Dp), s, Z, nrm, p.N, p.Dp, gm, n_gamma, 1.0f / (float)n_gamma, nbj,
-                     K, p.Np);
+  hipLaunchKernelGGL(k_mmd_gram, dim3(nbi * nbj), dim3(256), nn_spill_bytes(k_mmd_gram, p.Dp), s, Z, nrm, p.N, p.Dp, gm,
+                     n_gamma, 1.0f / (float)n_gamma, nbj, K, p.Np);
   return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
 }
 
@@ -577,12 +550,10 @@ int ffd_mmd_permute(const void* gram_work, int n, int m, const uint8_t* assign, 
   if (!gram_work || !assign || !t_out || !work || !mmd_pool_ok(n, m) || P < 1) return FFD_ERR_INVALID;
   if (!mmd_pool_supported(n, m) || P > FFD_MMD_MAX_PERMUTATIONS) return FFD_ERR_UNSUPPORTED;
   const MmdPermPlan p = mmd_perm_plan(n, m, P);
-  if (((uintptr_t)work & 15) || ((uintptr_t)gram_work & 15) || work_bytes < p.bytes) return FFD_ERR_INVALID;
-  const size_t kb = (size_t)p.N * p.Np * 4, ab = (size_t)P * p.N, tb = (size_t)P * 8;
-  if (nn_overlap(work, work_bytes, gram_work, kb) || nn_overlap(work, work_bytes, assign, ab) ||
-      nn_overlap(work, work_bytes, t_out, tb) || nn_overlap(t_out, tb, gram_work, kb) || nn_overlap(t_out, tb, assign, ab) ||
-      nn_overlap(assign, ab, gram_work, kb))
-    return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, p.bytes) || ((uintptr_t)gram_work & 15)) return FFD_ERR_INVALID;
+  const Region kmat{gram_work, (size_t)p.N * p.Np * 4}, asg{assign, (size_t)P * p.N};
+  if (regions_clash({{t_out, (size_t)P * 8}, {work, work_bytes}}, {kmat, asg})) return FFD_ERR_INVALID;
+  if (regions_meet(asg, kmat)) return FFD_ERR_INVALID;  // two read regions, refused all the same
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)work;
   const float* K = (const float*)gram_work;

@@ -230,32 +230,28 @@ static size_t nn_pow2_ceil(size_t v) {
   return p;
 }
 
-// The fixed part of the workspace, every piece a multiple of 16 bytes: the centred sets, their norms, the mean and its
-// slab sums, then the running lists (search, k >= 1) or the partial counts (ball counts, k == 0).
+// The fixed part of the workspace: the centred sets and their norms, the mean and its slab sums, then the running lists
+// (search, k >= 1) or the partial counts (ball counts, k == 0).
 struct NNPlan {
-  int Dp, nslab, nbi, nbj;
-  size_t zr, zq, nrm_r, nrm_q, mean, colpart, tail_a, tail_b, fixed;  // byte offsets
+  PairPlan pair;
+  int nbi, nbj;
+  size_t mean, colpart, tail_a, tail_b, fixed;  // byte offsets
 };
 static NNPlan nn_plan(int nq, int nr, int D, int k) {
   NNPlan p;
-  p.Dp = (int)nn_up(D, 16);
-  p.nslab = cdiv(nr, NN_SLAB);
   p.nbi = cdiv(nq, NN_I);
   p.nbj = cdiv(nr, NN_J);
-  size_t o = 0;
-  p.zr = o, o += (size_t)nr * p.Dp * 4;
-  p.zq = o, o += (size_t)nq * p.Dp * 4;
-  p.nrm_r = o, o += nn_up((size_t)nr * 4, 16);
-  p.nrm_q = o, o += nn_up((size_t)nq * 4, 16);
-  p.mean = o, o += (size_t)p.Dp * 4;
-  p.colpart = o, o += nn_up((size_t)p.nslab * D * 8, 16);
+  Carver c;
+  p.pair = nn_pair_plan(c, nq, nr, D);
+  p.mean = c.take((size_t)p.pair.Dp * 4);
+  p.colpart = c.take(nn_colpart_bytes(nr, D));
   if (k > 0) {
-    p.tail_a = o, o += nn_up((size_t)nq * k * 4, 16);  // cand_d
-    p.tail_b = o, o += nn_up((size_t)nq * k * 4, 16);  // cand_i
+    p.tail_a = c.take((size_t)nq * k * 4);  // cand_d
+    p.tail_b = c.take((size_t)nq * k * 4);  // cand_i
   } else {
-    p.tail_a = p.tail_b = o, o += nn_up((size_t)std::min(p.nbj, NN_MAX_CHUNKS) * nq * 4, 16);  // part
+    p.tail_a = p.tail_b = c.take((size_t)std::min(p.nbj, NN_MAX_CHUNKS) * nq * 4);  // part
   }
-  p.fixed = o;
+  p.fixed = c.total;
   return p;
 }
 // column tiles per chunk and row tiles per block of the distance block that `units` 64 x 256 tiles allow
@@ -264,8 +260,6 @@ static void nn_block(size_t units, const NNPlan& p, int* cbt, int* qbt) {
   *cbt = (int)std::min(units, std::min<size_t>(nn_pow2_ceil(p.nbj), NN_MAX_CBT));
   *qbt = (int)std::min<size_t>(units / *cbt, p.nbi);
 }
-static bool nn_shape_ok(int nq, int nr, int D) { return nq >= 1 && nr >= 1 && D >= 1; }
-static bool nn_shape_supported(int nq, int nr, int D) { return nq <= NN_MAX_ROWS && nr <= NN_MAX_ROWS && D <= NN_MAX_D; }
 static size_t nn_search_bytes(int nq, int nr, int D, int k, size_t budget) {
   const NNPlan p = nn_plan(nq, nr, D, k);
   int cbt, qbt;
@@ -274,25 +268,12 @@ static size_t nn_search_bytes(int nq, int nr, int D, int k, size_t budget) {
 }
 static size_t nn_ball_bytes(int nq, int nr, int D) { return nn_plan(nq, nr, D, 0).fixed; }
 
-// the reference mean, then both centred copies (one where the query set is the reference set)
+// the reference mean, then both sets centred on it
 static hipError_t nn_centre(const float* query, int nq, const float* ref, int nr, int D, const NNPlan& p, char* work,
-                            const float** zq_out, const float** nrm_q_out, hipStream_t s) {
-  float* Zr = (float*)(work + p.zr);
-  float* nrm_r = (float*)(work + p.nrm_r);
+                            PairRows* rows, hipStream_t s) {
   float* mean = (float*)(work + p.mean);
-  double* colpart = (double*)(work + p.colpart);
-  hipLaunchKernelGGL(k_nn_colpart, dim3(cdiv(D, 64), p.nslab), dim3(256), 0, s, ref, nr, D, colpart);
-  hipLaunchKernelGGL(k_nn_colmean<float>, dim3(cdiv(D, 256)), dim3(256), 0, s, colpart, p.nslab, nr, D, mean);
-  hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(nr, 4)), dim3(256), 0, s, ref, mean, Zr, nrm_r, nr, D, p.Dp);
-  *zq_out = Zr;
-  *nrm_q_out = nrm_r;
-  if (!(query == ref && nq == nr)) {
-    float* Zq = (float*)(work + p.zq);
-    float* nrm_q = (float*)(work + p.nrm_q);
-    hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(nq, 4)), dim3(256), 0, s, query, mean, Zq, nrm_q, nq, D, p.Dp);
-    *zq_out = Zq;
-    *nrm_q_out = nrm_q;
-  }
+  nn_launch_colmean(ref, nr, D, (double*)(work + p.colpart), mean, s);
+  *rows = nn_centre_pair(query, nq, ref, nr, D, mean, p.pair, work, s);
   return hipGetLastError();
 }
 
@@ -315,19 +296,13 @@ int ffd_nn_search(const float* query, int nq, const float* ref, int nr, int D, i
   if (exclude_self && (query != ref || nq != nr)) return FFD_ERR_INVALID;
   if (!nn_shape_supported(nq, nr, D)) return FFD_ERR_UNSUPPORTED;
   const NNPlan p = nn_plan(nq, nr, D, k);
-  if (((uintptr_t)work & 15) || work_bytes < p.fixed + NN_UNIT_BYTES) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, p.fixed + NN_UNIT_BYTES)) return FFD_ERR_INVALID;
   const size_t qb = (size_t)nq * D * 4, rb = (size_t)nr * D * 4, db = (size_t)nq * k * 8, xb = (size_t)nq * k * 4;
-  if (nn_overlap(dist2_out, db, query, qb) || nn_overlap(dist2_out, db, ref, rb) || nn_overlap(index_out, xb, query, qb) ||
-      nn_overlap(index_out, xb, ref, rb) || nn_overlap(dist2_out, db, index_out, xb) ||
-      nn_overlap(work, work_bytes, query, qb) || nn_overlap(work, work_bytes, ref, rb) ||
-      nn_overlap(work, work_bytes, dist2_out, db) || nn_overlap(work, work_bytes, index_out, xb))
-    return FFD_ERR_INVALID;
+  if (regions_clash({{dist2_out, db}, {index_out, xb}, {work, work_bytes}}, {{query, qb}, {ref, rb}})) return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)work;
-  const float *Zq, *nrm_q;
-  if (nn_centre(query, nq, ref, nr, D, p, w, &Zq, &nrm_q, s) != hipSuccess) return FFD_ERR_HIP;
-  const float* Zr = (const float*)(w + p.zr);
-  const float* nrm_r = (const float*)(w + p.nrm_r);
+  PairRows z;
+  if (nn_centre(query, nq, ref, nr, D, p, w, &z, s) != hipSuccess) return FFD_ERR_HIP;
   float* cand_d = (float*)(w + p.tail_a);
   int* cand_i = (int*)(w + p.tail_b);
   float* T = (float*)(w + p.fixed);
@@ -338,8 +313,8 @@ int ffd_nn_search(const float* query, int nq, const float* ref, int nr, int D, i
     const int ib0 = bi * NN_I, rows = std::min(qbt * NN_I, nq - ib0), nqt = cdiv(rows, NN_I);
     for (int bj = 0; bj < p.nbj; bj += cbt) {
       const int jc0 = bj * NN_J, nct = std::min(cbt, p.nbj - bj), ncols = std::min(cb, nr - jc0);
-      hipLaunchKernelGGL(k_nn_tile, dim3(nqt * nct), dim3(256), 0, s, Zq, nrm_q, nq, Zr, nrm_r, nr, p.Dp, ib0, jc0, nct, cb,
-                         T);
+      hipLaunchKernelGGL(k_nn_tile, dim3(nqt * nct), dim3(256), 0, s, z.Zq, z.nrm_q, nq, z.Zr, z.nrm_r, nr,
+                         p.pair.Dp, ib0, jc0, nct, cb, T);
       hipLaunchKernelGGL(k_nn_merge, dim3(cdiv(rows, 4)), dim3(256), 0, s, T, cb, rows, ib0, jc0, ncols, exclude_self ? 1 : 0,
                          k, bj == 0 ? 1 : 0, cand_d, cand_i);
       if (hipGetLastError() != hipSuccess) return FFD_ERR_HIP;
@@ -354,29 +329,26 @@ int ffd_nn_ball_count(const float* query, int nq, const float* ref, int nr, int 
   if (!query || !ref || !radius2 || !count_out || !work || !nn_shape_ok(nq, nr, D)) return FFD_ERR_INVALID;
   if (exclude_self && (query != ref || nq != nr)) return FFD_ERR_INVALID;
   if (!nn_shape_supported(nq, nr, D)) return FFD_ERR_UNSUPPORTED;
-  if (((uintptr_t)work & 15) || work_bytes < ffd_nn_work_bytes(nq, nr, D, 1, 0)) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, ffd_nn_work_bytes(nq, nr, D, 1, 0))) return FFD_ERR_INVALID;
   const size_t qb = (size_t)nq * D * 4, rb = (size_t)nr * D * 4, cbytes = (size_t)nq * 4, radb = (size_t)nr * 4;
-  if (nn_overlap(count_out, cbytes, query, qb) || nn_overlap(count_out, cbytes, ref, rb) ||
-      nn_overlap(count_out, cbytes, radius2, radb) || nn_overlap(work, work_bytes, query, qb) ||
-      nn_overlap(work, work_bytes, ref, rb) || nn_overlap(work, work_bytes, radius2, radb) ||
-      nn_overlap(work, work_bytes, count_out, cbytes))
+  if (regions_clash({{count_out, cbytes}, {work, work_bytes}}, {{query, qb}, {ref, rb}, {radius2, radb}}))
     return FFD_ERR_INVALID;
   const NNPlan p = nn_plan(nq, nr, D, 0);
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)work;
-  const float *Zq, *nrm_q;
-  if (nn_centre(query, nq, ref, nr, D, p, w, &Zq, &nrm_q, s) != hipSuccess) return FFD_ERR_HIP;
+  PairRows z;
+  if (nn_centre(query, nq, ref, nr, D, p, w, &z, s) != hipSuccess) return FFD_ERR_HIP;
   int* part = (int*)(w + p.tail_a);
   const int CH = cdiv(p.nbj, NN_MAX_CHUNKS), nch = cdiv(p.nbj, CH);
-  hipLaunchKernelGGL(k_nn_ball, dim3(p.nbi * nch), dim3(256), 0, s, Zq, nrm_q, nq, (const float*)(w + p.zr),
-                     (const float*)(w + p.nrm_r), nr, p.Dp, radius2, exclude_self ? 1 : 0, p.nbj, CH, nch, part);
+  hipLaunchKernelGGL(k_nn_ball, dim3(p.nbi * nch), dim3(256), 0, s, z.Zq, z.nrm_q, nq, z.Zr, z.nrm_r, nr, p.pair.Dp,
+                     radius2, exclude_self ? 1 : 0, p.nbj, CH, nch, part);
   hipLaunchKernelGGL(k_nn_count_sum, dim3(cdiv(nq, 256)), dim3(256), 0, s, part, nch, nq, count_out);
   return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
 }
 
 int ffd_nn_radius(const double* dist2, int n, int k, int col, float* radius2_out, void* stream) {
   if (!dist2 || !radius2_out || n < 1 || k < 1 || k > FFD_NN_MAX_K || col < 0 || col >= k) return FFD_ERR_INVALID;
-  if (nn_overlap(dist2, (size_t)n * k * 8, radius2_out, (size_t)n * 4)) return FFD_ERR_INVALID;
+  if (regions_clash({{radius2_out, (size_t)n * 4}}, {{dist2, (size_t)n * k * 8}})) return FFD_ERR_INVALID;
   if (n > NN_MAX_ROWS) return FFD_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(k_nn_radius, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, dist2, n, k, col, radius2_out);
   return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
@@ -386,9 +358,12 @@ int ffd_nn_scores(const double* self_dist2, const double* xy_dist2, const int32_
                   const int32_t* count_x, const int32_t* count_y, int n, int m, int k, double* out8, void* stream) {
   if (!self_dist2 || !xy_dist2 || !xy_index || !yx_dist2 || !count_x || !count_y || !out8) return FFD_ERR_INVALID;
   if (n < 1 || m < 1 || k < 1 || k > FFD_NN_MAX_K) return FFD_ERR_INVALID;
-  if (nn_overlap(out8, 64, self_dist2, (size_t)n * k * 8) || nn_overlap(out8, 64, xy_dist2, (size_t)m * 8) ||
-      nn_overlap(out8, 64, xy_index, (size_t)m * 4) || nn_overlap(out8, 64, yx_dist2, (size_t)n * 8) ||
-      nn_overlap(out8, 64, count_x, (size_t)m * 4) || nn_overlap(out8, 64, count_y, (size_t)n * 4))
+  if (regions_clash({{out8, 64}}, {{self_dist2, (size_t)n * k * 8},
+                                   {xy_dist2, (size_t)m * 8},
+                                   {xy_index, (size_t)m * 4},
+                                   {yx_dist2, (size_t)n * 8},
+                                   {count_x, (size_t)m * 4},
+                                   {count_y, (size_t)n * 4}}))
     return FFD_ERR_INVALID;
   if (n > NN_MAX_ROWS || m > NN_MAX_ROWS) return FFD_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(k_nn_scores, dim3(1), dim3(256), 0, (hipStream_t)stream, self_dist2, xy_dist2, xy_index, yx_dist2,

@@ -9,12 +9,16 @@
 //   nn_d2          d^2 = (n_i + n_j) - 2 z_i . z_j, clamped at 0
 //   k_nn_merge     a block of pair values (rows x a chunk of columns) merged into each row's list of the k smallest,
 //                  ordered by nn_before: (value, then lower index); also used by ffd_dtw.hip
+// Host side, for the entry points of these sources and of ffd_sinkhorn.hip and ffd_pca.hip: the shape limits, the tile
+// kernels' dynamic LDS (nn_spill_bytes), the column-mean launcher, and the centred-pair layout with its launcher
+// (nn_pair_plan, nn_centre_pair); the workspace helpers they stand on are ffd_workspace.h.
 // The kernels are static: each translation unit that launches one carries its own copy (the library is built without
 // relocatable device code).
 #pragma once
 #include <climits>
 
 #include "ffd_internal.h"
+#include "ffd_workspace.h"
 
 namespace ffd {
 
@@ -199,10 +203,60 @@ static __global__ __launch_bounds__(256) void k_nn_merge(const float* __restrict
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------
-static inline size_t nn_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-static inline bool nn_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
+// (the round-up, the workspace carver, work_ok and regions_clash: ffd_workspace.h)
+static inline bool nn_shape_ok(int nq, int nr, int D) { return nq >= 1 && nr >= 1 && D >= 1; }
+static inline bool nn_shape_supported(int nq, int nr, int D) {
+  return nq <= NN_MAX_ROWS && nr <= NN_MAX_ROWS && D <= NN_MAX_D;
+}
+
+// Dynamic LDS of a tile kernel: the chunked sum's cells for rows of more than NN_K_CHUNK padded columns (the attribute
+// lifts the kernel's limit; a failure shows as the launch's error)
+template <typename K>
+static size_t nn_spill_bytes(K kernel, int Dp) {
+  if (Dp <= NN_K_CHUNK) return 0;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)NN_SPILL_BYTES);
+  return NN_SPILL_BYTES;
+}
+
+// mean = the column mean of X (n, D), as float (what rows are centred on) or double; colpart: nn_colpart_bytes
+static inline size_t nn_colpart_bytes(int n, int D) { return (size_t)cdiv(n, NN_SLAB) * D * 8; }
+template <typename T>
+static void nn_launch_colmean(const float* X, int n, int D, double* colpart, T* mean, hipStream_t s) {
+  const int nslab = cdiv(n, NN_SLAB);
+  hipLaunchKernelGGL(k_nn_colpart, dim3(cdiv(D, 64), nslab), dim3(256), 0, s, X, n, D, colpart);
+  hipLaunchKernelGGL(k_nn_colmean<T>, dim3(cdiv(D, 256)), dim3(256), 0, s, (const double*)colpart, nslab, n, D, mean);
+}
+
+// The centred copies of a reference and a query set and their norms, carved in this order
+struct PairPlan {
+  int Dp;
+  size_t zr, zq, nrm_r, nrm_q;  // byte offsets
+};
+static inline PairPlan nn_pair_plan(Carver& c, int nq, int nr, int D) {
+  PairPlan p;
+  p.Dp = (int)nn_up(D, 16);
+  p.zr = c.take((size_t)nr * p.Dp * 4);
+  p.zq = c.take((size_t)nq * p.Dp * 4);
+  p.nrm_r = c.take((size_t)nr * 4);
+  p.nrm_q = c.take((size_t)nq * 4);
+  return p;
+}
+struct PairRows {
+  const float *Zq, *nrm_q, *Zr, *nrm_r;
+};
+// Centres the reference rows on `centre`, and the query rows unless they are the same set: then the query side is the
+// reference side's copy.
+static inline PairRows nn_centre_pair(const float* query, int nq, const float* ref, int nr, int D, const float* centre,
+                                      const PairPlan& p, char* work, hipStream_t s) {
+  float* Zr = (float*)(work + p.zr);
+  float* nrm_r = (float*)(work + p.nrm_r);
+  hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(nr, 4)), dim3(256), 0, s, ref, centre, Zr, nrm_r, nr, D, p.Dp);
+  if (query == ref && nq == nr) return PairRows{Zr, nrm_r, Zr, nrm_r};
+  float* Zq = (float*)(work + p.zq);
+  float* nrm_q = (float*)(work + p.nrm_q);
+  hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(nq, 4)), dim3(256), 0, s, query, centre, Zq, nrm_q, nq, D, p.Dp);
+  return PairRows{Zq, nrm_q, Zr, nrm_r};
 }
 
 }  // namespace ffd

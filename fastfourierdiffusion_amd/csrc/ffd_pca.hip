@@ -345,7 +345,7 @@ static size_t pca_mat(int D) { return nn_up((size_t)D * D * 8, 16); }
 static size_t pca_vec(int D) { return nn_up((size_t)D * 8, 16); }
 
 struct CovPlan {
-  int nslab, spr, nruns, nmean;
+  int nslab, spr, nruns;
   size_t mean_part, part, bytes;
 };
 static CovPlan cov_plan(int n, int D) {
@@ -353,12 +353,11 @@ static CovPlan cov_plan(int n, int D) {
   p.nslab = cdiv(n, PCA_SLAB);
   p.spr = cdiv(p.nslab, PCA_MAX_RUNS);
   p.nruns = cdiv(p.nslab, p.spr);
-  p.nmean = cdiv(n, NN_SLAB);
-  size_t o = 0;
-  p.mean_part = o, o += nn_up((size_t)p.nmean * D * 8, 16);
+  Carver c;
+  p.mean_part = c.take(nn_colpart_bytes(n, D));
   // (PCA_MAX_RUNS parts for every n, so that the need never falls as n grows)
-  p.part = o, o += (size_t)PCA_MAX_RUNS * pca_mat(D);
-  p.bytes = o;
+  p.part = c.take((size_t)PCA_MAX_RUNS * pca_mat(D));
+  p.bytes = c.total;
   return p;
 }
 
@@ -373,17 +372,17 @@ struct EigPlan {
 };
 static EigPlan eig_plan(int D) {
   EigPlan p;
-  size_t o = 0;
-  p.a0 = o, o += pca_mat(D);
-  p.a1 = o, o += pca_mat(D);
-  p.vt = o, o += pca_mat(D);
-  p.alpha = o, o += pca_vec(D);
-  p.beta = o, o += pca_vec(D);
-  p.ndiag = o, o += pca_vec(D);
-  p.partner = o, o += pca_vec(D);
-  p.rank = o, o += pca_vec(D);
-  p.stat = o, o += 16;
-  p.bytes = o;
+  Carver c;
+  p.a0 = c.take(pca_mat(D));
+  p.a1 = c.take(pca_mat(D));
+  p.vt = c.take(pca_mat(D));
+  p.alpha = c.take(pca_vec(D));
+  p.beta = c.take(pca_vec(D));
+  p.ndiag = c.take(pca_vec(D));
+  p.partner = c.take(pca_vec(D));
+  p.rank = c.take(pca_vec(D));
+  p.stat = c.take(16);
+  p.bytes = c.total;
   return p;
 }
 // The sweeps on `a` (its upper triangle), w and optionally v out; info = {sweeps done, off / |A|_F at the end, 1 if that
@@ -438,23 +437,15 @@ struct FrechetPlan {
 };
 static FrechetPlan frechet_plan(int D) {
   FrechetPlan p;
-  size_t o = 0;
-  p.eig = o, o += eig_plan(D).bytes;
-  p.w = o, o += pca_vec(D);
-  p.v = o, o += pca_mat(D);
-  p.root = o, o += pca_mat(D);
-  p.t1 = o, o += pca_mat(D);
-  p.t2 = o, o += pca_mat(D);
-  p.bytes = o;
+  Carver c;
+  p.eig = c.take(eig_plan(D).bytes);
+  p.w = c.take(pca_vec(D));
+  p.v = c.take(pca_mat(D));
+  p.root = c.take(pca_mat(D));
+  p.t1 = c.take(pca_mat(D));
+  p.t2 = c.take(pca_mat(D));
+  p.bytes = c.total;
   return p;
-}
-
-static bool pca_any_overlap(const void* const* ptr, const size_t* bytes, int count, int n_out) {
-  // the first n_out regions are written: none of them may meet any other region (a NULL optional region meets none)
-  for (int o = 0; o < n_out; ++o)
-    for (int i = o + 1; i < count; ++i)
-      if (ptr[o] && ptr[i] && nn_overlap(ptr[o], bytes[o], ptr[i], bytes[i])) return true;
-  return false;
 }
 
 }  // namespace ffd
@@ -473,17 +464,13 @@ int ffd_cov(const float* x, int n, int D, double* mean_out, double* cov_out, voi
   if (!x || !mean_out || !cov_out || !work || n < 2 || !pca_d_ok(D)) return FFD_ERR_INVALID;
   if (n > PCA_MAX_ROWS || !pca_d_supported(D)) return FFD_ERR_UNSUPPORTED;
   const CovPlan p = cov_plan(n, D);
-  if (((uintptr_t)work & 15) || work_bytes < p.bytes) return FFD_ERR_INVALID;
-  const void* ptr[4] = {mean_out, cov_out, work, x};
-  const size_t bytes[4] = {(size_t)D * 8, (size_t)D * D * 8, work_bytes, (size_t)n * D * 4};
-  if (pca_any_overlap(ptr, bytes, 4, 3)) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, p.bytes)) return FFD_ERR_INVALID;
+  const size_t vb = (size_t)D * 8, mb = (size_t)D * D * 8;
+  if (regions_clash({{mean_out, vb}, {cov_out, mb}, {work, work_bytes}}, {{x, (size_t)n * D * 4}})) return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)work;
-  double* mean_part = (double*)(w + p.mean_part);
   double* part = (double*)(w + p.part);
-  hipLaunchKernelGGL(k_nn_colpart, dim3(cdiv(D, 64), p.nmean), dim3(256), 0, s, x, n, D, mean_part);
-  hipLaunchKernelGGL(k_nn_colmean<double>, dim3(cdiv(D, 256)), dim3(256), 0, s, (const double*)mean_part, p.nmean, n, D,
-                     mean_out);
+  nn_launch_colmean(x, n, D, (double*)(w + p.mean_part), mean_out, s);
   const int nt = cdiv(D, 64);
   hipLaunchKernelGGL(k_pca_cov, dim3(nt, nt, p.nruns), dim3(256), 0, s, x, (const double*)mean_out, n, D, p.nslab, p.spr,
                      part);
@@ -500,10 +487,9 @@ int ffd_sym_eig(const double* a, int D, int max_sweeps, double* w_out, double* v
                 size_t work_bytes, void* stream) {
   if (!a || !w_out || !info3_host || !work || !pca_d_ok(D) || max_sweeps < 0) return FFD_ERR_INVALID;
   if (!pca_d_supported(D)) return FFD_ERR_UNSUPPORTED;
-  if (((uintptr_t)work & 15) || work_bytes < eig_plan(D).bytes) return FFD_ERR_INVALID;
-  const void* ptr[4] = {w_out, v_out, work, a};
-  const size_t bytes[4] = {(size_t)D * 8, (size_t)D * D * 8, work_bytes, (size_t)D * D * 8};
-  if (pca_any_overlap(ptr, bytes, 4, 3)) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, eig_plan(D).bytes)) return FFD_ERR_INVALID;
+  const size_t vb = (size_t)D * 8, mb = (size_t)D * D * 8;
+  if (regions_clash({{w_out, vb}, {v_out, mb}, {work, work_bytes}}, {{a, mb}})) return FFD_ERR_INVALID;
   return eig_run(a, D, max_sweeps ? max_sweeps : PCA_DEFAULT_SWEEPS, w_out, v_out, (char*)work, (hipStream_t)stream,
                  info3_host);
 }
@@ -516,10 +502,9 @@ size_t ffd_sym_root_work_bytes(int D) {
 int ffd_sym_root(const double* w, const double* v, int D, double* root_out, void* work, size_t work_bytes, void* stream) {
   if (!w || !v || !root_out || !work || !pca_d_ok(D)) return FFD_ERR_INVALID;
   if (!pca_d_supported(D)) return FFD_ERR_UNSUPPORTED;
-  if (((uintptr_t)work & 15) || work_bytes < 2 * pca_mat(D)) return FFD_ERR_INVALID;
-  const void* ptr[4] = {root_out, work, w, v};
-  const size_t bytes[4] = {(size_t)D * D * 8, work_bytes, (size_t)D * 8, (size_t)D * D * 8};
-  if (pca_any_overlap(ptr, bytes, 4, 2)) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, 2 * pca_mat(D))) return FFD_ERR_INVALID;
+  const size_t vb = (size_t)D * 8, mb = (size_t)D * D * 8;
+  if (regions_clash({{root_out, mb}, {work, work_bytes}}, {{w, vb}, {v, mb}})) return FFD_ERR_INVALID;
   char* wk = (char*)work;
   root_run(w, v, D, root_out, (double*)wk, (double*)(wk + pca_mat(D)), (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
@@ -536,11 +521,10 @@ int ffd_frechet(const double* mean_x, const double* cov_x, const double* mean_y,
     return FFD_ERR_INVALID;
   if (!pca_d_supported(D)) return FFD_ERR_UNSUPPORTED;
   const FrechetPlan p = frechet_plan(D);
-  if (((uintptr_t)work & 15) || work_bytes < p.bytes) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, p.bytes)) return FFD_ERR_INVALID;
   const size_t vb = (size_t)D * 8, mb = (size_t)D * D * 8;
-  const void* ptr[7] = {out5, work, mean_x, cov_x, mean_y, cov_y, root_y};
-  const size_t bytes[7] = {40, work_bytes, vb, mb, vb, mb, mb};
-  if (pca_any_overlap(ptr, bytes, 7, 2)) return FFD_ERR_INVALID;
+  if (regions_clash({{out5, 40}, {work, work_bytes}}, {{mean_x, vb}, {cov_x, mb}, {mean_y, vb}, {cov_y, mb}, {root_y, mb}}))
+    return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   char* wk = (char*)work;
   double* lam = (double*)(wk + p.w);
@@ -583,10 +567,9 @@ int ffd_pca_variances(const double* cov, const double* v, int D, int k, double* 
   if (!cov || !v || !out || !work || !pca_d_ok(D) || k < 1) return FFD_ERR_INVALID;
   if (!pca_d_supported(D)) return FFD_ERR_UNSUPPORTED;
   if (k > D) return FFD_ERR_INVALID;
-  if (((uintptr_t)work & 15) || work_bytes < nn_up((size_t)D * k * 8, 16)) return FFD_ERR_INVALID;
-  const void* ptr[4] = {out, work, cov, v};
-  const size_t bytes[4] = {(size_t)k * 8, work_bytes, (size_t)D * D * 8, (size_t)D * D * 8};
-  if (pca_any_overlap(ptr, bytes, 4, 2)) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, nn_up((size_t)D * k * 8, 16))) return FFD_ERR_INVALID;
+  const size_t mb = (size_t)D * D * 8;
+  if (regions_clash({{out, (size_t)k * 8}, {work, work_bytes}}, {{cov, mb}, {v, mb}})) return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   double* T = (double*)work;
   pca_gemm(cov, D, 1, v + (D - 1), D, -1, D, k, D, T, k, s);  // B(d, j) = v[d][D - 1 - j]
@@ -599,9 +582,8 @@ int ffd_pca_transform(const float* x, int n, int D, const double* mean, const do
   if (!x || !mean || !v || !scores_out || n < 1 || !pca_d_ok(D) || k < 1) return FFD_ERR_INVALID;
   if (n > PCA_MAX_ROWS || !pca_d_supported(D)) return FFD_ERR_UNSUPPORTED;
   if (k > D) return FFD_ERR_INVALID;
-  const void* ptr[4] = {scores_out, x, mean, v};
-  const size_t bytes[4] = {(size_t)n * k * 8, (size_t)n * D * 4, (size_t)D * 8, (size_t)D * D * 8};
-  if (pca_any_overlap(ptr, bytes, 4, 1)) return FFD_ERR_INVALID;
+  if (regions_clash({{scores_out, (size_t)n * k * 8}}, {{x, (size_t)n * D * 4}, {mean, (size_t)D * 8}, {v, (size_t)D * D * 8}}))
+    return FFD_ERR_INVALID;
   hipLaunchKernelGGL(k_pca_gemm<true>, dim3(cdiv(n, 64), cdiv(k, 64)), dim3(256), 0, (hipStream_t)stream, (const void*)x,
                      (long)D, 1L, mean, v + (D - 1), (long)D, -1L, n, k, D, scores_out, (long)k);
   return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;

@@ -227,8 +227,6 @@ __global__ __launch_bounds__(256) void k_sk_diameter2(const double* __restrict__
 }
 
 // ---- host: checks, workspaces --------------------------------------------------------------------------------------
-static bool sk_shape_ok(int na, int nb, int D) { return na >= 1 && nb >= 1 && D >= 1; }
-static bool sk_shape_supported(int na, int nb, int D) { return na <= NN_MAX_ROWS && nb <= NN_MAX_ROWS && D <= NN_MAX_D; }
 // eps finite and > 0, and log2(e) / eps a normal fp32 number (the exponent's factor, rounded once)
 static bool sk_eps_ok(double eps) {
   if (!std::isfinite(eps) || !(eps > 0.0)) return false;
@@ -244,18 +242,12 @@ struct SkPassPlan {
 static SkPassPlan sk_pass_plan(int na, int nb) {
   SkPassPlan p;
   p.nruns = cdiv(cdiv(nb, NN_J), SK_RUN);
-  size_t o = 0;
-  p.hf = o, o += nn_up((size_t)nb * 4, 16);
-  p.part_m = o, o += nn_up((size_t)p.nruns * na * 4, 16);
-  p.part_s = o, o += nn_up((size_t)p.nruns * na * 8, 16);
-  p.bytes = o;
+  Carver c;
+  p.hf = c.take((size_t)nb * 4);
+  p.part_m = c.take((size_t)p.nruns * na * 4);
+  p.part_s = c.take((size_t)p.nruns * na * 8);
+  p.bytes = c.total;
   return p;
-}
-static size_t sk_spill_bytes(int Dp) {
-  if (Dp <= NN_K_CHUNK) return 0;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sk_softmin), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)NN_SPILL_BYTES);
-  return NN_SPILL_BYTES;
 }
 // out = softmin_eps(a | b, h), damped with `old` where given: centred rows and norms in, `scratch` of sk_pass_plan bytes
 static void sk_pass(const float* Za, const float* nrm_a, int na, const float* Zb, const float* nrm_b, int nb, int Dp,
@@ -266,52 +258,46 @@ static void sk_pass(const float* Za, const float* nrm_a, int na, const float* Zb
   double* part_s = (double*)(scratch + p.part_s);
   const double cd = 1.4426950408889634 / eps;
   hipLaunchKernelGGL(k_sk_potential, dim3(cdiv(nb, 256)), dim3(256), 0, s, h, nb, hf);
-  hipLaunchKernelGGL(k_sk_softmin, dim3(cdiv(na, NN_I), p.nruns), dim3(256), sk_spill_bytes(Dp), s, Za, nrm_a, na, Zb, nrm_b,
-                     nb, Dp, hf, (float)cd, (double)(float)cd, cdiv(nb, NN_J), part_m, part_s);
+  hipLaunchKernelGGL(k_sk_softmin, dim3(cdiv(na, NN_I), p.nruns), dim3(256), nn_spill_bytes(k_sk_softmin, Dp), s, Za, nrm_a,
+                     na, Zb, nrm_b, nb, Dp, hf, (float)cd, (double)(float)cd, cdiv(nb, NN_J), part_m, part_s);
   hipLaunchKernelGGL(k_sk_finish, dim3(cdiv(na, 256)), dim3(256), 0, s, part_m, part_s, p.nruns, na, nb, eps,
                      (double)(float)cd, old, out);
 }
 
+// One softmin call's workspace: the centred pair and a pass scratch
 struct SkSoftminPlan {
-  int Dp;
-  size_t zb, za, nrm_b, nrm_a, pass, bytes;
+  PairPlan pair;
+  size_t pass, bytes;
 };
 static SkSoftminPlan sk_softmin_plan(int na, int nb, int D) {
   SkSoftminPlan p;
-  p.Dp = (int)nn_up(D, 16);
-  size_t o = 0;
-  p.zb = o, o += (size_t)nb * p.Dp * 4;
-  p.za = o, o += (size_t)na * p.Dp * 4;
-  p.nrm_b = o, o += nn_up((size_t)nb * 4, 16);
-  p.nrm_a = o, o += nn_up((size_t)na * 4, 16);
-  p.pass = o, o += sk_pass_plan(na, nb).bytes;
-  p.bytes = o;
+  Carver c;
+  p.pair = nn_pair_plan(c, na, nb, D);
+  p.pass = c.take(sk_pass_plan(na, nb).bytes);
+  p.bytes = c.total;
   return p;
 }
 
-// The loop's workspace: both centred sets, two generations of the four potentials (generation 0 starts as zeros: a pass
-// reads one generation and writes the other), one pass scratch sized for the largest of the four problems
+// The loop's workspace: both centred sets (x on the pair's reference side, y on its query side), two generations of the
+// four potentials (generation 0 starts as zeros: a pass reads one generation and writes the other), one pass scratch
+// sized for the largest of the four problems
 struct SkLoopPlan {
-  int Dp;
-  size_t zx, zy, nrm_x, nrm_y, f[2], g[2], p[2], q[2], pass, bytes;
+  PairPlan pair;
+  size_t f[2], g[2], p[2], q[2], pass, bytes;
 };
 static SkLoopPlan sk_loop_plan(int n, int m, int D) {
   SkLoopPlan p;
-  p.Dp = (int)nn_up(D, 16);
-  size_t o = 0;
-  p.zx = o, o += (size_t)n * p.Dp * 4;
-  p.zy = o, o += (size_t)m * p.Dp * 4;
-  p.nrm_x = o, o += nn_up((size_t)n * 4, 16);
-  p.nrm_y = o, o += nn_up((size_t)m * 4, 16);
+  Carver c;
+  p.pair = nn_pair_plan(c, m, n, D);
   for (int k = 0; k < 2; ++k) {
-    p.f[k] = o, o += nn_up((size_t)n * 8, 16);
-    p.g[k] = o, o += nn_up((size_t)m * 8, 16);
-    p.p[k] = o, o += nn_up((size_t)n * 8, 16);
-    p.q[k] = o, o += nn_up((size_t)m * 8, 16);
+    p.f[k] = c.take((size_t)n * 8);
+    p.g[k] = c.take((size_t)m * 8);
+    p.p[k] = c.take((size_t)n * 8);
+    p.q[k] = c.take((size_t)m * 8);
   }
   const int big = std::max(n, m);
-  p.pass = o, o += sk_pass_plan(big, big).bytes;
-  p.bytes = o;
+  p.pass = c.take(sk_pass_plan(big, big).bytes);
+  p.bytes = c.total;
   return p;
 }
 
@@ -323,85 +309,63 @@ using namespace ffd;
 extern "C" {
 
 size_t ffd_sinkhorn_softmin_work_bytes(int nq, int nr, int D) {
-  if (!sk_shape_ok(nq, nr, D) || !sk_shape_supported(nq, nr, D)) return 0;
+  if (!nn_shape_ok(nq, nr, D) || !nn_shape_supported(nq, nr, D)) return 0;
   return sk_softmin_plan(nq, nr, D).bytes;
 }
 
 int ffd_sinkhorn_softmin(const float* query, int nq, const float* ref, int nr, int D, const float* centre, const double* h,
                          double eps, const double* old, double* out, void* work, size_t work_bytes, void* stream) {
-  if (!query || !ref || !centre || !h || !out || !work || !sk_shape_ok(nq, nr, D)) return FFD_ERR_INVALID;
+  if (!query || !ref || !centre || !h || !out || !work || !nn_shape_ok(nq, nr, D)) return FFD_ERR_INVALID;
   if (!sk_eps_ok(eps)) return FFD_ERR_INVALID;
-  if (!sk_shape_supported(nq, nr, D)) return FFD_ERR_UNSUPPORTED;
+  if (!nn_shape_supported(nq, nr, D)) return FFD_ERR_UNSUPPORTED;
   const SkSoftminPlan p = sk_softmin_plan(nq, nr, D);
-  if (((uintptr_t)work & 15) || work_bytes < p.bytes) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, p.bytes)) return FFD_ERR_INVALID;
   const size_t qb = (size_t)nq * D * 4, rb = (size_t)nr * D * 4, cb = (size_t)D * 4, hb = (size_t)nr * 8, ob = (size_t)nq * 8;
-  const void* in[5] = {query, ref, centre, h, old};
-  const size_t inb[5] = {qb, rb, cb, hb, ob};
-  for (int i = 0; i < 5; ++i)
-    if (in[i] && (nn_overlap(out, ob, in[i], inb[i]) || nn_overlap(work, work_bytes, in[i], inb[i]))) return FFD_ERR_INVALID;
-  if (nn_overlap(work, work_bytes, out, ob)) return FFD_ERR_INVALID;
+  if (regions_clash({{out, ob}, {work, work_bytes}}, {{query, qb}, {ref, rb}, {centre, cb}, {h, hb}, {old, ob}}))
+    return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)work;
-  float* Zb = (float*)(w + p.zb);
-  float* nrm_b = (float*)(w + p.nrm_b);
-  const float* Za = Zb;
-  const float* nrm_a = nrm_b;
-  hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(nr, 4)), dim3(256), 0, s, ref, centre, Zb, nrm_b, nr, D, p.Dp);
-  if (!(query == ref && nq == nr)) {
-    float* Zq = (float*)(w + p.za);
-    float* nrm_q = (float*)(w + p.nrm_a);
-    hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(nq, 4)), dim3(256), 0, s, query, centre, Zq, nrm_q, nq, D, p.Dp);
-    Za = Zq, nrm_a = nrm_q;
-  }
-  sk_pass(Za, nrm_a, nq, Zb, nrm_b, nr, p.Dp, h, eps, old, out, w + p.pass, s);
+  const PairRows z = nn_centre_pair(query, nq, ref, nr, D, centre, p.pair, w, s);
+  sk_pass(z.Zq, z.nrm_q, nq, z.Zr, z.nrm_r, nr, p.pair.Dp, h, eps, old, out, w + p.pass, s);
   return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
 }
 
 size_t ffd_sinkhorn_work_bytes(int n, int m, int D) {
-  if (!sk_shape_ok(n, m, D) || !sk_shape_supported(n, m, D)) return 0;
+  if (!nn_shape_ok(n, m, D) || !nn_shape_supported(n, m, D)) return 0;
   return sk_loop_plan(n, m, D).bytes;
 }
 
 int ffd_sinkhorn(const float* x, int n, const float* y, int m, int D, const float* centre, const double* eps_schedule,
                  int n_eps, const double* q_in, double* f_out, double* g_out, double* p_out, double* q_out, double* out3,
                  void* work, size_t work_bytes, void* stream) {
-  if (!x || !y || !centre || !eps_schedule || !f_out || !g_out || !p_out || !q_out || !out3 || !work || !sk_shape_ok(n, m, D))
+  if (!x || !y || !centre || !eps_schedule || !f_out || !g_out || !p_out || !q_out || !out3 || !work || !nn_shape_ok(n, m, D))
     return FFD_ERR_INVALID;
   if (n_eps < 1) return FFD_ERR_INVALID;
   for (int e = 0; e < n_eps; ++e)
     if (!sk_eps_ok(eps_schedule[e])) return FFD_ERR_INVALID;
-  if (!sk_shape_supported(n, m, D)) return FFD_ERR_UNSUPPORTED;
+  if (!nn_shape_supported(n, m, D)) return FFD_ERR_UNSUPPORTED;
   const SkLoopPlan pl = sk_loop_plan(n, m, D);
-  if (((uintptr_t)work & 15) || work_bytes < pl.bytes) return FFD_ERR_INVALID;
+  if (!work_ok(work, work_bytes, pl.bytes)) return FFD_ERR_INVALID;
   const size_t xb = (size_t)n * D * 4, yb = (size_t)m * D * 4, cb = (size_t)D * 4, nb8 = (size_t)n * 8, mb8 = (size_t)m * 8;
-  const void* in[4] = {x, y, centre, q_in};
-  const size_t inb[4] = {xb, yb, cb, mb8};
-  void* outs[5] = {f_out, g_out, p_out, q_out, out3};
-  const size_t outb[5] = {nb8, mb8, nb8, mb8, 24};
-  for (int o = 0; o < 5; ++o) {
-    for (int i = 0; i < 4; ++i)
-      if (in[i] && nn_overlap(outs[o], outb[o], in[i], inb[i])) return FFD_ERR_INVALID;
-    for (int o2 = o + 1; o2 < 5; ++o2)
-      if (nn_overlap(outs[o], outb[o], outs[o2], outb[o2])) return FFD_ERR_INVALID;
-    if (nn_overlap(work, work_bytes, outs[o], outb[o])) return FFD_ERR_INVALID;
-  }
-  for (int i = 0; i < 4; ++i)
-    if (in[i] && nn_overlap(work, work_bytes, in[i], inb[i])) return FFD_ERR_INVALID;
+  if (regions_clash({{f_out, nb8}, {g_out, mb8}, {p_out, nb8}, {q_out, mb8}, {out3, 24}, {work, work_bytes}},
+                    {{x, xb}, {y, yb}, {centre, cb}, {q_in, mb8}}))
+    return FFD_ERR_INVALID;
 
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)work;
-  float* Zx = (float*)(w + pl.zx);
-  float* Zy = (float*)(w + pl.zy);
-  float* nx = (float*)(w + pl.nrm_x);
-  float* ny = (float*)(w + pl.nrm_y);
+  float* Zx = (float*)(w + pl.pair.zr);
+  float* Zy = (float*)(w + pl.pair.zq);
+  float* nx = (float*)(w + pl.pair.nrm_r);
+  float* ny = (float*)(w + pl.pair.nrm_q);
+  const int Dp = pl.pair.Dp;
   double *f[2], *g[2], *p[2], *q[2];
   for (int k = 0; k < 2; ++k) {
     f[k] = (double*)(w + pl.f[k]), g[k] = (double*)(w + pl.g[k]);
     p[k] = (double*)(w + pl.p[k]), q[k] = (double*)(w + pl.q[k]);
   }
   char* scratch = w + pl.pass;
-  hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(n, 4)), dim3(256), 0, s, x, centre, Zx, nx, n, D, pl.Dp);
-  hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(m, 4)), dim3(256), 0, s, y, centre, Zy, ny, m, D, pl.Dp);
+  hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(n, 4)), dim3(256), 0, s, x, centre, Zx, nx, n, D, Dp);
+  hipLaunchKernelGGL(k_nn_centre, dim3(cdiv(m, 4)), dim3(256), 0, s, y, centre, Zy, ny, m, D, Dp);
   // generation 0: all potentials 0 (the bytes of +0.0)
   if (hipMemsetAsync(w + pl.f[0], 0, pl.f[1] - pl.f[0], s) != hipSuccess) return FFD_ERR_HIP;
   int cur = 0;
@@ -409,40 +373,38 @@ int ffd_sinkhorn(const float* x, int n, const float* y, int m, int D, const floa
     const double eps = eps_schedule[e];
     const int nxt = cur ^ 1;
     const bool damp = e > 0;  // the first pass is the softmin itself
-    sk_pass(Zx, nx, n, Zy, ny, m, pl.Dp, g[cur], eps, damp ? f[cur] : nullptr, f[nxt], scratch, s);
-    sk_pass(Zy, ny, m, Zx, nx, n, pl.Dp, f[cur], eps, damp ? g[cur] : nullptr, g[nxt], scratch, s);
-    sk_pass(Zx, nx, n, Zx, nx, n, pl.Dp, p[cur], eps, damp ? p[cur] : nullptr, p[nxt], scratch, s);
-    if (!q_in) sk_pass(Zy, ny, m, Zy, ny, m, pl.Dp, q[cur], eps, damp ? q[cur] : nullptr, q[nxt], scratch, s);
+    sk_pass(Zx, nx, n, Zy, ny, m, Dp, g[cur], eps, damp ? f[cur] : nullptr, f[nxt], scratch, s);
+    sk_pass(Zy, ny, m, Zx, nx, n, Dp, f[cur], eps, damp ? g[cur] : nullptr, g[nxt], scratch, s);
+    sk_pass(Zx, nx, n, Zx, nx, n, Dp, p[cur], eps, damp ? p[cur] : nullptr, p[nxt], scratch, s);
+    if (!q_in) sk_pass(Zy, ny, m, Zy, ny, m, Dp, q[cur], eps, damp ? q[cur] : nullptr, q[nxt], scratch, s);
     if (e == n_eps - 1) hipLaunchKernelGGL(k_sk_change, dim3(1), dim3(256), 0, s, f[cur], f[nxt], n, g[cur], g[nxt], m, out3 + 2);
     cur = nxt;
   }
   // the extrapolation: one undamped pass at the final eps, from the last damped values
   const double eps = eps_schedule[n_eps - 1];
-  sk_pass(Zx, nx, n, Zy, ny, m, pl.Dp, g[cur], eps, nullptr, f_out, scratch, s);
-  sk_pass(Zy, ny, m, Zx, nx, n, pl.Dp, f[cur], eps, nullptr, g_out, scratch, s);
-  sk_pass(Zx, nx, n, Zx, nx, n, pl.Dp, p[cur], eps, nullptr, p_out, scratch, s);
+  sk_pass(Zx, nx, n, Zy, ny, m, Dp, g[cur], eps, nullptr, f_out, scratch, s);
+  sk_pass(Zy, ny, m, Zx, nx, n, Dp, f[cur], eps, nullptr, g_out, scratch, s);
+  sk_pass(Zx, nx, n, Zx, nx, n, Dp, p[cur], eps, nullptr, p_out, scratch, s);
   if (q_in) {
     if (hipMemcpyAsync(q_out, q_in, mb8, hipMemcpyDeviceToDevice, s) != hipSuccess) return FFD_ERR_HIP;
   } else {
-    sk_pass(Zy, ny, m, Zy, ny, m, pl.Dp, q[cur], eps, nullptr, q_out, scratch, s);
+    sk_pass(Zy, ny, m, Zy, ny, m, Dp, q[cur], eps, nullptr, q_out, scratch, s);
   }
   hipLaunchKernelGGL(k_sk_scores, dim3(1), dim3(256), 0, s, f_out, p_out, n, g_out, q_out, m, out3);
   return hipGetLastError() == hipSuccess ? FFD_OK : FFD_ERR_HIP;
 }
 
 size_t ffd_sinkhorn_diameter2_work_bytes(int n, int D) {
-  if (n < 1 || D < 1 || n > NN_MAX_ROWS || D > NN_MAX_D) return 0;
+  if (!nn_shape_ok(n, n, D) || !nn_shape_supported(n, n, D)) return 0;
   return nn_up((size_t)n * 8, 16);
 }
 
 int ffd_sinkhorn_diameter2(const float* y, int n, int D, const float* centre, double* diameter2_out, void* work,
                            size_t work_bytes, void* stream) {
-  if (!y || !centre || !diameter2_out || !work || n < 1 || D < 1) return FFD_ERR_INVALID;
-  if (n > NN_MAX_ROWS || D > NN_MAX_D) return FFD_ERR_UNSUPPORTED;
-  if (((uintptr_t)work & 15) || work_bytes < ffd_sinkhorn_diameter2_work_bytes(n, D)) return FFD_ERR_INVALID;
-  const size_t yb = (size_t)n * D * 4, cb = (size_t)D * 4;
-  if (nn_overlap(diameter2_out, 8, y, yb) || nn_overlap(diameter2_out, 8, centre, cb) || nn_overlap(work, work_bytes, y, yb) ||
-      nn_overlap(work, work_bytes, centre, cb) || nn_overlap(work, work_bytes, diameter2_out, 8))
+  if (!y || !centre || !diameter2_out || !work || !nn_shape_ok(n, n, D)) return FFD_ERR_INVALID;
+  if (!nn_shape_supported(n, n, D)) return FFD_ERR_UNSUPPORTED;
+  if (!work_ok(work, work_bytes, ffd_sinkhorn_diameter2_work_bytes(n, D))) return FFD_ERR_INVALID;
+  if (regions_clash({{diameter2_out, 8}, {work, work_bytes}}, {{y, (size_t)n * D * 4}, {centre, (size_t)D * 4}}))
     return FFD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_sk_radius2, dim3(cdiv(n, 4)), dim3(256), 0, s, y, centre, n, D, (double*)work);

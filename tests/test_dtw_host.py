@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import dtw_restatement as DR
+from host_entry_checks import HostBuffers, checks_work, one_host_prologue, refuses_every_alias
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED = -1, -2
@@ -65,6 +66,7 @@ def test_symbols_header_and_argtypes(lib):
         for source in ("ffd_neighbours.hip", "ffd_mmd.hip", "ffd_dtw.hip"):
             text = open(os.path.join(csrc, source)).read()
             assert piece not in text and '#include "ffd_pairtile.h"' in text, (piece, source)
+    one_host_prologue(csrc)  # ... and one statement of the host prologue
     assert "hipLaunchKernelGGL(k_nn_merge" in open(os.path.join(csrc, "ffd_dtw.hip")).read()
 
 
@@ -95,28 +97,10 @@ def test_work_bytes_monotone_multiple_of_16_and_zero_for_refused(lib):
         assert lib.ffd_dtw_work_bytes(*(shape[key] for key in order)) == 0, bad
 
 
-class _HostBuffers:
-    """Distinct 16-byte aligned host regions standing where device buffers would: every refusal comes before any device
-    work, so none of them is ever read by a kernel.  ``untouched`` checks that nothing changed."""
-
-    def __init__(self, **sizes):
-        self.store = {}
-        for name, size in sizes.items():
-            raw = np.full(size + 16, 0xA5, np.uint8)
-            self.store[name] = (raw, (-raw.ctypes.data) % 16)
-
-    def __getattr__(self, name):
-        raw, off = self.store[name]
-        return raw.ctypes.data + off
-
-    def untouched(self):
-        return all((raw == 0xA5).all() for raw, _ in self.store.values())
-
-
 def test_argument_errors_before_device_work(lib):
     nq, nr, L, Cn, w, k = 6, 9, 7, 2, 2, 3
     need = lib.ffd_dtw_work_bytes(nq, nr, L, Cn, w, k, 0)
-    b = _HostBuffers(q=nq * L * Cn * 4, r=nr * L * Cn * 4, d=nr * k * 4, i=nr * k * 4, work=need, pd=nr * 4, xx=nq * 4, xy=nq * 4,
+    b = HostBuffers(q=nq * L * Cn * 4, r=nr * L * Cn * 4, d=nr * k * 4, i=nr * k * 4, work=need, pd=nr * 4, xx=nq * 4, xy=nq * 4,
                      e2=nq * 4, yx=nr * 4, yy=nr * 4, out6=48)
 
     def search(q=b.q, nq=nq, r=b.r, nr=nr, L=L, Cn=Cn, w=w, k=k, excl=0, d=b.d, i=b.i, work=b.work, nbytes=need):
@@ -128,6 +112,10 @@ def test_argument_errors_before_device_work(lib):
                dict(work=b.work + 4), dict(work=b.q), dict(work=b.r), dict(d=b.q), dict(d=b.r), dict(i=b.q), dict(i=b.r),
                dict(i=b.d), dict(d=b.work), dict(i=b.work)):
         assert search(**kw) == INVALID, kw
+    # every written region on every other region, two sets and one; the workspace misaligned, a byte short, exactly the need
+    assert refuses_every_alias(search, dict(d=b.d, i=b.i, work=b.work), dict(q=b.q, r=b.r)) == 12
+    assert refuses_every_alias(partial(search, q=b.r, nq=nr), dict(d=b.d, i=b.i, work=b.work), dict(r=b.r)) == 9
+    checks_work(search, b.work, need)
     big = (1 << 24) + 1
     for kw in (dict(nq=big), dict(nr=big), dict(L=4097, Cn=1), dict(Cn=65), dict(L=2048, Cn=33), dict(L=200, w=65),
                dict(L=4096, Cn=1, w=100)):
@@ -139,6 +127,7 @@ def test_argument_errors_before_device_work(lib):
     for kw in (dict(a=None), dict(bb=None), dict(d=None), dict(n=0), dict(n=-2), dict(L=0), dict(Cn=0), dict(w=-1), dict(d=b.q),
                dict(d=b.r)):
         assert pairs(**kw) == INVALID, kw
+    assert refuses_every_alias(pairs, dict(d=b.pd), dict(a=b.q, bb=b.r)) == 2
     for kw in (dict(n=big), dict(L=4097, Cn=1), dict(Cn=65), dict(L=2048, Cn=33), dict(L=200, w=65)):
         assert pairs(**kw) == UNSUPPORTED, kw
 
@@ -148,6 +137,7 @@ def test_argument_errors_before_device_work(lib):
     for kw in (dict(xx=None), dict(xy=None), dict(yx=None), dict(yy=None), dict(e2=None), dict(out=None), dict(n=1), dict(m=1),
                dict(n=0), dict(m=-1), dict(out=b.xx), dict(out=b.xy), dict(out=b.yx), dict(out=b.yy), dict(out=b.e2)):
         assert scores(**kw) == INVALID, kw
+    assert refuses_every_alias(scores, dict(out=b.out6), dict(xx=b.xx, xy=b.xy, yx=b.yx, yy=b.yy, e2=b.e2)) == 5
     assert scores(n=big) == UNSUPPORTED and scores(m=big) == UNSUPPORTED
     assert b.untouched()
 

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import kernel_mmd_restatement as KR
+from host_entry_checks import HostBuffers, checks_work, one_host_prologue, refuses_every_alias
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED = -1, -2
@@ -68,6 +69,7 @@ def test_symbols_header_and_argtypes(lib):
         for source in ("ffd_neighbours.hip", "ffd_mmd.hip"):
             text = open(os.path.join(csrc, source)).read()
             assert piece not in text and '#include "ffd_pairtile.h"' in text, (piece, source)
+    one_host_prologue(csrc)  # ... and one statement of the host prologue
 
 
 def test_work_bytes_monotone_and_zero_for_refused(lib):
@@ -112,30 +114,12 @@ def test_work_bytes_monotone_and_zero_for_refused(lib):
         assert lib.ffd_mmd_permute_work_bytes(*bad) == 0, bad
 
 
-class _HostBuffers:
-    """Distinct 16-byte aligned host regions standing where device buffers would: every refusal comes before any device
-    work, so none of them is ever read by a kernel.  ``untouched`` checks that nothing changed."""
-
-    def __init__(self, **sizes):
-        self.store = {}
-        for name, size in sizes.items():
-            raw = np.full(size + 16, 0xA5, np.uint8)
-            self.store[name] = (raw, (-raw.ctypes.data) % 16)
-
-    def __getattr__(self, name):
-        raw, off = self.store[name]
-        return raw.ctypes.data + off
-
-    def untouched(self):
-        return all((raw == 0xA5).all() for raw, _ in self.store.values())
-
-
 def test_argument_errors_before_device_work(lib):
     na, nb, D, ng, P = 6, 9, 5, 3, 7
     need = lib.ffd_mmd_rowsums_work_bytes(na, nb, D, ng)
     gneed, pneed = lib.ffd_mmd_gram_work_bytes(na, nb, D), lib.ffd_mmd_permute_work_bytes(na, nb, P)
     cneed, bneed = lib.ffd_mmd_centre_work_bytes(nb, D), lib.ffd_mmd_bandwidth_work_bytes(nb, D)
-    b = _HostBuffers(a=na * D * 4, b=nb * D * 4, centre=D * 4, out=ng * max(na, nb) * 8, work=max(need, pneed, cneed, bneed),
+    b = HostBuffers(a=na * D * 4, b=nb * D * 4, centre=D * 4, out=ng * max(na, nb) * 8, work=max(need, pneed, cneed, bneed),
                      gwork=gneed, xx=ng * na * 8, xy=ng * na * 8, yy=ng * nb * 8, mmd2=(2 * ng + 2) * 8, wit=na * 8,
                      assign=P * (na + nb), t=P * 8, sig=8)
     gam = (C.c_double * 8)(0.5, 1.0, 2.0, 0.1, 0.2, 0.3, 0.4, 0.5)
@@ -152,6 +136,10 @@ def test_argument_errors_before_device_work(lib):
     for bad in (-1.0, float("nan"), float("inf"), 1e39):
         bad_g = (C.c_double * 3)(0.5, bad, 1.0)
         assert rows(g=C.addressof(bad_g)) == INVALID, bad
+    # every written region on every other region; the workspace misaligned, a byte short, and exactly the need
+    assert refuses_every_alias(rows, dict(out=b.out, work=b.work), dict(a=b.a, bb=b.b, centre=b.centre)) == 8
+    assert refuses_every_alias(partial(rows, a=b.b, na=nb), dict(out=b.out, work=b.work), dict(bb=b.b, centre=b.centre)) == 6
+    checks_work(rows, b.work, need)
     big = (1 << 24) + 1
     assert rows(na=big) == UNSUPPORTED and rows(nb=big) == UNSUPPORTED and rows(D=(1 << 16) + 1) == UNSUPPORTED
 
@@ -166,6 +154,10 @@ def test_argument_errors_before_device_work(lib):
     assert centre(x=None) == INVALID and band(y=None) == INVALID and band(n=1) == INVALID
     assert centre(out=b.b) == INVALID and band(out=b.b) == INVALID
     assert centre(nbytes=cneed - 1) == INVALID and band(nbytes=bneed - 1) == INVALID
+    assert refuses_every_alias(centre, dict(out=b.centre, work=b.work), dict(x=b.b)) == 4
+    assert refuses_every_alias(band, dict(out=b.sig, work=b.work), dict(y=b.b)) == 4
+    checks_work(centre, b.work, cneed)
+    checks_work(band, b.work, bneed)
     assert centre(n=big) == UNSUPPORTED and band(n=big) == UNSUPPORTED and band(D=(1 << 16) + 1) == UNSUPPORTED
 
     def scores(xx=b.xx, xy=b.xy, yy=b.yy, n=na, m=nb, ng=ng, mmd2=b.mmd2, wit=b.wit):
@@ -174,6 +166,7 @@ def test_argument_errors_before_device_work(lib):
     for kw in (dict(xx=None), dict(xy=None), dict(yy=None), dict(mmd2=None), dict(wit=None), dict(n=1), dict(m=1), dict(n=0),
                dict(ng=0), dict(ng=9), dict(mmd2=b.xx), dict(mmd2=b.yy), dict(wit=b.xy), dict(wit=b.mmd2)):
         assert scores(**kw) == INVALID, kw
+    assert refuses_every_alias(scores, dict(mmd2=b.mmd2, wit=b.wit), dict(xx=b.xx, xy=b.xy, yy=b.yy)) == 8
     assert scores(n=big) == UNSUPPORTED
 
     def gram(x=b.a, n=na, y=b.b, m=nb, D=D, centre=b.centre, g=gptr, ng=ng, work=b.gwork, nbytes=gneed):
@@ -182,6 +175,8 @@ def test_argument_errors_before_device_work(lib):
     for kw in (dict(x=None), dict(y=None), dict(centre=None), dict(g=None), dict(work=None), dict(n=1), dict(m=1), dict(D=0),
                dict(ng=0), dict(ng=9), dict(nbytes=gneed - 1), dict(work=b.gwork + 4), dict(work=b.a), dict(work=b.b)):
         assert gram(**kw) == INVALID, kw
+    assert refuses_every_alias(gram, dict(work=b.gwork), dict(x=b.a, y=b.b, centre=b.centre)) == 3
+    checks_work(gram, b.gwork, gneed)
     assert gram(n=16383) == UNSUPPORTED and gram(D=(1 << 16) + 1) == UNSUPPORTED
 
     def permute(k=b.gwork, n=na, m=nb, assign=b.assign, P=P, t=b.t, work=b.work, nbytes=pneed):
@@ -191,6 +186,9 @@ def test_argument_errors_before_device_work(lib):
                dict(nbytes=pneed - 1), dict(work=b.work + 4), dict(k=b.gwork + 4), dict(work=b.gwork), dict(work=b.assign),
                dict(t=b.gwork), dict(t=b.assign), dict(t=b.work)):
         assert permute(**kw) == INVALID, kw
+    assert refuses_every_alias(permute, dict(t=b.t, work=b.work), dict(k=b.gwork, assign=b.assign)) == 6
+    assert permute(assign=b.gwork) == INVALID and permute(k=b.assign) == INVALID  # two read regions, refused all the same
+    checks_work(permute, b.work, pneed)
     assert permute(P=4097) == UNSUPPORTED and permute(n=16383) == UNSUPPORTED
     assert b.untouched()
 

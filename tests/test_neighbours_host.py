@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import neighbours_restatement as NR
+from host_entry_checks import HostBuffers, checks_work, refuses_every_alias
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED = -1, -2
@@ -87,31 +88,11 @@ def test_work_bytes_monotone_and_nonzero(lib):
         assert lib.ffd_nn_work_bytes(*bad, 0) == 0, bad
 
 
-class _HostBuffers:
-    """Distinct 16-byte aligned host regions standing where device buffers would: every refusal comes before any device
-    work, so none of them is ever read by a kernel.  ``untouched`` checks that no output changed."""
-
-    def __init__(self, nq, nr, D, k, nbytes):
-        self.store = {}
-        for name, size in (("q", nq * D * 4), ("r", nr * D * 4), ("rad", nr * 4), ("dist2", nq * k * 8),
-                           ("index", nq * k * 4), ("count", nq * 4), ("work", nbytes), ("out8", 64),
-                           ("f64", max(nq, nr) * k * 8), ("i32", max(nq, nr) * 4)):
-            raw = np.full(size + 16, 0xA5, np.uint8)
-            off = (-raw.ctypes.data) % 16
-            self.store[name] = (raw, off, size)
-
-    def __getattr__(self, name):
-        raw, off, _ = self.store[name]
-        return raw.ctypes.data + off
-
-    def untouched(self):
-        return all((raw == 0xA5).all() for raw, _, _ in self.store.values())
-
-
 def test_argument_errors_before_device_work(lib):
     nq, nr, D, k = 6, 9, 5, 3
     need = lib.ffd_nn_work_bytes(nq, nr, D, k, 0)
-    b = _HostBuffers(nq, nr, D, k, need)
+    b = HostBuffers(q=nq * D * 4, r=nr * D * 4, rad=nr * 4, dist2=nq * k * 8, index=nq * k * 4, count=nq * 4, work=need,
+                    out8=64, f64=max(nq, nr) * k * 8, i32=max(nq, nr) * 4)
 
     def search(query=b.q, nq=nq, ref=b.r, nr=nr, D=D, k=k, excl=0, dist2=b.dist2, index=b.index, work=b.work, nbytes=need):
         return lib.ffd_nn_search(query, nq, ref, nr, D, k, excl, dist2, index, work, nbytes, None)
@@ -133,6 +114,13 @@ def test_argument_errors_before_device_work(lib):
                dict(rad=b.work)):
         assert ball(**kw) == INVALID, kw
     assert ball(nbytes=lib.ffd_nn_work_bytes(nq, nr, D, 1, 0) - 1) == INVALID
+    # every written region on every other region; the workspace misaligned, a byte short, and exactly the need
+    assert refuses_every_alias(search, dict(dist2=b.dist2, index=b.index, work=b.work), dict(query=b.q, ref=b.r)) == 12
+    assert refuses_every_alias(partial(search, query=b.r, nq=nr), dict(dist2=b.dist2, index=b.index, work=b.work),
+                               dict(ref=b.r)) == 9  # the same-set form
+    assert refuses_every_alias(ball, dict(count=b.count, work=b.work), dict(query=b.q, ref=b.r, rad=b.rad)) == 8
+    checks_work(search, b.work, need)
+    checks_work(ball, b.work, lib.ffd_nn_work_bytes(nq, nr, D, 1, 0))
     big = (1 << 24) + 1
     assert search(nr=big) == UNSUPPORTED and search(nq=big) == UNSUPPORTED and search(D=(1 << 16) + 1) == UNSUPPORTED
     assert ball(nr=big) == UNSUPPORTED and ball(D=(1 << 16) + 1) == UNSUPPORTED
@@ -142,6 +130,7 @@ def test_argument_errors_before_device_work(lib):
 
     for kw in (dict(d=None), dict(out=None), dict(n=0), dict(k=0), dict(k=33), dict(col=-1), dict(col=k), dict(out=b.f64)):
         assert radius(**kw) == INVALID, kw
+    assert refuses_every_alias(radius, dict(out=b.rad), dict(d=b.f64)) == 1
 
     def scores(s=b.f64, xd=b.dist2, xi=b.index, yd=b.work, cx=b.count, cy=b.i32, n=nr, m=nq, k=k, out=b.out8):
         return lib.ffd_nn_scores(s, xd, xi, yd, cx, cy, n, m, k, out, None)
@@ -149,6 +138,8 @@ def test_argument_errors_before_device_work(lib):
     for kw in (dict(s=None), dict(xd=None), dict(xi=None), dict(yd=None), dict(cx=None), dict(cy=None), dict(out=None),
                dict(n=0), dict(m=0), dict(k=0), dict(k=33), dict(out=b.f64), dict(out=b.count)):
         assert scores(**kw) == INVALID, kw
+    assert refuses_every_alias(scores, dict(out=b.out8), dict(s=b.f64, xd=b.dist2, xi=b.index, yd=b.work, cx=b.count,
+                                                              cy=b.i32)) == 6
     assert b.untouched()
 
 

@@ -14,6 +14,7 @@ import torch
 
 import kernel_mmd_restatement as KR
 import pca_restatement as PR
+from host_entry_checks import HostBuffers, checks_work, refuses_every_alias
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED = -1, -2
@@ -107,30 +108,12 @@ def test_work_bytes_monotone_and_zero_for_refused(lib):
         assert lib.ffd_pca_variances_work_bytes(*bad) == 0, bad
 
 
-class _HostBuffers:
-    """Distinct 16-byte aligned host regions standing where device buffers would: every refusal comes before any device
-    work, so none of them is ever read by a kernel.  ``untouched`` checks that nothing changed."""
-
-    def __init__(self, **sizes):
-        self.store = {}
-        for name, size in sizes.items():
-            raw = np.full(size + 16, 0xA5, np.uint8)
-            self.store[name] = (raw, (-raw.ctypes.data) % 16)
-
-    def __getattr__(self, name):
-        raw, off = self.store[name]
-        return raw.ctypes.data + off
-
-    def untouched(self):
-        return all((raw == 0xA5).all() for raw, _ in self.store.values())
-
-
 def test_argument_errors_before_device_work(lib):
     n, D, k = 7, 5, 3
     cneed, eneed, rneed = lib.ffd_cov_work_bytes(n, D), lib.ffd_sym_eig_work_bytes(D), lib.ffd_sym_root_work_bytes(D)
     fneed, vneed = lib.ffd_frechet_work_bytes(D), lib.ffd_pca_variances_work_bytes(D, k)
     vec, mat = D * 8, D * D * 8
-    b = _HostBuffers(x=n * D * 4, mean=vec, cov=mat, work=max(cneed, eneed, rneed, fneed, vneed), a=mat, w=vec, v=mat, info=24,
+    b = HostBuffers(x=n * D * 4, mean=vec, cov=mat, work=max(cneed, eneed, rneed, fneed, vneed), a=mat, w=vec, v=mat, info=24,
                      root=mat, mx=vec, cx=mat, my=vec, cy=mat, out5=40, out=k * 8, scores=n * k * 8)
 
     def cov(x=b.x, n=n, D=D, mean=b.mean, cov=b.cov, work=b.work, nbytes=cneed):
@@ -140,6 +123,10 @@ def test_argument_errors_before_device_work(lib):
                dict(D=-1), dict(nbytes=0), dict(nbytes=cneed - 1), dict(work=b.work + 8), dict(work=b.x), dict(work=b.mean),
                dict(work=b.cov), dict(mean=b.x), dict(cov=b.x), dict(cov=b.mean), dict(mean=b.cov)):
         assert cov(**kw) == INVALID, kw
+    # every written region on every other region, optional ones given and left out; the workspace misaligned, a byte
+    # short, and exactly the need
+    assert refuses_every_alias(cov, dict(mean=b.mean, cov=b.cov, work=b.work), dict(x=b.x)) == 9
+    checks_work(cov, b.work, cneed)
     assert cov(n=BIG_N) == UNSUPPORTED and cov(D=BIG_D) == UNSUPPORTED
 
     def eig(a=b.a, D=D, max_sweeps=30, w=b.w, v=b.v, info=b.info, work=b.work, nbytes=eneed):
@@ -152,6 +139,10 @@ def test_argument_errors_before_device_work(lib):
     for kw in (dict(a=None), dict(w=None), dict(info=None), dict(work=None), dict(D=0), dict(max_sweeps=-1),
                dict(nbytes=eneed - 1), dict(work=b.work + 8), dict(work=b.a), dict(work=b.w), dict(w=b.a)):
         assert eig(v=None, **kw) == INVALID, kw  # ... and without vectors
+    assert refuses_every_alias(eig, dict(w=b.w, v=b.v, work=b.work), dict(a=b.a)) == 9
+    assert refuses_every_alias(partial(eig, v=None), dict(w=b.w, v=None, work=b.work), dict(a=b.a)) == 4
+    checks_work(eig, b.work, eneed)
+    checks_work(partial(eig, v=None), b.work, eneed)
     assert eig(D=BIG_D) == UNSUPPORTED and eig(D=BIG_D, v=None) == UNSUPPORTED
 
     def root(w=b.w, v=b.v, D=D, out=b.root, work=b.work, nbytes=rneed):
@@ -161,6 +152,8 @@ def test_argument_errors_before_device_work(lib):
                dict(nbytes=rneed - 1), dict(work=b.work + 8), dict(work=b.w), dict(work=b.v), dict(work=b.root), dict(out=b.w),
                dict(out=b.v)):
         assert root(**kw) == INVALID, kw
+    assert refuses_every_alias(root, dict(out=b.root, work=b.work), dict(w=b.w, v=b.v)) == 6
+    checks_work(root, b.work, rneed)
     assert root(D=BIG_D) == UNSUPPORTED
 
     def fd(mx=b.mx, cx=b.cx, my=b.my, cy=b.cy, root=b.root, D=D, max_sweeps=30, out5=b.out5, info=b.info, work=b.work,
@@ -174,6 +167,11 @@ def test_argument_errors_before_device_work(lib):
         assert fd(**kw) == INVALID, kw
         assert fd(root=None, **kw) == INVALID, kw  # ... and without a supplied root
     assert fd(work=b.root) == INVALID and fd(out5=b.root) == INVALID
+    fd_in = dict(mx=b.mx, cx=b.cx, my=b.my, cy=b.cy)
+    assert refuses_every_alias(fd, dict(out5=b.out5, work=b.work), dict(fd_in, root=b.root)) == 12
+    assert refuses_every_alias(partial(fd, root=None), dict(out5=b.out5, work=b.work), dict(fd_in, root=None)) == 10
+    checks_work(fd, b.work, fneed)
+    checks_work(partial(fd, root=None), b.work, fneed)
     assert fd(D=BIG_D) == UNSUPPORTED and fd(D=BIG_D, root=None) == UNSUPPORTED
 
     def pcv(cov=b.cov, v=b.v, D=D, k=k, out=b.out, work=b.work, nbytes=vneed):
@@ -183,6 +181,8 @@ def test_argument_errors_before_device_work(lib):
                dict(nbytes=0), dict(nbytes=vneed - 1), dict(work=b.work + 8), dict(work=b.cov), dict(work=b.v), dict(work=b.out),
                dict(out=b.cov), dict(out=b.v)):
         assert pcv(**kw) == INVALID, kw
+    assert refuses_every_alias(pcv, dict(out=b.out, work=b.work), dict(cov=b.cov, v=b.v)) == 6
+    checks_work(pcv, b.work, vneed)
     assert pcv(D=BIG_D) == UNSUPPORTED
 
     def tr(x=b.x, n=n, D=D, mean=b.mean, v=b.v, k=k, scores=b.scores):
@@ -191,6 +191,7 @@ def test_argument_errors_before_device_work(lib):
     for kw in (dict(x=None), dict(mean=None), dict(v=None), dict(scores=None), dict(n=0), dict(n=-1), dict(D=0), dict(k=0),
                dict(k=D + 1), dict(scores=b.x), dict(scores=b.mean), dict(scores=b.v)):
         assert tr(**kw) == INVALID, kw
+    assert refuses_every_alias(tr, dict(scores=b.scores), dict(x=b.x, mean=b.mean, v=b.v)) == 3
     assert tr(n=BIG_N) == UNSUPPORTED and tr(D=BIG_D) == UNSUPPORTED
     assert b.untouched()
 

@@ -14,6 +14,7 @@ import torch
 
 import kernel_mmd_restatement as KR
 import sinkhorn_restatement as SR
+from host_entry_checks import HostBuffers, checks_work, one_host_prologue, refuses_every_alias
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED = -1, -2
@@ -64,6 +65,7 @@ def test_symbols_header_and_argtypes(lib):
     assert '#include "ffd_pairtile.h"' in text
     for piece in ("void nn_tile(", "float nn_d2(", "void k_nn_colpart(", "void k_nn_colmean(", "void k_nn_centre("):
         assert piece not in text, piece
+    one_host_prologue(csrc)  # ... and none of the host prologue
     assert "atomic" not in text.replace("No atomics", "")
     run = re.search(r"constexpr int SK_RUN = (\d+);", text)
     assert run and int(run.group(1)) * 256 == SR.RUN_COLUMNS  # a constant of the source: what the tests' run edges assume
@@ -98,24 +100,6 @@ def test_work_bytes_monotone_and_zero_for_refused(lib):
         assert lib.ffd_sinkhorn_diameter2_work_bytes(*bad) == 0, bad
 
 
-class _HostBuffers:
-    """Distinct 16-byte aligned host regions standing where device buffers would: every refusal comes before any device
-    work, so none of them is ever read by a kernel.  ``untouched`` checks that nothing changed."""
-
-    def __init__(self, **sizes):
-        self.store = {}
-        for name, size in sizes.items():
-            raw = np.full(size + 16, 0xA5, np.uint8)
-            self.store[name] = (raw, (-raw.ctypes.data) % 16)
-
-    def __getattr__(self, name):
-        raw, off = self.store[name]
-        return raw.ctypes.data + off
-
-    def untouched(self):
-        return all((raw == 0xA5).all() for raw, _ in self.store.values())
-
-
 BAD_EPS = (0.0, -1.0, float("nan"), float("inf"), -float("inf"), 1e-60, 1e60)
 
 
@@ -123,7 +107,7 @@ def test_argument_errors_before_device_work(lib):
     n, m, D = 6, 9, 5
     sneed, lneed = lib.ffd_sinkhorn_softmin_work_bytes(n, m, D), lib.ffd_sinkhorn_work_bytes(n, m, D)
     dneed = lib.ffd_sinkhorn_diameter2_work_bytes(m, D)
-    b = _HostBuffers(x=n * D * 4, y=m * D * 4, centre=D * 4, h=m * 8, old=n * 8, out=n * 8, work=max(sneed, lneed, dneed),
+    b = HostBuffers(x=n * D * 4, y=m * D * 4, centre=D * 4, h=m * 8, old=n * 8, out=n * 8, work=max(sneed, lneed, dneed),
                      qin=m * 8, f=n * 8, g=m * 8, p=n * 8, q=m * 8, out3=24, diam=8)
 
     def soft(query=b.x, nq=n, ref=b.y, nr=m, D=D, centre=b.centre, h=b.h, eps=0.5, old=b.old, out=b.out, work=b.work,
@@ -137,6 +121,15 @@ def test_argument_errors_before_device_work(lib):
         assert soft(**kw) == INVALID, kw
     for bad in BAD_EPS:
         assert soft(eps=bad) == INVALID and soft(eps=bad, old=None) == INVALID, bad
+    # every written region on every other region, with and without `old`, two sets and one; the workspace misaligned, a
+    # byte short, and exactly the need
+    soft_in = dict(query=b.x, ref=b.y, centre=b.centre, h=b.h)
+    assert refuses_every_alias(soft, dict(out=b.out, work=b.work), dict(soft_in, old=b.old)) == 12
+    assert refuses_every_alias(partial(soft, old=None), dict(out=b.out, work=b.work), dict(soft_in, old=None)) == 10
+    assert refuses_every_alias(partial(soft, query=b.y, nq=m, old=None, out=b.g), dict(out=b.g, work=b.work),
+                               dict(ref=b.y, centre=b.centre, h=b.h)) == 8
+    checks_work(soft, b.work, sneed)
+    checks_work(partial(soft, old=None), b.work, sneed)
     big = (1 << 24) + 1
     assert soft(nq=big) == UNSUPPORTED and soft(nr=big) == UNSUPPORTED and soft(D=(1 << 16) + 1) == UNSUPPORTED
 
@@ -154,6 +147,11 @@ def test_argument_errors_before_device_work(lib):
         assert loop(**kw) == INVALID, kw
     for kw in (dict(x=None), dict(n_eps=0), dict(nbytes=lneed - 1), dict(f=b.g), dict(work=b.y)):  # ... and without q_in
         assert loop(qin=None, **kw) == INVALID, kw
+    loop_out = dict(f=b.f, g=b.g, p=b.p, q=b.q, out3=b.out3, work=b.work)
+    assert refuses_every_alias(loop, loop_out, dict(x=b.x, y=b.y, centre=b.centre, qin=b.qin)) == 6 * 9
+    assert refuses_every_alias(partial(loop, qin=None), loop_out, dict(x=b.x, y=b.y, centre=b.centre, qin=None)) == 6 * 8
+    checks_work(loop, b.work, lneed)
+    checks_work(partial(loop, qin=None), b.work, lneed)
     for bad in BAD_EPS:
         for at in range(3):
             sched = (C.c_double * 3)(4.0, 1.0, 0.25)
@@ -168,6 +166,8 @@ def test_argument_errors_before_device_work(lib):
                dict(nbytes=dneed - 1), dict(work=b.work + 8), dict(work=b.y), dict(work=b.centre), dict(out=b.y),
                dict(out=b.centre), dict(out=b.work)):
         assert diam(**kw) == INVALID, kw
+    assert refuses_every_alias(diam, dict(out=b.diam, work=b.work), dict(y=b.y, centre=b.centre)) == 6
+    checks_work(diam, b.work, dneed)
     assert diam(n=big) == UNSUPPORTED and diam(D=(1 << 16) + 1) == UNSUPPORTED
     assert b.untouched()
 
